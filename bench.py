@@ -24,6 +24,12 @@ concatenates).
 Prints ONE JSON line (rank 0).  value = all ranks' env-steps / max-over-ranks seconds, with
 inputs resident in HBM (the only per-step host traffic is 4 + 8 B/env of actions and candidate
 reset states in and 29 B/env of observations, rewards and flags out, inside the timed region).
+ms_per_step = the max-over-ranks time of the --steps timed steps / --steps.
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the last step returned for all
+environments (observations, rewards, terminated, truncated) as DIR/<name>.npy.  Actions, initial
+states and RNG states are seeded, so two builds run with the same arguments can be compared
+output for output.
 """
 
 import argparse
@@ -73,7 +79,14 @@ def parse_args(argv=None):
                          "their step as one hipGraph")
     ap.add_argument("--plumbing-test", action="store_true",
                     help="no GPU work: exercises only the multi-rank plumbing (CPU tests)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned (observations, rewards, terminated, "
+                         "truncated of all environments) as DIR/<name>.npy: the inputs are seeded, so two builds run "
+                         "with the same arguments can be compared output for output")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------
@@ -263,6 +276,19 @@ class Ranks:
             return sum(int(t.numel()) for t in self._gathered)
         self.dist.gather(mine, None, dst=0)
         return 0
+
+    def step_outputs(self, obs, rewards, terminated, truncated):
+        """What the one vector environment returned from the last step, on rank 0: this rank's own arrays, or with N
+        ranks every rank's block of that step (gather_step) decoded in rank order.  None on the other ranks."""
+        if self.dist is None:
+            return {"observations": obs, "rewards": rewards, "terminated": terminated, "truncated": truncated}
+        if self.rank != 0:
+            return None
+        blocks = np.concatenate([t.numpy() for t in self._gathered])
+        n = len(blocks)
+        return {"observations": np.ascontiguousarray(blocks[:, 0:16]).view(np.float32).reshape(n, 4),
+                "rewards": np.ascontiguousarray(blocks[:, 16:24]).view(np.float64).reshape(n),
+                "terminated": blocks[:, 24] != 0, "truncated": blocks[:, 25] != 0}
 
     def close(self):
         if self.dist is not None:
@@ -519,6 +545,31 @@ def shard_plan(rank, envs_per_gpu, frame):
     return {"first_env": rank * envs_per_gpu, "first_state_index": rank * envs_per_gpu * frame * frame}
 
 
+DUMP_BYTES = 63_000_000  # --dump-outputs: at most 64 MB in all, .npy headers included
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: every array as <directory>/<name>.npy, float64 where the step returned float64 and float32
+    otherwise (flags as 0 / 1).  Should they hold more than DUMP_BYTES, the same fixed sample of environments (seed 0)
+    is kept of every array and its indices are written as rows.npy."""
+    out = {name: np.asarray(a, dtype=np.float64 if np.asarray(a).dtype == np.float64 else np.float32)
+           for name, a in arrays.items()}
+    n = len(out["rewards"])
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_BYTES:
+        keep = max(1, n * DUMP_BYTES // (total + 8 * n))  # (8 B per kept environment for rows.npy)
+        rows = np.sort(np.random.Generator(np.random.PCG64DXSM(0)).choice(n, keep, replace=False))
+        out = {name: a[rows] for name, a in out.items()}
+        out["rows"] = rows.astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    stale = os.path.join(directory, "rows.npy")
+    if "rows" not in out and os.path.exists(stale):  # (from an earlier, sampled dump into the same directory)
+        os.remove(stale)
+    for name, a in out.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+    return sorted(out)
+
+
 # ---------------------------------------------------------------------------------------------
 # CPU baseline (rank 0, N = 1 only)
 # ---------------------------------------------------------------------------------------------
@@ -708,13 +759,18 @@ def main(argv=None):
         gathered_bytes[0] = ranks.gather_step(*arrays)
         gather_seconds[0] += time.perf_counter() - t_gather
 
+    last_step = [None]  # obs, rewards, terminated, truncated of the step that ran last (--dump-outputs)
+
     def one_step():
         actions = action_rng.integers(0, 13, n_here)
-        if env is None:  # (plumbing: a fake block goes through the same gather)
+        if env is None:  # (plumbing: a fake block goes through the same gather; its rewards are the rank)
             time.sleep(0.002)
-            gather_step(np.zeros((n_here, 4), np.float32), np.zeros(n_here), np.zeros(n_here, bool), np.ones(n_here, bool))
+            last_step[0] = (np.zeros((n_here, 4), np.float32), np.full(n_here, float(ranks.rank)), np.zeros(n_here, bool),
+                            np.ones(n_here, bool))
+            gather_step(*last_step[0])
             return 0
         obs, rewards, term, trunc, _ = env.step(actions)
+        last_step[0] = (obs, rewards, term, trunc)
         # one process per GPU: the ranks' blocks are gathered on rank 0, as the one vector environment they stand for would
         # return them (the sharded product object concatenates inside step() itself)
         gather_step(obs, rewards, term, trunc)
@@ -749,6 +805,8 @@ def main(argv=None):
     # every rank's own time per step (its steps + its share of the gather), in rank order: a straggling rank -- a GPU behind
     # another PCIe root, a rank on the wrong NUMA node -- is visible in the line, not only in the maximum
     per_rank_ms = [1000.0 * seconds / max(args.steps, 1) for seconds in ranks.gather(elapsed_local)]
+    if args.dump_outputs is not None and ranks.rank == 0:
+        dump_outputs(args.dump_outputs, ranks.step_outputs(*last_step[0]))
 
     timing = None
     if env is not None and not args.no_kernel_timing:

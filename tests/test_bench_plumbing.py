@@ -236,3 +236,49 @@ def test_committed_profile_is_matched_by_kernel_and_configuration():
     low, high = valu["attainable_for_this_mix"]["no_overlap"], valu["attainable_for_this_mix"]["fast_fp_hidden"]
     assert 0.2 < low < high < 0.5 and abs(sum(valu["attainable_for_this_mix"]["shares"].values()) - 1) < 1e-9
     assert valu["frac_of_attainable"][0] < valu["frac_of_attainable"][1]
+
+
+def test_dump_outputs_of_two_ranks(tmp_path):
+    """--dump-outputs: rank 0 writes what the one vector environment returned from the last timed step -- every
+    rank's block of it, decoded in rank order (the plumbing's fake block carries its rank as the reward) -- as
+    float32 / float64 .npy files; --steps below 1 is refused."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
+    out = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--plumbing-test", "--envs-per-gpu", "16", "--steps",
+                          "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "dump")],
+                         cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1 and json.loads(lines[0])["steps"] == 3
+    import numpy as np
+
+    got = {name[:-4]: np.load(tmp_path / "dump" / name) for name in os.listdir(tmp_path / "dump")}
+    assert sorted(got) == ["observations", "rewards", "terminated", "truncated"]
+    assert got["observations"].shape == (32, 4) and got["observations"].dtype == np.float32
+    assert got["rewards"].dtype == np.float64 and list(got["rewards"]) == [0.0] * 16 + [1.0] * 16
+    assert got["terminated"].dtype == np.float32 and not got["terminated"].any()
+    assert got["truncated"].dtype == np.float32 and got["truncated"].shape == (32,) and got["truncated"].all()
+    out = subprocess.run([sys.executable, "bench.py", "--plumbing-test", "--steps", "0"], cwd=ROOT, env=env,
+                         capture_output=True, text=True, timeout=600)
+    assert out.returncode != 0 and "--steps must be at least 1" in out.stderr
+
+
+def test_dump_outputs_keeps_a_fixed_sample_of_large_outputs(tmp_path, monkeypatch):
+    sys.path.insert(0, ROOT)
+    import numpy as np
+
+    import bench
+
+    n = 1000
+    arrays = {"observations": np.arange(4 * n, dtype=np.float32).reshape(n, 4), "rewards": np.arange(n, dtype=np.float64),
+              "terminated": np.zeros(n, bool), "truncated": np.arange(n) % 3 == 0}
+    assert bench.dump_outputs(str(tmp_path / "all"), arrays) == ["observations", "rewards", "terminated", "truncated"]
+    assert np.array_equal(np.load(tmp_path / "all" / "rewards.npy"), arrays["rewards"])
+    monkeypatch.setattr(bench, "DUMP_BYTES", 10_000)
+    for run in ("a", "b"):
+        assert "rows" in bench.dump_outputs(str(tmp_path / run), arrays)
+        assert sum(os.path.getsize(tmp_path / run / f) for f in os.listdir(tmp_path / run)) <= 10_000 + 5 * 128
+    rows = np.load(tmp_path / "a" / "rows.npy")
+    assert rows.dtype == np.float64 and 0 < len(rows) < n and np.all(np.diff(rows) > 0)
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "rows.npy"))  # the same sample every time
+    assert np.array_equal(np.load(tmp_path / "a" / "rewards.npy"), rows)
+    assert np.array_equal(np.load(tmp_path / "a" / "truncated.npy"), (rows % 3 == 0).astype(np.float32))

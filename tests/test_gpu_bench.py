@@ -51,3 +51,21 @@ def test_bench_of_the_sharded_product_object():
     assert line["n_gpus"] == 1 and line["value"] > 0
     assert "ShardedVectorDiscreteSteps" in line["config"]["sharding"]
     assert line["roofline"]["traffic_from_committed_profile"] is False and line["roofline"]["traffic"] is None
+
+
+def test_bench_dumps_the_same_outputs_on_every_run(tmp_path):
+    """--dump-outputs: the last timed step's observations, rewards and flags of every environment; actions, initial states
+    and RNG states are seeded, so a second run with the same arguments writes the same arrays."""
+    import numpy as np
+
+    got = []
+    for run in ("a", "b"):
+        line = run_bench("--no-cpu-baseline", "--no-pmc", "--dump-outputs", str(tmp_path / run))
+        assert line["steps"] == 4 and line["ms_per_step"] > 0
+        got.append({name: np.load(tmp_path / run / (name + ".npy"))
+                    for name in ("observations", "rewards", "terminated", "truncated")})
+    assert got[0]["observations"].shape == (64, 4) and got[0]["observations"].dtype == np.float32
+    assert got[0]["rewards"].shape == (64,) and got[0]["rewards"].dtype == np.float64
+    assert np.isfinite(got[0]["observations"]).all() and np.abs(got[0]["observations"]).max() > 0
+    for name in got[0]:
+        assert np.array_equal(got[0][name], got[1][name]), name
