@@ -302,6 +302,30 @@ int rf_env_last_step_branch(rf_ctx *ctx, int *branch);
 /* Current states float32[n][2] (tests / checkpoint). */
 int rf_env_get_states(rf_ctx *ctx, float *host_states);
 
+/* ---- the same device-resident step for ContinuousJumps (examples/__init__.py:14-18) -------------------------------
+ * A vector ContinuousJumps: the environment of examples/custom_environments.py:244-339 with num_envs in place of 1 and
+ * the vector DiscreteSteps' TimeLimitEnder | DivergingEnder (:185-190), driven by VectorEnvironment
+ * (environments/vector_environment.py:104-164).  It differs from the DiscreteSteps step in two strategies only:
+ *   ContinuousJumpTransformer(n, 1, limits, stop_threshold)   environments/state_transformer.py:66-118
+ *     a = float32 action; focus' = (a + 1) / 2.0 * (hi - lo) + lo where |focus - focus'| > stop_threshold; no clip
+ *   ObservationRewarder(1) + StoppedRewarder(1, stop_threshold) * OnTargetRewarder((0, 1), on_target_span)
+ *                                                             environments/episode_rewarder.py:210-292, :361-429
+ * Everything else -- enders, observer, scene packing, auto-reset, render, focus measure, rf_env_reset / _step_end /
+ * _step_run / _render_states / _step_end_given / _step_abort / _render / _get_* -- is the DiscreteSteps step's.
+ *   rf_env_configure_jumps  rf_env_configure for this task: cfg as there, except that n_actions / action_set / reward_scale
+ *                           are unused and limit_lo / limit_hi are the range the focus plane jumps in (the state's [5, 10]).
+ *   rf_env_step_jumps, rf_env_step_begin_jumps, rf_env_step_plan_jumps
+ *                           rf_env_step / _begin / _plan with host_actions float32[n]: same schedules, same outputs.
+ * Deliberate difference from the reference: an action that is NaN, infinite or outside [-1, 1] is refused
+ * (RF_ERR_INVALID) before any state changes; the reference would carry it into the focus plane.  The int32 calls on a
+ * context configured by rf_env_configure_jumps, and these on one configured by rf_env_configure, are refused too. */
+int rf_env_configure_jumps(rf_ctx *ctx, const rf_env_config *cfg, float stop_threshold);
+int rf_env_step_jumps(rf_ctx *ctx, const float *host_actions, const float *host_pool, float *host_obs,
+                      double *host_rewards, uint8_t *host_truncated, int *host_n_reset);
+int rf_env_step_begin_jumps(rf_ctx *ctx, const float *host_actions, double *host_rewards, uint8_t *host_truncated,
+                            int *host_n_reset);
+int rf_env_step_plan_jumps(rf_ctx *ctx, const float *host_actions, int *host_n_reset);
+
 #ifdef __cplusplus
 }
 #endif

@@ -61,6 +61,10 @@ SYMBOLS = (
     "rf_env_render",
     "rf_env_get_counters",
     "rf_env_last_step_branch",
+    "rf_env_configure_jumps",
+    "rf_env_step_jumps",
+    "rf_env_step_begin_jumps",
+    "rf_env_step_plan_jumps",
     "rf_render_kernel_name",
     "rf_pixels_rendered",
     "rf_allocations_poisoned",
@@ -154,6 +158,10 @@ def load():
     lib.rf_env_render.argtypes = [vp, i32, i32, vp]
     lib.rf_env_get_counters.argtypes = [vp, vp, vp]
     lib.rf_env_last_step_branch.argtypes = [vp, ctypes.POINTER(i32)]
+    lib.rf_env_configure_jumps.argtypes = [vp, ctypes.POINTER(EnvConfig), ctypes.c_float]
+    lib.rf_env_step_jumps.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.POINTER(i32)]
+    lib.rf_env_step_begin_jumps.argtypes = [vp, vp, vp, vp, ctypes.POINTER(i32)]
+    lib.rf_env_step_plan_jumps.argtypes = [vp, vp, ctypes.POINTER(i32)]
     lib.rf_render_kernel_name.restype = ctypes.c_char_p
     lib.rf_render_kernel_name.argtypes = [vp]
     lib.rf_pixels_rendered.restype = ctypes.c_ulonglong
@@ -353,6 +361,13 @@ class Context:
         self._env_k_ref = ctypes.byref(self._env_k)
         _check(self._lib.rf_env_configure(self._h, ctypes.byref(cfg)))
 
+    def env_configure_jumps(self, cfg, stop_threshold):
+        """rf_env_configure_jumps: the context steps ContinuousJumps (float32 actions, the env_step*_jumps calls)."""
+        self._env_n = cfg.n
+        self._env_k = ctypes.c_int(0)
+        self._env_k_ref = ctypes.byref(self._env_k)
+        _check(self._lib.rf_env_configure_jumps(self._h, ctypes.byref(cfg), float(stop_threshold)))
+
     def env_reset(self, states):
         states = np.ascontiguousarray(states, dtype=np.float32).reshape(self._env_n, 2)
         obs = np.empty((self._env_n, 4), dtype=np.float32)
@@ -373,6 +388,39 @@ class Context:
         if rc != 0:
             _check(rc)
         return obs, rewards, truncated, k.value
+
+    def env_step_jumps(self, actions, pool):
+        """env_step with float32 actions in [-1, 1] (rf_env_step_jumps; anything else is refused by the library)."""
+        n = self._env_n
+        actions = np.ascontiguousarray(actions, dtype=np.float32).reshape(n)
+        pool = np.ascontiguousarray(pool, dtype=np.float32).reshape(n, 2)
+        obs = np.empty((n, 4), dtype=np.float32)
+        rewards = np.empty(n, dtype=np.float64)
+        truncated = np.empty(n, dtype=np.bool_)
+        k = self._env_k
+        rc = self._lib.rf_env_step_jumps(self._h, actions.ctypes.data, pool.ctypes.data, obs.ctypes.data,
+                                         rewards.ctypes.data, truncated.ctypes.data, self._env_k_ref)
+        if rc != 0:
+            _check(rc)
+        return obs, rewards, truncated, k.value
+
+    def env_step_begin_jumps(self, actions):
+        """env_step_begin with float32 actions (rf_env_step_begin_jumps)."""
+        n = self._env_n
+        actions = np.ascontiguousarray(actions, dtype=np.float32).reshape(n)
+        rewards = np.empty(n, dtype=np.float64)
+        truncated = np.empty(n, dtype=np.uint8)
+        k = ctypes.c_int(0)
+        _check(self._lib.rf_env_step_begin_jumps(self._h, _ptr(actions), _ptr(rewards), _ptr(truncated),
+                                                 ctypes.byref(k)))
+        return rewards, truncated.astype(bool), k.value
+
+    def env_step_plan_jumps(self, actions):
+        """env_step_plan with float32 actions (rf_env_step_plan_jumps)."""
+        actions = np.ascontiguousarray(actions, dtype=np.float32).reshape(self._env_n)
+        k = ctypes.c_int(0)
+        _check(self._lib.rf_env_step_plan_jumps(self._h, _ptr(actions), ctypes.byref(k)))
+        return k.value
 
     def env_step_begin(self, actions):
         """First half of a two-phase step: (rewards, truncated, number of environments that ended)."""

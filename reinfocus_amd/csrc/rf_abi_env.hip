@@ -35,20 +35,37 @@ bool fused_step_possible(const rf_ctx *ctx)
     return ctx->env_fused && ctx->env_axis;
 }
 
-} // namespace
-
-extern "C" {
-
-int rf_env_configure(rf_ctx *ctx, const rf_env_config *cfg)
+// The actions of one step, checked on the host before anything is enqueued (a refused step changes no state).  The
+// int32 form (DiscreteSteps-v0) takes indices into the action set; the float32 form (ContinuousJumps) takes values in
+// [-1, 1] -- NaN, infinities and values outside are refused, where the reference's ContinuousJumpTransformer would carry
+// them into the focus plane.  Calling the form of the other task is an error: the 4-byte slots are never reinterpreted.
+int check_actions(const rf_ctx *ctx, const int32_t *actions, const char *fn)
 {
-    RF_REQUIRE(ctx != nullptr && cfg != nullptr, "rf_env_configure: NULL argument");
-    RF_REQUIRE(cfg->n > 0 && cfg->n_actions > 0 && cfg->n_actions <= 32, "rf_env_configure: bad n / n_actions");
+    const rf_env_config &h = ctx->env_host;
+    RF_REQUIRE(ctx->env_cfg.task == rf::kEnvTaskSteps, "%s: the context is configured for ContinuousJumps (%s_jumps)", fn,
+               fn);
+    for (int i = 0; i < h.n; ++i)
+        RF_REQUIRE(actions[i] >= 0 && actions[i] < h.n_actions, "%s: action %d of env %d out of range", fn, actions[i], i);
+    return RF_OK;
+}
+
+int check_actions(const rf_ctx *ctx, const float *actions, const char *fn)
+{
+    RF_REQUIRE(ctx->env_cfg.task == rf::kEnvTaskJumps, "%s: the context is configured for DiscreteSteps (int32 actions)",
+               fn);
+    for (int i = 0; i < ctx->env_host.n; ++i)
+        RF_REQUIRE(actions[i] >= -1.0f && actions[i] <= 1.0f, "%s: action %g of env %d outside [-1, 1]", fn,
+                   (double)actions[i], i); // (false for NaN)
+    return RF_OK;
+}
+
+int env_configure(rf_ctx *ctx, const rf_env_config *cfg, int task, float stop_threshold)
+{
     RF_REQUIRE(cfg->frame_height > 0 && cfg->spp > 0, "rf_env_configure: frame_height, spp must be positive");
     RF_REQUIRE(cfg->gray_mode == RF_GRAY_15BIT || cfg->gray_mode == RF_GRAY_14BIT, "rf_env_configure: gray_mode");
     const uint64_t need = (uint64_t)cfg->n * cfg->frame_height * cfg->frame_height;
     RF_REQUIRE(need <= ctx->n_states, "rf_env_configure: %llu pixels but only %llu RNG states (rf_seed first)",
                (unsigned long long)need, (unsigned long long)ctx->n_states);
-    RF_HIP(hipSetDevice(ctx->device));
     drop_env_graph(ctx);
     RF_HIP(hipStreamSynchronize(ctx->stream));
     if (ctx->env_block) {
@@ -92,6 +109,8 @@ int rf_env_configure(rf_ctx *ctx, const rf_env_config *cfg)
     ctx->d_pool = (float *)(base + o_io + io.o_pool);
 
     rf::EnvConfig &c = ctx->env_cfg;
+    c.task = task;
+    c.stop_threshold = stop_threshold;
     c.n = cfg->n;
     c.n_actions = cfg->n_actions;
     for (int i = 0; i < 32; ++i)
@@ -146,6 +165,29 @@ int rf_env_configure(rf_ctx *ctx, const rf_env_config *cfg)
     return RF_OK;
 }
 
+} // namespace
+
+extern "C" {
+
+int rf_env_configure(rf_ctx *ctx, const rf_env_config *cfg)
+{
+    RF_REQUIRE(ctx != nullptr && cfg != nullptr, "rf_env_configure: NULL argument");
+    RF_REQUIRE(cfg->n > 0 && cfg->n_actions > 0 && cfg->n_actions <= 32, "rf_env_configure: bad n / n_actions");
+    RF_HIP(hipSetDevice(ctx->device));
+    return env_configure(ctx, cfg, rf::kEnvTaskSteps, 0.0f);
+}
+
+int rf_env_configure_jumps(rf_ctx *ctx, const rf_env_config *cfg, float stop_threshold)
+{
+    RF_REQUIRE(ctx != nullptr && cfg != nullptr, "rf_env_configure_jumps: NULL argument");
+    RF_REQUIRE(cfg->n > 0, "rf_env_configure_jumps: bad n");
+    RF_REQUIRE(isfinite(cfg->limit_lo) && isfinite(cfg->limit_hi) && cfg->limit_lo < cfg->limit_hi,
+               "rf_env_configure_jumps: limit_lo < limit_hi must be finite");
+    RF_REQUIRE(isfinite(stop_threshold) && stop_threshold >= 0.0f, "rf_env_configure_jumps: stop_threshold");
+    RF_HIP(hipSetDevice(ctx->device));
+    return env_configure(ctx, cfg, rf::kEnvTaskJumps, stop_threshold);
+}
+
 int rf_env_reset(rf_ctx *ctx, const float *host_states, float *host_obs)
 {
     RF_REQUIRE(ctx != nullptr && host_states != nullptr && host_obs != nullptr, "rf_env_reset: NULL argument");
@@ -191,7 +233,7 @@ bool env_one_sync(const rf_ctx *ctx)
 // render + focus, the glue kernels, the auto-reset render for all n slots (env_reset_kernel marks
 // the unused ones, whose blocks exit at once), the downloads.  Used directly and under stream
 // capture.
-int enqueue_env_step(rf_ctx *ctx, const int32_t *actions, const float *pool, float *obs, double *rewards,
+int enqueue_env_step(rf_ctx *ctx, const void *actions, const float *pool, float *obs, double *rewards,
                      uint8_t *truncated, int *count, uint8_t *host_io = nullptr)
 {
     // host_io: the host side is an image of the device's io block (EnvIo: the pinned staging buffer of the replayed
@@ -260,7 +302,7 @@ int enqueue_env_step(rf_ctx *ctx, const int32_t *actions, const float *pool, flo
 // the ranking of the environments that ended (vector_environment.py:124-135).  Synchronises once:
 // *k, rewards and truncated are final on return; the observations of the environments that did not
 // end are final on the device.
-int env_step_begin(rf_ctx *ctx, const int32_t *host_actions, double *host_rewards, uint8_t *host_truncated, int *k)
+int env_step_begin(rf_ctx *ctx, const void *host_actions, double *host_rewards, uint8_t *host_truncated, int *k)
 {
     const rf_env_config &h = ctx->env_host;
     const int n = h.n, fh = h.frame_height;
@@ -309,24 +351,20 @@ int env_step_end(rf_ctx *ctx, const float *host_pool, int k, float *host_obs)
     return RF_OK;
 }
 
-} // namespace
-
-extern "C" {
-
-int rf_env_step(rf_ctx *ctx, const int32_t *host_actions, const float *host_pool, float *host_obs,
-                double *host_rewards, uint8_t *host_truncated, int *host_n_reset)
+// rf_env_step / rf_env_step_jumps: T = int32_t or float (check_actions)
+template <typename T>
+int env_step(rf_ctx *ctx, const T *host_actions, const float *host_pool, float *host_obs, double *host_rewards,
+             uint8_t *host_truncated, int *host_n_reset, const char *fn)
 {
     RF_REQUIRE(ctx != nullptr && host_actions && host_pool && host_obs && host_rewards && host_truncated,
-               "rf_env_step: NULL argument");
-    RF_REQUIRE(ctx->env_ready, "rf_env_step: rf_env_configure first");
-    RF_REQUIRE(ctx->env_pending < 0, "rf_env_step: a two-phase step is open (rf_env_step_end first)");
-    RF_REQUIRE(!ctx->env_needs_reset, "rf_env_step: a step was aborted (rf_env_reset first)");
-    RF_HIP(hipSetDevice(ctx->device));
+               "%s: NULL argument", fn);
+    RF_REQUIRE(ctx->env_ready, "%s: rf_env_configure first", fn);
+    RF_REQUIRE(ctx->env_pending < 0, "%s: a two-phase step is open (rf_env_step_end first)", fn);
+    RF_REQUIRE(!ctx->env_needs_reset, "%s: a step was aborted (rf_env_reset first)", fn);
+    if (int rc = check_actions(ctx, host_actions, fn))
+        return rc;
     const rf_env_config &h = ctx->env_host;
     const int n = h.n;
-    for (int i = 0; i < n; ++i)
-        RF_REQUIRE(host_actions[i] >= 0 && host_actions[i] < h.n_actions, "rf_env_step: action %d of env %d out of range",
-                   host_actions[i], i);
     int k = 0;
     // vector_environment.py:137-151: the envs that just ended are rendered again.  Small
     // configurations are launch- and sync-bound: their step is enqueued in one go (see
@@ -425,6 +463,75 @@ int rf_env_step(rf_ctx *ctx, const int32_t *host_actions, const float *host_pool
     return RF_OK;
 }
 
+template <typename T>
+int env_step_begin_checked(rf_ctx *ctx, const T *host_actions, double *host_rewards, uint8_t *host_truncated,
+                           int *host_n_reset, const char *fn)
+{
+    RF_REQUIRE(ctx != nullptr && host_actions && host_rewards && host_truncated && host_n_reset, "%s: NULL argument", fn);
+    RF_REQUIRE(ctx->env_ready, "%s: rf_env_configure first", fn);
+    RF_REQUIRE(ctx->env_pending < 0, "%s: the previous step was not finished (rf_env_step_end)", fn);
+    RF_REQUIRE(!ctx->env_needs_reset, "%s: a step was aborted (rf_env_reset first)", fn);
+    if (int rc = check_actions(ctx, host_actions, fn))
+        return rc;
+    drop_env_graph(ctx);
+    int k = 0;
+    int rc = env_step_begin(ctx, host_actions, host_rewards, host_truncated, &k);
+    if (rc != RF_OK)
+        return rc;
+    ctx->env_pending = k;
+    *host_n_reset = k;
+    return RF_OK;
+}
+
+template <typename T>
+int env_step_plan(rf_ctx *ctx, const T *host_actions, int *host_n_reset, const char *fn)
+{
+    RF_REQUIRE(ctx != nullptr && host_actions && host_n_reset, "%s: NULL argument", fn);
+    RF_REQUIRE(ctx->env_ready, "%s: rf_env_configure first", fn);
+    RF_REQUIRE(ctx->env_pending < 0, "%s: the previous step was not finished", fn);
+    RF_REQUIRE(!ctx->env_needs_reset, "%s: a step was aborted (rf_env_reset first)", fn);
+    if (int rc = check_actions(ctx, host_actions, fn))
+        return rc;
+    drop_env_graph(ctx);
+    const rf_env_config &h = ctx->env_host;
+    RF_HIP(hipMemcpyAsync(ctx->d_actions, host_actions, (size_t)h.n * 4, hipMemcpyHostToDevice, ctx->stream));
+    // the kernel below applies the actions and advances the counters: from here until the step is open (a HIP failure
+    // returns early) only a reset makes the environment usable again -- a retried step would apply the actions twice
+    ctx->env_needs_reset = true;
+    hipLaunchKernelGGL(rf::env_reset_kernel, dim3(1), dim3(1024), 0, ctx->stream, ctx->env_cfg, ctx->env,
+                       (const float *)nullptr, rf::kEnvResetRank, (const int *)ctx->d_actions);
+    RF_HIP(hipGetLastError());
+    int k = 0;
+    RF_HIP(hipMemcpyAsync(&k, ctx->env.done_count, 4, hipMemcpyDeviceToHost, ctx->stream));
+    RF_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->env_pending = k;
+    ctx->env_planned = true;
+    ctx->env_needs_reset = false;
+    *host_n_reset = k;
+    return RF_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int rf_env_step(rf_ctx *ctx, const int32_t *host_actions, const float *host_pool, float *host_obs,
+                double *host_rewards, uint8_t *host_truncated, int *host_n_reset)
+{
+    RF_REQUIRE(ctx != nullptr, "rf_env_step: ctx is NULL");
+    RF_HIP(hipSetDevice(ctx->device));
+    return env_step(ctx, host_actions, host_pool, host_obs, host_rewards, host_truncated, host_n_reset, "rf_env_step");
+}
+
+int rf_env_step_jumps(rf_ctx *ctx, const float *host_actions, const float *host_pool, float *host_obs,
+                      double *host_rewards, uint8_t *host_truncated, int *host_n_reset)
+{
+    RF_REQUIRE(ctx != nullptr, "rf_env_step_jumps: ctx is NULL");
+    RF_HIP(hipSetDevice(ctx->device));
+    return env_step(ctx, host_actions, host_pool, host_obs, host_rewards, host_truncated, host_n_reset,
+                    "rf_env_step_jumps");
+}
+
 int rf_env_last_step_branch(rf_ctx *ctx, int *branch)
 {
     RF_REQUIRE(ctx != nullptr && branch != nullptr, "rf_env_last_step_branch: NULL argument");
@@ -435,24 +542,18 @@ int rf_env_last_step_branch(rf_ctx *ctx, int *branch)
 int rf_env_step_begin(rf_ctx *ctx, const int32_t *host_actions, double *host_rewards, uint8_t *host_truncated,
                       int *host_n_reset)
 {
-    RF_REQUIRE(ctx != nullptr && host_actions && host_rewards && host_truncated && host_n_reset,
-               "rf_env_step_begin: NULL argument");
-    RF_REQUIRE(ctx->env_ready, "rf_env_step_begin: rf_env_configure first");
-    RF_REQUIRE(ctx->env_pending < 0, "rf_env_step_begin: the previous step was not finished (rf_env_step_end)");
-    RF_REQUIRE(!ctx->env_needs_reset, "rf_env_step_begin: a step was aborted (rf_env_reset first)");
+    RF_REQUIRE(ctx != nullptr, "rf_env_step_begin: ctx is NULL");
     RF_HIP(hipSetDevice(ctx->device));
-    drop_env_graph(ctx);
-    const rf_env_config &h = ctx->env_host;
-    for (int i = 0; i < h.n; ++i)
-        RF_REQUIRE(host_actions[i] >= 0 && host_actions[i] < h.n_actions,
-                   "rf_env_step_begin: action %d of env %d out of range", host_actions[i], i);
-    int k = 0;
-    int rc = env_step_begin(ctx, host_actions, host_rewards, host_truncated, &k);
-    if (rc != RF_OK)
-        return rc;
-    ctx->env_pending = k;
-    *host_n_reset = k;
-    return RF_OK;
+    return env_step_begin_checked(ctx, host_actions, host_rewards, host_truncated, host_n_reset, "rf_env_step_begin");
+}
+
+int rf_env_step_begin_jumps(rf_ctx *ctx, const float *host_actions, double *host_rewards, uint8_t *host_truncated,
+                            int *host_n_reset)
+{
+    RF_REQUIRE(ctx != nullptr, "rf_env_step_begin_jumps: ctx is NULL");
+    RF_HIP(hipSetDevice(ctx->device));
+    return env_step_begin_checked(ctx, host_actions, host_rewards, host_truncated, host_n_reset,
+                                  "rf_env_step_begin_jumps");
 }
 
 int rf_env_step_end(rf_ctx *ctx, const float *host_pool, float *host_obs)
@@ -477,31 +578,16 @@ int rf_env_step_end(rf_ctx *ctx, const float *host_pool, float *host_obs)
 
 int rf_env_step_plan(rf_ctx *ctx, const int32_t *host_actions, int *host_n_reset)
 {
-    RF_REQUIRE(ctx != nullptr && host_actions && host_n_reset, "rf_env_step_plan: NULL argument");
-    RF_REQUIRE(ctx->env_ready, "rf_env_step_plan: rf_env_configure first");
-    RF_REQUIRE(ctx->env_pending < 0, "rf_env_step_plan: the previous step was not finished");
-    RF_REQUIRE(!ctx->env_needs_reset, "rf_env_step_plan: a step was aborted (rf_env_reset first)");
+    RF_REQUIRE(ctx != nullptr, "rf_env_step_plan: ctx is NULL");
     RF_HIP(hipSetDevice(ctx->device));
-    drop_env_graph(ctx);
-    const rf_env_config &h = ctx->env_host;
-    for (int i = 0; i < h.n; ++i)
-        RF_REQUIRE(host_actions[i] >= 0 && host_actions[i] < h.n_actions,
-                   "rf_env_step_plan: action %d of env %d out of range", host_actions[i], i);
-    RF_HIP(hipMemcpyAsync(ctx->d_actions, host_actions, (size_t)h.n * 4, hipMemcpyHostToDevice, ctx->stream));
-    // the kernel below applies the actions and advances the counters: from here until the step is open (a HIP failure
-    // returns early) only a reset makes the environment usable again -- a retried step would apply the actions twice
-    ctx->env_needs_reset = true;
-    hipLaunchKernelGGL(rf::env_reset_kernel, dim3(1), dim3(1024), 0, ctx->stream, ctx->env_cfg, ctx->env,
-                       (const float *)nullptr, rf::kEnvResetRank, (const int *)ctx->d_actions);
-    RF_HIP(hipGetLastError());
-    int k = 0;
-    RF_HIP(hipMemcpyAsync(&k, ctx->env.done_count, 4, hipMemcpyDeviceToHost, ctx->stream));
-    RF_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->env_pending = k;
-    ctx->env_planned = true;
-    ctx->env_needs_reset = false;
-    *host_n_reset = k;
-    return RF_OK;
+    return env_step_plan(ctx, host_actions, host_n_reset, "rf_env_step_plan");
+}
+
+int rf_env_step_plan_jumps(rf_ctx *ctx, const float *host_actions, int *host_n_reset)
+{
+    RF_REQUIRE(ctx != nullptr, "rf_env_step_plan_jumps: ctx is NULL");
+    RF_HIP(hipSetDevice(ctx->device));
+    return env_step_plan(ctx, host_actions, host_n_reset, "rf_env_step_plan_jumps");
 }
 
 int rf_env_step_run(rf_ctx *ctx, const float *host_pool, float *host_obs, double *host_rewards, uint8_t *host_truncated)

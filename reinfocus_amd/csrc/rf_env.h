@@ -1,11 +1,13 @@
-// rf_env.h -- device-resident DiscreteSteps-v0 step.
+// rf_env.h -- device-resident DiscreteSteps-v0 and ContinuousJumps step.
 //
 // The O(N) numpy glue the reference runs on the host every step --
 //   DiscreteMoveTransformer.transform      environments/state_transformer.py:248-266
+//   (ContinuousJumpTransformer.transform   environments/state_transformer.py:95-118, EnvConfig::task == kEnvTaskJumps)
 //   TimeLimitEnder | DivergingEnder        environments/episode_ender.py:137-170, :602-628
 //   FastCameras / FastWorlds packing       graphics/camera.py:144-179, graphics/world.py:110-123
 //   NormalizedObserver(DeltaObserver(..))  environments/state_observer.py:232-292, :472-517
 //   Delta + Observation + OnTarget reward  environments/episode_rewarder.py:130-155, :226-292
+//   (Observation + Stopped * OnTarget      environments/episode_rewarder.py:226-292, :361-429, kEnvTaskJumps)
 //   same-step auto-reset                   environments/vector_environment.py:137-151
 // -- as two small kernels around the render and focus kernels, so that a step moves only the
 // actions and a pool of candidate reset states to the GPU and the observations / rewards /
@@ -53,12 +55,23 @@ __device__ __forceinline__ void pack_scene(const EnvConfig &c, float target, flo
 __device__ __forceinline__ void env_pre_one(const EnvConfig &c, const EnvState &s, const int *actions, int e)
 {
     float target = s.state[2 * e], focus = s.state[2 * e + 1];
-    if (actions) { // step: new = clip(f32(f64(old) + move), lo, hi) on BOTH columns
+    if (actions && c.task == kEnvTaskJumps) {
+        // ContinuousJumpTransformer (state_transformer.py:95-118), float32 throughout: a1 = (a + 1) / 2.0,
+        // m = a1 * (hi - lo) + lo, the focus plane jumps to m where |focus - m| > stop_threshold; no clip
+        const float a = __builtin_bit_cast(float, actions[e]); // (the 4-byte action slot holds a float32 here)
+        const float a1 = (a + 1.0f) / 2.0f;
+        const float m = a1 * (float)((double)c.limit_hi - (double)c.limit_lo) + c.limit_lo;
+        if (fabsf(focus - m) > c.stop_threshold)
+            focus = m;
+        s.state[2 * e + 1] = focus;
+    } else if (actions) { // step: new = clip(f32(f64(old) + move), lo, hi) on BOTH columns
         focus = (float)((double)focus + c.action_set[actions[e]]);
         focus = fminf(fmaxf(focus, c.limit_lo), c.limit_hi);
         target = fminf(fmaxf(target, c.limit_lo), c.limit_hi);
         s.state[2 * e] = target;
         s.state[2 * e + 1] = focus;
+    }
+    if (actions) {
         // enders (episode_ender.py:137-148, :602-607)
         s.steps[e] += 1;
         const float diff = fabsf(target - focus);
@@ -119,11 +132,18 @@ __device__ __forceinline__ void env_post_one(const EnvConfig &c, const EnvState 
         s.reward[e] = 0.0;
         return;
     }
-    // (abs(focus - old) * -1.0 / scale + obs[:, 1]) + ((abs(target - focus) < span) * 1.0 + 0.0)
-    const float moved = fabsf(focus - s.old_focus[e]) * -1.0f / c.reward_scale;
-    s.old_focus[e] = focus;
     const double on_target = (fabsf(target - focus) < c.on_target_span ? 1.0 : 0.0) * 1.0 + 0.0;
-    s.reward[e] = (double)(moved + o1) + on_target;
+    if (c.task == kEnvTaskJumps) {
+        // f64(obs[:, 1]) + f64(abs(focus - old) < threshold) * ((abs(target - focus) < span) * 1.0 + 0.0)
+        const double stopped = fabsf(focus - s.old_focus[e]) < c.stop_threshold ? 1.0 : 0.0;
+        s.old_focus[e] = focus;
+        s.reward[e] = (double)o1 + stopped * on_target;
+    } else {
+        // (abs(focus - old) * -1.0 / scale + obs[:, 1]) + ((abs(target - focus) < span) * 1.0 + 0.0)
+        const float moved = fabsf(focus - s.old_focus[e]) * -1.0f / c.reward_scale;
+        s.old_focus[e] = focus;
+        s.reward[e] = (double)(moved + o1) + on_target;
+    }
     bool trunc = s.diverging[e] >= c.early_end_steps;
     if (c.max_steps > 0)
         trunc = (s.steps[e] >= c.max_steps) || trunc;

@@ -5,11 +5,19 @@
 
 namespace rf {
 
+// EnvConfig::task: which of the reference's two tasks (examples/__init__.py:6-18) the step computes.  Both share the
+// ender, the observer, the scene packing, the auto-reset, the render and the focus measure; they differ in the
+// transformer and the rewarder only.  The branch is on a kernel argument: uniform over every launch.
+constexpr int kEnvTaskSteps = 0; // DiscreteSteps-v0: int32 action indices into action_set, Delta + Observation + OnTarget
+constexpr int kEnvTaskJumps = 1; // ContinuousJumps-v0: float32 actions in [-1, 1], Observation + Stopped * OnTarget
+
 struct EnvConfig {
+    int task;                 // kEnvTaskSteps / kEnvTaskJumps
     int n;                    // environments
     int n_actions;
     double action_set[32];    // float64 moves (state_transformer.py:246 numpy.asarray(action_set))
-    float limit_lo, limit_hi; // clip limits
+    float limit_lo, limit_hi; // clip limits (kEnvTaskSteps); the range the focus plane jumps in (kEnvTaskJumps)
+    float stop_threshold;     // kEnvTaskJumps: ContinuousJumpTransformer / StoppedRewarder threshold (target_radius / 2)
     int max_steps;            // <= 0: no time limit (single-env DiscreteSteps)
     float diverge_threshold;  // target_radius / 2
     int early_end_steps;
@@ -28,7 +36,7 @@ struct EnvState {            // all device arrays, length n unless noted
     int *diverging;          // DivergingEnder._diverging_steps
     float *last_diff;        // DivergingEnder._last_diff
     float *old_wrapped;      // [n][2] DeltaObserver._old_wrapped_observations
-    float *old_focus;        // DeltaRewarder._old_states
+    float *old_focus;        // DeltaRewarder._old_states (kEnvTaskJumps: StoppedRewarder._old_states, same rules)
     // per-step scratch / outputs
     float *cam_dyn, *rect;   // scene of all n envs
     float *cam_dyn2, *rect2; // compacted scene of the envs that reset this step

@@ -1,4 +1,4 @@
-"""Thin vector-environment harness for the DiscreteSteps-v0 task.
+"""Thin vector-environment harness for the DiscreteSteps-v0 and ContinuousJumps tasks.
 
 The reference assembles this environment from six strategy objects
 (examples/custom_environments.py:114-241 on top of
@@ -15,6 +15,13 @@ State is float32[N, 2] = [target position, focus plane]; observations are
 float32[N, 4] = [focus plane, focus value, their changes], normalised to [-1, 1].
 Deliberate difference: the reference's RangedInitializer is unseeded
 (state_initializer.py:50); here `seed` makes runs reproducible.
+
+ContinuousJumps (custom_environments.py:244-339) differs from DiscreteSteps in its transformer
+(ContinuousJumpTransformer) and its rewarder (ObservationRewarder + StoppedRewarder *
+OnTargetRewarder) only; its vector form (VectorContinuousJumps, DeviceVectorContinuousJumps,
+ShardedVectorContinuousJumps) is what the reference's docstring prescribes for vectorising an
+environment (custom_environments.py:117-133): the same strategies with num_envs in place of 1, driven
+by VectorEnvironment with the vector DiscreteSteps' TimeLimitEnder | DivergingEnder.
 """
 
 import numpy as np
@@ -25,6 +32,21 @@ from reinfocus_amd.environments import state_observer
 from reinfocus_amd.graphics import render
 
 TARGET, FOCUS = 0, 1  # state element indices (custom_environments.py:169-171)
+JUMP_STOP = 0.25 / 2.0  # ContinuousJumps: target_radius / 2.0, the transformer's and the stopped rewarder's threshold
+
+
+def jump_actions(actions, num_envs):
+    """The float32[num_envs] actions of a ContinuousJumps vector step (also accepted as [num_envs, 1]).
+    Deliberate difference from the reference: actions that are NaN, infinite or outside [-1, 1] are refused
+    (AssertionError, before any state changes), as the device step refuses them (rf_env_step_jumps); the reference's
+    ContinuousJumpTransformer would move the focus plane outside [5, 10] or make the camera non-finite."""
+    actions = np.asarray(actions, dtype=np.float32)
+    if actions.shape not in ((num_envs,), (num_envs, 1)):
+        raise AssertionError(f"expected {num_envs} actions (shape ({num_envs},) or ({num_envs}, 1)), got {actions.shape}")
+    actions = actions.reshape(num_envs)
+    if not np.all(np.abs(actions) <= 1):  # (False for NaN)
+        raise AssertionError("ContinuousJumps actions must be finite and in [-1, 1]")
+    return actions
 
 
 def _gymnasium_bases():
@@ -207,6 +229,73 @@ class _Rewarder:
         return (moved + observations[:, self._o_index]) + on_target
 
 
+class _JumpTransformer:
+    """ContinuousJumpTransformer (state_transformer.py:66-118): the element `move_index` jumps to the position in
+    `limits` proportional to the action's in [-1, 1], unless the jump is not longer than stop_threshold.  No clip."""
+
+    def __init__(self, move_index, limits, stop_threshold):
+        self._move_index = move_index
+        self._limits = limits
+        self._stop_threshold = abs(stop_threshold)
+
+    def transform(self, states, actions):
+        new_states = states.copy()
+        actions = (np.asarray(actions).flatten() + 1) / 2.0
+        moved_states = actions * (self._limits[1] - self._limits[0]) + self._limits[0]
+        moved = abs(new_states[:, self._move_index] - moved_states) > self._stop_threshold
+        new_states[moved, self._move_index] = moved_states[moved]
+        return new_states
+
+
+class _StoppedRewarder:
+    """StoppedRewarder (episode_rewarder.py:361-429): `reward` where the element `check_index` moved less than
+    threshold since the last step (or the episode's start)."""
+
+    def __init__(self, check_index, threshold, reward=1.0):
+        self._check_index = check_index
+        self._threshold = abs(threshold)
+        self._reward = reward
+        self._old_states = None
+
+    def reset(self, states, observations, indices=None):
+        if self._old_states is not None and indices is not None:
+            self._old_states[indices] = states[:, self._check_index]
+        else:
+            self._old_states = states[:, self._check_index]
+
+    def reward(self, states, observations):
+        reward = (abs(states[:, self._check_index] - self._old_states) < self._threshold) * self._reward
+        self._old_states = states[:, self._check_index]
+        return reward
+
+
+class _JumpRewarder:
+    """ObservationRewarder(1) + StoppedRewarder(1, stop_threshold) * OnTargetRewarder((0, 1), span)
+    (custom_environments.py:316-323; episode_rewarder.py:210-292, :361-429): float64 focus value + [stopped] *
+    [on target]."""
+
+    def __init__(self, stop_threshold, span, focus_value_o_index=1):
+        self._stopped = _StoppedRewarder(FOCUS, stop_threshold)
+        self._span = span
+        self._o_index = focus_value_o_index
+
+    def reset(self, states, observations, indices=None):
+        self._stopped.reset(states, observations, indices)
+
+    def _on_target(self, states, observations):
+        return (abs(states[:, TARGET] - states[:, FOCUS]) < self._span) * 1.0 + 0.0
+
+    def reward(self, states, observations):
+        return observations[:, self._o_index] + (self._stopped.reward(states, observations)
+                                                 * self._on_target(states, observations))
+
+
+def _jump_spaces(env, num_envs):
+    """ContinuousJumpTransformer's action space (state_transformer.py:85), batched."""
+    env.single_action_space = spaces.Box(-1, 1, (1,), dtype=np.float32)
+    env.action_space = spaces.batch_space(env.single_action_space, num_envs)
+
+
 class _HostGlue:
     """The DiscreteSteps task with the reference's numpy glue on the host around the GPU
     render + focus (FocusObserver): everything VectorDiscreteSteps, DiscreteSteps and
@@ -385,18 +474,40 @@ class ContinuousJumps(_HostGlue, _EnvBase):
         return observations[0], reward, self._ender.is_terminated()[0], self._ender.is_truncated()[0], {}
 
 
+class VectorContinuousJumps(_HostGlue, _VectorEnvBase):
+    """A vector ContinuousJumps (custom_environments.py:244-339 with num_envs in place of 1, and the vector
+    DiscreteSteps' TimeLimitEnder | DivergingEnder, :185-190) with the reference's numpy glue on the host, driven as
+    VectorEnvironment.step drives its strategies (vector_environment.py:104-164).  Same extensions as
+    VectorDiscreteSteps.  Actions: float32[num_envs] (or [num_envs, 1]) in [-1, 1]; NaN, infinite or out-of-range
+    actions are refused before any state changes (jump_actions: a deliberate difference from the reference).
+    DeviceVectorContinuousJumps is the same environment with the glue on the GPU; results are identical bit for bit."""
+
+    def __init__(self, max_episode_steps=20, num_envs=1, render_mode=None, **kwargs):
+        super().__init__(max_episode_steps, num_envs, render_mode, **kwargs)
+        self._transformer = _JumpTransformer(FOCUS, self._limits, JUMP_STOP)
+        self._rewarder = _JumpRewarder(JUMP_STOP, 0.25)
+        _jump_spaces(self, num_envs)
+
+    def _transform(self, states, actions):
+        return self._transformer.transform(states, actions)
+
+    def step(self, actions):
+        return super().step(jump_actions(actions, self.num_envs))
+
+
 class _DeviceShard:
-    """One rf_ctx holding a contiguous range of device-resident DiscreteSteps environments
-    (rf_env_*): the context, its RNG states at `first_state_index`, and the rf_env_config of the
-    task (custom_environments.py:166-241).  DeviceVectorDiscreteSteps owns one,
-    ShardedVectorDiscreteSteps one per device."""
+    """One rf_ctx holding a contiguous range of device-resident environments (rf_env_*): the context, its RNG states
+    at `first_state_index`, and the rf_env_config of the task (custom_environments.py:166-241) -- DiscreteSteps, or
+    ContinuousJumps with jumps=True (rf_env_configure_jumps).  DeviceVectorDiscreteSteps /
+    DeviceVectorContinuousJumps own one, the sharded environments one per device."""
 
     ENDS = (5.0, 10.0)
     TARGET_RADIUS = 0.25
     MAX_MOVE = 5.0
     EARLY_END_STEPS = 3  # DivergingEnder(..., early_end_steps=3), custom_environments.py:186-190
 
-    def __init__(self, num_envs, max_episode_steps, frame_height, samples_per_pixel, device, first_state_index):
+    def __init__(self, num_envs, max_episode_steps, frame_height, samples_per_pixel, device, first_state_index,
+                 jumps=False):
         import math
 
         from reinfocus_amd import _native, vision
@@ -443,7 +554,10 @@ class _DeviceShard:
             cfg.spp = samples_per_pixel
             cfg.gray_mode = vision.GRAY_MODE
             self.ctx.seed(num_envs * frame_height * frame_height, 0, self.first_state_index)
-            self.ctx.env_configure(cfg)
+            if jumps:  # (limit_lo / limit_hi: the range the focus plane jumps in)
+                self.ctx.env_configure_jumps(cfg, JUMP_STOP)
+            else:
+                self.ctx.env_configure(cfg)
         except Exception:
             self.ctx.close()
             raise
@@ -469,26 +583,23 @@ class _DeviceShard:
 
 
 def _device_spaces(env, action_set, num_envs):
-    env.single_action_space = spaces.Discrete(len(action_set))
-    env.action_space = spaces.batch_space(env.single_action_space, num_envs)
+    """action_set None: ContinuousJumps' Box(-1, 1, (1,))."""
+    if action_set is None:
+        _jump_spaces(env, num_envs)
+    else:
+        env.single_action_space = spaces.Discrete(len(action_set))
+        env.action_space = spaces.batch_space(env.single_action_space, num_envs)
     env.single_observation_space = spaces.Box(-np.ones(4, dtype=np.float32), np.ones(4, dtype=np.float32),
                                               dtype=np.float32)
     env.observation_space = spaces.batch_space(env.single_observation_space, num_envs)
 
 
-class DeviceVectorDiscreteSteps(_VectorEnvBase):
-    """VectorDiscreteSteps with the whole step resident on the GPU (rf_env_*, SURVEY.md
-    section 8(f) item 1): same constructor, same reset/step results bit for bit, but a step
-    only uploads the actions and the initializer's candidate states and downloads
-    observations, rewards and flags.  This is what `DiscreteSteps-v0`'s vector entry point
-    builds.  The initializer stays on the host (numpy PCG64DXSM): a copy of the generator
-    proposes num_envs candidate states per step, the device hands row r to the r-th environment
-    that ended, and the real generator then draws exactly the rows that were used -- the same
-    consumption as VectorDiscreteSteps.  render_mode="rgb_array" works as in the reference
-    (HistoryVisualizer on the environment's own renderer state: the 600 px render advances /
-    re-seeds the RNG states the next step uses)."""
+class _DeviceVectorEnv(_VectorEnvBase):
+    """The device-resident vector environment of either task (_JUMPS): DeviceVectorDiscreteSteps,
+    DeviceVectorContinuousJumps."""
 
     metadata = {"render_modes": ["rgb_array"], "render_fps": 4}
+    _JUMPS = False
 
     def __init__(self, max_episode_steps=20, num_envs=1, render_mode=None, *, frame_height=300,
                  samples_per_pixel=100, seed=None, device=None, first_state_index=0):
@@ -497,11 +608,11 @@ class DeviceVectorDiscreteSteps(_VectorEnvBase):
         self.render_mode = render_mode
         self.num_envs = num_envs
         self._shard = _DeviceShard(num_envs, max_episode_steps, frame_height, samples_per_pixel, device,
-                                   first_state_index)
+                                   first_state_index, jumps=self._JUMPS)
         self._ctx = self._shard.ctx
         self._limits = _DeviceShard.ENDS
         self._initializer = _Initializer(self._limits, seed)
-        self._action_set = self._shard.action_set
+        self._action_set = None if self._JUMPS else self._shard.action_set
         _device_spaces(self, self._action_set, num_envs)
         self._visualizer = None
         if render_mode == "rgb_array":  # custom_environments.py:229-238
@@ -524,8 +635,13 @@ class DeviceVectorDiscreteSteps(_VectorEnvBase):
         return observations, {}
 
     def step(self, actions):
+        if self._JUMPS:
+            actions = jump_actions(actions, self.num_envs)
         pool = self._initializer.propose(self.num_envs)
-        observations, rewards, truncated, used = self._ctx.env_step(actions, pool)
+        if self._JUMPS:
+            observations, rewards, truncated, used = self._ctx.env_step_jumps(actions, pool)
+        else:
+            observations, rewards, truncated, used = self._ctx.env_step(actions, pool)
         if used:
             self._initializer.initialize(used)  # consume exactly the rows that were used
         if self._visualizer is not None:  # vector_environment.py:149-156
@@ -547,6 +663,29 @@ class DeviceVectorDiscreteSteps(_VectorEnvBase):
 
     def close(self):
         self._ctx.close()
+
+
+class DeviceVectorDiscreteSteps(_DeviceVectorEnv):
+    """VectorDiscreteSteps with the whole step resident on the GPU (rf_env_*, SURVEY.md
+    section 8(f) item 1): same constructor, same reset/step results bit for bit, but a step
+    only uploads the actions and the initializer's candidate states and downloads
+    observations, rewards and flags.  This is what `DiscreteSteps-v0`'s vector entry point
+    builds.  The initializer stays on the host (numpy PCG64DXSM): a copy of the generator
+    proposes num_envs candidate states per step, the device hands row r to the r-th environment
+    that ended, and the real generator then draws exactly the rows that were used -- the same
+    consumption as VectorDiscreteSteps.  render_mode="rgb_array" works as in the reference
+    (HistoryVisualizer on the environment's own renderer state: the 600 px render advances /
+    re-seeds the RNG states the next step uses)."""
+
+
+class DeviceVectorContinuousJumps(_DeviceVectorEnv):
+    """VectorContinuousJumps with the whole step resident on the GPU (rf_env_configure_jumps, rf_env_step_jumps): the
+    DiscreteSteps step's kernels with the continuous-jump transform and the stopped * on-target reward, selected by the
+    context's task; same constructor and reset/step results bit for bit as VectorContinuousJumps, the same
+    initializer consumption and render_mode="rgb_array" as DeviceVectorDiscreteSteps.  Actions: float32[num_envs]
+    (or [num_envs, 1]) in [-1, 1]; NaN, infinite or out-of-range actions are refused before any state changes."""
+
+    _JUMPS = True
 
 
 def split_environments(num_envs, shards):
@@ -581,8 +720,9 @@ class _ShardSet:
         return self._env._threads[g].submit(self._env._shards[g].status, local).result()
 
 
-class ShardedVectorDiscreteSteps(_VectorEnvBase):
-    """DeviceVectorDiscreteSteps over several GPUs of one node (the
+class _ShardedVectorEnv(_VectorEnvBase):
+    """The device-resident environment of either task (_JUMPS) over several GPUs of one node: ShardedVectorDiscreteSteps
+    is DeviceVectorDiscreteSteps, ShardedVectorContinuousJumps DeviceVectorContinuousJumps so sharded (the
     reference has no counterpart: vector_environment.py:104-164 steps all environments on one
     device).  Environments are independent, so device g owns the contiguous range
     [first_g, first_g + n_g) -- one rf_ctx and one host thread per device (a single-worker executor
@@ -616,6 +756,7 @@ class ShardedVectorDiscreteSteps(_VectorEnvBase):
     to the CPUs of its GPU's NUMA node (`placements` says where each shard ended up)."""
 
     metadata = {"render_modes": ["rgb_array"], "render_fps": 4}
+    _JUMPS = False
 
     def __init__(self, max_episode_steps=20, num_envs=1, render_mode=None, *, devices=None, frame_height=300,
                  samples_per_pixel=100, seed=None, first_state_index=0, exact=False, numa_pin=True):
@@ -644,6 +785,7 @@ class ShardedVectorDiscreteSteps(_VectorEnvBase):
         self._threads = [concurrent.futures.ThreadPoolExecutor(max_workers=1, thread_name_prefix=f"reinfocus-shard{g}")
                          for g in range(len(devices))]
         pixels = frame_height * frame_height
+        options = {"jumps": True} if self._JUMPS else {}
         self._shards = []
         try:
             def make_shard(count, device, first):
@@ -652,7 +794,7 @@ class ShardedVectorDiscreteSteps(_VectorEnvBase):
                 placement = _native.device_info(device)
                 placement["cpus"] = _native.pin_to_numa_node(placement["numa_node"]) if numa_pin else None
                 shard = _DeviceShard(count, max_episode_steps, frame_height, samples_per_pixel, device,
-                                     first_state_index + first * pixels)
+                                     first_state_index + first * pixels, **options)
                 shard.placement = placement
                 return shard
 
@@ -672,7 +814,7 @@ class ShardedVectorDiscreteSteps(_VectorEnvBase):
             for thread in self._threads:
                 thread.shutdown(wait=True)
             raise
-        self._action_set = self._shards[0].action_set
+        self._action_set = None if self._JUMPS else self._shards[0].action_set
         _device_spaces(self, self._action_set, num_envs)
         self._visualizer = None
         if render_mode == "rgb_array":  # custom_environments.py:229-238
@@ -737,8 +879,13 @@ class ShardedVectorDiscreteSteps(_VectorEnvBase):
         render that lets the second half run as ONE render launch), in the exact mode rf_env_step_begin (the cut after
         the full render: its row renders happen on other shards).  If any shard fails, the shards whose half did run
         drop it (rf_env_step_abort: they then insist on a reset) and the first error is raised."""
-        if self.exact:
+        if self.exact and self._JUMPS:
+            futures = self._submit(lambda shard, a: shard.ctx.env_step_begin_jumps(a), self._slices(actions))
+        elif self.exact:
             futures = self._submit(lambda shard, a: shard.ctx.env_step_begin(a), self._slices(actions))
+        elif self._JUMPS:
+            futures = self._submit(lambda shard, a: (None, None, shard.ctx.env_step_plan_jumps(a)),
+                                   self._slices(actions))
         else:
             futures = self._submit(lambda shard, a: (None, None, shard.ctx.env_step_plan(a)), self._slices(actions))
         results, errors = [], []
@@ -757,11 +904,14 @@ class ShardedVectorDiscreteSteps(_VectorEnvBase):
         return results
 
     def step(self, actions):
-        actions = np.asarray(actions).reshape(self.num_envs)
         # every shard validates its slice again, but a bad action must not leave some shards half way
         # through a step: check all of them before any shard begins
-        if actions.size and (actions.min() < 0 or actions.max() >= len(self._action_set)):
-            raise AssertionError(f"action outside [0, {len(self._action_set)})")
+        if self._JUMPS:
+            actions = jump_actions(actions, self.num_envs)
+        else:
+            actions = np.asarray(actions).reshape(self.num_envs)
+            if actions.size and (actions.min() < 0 or actions.max() >= len(self._action_set)):
+                raise AssertionError(f"action outside [0, {len(self._action_set)})")
         pool = self._initializer.propose(self.num_envs)
         firsts = self._begin(actions)
         ended = [k for _, _, k in firsts]
@@ -825,3 +975,15 @@ class ShardedVectorDiscreteSteps(_VectorEnvBase):
         for thread in self._threads:
             thread.shutdown(wait=True)
         self._threads = []
+
+
+class ShardedVectorDiscreteSteps(_ShardedVectorEnv):
+    """DeviceVectorDiscreteSteps over several GPUs of one node (see _ShardedVectorEnv)."""
+
+
+class ShardedVectorContinuousJumps(_ShardedVectorEnv):
+    """DeviceVectorContinuousJumps over several GPUs of one node (see _ShardedVectorEnv): float32 actions, handed to
+    every shard's slice (rf_env_step_plan_jumps; rf_env_step_begin_jumps in the exact mode); refused as a whole before
+    any shard begins when one of them is NaN, infinite or outside [-1, 1]."""
+
+    _JUMPS = True

@@ -9,6 +9,17 @@ gymnasium.make / gymnasium.make_vec(id, num_envs, vectorization_mode="custom", v
 The vector entry point builds the device-resident environment (harness.DeviceVectorDiscreteSteps,
 the one bench.py measures); `glue="host"` selects the numpy-glue VectorDiscreteSteps (identical
 results) and `devices=[...]` the environment sharded over several GPUs.
+
+`ContinuousJumps-v0` has no vector entry point here, as in the reference (examples/__init__.py:14-18).
+vector_continuous_jumps below is one: the vector form the reference's docstring tells users to add
+(examples/custom_environments.py:117-133).  A user who wants it from gymnasium registers it under an id
+of their own, e.g.
+
+    gymnasium.register(id="MyContinuousJumps-v0",
+                       entry_point="reinfocus_amd.environments.harness:ContinuousJumps",
+                       vector_entry_point="reinfocus_amd.registration:vector_continuous_jumps",
+                       max_episode_steps=20)
+    gymnasium.make_vec("MyContinuousJumps-v0", num_envs=64, vectorization_mode="custom")
 """
 
 from reinfocus_amd.environments import harness
@@ -40,6 +51,23 @@ def vector_discrete_steps(max_episode_steps=20, num_envs=1, render_mode=None, *,
         return harness.VectorDiscreteSteps(max_episode_steps, num_envs, render_mode, **kwargs)
     assert glue == "device", f"glue must be 'device' or 'host', not {glue!r}"
     return harness.DeviceVectorDiscreteSteps(max_episode_steps, num_envs, render_mode, **kwargs)
+
+
+def vector_continuous_jumps(max_episode_steps=20, num_envs=1, render_mode=None, *, glue="device", devices=None,
+                            **kwargs):
+    """A vector ContinuousJumps, usable as a gymnasium vector_entry_point (see the module docstring; not registered
+    here: ENTRY_POINTS mirrors the reference's registrations).  Arguments and extensions as vector_discrete_steps:
+    glue = "device" (default: harness.DeviceVectorContinuousJumps, whole step on the GPU) or "host"
+    (harness.VectorContinuousJumps, numpy glue around render + focus; identical results); devices = list of GPU
+    indices -> harness.ShardedVectorContinuousJumps.  Actions are float32[num_envs] in [-1, 1]; anything else is
+    refused (a deliberate difference from the reference)."""
+    if devices is not None:
+        assert glue == "device", "the sharded environment is device-resident"
+        return harness.ShardedVectorContinuousJumps(max_episode_steps, num_envs, render_mode, devices=devices, **kwargs)
+    if glue == "host":
+        return harness.VectorContinuousJumps(max_episode_steps, num_envs, render_mode, **kwargs)
+    assert glue == "device", f"glue must be 'device' or 'host', not {glue!r}"
+    return harness.DeviceVectorContinuousJumps(max_episode_steps, num_envs, render_mode, **kwargs)
 
 
 def register_with_gymnasium():
