@@ -316,6 +316,8 @@ int rf_env_get_states(rf_ctx *ctx, float *host_states);
  *                           are unused and limit_lo / limit_hi are the range the focus plane jumps in (the state's [5, 10]).
  *   rf_env_step_jumps, rf_env_step_begin_jumps, rf_env_step_plan_jumps
  *                           rf_env_step / _begin / _plan with host_actions float32[n]: same schedules, same outputs.
+ *                           These are the float32-action forms: a composed context with a continuous transformer
+ *                           (rf_env_configure_composed below) steps through them too.
  * Deliberate difference from the reference: an action that is NaN, infinite or outside [-1, 1] is refused
  * (RF_ERR_INVALID) before any state changes; the reference would carry it into the focus plane.  The int32 calls on a
  * context configured by rf_env_configure_jumps, and these on one configured by rf_env_configure, are refused too. */
@@ -325,6 +327,82 @@ int rf_env_step_jumps(rf_ctx *ctx, const float *host_actions, const float *host_
 int rf_env_step_begin_jumps(rf_ctx *ctx, const float *host_actions, double *host_rewards, uint8_t *host_truncated,
                             int *host_n_reset);
 int rf_env_step_plan_jumps(rf_ctx *ctx, const float *host_actions, int *host_n_reset);
+
+/* ---- the same device-resident step for an environment composed of strategy objects ---------------------------------
+ * VectorEnvironment (environments/vector_environment.py:104-164) over any transformer, ender and rewarder the
+ * reference's classes can express (environments/state_transformer.py, episode_ender.py, episode_rewarder.py), with the
+ * observer both tasks use: NormalizedObserver(DeltaObserver([IndexedElementObserver(1), FocusObserver])).  State is
+ * [target, focus plane], so every state index is 0 or 1.  Python compiles the objects into an rf_env_program
+ * (harness.DeviceVectorEnvironment); rf_env_configure_composed uploads it once, and every schedule of the step runs it.
+ *
+ * Ender and rewarder trees are postfix lists over their leaves: an entry >= 0 pushes leaf [entry], RF_OP_OR / RF_OP_ADD
+ * (-1) and RF_OP_AND / RF_OP_MUL (-2) pop two operands and push the result.  reward_f64[i] says whether entry i's value
+ * is float64 (numpy's promotion, decided by Python): a float32 node computes in float32.  Rewards are returned as
+ * float64.  Parameters are doubles, rounded to float32 where numpy rounds a Python scalar next to a float32 array. */
+#define RF_ENV_MAX_LEAVES 8
+#define RF_ENV_MAX_OPS (2 * RF_ENV_MAX_LEAVES - 1)
+#define RF_ENV_MAX_STOPPED_STEPS 31
+
+enum { RF_TRANSFORM_CONTINUOUS_JUMP = 0, RF_TRANSFORM_CONTINUOUS_MOVE = 1, RF_TRANSFORM_DISCRETE_JUMP = 2,
+       RF_TRANSFORM_DISCRETE_MOVE = 3 };
+enum { RF_ENDER_DIVERGING = 0, RF_ENDER_ENDLESS = 1, RF_ENDER_ON_TARGET = 2, RF_ENDER_STOPPED = 3,
+       RF_ENDER_TIME_LIMIT = 4 };
+enum { RF_REWARD_DELTA = 0, RF_REWARD_DISTANCE = 1, RF_REWARD_OBSERVATION = 2, RF_REWARD_ON_TARGET = 3,
+       RF_REWARD_STOPPED = 4 };
+enum { RF_OP_OR = -1, RF_OP_AND = -2, RF_OP_ADD = -1, RF_OP_MUL = -2 };
+
+typedef struct rf_env_ender {
+    int kind;              /* RF_ENDER_* */
+    int index0, index1;    /* check_indices (StoppedEnder: check_index in index0) */
+    int steps;             /* early_end_steps (Diverging, OnTarget, Stopped <= 31) / max_steps (TimeLimit) */
+    double threshold;      /* Diverging threshold / OnTarget early_end_radius / Stopped early_end_span */
+} rf_env_ender;
+
+typedef struct rf_env_rewarder {
+    int kind;              /* RF_REWARD_* */
+    int index0, index1;    /* check_index(es); Observation: reward_observation_index (0-3) in index0 */
+    double p[3];           /* Delta: reward, scale | Distance: span, high - low, low | OnTarget: span, on - off, off
+                              | Stopped: |threshold|, reward | Observation: unused */
+} rf_env_rewarder;
+
+typedef struct rf_env_program {
+    int transformer;         /* RF_TRANSFORM_* */
+    int move_index;          /* 0 or 1 */
+    int n_actions;           /* discrete transformers: 1 ... 32 */
+    double action_set[32];   /* DiscreteMove: the float64 moves; DiscreteJump: the float32 positions */
+    double limit_lo, limit_hi; /* limits (clip limits; ContinuousJump: the range the element jumps in) */
+    double speed;            /* ContinuousMove */
+    double stop_threshold;   /* ContinuousJump / ContinuousMove: |stop_threshold| */
+    int n_enders, n_ender_ops;
+    rf_env_ender enders[RF_ENV_MAX_LEAVES];
+    int ender_ops[RF_ENV_MAX_OPS];
+    int n_rewarders, n_reward_ops;
+    rf_env_rewarder rewarders[RF_ENV_MAX_LEAVES];
+    int reward_ops[RF_ENV_MAX_OPS];
+    int reward_f64[RF_ENV_MAX_OPS];
+} rf_env_program;
+
+/* rf_env_configure for a composed environment.  Of cfg, only n, mid, scale, the camera / world packing, lens_radius,
+ * frame_height, spp and gray_mode are used: n_actions, action_set, limit_lo, limit_hi, max_steps, diverge_threshold,
+ * early_end_steps, reward_scale and on_target_span are ignored (the program replaces them).  Refused (RF_ERR_INVALID,
+ * nothing changes): more than RF_ENV_MAX_LEAVES leaves, a postfix list that is not one well-formed expression over
+ * every leaf once, an unknown kind, a state index outside {0, 1} or an observation index outside 0-3, a StoppedEnder
+ * with steps outside [0, 31], n_actions outside [1, 32] for a discrete transformer, a non-finite parameter.
+ * Actions: the discrete transformers take the int32 rf_env_step / _begin / _plan (indices outside [0, n_actions) are
+ * refused), the continuous ones the float32 forms rf_env_step_jumps / _begin_jumps / _plan_jumps (NaN and infinities
+ * are refused; ContinuousJump also refuses values outside [-1, 1]; ContinuousMove clips them, as the reference does).
+ * The other dtype's entry points are refused.  All else -- reset, the schedules, the sharded halves, render, states --
+ * is the DiscreteSteps step's. */
+int rf_env_configure_composed(rf_ctx *ctx, const rf_env_config *cfg, const rf_env_program *program);
+
+/* The per-leaf strategy state of a composed environment, each array NULL or as laid out here:
+ *   host_counters  int32[n_enders][n]    Diverging: diverging steps; OnTarget: on-target steps; TimeLimit: steps; else 0
+ *   host_floats    float32[n_enders][n]  Diverging: the last difference; else 0
+ *   host_histories float32[H][n]         the StoppedEnder histories in leaf order, steps + 1 rows each, oldest first,
+ *                                        NaN where empty; H = the sum of those lengths
+ *   host_old       float32[n_rewarders][n] Delta / Stopped: the element's previous value; else 0 */
+int rf_env_get_strategy_state(rf_ctx *ctx, int32_t *host_counters, float *host_floats, float *host_histories,
+                              float *host_old);
 
 #ifdef __cplusplus
 }

@@ -65,6 +65,8 @@ SYMBOLS = (
     "rf_env_step_jumps",
     "rf_env_step_begin_jumps",
     "rf_env_step_plan_jumps",
+    "rf_env_configure_composed",
+    "rf_env_get_strategy_state",
     "rf_render_kernel_name",
     "rf_pixels_rendered",
     "rf_allocations_poisoned",
@@ -99,6 +101,48 @@ class EnvConfig(ctypes.Structure):
         ("frame_height", ctypes.c_int),
         ("spp", ctypes.c_int),
         ("gray_mode", ctypes.c_int),
+    ]
+
+
+MAX_LEAVES = 8  # RF_ENV_MAX_LEAVES
+MAX_OPS = 2 * MAX_LEAVES - 1  # RF_ENV_MAX_OPS
+MAX_STOPPED_STEPS = 31  # RF_ENV_MAX_STOPPED_STEPS
+
+
+class EnvEnder(ctypes.Structure):
+    """rf_env_ender (include/reinfocus_hip.h)."""
+
+    _fields_ = [("kind", ctypes.c_int), ("index0", ctypes.c_int), ("index1", ctypes.c_int), ("steps", ctypes.c_int),
+                ("threshold", ctypes.c_double)]
+
+
+class EnvRewarder(ctypes.Structure):
+    """rf_env_rewarder (include/reinfocus_hip.h)."""
+
+    _fields_ = [("kind", ctypes.c_int), ("index0", ctypes.c_int), ("index1", ctypes.c_int), ("p", ctypes.c_double * 3)]
+
+
+class EnvProgram(ctypes.Structure):
+    """rf_env_program (include/reinfocus_hip.h): a composed environment's strategies."""
+
+    _fields_ = [
+        ("transformer", ctypes.c_int),
+        ("move_index", ctypes.c_int),
+        ("n_actions", ctypes.c_int),
+        ("action_set", ctypes.c_double * 32),
+        ("limit_lo", ctypes.c_double),
+        ("limit_hi", ctypes.c_double),
+        ("speed", ctypes.c_double),
+        ("stop_threshold", ctypes.c_double),
+        ("n_enders", ctypes.c_int),
+        ("n_ender_ops", ctypes.c_int),
+        ("enders", EnvEnder * MAX_LEAVES),
+        ("ender_ops", ctypes.c_int * MAX_OPS),
+        ("n_rewarders", ctypes.c_int),
+        ("n_reward_ops", ctypes.c_int),
+        ("rewarders", EnvRewarder * MAX_LEAVES),
+        ("reward_ops", ctypes.c_int * MAX_OPS),
+        ("reward_f64", ctypes.c_int * MAX_OPS),
     ]
 
 
@@ -162,6 +206,8 @@ def load():
     lib.rf_env_step_jumps.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.POINTER(i32)]
     lib.rf_env_step_begin_jumps.argtypes = [vp, vp, vp, vp, ctypes.POINTER(i32)]
     lib.rf_env_step_plan_jumps.argtypes = [vp, vp, ctypes.POINTER(i32)]
+    lib.rf_env_configure_composed.argtypes = [vp, ctypes.POINTER(EnvConfig), ctypes.POINTER(EnvProgram)]
+    lib.rf_env_get_strategy_state.argtypes = [vp, vp, vp, vp, vp]
     lib.rf_render_kernel_name.restype = ctypes.c_char_p
     lib.rf_render_kernel_name.argtypes = [vp]
     lib.rf_pixels_rendered.restype = ctypes.c_ulonglong
@@ -367,6 +413,30 @@ class Context:
         self._env_k = ctypes.c_int(0)
         self._env_k_ref = ctypes.byref(self._env_k)
         _check(self._lib.rf_env_configure_jumps(self._h, ctypes.byref(cfg), float(stop_threshold)))
+
+    def env_configure_composed(self, cfg, program):
+        """rf_env_configure_composed: the context steps the composed environment `program` (an EnvProgram; int32
+        actions for a discrete transformer, the float32 env_step*_jumps calls for a continuous one)."""
+        self._env_n = cfg.n
+        self._env_k = ctypes.c_int(0)
+        self._env_k_ref = ctypes.byref(self._env_k)
+        _check(self._lib.rf_env_configure_composed(self._h, ctypes.byref(cfg), ctypes.byref(program)))
+        self._env_program = (program.n_enders, program.n_rewarders,
+                             sum(program.enders[i].steps + 1 for i in range(program.n_enders)
+                                 if program.enders[i].kind == 3))  # (RF_ENDER_STOPPED)
+
+    def env_strategy_state(self):
+        """rf_env_get_strategy_state: (counters int32[n_enders, n], floats float32[n_enders, n], histories
+        float32[rows, n], old values float32[n_rewarders, n])."""
+        n_enders, n_rewarders, rows = self._env_program
+        n = self._env_n
+        counters = np.empty((n_enders, n), dtype=np.int32)
+        floats = np.empty((n_enders, n), dtype=np.float32)
+        histories = np.empty((rows, n), dtype=np.float32)
+        old = np.empty((n_rewarders, n), dtype=np.float32)
+        _check(self._lib.rf_env_get_strategy_state(self._h, _ptr(counters), _ptr(floats),
+                                                   _ptr(histories) if rows else None, _ptr(old)))
+        return counters, floats, histories, old
 
     def env_reset(self, states):
         states = np.ascontiguousarray(states, dtype=np.float32).reshape(self._env_n, 2)

@@ -36,30 +36,187 @@ bool fused_step_possible(const rf_ctx *ctx)
 }
 
 // The actions of one step, checked on the host before anything is enqueued (a refused step changes no state).  The
-// int32 form (DiscreteSteps-v0) takes indices into the action set; the float32 form (ContinuousJumps) takes values in
-// [-1, 1] -- NaN, infinities and values outside are refused, where the reference's ContinuousJumpTransformer would carry
-// them into the focus plane.  Calling the form of the other task is an error: the 4-byte slots are never reinterpreted.
+// int32 form (DiscreteSteps-v0, the composed discrete transformers) takes indices into the action set; the float32 form
+// (ContinuousJumps, the composed continuous transformers) takes finite values, in [-1, 1] for a jump -- NaN, infinities
+// and jumps outside are refused, where the reference's ContinuousJumpTransformer would carry them into the focus plane
+// (a ContinuousMoveTransformer clips finite values, as the reference does).  Calling the form of the other dtype is an
+// error: the 4-byte slots are never reinterpreted.
+bool composed_discrete(const rf_ctx *ctx)
+{
+    return ctx->env_program.transformer == RF_TRANSFORM_DISCRETE_JUMP ||
+           ctx->env_program.transformer == RF_TRANSFORM_DISCRETE_MOVE;
+}
+
 int check_actions(const rf_ctx *ctx, const int32_t *actions, const char *fn)
 {
-    const rf_env_config &h = ctx->env_host;
-    RF_REQUIRE(ctx->env_cfg.task == rf::kEnvTaskSteps, "%s: the context is configured for ContinuousJumps (%s_jumps)", fn,
-               fn);
-    for (int i = 0; i < h.n; ++i)
-        RF_REQUIRE(actions[i] >= 0 && actions[i] < h.n_actions, "%s: action %d of env %d out of range", fn, actions[i], i);
+    const int task = ctx->env_cfg.task;
+    RF_REQUIRE(task == rf::kEnvTaskSteps || (task == rf::kEnvTaskComposed && composed_discrete(ctx)),
+               "%s: the context takes float32 actions (%s_jumps)", fn, fn);
+    const int n_actions = task == rf::kEnvTaskComposed ? ctx->env_program.n_actions : ctx->env_host.n_actions;
+    for (int i = 0; i < ctx->env_host.n; ++i)
+        RF_REQUIRE(actions[i] >= 0 && actions[i] < n_actions, "%s: action %d of env %d out of range", fn, actions[i], i);
     return RF_OK;
 }
 
 int check_actions(const rf_ctx *ctx, const float *actions, const char *fn)
 {
-    RF_REQUIRE(ctx->env_cfg.task == rf::kEnvTaskJumps, "%s: the context is configured for DiscreteSteps (int32 actions)",
-               fn);
-    for (int i = 0; i < ctx->env_host.n; ++i)
-        RF_REQUIRE(actions[i] >= -1.0f && actions[i] <= 1.0f, "%s: action %g of env %d outside [-1, 1]", fn,
-                   (double)actions[i], i); // (false for NaN)
+    const int task = ctx->env_cfg.task;
+    RF_REQUIRE(task == rf::kEnvTaskJumps || (task == rf::kEnvTaskComposed && !composed_discrete(ctx)),
+               "%s: the context takes int32 actions", fn);
+    const bool jump = task == rf::kEnvTaskJumps || ctx->env_program.transformer == RF_TRANSFORM_CONTINUOUS_JUMP;
+    for (int i = 0; i < ctx->env_host.n; ++i) {
+        if (jump)
+            RF_REQUIRE(actions[i] >= -1.0f && actions[i] <= 1.0f, "%s: action %g of env %d outside [-1, 1]", fn,
+                       (double)actions[i], i); // (false for NaN)
+        else
+            RF_REQUIRE(isfinite(actions[i]), "%s: action %g of env %d is not finite", fn, (double)actions[i], i);
+    }
     return RF_OK;
 }
 
-int env_configure(rf_ctx *ctx, const rf_env_config *cfg, int task, float stop_threshold)
+// A postfix list over n_leaves leaves: every leaf exactly once, two operands for every operation, one value left.
+bool postfix_ok(const int *ops, int n_ops, int n_leaves)
+{
+    if (n_leaves < 1 || n_leaves > RF_ENV_MAX_LEAVES || n_ops != 2 * n_leaves - 1)
+        return false;
+    unsigned seen = 0;
+    int depth = 0;
+    for (int t = 0; t < n_ops; ++t) {
+        const int op = ops[t];
+        if (op >= 0) {
+            if (op >= n_leaves || (seen >> op) & 1u)
+                return false;
+            seen |= 1u << op;
+            ++depth;
+        } else {
+            if ((op != -1 && op != -2) || depth < 2)
+                return false;
+            --depth;
+        }
+    }
+    return depth == 1;
+}
+
+bool finite_all(const double *v, int n)
+{
+    for (int i = 0; i < n; ++i)
+        if (!isfinite(v[i]))
+            return false;
+    return true;
+}
+
+int check_program(const rf_env_program *p)
+{
+    auto state_index = [](int i) { return i == 0 || i == 1; };
+    const int t = p->transformer;
+    RF_REQUIRE(t >= RF_TRANSFORM_CONTINUOUS_JUMP && t <= RF_TRANSFORM_DISCRETE_MOVE,
+               "rf_env_configure_composed: unknown transformer %d", t);
+    RF_REQUIRE(state_index(p->move_index), "rf_env_configure_composed: move_index %d outside {0, 1}", p->move_index);
+    const double params[4] = {p->limit_lo, p->limit_hi, p->speed, p->stop_threshold};
+    RF_REQUIRE(finite_all(params, 4), "rf_env_configure_composed: a transformer parameter is not finite");
+    if (t == RF_TRANSFORM_DISCRETE_JUMP || t == RF_TRANSFORM_DISCRETE_MOVE) {
+        RF_REQUIRE(p->n_actions >= 1 && p->n_actions <= 32, "rf_env_configure_composed: n_actions %d outside [1, 32]",
+                   p->n_actions);
+        RF_REQUIRE(finite_all(p->action_set, p->n_actions), "rf_env_configure_composed: an action is not finite");
+    }
+    RF_REQUIRE(p->n_enders >= 1 && p->n_enders <= RF_ENV_MAX_LEAVES && p->n_rewarders >= 1 &&
+                   p->n_rewarders <= RF_ENV_MAX_LEAVES,
+               "rf_env_configure_composed: %d enders, %d rewarders (1 to %d each)", p->n_enders, p->n_rewarders,
+               RF_ENV_MAX_LEAVES);
+    RF_REQUIRE(postfix_ok(p->ender_ops, p->n_ender_ops, p->n_enders),
+               "rf_env_configure_composed: the enders' postfix list is malformed");
+    RF_REQUIRE(postfix_ok(p->reward_ops, p->n_reward_ops, p->n_rewarders),
+               "rf_env_configure_composed: the rewarders' postfix list is malformed");
+    for (int i = 0; i < p->n_enders; ++i) {
+        const rf_env_ender &l = p->enders[i];
+        RF_REQUIRE(l.kind >= RF_ENDER_DIVERGING && l.kind <= RF_ENDER_TIME_LIMIT,
+                   "rf_env_configure_composed: ender %d: unknown kind %d", i, l.kind);
+        RF_REQUIRE(state_index(l.index0) && state_index(l.index1),
+                   "rf_env_configure_composed: ender %d: index outside {0, 1}", i);
+        RF_REQUIRE(isfinite(l.threshold), "rf_env_configure_composed: ender %d: parameter not finite", i);
+        RF_REQUIRE(l.kind != RF_ENDER_STOPPED || (l.steps >= 0 && l.steps <= RF_ENV_MAX_STOPPED_STEPS),
+                   "rf_env_configure_composed: ender %d: StoppedEnder steps %d outside [0, %d]", i, l.steps,
+                   RF_ENV_MAX_STOPPED_STEPS);
+    }
+    // every node's dtype: float64 for OnTarget / Stopped, float32 for the others, numpy's promotion for an operation
+    unsigned stack = 0;
+    for (int k = 0; k < p->n_reward_ops; ++k) {
+        const int op = p->reward_ops[k];
+        unsigned f64;
+        if (op >= 0) {
+            const int kind = p->rewarders[op].kind;
+            f64 = (kind == RF_REWARD_ON_TARGET || kind == RF_REWARD_STOPPED) ? 1u : 0u;
+            stack = (stack << 1) | f64;
+        } else {
+            f64 = (stack | (stack >> 1)) & 1u;
+            stack = ((stack >> 2) << 1) | f64;
+        }
+        RF_REQUIRE(p->reward_f64[k] == (int)f64, "rf_env_configure_composed: reward_f64[%d] is not numpy's promotion", k);
+    }
+    for (int i = 0; i < p->n_rewarders; ++i) {
+        const rf_env_rewarder &l = p->rewarders[i];
+        RF_REQUIRE(l.kind >= RF_REWARD_DELTA && l.kind <= RF_REWARD_STOPPED,
+                   "rf_env_configure_composed: rewarder %d: unknown kind %d", i, l.kind);
+        if (l.kind == RF_REWARD_OBSERVATION)
+            RF_REQUIRE(l.index0 >= 0 && l.index0 < 4, "rf_env_configure_composed: rewarder %d: observation index %d "
+                       "outside 0-3", i, l.index0);
+        else
+            RF_REQUIRE(state_index(l.index0) && state_index(l.index1),
+                       "rf_env_configure_composed: rewarder %d: index outside {0, 1}", i);
+        RF_REQUIRE(finite_all(l.p, 3), "rf_env_configure_composed: rewarder %d: parameter not finite", i);
+    }
+    return RF_OK;
+}
+
+// the kernels' form of a checked program (rf::EnvProgram): parameters rounded to what numpy computes them in
+rf::EnvProgram device_program(const rf_env_program &h)
+{
+    rf::EnvProgram d{};
+    d.transformer = h.transformer;
+    d.move_index = h.move_index;
+    d.n_actions = h.n_actions;
+    d.limit_lo = (float)h.limit_lo;
+    d.limit_hi = (float)h.limit_hi;
+    d.jump_span = (float)(h.limit_hi - h.limit_lo);
+    d.speed = (float)h.speed;
+    d.stop_threshold = (float)h.stop_threshold;
+    for (int i = 0; i < 32; ++i) {
+        d.move64[i] = h.action_set[i];
+        d.jump32[i] = (float)h.action_set[i];
+    }
+    d.n_enders = h.n_enders;
+    d.n_ender_ops = h.n_ender_ops;
+    d.n_rewarders = h.n_rewarders;
+    d.n_reward_ops = h.n_reward_ops;
+    int rows = 0;
+    for (int i = 0; i < h.n_enders; ++i) {
+        const rf_env_ender &l = h.enders[i];
+        d.enders[i] = rf::EnvEnderLeaf{l.kind, l.index0, l.index1, l.steps, (float)l.threshold, rows};
+        if (l.kind == RF_ENDER_STOPPED)
+            rows += l.steps + 1;
+    }
+    d.history_rows = rows;
+    for (int i = 0; i < h.n_rewarders; ++i) {
+        const rf_env_rewarder &l = h.rewarders[i];
+        rf::EnvRewardLeaf &r = d.rewarders[i];
+        r.kind = l.kind;
+        r.i0 = l.index0;
+        r.i1 = l.index1;
+        for (int k = 0; k < 3; ++k)
+            r.f[k] = (float)l.p[k];
+        r.d[0] = l.p[1]; // OnTarget: on - off | Stopped: reward
+        r.d[1] = l.p[2]; // OnTarget: off
+    }
+    for (int k = 0; k < RF_ENV_MAX_OPS; ++k) {
+        d.ender_ops[k] = h.ender_ops[k];
+        d.reward_ops[k] = h.reward_ops[k];
+        d.reward_f64[k] = h.reward_f64[k];
+    }
+    return d;
+}
+
+int env_configure(rf_ctx *ctx, const rf_env_config *cfg, int task, float stop_threshold,
+                  const rf_env_program *program = nullptr)
 {
     RF_REQUIRE(cfg->frame_height > 0 && cfg->spp > 0, "rf_env_configure: frame_height, spp must be positive");
     RF_REQUIRE(cfg->gray_mode == RF_GRAY_15BIT || cfg->gray_mode == RF_GRAY_14BIT, "rf_env_configure: gray_mode");
@@ -81,6 +238,12 @@ int env_configure(rf_ctx *ctx, const rf_env_config *cfg, int task, float stop_th
                  o_oldw = take(n * 8), o_oldf = take(n * 4), o_cam = take(n * 36), o_rect = take(n * 8),
                  o_cam2 = take(n * 36), o_rect2 = take(n * 8), o_didx = take(n * 4), o_done = take(n), o_sums2 = take(n * 16),
                  o_drank = take(n * 4);
+    // kEnvTaskComposed: the program, then the per-leaf strategy state ([leaf][n] each)
+    const rf::EnvProgram prog = program ? device_program(*program) : rf::EnvProgram{};
+    const size_t n_enders = program ? (size_t)program->n_enders : 0, n_rewarders = program ? (size_t)program->n_rewarders : 0;
+    const size_t o_prog = take(program ? sizeof(rf::EnvProgram) : 0), o_count = take(n_enders * n * 4),
+                 o_float = take(n_enders * n * 4), o_hist = take((size_t)prog.history_rows * n * 4),
+                 o_old = take(n_rewarders * n * 4);
     const EnvIo io(n);
     const size_t o_io = take(io.bytes);
     RF_HIP(dev_malloc(&ctx->env_block, off));
@@ -105,6 +268,18 @@ int env_configure(rf_ctx *ctx, const rf_env_config *cfg, int task, float stop_th
     s.done = (uint8_t *)(base + o_done);
     s.sums2 = (unsigned long long *)(base + o_sums2);
     s.done_rank = (int *)(base + o_drank);
+    s.program = program ? (const rf::EnvProgram *)(base + o_prog) : nullptr;
+    s.leaf_count = program ? (int *)(base + o_count) : nullptr;
+    s.leaf_float = program ? (float *)(base + o_float) : nullptr;
+    s.history = program ? (float *)(base + o_hist) : nullptr;
+    s.leaf_old = program ? (float *)(base + o_old) : nullptr;
+    if (program) {
+        ctx->env_program = *program;
+        RF_HIP(hipMemcpyAsync(base + o_prog, &prog, sizeof(prog), hipMemcpyHostToDevice, ctx->stream));
+        RF_HIP(hipStreamSynchronize(ctx->stream)); // (prog lives on this stack frame)
+    } else {
+        ctx->env_program = rf_env_program{};
+    }
     ctx->d_actions = (int *)(base + o_io + io.o_actions);
     ctx->d_pool = (float *)(base + o_io + io.o_pool);
 
@@ -186,6 +361,41 @@ int rf_env_configure_jumps(rf_ctx *ctx, const rf_env_config *cfg, float stop_thr
     RF_REQUIRE(isfinite(stop_threshold) && stop_threshold >= 0.0f, "rf_env_configure_jumps: stop_threshold");
     RF_HIP(hipSetDevice(ctx->device));
     return env_configure(ctx, cfg, rf::kEnvTaskJumps, stop_threshold);
+}
+
+int rf_env_configure_composed(rf_ctx *ctx, const rf_env_config *cfg, const rf_env_program *program)
+{
+    RF_REQUIRE(ctx != nullptr && cfg != nullptr && program != nullptr, "rf_env_configure_composed: NULL argument");
+    RF_REQUIRE(cfg->n > 0, "rf_env_configure_composed: bad n");
+    if (int rc = check_program(program))
+        return rc;
+    RF_HIP(hipSetDevice(ctx->device));
+    return env_configure(ctx, cfg, rf::kEnvTaskComposed, 0.0f, program);
+}
+
+int rf_env_get_strategy_state(rf_ctx *ctx, int32_t *host_counters, float *host_floats, float *host_histories,
+                              float *host_old)
+{
+    RF_REQUIRE(ctx != nullptr, "rf_env_get_strategy_state: ctx is NULL");
+    RF_REQUIRE(ctx->env_ready && ctx->env_cfg.task == rf::kEnvTaskComposed,
+               "rf_env_get_strategy_state: rf_env_configure_composed first");
+    RF_HIP(hipSetDevice(ctx->device));
+    const rf_env_program &p = ctx->env_program;
+    const size_t n = (size_t)ctx->env_host.n;
+    size_t rows = 0;
+    for (int i = 0; i < p.n_enders; ++i)
+        rows += p.enders[i].kind == RF_ENDER_STOPPED ? (size_t)p.enders[i].steps + 1 : 0;
+    const rf::EnvState &s = ctx->env;
+    if (host_counters)
+        RF_HIP(hipMemcpyAsync(host_counters, s.leaf_count, p.n_enders * n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (host_floats)
+        RF_HIP(hipMemcpyAsync(host_floats, s.leaf_float, p.n_enders * n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (host_histories && rows)
+        RF_HIP(hipMemcpyAsync(host_histories, s.history, rows * n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (host_old)
+        RF_HIP(hipMemcpyAsync(host_old, s.leaf_old, p.n_rewarders * n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    RF_HIP(hipStreamSynchronize(ctx->stream));
+    return RF_OK;
 }
 
 int rf_env_reset(rf_ctx *ctx, const float *host_states, float *host_obs)

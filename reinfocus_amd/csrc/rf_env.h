@@ -1,4 +1,4 @@
-// rf_env.h -- device-resident DiscreteSteps-v0 and ContinuousJumps step.
+// rf_env.h -- device-resident DiscreteSteps-v0, ContinuousJumps and composed step.
 //
 // The O(N) numpy glue the reference runs on the host every step --
 //   DiscreteMoveTransformer.transform      environments/state_transformer.py:248-266
@@ -9,6 +9,8 @@
 //   Delta + Observation + OnTarget reward  environments/episode_rewarder.py:130-155, :226-292
 //   (Observation + Stopped * OnTarget      environments/episode_rewarder.py:226-292, :361-429, kEnvTaskJumps)
 //   same-step auto-reset                   environments/vector_environment.py:137-151
+//   (any transformer, ender and rewarder tree of state_transformer.py / episode_ender.py / episode_rewarder.py,
+//    EnvConfig::task == kEnvTaskComposed: the interpreter of EnvProgram below)
 // -- as two small kernels around the render and focus kernels, so that a step moves only the
 // actions and a pool of candidate reset states to the GPU and the observations / rewards /
 // flags back.  Arithmetic follows the numpy expressions operation by operation (float32
@@ -19,6 +21,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/reinfocus_hip.h"
+#include "rf_common.h"
 #include "rf_env_types.h"
 #include "rf_math.h"
 
@@ -50,11 +54,240 @@ __device__ __forceinline__ void pack_scene(const EnvConfig &c, float target, flo
     rc[1] = -target;
 }
 
+// ---- kEnvTaskComposed: a small interpreter of the strategy program (EnvProgram) ------------------------------------
+// The reference's strategy classes (state_transformer.py, episode_ender.py, episode_rewarder.py) operation by operation:
+// float32 state arithmetic with the Python-scalar parameters rounded to float32 (the program holds them so), float64
+// where numpy promotes to it.  Per-leaf state is leaf-major: [leaf][n].
+
+__device__ __forceinline__ const_as<EnvProgram> &env_program(const EnvState &s)
+{
+    return *as_const(s.program);
+}
+
+// st[i] / obs[i] for a program index by selects (a dynamic index would put the small arrays in scratch memory)
+__device__ __forceinline__ float pick2(const float st[2], int i)
+{
+    return i ? st[1] : st[0];
+}
+
+__device__ __forceinline__ float pick4(const float v[4], int i)
+{
+    return i == 0 ? v[0] : i == 1 ? v[1] : i == 2 ? v[2] : v[3];
+}
+
+__device__ __forceinline__ float clip_limits(const_as<EnvProgram> &p, float v)
+{
+    return fminf(fmaxf(v, p.limit_lo), p.limit_hi); // numpy.clip(states, *limits) = minimum(maximum(x, lo), hi)
+}
+
+// transformer.transform for one environment; `action` is the 4-byte slot (int32 index or float32 action)
+__device__ __forceinline__ void composed_transform(const_as<EnvProgram> &p, float st[2], int action)
+{
+    const int mi = p.move_index;
+    float x = pick2(st, mi);
+    const float a = __builtin_bit_cast(float, action);
+    switch (p.transformer) {
+    case RF_TRANSFORM_CONTINUOUS_JUMP: { // (a + 1) / 2.0 * (hi - lo) + lo, taken where farther than the threshold; no clip
+        const float m = (a + 1.0f) / 2.0f * p.jump_span + p.limit_lo;
+        if (fabsf(x - m) > p.stop_threshold) {
+            st[0] = mi ? st[0] : m;
+            st[1] = mi ? m : st[1];
+        }
+        return;
+    }
+    case RF_TRANSFORM_CONTINUOUS_MOVE: { // clip(a, -1, 1) * speed, added as (|move| > threshold) * move
+        const float m = fminf(fmaxf(a, -1.0f), 1.0f) * p.speed;
+        x = x + (fabsf(m) > p.stop_threshold ? 1.0f : 0.0f) * m;
+        break;
+    }
+    case RF_TRANSFORM_DISCRETE_JUMP:
+        x = p.jump32[action];
+        break;
+    default: // RF_TRANSFORM_DISCRETE_MOVE: float32 += float64 rounds the float64 sum
+        x = (float)((double)x + p.move64[action]);
+        break;
+    }
+    st[0] = clip_limits(p, mi ? st[0] : x);
+    st[1] = clip_limits(p, mi ? x : st[1]);
+}
+
+// is_truncated of ender leaf i (its state after the step)
+__device__ __forceinline__ bool composed_leaf_truncated(const EnvConfig &c, const EnvState &s, const_as<EnvProgram> &p,
+                                                        int i, int e)
+{
+    const size_t at = (size_t)i * c.n + e;
+    switch (p.enders[i].kind) {
+    case RF_ENDER_ENDLESS:
+        return false;
+    case RF_ENDER_STOPPED: { // a full history (no NaN) whose span nanmax - nanmin is below early_end_span
+        const int rows = p.enders[i].steps + 1, first = p.enders[i].history;
+        float lo = s.history[(size_t)first * c.n + e], hi = lo;
+        bool full = !isnan(lo);
+        for (int k = 1; k < rows; ++k) {
+            const float v = s.history[(size_t)(first + k) * c.n + e];
+            full = full && !isnan(v);
+            lo = fminf(lo, v);
+            hi = fmaxf(hi, v);
+        }
+        return full && hi - lo < p.enders[i].threshold;
+    }
+    default: // Diverging, OnTarget, TimeLimit: counter >= steps
+        return s.leaf_count[at] >= p.enders[i].steps;
+    }
+}
+
+// the ender tree's is_truncated: the postfix list over the leaves' flags (a bit stack: | and & of numpy bools)
+__device__ __forceinline__ bool composed_truncated(const EnvConfig &c, const EnvState &s, const_as<EnvProgram> &p, int e)
+{
+    unsigned stack = 0;
+    for (int t = 0; t < p.n_ender_ops; ++t) {
+        const int op = p.ender_ops[t];
+        if (op >= 0) {
+            stack = (stack << 1) | (composed_leaf_truncated(c, s, p, op, e) ? 1u : 0u);
+        } else {
+            const unsigned b = stack & 1u, a = (stack >> 1) & 1u;
+            stack = ((stack >> 2) << 1) | (op == RF_OP_OR ? (a | b) : (a & b));
+        }
+    }
+    return stack & 1u;
+}
+
+// ender.step for one environment (episode_ender.py: every leaf, whatever the tree's operations)
+__device__ __forceinline__ void composed_enders_step(const EnvConfig &c, const EnvState &s, const_as<EnvProgram> &p,
+                                                     const float st[2], int e)
+{
+    for (int i = 0; i < p.n_enders; ++i) {
+        const size_t at = (size_t)i * c.n + e;
+        const float diff = fabsf(pick2(st, p.enders[i].i0) - pick2(st, p.enders[i].i1));
+        switch (p.enders[i].kind) {
+        case RF_ENDER_DIVERGING:
+            if (diff > s.leaf_float[at] + p.enders[i].threshold)
+                s.leaf_count[at] += 1;
+            s.leaf_float[at] = diff;
+            break;
+        case RF_ENDER_ON_TARGET:
+            s.leaf_count[at] = diff < p.enders[i].threshold ? s.leaf_count[at] + 1 : 0;
+            break;
+        case RF_ENDER_TIME_LIMIT:
+            s.leaf_count[at] += 1;
+            break;
+        case RF_ENDER_STOPPED: { // Histories.append_events: shift left by one, newest last
+            const int rows = p.enders[i].steps + 1, first = p.enders[i].history;
+            for (int k = 0; k + 1 < rows; ++k)
+                s.history[(size_t)(first + k) * c.n + e] = s.history[(size_t)(first + k + 1) * c.n + e];
+            s.history[(size_t)(first + rows - 1) * c.n + e] = pick2(st, p.enders[i].i0);
+            break;
+        }
+        default: // Endless
+            break;
+        }
+    }
+}
+
+// ender.reset for one environment that starts an episode in state st
+__device__ __forceinline__ void composed_enders_reset(const EnvConfig &c, const EnvState &s, const_as<EnvProgram> &p,
+                                                      const float st[2], int e)
+{
+    for (int i = 0; i < p.n_enders; ++i) {
+        const size_t at = (size_t)i * c.n + e;
+        s.leaf_count[at] = 0;
+        if (p.enders[i].kind == RF_ENDER_DIVERGING)
+            s.leaf_float[at] = fabsf(pick2(st, p.enders[i].i0) - pick2(st, p.enders[i].i1));
+        if (p.enders[i].kind == RF_ENDER_STOPPED) { // Histories.reset, then the episode's first state as its first event
+            const int rows = p.enders[i].steps + 1, first = p.enders[i].history;
+            for (int k = 0; k + 1 < rows; ++k)
+                s.history[(size_t)(first + k) * c.n + e] = __builtin_nanf("");
+            s.history[(size_t)(first + rows - 1) * c.n + e] = pick2(st, p.enders[i].i0);
+        }
+    }
+}
+
+// rewarder.reset for one environment: Delta / Stopped remember the element's value
+__device__ __forceinline__ void composed_rewarders_reset(const EnvConfig &c, const EnvState &s, const_as<EnvProgram> &p,
+                                                         const float st[2], int e)
+{
+    for (int i = 0; i < p.n_rewarders; ++i)
+        if (p.rewarders[i].kind == RF_REWARD_DELTA || p.rewarders[i].kind == RF_REWARD_STOPPED)
+            s.leaf_old[(size_t)i * c.n + e] = pick2(st, p.rewarders[i].i0);
+}
+
+// reward of rewarder leaf i, carried as a double (a float32 term computes in float32: widening it is exact)
+__device__ __forceinline__ double composed_leaf_reward(const EnvConfig &c, const EnvState &s, const_as<EnvProgram> &p,
+                                                       const float st[2], const float obs[4], int i, int e)
+{
+    const_as<EnvRewardLeaf> &r = p.rewarders[i];
+    const size_t at = (size_t)i * c.n + e;
+    switch (r.kind) {
+    case RF_REWARD_DELTA: { // abs(x - old) * reward / scale, float32
+        const float v = fabsf(pick2(st, r.i0) - s.leaf_old[at]) * r.f[0] / r.f[1];
+        s.leaf_old[at] = pick2(st, r.i0);
+        return v;
+    }
+    case RF_REWARD_DISTANCE: // (1 - abs(a - b) / span) * (high - low) + low, float32
+        return (1.0f - fabsf(pick2(st, r.i0) - pick2(st, r.i1)) / r.f[0]) * r.f[1] + r.f[2];
+    case RF_REWARD_OBSERVATION:
+        return pick4(obs, r.i0);
+    case RF_REWARD_ON_TARGET: // (abs(a - b) < span) * (on - off) + off, float64
+        return (fabsf(pick2(st, r.i0) - pick2(st, r.i1)) < r.f[0] ? 1.0 : 0.0) * r.d[0] + r.d[1];
+    default: { // RF_REWARD_STOPPED: (abs(x - old) < threshold) * reward, float64
+        const double v = (fabsf(pick2(st, r.i0) - s.leaf_old[at]) < r.f[0] ? 1.0 : 0.0) * r.d[0];
+        s.leaf_old[at] = pick2(st, r.i0);
+        return v;
+    }
+    }
+}
+
+// the rewarder tree: every leaf once, in leaf order, then the postfix list of + / * (each node in its own dtype)
+__device__ __forceinline__ double composed_reward(const EnvConfig &c, const EnvState &s, const_as<EnvProgram> &p,
+                                                  const float st[2], const float obs[4], int e)
+{
+    double leaf[kEnvMaxLeaves];
+#pragma unroll
+    for (int i = 0; i < kEnvMaxLeaves; ++i)
+        leaf[i] = i < p.n_rewarders ? composed_leaf_reward(c, s, p, st, obs, i, e) : 0.0;
+    double stack[kEnvMaxLeaves];
+    int sp = 0;
+    for (int t = 0; t < p.n_reward_ops; ++t) {
+        const int op = p.reward_ops[t];
+        if (op >= 0) {
+            stack[sp++] = leaf[op];
+            continue;
+        }
+        const double b = stack[--sp], a = stack[sp - 1];
+        double v;
+        if (p.reward_f64[t])
+            v = op == RF_OP_ADD ? a + b : a * b;
+        else
+            v = op == RF_OP_ADD ? (double)((float)a + (float)b) : (double)((float)a * (float)b);
+        stack[sp - 1] = v;
+    }
+    return stack[0];
+}
+
 // transformer -> ender.step -> scene of every env (vector_environment.py:124-126 + the
 // update_targets / update_focus_planes of FocusObserver.observe)
 __device__ __forceinline__ void env_pre_one(const EnvConfig &c, const EnvState &s, const int *actions, int e)
 {
     float target = s.state[2 * e], focus = s.state[2 * e + 1];
+    if (c.task == kEnvTaskComposed) {
+        // The reference's enders read the state only, never observations (episode_ender.py), so which environments end
+        // is settled here for every composition too: the fused step's ranking before the render still holds.
+        const_as<EnvProgram> &p = env_program(s);
+        float st[2] = {target, focus};
+        if (actions) {
+            composed_transform(p, st, actions[e]);
+            s.state[2 * e] = st[0];
+            s.state[2 * e + 1] = st[1];
+            composed_enders_step(c, s, p, st, e);
+            s.done[e] = composed_truncated(c, s, p, e) ? 1 : 0;
+        } else {
+            composed_enders_reset(c, s, p, st, e);
+        }
+        pack_scene(c, st[0], st[1], s.cam_dyn + 9 * e, s.rect + 2 * e);
+        s.sums[2 * e] = 0;
+        s.sums[2 * e + 1] = 0;
+        return;
+    }
     if (actions && c.task == kEnvTaskJumps) {
         // ContinuousJumpTransformer (state_transformer.py:95-118), float32 throughout: a1 = (a + 1) / 2.0,
         // m = a1 * (hi - lo) + lo, the focus plane jumps to m where |focus - m| > stop_threshold; no clip
@@ -125,6 +358,22 @@ __device__ __forceinline__ void env_post_one(const EnvConfig &c, const EnvState 
     s.obs[4 * e + 1] = o1;
     s.obs[4 * e + 2] = o2;
     s.obs[4 * e + 3] = o3;
+    if (c.task == kEnvTaskComposed) {
+        const_as<EnvProgram> &p = env_program(s);
+        const float st[2] = {target, focus}, obs[4] = {o0, o1, o2, o3};
+        if (first) {
+            composed_rewarders_reset(c, s, p, st, e);
+            s.truncated[e] = 0;
+            s.done[e] = 0;
+            s.reward[e] = 0.0;
+            return;
+        }
+        s.reward[e] = composed_reward(c, s, p, st, obs, e);
+        const bool trunc = composed_truncated(c, s, p, e);
+        s.truncated[e] = trunc ? 1 : 0;
+        s.done[e] = trunc ? 1 : 0;
+        return;
+    }
     if (first) {
         s.old_focus[e] = focus;
         s.truncated[e] = 0;
@@ -172,11 +421,16 @@ __global__ void env_post_kernel(EnvConfig c, EnvState s, const double *focus_val
 // `actions` != null in a ranking mode: the transformer / ender work of env_pre_kernel first.
 constexpr int kEnvResetBoth = 0, kEnvResetRank = 1, kEnvResetApply = 2, kEnvResetPlan = 3, kEnvResetPack = 4;
 
-__device__ __forceinline__ void env_apply_state(const EnvState &s, const float *pool, int r, int e)
+__device__ __forceinline__ void env_apply_state(const EnvConfig &c, const EnvState &s, const float *pool, int r, int e)
 {
     const float target = pool[2 * r], focus = pool[2 * r + 1];
     s.state[2 * e] = target;
     s.state[2 * e + 1] = focus;
+    if (c.task == kEnvTaskComposed) {
+        const float st[2] = {target, focus};
+        composed_enders_reset(c, s, env_program(s), st, e);
+        return;
+    }
     s.steps[e] = 0;
     s.diverging[e] = 0;
     s.last_diff[e] = fabsf(target - focus);
@@ -184,7 +438,7 @@ __device__ __forceinline__ void env_apply_state(const EnvState &s, const float *
 
 __device__ __forceinline__ void env_apply_reset(const EnvConfig &c, const EnvState &s, const float *pool, int r, int e)
 {
-    env_apply_state(s, pool, r, e);
+    env_apply_state(c, s, pool, r, e);
     pack_scene(c, pool[2 * r], pool[2 * r + 1], s.cam_dyn2 + 9 * r, s.rect2 + 2 * r);
 }
 
@@ -279,7 +533,7 @@ __device__ __forceinline__ void env_reset_post_one(const EnvConfig &c, const Env
                                                    const float *planned_pool, int r, int e)
 {
     if (planned_pool)
-        env_apply_state(s, planned_pool, r, e);
+        env_apply_state(c, s, planned_pool, r, e);
     const float focus = s.state[2 * e + 1];
     const float w0 = focus,
                 w1 = (float)(focus_values ? focus_values[r] : env_variance(c, planned_pool ? s.sums2 : s.sums, r));
@@ -289,6 +543,11 @@ __device__ __forceinline__ void env_reset_post_one(const EnvConfig &c, const Env
     s.obs[4 * e + 1] = normalize1(c, 1, w1);
     s.obs[4 * e + 2] = normalize1(c, 2, 0.0f);
     s.obs[4 * e + 3] = normalize1(c, 3, 0.0f);
+    if (c.task == kEnvTaskComposed) {
+        const float st[2] = {s.state[2 * e], focus};
+        composed_rewarders_reset(c, s, env_program(s), st, e);
+        return;
+    }
     s.old_focus[e] = focus;
 }
 

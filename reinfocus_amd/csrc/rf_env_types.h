@@ -10,9 +10,45 @@ namespace rf {
 // transformer and the rewarder only.  The branch is on a kernel argument: uniform over every launch.
 constexpr int kEnvTaskSteps = 0; // DiscreteSteps-v0: int32 action indices into action_set, Delta + Observation + OnTarget
 constexpr int kEnvTaskJumps = 1; // ContinuousJumps-v0: float32 actions in [-1, 1], Observation + Stopped * OnTarget
+constexpr int kEnvTaskComposed = 2; // any composition of the reference's strategy classes: EnvState::program
+
+// The strategy program of kEnvTaskComposed (rf_env_program, include/reinfocus_hip.h), as the kernels read it: uploaded
+// once by rf_env_configure_composed, with every parameter already rounded to the type numpy computes it in.  Every
+// thread reads the same entries (through the constant address space: scalar loads).  EnvConfig, which every launch
+// takes by value and the replayed graphs capture, does not grow.
+constexpr int kEnvMaxLeaves = 8, kEnvMaxOps = 2 * kEnvMaxLeaves - 1;
+
+struct EnvEnderLeaf {
+    int kind, i0, i1, steps; // RF_ENDER_*, check indices, early_end_steps / max_steps
+    float threshold;         // float32(threshold / early_end_radius / early_end_span)
+    int history;             // StoppedEnder: first row of its history in EnvState::history (steps + 1 rows)
+};
+
+struct EnvRewardLeaf {
+    int kind, i0, i1;        // RF_REWARD_*, check indices / observation index
+    float f[3];              // float32 parameters: Delta reward, scale | Distance span, high - low, low | OnTarget span
+                             // | Stopped threshold
+    double d[2];             // float64 parameters: OnTarget on - off, off | Stopped reward
+};
+
+struct EnvProgram {
+    int transformer, move_index, n_actions;
+    float limit_lo, limit_hi;       // float32(limits): the clip limits; ContinuousJump: limit_lo is where a jump starts
+    float jump_span;                // ContinuousJump: float32(hi - lo), the difference taken in float64
+    float speed, stop_threshold;    // float32
+    double move64[32];              // DiscreteMove
+    float jump32[32];               // DiscreteJump
+    int n_enders, n_ender_ops, n_rewarders, n_reward_ops;
+    EnvEnderLeaf enders[kEnvMaxLeaves];
+    int ender_ops[kEnvMaxOps];
+    EnvRewardLeaf rewarders[kEnvMaxLeaves];
+    int reward_ops[kEnvMaxOps];
+    int reward_f64[kEnvMaxOps];
+    int history_rows;               // rows of EnvState::history
+};
 
 struct EnvConfig {
-    int task;                 // kEnvTaskSteps / kEnvTaskJumps
+    int task;                 // kEnvTaskSteps / kEnvTaskJumps / kEnvTaskComposed
     int n;                    // environments
     int n_actions;
     double action_set[32];    // float64 moves (state_transformer.py:246 numpy.asarray(action_set))
@@ -49,6 +85,12 @@ struct EnvState {            // all device arrays, length n unless noted
     uint8_t *done;           // [n] scratch
     unsigned long long *sums; // [n][2] the focus measure's (sum, sum of squares): zeroed here before a measure, read after
     unsigned long long *sums2; // [n][2] the same for the re-rendered frames of a fused step (both measures are one launch there)
+    // kEnvTaskComposed only (null otherwise): the program and the per-leaf strategy state, leaf-major ([leaf][n])
+    const EnvProgram *program;
+    int *leaf_count;         // [n_enders][n] Diverging / OnTarget / TimeLimit counters
+    float *leaf_float;       // [n_enders][n] DivergingEnder._last_diff
+    float *history;          // [history_rows][n] StoppedEnder histories, oldest first, NaN where empty
+    float *leaf_old;         // [n_rewarders][n] Delta / Stopped: the element's previous value
 };
 
 } // namespace rf

@@ -97,6 +97,7 @@ struct rf_ctx {
     bool env_graph_fail_once = false; // REINFOCUS_ENV_GRAPH_FAIL=1 (tests): the first instantiation "fails"
     int env_last_branch = RF_ENV_BRANCH_NONE; // rf_env_last_step_branch
     bool env_needs_reset = false; // rf_env_step_abort dropped a half-finished step
+    rf_env_program env_program{}; // rf_env_configure_composed's program (host copy: action checks, strategy readback)
     bool env_fused = true; // the step's two renders and two focus measures as one launch each (REINFOCUS_ENV_FUSED=0: the
                            // three schedules of separate launches)
     long env_one_sync_max = 65536; // blocks of a full render up to which rf_env_step runs without the mid-step round

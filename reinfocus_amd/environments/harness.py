@@ -22,6 +22,10 @@ OnTargetRewarder) only; its vector form (VectorContinuousJumps, DeviceVectorCont
 ShardedVectorContinuousJumps) is what the reference's docstring prescribes for vectorising an
 environment (custom_environments.py:117-133): the same strategies with num_envs in place of 1, driven
 by VectorEnvironment with the vector DiscreteSteps' TimeLimitEnder | DivergingEnder.
+
+VectorEnvironment / DeviceVectorEnvironment go further: any composition of the reference's strategy classes
+(environments/state_transformer.py, episode_ender.py, episode_rewarder.py, state_initializer.py) around the same
+observer, on the host and with the whole step on the GPU (rf_env_configure_composed).
 """
 
 import numpy as np
@@ -507,12 +511,15 @@ class _DeviceShard:
     EARLY_END_STEPS = 3  # DivergingEnder(..., early_end_steps=3), custom_environments.py:186-190
 
     def __init__(self, num_envs, max_episode_steps, frame_height, samples_per_pixel, device, first_state_index,
-                 jumps=False):
+                 jumps=False, program=None, ends=None, max_move=None):
+        """program: an rf_env_program (rf_env_configure_composed) with the observer's `ends` and `max_move`."""
         import math
 
         from reinfocus_amd import _native, vision
         from reinfocus_amd.graphics import camera
 
+        ends = self.ENDS if ends is None else tuple(ends)
+        max_move = self.MAX_MOVE if max_move is None else max_move
         moves = self.MAX_MOVE / 2.0 ** np.arange(6)
         self.action_set = np.concatenate([-moves, [0], moves[::-1]])
         self.num_envs = num_envs
@@ -522,10 +529,10 @@ class _DeviceShard:
         self.max_episode_steps = max_episode_steps
         self.ctx = _native.Context(device)
         try:
-            min_focus, max_focus = state_observer.cached_focus_extrema(self.ENDS, frame_height, samples_per_pixel,
+            min_focus, max_focus = state_observer.cached_focus_extrema(ends, frame_height, samples_per_pixel,
                                                                        self.ctx.device)
             box = spaces.Box(min_focus, max_focus, dtype=np.float32)  # float32 rounding of the extrema
-            mid, scale = normaliser_constants(self.ENDS, self.MAX_MOVE, box.low[0], box.high[0])
+            mid, scale = normaliser_constants(ends, max_move, box.low[0], box.high[0])
             cams = camera.FastCameras()
             cfg = _native.EnvConfig()
             cfg.n = num_envs
@@ -554,7 +561,9 @@ class _DeviceShard:
             cfg.spp = samples_per_pixel
             cfg.gray_mode = vision.GRAY_MODE
             self.ctx.seed(num_envs * frame_height * frame_height, 0, self.first_state_index)
-            if jumps:  # (limit_lo / limit_hi: the range the focus plane jumps in)
+            if program is not None:
+                self.ctx.env_configure_composed(cfg, program)
+            elif jumps:  # (limit_lo / limit_hi: the range the focus plane jumps in)
                 self.ctx.env_configure_jumps(cfg, JUMP_STOP)
             else:
                 self.ctx.env_configure(cfg)
@@ -987,3 +996,199 @@ class ShardedVectorContinuousJumps(_ShardedVectorEnv):
     any shard begins when one of them is NaN, infinite or outside [-1, 1]."""
 
     _JUMPS = True
+
+
+def composed_actions(transformer, actions, num_envs, index_range=True):
+    """The actions of a composed environment's step, checked before any state changes (AssertionError): num_envs
+    integer indices in [0, n) for a discrete transformer; num_envs float32 values (also as [num_envs, 1]) for a
+    continuous one -- finite, and in [-1, 1] for a ContinuousJumpTransformer (jump_actions); a ContinuousMoveTransformer
+    clips finite values, as the reference does.  The device refuses the same (rf_env_configure_composed); the device
+    environment leaves the range of discrete indices to it (index_range=False), as DeviceVectorDiscreteSteps does."""
+    from reinfocus_amd.environments import state_transformer
+
+    if transformer.kind == state_transformer.CONTINUOUS_JUMP:
+        return jump_actions(actions, num_envs)
+    if transformer.kind == state_transformer.CONTINUOUS_MOVE:
+        actions = np.asarray(actions, dtype=np.float32)
+        if actions.shape not in ((num_envs,), (num_envs, 1)):
+            raise AssertionError(f"expected {num_envs} actions (shape ({num_envs},) or ({num_envs}, 1)), got {actions.shape}")
+        if not np.all(np.isfinite(actions)):
+            raise AssertionError("continuous actions must be finite")
+        return actions.reshape(num_envs)
+    actions = np.asarray(actions)
+    if actions.shape not in ((num_envs,), (num_envs, 1)) or not np.issubdtype(actions.dtype, np.integer):
+        raise AssertionError(f"expected {num_envs} integer actions, got {actions.dtype} {actions.shape}")
+    actions = actions.reshape(num_envs)
+    n = transformer.single_action_space.n
+    if index_range and actions.size and (actions.min() < 0 or actions.max() >= n):
+        raise AssertionError(f"action outside [0, {n})")
+    return actions
+
+
+class VectorEnvironment(_VectorEnvBase):
+    """A vector environment composed of the reference's strategy objects (vector_environment.py:19-176): an ender, an
+    initializer, a rewarder and a transformer from environments/episode_ender.py, state_initializer.py,
+    episode_rewarder.py and state_transformer.py, around the observer both tasks use --
+    NormalizedObserver(DeltaObserver([IndexedElementObserver(1), FocusObserver], True, [max_focus_move, nan])) over
+    states [target, focus plane] in `ends`.  The host twin: numpy glue around the GPU render and focus measure, in the
+    reference's call order, same-step auto-reset included.  Rewards are returned as float64.  Actions are checked before
+    any state changes (composed_actions).  `reset(seed=...)` reseeds the initializer; `state=` (extension) pins the
+    initial states.  DeviceVectorEnvironment is the same environment with the whole step on the GPU."""
+
+    metadata = {"render_modes": ["rgb_array"], "render_fps": 4}
+
+    def __init__(self, ender, initializer, rewarder, transformer, num_envs, ends=(5.0, 10.0), max_focus_move=5.0,
+                 render_mode=None, *, frame_height=300, samples_per_pixel=100, device=None):
+        super().__init__()
+        assert render_mode is None or render_mode in self.metadata["render_modes"]
+        self.render_mode = render_mode
+        self.num_envs = num_envs
+        self._ender = ender
+        self._initializer = initializer
+        self._rewarder = rewarder
+        self._transformer = transformer
+        self._renderer = render.FastRenderer(samples_per_pixel=samples_per_pixel, device=device)
+        self._focus_observer = state_observer.FocusObserver(num_envs, TARGET, FOCUS, ends, self._renderer,
+                                                            frame_height)
+        self._observer = _Observer(num_envs, ends, max_focus_move, self._focus_observer)
+        self._visualizer = episode_visualizer.HistoryVisualizer(num_envs, TARGET, FOCUS, 1, self._renderer, ends,
+                                                                ender=ender)
+        self.single_action_space = transformer.single_action_space
+        self.action_space = transformer.action_space
+        self.single_observation_space = self._observer.single_observation_space
+        self.observation_space = self._observer.observation_space
+        self._state = None
+
+    def reset(self, *, seed=None, options=None, state=None):
+        if seed is not None:
+            self._initializer.seed(seed)
+        self._state = (self._initializer.initialize(self.num_envs) if state is None
+                       else np.array(state, dtype=np.float32).reshape(self.num_envs, 2))
+        self._ender.reset(self._state)
+        observations = self._observer.reset(self._state, None)
+        self._rewarder.reset(self._state, observations)
+        if self.render_mode == "rgb_array":
+            self._visualizer.reset(self._state, observations)
+        return observations, {}
+
+    def step(self, actions):
+        assert self._state is not None
+        actions = composed_actions(self._transformer, actions, self.num_envs)
+        self._state = self._transformer.transform(self._state, actions)
+        self._ender.step(self._state)
+        observations = self._observer.observe(self._state)
+        rewards = self._rewarder.reward(self._state, observations)
+        terminated = self._ender.is_terminated()
+        truncated = self._ender.is_truncated()
+        done = terminated | truncated
+        if done.any():
+            new_state = self._initializer.initialize(done.sum())
+            self._state[done] = new_state
+            self._ender.reset(new_state, done)
+            new_observations = self._observer.reset(new_state, done)
+            observations[done] = new_observations
+            self._rewarder.reset(new_state, new_observations, done)
+            if self.render_mode == "rgb_array":
+                self._visualizer.reset(new_state, new_observations, done)
+        if self.render_mode == "rgb_array":
+            not_done = ~done
+            self._visualizer.step(self._state[not_done], observations[not_done], not_done)
+        return observations, np.asarray(rewards, dtype=np.float64), terminated, truncated, {}
+
+    def strategy_state(self):
+        """The per-leaf strategy state, laid out as DeviceVectorEnvironment.strategy_state returns it."""
+        from reinfocus_amd.environments import strategy_program
+
+        return strategy_program.host_strategy_state(self._ender, self._rewarder, self.num_envs)
+
+    def status(self, index):
+        return self._ender.status(index)
+
+    def render(self):
+        if self.render_mode == "rgb_array":
+            return self._visualizer.visualize()
+        return None
+
+    def render_frames(self):
+        return np.asarray(self._renderer.render(600))
+
+    def close(self):
+        self._renderer.close()
+
+
+class DeviceVectorEnvironment(_DeviceVectorEnv):
+    """VectorEnvironment with the whole step resident on the GPU (rf_env_configure_composed): the strategy objects are
+    compiled into a device program (strategy_program.compile_program: AssertionError for anything the device cannot
+    run) that every schedule of the DiscreteSteps step interprets; reset / step results equal VectorEnvironment's bit
+    for bit, with the same initializer consumption (propose, then initialize the rows that were used).  The strategy
+    objects only describe the environment here: their own state is not advanced (strategy_state() and status() read
+    the device's).  Discrete transformers step through the int32 calls, continuous ones through the float32 ones.
+    One device only: `devices=` (sharding) is refused."""
+
+    def __init__(self, ender, initializer, rewarder, transformer, num_envs, ends=(5.0, 10.0), max_focus_move=5.0,
+                 render_mode=None, *, frame_height=300, samples_per_pixel=100, device=None, first_state_index=0,
+                 devices=None):
+        from reinfocus_amd.environments import state_transformer, strategy_program
+
+        if devices is not None:
+            raise ValueError("DeviceVectorEnvironment runs on one device (device=); a composed environment cannot be "
+                             "sharded over several (devices=)")
+        _VectorEnvBase.__init__(self)
+        assert render_mode is None or render_mode in self.metadata["render_modes"]
+        program = strategy_program.compile_program(transformer, ender, rewarder, num_envs)
+        self.render_mode = render_mode
+        self.num_envs = num_envs
+        self._ender = ender
+        self._transformer = transformer
+        self._discrete = transformer.kind in (state_transformer.DISCRETE_JUMP, state_transformer.DISCRETE_MOVE)
+        self._shard = _DeviceShard(num_envs, None, frame_height, samples_per_pixel, device, first_state_index,
+                                   program=program, ends=ends, max_move=max_focus_move)
+        self._ctx = self._shard.ctx
+        self._limits = tuple(ends)
+        self._initializer = initializer
+        self.single_action_space = transformer.single_action_space
+        self.action_space = transformer.action_space
+        self.single_observation_space = spaces.Box(-np.ones(4, dtype=np.float32), np.ones(4, dtype=np.float32),
+                                                   dtype=np.float32)
+        self.observation_space = spaces.batch_space(self.single_observation_space, num_envs)
+        self._visualizer = None
+        if render_mode == "rgb_array":
+            self._visualizer = episode_visualizer.HistoryVisualizer(num_envs, TARGET, FOCUS, 1, self._shard,
+                                                                    self._limits, ender=self)
+
+    def strategy_state(self):
+        """(counters int32[n_enders, n], floats float32[n_enders, n], StoppedEnder histories float32[rows, n], old
+        values float32[n_rewarders, n]) from the device (rf_env_get_strategy_state)."""
+        return self._ctx.env_strategy_state()
+
+    def status(self, index):
+        """ender.status(index) from the device's strategy state."""
+        from reinfocus_amd.environments import strategy_program
+
+        return strategy_program.device_status(self._ender, self.strategy_state(), index)
+
+    def reset(self, *, seed=None, options=None, state=None):
+        if seed is not None:
+            self._initializer.seed(seed)
+        initial = (self._initializer.initialize(self.num_envs) if state is None
+                   else np.array(state, dtype=np.float32).reshape(self.num_envs, 2))
+        observations = self._ctx.env_reset(initial)
+        if self._visualizer is not None:
+            self._visualizer.reset(initial, observations)
+        return observations, {}
+
+    def step(self, actions):
+        actions = composed_actions(self._transformer, actions, self.num_envs, index_range=False)
+        pool = self._initializer.propose(self.num_envs)
+        if self._discrete:
+            observations, rewards, truncated, used = self._ctx.env_step(actions, pool)
+        else:
+            observations, rewards, truncated, used = self._ctx.env_step_jumps(actions, pool)
+        if used:
+            self._initializer.initialize(used)  # consume exactly the rows that were used
+        if self._visualizer is not None:  # vector_environment.py:149-156
+            state = self._state
+            if used:
+                self._visualizer.reset(state[truncated], observations[truncated], truncated)
+            self._visualizer.step(state[~truncated], observations[~truncated], ~truncated)
+        return observations, rewards, np.full(self.num_envs, False), truncated, {}

@@ -1,0 +1,231 @@
+"""Compiles strategy objects into the device program of a composed environment (rf_env_program, rf_env_configure_composed).
+
+A program holds the transformer (its kind and parameters), up to eight ender leaves with a postfix list of `|` / `&`
+over them, and up to eight rewarder leaves with a postfix list of `+` / `*` and the dtype of every node.  Leaves are
+numbered in the order a left-to-right walk of the tree meets them; that is also the order of the per-leaf strategy
+state the device keeps (rf_env_get_strategy_state) and `host_strategy_state` reads from the host twin's objects.
+
+Every check of rf_env_configure_composed is made here first and raises AssertionError, so that nothing malformed
+reaches the device; so do the checks only Python can make: every strategy's num_envs, and rewarders whose numpy result
+would not be floating point (an OnTargetRewarder with integer on / off, which numpy evaluates in int64).
+"""
+
+import math
+
+import numpy as np
+
+from reinfocus_amd import _native
+from reinfocus_amd.environments import episode_ender
+from reinfocus_amd.environments import episode_rewarder
+from reinfocus_amd.environments import state_transformer
+
+# the dtype numpy gives each rewarder leaf with Python-number parameters, which is the one the device computes it in
+LEAF_DTYPES = {
+    episode_rewarder.DELTA: np.dtype(np.float32),
+    episode_rewarder.DISTANCE: np.dtype(np.float32),
+    episode_rewarder.OBSERVATION: np.dtype(np.float32),
+    episode_rewarder.ON_TARGET: np.dtype(np.float64),
+    episode_rewarder.STOPPED: np.dtype(np.float64),
+}
+
+
+def postfix(tree, op_class, children, op_code):
+    """(leaves in walk order, postfix list): an entry >= 0 is a leaf's number, a negative one an operation."""
+    leaves, ops = [], []
+
+    def walk(node):
+        if isinstance(node, op_class):
+            left, right = children(node)
+            walk(left)
+            walk(right)
+            ops.append(op_code(node))
+        else:
+            assert not any(node is leaf for leaf in leaves), "a strategy object may occur only once in a composition"
+            ops.append(len(leaves))
+            leaves.append(node)
+
+    walk(tree)
+    return leaves, ops
+
+
+def ender_postfix(ender):
+    return postfix(ender, episode_ender.OpEnder, lambda node: (node._l_ender, node._r_ender),
+                   lambda node: episode_ender.OR if node._op is np.bitwise_or else episode_ender.AND)
+
+
+def rewarder_postfix(rewarder):
+    return postfix(rewarder, episode_rewarder.OpRewarder, lambda node: (node._l_rewarder, node._r_rewarder),
+                   lambda node: episode_rewarder.ADD if node._op is np.add else episode_rewarder.MUL)
+
+
+def _number(x, what):
+    assert isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, bool), f"{what}: {x!r} is not a number"
+    assert math.isfinite(float(x)), f"{what}: {x!r} is not finite"
+    return float(x)
+
+
+def _state_index(i, what):
+    assert isinstance(i, (int, np.integer)) and i in (0, 1), f"{what}: state index {i!r} outside {{0, 1}}"
+    return int(i)
+
+
+def _steps(k, what, most=2 ** 31 - 1):
+    assert isinstance(k, (int, np.integer)) and 0 <= k <= most, f"{what}: {k!r} outside [0, {most}]"
+    return int(k)
+
+
+def _transformer(program, transformer, num_envs):
+    assert isinstance(transformer, state_transformer.StateTransformer) and transformer.kind is not None, \
+        f"unsupported transformer {transformer!r}"
+    assert transformer.num_envs == num_envs, f"the transformer has num_envs {transformer.num_envs}, not {num_envs}"
+    program.transformer = transformer.kind
+    program.move_index = _state_index(transformer._move_index, "transformer move_index")
+    assert len(transformer._limits) == 2, "transformer limits: (low, high)"
+    program.limit_lo = _number(transformer._limits[0], "transformer limits")
+    program.limit_hi = _number(transformer._limits[1], "transformer limits")
+    if transformer.kind == state_transformer.CONTINUOUS_MOVE:
+        program.speed = _number(transformer._speed, "ContinuousMoveTransformer speed")
+    if transformer.kind in (state_transformer.CONTINUOUS_JUMP, state_transformer.CONTINUOUS_MOVE):
+        program.stop_threshold = _number(transformer._stop_threshold, "transformer stop_threshold")
+    else:
+        action_set = transformer._action_set
+        assert 1 <= len(action_set) <= 32, f"{len(action_set)} actions (1 to 32)"
+        assert action_set.dtype.kind in "iuf", f"action set of dtype {action_set.dtype}"
+        program.n_actions = len(action_set)
+        for i, a in enumerate(action_set):
+            program.action_set[i] = _number(a, "action set")
+
+
+def _ender(leaf, num_envs):
+    assert isinstance(leaf, episode_ender.BaseEnder) and leaf.kind is not None, f"unsupported ender {leaf!r}"
+    assert leaf._num_envs == num_envs, f"{type(leaf).__name__} has num_envs {leaf._num_envs}, not {num_envs}"
+    out = _native.EnvEnder()
+    out.kind = leaf.kind
+    name = type(leaf).__name__
+    if leaf.kind in (episode_ender.DIVERGING, episode_ender.ON_TARGET):
+        out.index0 = _state_index(leaf._check_indices[0], name)
+        out.index1 = _state_index(leaf._check_indices[1], name)
+        out.steps = _steps(leaf._early_end_steps, f"{name} early_end_steps")
+        out.threshold = _number(leaf._threshold if leaf.kind == episode_ender.DIVERGING else leaf._radius, name)
+    elif leaf.kind == episode_ender.STOPPED:
+        out.index0 = _state_index(leaf._check_index, name)
+        out.steps = _steps(leaf._early_end_steps, f"{name} early_end_steps", _native.MAX_STOPPED_STEPS)
+        out.threshold = _number(leaf._early_end_span, name)
+    elif leaf.kind == episode_ender.TIME_LIMIT:
+        out.steps = _steps(leaf._max_steps, f"{name} max_steps")
+    return out
+
+
+def _rewarder(leaf):
+    assert isinstance(leaf, episode_rewarder.BaseRewarder) and leaf.kind is not None, f"unsupported rewarder {leaf!r}"
+    name = type(leaf).__name__
+    assert np.issubdtype(leaf.dtype, np.floating), f"{name}: numpy evaluates it in {leaf.dtype}, not floating point"
+    assert leaf.dtype == LEAF_DTYPES[leaf.kind], \
+        f"{name}: numpy evaluates it in {leaf.dtype}, the device in {LEAF_DTYPES[leaf.kind]} (Python-number parameters)"
+    out = _native.EnvRewarder()
+    out.kind = leaf.kind
+    if leaf.kind == episode_rewarder.OBSERVATION:
+        i = leaf._reward_observation_index
+        assert isinstance(i, (int, np.integer)) and 0 <= i < 4, f"{name}: observation index {i!r} outside 0-3"
+        out.index0 = int(i)
+        return out
+    if leaf.kind in (episode_rewarder.DELTA, episode_rewarder.STOPPED):
+        out.index0 = _state_index(leaf._check_index, name)
+    else:
+        out.index0 = _state_index(leaf._check_indices[0], name)
+        out.index1 = _state_index(leaf._check_indices[1], name)
+    params = {
+        episode_rewarder.DELTA: lambda: (leaf._reward, leaf._scale, 0.0),
+        episode_rewarder.DISTANCE: lambda: (leaf._span, leaf._high - leaf._low, leaf._low),
+        episode_rewarder.ON_TARGET: lambda: (leaf._span, leaf._delta, leaf._off),
+        episode_rewarder.STOPPED: lambda: (leaf._threshold, leaf._reward, 0.0),
+    }[leaf.kind]()
+    for k, value in enumerate(params):
+        out.p[k] = _number(value, name)
+    return out
+
+
+def compile_program(transformer, ender, rewarder, num_envs):
+    """The rf_env_program of a composition (AssertionError for anything the device cannot run)."""
+    program = _native.EnvProgram()
+    _transformer(program, transformer, num_envs)
+    enders, ender_ops = ender_postfix(ender)
+    assert len(enders) <= _native.MAX_LEAVES, f"{len(enders)} ender leaves (at most {_native.MAX_LEAVES})"
+    program.n_enders = len(enders)
+    program.n_ender_ops = len(ender_ops)
+    for i, leaf in enumerate(enders):
+        program.enders[i] = _ender(leaf, num_envs)
+    for t, op in enumerate(ender_ops):
+        program.ender_ops[t] = op
+    rewarders, reward_ops = rewarder_postfix(rewarder)
+    assert len(rewarders) <= _native.MAX_LEAVES, f"{len(rewarders)} rewarder leaves (at most {_native.MAX_LEAVES})"
+    program.n_rewarders = len(rewarders)
+    program.n_reward_ops = len(reward_ops)
+    for i, leaf in enumerate(rewarders):
+        program.rewarders[i] = _rewarder(leaf)
+    dtypes = []
+    for t, op in enumerate(reward_ops):
+        program.reward_ops[t] = op
+        if op >= 0:
+            dtypes.append(rewarders[op].dtype)
+        else:
+            right, left = dtypes.pop(), dtypes.pop()
+            dtypes.append(np.promote_types(left, right))
+        program.reward_f64[t] = int(dtypes[-1] == np.float64)
+    return program
+
+
+def host_strategy_state(ender, rewarder, num_envs):
+    """The per-leaf strategy state of the host twin's objects, laid out as rf_env_get_strategy_state returns it:
+    (counters int32[n_enders, n], floats float32[n_enders, n], histories float32[rows, n], old float32[n_rewarders, n])."""
+    enders, _ = ender_postfix(ender)
+    rewarders, _ = rewarder_postfix(rewarder)
+    counters = np.zeros((len(enders), num_envs), dtype=np.int32)
+    floats = np.zeros((len(enders), num_envs), dtype=np.float32)
+    histories = []
+    for i, leaf in enumerate(enders):
+        if leaf.kind == episode_ender.DIVERGING:
+            counters[i] = leaf._diverging_steps
+            floats[i] = leaf._last_diff
+        elif leaf.kind == episode_ender.ON_TARGET:
+            counters[i] = leaf._on_target_steps
+        elif leaf.kind == episode_ender.TIME_LIMIT:
+            counters[i] = leaf._steps
+        elif leaf.kind == episode_ender.STOPPED:
+            histories.append(leaf._moves.data.T)
+    old = np.zeros((len(rewarders), num_envs), dtype=np.float32)
+    for i, leaf in enumerate(rewarders):
+        if leaf.kind in (episode_rewarder.DELTA, episode_rewarder.STOPPED) and leaf._old_states is not None:
+            old[i] = leaf._old_states
+    rows = np.concatenate(histories).astype(np.float32) if histories else np.zeros((0, num_envs), dtype=np.float32)
+    return counters, floats, rows, old
+
+
+def device_status(ender, state, index):
+    """ender.status(index) of a composed environment from its device-side strategy state (rf_env_get_strategy_state):
+    the status strings of the reference, leaf by leaf, joined as OpEnder joins them."""
+    counters, _, histories, _ = state
+    enders, _ = ender_postfix(ender)
+    first_rows, row = [], 0
+    for leaf in enders:
+        first_rows.append(row)
+        row += leaf._early_end_steps + 1 if leaf.kind == episode_ender.STOPPED else 0
+
+    def walk(node):
+        if isinstance(node, episode_ender.OpEnder):
+            left, right = walk(node._l_ender), walk(node._r_ender)
+            return left + (", " if left and right else "") + right
+        i = next(k for k, leaf in enumerate(enders) if leaf is node)
+        count = counters[i, index]
+        if node.kind == episode_ender.DIVERGING:
+            return f"diverging {count} / {node._early_end_steps}" if count > 0 else ""
+        if node.kind == episode_ender.ON_TARGET:
+            return f"on target {count} / {node._early_end_steps}" if count > 0 else ""
+        if node.kind == episode_ender.TIME_LIMIT:
+            return f"step {count} / {node._max_steps}"
+        if node.kind == episode_ender.STOPPED:
+            moves = histories[first_rows[i]:first_rows[i] + node._early_end_steps + 1, index]
+            return episode_ender.stopped_status(moves, node._early_end_steps, node._early_end_span)
+        return ""
+
+    return walk(ender)

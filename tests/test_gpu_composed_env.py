@@ -1,0 +1,225 @@
+"""GPU tests of the device-resident composed environment (rf_env_configure_composed): harness.DeviceVectorEnvironment
+against its numpy-glue twin harness.VectorEnvironment bit for bit on every schedule of the step, for a matrix of
+compositions that together use every transformer, every ender and rewarder leaf and both operations of each; the
+compositions that restate DiscreteSteps and ContinuousJumps against those tasks' device environments at the benchmark's
+shape; a DiscreteSteps context next to a composed one; refused actions; the visualiser."""
+
+import numpy as np
+import pytest
+
+from reinfocus_amd.environments import episode_ender as ee
+from reinfocus_amd.environments import episode_rewarder as er
+from reinfocus_amd.environments import state_initializer as si
+from reinfocus_amd.environments import state_transformer as st
+from reinfocus_amd.environments import strategy_program as sp
+from tests.test_composed_env_logic import ACTION_SET, ENDS, continuous_jumps, discrete_steps
+from tests.test_continuous_vector_logic import _actions
+from tests.test_gpu_environment import BRANCH_NAME, FIRST_STEP_BRANCH, STEP_BRANCHES
+
+pytestmark = pytest.mark.gpu
+
+
+def _matrix(name, n, seed):
+    """Fresh strategy objects of composition `name` (each environment owns its own)."""
+    init = si.RangedInitializer([[ENDS], [(5.0, 6.0), (9.0, 10.0)]] if name == "jump" else [[ENDS], [ENDS]], seed=seed)
+    if name == "move":  # nested enders and rewarders, both ender ops and both rewarder ops
+        return dict(ender=(ee.TimeLimitEnder(n, 7) | ee.DivergingEnder(n, (0, 1), 0.125, 3))
+                    | (ee.OnTargetEnder(n, (1, 0), 0.3, 2) & ee.StoppedEnder(n, 1, 0.2, 2)),
+                    rewarder=(er.DeltaRewarder(1, 0.5) + er.ObservationRewarder(1)) * er.DistanceRewarder((0, 1), 5.0, -1.0, 1.0)
+                    + er.OnTargetRewarder((0, 1), 0.25, -0.5, 2.0),
+                    transformer=st.DiscreteMoveTransformer(n, 1, ENDS, ACTION_SET), initializer=init, num_envs=n)
+    if name == "jump":  # several ranges per element in the initializer
+        return dict(ender=ee.TimeLimitEnder(n, 9) | ee.StoppedEnder(n, 1, 0.1, 3),
+                    rewarder=er.ObservationRewarder(3) + er.StoppedRewarder(1, 0.125, 2.0) * er.OnTargetRewarder((0, 1), 0.25),
+                    transformer=st.ContinuousJumpTransformer(n, 1, ENDS, 0.125), initializer=init, num_envs=n)
+    if name == "cmove":
+        return dict(ender=(ee.OnTargetEnder(n, (0, 1), 0.5, 3) | ee.TimeLimitEnder(n, 12))
+                    & (ee.DivergingEnder(n, (0, 1), 0.0, 2) | ee.EndlessEnder(n)),
+                    rewarder=er.DeltaRewarder(1, 0.25, -0.5) * er.ObservationRewarder(0) + er.DistanceRewarder((0, 1), 2.5),
+                    transformer=st.ContinuousMoveTransformer(n, 1, ENDS, 2.0, 0.1), initializer=init, num_envs=n)
+    return dict(ender=ee.TimeLimitEnder(n, 6) | ee.DivergingEnder(n, (0, 1), 0.125, 2),
+                rewarder=er.StoppedRewarder(1, 0.3) + er.ObservationRewarder(2) * er.DeltaRewarder(1, 0.5),
+                transformer=st.DiscreteJumpTransformer(n, 1, ENDS, np.linspace(5.0, 10.0, 9)), initializer=init,
+                num_envs=n)
+
+
+def _step_actions(name, rng, state, n):
+    if name in ("move", "djump"):
+        return rng.integers(0, 13 if name == "move" else 9, n)
+    if name == "jump":
+        return _actions(rng, state)
+    actions = rng.uniform(-1.5, 1.5, n).astype(np.float32)
+    actions[rng.integers(0, 4, n) == 0] = 0.0  # (moves shorter than the stop threshold)
+    return actions
+
+
+def _same_step(got, want):
+    for x, y in zip(got[:4], want[:4]):
+        assert x.dtype == y.dtype and x.shape == y.shape and np.array_equal(x, y)
+
+
+def _same_strategy_state(host, dev):
+    want, got = host.strategy_state(), dev.strategy_state()
+    for x, y in zip(got, want):
+        assert x.dtype == y.dtype and x.shape == y.shape and np.array_equal(x, y, equal_nan=True)
+    return got
+
+
+@pytest.mark.parametrize("branch", list(STEP_BRANCHES))
+@pytest.mark.parametrize("n,height,spp,steps", [(64, 32, 4, 30), (300, 24, 2, 24)])
+@pytest.mark.parametrize("name", ["move", "jump", "cmove", "djump"])
+def test_device_step_equals_host_twin(name, n, height, spp, steps, branch, monkeypatch):
+    """Observations, float64 rewards, flags, states, per-leaf strategy state, status strings and initializer
+    consumption after every step, through auto-resets, on every schedule of the step."""
+    from reinfocus_amd.environments import harness
+
+    kw = dict(frame_height=height, samples_per_pixel=spp, device=0)
+    host = harness.VectorEnvironment(**_matrix(name, n, 13), **kw)
+    for key, value in STEP_BRANCHES[branch].items():
+        monkeypatch.setenv(key, value)
+    dev = harness.DeviceVectorEnvironment(**_matrix(name, n, 13), **kw)
+    for key in STEP_BRANCHES[branch]:
+        monkeypatch.delenv(key)
+    o_h, _ = host.reset()
+    o_d, _ = dev.reset()
+    assert o_d.dtype == np.float32 and np.array_equal(o_h, o_d)
+    assert np.array_equal(host._state, dev._state)
+    _same_strategy_state(host, dev)
+    rng = np.random.default_rng(6)
+    resets = 0
+    for step in range(steps):
+        actions = _step_actions(name, rng, host._state, n)
+        want = host.step(actions)
+        got = dev.step(actions)
+        _same_step(got, want)
+        assert got[1].dtype == np.float64
+        assert np.array_equal(host._state, dev._state)
+        snapshot = _same_strategy_state(host, dev)
+        assert [sp.device_status(dev._ender, snapshot, i) for i in range(n)] == [host.status(i) for i in range(n)]
+        assert host._initializer._generator.bit_generator.state == dev._initializer._generator.bit_generator.state
+        name_b = BRANCH_NAME.get(branch, branch)
+        assert dev._ctx.env_last_step_branch() == (FIRST_STEP_BRANCH.get(name_b, name_b) if step == 0 else name_b)
+        resets += int(want[3].sum())
+    assert resets > 0 and dev.status(0) == host.status(0)
+    host.close()
+    dev.close()
+
+
+@pytest.mark.parametrize("task", ["discrete", "continuous"])
+def test_restating_compositions_equal_the_task_environments_at_the_headline_shape(task):
+    """4096 environments of 256 x 256 pixels at 16 samples (bench.py's shape), a few steps with auto-resets: the
+    compositions that restate the tasks against DeviceVectorDiscreteSteps / DeviceVectorContinuousJumps."""
+    from reinfocus_amd.environments import harness
+
+    n = 4096
+    kw = dict(frame_height=256, samples_per_pixel=16, device=0)
+    if task == "discrete":
+        task_env = harness.DeviceVectorDiscreteSteps(max_episode_steps=2, num_envs=n, seed=4, **kw)
+        composed = harness.DeviceVectorEnvironment(**discrete_steps(n, 2, seed=4), **kw)
+    else:
+        task_env = harness.DeviceVectorContinuousJumps(max_episode_steps=2, num_envs=n, seed=4, **kw)
+        composed = harness.DeviceVectorEnvironment(**continuous_jumps(n, 2, seed=4), **kw)
+    assert np.array_equal(task_env.reset()[0], composed.reset()[0])
+    rng = np.random.default_rng(0)
+    for _ in range(4):
+        actions = rng.integers(0, 13, n) if task == "discrete" else _actions(rng, task_env._state)
+        want = task_env.step(actions)
+        _same_step(composed.step(actions), want)
+        assert np.array_equal(task_env._state, composed._state)
+    assert want[3].all()  # (the time limit ended every environment in the last step)
+    task_env.close()
+    composed.close()
+
+
+def test_discrete_steps_and_composed_contexts_side_by_side():
+    """A DiscreteSteps context and a composed one stepped alternately in one process each equal their twin."""
+    from reinfocus_amd.environments import harness
+
+    n = 40
+    kw = dict(num_envs=n, frame_height=24, samples_per_pixel=3, device=0)
+    d_host = harness.VectorDiscreteSteps(max_episode_steps=6, seed=1, **kw)
+    d_dev = harness.DeviceVectorDiscreteSteps(max_episode_steps=6, seed=1, **kw)
+    ckw = dict(frame_height=24, samples_per_pixel=3, device=0)
+    c_host = harness.VectorEnvironment(**_matrix("cmove", n, 2), **ckw)
+    c_dev = harness.DeviceVectorEnvironment(**_matrix("cmove", n, 2), **ckw)
+    assert np.array_equal(d_host.reset()[0], d_dev.reset()[0])
+    assert np.array_equal(c_host.reset()[0], c_dev.reset()[0])
+    rng = np.random.default_rng(9)
+    for _ in range(16):
+        _same_step(d_dev.step(a := rng.integers(0, 13, n)), d_host.step(a))
+        _same_step(c_dev.step(a := _step_actions("cmove", rng, c_host._state, n)), c_host.step(a))
+        assert np.array_equal(d_host._state, d_dev._state) and np.array_equal(c_host._state, c_dev._state)
+        _same_strategy_state(c_host, c_dev)
+    for env in (d_host, d_dev, c_host, c_dev):
+        env.close()
+
+
+@pytest.mark.parametrize("name", ["move", "jump", "cmove"])
+def test_refused_actions_change_nothing(name):
+    """Discrete indices outside [0, n), NaN or infinite continuous actions, jumps outside [-1, 1] and the entry points
+    of the other dtype are refused by the library and by the environment; the device state is left as it was."""
+    from reinfocus_amd.environments import harness
+
+    n = 12
+    dev = harness.DeviceVectorEnvironment(**_matrix(name, n, 5), frame_height=16, samples_per_pixel=2, device=0)
+    dev.reset()
+    rng = np.random.default_rng(1)
+    for _ in range(3):
+        dev.step(_step_actions(name, rng, dev._state, n))
+    ctx = dev._ctx
+    pool = np.full((n, 2), 7.5, dtype=np.float32)
+
+    def snapshot():
+        return [dev._state, *dev.strategy_state()]
+
+    before = snapshot()
+    ints, floats = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.float32)
+    if name == "move":
+        calls = [lambda: ctx.env_step_jumps(floats, pool), lambda: ctx.env_step_begin_jumps(floats),
+                 lambda: ctx.env_step_plan_jumps(floats)]
+        for bad in (13, -1):
+            i = ints.copy()
+            i[n // 2] = bad
+            calls += [lambda i=i: ctx.env_step(i, pool), lambda i=i: ctx.env_step_begin(i),
+                      lambda i=i: ctx.env_step_plan(i)]
+            with pytest.raises(AssertionError):
+                dev.step(i)
+    else:
+        calls = [lambda: ctx.env_step(ints, pool), lambda: ctx.env_step_begin(ints), lambda: ctx.env_step_plan(ints)]
+        for bad in (np.nan, np.inf, -np.inf) + ((1.5, -1.0000001) if name == "jump" else ()):
+            f = floats.copy()
+            f[n // 2] = bad
+            calls += [lambda f=f: ctx.env_step_jumps(f, pool), lambda f=f: ctx.env_step_begin_jumps(f),
+                      lambda f=f: ctx.env_step_plan_jumps(f)]
+            with pytest.raises(AssertionError):
+                dev.step(f)
+    for call in calls:
+        with pytest.raises(AssertionError):
+            call()
+    after = snapshot()
+    assert all(np.array_equal(x, y, equal_nan=True) for x, y in zip(before, after))
+    if name == "cmove":  # finite actions outside [-1, 1] are clipped, not refused
+        dev.step(np.full(n, 3.0, dtype=np.float32))
+    dev.close()
+
+
+def test_device_visualiser_equals_host_glue():
+    """render_mode="rgb_array": the same 600 px frames and status strings as the numpy-glue twin."""
+    from reinfocus_amd.environments import harness
+
+    n = 4
+    kw = dict(render_mode="rgb_array", frame_height=32, samples_per_pixel=2, device=0)
+    host = harness.VectorEnvironment(**_matrix("move", n, 9), **kw)
+    dev = harness.DeviceVectorEnvironment(**_matrix("move", n, 9), **kw)
+    start = [[7.5, 7.5]] * n
+    assert np.array_equal(host.reset(state=start)[0], dev.reset(state=start)[0])
+    rng = np.random.default_rng(2)
+    for _ in range(8):
+        a, b = host.render(), dev.render()
+        assert a.shape == b.shape and a.shape[0] % 600 == 0
+        assert np.array_equal(a[:, :600], b[:, :600])
+        actions = rng.integers(0, 13, n)
+        _same_step(dev.step(actions), host.step(actions))
+        assert [host.status(i) for i in range(n)] == [dev.status(i) for i in range(n)]
+    host.close()
+    dev.close()
