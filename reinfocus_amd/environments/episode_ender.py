@@ -6,6 +6,9 @@ alone (never from observations) -- which is what lets the device step decide whi
 (csrc/rf_env.h).  harness.VectorEnvironment drives them on the host; rf_env_configure_composed runs the same rules on
 the GPU.
 
+Thresholds, radii and spans pass through scalars.parameter, so the float32 comparisons are numpy 1.26's (the
+reference's numpy) under any numpy, numpy.float64 parameters included.
+
 `kind` names a leaf for the device program (rf_env_program.enders).
 """
 
@@ -14,6 +17,7 @@ import warnings
 import numpy as np
 
 from reinfocus_amd import histories
+from reinfocus_amd.environments import scalars
 
 DIVERGING, ENDLESS, ON_TARGET, STOPPED, TIME_LIMIT = 0, 1, 2, 3, 4
 OR, AND = -1, -2  # postfix operations of rf_env_program.ender_ops
@@ -52,7 +56,7 @@ class DivergingEnder(BaseEnder):
     def __init__(self, num_envs, check_indices, threshold, early_end_steps=10):
         self._num_envs = num_envs
         self._check_indices = check_indices
-        self._threshold = threshold
+        self._threshold = scalars.parameter(threshold, "DivergingEnder threshold")
         self._early_end_steps = early_end_steps
         self._diverging_steps = np.zeros(num_envs, dtype=np.int32)
         self._last_diff = np.zeros(num_envs, dtype=np.float32)
@@ -101,7 +105,7 @@ class OnTargetEnder(BaseEnder):
     def __init__(self, num_envs, check_indices, early_end_radius, early_end_steps=10):
         self._num_envs = num_envs
         self._check_indices = check_indices
-        self._radius = early_end_radius
+        self._radius = scalars.parameter(early_end_radius, "OnTargetEnder early_end_radius")
         self._early_end_steps = early_end_steps
         self._on_target_steps = np.zeros(num_envs, dtype=np.int32)
 
@@ -132,7 +136,7 @@ class StoppedEnder(BaseEnder):
     def __init__(self, num_envs, check_index, early_end_span, early_end_steps=10):
         self._num_envs = num_envs
         self._check_index = check_index
-        self._early_end_span = early_end_span
+        self._early_end_span = scalars.parameter(early_end_span, "StoppedEnder early_end_span")
         self._early_end_steps = early_end_steps
         self._moves = histories.Histories(num_envs, early_end_steps + 1)
 

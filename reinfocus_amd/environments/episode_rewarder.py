@@ -1,16 +1,21 @@
 """Episode rewarders: the reward of a step (reference: environments/episode_rewarder.py).
 
 Same class names, constructor arguments and numpy arithmetic as the reference.  Rewarders combine with `+` and `*`
-into an OpRewarder.  `dtype` is a term's result dtype, evaluated by numpy itself.  With Python-float parameters it is
-fixed per class: DeltaRewarder, DistanceRewarder and ObservationRewarder float32 (float32 arrays with Python scalars),
-OnTargetRewarder and StoppedRewarder float64 (a bool array times a Python float); an OpRewarder's is the numpy
-promotion of its two operands.  harness.VectorEnvironment drives them on the host; rf_env_configure_composed runs the same arithmetic on the
+into an OpRewarder.  Scalar parameters pass through scalars.parameter (on - off and high - low through
+scalars.difference), so every term computes what numpy 1.26, the reference's numpy, computes under any numpy.  `dtype`
+is a term's result dtype, evaluated by numpy itself.  With Python-number or numpy.float64 parameters it is fixed per
+class: DeltaRewarder, DistanceRewarder and ObservationRewarder float32 (float32 arrays with scalars), OnTargetRewarder
+and StoppedRewarder float64 (a bool array times a float64 scalar); with numpy.float32 on and off (OnTargetRewarder) or
+reward (StoppedRewarder) those two are float32, as numpy 1.26 has them.  An OpRewarder's is the numpy promotion of its
+two operands.  harness.VectorEnvironment drives them on the host; rf_env_configure_composed runs the same arithmetic on the
 GPU, a float32 node in float32.
 
 `kind` names a leaf for the device program (rf_env_program.rewarders).
 """
 
 import numpy as np
+
+from reinfocus_amd.environments import scalars
 
 DELTA, DISTANCE, OBSERVATION, ON_TARGET, STOPPED = 0, 1, 2, 3, 4
 ADD, MUL = -1, -2  # postfix operations of rf_env_program.reward_ops
@@ -50,8 +55,8 @@ class DeltaRewarder(_OldStateRewarder):
 
     def __init__(self, check_index, scale, reward=-1.0):
         self._check_index = check_index
-        self._scale = scale
-        self._reward = reward
+        self._scale = scalars.parameter(scale, "DeltaRewarder scale")
+        self._reward = scalars.parameter(reward, "DeltaRewarder reward")
         self._old_states = None
 
     @property
@@ -72,17 +77,18 @@ class DistanceRewarder(BaseRewarder):
 
     def __init__(self, check_indices, span, low=-1.0, high=0.0):
         self._check_indices = check_indices
-        self._span = span
-        self._low = low
-        self._high = high
+        self._span = scalars.parameter(span, "DistanceRewarder span")
+        self._low = scalars.parameter(low, "DistanceRewarder low")
+        self._high = scalars.parameter(high, "DistanceRewarder high")
+        self._width = scalars.difference(self._high, self._low, "DistanceRewarder high - low")
 
     @property
     def dtype(self):
-        return ((1 - _PROBE[:, 0] / self._span) * (self._high - self._low) + self._low).dtype
+        return ((1 - _PROBE[:, 0] / self._span) * self._width + self._low).dtype
 
     def reward(self, states, observations):
         distance = abs(states[:, self._check_indices[0]] - states[:, self._check_indices[1]])
-        return (1 - distance / self._span) * (self._high - self._low) + self._low
+        return (1 - distance / self._span) * self._width + self._low
 
 
 class ObservationRewarder(BaseRewarder):
@@ -105,9 +111,9 @@ class OnTargetRewarder(BaseRewarder):
 
     def __init__(self, check_indices, span, off=0.0, on=1.0):
         self._check_indices = check_indices
-        self._span = span
-        self._off = off
-        self._delta = on - off
+        self._span = scalars.parameter(span, "OnTargetRewarder span")
+        self._off = scalars.parameter(off, "OnTargetRewarder off")
+        self._delta = scalars.difference(scalars.parameter(on, "OnTargetRewarder on"), self._off, "OnTargetRewarder on - off")
 
     @property
     def dtype(self):
@@ -125,8 +131,8 @@ class StoppedRewarder(_OldStateRewarder):
 
     def __init__(self, check_index, threshold, reward=1.0):
         self._check_index = check_index
-        self._threshold = abs(threshold)
-        self._reward = reward
+        self._threshold = abs(scalars.parameter(threshold, "StoppedRewarder threshold"))
+        self._reward = scalars.parameter(reward, "StoppedRewarder reward")
         self._old_states = None
 
     @property

@@ -1,8 +1,9 @@
 """State transformers: how an action moves a batch of states (reference: environments/state_transformer.py).
 
 Same class names, constructor arguments and numpy arithmetic as the reference; states are float32[num_envs, n].  Every
-expression mixes float32 arrays with Python scalars, so it computes the same under numpy 1.26's value-based casting and
-under NEP 50.  harness.VectorEnvironment drives them on the host; rf_env_configure_composed runs the same arithmetic on
+expression mixes float32 arrays with scalar parameters, which the constructors pass through scalars.parameter (and
+ContinuousJumpTransformer's span through scalars.difference), so it computes what numpy 1.26, the reference's numpy,
+computes under any numpy, numpy.float64 parameters included.  Action sets are arrays and stay as given.  harness.VectorEnvironment drives them on the host; rf_env_configure_composed runs the same arithmetic on
 the GPU (csrc/rf_env.h, composed task).
 
 `kind` names the transformer for the device program (rf_env_program.transformer).
@@ -10,9 +11,15 @@ the GPU (csrc/rf_env.h, composed task).
 
 import numpy as np
 
+from reinfocus_amd.environments import scalars
 from reinfocus_amd.environments import spaces
 
 CONTINUOUS_JUMP, CONTINUOUS_MOVE, DISCRETE_JUMP, DISCRETE_MOVE = 0, 1, 2, 3
+
+
+def _limits(limits):
+    """(low, high) as scalars.parameter makes them: a tuple, whatever sequence or array they came in."""
+    return tuple(scalars.parameter(x, "limits") for x in limits)
 
 
 class StateTransformer:
@@ -37,14 +44,14 @@ class ContinuousJumpTransformer(StateTransformer):
 
     def __init__(self, num_envs, move_index, limits, stop_threshold=0.1):
         super().__init__(num_envs, spaces.Box(-1, 1, dtype=np.float32))
-        self._limits = limits
+        self._limits = _limits(limits)
         self._move_index = move_index
-        self._stop_threshold = abs(stop_threshold)
+        self._stop_threshold = abs(scalars.parameter(stop_threshold, "stop_threshold"))
 
     def transform(self, states, actions):
         new_states = states.copy()
         actions = (actions.flatten() + 1) / 2.0
-        moved_states = actions * (self._limits[1] - self._limits[0]) + self._limits[0]
+        moved_states = actions * scalars.difference(self._limits[1], self._limits[0], "limits") + self._limits[0]
         moved = abs(new_states[:, self._move_index] - moved_states) > self._stop_threshold
         new_states[moved, self._move_index] = moved_states[moved]
         return new_states
@@ -58,10 +65,10 @@ class ContinuousMoveTransformer(StateTransformer):
 
     def __init__(self, num_envs, move_index, limits, speed, stop_threshold=0.1):
         super().__init__(num_envs, spaces.Box(-1, 1, dtype=np.float32))
-        self._limits = limits
+        self._limits = _limits(limits)
         self._move_index = move_index
-        self._speed = speed
-        self._stop_threshold = abs(stop_threshold)
+        self._speed = scalars.parameter(speed, "ContinuousMoveTransformer speed")
+        self._stop_threshold = abs(scalars.parameter(stop_threshold, "stop_threshold"))
 
     def transform(self, states, actions):
         new_states = states.copy()
@@ -78,7 +85,7 @@ class DiscreteJumpTransformer(StateTransformer):
 
     def __init__(self, num_envs, move_index, limits, action_set):
         super().__init__(num_envs, spaces.Discrete(len(action_set)))
-        self._limits = limits
+        self._limits = _limits(limits)
         self._move_index = move_index
         self._action_set = np.asarray(action_set, dtype=np.float32)
 
@@ -96,7 +103,7 @@ class DiscreteMoveTransformer(StateTransformer):
 
     def __init__(self, num_envs, move_index, limits, action_set):
         super().__init__(num_envs, spaces.Discrete(len(action_set)))
-        self._limits = limits
+        self._limits = _limits(limits)
         self._move_index = move_index
         self._action_set = np.asarray(action_set)
 

@@ -7,7 +7,8 @@ state the device keeps (rf_env_get_strategy_state) and `host_strategy_state` rea
 
 Every check of rf_env_configure_composed is made here first and raises AssertionError, so that nothing malformed
 reaches the device; so do the checks only Python can make: every strategy's num_envs, and rewarders whose numpy result
-would not be floating point (an OnTargetRewarder with integer on / off, which numpy evaluates in int64).
+would not be floating point (an OnTargetRewarder with integer on / off, which numpy evaluates in int64) or not in the
+dtype the device computes them in (an OnTargetRewarder / StoppedRewarder with numpy.float32 on and off / reward).
 """
 
 import math
@@ -19,7 +20,8 @@ from reinfocus_amd.environments import episode_ender
 from reinfocus_amd.environments import episode_rewarder
 from reinfocus_amd.environments import state_transformer
 
-# the dtype numpy gives each rewarder leaf with Python-number parameters, which is the one the device computes it in
+# the dtype numpy 1.26 gives each rewarder leaf with Python-number or numpy.float64 parameters (environments/scalars.py),
+# which is the one the device computes it in; numpy.float32 on / off or reward make OnTarget / Stopped float32: refused
 LEAF_DTYPES = {
     episode_rewarder.DELTA: np.dtype(np.float32),
     episode_rewarder.DISTANCE: np.dtype(np.float32),
@@ -121,7 +123,7 @@ def _rewarder(leaf):
     name = type(leaf).__name__
     assert np.issubdtype(leaf.dtype, np.floating), f"{name}: numpy evaluates it in {leaf.dtype}, not floating point"
     assert leaf.dtype == LEAF_DTYPES[leaf.kind], \
-        f"{name}: numpy evaluates it in {leaf.dtype}, the device in {LEAF_DTYPES[leaf.kind]} (Python-number parameters)"
+        f"{name}: numpy evaluates it in {leaf.dtype}, the device in {LEAF_DTYPES[leaf.kind]} (Python-number or numpy.float64 parameters)"
     out = _native.EnvRewarder()
     out.kind = leaf.kind
     if leaf.kind == episode_rewarder.OBSERVATION:
@@ -136,7 +138,7 @@ def _rewarder(leaf):
         out.index1 = _state_index(leaf._check_indices[1], name)
     params = {
         episode_rewarder.DELTA: lambda: (leaf._reward, leaf._scale, 0.0),
-        episode_rewarder.DISTANCE: lambda: (leaf._span, leaf._high - leaf._low, leaf._low),
+        episode_rewarder.DISTANCE: lambda: (leaf._span, leaf._width, leaf._low),
         episode_rewarder.ON_TARGET: lambda: (leaf._span, leaf._delta, leaf._off),
         episode_rewarder.STOPPED: lambda: (leaf._threshold, leaf._reward, 0.0),
     }[leaf.kind]()
