@@ -316,25 +316,54 @@ __device__ __forceinline__ int coop_finish2m(CoopLds2 &lds, int parity, int *cnt
     uint4 *const state = lds.state[parity];
     int slot[kSets];
     lanemask parked[kSets];
+    // the stragglers of set j (lanes `need[j]`, list slots `slot[j]`) write their states into the list; the ones beyond
+    // its end finish in place
+    auto park = [&]() {
+#pragma unroll
+        for (int j = 0; j < kSets; ++j) {
+            parked[j] = need[j] & lanes_where(slot[j] < kCoopCap * 16); // (a ballot of one compare is that compare)
+            if (lane_in(parked[j]))
+                *entry16(state, slot[j]) = make_uint4(g[j].a_lo, g[j].a_hi, g[j].b_lo, g[j].b_hi);
+            if (lane_in(need[j] & ~parked[j])) { // overflow of the packed list: finish in place
+                if (DIM == 2) {
+                    while (!disc_attempt(g[j], w[j])) {
+                    }
+                } else {
+                    while (!sphere_attempt(g[j], w[j])) {
+                    }
+                }
+            }
+        }
+    };
+    int all = 0; // stragglers of this wave (WAVE_SLOTS)
     if (WAVE_SLOTS) {
-        int pop[kSets], all = 0;
+        int pop[kSets];
 #pragma unroll
         for (int j = 0; j < kSets; ++j) {
             pop[j] = (int)__builtin_popcountll(need[j]);
             all += pop[j];
         }
-        int base = 0;
-        if (all != 0) { // wave-uniform
+        // A wave without a straggler (about half of the wave-samples at the headline: tiles beside the target, outermost
+        // waves) has nothing to rank or to park: its twelve vector instructions -- two v_mbcnt, the slot and the
+        // `slot < cap` compare per set -- are skipped; it goes straight to B1 (wave-uniform: a scalar compare; +1.1 %,
+        // profiles/r07_ab.txt).
+        if (all == 0) {
+#pragma unroll
+            for (int j = 0; j < kSets; ++j)
+                parked[j] = 0; // (and no slot: the collect below does not look at it)
+        } else {
+            int base = 0;
             if ((tid & 63) == 0)
                 base = atomicAdd(cnt, all * 16);
             base = __builtin_amdgcn_readfirstlane(base);
-        }
 #pragma unroll
-        for (int j = 0; j < kSets; ++j) {
-            const int rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(need[j] >> 32),
-                                                            __builtin_amdgcn_mbcnt_lo((unsigned)need[j], 0));
-            slot[j] = base + rank * 16;
-            base += pop[j] * 16;
+            for (int j = 0; j < kSets; ++j) {
+                const int rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(need[j] >> 32),
+                                                                __builtin_amdgcn_mbcnt_lo((unsigned)need[j], 0));
+                slot[j] = base + rank * 16;
+                base += pop[j] * 16;
+            }
+            park();
         }
     } else {
 #pragma unroll
@@ -344,21 +373,7 @@ __device__ __forceinline__ int coop_finish2m(CoopLds2 &lds, int parity, int *cnt
             if (lane_in(need[j]))
                 slot[j] = atomicAdd(cnt, 16);
         }
-    }
-#pragma unroll
-    for (int j = 0; j < kSets; ++j) {
-        parked[j] = need[j] & lanes_where(slot[j] < kCoopCap * 16); // (a ballot of one compare is that compare)
-        if (lane_in(parked[j]))
-            *entry16(state, slot[j]) = make_uint4(g[j].a_lo, g[j].a_hi, g[j].b_lo, g[j].b_hi);
-        if (lane_in(need[j] & ~parked[j])) { // overflow of the packed list: finish in place
-            if (DIM == 2) {
-                while (!disc_attempt(g[j], w[j])) {
-                }
-            } else {
-                while (!sphere_attempt(g[j], w[j])) {
-                }
-            }
-        }
+        park();
     }
     __syncthreads(); // B1
     test_skew(tid, (int)(cnt - lds.cnt) + 1); // (a wave late with its read of the counter)
@@ -370,6 +385,8 @@ __device__ __forceinline__ int coop_finish2m(CoopLds2 &lds, int parity, int *cnt
     test_skew(tid, total + 2); // (a wave late with its collect reads)
 #pragma unroll
     for (int j = 0; j < kSets; ++j) {
+        if (WAVE_SLOTS && all == 0) // wave-uniform: nothing parked, no slot
+            break;
         if (lane_in(parked[j])) {
             uint4 ps = *entry16(state, slot[j]);
             // (opaque: or the first draw's 64-bit sum is fed by a second, 8-byte read of the same entry)
