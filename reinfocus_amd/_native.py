@@ -401,25 +401,24 @@ class Context:
         return out
 
     # --- device-resident env step ----------------------------------------------------------
-    def env_configure(self, cfg):
-        self._env_n = cfg.n
+    def _env_configured(self, n):
+        self._env_n = n
         self._env_k = ctypes.c_int(0)  # (env_step's count of ended environments, and its reference, made once)
         self._env_k_ref = ctypes.byref(self._env_k)
+
+    def env_configure(self, cfg):
+        self._env_configured(cfg.n)
         _check(self._lib.rf_env_configure(self._h, ctypes.byref(cfg)))
 
     def env_configure_jumps(self, cfg, stop_threshold):
         """rf_env_configure_jumps: the context steps ContinuousJumps (float32 actions, the env_step*_jumps calls)."""
-        self._env_n = cfg.n
-        self._env_k = ctypes.c_int(0)
-        self._env_k_ref = ctypes.byref(self._env_k)
+        self._env_configured(cfg.n)
         _check(self._lib.rf_env_configure_jumps(self._h, ctypes.byref(cfg), float(stop_threshold)))
 
     def env_configure_composed(self, cfg, program):
         """rf_env_configure_composed: the context steps the composed environment `program` (an EnvProgram; int32
         actions for a discrete transformer, the float32 env_step*_jumps calls for a continuous one)."""
-        self._env_n = cfg.n
-        self._env_k = ctypes.c_int(0)
-        self._env_k_ref = ctypes.byref(self._env_k)
+        self._env_configured(cfg.n)
         _check(self._lib.rf_env_configure_composed(self._h, ctypes.byref(cfg), ctypes.byref(program)))
         self._env_program = (program.n_enders, program.n_rewarders,
                              sum(program.enders[i].steps + 1 for i in range(program.n_enders)
@@ -444,63 +443,61 @@ class Context:
         _check(self._lib.rf_env_reset(self._h, _ptr(states), _ptr(obs)))
         return obs
 
-    def env_step(self, actions, pool):
+    # the int32 calls and their float32 (_jumps) twins: one body each, given the C function and the actions' dtype
+    def _env_step(self, function, dtype, actions, pool):
         # (addresses as plain integers: the ctypes casts of _ptr cost 2 us each, a sixth of a small environment's step)
         n = self._env_n
-        actions = np.ascontiguousarray(actions, dtype=np.int32).reshape(n)
+        actions = np.ascontiguousarray(actions, dtype=dtype).reshape(n)
         pool = np.ascontiguousarray(pool, dtype=np.float32).reshape(n, 2)
         obs = np.empty((n, 4), dtype=np.float32)
         rewards = np.empty(n, dtype=np.float64)
         truncated = np.empty(n, dtype=np.bool_)  # (the library writes 0 / 1 bytes)
         k = self._env_k
-        rc = self._lib.rf_env_step(self._h, actions.ctypes.data, pool.ctypes.data, obs.ctypes.data, rewards.ctypes.data,
-                                   truncated.ctypes.data, self._env_k_ref)
+        rc = function(self._h, actions.ctypes.data, pool.ctypes.data, obs.ctypes.data, rewards.ctypes.data,
+                      truncated.ctypes.data, self._env_k_ref)
         if rc != 0:
             _check(rc)
         return obs, rewards, truncated, k.value
+
+    def _env_step_begin(self, function, dtype, actions):
+        n = self._env_n
+        actions = np.ascontiguousarray(actions, dtype=dtype).reshape(n)
+        rewards = np.empty(n, dtype=np.float64)
+        truncated = np.empty(n, dtype=np.uint8)
+        k = ctypes.c_int(0)
+        _check(function(self._h, _ptr(actions), _ptr(rewards), _ptr(truncated), ctypes.byref(k)))
+        return rewards, truncated.astype(bool), k.value
+
+    def _env_step_plan(self, function, dtype, actions):
+        actions = np.ascontiguousarray(actions, dtype=dtype).reshape(self._env_n)
+        k = ctypes.c_int(0)
+        _check(function(self._h, _ptr(actions), ctypes.byref(k)))
+        return k.value
+
+    def env_step(self, actions, pool):
+        """One whole step: (observations, rewards, truncated, number of environments that ended and took rows of
+        `pool`)."""
+        return self._env_step(self._lib.rf_env_step, np.int32, actions, pool)
 
     def env_step_jumps(self, actions, pool):
         """env_step with float32 actions in [-1, 1] (rf_env_step_jumps; anything else is refused by the library)."""
-        n = self._env_n
-        actions = np.ascontiguousarray(actions, dtype=np.float32).reshape(n)
-        pool = np.ascontiguousarray(pool, dtype=np.float32).reshape(n, 2)
-        obs = np.empty((n, 4), dtype=np.float32)
-        rewards = np.empty(n, dtype=np.float64)
-        truncated = np.empty(n, dtype=np.bool_)
-        k = self._env_k
-        rc = self._lib.rf_env_step_jumps(self._h, actions.ctypes.data, pool.ctypes.data, obs.ctypes.data,
-                                         rewards.ctypes.data, truncated.ctypes.data, self._env_k_ref)
-        if rc != 0:
-            _check(rc)
-        return obs, rewards, truncated, k.value
-
-    def env_step_begin_jumps(self, actions):
-        """env_step_begin with float32 actions (rf_env_step_begin_jumps)."""
-        n = self._env_n
-        actions = np.ascontiguousarray(actions, dtype=np.float32).reshape(n)
-        rewards = np.empty(n, dtype=np.float64)
-        truncated = np.empty(n, dtype=np.uint8)
-        k = ctypes.c_int(0)
-        _check(self._lib.rf_env_step_begin_jumps(self._h, _ptr(actions), _ptr(rewards), _ptr(truncated),
-                                                 ctypes.byref(k)))
-        return rewards, truncated.astype(bool), k.value
-
-    def env_step_plan_jumps(self, actions):
-        """env_step_plan with float32 actions (rf_env_step_plan_jumps)."""
-        actions = np.ascontiguousarray(actions, dtype=np.float32).reshape(self._env_n)
-        k = ctypes.c_int(0)
-        _check(self._lib.rf_env_step_plan_jumps(self._h, _ptr(actions), ctypes.byref(k)))
-        return k.value
+        return self._env_step(self._lib.rf_env_step_jumps, np.float32, actions, pool)
 
     def env_step_begin(self, actions):
         """First half of a two-phase step: (rewards, truncated, number of environments that ended)."""
-        n = self._env_n
-        actions = np.ascontiguousarray(actions, dtype=np.int32).reshape(n)
-        rewards = np.empty(n, dtype=np.float64)
-        truncated = np.empty(n, dtype=np.uint8)
-        k = ctypes.c_int(0)
-        _check(self._lib.rf_env_step_begin(self._h, _ptr(actions), _ptr(rewards), _ptr(truncated), ctypes.byref(k)))
-        return rewards, truncated.astype(bool), k.value
+        return self._env_step_begin(self._lib.rf_env_step_begin, np.int32, actions)
+
+    def env_step_begin_jumps(self, actions):
+        """env_step_begin with float32 actions (rf_env_step_begin_jumps)."""
+        return self._env_step_begin(self._lib.rf_env_step_begin_jumps, np.float32, actions)
+
+    def env_step_plan(self, actions):
+        """First half of a step cut BEFORE its render (transform, enders, ranking): how many environments end."""
+        return self._env_step_plan(self._lib.rf_env_step_plan, np.int32, actions)
+
+    def env_step_plan_jumps(self, actions):
+        """env_step_plan with float32 actions (rf_env_step_plan_jumps)."""
+        return self._env_step_plan(self._lib.rf_env_step_plan_jumps, np.float32, actions)
 
     def env_step_end(self, pool_rows):
         """Second half: the environments that ended take pool_rows float32[k, 2]; observations."""
@@ -509,13 +506,6 @@ class Context:
         obs = np.empty((n, 4), dtype=np.float32)
         _check(self._lib.rf_env_step_end(self._h, _ptr(pool_rows) if len(pool_rows) else None, _ptr(obs)))
         return obs
-
-    def env_step_plan(self, actions):
-        """First half of a step cut BEFORE its render (transform, enders, ranking): how many environments end."""
-        actions = np.ascontiguousarray(actions, dtype=np.int32).reshape(self._env_n)
-        k = ctypes.c_int(0)
-        _check(self._lib.rf_env_step_plan(self._h, _ptr(actions), ctypes.byref(k)))
-        return k.value
 
     def env_step_run(self, pool_rows):
         """The rest of a planned step with pool_rows float32[k, 2] for the environments that end:

@@ -340,6 +340,336 @@ int env_configure(rf_ctx *ctx, const rf_env_config *cfg, int task, float stop_th
     return RF_OK;
 }
 
+// What every launch of a schedule needs of the configured environment, made once from the context.  count: the
+// schedule's renders count their pixels as they are launched; a schedule that is enqueued in one go counts after the
+// step instead (its launches may be replayed, and skip slots).
+struct EnvLaunch {
+    int n, fh, spp, gray_mode;
+    dim3 grid, block; // one thread per environment
+    bool count;
+    EnvLaunch(const rf_ctx *ctx, bool count_)
+        : n(ctx->env_host.n), fh(ctx->env_host.frame_height), spp(ctx->env_host.spp),
+          gray_mode(ctx->env_host.gray_mode), grid((n + 255) / 256), block(256), count(count_)
+    {
+    }
+    unsigned long long pixels(int envs) const { return (unsigned long long)envs * (unsigned long long)fh * fh; }
+};
+
+constexpr int kEnvResetNone = -1; // fused_pass: nobody ended, nothing to pack
+
+void launch_reset_kernel(rf_ctx *ctx, const float *pool, int mode, const int *actions)
+{
+    hipLaunchKernelGGL(rf::env_reset_kernel, dim3(1), dim3(1024), 0, ctx->stream, ctx->env_cfg, ctx->env, pool, mode,
+                       actions);
+}
+
+// The full pass: env_pre_kernel (if `pre`), the render of all n environments, their focus measure, env_post_kernel.
+// A pre kernel without actions starts the episodes (rf_env_reset): env_post_kernel then takes its `first` form.
+int full_pass(rf_ctx *ctx, const EnvLaunch &d, bool pre, const int *actions)
+{
+    const bool first = pre && !actions;
+    if (pre)
+        hipLaunchKernelGGL(rf::env_pre_kernel, d.grid, d.block, 0, ctx->stream, ctx->env_cfg, ctx->env, actions);
+    int rc = launch_render(ctx, d.n, d.fh, d.fh, d.spp, ctx->env.cam_dyn, ctx->env.rect, ctx->env_axis, d.count);
+    if (rc == RF_OK && first && fused_step_possible(ctx))
+        rc = ensure_frames2(ctx, d.n, d.fh, d.fh); // (not inside a step: the first one after this may already be captured)
+    if (rc == RF_OK)
+        rc = launch_focus(ctx, d.n, d.fh, d.fh, d.gray_mode, nullptr, true);
+    if (rc != RF_OK)
+        return rc;
+    hipLaunchKernelGGL(rf::env_post_kernel, d.grid, d.block, 0, ctx->stream, ctx->env_cfg, ctx->env,
+                       (const double *)nullptr, first ? 1 : 0);
+    return RF_OK;
+}
+
+// The reset pass over `slots` compacted rows (vector_environment.py:137-151): env_reset_kernel in `mode` --
+// kEnvResetApply for the k rows of a count the host knows, kEnvResetBoth for all n slots (it ranks too, and marks the
+// unused slots, whose blocks exit at once) --, the render of the compacted set and its focus measure, or with
+// render == false the focus values somebody else measured (in d_var), then env_reset_post_kernel.
+int reset_pass(rf_ctx *ctx, const EnvLaunch &d, int slots, int mode, bool render)
+{
+    launch_reset_kernel(ctx, ctx->d_pool, mode, nullptr);
+    if (render) {
+        int rc = launch_render(ctx, slots, d.fh, d.fh, d.spp, ctx->env.cam_dyn2, ctx->env.rect2, ctx->env_axis, d.count);
+        if (rc == RF_OK)
+            rc = launch_focus(ctx, slots, d.fh, d.fh, d.gray_mode, mode == rf::kEnvResetBoth ? ctx->env.rect2 : nullptr,
+                              true);
+        if (rc != RF_OK)
+            return rc;
+    }
+    hipLaunchKernelGGL(rf::env_reset_post_kernel, dim3((slots + 255) / 256), dim3(256), 0, ctx->stream, ctx->env_cfg,
+                       ctx->env, render ? (const double *)nullptr : (const double *)ctx->d_var, (const float *)nullptr);
+    return RF_OK;
+}
+
+// The fused pass: one render launch and one focus launch per step.  Which environments end depends on their counters
+// alone (env_pre_kernel), so they are ranked and the compacted scene of the auto-reset is packed BEFORE the render --
+// `mode` kEnvResetPlan: from the step's actions; kEnvResetPack: for a ranking that exists already (rf_env_step_plan);
+// kEnvResetNone: nobody ended --; the r-th of them is rendered as row r of that set with the RNG streams of slot r
+// (render.py:217), i.e. right after slot r's own frame: the blocks of the slots below the count make two passes
+// (render_kernel_coop2<.., TWO>).  The step's frames of those slots go to frames2, so that the frame buffer ends up as
+// the two launches leave it.  The render cannot count its own pixels: the count is on the device.
+int fused_pass(rf_ctx *ctx, const EnvLaunch &d, int mode)
+{
+    if (mode != kEnvResetNone)
+        launch_reset_kernel(ctx, ctx->d_pool, mode, mode == rf::kEnvResetPlan ? ctx->d_actions : nullptr);
+    const SecondPass second{ctx->env.done_count, ctx->env.cam_dyn2, ctx->env.rect2};
+    int rc = launch_render(ctx, d.n, d.fh, d.fh, d.spp, ctx->env.cam_dyn, ctx->env.rect, ctx->env_axis, false, &second);
+    if (rc == RF_OK)
+        rc = launch_focus(ctx, d.n, d.fh, d.fh, d.gray_mode, nullptr, true, ctx->env.done_count);
+    if (rc != RF_OK)
+        return rc;
+    hipLaunchKernelGGL(rf::env_finish_kernel, d.grid, d.block, 0, ctx->stream, ctx->env_cfg, ctx->env,
+                       (const float *)ctx->d_pool);
+    return RF_OK;
+}
+
+// May a step start?  `open_step`: what the entry point `fn` says while a two-phase step is open.
+template <typename T>
+int step_may_start(const rf_ctx *ctx, const T *host_actions, const char *fn, const char *open_step)
+{
+    RF_REQUIRE(ctx->env_ready, "%s: rf_env_configure first", fn);
+    RF_REQUIRE(ctx->env_pending < 0, "%s: %s", fn, open_step);
+    RF_REQUIRE(!ctx->env_needs_reset, "%s: a step was aborted (rf_env_reset first)", fn);
+    return check_actions(ctx, host_actions, fn);
+}
+
+// The end of a whole step in which k environments ended: the renderer holds their compacted set, or the full one.
+void finish_step(rf_ctx *ctx, int k)
+{
+    ctx->env_steps += 1;
+    ctx->env_scene_len = k > 0 ? k : ctx->env_host.n;
+    ctx->env_last_partial = k > 0;
+}
+
+bool env_one_sync(const rf_ctx *ctx)
+{
+    const int n = ctx->env_host.n, fh = ctx->env_host.frame_height;
+    const long tiles = (long)((fh + 127) / 128) * ((fh + 5) / 6); // (blocks of the default 128 x 6 tiles, rf_coop2.h)
+    return (long)n * tiles <= ctx->env_one_sync_max;
+}
+
+// Enqueues one whole step on the ctx's stream without waiting for anything: uploads, the fused pass -- or the full
+// pass and the reset pass over all n slots --, the downloads.  Used directly and under stream capture.
+int enqueue_env_step(rf_ctx *ctx, const void *actions, const float *pool, float *obs, double *rewards,
+                     uint8_t *truncated, int *count, uint8_t *host_io = nullptr)
+{
+    // host_io: the host side is an image of the device's io block (EnvIo: the pinned staging buffer of the replayed
+    // step) -- one copy in, one copy out; otherwise the caller's six separate arrays
+    const EnvLaunch d(ctx, false);
+    const size_t n = (size_t)d.n;
+    const EnvIo io(n);
+    uint8_t *const d_io = (uint8_t *)ctx->d_pool; // (the io block starts with the pool)
+    if (host_io) {
+        RF_HIP(hipMemcpyAsync(d_io, host_io, io.in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    } else {
+        RF_HIP(hipMemcpyAsync(ctx->d_actions, actions, n * 4, hipMemcpyHostToDevice, ctx->stream));
+        RF_HIP(hipMemcpyAsync(ctx->d_pool, pool, n * 8, hipMemcpyHostToDevice, ctx->stream));
+    }
+    int rc;
+    if (fused_step_possible(ctx)) {
+        rc = fused_pass(ctx, d, rf::kEnvResetPlan);
+    } else {
+        rc = full_pass(ctx, d, true, ctx->d_actions);
+        if (rc == RF_OK)
+            rc = reset_pass(ctx, d, d.n, rf::kEnvResetBoth, true);
+    }
+    if (rc != RF_OK)
+        return rc;
+    if (host_io) {
+        RF_HIP(hipMemcpyAsync(host_io + io.o_rewards, d_io + io.o_rewards, io.bytes - io.o_rewards, hipMemcpyDeviceToHost,
+                              ctx->stream));
+    } else {
+        RF_HIP(hipMemcpyAsync(count, ctx->env.done_count, 4, hipMemcpyDeviceToHost, ctx->stream));
+        RF_HIP(hipMemcpyAsync(rewards, ctx->env.reward, n * 8, hipMemcpyDeviceToHost, ctx->stream));
+        RF_HIP(hipMemcpyAsync(truncated, ctx->env.truncated, n, hipMemcpyDeviceToHost, ctx->stream));
+        RF_HIP(hipMemcpyAsync(obs, ctx->env.obs, n * 16, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    return RF_OK;
+}
+
+// The replayed step's pinned staging block (an image of the io block, `bytes`) and its graph, made when missing.
+// Capture problems are not the caller's problem: RF_OK with ctx->env_graph still null says that the graph is disabled
+// from now on and the step keeps being enqueued call by call (same kernels, same results).
+int ensure_env_graph(rf_ctx *ctx, size_t bytes)
+{
+    if (ctx->h_stage_bytes < bytes) {
+        if (ctx->env_graph)
+            (void)hipGraphExecDestroy(ctx->env_graph);
+        ctx->env_graph = nullptr;
+        if (ctx->h_stage)
+            RF_HIP(hipHostFree(ctx->h_stage));
+        ctx->h_stage = nullptr;
+        ctx->h_stage_bytes = 0;
+        RF_HIP(host_malloc((void **)&ctx->h_stage, bytes));
+        ctx->h_stage_bytes = bytes;
+    }
+    if (ctx->env_graph)
+        return RF_OK;
+    hipGraph_t captured = nullptr;
+    hipError_t he = hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal);
+    int rc = RF_OK;
+    if (he == hipSuccess) {
+        rc = enqueue_env_step(ctx, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ctx->h_stage);
+        he = hipStreamEndCapture(ctx->stream, &captured);
+        if (he == hipSuccess && rc == RF_OK && ctx->env_graph_fail_once) {
+            ctx->env_graph_fail_once = false; // test hook: behave as if instantiation had failed
+            he = hipErrorUnknown;
+        } else if (he == hipSuccess && rc == RF_OK)
+            he = hipGraphInstantiate(&ctx->env_graph, captured, nullptr, nullptr, 0);
+        if (captured)
+            (void)hipGraphDestroy(captured);
+    }
+    if (he != hipSuccess || rc != RF_OK || !ctx->env_graph) {
+        (void)hipGetLastError();
+        ctx->env_graph = nullptr;
+        ctx->env_graph_enabled = false;
+    }
+    return RF_OK;
+}
+
+// First half of a step: transform, enders, full render + focus, observations, rewards, flags, and
+// the ranking of the environments that ended (vector_environment.py:124-135).  Synchronises once:
+// *k, rewards and truncated are final on return; the observations of the environments that did not
+// end are final on the device.
+int env_step_begin(rf_ctx *ctx, const void *host_actions, double *host_rewards, uint8_t *host_truncated, int *k)
+{
+    const EnvLaunch d(ctx, true);
+    const size_t n = (size_t)d.n;
+    RF_HIP(hipMemcpyAsync(ctx->d_actions, host_actions, n * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = full_pass(ctx, d, true, ctx->d_actions))
+        return rc;
+    launch_reset_kernel(ctx, nullptr, rf::kEnvResetRank, nullptr);
+    RF_HIP(hipGetLastError());
+    RF_HIP(hipMemcpyAsync(k, ctx->env.done_count, 4, hipMemcpyDeviceToHost, ctx->stream));
+    RF_HIP(hipMemcpyAsync(host_rewards, ctx->env.reward, n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    RF_HIP(hipMemcpyAsync(host_truncated, ctx->env.truncated, n, hipMemcpyDeviceToHost, ctx->stream));
+    RF_HIP(hipStreamSynchronize(ctx->stream));
+    return RF_OK;
+}
+
+// Second half: the k environments that ended take host_pool's rows 0..k-1 in index order and are rendered and scored
+// again (the reset pass, sized by k) -- or, with host_focus, take the focus values that were measured elsewhere.
+int env_step_end(rf_ctx *ctx, const float *host_pool, const double *host_focus, int k, float *host_obs)
+{
+    const EnvLaunch d(ctx, true);
+    if (k > 0) {
+        RF_HIP(hipMemcpyAsync(ctx->d_pool, host_pool, (size_t)k * 8, hipMemcpyHostToDevice, ctx->stream));
+        if (host_focus) // (they take the place launch_focus would have filled)
+            RF_HIP(hipMemcpyAsync(ctx->d_var, host_focus, (size_t)k * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        if (int rc = reset_pass(ctx, d, k, rf::kEnvResetApply, host_focus == nullptr))
+            return rc;
+        RF_HIP(hipGetLastError());
+    }
+    RF_HIP(hipMemcpyAsync(host_obs, ctx->env.obs, (size_t)d.n * 16, hipMemcpyDeviceToHost, ctx->stream));
+    RF_HIP(hipStreamSynchronize(ctx->stream));
+    return RF_OK;
+}
+
+// rf_env_step / rf_env_step_jumps: T = int32_t or float (check_actions)
+template <typename T>
+int env_step(rf_ctx *ctx, const T *host_actions, const float *host_pool, float *host_obs, double *host_rewards,
+             uint8_t *host_truncated, int *host_n_reset, const char *fn)
+{
+    RF_REQUIRE(ctx != nullptr && host_actions && host_pool && host_obs && host_rewards && host_truncated,
+               "%s: NULL argument", fn);
+    if (int rc = step_may_start(ctx, host_actions, fn, "a two-phase step is open (rf_env_step_end first)"))
+        return rc;
+    const EnvLaunch d(ctx, false);
+    const size_t n = (size_t)d.n;
+    int k = 0;
+    // vector_environment.py:137-151: the envs that just ended are rendered again.  Small
+    // configurations are launch- and sync-bound: their step is enqueued in one go (see
+    // enqueue_env_step) and, from the second step on (all buffers have their final size by then),
+    // replayed as one hipGraph through pinned staging buffers; it ends with its only host
+    // synchronisation.  Large ones size the auto-reset launch by the count, which costs one round
+    // trip and saves up to a few hundred thousand empty blocks.
+    const bool fused = fused_step_possible(ctx); // (one render launch, no count to wait for: enqueued in one go at any size)
+    if (fused || env_one_sync(ctx)) {
+        const EnvIo io(n);
+        bool graph = ctx->env_graph_enabled && !ctx->timing && ctx->env_steps >= 1;
+        if (graph) {
+            if (int rc = ensure_env_graph(ctx, io.bytes))
+                return rc;
+            graph = ctx->env_graph != nullptr;
+        }
+        if (graph) {
+            uint8_t *st = ctx->h_stage;
+            memcpy(st + io.o_actions, host_actions, n * 4);
+            memcpy(st + io.o_pool, host_pool, n * 8);
+            RF_HIP(hipGraphLaunch(ctx->env_graph, ctx->stream));
+            RF_HIP(hipStreamSynchronize(ctx->stream));
+            memcpy(host_obs, st + io.o_obs, n * 16);
+            memcpy(host_rewards, st + io.o_rewards, n * 8);
+            memcpy(host_truncated, st + io.o_truncated, n);
+            k = *(const int *)(st + io.o_count);
+            ctx->env_last_branch = fused ? RF_ENV_BRANCH_FUSED_GRAPH : RF_ENV_BRANCH_GRAPH;
+        } else {
+            int rc = enqueue_env_step(ctx, host_actions, host_pool, host_obs, host_rewards, host_truncated, &k);
+            if (rc != RF_OK)
+                return rc;
+            RF_HIP(hipGetLastError());
+            RF_HIP(hipStreamSynchronize(ctx->stream));
+            ctx->env_last_branch = fused ? RF_ENV_BRANCH_FUSED : RF_ENV_BRANCH_ONE_SYNC;
+        }
+        // what this step really rendered: all n environments, then the k that ended (the other slots of the
+        // second launch exit at once)
+        rfh::count_pixels(d.pixels(d.n + k));
+    } else {
+        // the step's flags and rewards are final after the first half; the count sizes the partial render
+        int rc = env_step_begin(ctx, host_actions, host_rewards, host_truncated, &k);
+        if (rc == RF_OK)
+            rc = env_step_end(ctx, host_pool, nullptr, k, host_obs);
+        if (rc != RF_OK)
+            return rc;
+        ctx->env_last_branch = RF_ENV_BRANCH_COUNT_SIZED;
+    }
+    finish_step(ctx, k);
+    if (host_n_reset)
+        *host_n_reset = k;
+    return RF_OK;
+}
+
+template <typename T>
+int env_step_begin_checked(rf_ctx *ctx, const T *host_actions, double *host_rewards, uint8_t *host_truncated,
+                           int *host_n_reset, const char *fn)
+{
+    RF_REQUIRE(ctx != nullptr && host_actions && host_rewards && host_truncated && host_n_reset, "%s: NULL argument", fn);
+    if (int rc = step_may_start(ctx, host_actions, fn, "the previous step was not finished (rf_env_step_end)"))
+        return rc;
+    drop_env_graph(ctx);
+    int k = 0;
+    int rc = env_step_begin(ctx, host_actions, host_rewards, host_truncated, &k);
+    if (rc != RF_OK)
+        return rc;
+    ctx->env_pending = k;
+    *host_n_reset = k;
+    return RF_OK;
+}
+
+template <typename T>
+int env_step_plan(rf_ctx *ctx, const T *host_actions, int *host_n_reset, const char *fn)
+{
+    RF_REQUIRE(ctx != nullptr && host_actions && host_n_reset, "%s: NULL argument", fn);
+    if (int rc = step_may_start(ctx, host_actions, fn, "the previous step was not finished"))
+        return rc;
+    drop_env_graph(ctx);
+    RF_HIP(hipMemcpyAsync(ctx->d_actions, host_actions, (size_t)ctx->env_host.n * 4, hipMemcpyHostToDevice, ctx->stream));
+    // the kernel below applies the actions and advances the counters: from here until the step is open (a HIP failure
+    // returns early) only a reset makes the environment usable again -- a retried step would apply the actions twice
+    ctx->env_needs_reset = true;
+    launch_reset_kernel(ctx, nullptr, rf::kEnvResetRank, ctx->d_actions);
+    RF_HIP(hipGetLastError());
+    int k = 0;
+    RF_HIP(hipMemcpyAsync(&k, ctx->env.done_count, 4, hipMemcpyDeviceToHost, ctx->stream));
+    RF_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->env_pending = k;
+    ctx->env_planned = true;
+    ctx->env_needs_reset = false;
+    *host_n_reset = k;
+    return RF_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -406,324 +736,17 @@ int rf_env_reset(rf_ctx *ctx, const float *host_states, float *host_obs)
     ctx->env_pending = -1;
     ctx->env_planned = false;
     ctx->env_needs_reset = false;
-    const rf_env_config &h = ctx->env_host;
-    const int n = h.n, fh = h.frame_height;
-    RF_HIP(hipMemcpyAsync(ctx->env.state, host_states, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    const dim3 grid((n + 255) / 256), block(256);
-    hipLaunchKernelGGL(rf::env_pre_kernel, grid, block, 0, ctx->stream, ctx->env_cfg, ctx->env, (const int *)nullptr);
-    int rc = launch_render(ctx, n, fh, fh, h.spp, ctx->env.cam_dyn, ctx->env.rect, ctx->env_axis);
-    if (rc == RF_OK && fused_step_possible(ctx))
-        rc = ensure_frames2(ctx, n, fh, fh); // (not inside a step: the first one after this may already be captured)
-    if (rc == RF_OK)
-        rc = launch_focus(ctx, n, fh, fh, h.gray_mode, nullptr, true);
-    if (rc != RF_OK)
+    const EnvLaunch d(ctx, true);
+    RF_HIP(hipMemcpyAsync(ctx->env.state, host_states, (size_t)d.n * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = full_pass(ctx, d, true, nullptr))
         return rc;
-    hipLaunchKernelGGL(rf::env_post_kernel, grid, block, 0, ctx->stream, ctx->env_cfg, ctx->env,
-                       (const double *)nullptr, 1);
     RF_HIP(hipGetLastError());
-    RF_HIP(hipMemcpyAsync(host_obs, ctx->env.obs, (size_t)n * 16, hipMemcpyDeviceToHost, ctx->stream));
+    RF_HIP(hipMemcpyAsync(host_obs, ctx->env.obs, (size_t)d.n * 16, hipMemcpyDeviceToHost, ctx->stream));
     RF_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->env_scene_len = n;
+    ctx->env_scene_len = d.n;
     ctx->env_last_partial = false;
     return RF_OK;
 }
-
-} // extern "C"
-
-namespace {
-
-bool env_one_sync(const rf_ctx *ctx)
-{
-    const int n = ctx->env_host.n, fh = ctx->env_host.frame_height;
-    const long tiles = (long)((fh + 127) / 128) * ((fh + 5) / 6); // (blocks of the default 128 x 6 tiles, rf_coop2.h)
-    return (long)n * tiles <= ctx->env_one_sync_max;
-}
-
-// Enqueues one whole step on the ctx's stream without waiting for anything: uploads, the full
-// render + focus, the glue kernels, the auto-reset render for all n slots (env_reset_kernel marks
-// the unused ones, whose blocks exit at once), the downloads.  Used directly and under stream
-// capture.
-int enqueue_env_step(rf_ctx *ctx, const void *actions, const float *pool, float *obs, double *rewards,
-                     uint8_t *truncated, int *count, uint8_t *host_io = nullptr)
-{
-    // host_io: the host side is an image of the device's io block (EnvIo: the pinned staging buffer of the replayed
-    // step) -- one copy in, one copy out; otherwise the caller's six separate arrays
-    const rf_env_config &h = ctx->env_host;
-    const int n = h.n, fh = h.frame_height;
-    const dim3 grid((n + 255) / 256), block(256);
-    const EnvIo io((size_t)n);
-    uint8_t *const d_io = (uint8_t *)ctx->d_pool; // (the io block starts with the pool)
-    if (host_io) {
-        RF_HIP(hipMemcpyAsync(d_io, host_io, io.in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    } else {
-        RF_HIP(hipMemcpyAsync(ctx->d_actions, actions, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-        RF_HIP(hipMemcpyAsync(ctx->d_pool, pool, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    }
-    int rc = RF_OK;
-    if (fused_step_possible(ctx)) {
-        // One render launch and one focus launch per step.  Which environments end depends on their counters alone
-        // (env_pre_kernel), so they are ranked and the compacted scene of the auto-reset is packed BEFORE the render;
-        // the r-th of them is rendered as row r of that set with the RNG streams of slot r (render.py:217), i.e. right
-        // after slot r's own frame: the blocks of the slots below the count make two passes (render_kernel_coop2<.., TWO>).
-        // The step's frames of those slots go to frames2, so that the frame buffer ends up as the two launches leave it.
-        hipLaunchKernelGGL(rf::env_reset_kernel, dim3(1), dim3(1024), 0, ctx->stream, ctx->env_cfg, ctx->env,
-                           (const float *)ctx->d_pool, rf::kEnvResetPlan, (const int *)ctx->d_actions);
-        const SecondPass second{ctx->env.done_count, ctx->env.cam_dyn2, ctx->env.rect2};
-        rc = launch_render(ctx, n, fh, fh, h.spp, ctx->env.cam_dyn, ctx->env.rect, ctx->env_axis, false, &second);
-        if (rc == RF_OK)
-            rc = launch_focus(ctx, n, fh, fh, h.gray_mode, nullptr, true, ctx->env.done_count);
-        if (rc != RF_OK)
-            return rc;
-        hipLaunchKernelGGL(rf::env_finish_kernel, grid, block, 0, ctx->stream, ctx->env_cfg, ctx->env,
-                           (const float *)ctx->d_pool);
-    } else {
-        hipLaunchKernelGGL(rf::env_pre_kernel, grid, block, 0, ctx->stream, ctx->env_cfg, ctx->env,
-                           (const int *)ctx->d_actions);
-        rc = launch_render(ctx, n, fh, fh, h.spp, ctx->env.cam_dyn, ctx->env.rect, ctx->env_axis, false);
-        if (rc == RF_OK)
-            rc = launch_focus(ctx, n, fh, fh, h.gray_mode, nullptr, true);
-        if (rc != RF_OK)
-            return rc;
-        hipLaunchKernelGGL(rf::env_post_kernel, grid, block, 0, ctx->stream, ctx->env_cfg, ctx->env,
-                           (const double *)nullptr, 0);
-        hipLaunchKernelGGL(rf::env_reset_kernel, dim3(1), dim3(1024), 0, ctx->stream, ctx->env_cfg, ctx->env,
-                           (const float *)ctx->d_pool, rf::kEnvResetBoth);
-        rc = launch_render(ctx, n, fh, fh, h.spp, ctx->env.cam_dyn2, ctx->env.rect2, ctx->env_axis, false);
-        if (rc == RF_OK)
-            rc = launch_focus(ctx, n, fh, fh, h.gray_mode, ctx->env.rect2, true);
-        if (rc != RF_OK)
-            return rc;
-        hipLaunchKernelGGL(rf::env_reset_post_kernel, grid, block, 0, ctx->stream, ctx->env_cfg, ctx->env,
-                           (const double *)nullptr, (const float *)nullptr);
-    }
-    if (host_io) {
-        RF_HIP(hipMemcpyAsync(host_io + io.o_rewards, d_io + io.o_rewards, io.bytes - io.o_rewards, hipMemcpyDeviceToHost,
-                              ctx->stream));
-    } else {
-        RF_HIP(hipMemcpyAsync(count, ctx->env.done_count, 4, hipMemcpyDeviceToHost, ctx->stream));
-        RF_HIP(hipMemcpyAsync(rewards, ctx->env.reward, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
-        RF_HIP(hipMemcpyAsync(truncated, ctx->env.truncated, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-        RF_HIP(hipMemcpyAsync(obs, ctx->env.obs, (size_t)n * 16, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    return RF_OK;
-}
-
-// First half of a step: transform, enders, full render + focus, observations, rewards, flags, and
-// the ranking of the environments that ended (vector_environment.py:124-135).  Synchronises once:
-// *k, rewards and truncated are final on return; the observations of the environments that did not
-// end are final on the device.
-int env_step_begin(rf_ctx *ctx, const void *host_actions, double *host_rewards, uint8_t *host_truncated, int *k)
-{
-    const rf_env_config &h = ctx->env_host;
-    const int n = h.n, fh = h.frame_height;
-    RF_HIP(hipMemcpyAsync(ctx->d_actions, host_actions, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    const dim3 grid((n + 255) / 256), block(256);
-    hipLaunchKernelGGL(rf::env_pre_kernel, grid, block, 0, ctx->stream, ctx->env_cfg, ctx->env,
-                       (const int *)ctx->d_actions);
-    int rc = launch_render(ctx, n, fh, fh, h.spp, ctx->env.cam_dyn, ctx->env.rect, ctx->env_axis);
-    if (rc == RF_OK)
-        rc = launch_focus(ctx, n, fh, fh, h.gray_mode, nullptr, true);
-    if (rc != RF_OK)
-        return rc;
-    hipLaunchKernelGGL(rf::env_post_kernel, grid, block, 0, ctx->stream, ctx->env_cfg, ctx->env,
-                       (const double *)nullptr, 0);
-    hipLaunchKernelGGL(rf::env_reset_kernel, dim3(1), dim3(1024), 0, ctx->stream, ctx->env_cfg, ctx->env,
-                       (const float *)nullptr, rf::kEnvResetRank);
-    RF_HIP(hipGetLastError());
-    RF_HIP(hipMemcpyAsync(k, ctx->env.done_count, 4, hipMemcpyDeviceToHost, ctx->stream));
-    RF_HIP(hipMemcpyAsync(host_rewards, ctx->env.reward, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    RF_HIP(hipMemcpyAsync(host_truncated, ctx->env.truncated, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    RF_HIP(hipStreamSynchronize(ctx->stream));
-    return RF_OK;
-}
-
-// Second half: the k environments that ended take host_pool's rows 0..k-1 in index order and are
-// rendered and scored again (vector_environment.py:137-151), with the launch sized by k.
-int env_step_end(rf_ctx *ctx, const float *host_pool, int k, float *host_obs)
-{
-    const rf_env_config &h = ctx->env_host;
-    const int n = h.n, fh = h.frame_height;
-    if (k > 0) {
-        RF_HIP(hipMemcpyAsync(ctx->d_pool, host_pool, (size_t)k * 8, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(rf::env_reset_kernel, dim3(1), dim3(1024), 0, ctx->stream, ctx->env_cfg, ctx->env,
-                           (const float *)ctx->d_pool, rf::kEnvResetApply);
-        int rc = launch_render(ctx, k, fh, fh, h.spp, ctx->env.cam_dyn2, ctx->env.rect2, ctx->env_axis);
-        if (rc == RF_OK)
-            rc = launch_focus(ctx, k, fh, fh, h.gray_mode, nullptr, true);
-        if (rc != RF_OK)
-            return rc;
-        hipLaunchKernelGGL(rf::env_reset_post_kernel, dim3((k + 255) / 256), dim3(256), 0, ctx->stream, ctx->env_cfg,
-                           ctx->env, (const double *)nullptr, (const float *)nullptr);
-        RF_HIP(hipGetLastError());
-    }
-    RF_HIP(hipMemcpyAsync(host_obs, ctx->env.obs, (size_t)n * 16, hipMemcpyDeviceToHost, ctx->stream));
-    RF_HIP(hipStreamSynchronize(ctx->stream));
-    return RF_OK;
-}
-
-// rf_env_step / rf_env_step_jumps: T = int32_t or float (check_actions)
-template <typename T>
-int env_step(rf_ctx *ctx, const T *host_actions, const float *host_pool, float *host_obs, double *host_rewards,
-             uint8_t *host_truncated, int *host_n_reset, const char *fn)
-{
-    RF_REQUIRE(ctx != nullptr && host_actions && host_pool && host_obs && host_rewards && host_truncated,
-               "%s: NULL argument", fn);
-    RF_REQUIRE(ctx->env_ready, "%s: rf_env_configure first", fn);
-    RF_REQUIRE(ctx->env_pending < 0, "%s: a two-phase step is open (rf_env_step_end first)", fn);
-    RF_REQUIRE(!ctx->env_needs_reset, "%s: a step was aborted (rf_env_reset first)", fn);
-    if (int rc = check_actions(ctx, host_actions, fn))
-        return rc;
-    const rf_env_config &h = ctx->env_host;
-    const int n = h.n;
-    int k = 0;
-    // vector_environment.py:137-151: the envs that just ended are rendered again.  Small
-    // configurations are launch- and sync-bound: their step is enqueued in one go (see
-    // enqueue_env_step) and, from the second step on (all buffers have their final size by then),
-    // replayed as one hipGraph through pinned staging buffers; it ends with its only host
-    // synchronisation.  Large ones size the auto-reset launch by the count, which costs one round
-    // trip and saves up to a few hundred thousand empty blocks.
-    const bool fused = fused_step_possible(ctx); // (one render launch, no count to wait for: enqueued in one go at any size)
-    if (fused || env_one_sync(ctx)) {
-        const EnvIo io((size_t)n);
-        const size_t bytes = io.bytes;
-        const bool graph = ctx->env_graph_enabled && !ctx->timing && ctx->env_steps >= 1;
-        if (!graph) {
-            int rc = enqueue_env_step(ctx, host_actions, host_pool, host_obs, host_rewards, host_truncated, &k);
-            if (rc != RF_OK)
-                return rc;
-            RF_HIP(hipGetLastError());
-            RF_HIP(hipStreamSynchronize(ctx->stream));
-            ctx->env_last_branch = fused ? RF_ENV_BRANCH_FUSED : RF_ENV_BRANCH_ONE_SYNC;
-        } else {
-            if (ctx->h_stage_bytes < bytes) {
-                if (ctx->env_graph)
-                    (void)hipGraphExecDestroy(ctx->env_graph);
-                ctx->env_graph = nullptr;
-                if (ctx->h_stage)
-                    RF_HIP(hipHostFree(ctx->h_stage));
-                ctx->h_stage = nullptr;
-                ctx->h_stage_bytes = 0;
-                RF_HIP(host_malloc((void **)&ctx->h_stage, bytes));
-                ctx->h_stage_bytes = bytes;
-            }
-            uint8_t *st = ctx->h_stage;
-            if (!ctx->env_graph) {
-                // Capture problems are not the caller's problem: the step then simply keeps being
-                // enqueued call by call (same kernels, same results).
-                hipGraph_t captured = nullptr;
-                hipError_t he = hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal);
-                int rc = RF_OK;
-                if (he == hipSuccess) {
-                    rc = enqueue_env_step(ctx, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, st);
-                    he = hipStreamEndCapture(ctx->stream, &captured);
-                    if (he == hipSuccess && rc == RF_OK && ctx->env_graph_fail_once) {
-                        ctx->env_graph_fail_once = false; // test hook: behave as if instantiation had failed
-                        he = hipErrorUnknown;
-                    } else if (he == hipSuccess && rc == RF_OK)
-                        he = hipGraphInstantiate(&ctx->env_graph, captured, nullptr, nullptr, 0);
-                    if (captured)
-                        (void)hipGraphDestroy(captured);
-                }
-                if (he != hipSuccess || rc != RF_OK || !ctx->env_graph) {
-                    (void)hipGetLastError();
-                    ctx->env_graph = nullptr;
-                    ctx->env_graph_enabled = false;
-                    rc = enqueue_env_step(ctx, host_actions, host_pool, host_obs, host_rewards, host_truncated, &k);
-                    if (rc != RF_OK)
-                        return rc;
-                    RF_HIP(hipGetLastError());
-                    RF_HIP(hipStreamSynchronize(ctx->stream));
-                    rfh::count_pixels((unsigned long long)(n + k) * (unsigned long long)h.frame_height * h.frame_height);
-                    ctx->env_steps += 1;
-                    ctx->env_scene_len = k > 0 ? k : n;
-                    ctx->env_last_partial = k > 0;
-                    ctx->env_last_branch = fused ? RF_ENV_BRANCH_FUSED : RF_ENV_BRANCH_ONE_SYNC;
-                    if (host_n_reset)
-                        *host_n_reset = k;
-                    return RF_OK;
-                }
-            }
-            memcpy(st + io.o_actions, host_actions, (size_t)n * 4);
-            memcpy(st + io.o_pool, host_pool, (size_t)n * 8);
-            RF_HIP(hipGraphLaunch(ctx->env_graph, ctx->stream));
-            RF_HIP(hipStreamSynchronize(ctx->stream));
-            memcpy(host_obs, st + io.o_obs, (size_t)n * 16);
-            memcpy(host_rewards, st + io.o_rewards, (size_t)n * 8);
-            memcpy(host_truncated, st + io.o_truncated, (size_t)n);
-            k = *(const int *)(st + io.o_count);
-            ctx->env_last_branch = fused ? RF_ENV_BRANCH_FUSED_GRAPH : RF_ENV_BRANCH_GRAPH;
-        }
-        // what this step really rendered: all n environments, then the k that ended (the other slots of the
-        // second launch exit at once)
-        rfh::count_pixels((unsigned long long)(n + k) * (unsigned long long)h.frame_height * h.frame_height);
-    } else {
-        // the step's flags and rewards are final after the first half; the count sizes the partial render
-        int rc = env_step_begin(ctx, host_actions, host_rewards, host_truncated, &k);
-        if (rc == RF_OK)
-            rc = env_step_end(ctx, host_pool, k, host_obs);
-        if (rc != RF_OK)
-            return rc;
-        ctx->env_last_branch = RF_ENV_BRANCH_COUNT_SIZED;
-    }
-    ctx->env_steps += 1;
-    ctx->env_scene_len = k > 0 ? k : n;
-    ctx->env_last_partial = k > 0;
-    if (host_n_reset)
-        *host_n_reset = k;
-    return RF_OK;
-}
-
-template <typename T>
-int env_step_begin_checked(rf_ctx *ctx, const T *host_actions, double *host_rewards, uint8_t *host_truncated,
-                           int *host_n_reset, const char *fn)
-{
-    RF_REQUIRE(ctx != nullptr && host_actions && host_rewards && host_truncated && host_n_reset, "%s: NULL argument", fn);
-    RF_REQUIRE(ctx->env_ready, "%s: rf_env_configure first", fn);
-    RF_REQUIRE(ctx->env_pending < 0, "%s: the previous step was not finished (rf_env_step_end)", fn);
-    RF_REQUIRE(!ctx->env_needs_reset, "%s: a step was aborted (rf_env_reset first)", fn);
-    if (int rc = check_actions(ctx, host_actions, fn))
-        return rc;
-    drop_env_graph(ctx);
-    int k = 0;
-    int rc = env_step_begin(ctx, host_actions, host_rewards, host_truncated, &k);
-    if (rc != RF_OK)
-        return rc;
-    ctx->env_pending = k;
-    *host_n_reset = k;
-    return RF_OK;
-}
-
-template <typename T>
-int env_step_plan(rf_ctx *ctx, const T *host_actions, int *host_n_reset, const char *fn)
-{
-    RF_REQUIRE(ctx != nullptr && host_actions && host_n_reset, "%s: NULL argument", fn);
-    RF_REQUIRE(ctx->env_ready, "%s: rf_env_configure first", fn);
-    RF_REQUIRE(ctx->env_pending < 0, "%s: the previous step was not finished", fn);
-    RF_REQUIRE(!ctx->env_needs_reset, "%s: a step was aborted (rf_env_reset first)", fn);
-    if (int rc = check_actions(ctx, host_actions, fn))
-        return rc;
-    drop_env_graph(ctx);
-    const rf_env_config &h = ctx->env_host;
-    RF_HIP(hipMemcpyAsync(ctx->d_actions, host_actions, (size_t)h.n * 4, hipMemcpyHostToDevice, ctx->stream));
-    // the kernel below applies the actions and advances the counters: from here until the step is open (a HIP failure
-    // returns early) only a reset makes the environment usable again -- a retried step would apply the actions twice
-    ctx->env_needs_reset = true;
-    hipLaunchKernelGGL(rf::env_reset_kernel, dim3(1), dim3(1024), 0, ctx->stream, ctx->env_cfg, ctx->env,
-                       (const float *)nullptr, rf::kEnvResetRank, (const int *)ctx->d_actions);
-    RF_HIP(hipGetLastError());
-    int k = 0;
-    RF_HIP(hipMemcpyAsync(&k, ctx->env.done_count, 4, hipMemcpyDeviceToHost, ctx->stream));
-    RF_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->env_pending = k;
-    ctx->env_planned = true;
-    ctx->env_needs_reset = false;
-    *host_n_reset = k;
-    return RF_OK;
-}
-
-} // namespace
-
-extern "C" {
 
 int rf_env_step(rf_ctx *ctx, const int32_t *host_actions, const float *host_pool, float *host_obs,
                 double *host_rewards, uint8_t *host_truncated, int *host_n_reset)
@@ -775,14 +798,11 @@ int rf_env_step_end(rf_ctx *ctx, const float *host_pool, float *host_obs)
     RF_HIP(hipSetDevice(ctx->device));
     const int k = ctx->env_pending;
     ctx->env_pending = -1;
-    int rc = env_step_end(ctx, host_pool, k, host_obs);
-    if (rc == RF_OK) {
-        ctx->env_steps += 1;
-        ctx->env_scene_len = k > 0 ? k : ctx->env_host.n;
-        ctx->env_last_partial = k > 0;
-    } else {
+    int rc = env_step_end(ctx, host_pool, nullptr, k, host_obs);
+    if (rc == RF_OK)
+        finish_step(ctx, k);
+    else
         ctx->env_needs_reset = true; // the second half failed part way: only a reset makes the environment usable again
-    }
     return rc;
 }
 
@@ -811,54 +831,28 @@ int rf_env_step_run(rf_ctx *ctx, const float *host_pool, float *host_obs, double
     ctx->env_pending = -1;
     ctx->env_planned = false;
     ctx->env_needs_reset = true; // until the step has finished (a failure below returns early)
-    const rf_env_config &h = ctx->env_host;
-    const int n = h.n, fh = h.frame_height;
-    const dim3 grid((n + 255) / 256), block(256);
-    int rc = RF_OK;
+    const EnvLaunch d(ctx, false);
+    const size_t n = (size_t)d.n;
     if (k > 0)
         RF_HIP(hipMemcpyAsync(ctx->d_pool, host_pool, (size_t)k * 8, hipMemcpyHostToDevice, ctx->stream));
+    int rc;
     if (fused_step_possible(ctx)) {
-        if (k > 0)
-            hipLaunchKernelGGL(rf::env_reset_kernel, dim3(1), dim3(1024), 0, ctx->stream, ctx->env_cfg, ctx->env,
-                               (const float *)ctx->d_pool, rf::kEnvResetPack, (const int *)nullptr);
-        const SecondPass second{ctx->env.done_count, ctx->env.cam_dyn2, ctx->env.rect2};
-        rc = launch_render(ctx, n, fh, fh, h.spp, ctx->env.cam_dyn, ctx->env.rect, ctx->env_axis, false, &second);
-        if (rc == RF_OK)
-            rc = launch_focus(ctx, n, fh, fh, h.gray_mode, nullptr, true, ctx->env.done_count);
-        if (rc != RF_OK)
-            return rc;
-        hipLaunchKernelGGL(rf::env_finish_kernel, grid, block, 0, ctx->stream, ctx->env_cfg, ctx->env,
-                           (const float *)ctx->d_pool);
-    } else {
-        rc = launch_render(ctx, n, fh, fh, h.spp, ctx->env.cam_dyn, ctx->env.rect, ctx->env_axis, false);
-        if (rc == RF_OK)
-            rc = launch_focus(ctx, n, fh, fh, h.gray_mode, nullptr, true);
-        if (rc != RF_OK)
-            return rc;
-        hipLaunchKernelGGL(rf::env_post_kernel, grid, block, 0, ctx->stream, ctx->env_cfg, ctx->env,
-                           (const double *)nullptr, 0);
-        if (k > 0) {
-            hipLaunchKernelGGL(rf::env_reset_kernel, dim3(1), dim3(1024), 0, ctx->stream, ctx->env_cfg, ctx->env,
-                               (const float *)ctx->d_pool, rf::kEnvResetApply, (const int *)nullptr);
-            rc = launch_render(ctx, k, fh, fh, h.spp, ctx->env.cam_dyn2, ctx->env.rect2, ctx->env_axis, false);
-            if (rc == RF_OK)
-                rc = launch_focus(ctx, k, fh, fh, h.gray_mode, nullptr, true);
-            if (rc != RF_OK)
-                return rc;
-            hipLaunchKernelGGL(rf::env_reset_post_kernel, dim3((k + 255) / 256), dim3(256), 0, ctx->stream, ctx->env_cfg,
-                               ctx->env, (const double *)nullptr, (const float *)nullptr);
-        }
+        rc = fused_pass(ctx, d, k > 0 ? rf::kEnvResetPack : kEnvResetNone);
+    } else { // (env_pre_kernel's work was rf_env_step_plan's)
+        rc = full_pass(ctx, d, false, nullptr);
+        if (rc == RF_OK && k > 0)
+            rc = reset_pass(ctx, d, k, rf::kEnvResetApply, true);
     }
+    if (rc != RF_OK)
+        return rc;
     RF_HIP(hipGetLastError());
-    RF_HIP(hipMemcpyAsync(host_rewards, ctx->env.reward, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    RF_HIP(hipMemcpyAsync(host_truncated, ctx->env.truncated, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    RF_HIP(hipMemcpyAsync(host_obs, ctx->env.obs, (size_t)n * 16, hipMemcpyDeviceToHost, ctx->stream));
+    RF_HIP(hipMemcpyAsync(host_rewards, ctx->env.reward, n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    RF_HIP(hipMemcpyAsync(host_truncated, ctx->env.truncated, n, hipMemcpyDeviceToHost, ctx->stream));
+    RF_HIP(hipMemcpyAsync(host_obs, ctx->env.obs, n * 16, hipMemcpyDeviceToHost, ctx->stream));
     RF_HIP(hipStreamSynchronize(ctx->stream));
-    rfh::count_pixels((unsigned long long)(n + k) * (unsigned long long)fh * fh);
+    rfh::count_pixels(d.pixels(d.n + k));
     ctx->env_needs_reset = false;
-    ctx->env_steps += 1;
-    ctx->env_scene_len = k > 0 ? k : n;
-    ctx->env_last_partial = k > 0;
+    finish_step(ctx, k);
     return RF_OK;
 }
 
@@ -887,6 +881,7 @@ int rf_env_render_states(rf_ctx *ctx, int k, const float *host_states, double *h
     return RF_OK;
 }
 
+
 int rf_env_step_end_given(rf_ctx *ctx, const float *host_pool, const double *host_focus, float *host_obs)
 {
     RF_REQUIRE(ctx != nullptr && host_obs != nullptr, "rf_env_step_end_given: NULL argument");
@@ -898,24 +893,12 @@ int rf_env_step_end_given(rf_ctx *ctx, const float *host_pool, const double *hos
     RF_HIP(hipSetDevice(ctx->device));
     ctx->env_pending = -1;
     ctx->env_needs_reset = true; // until the second half has finished (a HIP failure below returns early)
-    const int n = ctx->env_host.n;
-    if (k > 0) {
-        RF_HIP(hipMemcpyAsync(ctx->d_pool, host_pool, (size_t)k * 8, hipMemcpyHostToDevice, ctx->stream));
-        // the focus values were measured elsewhere: they take the place launch_focus would have filled
-        RF_HIP(hipMemcpyAsync(ctx->d_var, host_focus, (size_t)k * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(rf::env_reset_kernel, dim3(1), dim3(1024), 0, ctx->stream, ctx->env_cfg, ctx->env,
-                           (const float *)ctx->d_pool, rf::kEnvResetApply);
-        hipLaunchKernelGGL(rf::env_reset_post_kernel, dim3((k + 255) / 256), dim3(256), 0, ctx->stream, ctx->env_cfg,
-                           ctx->env, (const double *)ctx->d_var, (const float *)nullptr);
-        RF_HIP(hipGetLastError());
-    }
-    RF_HIP(hipMemcpyAsync(host_obs, ctx->env.obs, (size_t)n * 16, hipMemcpyDeviceToHost, ctx->stream));
-    RF_HIP(hipStreamSynchronize(ctx->stream));
+    if (int rc = env_step_end(ctx, host_pool, host_focus, k, host_obs))
+        return rc;
     ctx->env_needs_reset = false;
-    ctx->env_steps += 1;
+    ctx->env_steps += 1; // (the renderer's scene set is not this step's: rf_env_render_states says what it holds)
     return RF_OK;
 }
-
 int rf_env_step_abort(rf_ctx *ctx)
 {
     RF_REQUIRE(ctx != nullptr, "rf_env_step_abort: ctx is NULL");
@@ -983,3 +966,4 @@ int rf_env_get_states(rf_ctx *ctx, float *host_states)
 }
 
 } // extern "C"
+

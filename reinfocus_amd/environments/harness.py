@@ -633,9 +633,21 @@ class _DeviceVectorEnv(_VectorEnvBase):
     def _state(self):
         return self._ctx.env_states()
 
+    # -- what the tasks and the composed environment differ in ---------------------------------
+    def _reseed(self, seed):
+        self._initializer = _Initializer(self._limits, seed)
+
+    def _checked(self, actions):
+        """The step's actions, refused here where the task says so (the library checks the rest)."""
+        return jump_actions(actions, self.num_envs) if self._JUMPS else actions
+
+    def _float_actions(self):
+        """float32 actions (rf_env_step_jumps), not int32 indices (rf_env_step)."""
+        return self._JUMPS
+
     def reset(self, *, seed=None, options=None, state=None):
         if seed is not None:
-            self._initializer = _Initializer(self._limits, seed)
+            self._reseed(seed)
         initial = (self._initializer.initialize(self.num_envs) if state is None
                    else np.array(state, dtype=np.float32).reshape(self.num_envs, 2))
         observations = self._ctx.env_reset(initial)
@@ -644,13 +656,10 @@ class _DeviceVectorEnv(_VectorEnvBase):
         return observations, {}
 
     def step(self, actions):
-        if self._JUMPS:
-            actions = jump_actions(actions, self.num_envs)
+        actions = self._checked(actions)
         pool = self._initializer.propose(self.num_envs)
-        if self._JUMPS:
-            observations, rewards, truncated, used = self._ctx.env_step_jumps(actions, pool)
-        else:
-            observations, rewards, truncated, used = self._ctx.env_step(actions, pool)
+        env_step = self._ctx.env_step_jumps if self._float_actions() else self._ctx.env_step
+        observations, rewards, truncated, used = env_step(actions, pool)
         if used:
             self._initializer.initialize(used)  # consume exactly the rows that were used
         if self._visualizer is not None:  # vector_environment.py:149-156
@@ -888,15 +897,13 @@ class _ShardedVectorEnv(_VectorEnvBase):
         render that lets the second half run as ONE render launch), in the exact mode rf_env_step_begin (the cut after
         the full render: its row renders happen on other shards).  If any shard fails, the shards whose half did run
         drop it (rf_env_step_abort: they then insist on a reset) and the first error is raised."""
-        if self.exact and self._JUMPS:
-            futures = self._submit(lambda shard, a: shard.ctx.env_step_begin_jumps(a), self._slices(actions))
-        elif self.exact:
-            futures = self._submit(lambda shard, a: shard.ctx.env_step_begin(a), self._slices(actions))
-        elif self._JUMPS:
-            futures = self._submit(lambda shard, a: (None, None, shard.ctx.env_step_plan_jumps(a)),
-                                   self._slices(actions))
-        else:
-            futures = self._submit(lambda shard, a: (None, None, shard.ctx.env_step_plan(a)), self._slices(actions))
+        name = ("env_step_begin" if self.exact else "env_step_plan") + ("_jumps" if self._JUMPS else "")
+
+        def first_half(shard, rows):
+            result = getattr(shard.ctx, name)(rows)
+            return result if self.exact else (None, None, result)  # (rewards and flags: rf_env_step_run's)
+
+        futures = self._submit(first_half, self._slices(actions))
         results, errors = [], []
         for future in futures:
             try:
@@ -1167,28 +1174,11 @@ class DeviceVectorEnvironment(_DeviceVectorEnv):
 
         return strategy_program.device_status(self._ender, self.strategy_state(), index)
 
-    def reset(self, *, seed=None, options=None, state=None):
-        if seed is not None:
-            self._initializer.seed(seed)
-        initial = (self._initializer.initialize(self.num_envs) if state is None
-                   else np.array(state, dtype=np.float32).reshape(self.num_envs, 2))
-        observations = self._ctx.env_reset(initial)
-        if self._visualizer is not None:
-            self._visualizer.reset(initial, observations)
-        return observations, {}
+    def _reseed(self, seed):
+        self._initializer.seed(seed)
 
-    def step(self, actions):
-        actions = composed_actions(self._transformer, actions, self.num_envs, index_range=False)
-        pool = self._initializer.propose(self.num_envs)
-        if self._discrete:
-            observations, rewards, truncated, used = self._ctx.env_step(actions, pool)
-        else:
-            observations, rewards, truncated, used = self._ctx.env_step_jumps(actions, pool)
-        if used:
-            self._initializer.initialize(used)  # consume exactly the rows that were used
-        if self._visualizer is not None:  # vector_environment.py:149-156
-            state = self._state
-            if used:
-                self._visualizer.reset(state[truncated], observations[truncated], truncated)
-            self._visualizer.step(state[~truncated], observations[~truncated], ~truncated)
-        return observations, rewards, np.full(self.num_envs, False), truncated, {}
+    def _checked(self, actions):
+        return composed_actions(self._transformer, actions, self.num_envs, index_range=False)
+
+    def _float_actions(self):
+        return not self._discrete
