@@ -197,7 +197,8 @@ typedef struct rf_env_config {
 int rf_env_configure(rf_ctx *ctx, const rf_env_config *cfg);
 
 /* vector_environment.py:75-102: installs host_states float32[n][2] = [target, focus plane],
- * renders and scores every environment, returns observations float32[n][4]. */
+ * renders and scores every environment, returns observations float32[n][4] (here and below: float32[n][W] for a
+ * context configured by rf_env_configure_observed). */
 int rf_env_reset(rf_ctx *ctx, const float *host_states, float *host_obs);
 
 /* vector_environment.py:104-164: one step.  host_actions int32[n]; host_pool float32[n][2]
@@ -330,8 +331,10 @@ int rf_env_step_plan_jumps(rf_ctx *ctx, const float *host_actions, int *host_n_r
 
 /* ---- the same device-resident step for an environment composed of strategy objects ---------------------------------
  * VectorEnvironment (environments/vector_environment.py:104-164) over any transformer, ender and rewarder the
- * reference's classes can express (environments/state_transformer.py, episode_ender.py, episode_rewarder.py), with the
- * observer both tasks use: NormalizedObserver(DeltaObserver([IndexedElementObserver(1), FocusObserver])).  State is
+ * reference's classes can express (environments/state_transformer.py, episode_ender.py, episode_rewarder.py).  The
+ * observer is the one both tasks use, NormalizedObserver(DeltaObserver([IndexedElementObserver(1), FocusObserver])), for
+ * rf_env_configure_composed, and any tree of the reference's observer classes around one FocusObserver for
+ * rf_env_configure_observed (rf_env_observer_program below).  State is
  * [target, focus plane], so every state index is 0 or 1.  Python compiles the objects into an rf_env_program
  * (harness.DeviceVectorEnvironment); rf_env_configure_composed uploads it once, and every schedule of the step runs it.
  *
@@ -360,7 +363,8 @@ typedef struct rf_env_ender {
 
 typedef struct rf_env_rewarder {
     int kind;              /* RF_REWARD_* */
-    int index0, index1;    /* check_index(es); Observation: reward_observation_index (0-3) in index0 */
+    int index0, index1;    /* check_index(es); Observation: reward_observation_index in index0 (0-3; below the
+                              observation width of an rf_env_observer_program) */
     double p[3];           /* Delta: reward, scale | Distance: span, high - low, low | OnTarget: span, on - off, off
                               | Stopped: |threshold|, reward | Observation: unused */
 } rf_env_rewarder;
@@ -403,6 +407,58 @@ int rf_env_configure_composed(rf_ctx *ctx, const rf_env_config *cfg, const rf_en
  *   host_old       float32[n_rewarders][n] Delta / Stopped: the element's previous value; else 0 */
 int rf_env_get_strategy_state(rf_ctx *ctx, int32_t *host_counters, float *host_floats, float *host_histories,
                               float *host_old);
+
+/* ---- the observer of a composed environment as a program -------------------------------------------------------------
+ * Any tree of the reference's observer classes (environments/state_observer.py:100-292, :386-517) around exactly one
+ * FocusObserver(target_index 0, focus_plane_index 1), as a list of nodes in evaluation order (children before their
+ * wrapper, left to right) over a file of float32 columns per environment -- the environment's row of observations
+ * itself.  The file is a stack: a leaf writes the next free column; a wrapper works on the `width` columns its children
+ * left on top, starting at column `first`:
+ *   RF_OBS_INDEXED     column first := state[index]                              IndexedElementObserver
+ *   RF_OBS_FOCUS       column first := float32(variance of the frame's Laplacian) FocusObserver
+ *   RF_OBS_DELTA       deltas := columns - old values (float32; zero in a reset); old values := columns; the deltas
+ *                      replace the columns, or with include_original follow them (width more columns).  Its old
+ *                      values are rows old_first ... old_first + width - 1 of the old-value rows, NaN until the first
+ *                      reset                                                      DeltaObserver
+ *   RF_OBS_NORMALIZED  columns := min(max((column - mid) / scale, -1), 1), float32 NormalizedObserver
+ * The last node leaves `width` columns: the observations, float32[n][width].  n_old is the number of old-value rows.
+ * Refused (RF_ERR_INVALID, nothing changes): more than RF_ENV_MAX_OBS_NODES nodes, more than RF_ENV_MAX_OBS_COLUMNS
+ * columns at any point or old-value rows, an unknown kind, an element index outside {0, 1}, a node that does not work on
+ * the top of the stack or old-value rows that are not handed out in node order, anything other than one RF_OBS_FOCUS
+ * node, a width or n_old that is not what the nodes leave, and a NORMALIZED mid that is not finite or scale that is
+ * zero or not finite (fminf / fmaxf do not propagate NaN as numpy.clip does). */
+#define RF_ENV_MAX_OBS_NODES 16
+#define RF_ENV_MAX_OBS_COLUMNS 16
+
+enum { RF_OBS_INDEXED = 0, RF_OBS_FOCUS = 1, RF_OBS_DELTA = 2, RF_OBS_NORMALIZED = 3 };
+
+typedef struct rf_env_observer_node {
+    int kind;              /* RF_OBS_* */
+    int index;             /* INDEXED: element_index */
+    int first, width;      /* leaves: the column written, 1 | wrappers: the columns [first, first + width) worked on */
+    int include_original;  /* DELTA */
+    int old_first;         /* DELTA: first of its `width` old-value rows */
+    float mid[RF_ENV_MAX_OBS_COLUMNS], scale[RF_ENV_MAX_OBS_COLUMNS]; /* NORMALIZED: per column, float32 */
+} rf_env_observer_node;
+
+typedef struct rf_env_observer_program {
+    int n_nodes;           /* 1 ... RF_ENV_MAX_OBS_NODES */
+    int width;             /* observation columns W the last node leaves */
+    int n_old;             /* old-value rows D of all DELTA nodes */
+    rf_env_observer_node nodes[RF_ENV_MAX_OBS_NODES];
+} rf_env_observer_program;
+
+/* rf_env_configure_composed with the observer as a program too: cfg's mid / scale are ignored as well, and an
+ * ObservationRewarder's index must be below observer->width.  For a context configured so, EVERY host_obs argument of
+ * the rf_env_* calls (rf_env_reset, rf_env_step, rf_env_step_jumps, rf_env_step_end, rf_env_step_run,
+ * rf_env_step_end_given) is float32[n][observer->width] in place of float32[n][4].  rf_env_configure_composed keeps
+ * the built-in observer, and its kernels' code path. */
+int rf_env_configure_observed(rf_ctx *ctx, const rf_env_config *cfg, const rf_env_program *program,
+                              const rf_env_observer_program *observer);
+
+/* The DELTA nodes' old values of a context configured by rf_env_configure_observed, node-major: host_old
+ * float32[observer->n_old][n] (DeltaObserver._old_wrapped_observations, one row per column, in node order). */
+int rf_env_get_observer_state(rf_ctx *ctx, float *host_old);
 
 #ifdef __cplusplus
 }

@@ -67,6 +67,8 @@ SYMBOLS = (
     "rf_env_step_plan_jumps",
     "rf_env_configure_composed",
     "rf_env_get_strategy_state",
+    "rf_env_configure_observed",
+    "rf_env_get_observer_state",
     "rf_render_kernel_name",
     "rf_pixels_rendered",
     "rf_allocations_poisoned",
@@ -146,6 +148,26 @@ class EnvProgram(ctypes.Structure):
     ]
 
 
+MAX_OBS_NODES = 16  # RF_ENV_MAX_OBS_NODES
+MAX_OBS_COLUMNS = 16  # RF_ENV_MAX_OBS_COLUMNS
+OBS_INDEXED, OBS_FOCUS, OBS_DELTA, OBS_NORMALIZED = range(4)  # RF_OBS_*
+
+
+class EnvObserverNode(ctypes.Structure):
+    """rf_env_observer_node (include/reinfocus_hip.h)."""
+
+    _fields_ = [("kind", ctypes.c_int), ("index", ctypes.c_int), ("first", ctypes.c_int), ("width", ctypes.c_int),
+                ("include_original", ctypes.c_int), ("old_first", ctypes.c_int),
+                ("mid", ctypes.c_float * MAX_OBS_COLUMNS), ("scale", ctypes.c_float * MAX_OBS_COLUMNS)]
+
+
+class EnvObserverProgram(ctypes.Structure):
+    """rf_env_observer_program (include/reinfocus_hip.h): a composed environment's observer tree."""
+
+    _fields_ = [("n_nodes", ctypes.c_int), ("width", ctypes.c_int), ("n_old", ctypes.c_int),
+                ("nodes", EnvObserverNode * MAX_OBS_NODES)]
+
+
 class NativeLibraryMissing(ImportError):
     """libreinfocus_hip.so has not been built (python -c 'import __graft_entry__ as g; g.build()')."""
 
@@ -208,6 +230,9 @@ def load():
     lib.rf_env_step_plan_jumps.argtypes = [vp, vp, ctypes.POINTER(i32)]
     lib.rf_env_configure_composed.argtypes = [vp, ctypes.POINTER(EnvConfig), ctypes.POINTER(EnvProgram)]
     lib.rf_env_get_strategy_state.argtypes = [vp, vp, vp, vp, vp]
+    lib.rf_env_configure_observed.argtypes = [vp, ctypes.POINTER(EnvConfig), ctypes.POINTER(EnvProgram),
+                                              ctypes.POINTER(EnvObserverProgram)]
+    lib.rf_env_get_observer_state.argtypes = [vp, vp]
     lib.rf_render_kernel_name.restype = ctypes.c_char_p
     lib.rf_render_kernel_name.argtypes = [vp]
     lib.rf_pixels_rendered.restype = ctypes.c_ulonglong
@@ -401,8 +426,12 @@ class Context:
         return out
 
     # --- device-resident env step ----------------------------------------------------------
-    def _env_configured(self, n):
+    def _env_configured(self, n, obs_width=4):
+        """obs_width: the columns of every observation array the rf_env_* calls fill (float32[n, obs_width]): 4, or the
+        width of the observer program the context is configured with."""
         self._env_n = n
+        self._env_obs_width = int(obs_width)
+        self._env_n_old = 0
         self._env_k = ctypes.c_int(0)  # (env_step's count of ended environments, and its reference, made once)
         self._env_k_ref = ctypes.byref(self._env_k)
 
@@ -424,6 +453,24 @@ class Context:
                              sum(program.enders[i].steps + 1 for i in range(program.n_enders)
                                  if program.enders[i].kind == 3))  # (RF_ENDER_STOPPED)
 
+    def env_configure_observed(self, cfg, program, observer_program):
+        """rf_env_configure_observed: env_configure_composed with the observer tree as a program too (an
+        EnvObserverProgram); observations are float32[n, observer_program.width] from then on."""
+        assert 1 <= observer_program.width <= MAX_OBS_COLUMNS, f"{observer_program.width} observation columns"
+        _check(self._lib.rf_env_configure_observed(self._h, ctypes.byref(cfg), ctypes.byref(program),
+                                                   ctypes.byref(observer_program)))  # (refused: nothing changes)
+        self._env_configured(cfg.n, observer_program.width)
+        self._env_n_old = observer_program.n_old
+        self._env_program = (program.n_enders, program.n_rewarders,
+                             sum(program.enders[i].steps + 1 for i in range(program.n_enders)
+                                 if program.enders[i].kind == 3))  # (RF_ENDER_STOPPED)
+
+    def env_observer_state(self):
+        """rf_env_get_observer_state: the DELTA nodes' old values, float32[n_old, n], node-major."""
+        old = np.empty((self._env_n_old, self._env_n), dtype=np.float32)
+        _check(self._lib.rf_env_get_observer_state(self._h, _ptr(old)))
+        return old
+
     def env_strategy_state(self):
         """rf_env_get_strategy_state: (counters int32[n_enders, n], floats float32[n_enders, n], histories
         float32[rows, n], old values float32[n_rewarders, n])."""
@@ -439,7 +486,7 @@ class Context:
 
     def env_reset(self, states):
         states = np.ascontiguousarray(states, dtype=np.float32).reshape(self._env_n, 2)
-        obs = np.empty((self._env_n, 4), dtype=np.float32)
+        obs = np.empty((self._env_n, self._env_obs_width), dtype=np.float32)
         _check(self._lib.rf_env_reset(self._h, _ptr(states), _ptr(obs)))
         return obs
 
@@ -449,7 +496,7 @@ class Context:
         n = self._env_n
         actions = np.ascontiguousarray(actions, dtype=dtype).reshape(n)
         pool = np.ascontiguousarray(pool, dtype=np.float32).reshape(n, 2)
-        obs = np.empty((n, 4), dtype=np.float32)
+        obs = np.empty((n, self._env_obs_width), dtype=np.float32)
         rewards = np.empty(n, dtype=np.float64)
         truncated = np.empty(n, dtype=np.bool_)  # (the library writes 0 / 1 bytes)
         k = self._env_k
@@ -503,7 +550,7 @@ class Context:
         """Second half: the environments that ended take pool_rows float32[k, 2]; observations."""
         n = self._env_n
         pool_rows = np.ascontiguousarray(pool_rows, dtype=np.float32).reshape(-1, 2)
-        obs = np.empty((n, 4), dtype=np.float32)
+        obs = np.empty((n, self._env_obs_width), dtype=np.float32)
         _check(self._lib.rf_env_step_end(self._h, _ptr(pool_rows) if len(pool_rows) else None, _ptr(obs)))
         return obs
 
@@ -512,7 +559,7 @@ class Context:
         (observations, rewards, truncated)."""
         n = self._env_n
         pool_rows = np.ascontiguousarray(pool_rows, dtype=np.float32).reshape(-1, 2)
-        obs = np.empty((n, 4), dtype=np.float32)
+        obs = np.empty((n, self._env_obs_width), dtype=np.float32)
         rewards = np.empty(n, dtype=np.float64)
         truncated = np.empty(n, dtype=np.uint8)
         _check(self._lib.rf_env_step_run(self._h, _ptr(pool_rows) if len(pool_rows) else None, _ptr(obs), _ptr(rewards),
@@ -533,7 +580,7 @@ class Context:
         pool_rows = np.ascontiguousarray(pool_rows, dtype=np.float32).reshape(-1, 2)
         focus = np.ascontiguousarray(focus, dtype=np.float64).reshape(-1)
         assert len(focus) == len(pool_rows)
-        obs = np.empty((n, 4), dtype=np.float32)
+        obs = np.empty((n, self._env_obs_width), dtype=np.float32)
         some = len(pool_rows) > 0
         _check(self._lib.rf_env_step_end_given(self._h, _ptr(pool_rows) if some else None,
                                                _ptr(focus) if some else None, _ptr(obs)))

@@ -14,21 +14,29 @@ namespace {
 
 // The per-step traffic of the device-resident environment as ONE block on either side -- inputs first, then outputs --
 // so that a step enqueued in one go moves it with one copy in and one copy out (a hipGraph node each, instead of two
-// and four): [pool f32 n x 2 | actions i32 n | pad to 16] [rewards f64 n | observations f32 n x 4 | count i32 | truncated u8 n]
+// and four): [pool f32 n x 2 | actions i32 n | pad to 16] [rewards f64 n | observations f32 n x W | count i32 | truncated u8 n]
+// (W = 4 columns, or the width of the context's observer program)
 struct EnvIo {
-    size_t o_pool, o_actions, in_bytes, o_rewards, o_obs, o_count, o_truncated, bytes;
-    explicit EnvIo(size_t n)
+    size_t o_pool, o_actions, in_bytes, o_rewards, o_obs, obs_bytes, o_count, o_truncated, bytes;
+    EnvIo(size_t n, size_t width)
     {
         o_pool = 0;
         o_actions = n * 8;
         in_bytes = (n * 12 + 15) & ~(size_t)15;
         o_rewards = in_bytes;
         o_obs = o_rewards + n * 8;
-        o_count = o_obs + n * 16;
+        obs_bytes = n * width * 4;
+        o_count = o_obs + obs_bytes;
         o_truncated = o_count + 4;
         bytes = (o_truncated + n + 15) & ~(size_t)15;
     }
 };
+
+// bytes of the context's observations, float32[n][W]
+size_t env_obs_bytes(const rf_ctx *ctx)
+{
+    return (size_t)ctx->env_host.n * (size_t)ctx->env_obs_width * 4;
+}
 
 bool fused_step_possible(const rf_ctx *ctx)
 {
@@ -105,7 +113,7 @@ bool finite_all(const double *v, int n)
     return true;
 }
 
-int check_program(const rf_env_program *p)
+int check_program(const rf_env_program *p, int obs_width)
 {
     auto state_index = [](int i) { return i == 0 || i == 1; };
     const int t = p->transformer;
@@ -158,13 +166,61 @@ int check_program(const rf_env_program *p)
         RF_REQUIRE(l.kind >= RF_REWARD_DELTA && l.kind <= RF_REWARD_STOPPED,
                    "rf_env_configure_composed: rewarder %d: unknown kind %d", i, l.kind);
         if (l.kind == RF_REWARD_OBSERVATION)
-            RF_REQUIRE(l.index0 >= 0 && l.index0 < 4, "rf_env_configure_composed: rewarder %d: observation index %d "
-                       "outside 0-3", i, l.index0);
+            RF_REQUIRE(l.index0 >= 0 && l.index0 < obs_width, "rf_env_configure_composed: rewarder %d: observation index %d "
+                       "outside 0-%d", i, l.index0, obs_width - 1);
         else
             RF_REQUIRE(state_index(l.index0) && state_index(l.index1),
                        "rf_env_configure_composed: rewarder %d: index outside {0, 1}", i);
         RF_REQUIRE(finite_all(l.p, 3), "rf_env_configure_composed: rewarder %d: parameter not finite", i);
     }
+    return RF_OK;
+}
+
+// An observer program as rf_env_configure_observed takes it (include/reinfocus_hip.h): the nodes work on a stack of
+// columns that never shrinks, so every column a node touches is below the final width.
+int check_observer_program(const rf_env_observer_program *p)
+{
+    const char *fn = "rf_env_configure_observed";
+    RF_REQUIRE(p->n_nodes >= 1 && p->n_nodes <= RF_ENV_MAX_OBS_NODES, "%s: %d observer nodes (1 to %d)", fn, p->n_nodes,
+               RF_ENV_MAX_OBS_NODES);
+    int top = 0, old = 0, focus = 0;
+    for (int k = 0; k < p->n_nodes; ++k) {
+        const rf_env_observer_node &node = p->nodes[k];
+        switch (node.kind) {
+        case RF_OBS_INDEXED:
+        case RF_OBS_FOCUS:
+            RF_REQUIRE(node.first == top && node.width == 1, "%s: node %d: a leaf writes the next free column", fn, k);
+            RF_REQUIRE(node.kind == RF_OBS_FOCUS || node.index == 0 || node.index == 1,
+                       "%s: node %d: element index %d outside {0, 1}", fn, k, node.index);
+            focus += node.kind == RF_OBS_FOCUS ? 1 : 0;
+            top += 1;
+            break;
+        case RF_OBS_DELTA:
+        case RF_OBS_NORMALIZED:
+            RF_REQUIRE(node.width >= 1 && node.first >= 0 && node.first + node.width == top,
+                       "%s: node %d: columns [%d, %d) are not the top of the %d columns there", fn, k, node.first,
+                       node.first + node.width, top);
+            if (node.kind == RF_OBS_DELTA) {
+                RF_REQUIRE(node.old_first == old, "%s: node %d: old-value rows are handed out in node order", fn, k);
+                old += node.width;
+                top += node.include_original ? node.width : 0;
+            } else {
+                for (int j = 0; j < node.width; ++j)
+                    RF_REQUIRE(isfinite(node.mid[j]) && isfinite(node.scale[j]) && node.scale[j] != 0.0f,
+                               "%s: node %d: column %d: mid %g / scale %g (finite, scale not zero)", fn, k, j,
+                               (double)node.mid[j], (double)node.scale[j]);
+            }
+            break;
+        default:
+            RF_REQUIRE(false, "%s: node %d: unknown kind %d", fn, k, node.kind);
+        }
+        RF_REQUIRE(top <= RF_ENV_MAX_OBS_COLUMNS && old <= RF_ENV_MAX_OBS_COLUMNS,
+                   "%s: node %d: %d columns, %d old-value rows (at most %d each)", fn, k, top, old, RF_ENV_MAX_OBS_COLUMNS);
+    }
+    RF_REQUIRE(p->nodes[p->n_nodes - 1].first == 0, "%s: the last node does not leave one observer's columns", fn);
+    RF_REQUIRE(focus == 1, "%s: %d FocusObserver nodes (exactly one: a step renders once)", fn, focus);
+    RF_REQUIRE(p->width == top && p->n_old == old, "%s: width %d / n_old %d, but the nodes leave %d / %d", fn, p->width,
+               p->n_old, top, old);
     return RF_OK;
 }
 
@@ -216,7 +272,7 @@ rf::EnvProgram device_program(const rf_env_program &h)
 }
 
 int env_configure(rf_ctx *ctx, const rf_env_config *cfg, int task, float stop_threshold,
-                  const rf_env_program *program = nullptr)
+                  const rf_env_program *program = nullptr, const rf_env_observer_program *observer = nullptr)
 {
     RF_REQUIRE(cfg->frame_height > 0 && cfg->spp > 0, "rf_env_configure: frame_height, spp must be positive");
     RF_REQUIRE(cfg->gray_mode == RF_GRAY_15BIT || cfg->gray_mode == RF_GRAY_14BIT, "rf_env_configure: gray_mode");
@@ -244,7 +300,11 @@ int env_configure(rf_ctx *ctx, const rf_env_config *cfg, int task, float stop_th
     const size_t o_prog = take(program ? sizeof(rf::EnvProgram) : 0), o_count = take(n_enders * n * 4),
                  o_float = take(n_enders * n * 4), o_hist = take((size_t)prog.history_rows * n * 4),
                  o_old = take(n_rewarders * n * 4);
-    const EnvIo io(n);
+    // rf_env_configure_observed: the observer program, then the DELTA nodes' old values ([row][n])
+    const size_t n_old = observer ? (size_t)observer->n_old : 0;
+    const size_t o_obsprog = take(observer ? sizeof(*observer) : 0), o_obsold = take(n_old * n * 4);
+    const int obs_width = observer ? observer->width : 4;
+    const EnvIo io(n, (size_t)obs_width);
     const size_t o_io = take(io.bytes);
     RF_HIP(dev_malloc(&ctx->env_block, off));
     RF_HIP(hipMemsetAsync(ctx->env_block, 0, off, ctx->stream));
@@ -273,6 +333,16 @@ int env_configure(rf_ctx *ctx, const rf_env_config *cfg, int task, float stop_th
     s.leaf_float = program ? (float *)(base + o_float) : nullptr;
     s.history = program ? (float *)(base + o_hist) : nullptr;
     s.leaf_old = program ? (float *)(base + o_old) : nullptr;
+    s.observer = observer ? (const rf_env_observer_program *)(base + o_obsprog) : nullptr;
+    s.obs_old = observer ? (float *)(base + o_obsold) : nullptr;
+    ctx->env_obs_width = obs_width;
+    ctx->env_observer = observer ? *observer : rf_env_observer_program{};
+    if (observer) { // (DeltaObserver._old_wrapped_observations starts as NaN; ctx->env_observer outlives the copy)
+        RF_HIP(hipMemcpyAsync(base + o_obsprog, &ctx->env_observer, sizeof(*observer), hipMemcpyHostToDevice, ctx->stream));
+        if (n_old)
+            RF_HIP(hipMemsetD32Async((hipDeviceptr_t)(base + o_obsold), 0x7fc00000, n_old * n, ctx->stream));
+        RF_HIP(hipStreamSynchronize(ctx->stream));
+    }
     if (program) {
         ctx->env_program = *program;
         RF_HIP(hipMemcpyAsync(base + o_prog, &prog, sizeof(prog), hipMemcpyHostToDevice, ctx->stream));
@@ -458,7 +528,7 @@ int enqueue_env_step(rf_ctx *ctx, const void *actions, const float *pool, float 
     // step) -- one copy in, one copy out; otherwise the caller's six separate arrays
     const EnvLaunch d(ctx, false);
     const size_t n = (size_t)d.n;
-    const EnvIo io(n);
+    const EnvIo io(n, (size_t)ctx->env_obs_width);
     uint8_t *const d_io = (uint8_t *)ctx->d_pool; // (the io block starts with the pool)
     if (host_io) {
         RF_HIP(hipMemcpyAsync(d_io, host_io, io.in_bytes, hipMemcpyHostToDevice, ctx->stream));
@@ -483,7 +553,7 @@ int enqueue_env_step(rf_ctx *ctx, const void *actions, const float *pool, float 
         RF_HIP(hipMemcpyAsync(count, ctx->env.done_count, 4, hipMemcpyDeviceToHost, ctx->stream));
         RF_HIP(hipMemcpyAsync(rewards, ctx->env.reward, n * 8, hipMemcpyDeviceToHost, ctx->stream));
         RF_HIP(hipMemcpyAsync(truncated, ctx->env.truncated, n, hipMemcpyDeviceToHost, ctx->stream));
-        RF_HIP(hipMemcpyAsync(obs, ctx->env.obs, n * 16, hipMemcpyDeviceToHost, ctx->stream));
+        RF_HIP(hipMemcpyAsync(obs, ctx->env.obs, io.obs_bytes, hipMemcpyDeviceToHost, ctx->stream));
     }
     return RF_OK;
 }
@@ -561,7 +631,7 @@ int env_step_end(rf_ctx *ctx, const float *host_pool, const double *host_focus, 
             return rc;
         RF_HIP(hipGetLastError());
     }
-    RF_HIP(hipMemcpyAsync(host_obs, ctx->env.obs, (size_t)d.n * 16, hipMemcpyDeviceToHost, ctx->stream));
+    RF_HIP(hipMemcpyAsync(host_obs, ctx->env.obs, env_obs_bytes(ctx), hipMemcpyDeviceToHost, ctx->stream));
     RF_HIP(hipStreamSynchronize(ctx->stream));
     return RF_OK;
 }
@@ -586,7 +656,7 @@ int env_step(rf_ctx *ctx, const T *host_actions, const float *host_pool, float *
     // trip and saves up to a few hundred thousand empty blocks.
     const bool fused = fused_step_possible(ctx); // (one render launch, no count to wait for: enqueued in one go at any size)
     if (fused || env_one_sync(ctx)) {
-        const EnvIo io(n);
+        const EnvIo io(n, (size_t)ctx->env_obs_width);
         bool graph = ctx->env_graph_enabled && !ctx->timing && ctx->env_steps >= 1;
         if (graph) {
             if (int rc = ensure_env_graph(ctx, io.bytes))
@@ -599,7 +669,7 @@ int env_step(rf_ctx *ctx, const T *host_actions, const float *host_pool, float *
             memcpy(st + io.o_pool, host_pool, n * 8);
             RF_HIP(hipGraphLaunch(ctx->env_graph, ctx->stream));
             RF_HIP(hipStreamSynchronize(ctx->stream));
-            memcpy(host_obs, st + io.o_obs, n * 16);
+            memcpy(host_obs, st + io.o_obs, io.obs_bytes);
             memcpy(host_rewards, st + io.o_rewards, n * 8);
             memcpy(host_truncated, st + io.o_truncated, n);
             k = *(const int *)(st + io.o_count);
@@ -697,10 +767,36 @@ int rf_env_configure_composed(rf_ctx *ctx, const rf_env_config *cfg, const rf_en
 {
     RF_REQUIRE(ctx != nullptr && cfg != nullptr && program != nullptr, "rf_env_configure_composed: NULL argument");
     RF_REQUIRE(cfg->n > 0, "rf_env_configure_composed: bad n");
-    if (int rc = check_program(program))
+    if (int rc = check_program(program, 4))
         return rc;
     RF_HIP(hipSetDevice(ctx->device));
     return env_configure(ctx, cfg, rf::kEnvTaskComposed, 0.0f, program);
+}
+
+int rf_env_configure_observed(rf_ctx *ctx, const rf_env_config *cfg, const rf_env_program *program,
+                              const rf_env_observer_program *observer)
+{
+    RF_REQUIRE(ctx != nullptr && cfg != nullptr && program != nullptr && observer != nullptr,
+               "rf_env_configure_observed: NULL argument");
+    RF_REQUIRE(cfg->n > 0, "rf_env_configure_observed: bad n");
+    if (int rc = check_observer_program(observer))
+        return rc;
+    if (int rc = check_program(program, observer->width))
+        return rc;
+    RF_HIP(hipSetDevice(ctx->device));
+    return env_configure(ctx, cfg, rf::kEnvTaskComposed, 0.0f, program, observer);
+}
+
+int rf_env_get_observer_state(rf_ctx *ctx, float *host_old)
+{
+    RF_REQUIRE(ctx != nullptr && host_old != nullptr, "rf_env_get_observer_state: NULL argument");
+    RF_REQUIRE(ctx->env_ready && ctx->env.observer != nullptr, "rf_env_get_observer_state: rf_env_configure_observed first");
+    RF_HIP(hipSetDevice(ctx->device));
+    const size_t bytes = (size_t)ctx->env_observer.n_old * (size_t)ctx->env_host.n * 4;
+    if (bytes)
+        RF_HIP(hipMemcpyAsync(host_old, ctx->env.obs_old, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    RF_HIP(hipStreamSynchronize(ctx->stream));
+    return RF_OK;
 }
 
 int rf_env_get_strategy_state(rf_ctx *ctx, int32_t *host_counters, float *host_floats, float *host_histories,
@@ -741,7 +837,7 @@ int rf_env_reset(rf_ctx *ctx, const float *host_states, float *host_obs)
     if (int rc = full_pass(ctx, d, true, nullptr))
         return rc;
     RF_HIP(hipGetLastError());
-    RF_HIP(hipMemcpyAsync(host_obs, ctx->env.obs, (size_t)d.n * 16, hipMemcpyDeviceToHost, ctx->stream));
+    RF_HIP(hipMemcpyAsync(host_obs, ctx->env.obs, env_obs_bytes(ctx), hipMemcpyDeviceToHost, ctx->stream));
     RF_HIP(hipStreamSynchronize(ctx->stream));
     ctx->env_scene_len = d.n;
     ctx->env_last_partial = false;
@@ -848,7 +944,7 @@ int rf_env_step_run(rf_ctx *ctx, const float *host_pool, float *host_obs, double
     RF_HIP(hipGetLastError());
     RF_HIP(hipMemcpyAsync(host_rewards, ctx->env.reward, n * 8, hipMemcpyDeviceToHost, ctx->stream));
     RF_HIP(hipMemcpyAsync(host_truncated, ctx->env.truncated, n, hipMemcpyDeviceToHost, ctx->stream));
-    RF_HIP(hipMemcpyAsync(host_obs, ctx->env.obs, n * 16, hipMemcpyDeviceToHost, ctx->stream));
+    RF_HIP(hipMemcpyAsync(host_obs, ctx->env.obs, env_obs_bytes(ctx), hipMemcpyDeviceToHost, ctx->stream));
     RF_HIP(hipStreamSynchronize(ctx->stream));
     rfh::count_pixels(d.pixels(d.n + k));
     ctx->env_needs_reset = false;

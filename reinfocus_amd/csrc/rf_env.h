@@ -6,6 +6,7 @@
 //   TimeLimitEnder | DivergingEnder        environments/episode_ender.py:137-170, :602-628
 //   FastCameras / FastWorlds packing       graphics/camera.py:144-179, graphics/world.py:110-123
 //   NormalizedObserver(DeltaObserver(..))  environments/state_observer.py:232-292, :472-517
+//   (any tree of the observer classes around one FocusObserver: the interpreter of rf_env_observer_program below)
 //   Delta + Observation + OnTarget reward  environments/episode_rewarder.py:130-155, :226-292
 //   (Observation + Stopped * OnTarget      environments/episode_rewarder.py:226-292, :361-429, kEnvTaskJumps)
 //   same-step auto-reset                   environments/vector_environment.py:137-151
@@ -74,6 +75,18 @@ __device__ __forceinline__ float pick4(const float v[4], int i)
 {
     return i == 0 ? v[0] : i == 1 ? v[1] : i == 2 ? v[2] : v[3];
 }
+
+// What an ObservationRewarder reads: the built-in observer's four values in registers, or the environment's row of
+// EnvState::obs that an observer program left (W columns; a program index is uniform, so the address is row + scalar)
+struct ObsBuiltIn {
+    float v[4];
+    __device__ __forceinline__ float operator()(int i) const { return pick4(v, i); }
+};
+
+struct ObsRow {
+    const float *row;
+    __device__ __forceinline__ float operator()(int i) const { return row[i]; }
+};
 
 __device__ __forceinline__ float clip_limits(const_as<EnvProgram> &p, float v)
 {
@@ -212,8 +225,9 @@ __device__ __forceinline__ void composed_rewarders_reset(const EnvConfig &c, con
 }
 
 // reward of rewarder leaf i, carried as a double (a float32 term computes in float32: widening it is exact)
+template <class Obs>
 __device__ __forceinline__ double composed_leaf_reward(const EnvConfig &c, const EnvState &s, const_as<EnvProgram> &p,
-                                                       const float st[2], const float obs[4], int i, int e)
+                                                       const float st[2], const Obs &obs, int i, int e)
 {
     const_as<EnvRewardLeaf> &r = p.rewarders[i];
     const size_t at = (size_t)i * c.n + e;
@@ -226,7 +240,7 @@ __device__ __forceinline__ double composed_leaf_reward(const EnvConfig &c, const
     case RF_REWARD_DISTANCE: // (1 - abs(a - b) / span) * (high - low) + low, float32
         return (1.0f - fabsf(pick2(st, r.i0) - pick2(st, r.i1)) / r.f[0]) * r.f[1] + r.f[2];
     case RF_REWARD_OBSERVATION:
-        return pick4(obs, r.i0);
+        return obs(r.i0);
     case RF_REWARD_ON_TARGET: // (abs(a - b) < span) * (on - off) + off, float64
         return (fabsf(pick2(st, r.i0) - pick2(st, r.i1)) < r.f[0] ? 1.0 : 0.0) * r.d[0] + r.d[1];
     default: { // RF_REWARD_STOPPED: (abs(x - old) < threshold) * reward, float64
@@ -238,8 +252,9 @@ __device__ __forceinline__ double composed_leaf_reward(const EnvConfig &c, const
 }
 
 // the rewarder tree: every leaf once, in leaf order, then the postfix list of + / * (each node in its own dtype)
+template <class Obs>
 __device__ __forceinline__ double composed_reward(const EnvConfig &c, const EnvState &s, const_as<EnvProgram> &p,
-                                                  const float st[2], const float obs[4], int e)
+                                                  const float st[2], const Obs &obs, int e)
 {
     double leaf[kEnvMaxLeaves];
 #pragma unroll
@@ -339,10 +354,74 @@ __device__ __forceinline__ float normalize1(const EnvConfig &c, int k, float v)
     return fminf(fmaxf((v - c.mid[k]) / c.scale[k], -1.0f), 1.0f);
 }
 
+// ---- rf_env_configure_observed: the interpreter of the observer program (rf_env_observer_program) -------------------
+// observer.observe (`first` == 0) or observer.reset (`first` != 0: zero deltas, fresh old values) of one environment in
+// state st whose frame measured focus_value: state_observer.py:143-164, :232-292, :403-421, :472-517 operation by
+// operation in float32.  The column file is the environment's own row of EnvState::obs, worked on in place -- column
+// numbers come from the program, so they are scalars and every access is the row's address plus a scalar offset: no
+// array indexed at run time in registers (which would go to scratch memory), no LDS.  The last node leaves the
+// observations there.
+__device__ __forceinline__ void observe_program(const EnvConfig &c, const EnvState &s, const float st[2],
+                                                float focus_value, int first, int e)
+{
+    const_as<rf_env_observer_program> &p = *as_const(s.observer);
+    float *row = s.obs + (size_t)e * p.width;
+    for (int k = 0; k < p.n_nodes; ++k) {
+        const_as<rf_env_observer_node> &node = p.nodes[k];
+        switch (node.kind) {
+        case RF_OBS_INDEXED:
+            row[node.first] = pick2(st, node.index);
+            break;
+        case RF_OBS_FOCUS: // hstack(..., dtype=float32) of the float64 focus value
+            row[node.first] = focus_value;
+            break;
+        case RF_OBS_DELTA: { // wrapped - old (numpy.zeros in a reset), then old = wrapped
+            float *out = row + (node.include_original ? node.first + node.width : node.first);
+            float *old = s.obs_old + (size_t)node.old_first * c.n + e;
+            for (int j = 0; j < node.width; ++j) {
+                const float wrapped = row[node.first + j];
+                out[j] = first ? 0.0f : wrapped - old[(size_t)j * c.n];
+                old[(size_t)j * c.n] = wrapped;
+            }
+            break;
+        }
+        default: // RF_OBS_NORMALIZED: clip((values - mid) / scale, -1, 1)
+            for (int j = 0; j < node.width; ++j)
+                row[node.first + j] = fminf(fmaxf((row[node.first + j] - node.mid[j]) / node.scale[j], -1.0f), 1.0f);
+            break;
+        }
+    }
+}
+
+// env_post_one for a context with an observer program (always kEnvTaskComposed)
+__device__ __forceinline__ void env_post_observed(const EnvConfig &c, const EnvState &s, const double *focus_values,
+                                                  int first, int e)
+{
+    const float st[2] = {s.state[2 * e], s.state[2 * e + 1]};
+    observe_program(c, s, st, (float)(focus_values ? focus_values[e] : env_variance(c, s.sums, e)), first, e);
+    const_as<EnvProgram> &p = env_program(s);
+    if (first) {
+        composed_rewarders_reset(c, s, p, st, e);
+        s.truncated[e] = 0;
+        s.done[e] = 0;
+        s.reward[e] = 0.0;
+        return;
+    }
+    const ObsRow obs{s.obs + (size_t)e * as_const(s.observer)->width};
+    s.reward[e] = composed_reward(c, s, p, st, obs, e);
+    const bool trunc = composed_truncated(c, s, p, e);
+    s.truncated[e] = trunc ? 1 : 0;
+    s.done[e] = trunc ? 1 : 0;
+}
+
 // observe -> reward -> done flags (vector_environment.py:128-135); `first` = reset() call
 // focus_values == nullptr: the variance comes from the sums the focus kernel left (env_variance)
 __device__ __forceinline__ void env_post_one(const EnvConfig &c, const EnvState &s, const double *focus_values, int first, int e)
 {
+    if (s.observer) {
+        env_post_observed(c, s, focus_values, first, e);
+        return;
+    }
     const float target = s.state[2 * e], focus = s.state[2 * e + 1];
     const float w0 = focus, w1 = (float)(focus_values ? focus_values[e] : env_variance(c, s.sums, e));
     float d0 = 0.0f, d1 = 0.0f;
@@ -360,7 +439,8 @@ __device__ __forceinline__ void env_post_one(const EnvConfig &c, const EnvState 
     s.obs[4 * e + 3] = o3;
     if (c.task == kEnvTaskComposed) {
         const_as<EnvProgram> &p = env_program(s);
-        const float st[2] = {target, focus}, obs[4] = {o0, o1, o2, o3};
+        const float st[2] = {target, focus};
+        const ObsBuiltIn obs{{o0, o1, o2, o3}};
         if (first) {
             composed_rewarders_reset(c, s, p, st, e);
             s.truncated[e] = 0;
@@ -534,6 +614,13 @@ __device__ __forceinline__ void env_reset_post_one(const EnvConfig &c, const Env
 {
     if (planned_pool)
         env_apply_state(c, s, planned_pool, r, e);
+    if (s.observer) { // observer.reset(new_state, done), rewarder.reset
+        const float st[2] = {s.state[2 * e], s.state[2 * e + 1]};
+        observe_program(c, s, st,
+                        (float)(focus_values ? focus_values[r] : env_variance(c, planned_pool ? s.sums2 : s.sums, r)), 1, e);
+        composed_rewarders_reset(c, s, env_program(s), st, e);
+        return;
+    }
     const float focus = s.state[2 * e + 1];
     const float w0 = focus,
                 w1 = (float)(focus_values ? focus_values[r] : env_variance(c, planned_pool ? s.sums2 : s.sums, r));

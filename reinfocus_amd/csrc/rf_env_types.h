@@ -3,6 +3,8 @@
 
 #include <stdint.h>
 
+#include "../../include/reinfocus_hip.h" // rf_env_observer_program: the kernels read it as the host wrote it
+
 namespace rf {
 
 // EnvConfig::task: which of the reference's two tasks (examples/__init__.py:6-18) the step computes.  Both share the
@@ -79,7 +81,7 @@ struct EnvState {            // all device arrays, length n unless noted
     int *done_index;         // [n] env index of the r-th reset env
     int *done_rank;          // [n] the inverse for the envs that ended (fused step)
     int *done_count;         // [1]
-    float *obs;              // [n][4]
+    float *obs;              // [n][4]; [n][W] with an observer program
     double *reward;          // [n]
     uint8_t *truncated;      // [n]
     uint8_t *done;           // [n] scratch
@@ -91,6 +93,9 @@ struct EnvState {            // all device arrays, length n unless noted
     float *leaf_float;       // [n_enders][n] DivergingEnder._last_diff
     float *history;          // [history_rows][n] StoppedEnder histories, oldest first, NaN where empty
     float *leaf_old;         // [n_rewarders][n] Delta / Stopped: the element's previous value
+    // rf_env_configure_observed only (null otherwise: the built-in observer of mid / scale / old_wrapped above)
+    const rf_env_observer_program *observer; // read like `program`; every value in it is float32 or an index already
+    float *obs_old;          // [n_old][n] the DELTA nodes' old values, node-major, NaN until the first reset
 };
 
 } // namespace rf

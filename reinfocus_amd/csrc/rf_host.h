@@ -98,6 +98,8 @@ struct rf_ctx {
     int env_last_branch = RF_ENV_BRANCH_NONE; // rf_env_last_step_branch
     bool env_needs_reset = false; // rf_env_step_abort dropped a half-finished step
     rf_env_program env_program{}; // rf_env_configure_composed's program (host copy: action checks, strategy readback)
+    rf_env_observer_program env_observer{}; // rf_env_configure_observed's observer program (host copy; n_nodes 0: none)
+    int env_obs_width = 4; // columns of the observations: 4, or that program's width
     bool env_fused = true; // the step's two renders and two focus measures as one launch each (REINFOCUS_ENV_FUSED=0: the
                            // three schedules of separate launches)
     long env_one_sync_max = 65536; // blocks of a full render up to which rf_env_step runs without the mid-step round

@@ -25,7 +25,8 @@ by VectorEnvironment with the vector DiscreteSteps' TimeLimitEnder | DivergingEn
 
 VectorEnvironment / DeviceVectorEnvironment go further: any composition of the reference's strategy classes
 (environments/state_transformer.py, episode_ender.py, episode_rewarder.py, state_initializer.py) around the same
-observer, on the host and with the whole step on the GPU (rf_env_configure_composed).
+observer -- or, with observer=, around any tree of the observer classes (environments/state_observer.py) that holds one
+FocusObserver --, on the host and with the whole step on the GPU (rf_env_configure_composed, rf_env_configure_observed).
 """
 
 import numpy as np
@@ -144,14 +145,14 @@ class _Ender:
 
 def delta_bounds(lows, highs, max_change=None, include_original=False):
     """Observation bounds of DeltaObserver (state_observer.py:166-230): a change is bounded by
-    high - low of what it is a change of, or by max_change where that is given (not NaN); with
+    high - low of what it is a change of, or by max_change where that is given (finite); with
     include_original the wrapped bounds come first.  float32, as gymnasium's Box."""
     lows = np.asarray(lows, dtype=np.float32)
     highs = np.asarray(highs, dtype=np.float32)
     diff = highs - lows
     if max_change is not None:
         max_change = np.asarray(max_change, dtype=np.float32)
-        diff = np.where(np.isnan(max_change), diff, max_change).astype(np.float32)
+        diff = np.where(np.isfinite(max_change), max_change, diff).astype(np.float32)
     if include_original:
         return np.append(lows, -diff), np.append(highs, diff)
     return -diff, diff
@@ -208,6 +209,39 @@ class _Observer:
         observations = np.hstack([wrapped, np.zeros(wrapped.shape, dtype=np.float32)], dtype=np.float32)
         self._old[indices] = wrapped
         return self._normalize(observations)
+
+
+def default_observer(num_envs, ends, max_focus_move, renderer, frame_height=300):
+    """The built-in observer (_Observer) restated with the public classes: NormalizedObserver(DeltaObserver(
+    [IndexedElementObserver(1), FocusObserver], True, [max_focus_move, nan])) over states [target, focus plane] in
+    `ends` -- custom_environments.py:196-218.  Observations equal the built-in observer's bit for bit."""
+    focus = state_observer.FocusObserver(num_envs, TARGET, FOCUS, ends, renderer, frame_height)
+    position = state_observer.IndexedElementObserver(num_envs, FOCUS, ends[0], ends[1])
+    return state_observer.NormalizedObserver(state_observer.DeltaObserver(
+        [position, focus], True, np.array([max_focus_move, np.nan], dtype=np.float32)))
+
+
+def _described_renderer(observer, frame_height, samples_per_pixel, device):
+    """(FocusObserver, renderer, frame height, samples per pixel) of an environment given an observer tree: they are
+    those of the tree's one FocusObserver, and the environment's own keywords must be left at their defaults or agree."""
+    from reinfocus_amd.environments import strategy_program
+
+    focus = strategy_program.focus_observer(observer)
+    renderer = focus._renderer
+    assert frame_height in (300, focus._frame_height), \
+        f"frame_height {frame_height} is not the FocusObserver's {focus._frame_height}"
+    assert samples_per_pixel in (100, renderer._samples_per_pixel), \
+        f"samples_per_pixel {samples_per_pixel} is not the FocusObserver's renderer's {renderer._samples_per_pixel}"
+    assert device is None or device == renderer._ctx.device, \
+        f"device {device} is not the FocusObserver's renderer's {renderer._ctx.device}"
+    return focus, renderer, focus._frame_height, renderer._samples_per_pixel
+
+
+def _checked_focus_index(index, single_observation_space):
+    width = single_observation_space.shape[0]
+    assert isinstance(index, (int, np.integer)) and 0 <= index < width, \
+        f"focus_observation_index {index!r} outside the {width} observation columns"
+    return int(index)
 
 
 class _Rewarder:
@@ -511,8 +545,9 @@ class _DeviceShard:
     EARLY_END_STEPS = 3  # DivergingEnder(..., early_end_steps=3), custom_environments.py:186-190
 
     def __init__(self, num_envs, max_episode_steps, frame_height, samples_per_pixel, device, first_state_index,
-                 jumps=False, program=None, ends=None, max_move=None):
-        """program: an rf_env_program (rf_env_configure_composed) with the observer's `ends` and `max_move`."""
+                 jumps=False, program=None, ends=None, max_move=None, observer_program=None):
+        """program: an rf_env_program (rf_env_configure_composed) with the built-in observer's `ends` and `max_move`, or
+        with observer_program, an rf_env_observer_program, in its place (rf_env_configure_observed)."""
         import math
 
         from reinfocus_amd import _native, vision
@@ -561,7 +596,9 @@ class _DeviceShard:
             cfg.spp = samples_per_pixel
             cfg.gray_mode = vision.GRAY_MODE
             self.ctx.seed(num_envs * frame_height * frame_height, 0, self.first_state_index)
-            if program is not None:
+            if observer_program is not None:
+                self.ctx.env_configure_observed(cfg, program, observer_program)
+            elif program is not None:
                 self.ctx.env_configure_composed(cfg, program)
             elif jumps:  # (limit_lo / limit_hi: the range the focus plane jumps in)
                 self.ctx.env_configure_jumps(cfg, JUMP_STOP)
@@ -1038,14 +1075,19 @@ class VectorEnvironment(_VectorEnvBase):
     episode_rewarder.py and state_transformer.py, around the observer both tasks use --
     NormalizedObserver(DeltaObserver([IndexedElementObserver(1), FocusObserver], True, [max_focus_move, nan])) over
     states [target, focus plane] in `ends`.  The host twin: numpy glue around the GPU render and focus measure, in the
-    reference's call order, same-step auto-reset included.  Rewards are returned as float64.  Actions are checked before
-    any state changes (composed_actions).  `reset(seed=...)` reseeds the initializer; `state=` (extension) pins the
+    reference's call order, same-step auto-reset included.  observer= replaces that observer by any tree of the observer
+    classes (environments/state_observer.py) around one FocusObserver: the environment then renders with that
+    FocusObserver's renderer at its frame height (frame_height / samples_per_pixel / device must be left at their
+    defaults or agree), its spaces are the tree's, `ends` and `max_focus_move` only describe the visualiser's range, and
+    focus_observation_index names the observation column the visualiser plots.  Rewards are returned as float64.
+    Actions are checked before any state changes (composed_actions).  `reset(seed=...)` reseeds the initializer; `state=` (extension) pins the
     initial states.  DeviceVectorEnvironment is the same environment with the whole step on the GPU."""
 
     metadata = {"render_modes": ["rgb_array"], "render_fps": 4}
 
     def __init__(self, ender, initializer, rewarder, transformer, num_envs, ends=(5.0, 10.0), max_focus_move=5.0,
-                 render_mode=None, *, frame_height=300, samples_per_pixel=100, device=None):
+                 render_mode=None, *, frame_height=300, samples_per_pixel=100, device=None, observer=None,
+                 focus_observation_index=1):
         super().__init__()
         assert render_mode is None or render_mode in self.metadata["render_modes"]
         self.render_mode = render_mode
@@ -1054,12 +1096,20 @@ class VectorEnvironment(_VectorEnvBase):
         self._initializer = initializer
         self._rewarder = rewarder
         self._transformer = transformer
-        self._renderer = render.FastRenderer(samples_per_pixel=samples_per_pixel, device=device)
-        self._focus_observer = state_observer.FocusObserver(num_envs, TARGET, FOCUS, ends, self._renderer,
-                                                            frame_height)
-        self._observer = _Observer(num_envs, ends, max_focus_move, self._focus_observer)
-        self._visualizer = episode_visualizer.HistoryVisualizer(num_envs, TARGET, FOCUS, 1, self._renderer, ends,
-                                                                ender=ender)
+        if observer is None:
+            self._renderer = render.FastRenderer(samples_per_pixel=samples_per_pixel, device=device)
+            self._focus_observer = state_observer.FocusObserver(num_envs, TARGET, FOCUS, ends, self._renderer,
+                                                                frame_height)
+            self._observer = _Observer(num_envs, ends, max_focus_move, self._focus_observer)
+        else:
+            assert observer.observation_space.shape[0] == num_envs, \
+                f"the observer has num_envs {observer.observation_space.shape[0]}, not {num_envs}"
+            self._focus_observer, self._renderer, _, _ = _described_renderer(observer, frame_height, samples_per_pixel,
+                                                                             device)
+            self._observer = observer
+        focus_observation_index = _checked_focus_index(focus_observation_index, self._observer.single_observation_space)
+        self._visualizer = episode_visualizer.HistoryVisualizer(num_envs, TARGET, FOCUS, focus_observation_index,
+                                                                self._renderer, ends, ender=ender)
         self.single_action_space = transformer.single_action_space
         self.action_space = transformer.action_space
         self.single_observation_space = self._observer.single_observation_space
@@ -1108,6 +1158,14 @@ class VectorEnvironment(_VectorEnvBase):
 
         return strategy_program.host_strategy_state(self._ender, self._rewarder, self.num_envs)
 
+    def observer_state(self):
+        """The DeltaObservers' old values of an environment given an observer, float32[rows, n], laid out as
+        DeviceVectorEnvironment.observer_state returns them."""
+        from reinfocus_amd.environments import strategy_program
+
+        assert not isinstance(self._observer, _Observer), "the environment was not given an observer"
+        return strategy_program.host_observer_state(self._observer, self.num_envs)
+
     def status(self, index):
         return self._ender.status(index)
 
@@ -1130,11 +1188,14 @@ class DeviceVectorEnvironment(_DeviceVectorEnv):
     for bit, with the same initializer consumption (propose, then initialize the rows that were used).  The strategy
     objects only describe the environment here: their own state is not advanced (strategy_state() and status() read
     the device's).  Discrete transformers step through the int32 calls, continuous ones through the float32 ones.
-    One device only: `devices=` (sharding) is refused."""
+    observer= and focus_observation_index= as VectorEnvironment's: the tree is compiled too
+    (strategy_program.compile_observer, rf_env_configure_observed) and only describes the environment -- frame height,
+    samples per pixel and device are those of its FocusObserver and that observer's renderer, which is never asked to
+    render; observer_state() reads the device.  One device only: `devices=` (sharding) is refused."""
 
     def __init__(self, ender, initializer, rewarder, transformer, num_envs, ends=(5.0, 10.0), max_focus_move=5.0,
                  render_mode=None, *, frame_height=300, samples_per_pixel=100, device=None, first_state_index=0,
-                 devices=None):
+                 devices=None, observer=None, focus_observation_index=1):
         from reinfocus_amd.environments import state_transformer, strategy_program
 
         if devices is not None:
@@ -1142,31 +1203,49 @@ class DeviceVectorEnvironment(_DeviceVectorEnv):
                              "sharded over several (devices=)")
         _VectorEnvBase.__init__(self)
         assert render_mode is None or render_mode in self.metadata["render_modes"]
-        program = strategy_program.compile_program(transformer, ender, rewarder, num_envs)
+        observer_program = None
+        if observer is None:
+            program = strategy_program.compile_program(transformer, ender, rewarder, num_envs)
+            single_observation_space = spaces.Box(-np.ones(4, dtype=np.float32), np.ones(4, dtype=np.float32),
+                                                  dtype=np.float32)
+        else:
+            program, observer_program = strategy_program.compile_program(transformer, ender, rewarder, num_envs, observer)
+            _, described, frame_height, samples_per_pixel = _described_renderer(observer, frame_height,
+                                                                                samples_per_pixel, device)
+            device = described._ctx.device
+            single_observation_space = observer.single_observation_space
+        focus_observation_index = _checked_focus_index(focus_observation_index, single_observation_space)
+        self._observed = observer is not None
         self.render_mode = render_mode
         self.num_envs = num_envs
         self._ender = ender
         self._transformer = transformer
         self._discrete = transformer.kind in (state_transformer.DISCRETE_JUMP, state_transformer.DISCRETE_MOVE)
         self._shard = _DeviceShard(num_envs, None, frame_height, samples_per_pixel, device, first_state_index,
-                                   program=program, ends=ends, max_move=max_focus_move)
+                                   program=program, ends=ends, max_move=max_focus_move,
+                                   observer_program=observer_program)
         self._ctx = self._shard.ctx
         self._limits = tuple(ends)
         self._initializer = initializer
         self.single_action_space = transformer.single_action_space
         self.action_space = transformer.action_space
-        self.single_observation_space = spaces.Box(-np.ones(4, dtype=np.float32), np.ones(4, dtype=np.float32),
-                                                   dtype=np.float32)
+        self.single_observation_space = single_observation_space
         self.observation_space = spaces.batch_space(self.single_observation_space, num_envs)
         self._visualizer = None
         if render_mode == "rgb_array":
-            self._visualizer = episode_visualizer.HistoryVisualizer(num_envs, TARGET, FOCUS, 1, self._shard,
-                                                                    self._limits, ender=self)
+            self._visualizer = episode_visualizer.HistoryVisualizer(num_envs, TARGET, FOCUS, focus_observation_index,
+                                                                    self._shard, self._limits, ender=self)
 
     def strategy_state(self):
         """(counters int32[n_enders, n], floats float32[n_enders, n], StoppedEnder histories float32[rows, n], old
         values float32[n_rewarders, n]) from the device (rf_env_get_strategy_state)."""
         return self._ctx.env_strategy_state()
+
+    def observer_state(self):
+        """The DeltaObservers' old values float32[rows, n], node-major in evaluation order, from the device
+        (rf_env_get_observer_state)."""
+        assert self._observed, "the environment was not given an observer"
+        return self._ctx.env_observer_state()
 
     def status(self, index):
         """ender.status(index) from the device's strategy state."""

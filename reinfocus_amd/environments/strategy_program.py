@@ -5,7 +5,12 @@ over them, and up to eight rewarder leaves with a postfix list of `+` / `*` and 
 numbered in the order a left-to-right walk of the tree meets them; that is also the order of the per-leaf strategy
 state the device keeps (rf_env_get_strategy_state) and `host_strategy_state` reads from the host twin's objects.
 
-Every check of rf_env_configure_composed is made here first and raises AssertionError, so that nothing malformed
+An observer tree is compiled into a second, separate program (rf_env_observer_program, rf_env_configure_observed):
+its nodes in evaluation order -- children before their wrapper, left to right -- over a stack of float32 columns (see
+`compile_observer`).  The DeltaObservers' old values are kept node-major in that order (rf_env_get_observer_state,
+`host_observer_state`).
+
+Every check of rf_env_configure_composed / rf_env_configure_observed is made here first and raises AssertionError, so that nothing malformed
 reaches the device; so do the checks only Python can make: every strategy's num_envs, and rewarders whose numpy result
 would not be floating point (an OnTargetRewarder with integer on / off, which numpy evaluates in int64) or not in the
 dtype the device computes them in (an OnTargetRewarder / StoppedRewarder with numpy.float32 on and off / reward).
@@ -18,6 +23,7 @@ import numpy as np
 from reinfocus_amd import _native
 from reinfocus_amd.environments import episode_ender
 from reinfocus_amd.environments import episode_rewarder
+from reinfocus_amd.environments import state_observer
 from reinfocus_amd.environments import state_transformer
 
 # the dtype numpy 1.26 gives each rewarder leaf with Python-number or numpy.float64 parameters (environments/scalars.py),
@@ -118,7 +124,7 @@ def _ender(leaf, num_envs):
     return out
 
 
-def _rewarder(leaf):
+def _rewarder(leaf, obs_width=4):
     assert isinstance(leaf, episode_rewarder.BaseRewarder) and leaf.kind is not None, f"unsupported rewarder {leaf!r}"
     name = type(leaf).__name__
     assert np.issubdtype(leaf.dtype, np.floating), f"{name}: numpy evaluates it in {leaf.dtype}, not floating point"
@@ -128,7 +134,8 @@ def _rewarder(leaf):
     out.kind = leaf.kind
     if leaf.kind == episode_rewarder.OBSERVATION:
         i = leaf._reward_observation_index
-        assert isinstance(i, (int, np.integer)) and 0 <= i < 4, f"{name}: observation index {i!r} outside 0-3"
+        assert isinstance(i, (int, np.integer)) and 0 <= i < obs_width, \
+            f"{name}: observation index {i!r} outside 0-{obs_width - 1}"
         out.index0 = int(i)
         return out
     if leaf.kind in (episode_rewarder.DELTA, episode_rewarder.STOPPED):
@@ -147,8 +154,110 @@ def _rewarder(leaf):
     return out
 
 
-def compile_program(transformer, ender, rewarder, num_envs):
-    """The rf_env_program of a composition (AssertionError for anything the device cannot run)."""
+def observer_nodes(observer):
+    """The nodes of an observer tree in evaluation order: children before their wrapper, left to right.  A strategy
+    object may occur only once."""
+    nodes = []
+
+    def walk(node):
+        assert not any(node is other for other in nodes), "a strategy object may occur only once in a composition"
+        for child in getattr(node, "_observers", ()):
+            walk(child)
+        nodes.append(node)
+
+    walk(observer)
+    return nodes
+
+
+def _is_focus(node):
+    return isinstance(node, state_observer.FocusObserver) or getattr(node, "kind", None) == state_observer.FOCUS
+
+
+def focus_observer(observer):
+    """The one FocusObserver of an observer tree: the environment renders with its renderer at its frame height.  None or
+    several are refused: a step renders once (two would advance the RNG streams twice, none would be a step without a
+    render, which is a different schedule)."""
+    found = [node for node in observer_nodes(observer) if _is_focus(node)]
+    assert len(found) == 1, f"{len(found)} FocusObservers in the observer tree (exactly one)"
+    return found[0]
+
+
+def compile_observer(observer, num_envs):
+    """The rf_env_observer_program of an observer tree (AssertionError for anything the device cannot run).
+
+    The nodes work on a stack of float32 columns per environment: an IndexedElementObserver or the FocusObserver writes
+    the next free column; a DeltaObserver / NormalizedObserver works in place on the columns its children left, which are
+    the top `width` ones, starting at `first` -- a DeltaObserver's changes replace them, or with include_original follow
+    them.  The stack never shrinks, so the root's width is the most columns in use at any point."""
+    nodes = observer_nodes(observer)
+    focus_observer(observer)
+    # (hstack(..., dtype=float32) is the wrappers'; the device's observations are float32 always)
+    assert not _is_focus(observer), \
+        "a FocusObserver alone observes in float64: wrap it (NormalizedObserver, DeltaObserver)"
+    assert len(nodes) <= _native.MAX_OBS_NODES, f"{len(nodes)} observer nodes (at most {_native.MAX_OBS_NODES})"
+    program = _native.EnvObserverProgram()
+    program.n_nodes = len(nodes)
+    starts = {}  # id(node) -> the first column of what it left
+    top = n_old = 0
+    for k, node in enumerate(nodes):
+        name = type(node).__name__
+        assert isinstance(node, state_observer.BaseObserver) and node.kind is not None, f"unsupported observer {node!r}"
+        assert node.observation_space.shape[0] == num_envs, \
+            f"{name} has num_envs {node.observation_space.shape[0]}, not {num_envs}"
+        out = program.nodes[k]
+        out.kind = node.kind
+        if node.kind in (state_observer.INDEXED_ELEMENT, state_observer.FOCUS):
+            assert node.single_observation_space.shape == (1,), f"{name}: not a scalar observer"
+            if node.kind == state_observer.FOCUS:
+                indices = (node._target_index, node._focus_plane_index)
+                assert indices == (0, 1), f"{name}: (target_index, focus_plane_index) {indices!r} is not (0, 1)"
+            else:
+                out.index = _state_index(node._element_index, name)
+            out.first, out.width = top, 1
+            starts[id(node)] = top
+            top += 1
+        else:
+            children = node._observers
+            assert len(children) >= 1, f"{name}: no wrapped observers"
+            out.first = starts[id(children[0])]
+            out.width = top - out.first
+            starts[id(node)] = out.first
+            if node.kind == state_observer.DELTA:
+                out.include_original = int(bool(node._include_original))
+                out.old_first = n_old
+                n_old += out.width
+                top += out.width if node._include_original else 0
+            else:
+                bounds = np.concatenate([np.ravel(getattr(child.single_observation_space, b)) for child in children
+                                         for b in ("low", "high")])
+                # (the kernels clip with fminf / fmaxf, which do not propagate NaN as numpy.clip does)
+                assert np.all(np.isfinite(bounds)), f"{name}: a wrapped bound is not finite"
+                assert np.all(np.isfinite(node._mid)) and np.all(np.isfinite(node._scale)) and np.all(node._scale != 0), \
+                    f"{name}: a scale is zero or not finite"
+                for j in range(out.width):
+                    out.mid[j] = float(node._mid[j])
+                    out.scale[j] = float(node._scale[j])
+        assert top <= _native.MAX_OBS_COLUMNS, f"{top} observation columns (at most {_native.MAX_OBS_COLUMNS})"
+        assert n_old <= _native.MAX_OBS_COLUMNS, f"{n_old} delta old-value columns (at most {_native.MAX_OBS_COLUMNS})"
+        assert node.single_observation_space.shape == (top - starts[id(node)],), f"{name}: its space is not what it observes"
+    program.width = top
+    program.n_old = n_old
+    return program
+
+
+def host_observer_state(observer, num_envs):
+    """The DeltaObservers' old values of the host twin's tree, laid out as rf_env_get_observer_state returns them:
+    float32[n_old, n], node-major in evaluation order."""
+    rows = [node._old_wrapped_observations.T for node in observer_nodes(observer) if getattr(node, "kind", None) == state_observer.DELTA]
+    return np.concatenate(rows).astype(np.float32) if rows else np.zeros((0, num_envs), dtype=np.float32)
+
+
+def compile_program(transformer, ender, rewarder, num_envs, observer=None):
+    """The rf_env_program of a composition (AssertionError for anything the device cannot run); with an observer
+    tree, (rf_env_program, rf_env_observer_program): an ObservationRewarder's index is then checked against that
+    program's width in place of the built-in observer's four columns."""
+    observer_program = None if observer is None else compile_observer(observer, num_envs)
+    obs_width = 4 if observer is None else observer_program.width
     program = _native.EnvProgram()
     _transformer(program, transformer, num_envs)
     enders, ender_ops = ender_postfix(ender)
@@ -164,7 +273,7 @@ def compile_program(transformer, ender, rewarder, num_envs):
     program.n_rewarders = len(rewarders)
     program.n_reward_ops = len(reward_ops)
     for i, leaf in enumerate(rewarders):
-        program.rewarders[i] = _rewarder(leaf)
+        program.rewarders[i] = _rewarder(leaf, obs_width)
     dtypes = []
     for t, op in enumerate(reward_ops):
         program.reward_ops[t] = op
@@ -174,7 +283,7 @@ def compile_program(transformer, ender, rewarder, num_envs):
             right, left = dtypes.pop(), dtypes.pop()
             dtypes.append(np.promote_types(left, right))
         program.reward_f64[t] = int(dtypes[-1] == np.float64)
-    return program
+    return program if observer is None else (program, observer_program)
 
 
 def host_strategy_state(ender, rewarder, num_envs):
