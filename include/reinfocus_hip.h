@@ -460,6 +460,38 @@ int rf_env_configure_observed(rf_ctx *ctx, const rf_env_config *cfg, const rf_en
  * float32[observer->n_old][n] (DeltaObserver._old_wrapped_observations, one row per column, in node order). */
 int rf_env_get_observer_state(rf_ctx *ctx, float *host_old);
 
+/* ---- the initializer of a device-resident environment as a program --------------------------------------------------
+ * A RangedInitializer over the two state elements (one or several (low, high) ranges each) and its numpy
+ * Generator(PCG64DXSM), so that the states of the auto-reset are drawn on the device: without it every step takes a pool
+ * of n candidate rows the host drew (host_pool) and the host draws the rows that were used a second time.
+ * Replaces: RangedInitializer.initialize (environments/state_initializer.py:53-71) as VectorEnvironment calls it for
+ * the environments that ended (environments/vector_environment.py:138) and in reset().
+ * The generator is numpy's: 128-bit state and odd increment, two 64-bit words each (low word first); a double is
+ * (output >> 11) * 2^-53.  Row r of a draw starts r * d outputs after the generator's state, d = 2 when both elements
+ * have one range (element j = float32(low_j + span_j * u_j)) and 4 otherwise (u_0 ... u_3; element j takes range
+ * min(int64(u_j * count_j), count_j - 1) and is float32(low + span * u_{2+j}) in it); float64 arithmetic, rounded once.
+ *   rf_env_configure_initializer   after any rf_env_configure*: the context draws its reset states itself from now on
+ *                                  (until the next rf_env_configure*).  Refused (RF_ERR_INVALID, nothing changes): a
+ *                                  count outside [1, RF_ENV_MAX_RANGES], a low or span that is not finite, a low or
+ *                                  low + span of magnitude >= 3.4e38 (environments/scalars.py: the float32 result stays
+ *                                  finite), an even increment, a context without an environment.
+ *   rf_env_set_initializer_state   reseeds: the generator's state and (odd) increment.
+ *   rf_env_get_initializer_state   reads them back (Generator.bit_generator.state of the host twin's initializer).
+ * On a context so configured rf_env_step / rf_env_step_jumps take host_pool == NULL (a pool is refused) and the
+ * generator advances by d for every environment that ended, as initialize(k) advances the twin's; rf_env_reset with
+ * host_states == NULL draws all n states (initialize(n)), with host_states it installs them and leaves the generator
+ * alone.  The two-phase and sharded halves -- rf_env_step_begin*, _end, _plan*, _run, _end_given -- and
+ * rf_env_render_states are refused: they have no row offset.  Everything else is unchanged. */
+#define RF_ENV_MAX_RANGES 8
+typedef struct rf_env_initializer_program {
+    int counts[2];                        /* ranges of element 0 / 1: 1 ... RF_ENV_MAX_RANGES */
+    double low[2][RF_ENV_MAX_RANGES], span[2][RF_ENV_MAX_RANGES];   /* span = high - low in float64 */
+    uint64_t state[2], inc[2];            /* PCG64DXSM: low word, high word */
+} rf_env_initializer_program;
+int rf_env_configure_initializer(rf_ctx *ctx, const rf_env_initializer_program *program);
+int rf_env_set_initializer_state(rf_ctx *ctx, const uint64_t state[2], const uint64_t inc[2]);
+int rf_env_get_initializer_state(rf_ctx *ctx, uint64_t state[2], uint64_t inc[2]);
+
 #ifdef __cplusplus
 }
 #endif

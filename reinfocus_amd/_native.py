@@ -69,6 +69,9 @@ SYMBOLS = (
     "rf_env_get_strategy_state",
     "rf_env_configure_observed",
     "rf_env_get_observer_state",
+    "rf_env_configure_initializer",
+    "rf_env_set_initializer_state",
+    "rf_env_get_initializer_state",
     "rf_render_kernel_name",
     "rf_pixels_rendered",
     "rf_allocations_poisoned",
@@ -168,6 +171,23 @@ class EnvObserverProgram(ctypes.Structure):
                 ("nodes", EnvObserverNode * MAX_OBS_NODES)]
 
 
+MAX_RANGES = 8  # RF_ENV_MAX_RANGES
+
+
+class EnvInitializerProgram(ctypes.Structure):
+    """rf_env_initializer_program (include/reinfocus_hip.h): a RangedInitializer of two elements and its generator."""
+
+    _fields_ = [("counts", ctypes.c_int * 2), ("low", (ctypes.c_double * MAX_RANGES) * 2),
+                ("span", (ctypes.c_double * MAX_RANGES) * 2), ("state", ctypes.c_uint64 * 2),
+                ("inc", ctypes.c_uint64 * 2)]
+
+
+def words128(value):
+    """(low word, high word) of a 128-bit integer, as the library takes a PCG64DXSM state or increment."""
+    assert 0 <= value < 1 << 128, f"{value!r} is not a 128-bit integer"
+    return value & (2 ** 64 - 1), value >> 64
+
+
 class NativeLibraryMissing(ImportError):
     """libreinfocus_hip.so has not been built (python -c 'import __graft_entry__ as g; g.build()')."""
 
@@ -233,6 +253,9 @@ def load():
     lib.rf_env_configure_observed.argtypes = [vp, ctypes.POINTER(EnvConfig), ctypes.POINTER(EnvProgram),
                                               ctypes.POINTER(EnvObserverProgram)]
     lib.rf_env_get_observer_state.argtypes = [vp, vp]
+    lib.rf_env_configure_initializer.argtypes = [vp, ctypes.POINTER(EnvInitializerProgram)]
+    lib.rf_env_set_initializer_state.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    lib.rf_env_get_initializer_state.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
     lib.rf_render_kernel_name.restype = ctypes.c_char_p
     lib.rf_render_kernel_name.argtypes = [vp]
     lib.rf_pixels_rendered.restype = ctypes.c_ulonglong
@@ -471,6 +494,22 @@ class Context:
         _check(self._lib.rf_env_get_observer_state(self._h, _ptr(old)))
         return old
 
+    def env_configure_initializer(self, program):
+        """rf_env_configure_initializer: the context draws its reset states itself from `program` (an
+        EnvInitializerProgram) -- env_reset() without states, env_step / env_step_jumps without a pool."""
+        _check(self._lib.rf_env_configure_initializer(self._h, ctypes.byref(program)))
+
+    def env_set_initializer_state(self, state, inc):
+        """rf_env_set_initializer_state: reseeds the device's generator (128-bit Python ints)."""
+        state, inc = (ctypes.c_uint64 * 2)(*words128(state)), (ctypes.c_uint64 * 2)(*words128(inc))
+        _check(self._lib.rf_env_set_initializer_state(self._h, state, inc))
+
+    def env_initializer_state(self):
+        """rf_env_get_initializer_state: (state, inc) of the device's generator as Python ints."""
+        state, inc = (ctypes.c_uint64 * 2)(), (ctypes.c_uint64 * 2)()
+        _check(self._lib.rf_env_get_initializer_state(self._h, state, inc))
+        return state[0] | state[1] << 64, inc[0] | inc[1] << 64
+
     def env_strategy_state(self):
         """rf_env_get_strategy_state: (counters int32[n_enders, n], floats float32[n_enders, n], histories
         float32[rows, n], old values float32[n_rewarders, n])."""
@@ -484,10 +523,12 @@ class Context:
                                                    _ptr(histories) if rows else None, _ptr(old)))
         return counters, floats, histories, old
 
-    def env_reset(self, states):
-        states = np.ascontiguousarray(states, dtype=np.float32).reshape(self._env_n, 2)
+    def env_reset(self, states=None):
+        """states None: the context's device initializer draws them (env_configure_initializer)."""
+        if states is not None:
+            states = np.ascontiguousarray(states, dtype=np.float32).reshape(self._env_n, 2)
         obs = np.empty((self._env_n, self._env_obs_width), dtype=np.float32)
-        _check(self._lib.rf_env_reset(self._h, _ptr(states), _ptr(obs)))
+        _check(self._lib.rf_env_reset(self._h, None if states is None else _ptr(states), _ptr(obs)))
         return obs
 
     # the int32 calls and their float32 (_jumps) twins: one body each, given the C function and the actions' dtype
@@ -495,13 +536,14 @@ class Context:
         # (addresses as plain integers: the ctypes casts of _ptr cost 2 us each, a sixth of a small environment's step)
         n = self._env_n
         actions = np.ascontiguousarray(actions, dtype=dtype).reshape(n)
-        pool = np.ascontiguousarray(pool, dtype=np.float32).reshape(n, 2)
+        if pool is not None:  # (None: the context's device initializer draws the reset states)
+            pool = np.ascontiguousarray(pool, dtype=np.float32).reshape(n, 2)
         obs = np.empty((n, self._env_obs_width), dtype=np.float32)
         rewards = np.empty(n, dtype=np.float64)
         truncated = np.empty(n, dtype=np.bool_)  # (the library writes 0 / 1 bytes)
         k = self._env_k
-        rc = function(self._h, actions.ctypes.data, pool.ctypes.data, obs.ctypes.data, rewards.ctypes.data,
-                      truncated.ctypes.data, self._env_k_ref)
+        rc = function(self._h, actions.ctypes.data, None if pool is None else pool.ctypes.data, obs.ctypes.data,
+                      rewards.ctypes.data, truncated.ctypes.data, self._env_k_ref)
         if rc != 0:
             _check(rc)
         return obs, rewards, truncated, k.value
@@ -521,12 +563,12 @@ class Context:
         _check(function(self._h, _ptr(actions), ctypes.byref(k)))
         return k.value
 
-    def env_step(self, actions, pool):
+    def env_step(self, actions, pool=None):
         """One whole step: (observations, rewards, truncated, number of environments that ended and took rows of
-        `pool`)."""
+        `pool`; None on a context with a device initializer)."""
         return self._env_step(self._lib.rf_env_step, np.int32, actions, pool)
 
-    def env_step_jumps(self, actions, pool):
+    def env_step_jumps(self, actions, pool=None):
         """env_step with float32 actions in [-1, 1] (rf_env_step_jumps; anything else is refused by the library)."""
         return self._env_step(self._lib.rf_env_step_jumps, np.float32, actions, pool)
 

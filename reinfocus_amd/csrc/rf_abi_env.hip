@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include "rf_env.h"
+#include "rf_env_init.h"
 
 using namespace rfh;
 
@@ -286,6 +287,7 @@ int env_configure(rf_ctx *ctx, const rf_env_config *cfg, int task, float stop_th
         ctx->env_block = nullptr;
     }
     ctx->env_ready = false;
+    ctx->env_init = false; // (rf_env_configure_initializer comes after the environment's configuration)
     const size_t n = (size_t)cfg->n;
     // carve one allocation (256-B aligned pieces)
     size_t off = 0;
@@ -427,6 +429,29 @@ struct EnvLaunch {
 
 constexpr int kEnvResetNone = -1; // fused_pass: nobody ended, nothing to pack
 
+// rf_env_configure_initializer's allocation (ctx->d_init): the program, then the generator
+constexpr size_t kInitGenOffset = (sizeof(rf::EnvInit) + 255) & ~(size_t)255;
+
+unsigned long long *init_gen(const rf_ctx *ctx)
+{
+    return (unsigned long long *)((char *)ctx->d_init + kInitGenOffset);
+}
+
+// In place of the pool's copy from the host: rows 0 .. rows-1 of the draw that starts at the generator's state, into
+// `out` (float32[rows][2]: the pool, or in rf_env_reset the states themselves).
+void launch_draw_pool(rf_ctx *ctx, float *out, int rows)
+{
+    hipLaunchKernelGGL(rf::env_draw_pool_kernel, dim3((rows + 255) / 256), dim3(256), 0, ctx->stream,
+                       (const rf::EnvInit *)ctx->d_init, (const unsigned long long *)init_gen(ctx), out, rows);
+}
+
+// initialize(k) of the host twin once the step's count is final on the device (count == null: `given` rows)
+void launch_init_advance(rf_ctx *ctx, const int *count, int given)
+{
+    hipLaunchKernelGGL(rf::env_init_advance_kernel, dim3(1), dim3(64), 0, ctx->stream, (const rf::EnvInit *)ctx->d_init,
+                       init_gen(ctx), count, given);
+}
+
 void launch_reset_kernel(rf_ctx *ctx, const float *pool, int mode, const int *actions)
 {
     hipLaunchKernelGGL(rf::env_reset_kernel, dim3(1), dim3(1024), 0, ctx->stream, ctx->env_cfg, ctx->env, pool, mode,
@@ -530,12 +555,19 @@ int enqueue_env_step(rf_ctx *ctx, const void *actions, const float *pool, float 
     const size_t n = (size_t)d.n;
     const EnvIo io(n, (size_t)ctx->env_obs_width);
     uint8_t *const d_io = (uint8_t *)ctx->d_pool; // (the io block starts with the pool)
-    if (host_io) {
+    const bool draw = ctx->env_init; // the pool is drawn here, where its copy would arrive
+    if (host_io && !draw) {
         RF_HIP(hipMemcpyAsync(d_io, host_io, io.in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    } else if (host_io) {
+        RF_HIP(hipMemcpyAsync(d_io + io.o_actions, host_io + io.o_actions, io.in_bytes - io.o_actions, hipMemcpyHostToDevice,
+                              ctx->stream));
     } else {
         RF_HIP(hipMemcpyAsync(ctx->d_actions, actions, n * 4, hipMemcpyHostToDevice, ctx->stream));
-        RF_HIP(hipMemcpyAsync(ctx->d_pool, pool, n * 8, hipMemcpyHostToDevice, ctx->stream));
+        if (!draw)
+            RF_HIP(hipMemcpyAsync(ctx->d_pool, pool, n * 8, hipMemcpyHostToDevice, ctx->stream));
     }
+    if (draw)
+        launch_draw_pool(ctx, ctx->d_pool, d.n);
     int rc;
     if (fused_step_possible(ctx)) {
         rc = fused_pass(ctx, d, rf::kEnvResetPlan);
@@ -546,6 +578,8 @@ int enqueue_env_step(rf_ctx *ctx, const void *actions, const float *pool, float 
     }
     if (rc != RF_OK)
         return rc;
+    if (draw)
+        launch_init_advance(ctx, ctx->env.done_count, 0);
     if (host_io) {
         RF_HIP(hipMemcpyAsync(host_io + io.o_rewards, d_io + io.o_rewards, io.bytes - io.o_rewards, hipMemcpyDeviceToHost,
                               ctx->stream));
@@ -624,11 +658,16 @@ int env_step_end(rf_ctx *ctx, const float *host_pool, const double *host_focus, 
 {
     const EnvLaunch d(ctx, true);
     if (k > 0) {
-        RF_HIP(hipMemcpyAsync(ctx->d_pool, host_pool, (size_t)k * 8, hipMemcpyHostToDevice, ctx->stream));
+        if (ctx->env_init) // (rf_env_step's count-sized schedule: only the k rows that are used are drawn)
+            launch_draw_pool(ctx, ctx->d_pool, k);
+        else
+            RF_HIP(hipMemcpyAsync(ctx->d_pool, host_pool, (size_t)k * 8, hipMemcpyHostToDevice, ctx->stream));
         if (host_focus) // (they take the place launch_focus would have filled)
             RF_HIP(hipMemcpyAsync(ctx->d_var, host_focus, (size_t)k * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
         if (int rc = reset_pass(ctx, d, k, rf::kEnvResetApply, host_focus == nullptr))
             return rc;
+        if (ctx->env_init)
+            launch_init_advance(ctx, ctx->env.done_count, 0);
         RF_HIP(hipGetLastError());
     }
     RF_HIP(hipMemcpyAsync(host_obs, ctx->env.obs, env_obs_bytes(ctx), hipMemcpyDeviceToHost, ctx->stream));
@@ -636,13 +675,20 @@ int env_step_end(rf_ctx *ctx, const float *host_pool, const double *host_focus, 
     return RF_OK;
 }
 
+// The two-phase and sharded halves hand pool rows to a context by the caller's own offsets; a device initializer has none.
+#define RF_REFUSE_DEVICE_INITIALIZER(ctx, fn)                                                                      \
+    RF_REQUIRE(!((ctx)->env_ready && (ctx)->env_init),                                                             \
+               "%s: the context draws its reset states itself (rf_env_configure_initializer): only whole steps", fn)
+
 // rf_env_step / rf_env_step_jumps: T = int32_t or float (check_actions)
 template <typename T>
 int env_step(rf_ctx *ctx, const T *host_actions, const float *host_pool, float *host_obs, double *host_rewards,
              uint8_t *host_truncated, int *host_n_reset, const char *fn)
 {
-    RF_REQUIRE(ctx != nullptr && host_actions && host_pool && host_obs && host_rewards && host_truncated,
-               "%s: NULL argument", fn);
+    RF_REQUIRE(ctx != nullptr && host_actions && host_obs && host_rewards && host_truncated, "%s: NULL argument", fn);
+    RF_REQUIRE(host_pool || (ctx->env_ready && ctx->env_init), "%s: NULL argument", fn);
+    RF_REQUIRE(!host_pool || !(ctx->env_ready && ctx->env_init),
+               "%s: the context draws its reset states itself (rf_env_configure_initializer): host_pool must be NULL", fn);
     if (int rc = step_may_start(ctx, host_actions, fn, "a two-phase step is open (rf_env_step_end first)"))
         return rc;
     const EnvLaunch d(ctx, false);
@@ -666,7 +712,8 @@ int env_step(rf_ctx *ctx, const T *host_actions, const float *host_pool, float *
         if (graph) {
             uint8_t *st = ctx->h_stage;
             memcpy(st + io.o_actions, host_actions, n * 4);
-            memcpy(st + io.o_pool, host_pool, n * 8);
+            if (host_pool)
+                memcpy(st + io.o_pool, host_pool, n * 8);
             RF_HIP(hipGraphLaunch(ctx->env_graph, ctx->stream));
             RF_HIP(hipStreamSynchronize(ctx->stream));
             memcpy(host_obs, st + io.o_obs, io.obs_bytes);
@@ -705,6 +752,7 @@ int env_step_begin_checked(rf_ctx *ctx, const T *host_actions, double *host_rewa
                            int *host_n_reset, const char *fn)
 {
     RF_REQUIRE(ctx != nullptr && host_actions && host_rewards && host_truncated && host_n_reset, "%s: NULL argument", fn);
+    RF_REFUSE_DEVICE_INITIALIZER(ctx, fn);
     if (int rc = step_may_start(ctx, host_actions, fn, "the previous step was not finished (rf_env_step_end)"))
         return rc;
     drop_env_graph(ctx);
@@ -721,6 +769,7 @@ template <typename T>
 int env_step_plan(rf_ctx *ctx, const T *host_actions, int *host_n_reset, const char *fn)
 {
     RF_REQUIRE(ctx != nullptr && host_actions && host_n_reset, "%s: NULL argument", fn);
+    RF_REFUSE_DEVICE_INITIALIZER(ctx, fn);
     if (int rc = step_may_start(ctx, host_actions, fn, "the previous step was not finished"))
         return rc;
     drop_env_graph(ctx);
@@ -799,6 +848,73 @@ int rf_env_get_observer_state(rf_ctx *ctx, float *host_old)
     return RF_OK;
 }
 
+int rf_env_configure_initializer(rf_ctx *ctx, const rf_env_initializer_program *program)
+{
+    const char *fn = "rf_env_configure_initializer";
+    RF_REQUIRE(ctx != nullptr && program != nullptr, "%s: NULL argument", fn);
+    RF_REQUIRE(ctx->env_ready, "%s: rf_env_configure first", fn);
+    RF_REQUIRE(ctx->env_pending < 0, "%s: a two-phase step is open", fn);
+    for (int j = 0; j < 2; ++j) {
+        const int count = program->counts[j];
+        RF_REQUIRE(count >= 1 && count <= RF_ENV_MAX_RANGES, "%s: element %d has %d ranges (1 to %d)", fn, j, count,
+                   RF_ENV_MAX_RANGES);
+        for (int c = 0; c < count; ++c) {
+            const double low = program->low[j][c], span = program->span[j][c];
+            RF_REQUIRE(isfinite(low) && isfinite(span), "%s: element %d range %d: low %g / span %g is not finite", fn, j, c,
+                       low, span);
+            RF_REQUIRE(fabs(low) < 3.4e38 && fabs(low + span) < 3.4e38,
+                       "%s: element %d range %d: [%g, %g] is outside the float32 range", fn, j, c, low, low + span);
+        }
+    }
+    RF_REQUIRE(program->inc[0] & 1u, "%s: the generator's increment is even", fn);
+    RF_HIP(hipSetDevice(ctx->device));
+    drop_env_graph(ctx); // (a captured step copies its pool from the host)
+    RF_HIP(hipStreamSynchronize(ctx->stream));
+    if (!ctx->d_init)
+        RF_HIP(dev_malloc(&ctx->d_init, kInitGenOffset + sizeof(ctx->env_gen_host)));
+    ctx->env_init_host = rf::init_program(*program);
+    const unsigned long long gen[4] = {program->state[0], program->state[1], program->inc[0], program->inc[1]};
+    memcpy(ctx->env_gen_host, gen, sizeof(gen));
+    RF_HIP(hipMemcpyAsync(ctx->d_init, &ctx->env_init_host, sizeof(rf::EnvInit), hipMemcpyHostToDevice, ctx->stream));
+    RF_HIP(hipMemcpyAsync(init_gen(ctx), ctx->env_gen_host, sizeof(gen), hipMemcpyHostToDevice, ctx->stream));
+    RF_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->env_init = true;
+    return RF_OK;
+}
+
+int rf_env_set_initializer_state(rf_ctx *ctx, const uint64_t state[2], const uint64_t inc[2])
+{
+    const char *fn = "rf_env_set_initializer_state";
+    RF_REQUIRE(ctx != nullptr && state != nullptr && inc != nullptr, "%s: NULL argument", fn);
+    RF_REQUIRE(ctx->env_ready && ctx->env_init, "%s: rf_env_configure_initializer first", fn);
+    RF_REQUIRE(inc[0] & 1u, "%s: the generator's increment is even", fn);
+    RF_HIP(hipSetDevice(ctx->device));
+    RF_HIP(hipStreamSynchronize(ctx->stream)); // (the host copies below are what an earlier upload may still read)
+    rf::init_jump_table(ctx->env_init_host, rf::U128{inc[0], inc[1]}); // (the jumps' additive parts follow the increment)
+    const unsigned long long gen[4] = {state[0], state[1], inc[0], inc[1]};
+    memcpy(ctx->env_gen_host, gen, sizeof(gen));
+    RF_HIP(hipMemcpyAsync(ctx->d_init, &ctx->env_init_host, sizeof(rf::EnvInit), hipMemcpyHostToDevice, ctx->stream));
+    RF_HIP(hipMemcpyAsync(init_gen(ctx), ctx->env_gen_host, sizeof(gen), hipMemcpyHostToDevice, ctx->stream));
+    RF_HIP(hipStreamSynchronize(ctx->stream));
+    return RF_OK;
+}
+
+int rf_env_get_initializer_state(rf_ctx *ctx, uint64_t state[2], uint64_t inc[2])
+{
+    const char *fn = "rf_env_get_initializer_state";
+    RF_REQUIRE(ctx != nullptr && state != nullptr && inc != nullptr, "%s: NULL argument", fn);
+    RF_REQUIRE(ctx->env_ready && ctx->env_init, "%s: rf_env_configure_initializer first", fn);
+    RF_HIP(hipSetDevice(ctx->device));
+    unsigned long long gen[4];
+    RF_HIP(hipMemcpyAsync(gen, init_gen(ctx), sizeof(gen), hipMemcpyDeviceToHost, ctx->stream));
+    RF_HIP(hipStreamSynchronize(ctx->stream));
+    state[0] = gen[0];
+    state[1] = gen[1];
+    inc[0] = gen[2];
+    inc[1] = gen[3];
+    return RF_OK;
+}
+
 int rf_env_get_strategy_state(rf_ctx *ctx, int32_t *host_counters, float *host_floats, float *host_histories,
                               float *host_old)
 {
@@ -826,14 +942,20 @@ int rf_env_get_strategy_state(rf_ctx *ctx, int32_t *host_counters, float *host_f
 
 int rf_env_reset(rf_ctx *ctx, const float *host_states, float *host_obs)
 {
-    RF_REQUIRE(ctx != nullptr && host_states != nullptr && host_obs != nullptr, "rf_env_reset: NULL argument");
+    RF_REQUIRE(ctx != nullptr && host_obs != nullptr, "rf_env_reset: NULL argument");
+    RF_REQUIRE(host_states != nullptr || (ctx->env_ready && ctx->env_init), "rf_env_reset: NULL argument");
     RF_REQUIRE(ctx->env_ready, "rf_env_reset: rf_env_configure first");
     RF_HIP(hipSetDevice(ctx->device));
     ctx->env_pending = -1;
     ctx->env_planned = false;
     ctx->env_needs_reset = false;
     const EnvLaunch d(ctx, true);
-    RF_HIP(hipMemcpyAsync(ctx->env.state, host_states, (size_t)d.n * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (host_states) {
+        RF_HIP(hipMemcpyAsync(ctx->env.state, host_states, (size_t)d.n * 8, hipMemcpyHostToDevice, ctx->stream));
+    } else { // initializer.initialize(num_envs): all n rows are the states, and the generator moves past them
+        launch_draw_pool(ctx, ctx->env.state, d.n);
+        launch_init_advance(ctx, nullptr, d.n);
+    }
     if (int rc = full_pass(ctx, d, true, nullptr))
         return rc;
     RF_HIP(hipGetLastError());
@@ -888,6 +1010,7 @@ int rf_env_step_begin_jumps(rf_ctx *ctx, const float *host_actions, double *host
 int rf_env_step_end(rf_ctx *ctx, const float *host_pool, float *host_obs)
 {
     RF_REQUIRE(ctx != nullptr && host_obs != nullptr, "rf_env_step_end: NULL argument");
+    RF_REFUSE_DEVICE_INITIALIZER(ctx, "rf_env_step_end");
     RF_REQUIRE(ctx->env_ready && ctx->env_pending >= 0 && !ctx->env_planned, "rf_env_step_end: rf_env_step_begin first");
     RF_REQUIRE(ctx->env_pending == 0 || host_pool != nullptr, "rf_env_step_end: %d environments ended but host_pool is NULL",
                ctx->env_pending);
@@ -919,6 +1042,7 @@ int rf_env_step_plan_jumps(rf_ctx *ctx, const float *host_actions, int *host_n_r
 int rf_env_step_run(rf_ctx *ctx, const float *host_pool, float *host_obs, double *host_rewards, uint8_t *host_truncated)
 {
     RF_REQUIRE(ctx != nullptr && host_obs && host_rewards && host_truncated, "rf_env_step_run: NULL argument");
+    RF_REFUSE_DEVICE_INITIALIZER(ctx, "rf_env_step_run");
     RF_REQUIRE(ctx->env_ready && ctx->env_pending >= 0 && ctx->env_planned, "rf_env_step_run: rf_env_step_plan first");
     RF_REQUIRE(ctx->env_pending == 0 || host_pool != nullptr, "rf_env_step_run: %d environments ended but host_pool is NULL",
                ctx->env_pending);
@@ -955,6 +1079,7 @@ int rf_env_step_run(rf_ctx *ctx, const float *host_pool, float *host_obs, double
 int rf_env_render_states(rf_ctx *ctx, int k, const float *host_states, double *host_focus)
 {
     RF_REQUIRE(ctx != nullptr && host_states != nullptr && host_focus != nullptr, "rf_env_render_states: NULL argument");
+    RF_REFUSE_DEVICE_INITIALIZER(ctx, "rf_env_render_states");
     RF_REQUIRE(ctx->env_ready, "rf_env_render_states: rf_env_configure first");
     const rf_env_config &h = ctx->env_host;
     RF_REQUIRE(k > 0 && k <= h.n, "rf_env_render_states: k=%d outside [1, %d]", k, h.n);
@@ -981,6 +1106,7 @@ int rf_env_render_states(rf_ctx *ctx, int k, const float *host_states, double *h
 int rf_env_step_end_given(rf_ctx *ctx, const float *host_pool, const double *host_focus, float *host_obs)
 {
     RF_REQUIRE(ctx != nullptr && host_obs != nullptr, "rf_env_step_end_given: NULL argument");
+    RF_REFUSE_DEVICE_INITIALIZER(ctx, "rf_env_step_end_given");
     RF_REQUIRE(ctx->env_ready && ctx->env_pending >= 0 && !ctx->env_planned, "rf_env_step_end_given: rf_env_step_begin first");
     const int k = ctx->env_pending;
     RF_REQUIRE(k == 0 || (host_pool != nullptr && host_focus != nullptr),

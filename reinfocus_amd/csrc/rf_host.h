@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "rf_env_types.h" // EnvConfig / EnvState (plain structs of device pointers)
+#include "rf_init.h" // EnvInit
 #include "rf_math.h" // CamStatic, CheckerTable
 
 typedef std::pair<hipEvent_t, hipEvent_t> EventPair;
@@ -100,6 +101,12 @@ struct rf_ctx {
     rf_env_program env_program{}; // rf_env_configure_composed's program (host copy: action checks, strategy readback)
     rf_env_observer_program env_observer{}; // rf_env_configure_observed's observer program (host copy; n_nodes 0: none)
     int env_obs_width = 4; // columns of the observations: 4, or that program's width
+    // rf_env_configure_initializer: the reset states are drawn on the device (rf_env_init.h).  One allocation of its own
+    // that outlives reconfigurations: the program (rf::EnvInit), then the generator (state, increment: four 64-bit words)
+    bool env_init = false; // on for the configured environment (every rf_env_configure* turns it off)
+    void *d_init = nullptr;
+    rf::EnvInit env_init_host{};       // what the program on the device was uploaded from (outlives the async copy)
+    unsigned long long env_gen_host[4] = {0, 0, 0, 0}; // ... and the generator
     bool env_fused = true; // the step's two renders and two focus measures as one launch each (REINFOCUS_ENV_FUSED=0: the
                            // three schedules of separate launches)
     long env_one_sync_max = 65536; // blocks of a full render up to which rf_env_step runs without the mid-step round

@@ -33,6 +33,7 @@ import numpy as np
 
 from reinfocus_amd.environments import episode_visualizer
 from reinfocus_amd.environments import spaces
+from reinfocus_amd.environments import state_initializer
 from reinfocus_amd.environments import state_observer
 from reinfocus_amd.graphics import render
 
@@ -642,13 +643,20 @@ def _device_spaces(env, action_set, num_envs):
 
 class _DeviceVectorEnv(_VectorEnvBase):
     """The device-resident vector environment of either task (_JUMPS): DeviceVectorDiscreteSteps,
-    DeviceVectorContinuousJumps."""
+    DeviceVectorContinuousJumps.
+
+    device_initializer=True (opt-in): the initializer is compiled into a device program as well
+    (strategy_program.compile_initializer, rf_env_configure_initializer) and the context draws the reset states itself --
+    reset() passes no states unless state= pins them, step() passes no pool and draws nothing on the host, and
+    reset(seed=...) reseeds the host object and uploads its generator's state.  The initializer object, like the other
+    strategy objects of a device environment, then only describes the environment: it is not advanced, and
+    initializer_state() reads the device's generator.  Results are the same bit for bit either way."""
 
     metadata = {"render_modes": ["rgb_array"], "render_fps": 4}
     _JUMPS = False
 
     def __init__(self, max_episode_steps=20, num_envs=1, render_mode=None, *, frame_height=300,
-                 samples_per_pixel=100, seed=None, device=None, first_state_index=0):
+                 samples_per_pixel=100, seed=None, device=None, first_state_index=0, device_initializer=False):
         super().__init__()
         assert render_mode is None or render_mode in self.metadata["render_modes"]
         self.render_mode = render_mode
@@ -657,7 +665,9 @@ class _DeviceVectorEnv(_VectorEnvBase):
                                    first_state_index, jumps=self._JUMPS)
         self._ctx = self._shard.ctx
         self._limits = _DeviceShard.ENDS
-        self._initializer = _Initializer(self._limits, seed)
+        self._device_initializer = bool(device_initializer)
+        self._initializer = self._task_initializer(seed)
+        self._configure_initializer()
         self._action_set = None if self._JUMPS else self._shard.action_set
         _device_spaces(self, self._action_set, num_envs)
         self._visualizer = None
@@ -670,9 +680,38 @@ class _DeviceVectorEnv(_VectorEnvBase):
     def _state(self):
         return self._ctx.env_states()
 
+    def _task_initializer(self, seed):
+        """The tasks' initializer: _Initializer, or for the device the RangedInitializer that draws exactly its rows
+        (one range per element: low + (high - low) * random(), from the same generator)."""
+        if self._device_initializer:
+            return state_initializer.RangedInitializer([[self._limits], [self._limits]], seed)
+        return _Initializer(self._limits, seed)
+
+    def _configure_initializer(self):
+        """device_initializer=True: compiles self._initializer and hands it to the context (which is closed if the
+        initializer cannot run on the device)."""
+        if not self._device_initializer:
+            return
+        from reinfocus_amd.environments import strategy_program
+
+        try:
+            self._ctx.env_configure_initializer(strategy_program.compile_initializer(self._initializer))
+        except Exception:
+            self._ctx.close()
+            raise
+
+    def initializer_state(self):
+        """(state, inc) of the initializer's PCG64DXSM generator as Python ints: the device's with
+        device_initializer=True (rf_env_get_initializer_state), the host object's otherwise."""
+        from reinfocus_amd.environments import strategy_program
+
+        if self._device_initializer:
+            return self._ctx.env_initializer_state()
+        return strategy_program.initializer_state(self._initializer)
+
     # -- what the tasks and the composed environment differ in ---------------------------------
     def _reseed(self, seed):
-        self._initializer = _Initializer(self._limits, seed)
+        self._initializer = self._task_initializer(seed)
 
     def _checked(self, actions):
         """The step's actions, refused here where the task says so (the library checks the rest)."""
@@ -685,19 +724,27 @@ class _DeviceVectorEnv(_VectorEnvBase):
     def reset(self, *, seed=None, options=None, state=None):
         if seed is not None:
             self._reseed(seed)
-        initial = (self._initializer.initialize(self.num_envs) if state is None
-                   else np.array(state, dtype=np.float32).reshape(self.num_envs, 2))
+            if self._device_initializer:
+                from reinfocus_amd.environments import strategy_program
+
+                self._ctx.env_set_initializer_state(*strategy_program.initializer_state(self._initializer))
+        if state is not None:
+            initial = np.array(state, dtype=np.float32).reshape(self.num_envs, 2)
+        elif self._device_initializer:
+            initial = None  # (drawn on the device)
+        else:
+            initial = self._initializer.initialize(self.num_envs)
         observations = self._ctx.env_reset(initial)
         if self._visualizer is not None:
-            self._visualizer.reset(initial, observations)
+            self._visualizer.reset(self._state if initial is None else initial, observations)
         return observations, {}
 
     def step(self, actions):
         actions = self._checked(actions)
-        pool = self._initializer.propose(self.num_envs)
+        pool = None if self._device_initializer else self._initializer.propose(self.num_envs)
         env_step = self._ctx.env_step_jumps if self._float_actions() else self._ctx.env_step
         observations, rewards, truncated, used = env_step(actions, pool)
-        if used:
+        if used and not self._device_initializer:
             self._initializer.initialize(used)  # consume exactly the rows that were used
         if self._visualizer is not None:  # vector_environment.py:149-156
             state = self._state
@@ -814,10 +861,14 @@ class _ShardedVectorEnv(_VectorEnvBase):
     _JUMPS = False
 
     def __init__(self, max_episode_steps=20, num_envs=1, render_mode=None, *, devices=None, frame_height=300,
-                 samples_per_pixel=100, seed=None, first_state_index=0, exact=False, numa_pin=True):
+                 samples_per_pixel=100, seed=None, first_state_index=0, exact=False, numa_pin=True,
+                 device_initializer=False):
         import concurrent.futures
         from reinfocus_amd import _native
 
+        if device_initializer:
+            raise ValueError(f"{type(self).__name__} draws its reset states on the host; a sharded environment cannot "
+                             "draw them on its devices (device_initializer=)")
         super().__init__()
         assert render_mode is None or render_mode in self.metadata["render_modes"]
         # (one array of RNG states aliased by 300 px and 600 px renders cannot be reproduced across devices, and the
@@ -1191,11 +1242,15 @@ class DeviceVectorEnvironment(_DeviceVectorEnv):
     observer= and focus_observation_index= as VectorEnvironment's: the tree is compiled too
     (strategy_program.compile_observer, rf_env_configure_observed) and only describes the environment -- frame height,
     samples per pixel and device are those of its FocusObserver and that observer's renderer, which is never asked to
-    render; observer_state() reads the device.  One device only: `devices=` (sharding) is refused."""
+    render; observer_state() reads the device.  One device only: `devices=` (sharding) is refused.
+    device_initializer=True: the initializer, a RangedInitializer of two elements, is compiled too
+    (strategy_program.compile_initializer) and, like the other strategy objects, only describes the environment: the
+    device draws the reset states and advances its own copy of the generator (initializer_state()); see
+    _DeviceVectorEnv."""
 
     def __init__(self, ender, initializer, rewarder, transformer, num_envs, ends=(5.0, 10.0), max_focus_move=5.0,
                  render_mode=None, *, frame_height=300, samples_per_pixel=100, device=None, first_state_index=0,
-                 devices=None, observer=None, focus_observation_index=1):
+                 devices=None, observer=None, focus_observation_index=1, device_initializer=False):
         from reinfocus_amd.environments import state_transformer, strategy_program
 
         if devices is not None:
@@ -1227,6 +1282,8 @@ class DeviceVectorEnvironment(_DeviceVectorEnv):
         self._ctx = self._shard.ctx
         self._limits = tuple(ends)
         self._initializer = initializer
+        self._device_initializer = bool(device_initializer)
+        self._configure_initializer()
         self.single_action_space = transformer.single_action_space
         self.action_space = transformer.action_space
         self.single_observation_space = single_observation_space

@@ -23,6 +23,8 @@ import numpy as np
 from reinfocus_amd import _native
 from reinfocus_amd.environments import episode_ender
 from reinfocus_amd.environments import episode_rewarder
+from reinfocus_amd.environments import scalars
+from reinfocus_amd.environments import state_initializer
 from reinfocus_amd.environments import state_observer
 from reinfocus_amd.environments import state_transformer
 
@@ -284,6 +286,39 @@ def compile_program(transformer, ender, rewarder, num_envs, observer=None):
             dtypes.append(np.promote_types(left, right))
         program.reward_f64[t] = int(dtypes[-1] == np.float64)
     return program if observer is None else (program, observer_program)
+
+
+def compile_initializer(initializer):
+    """The rf_env_initializer_program of a RangedInitializer over the two state elements (rf_env_configure_initializer):
+    its ranges as float64 low / high - low, and its generator's state and increment as it stands now (the object itself
+    is not advanced).  Every check of the library is made here first (AssertionError)."""
+    assert isinstance(initializer, state_initializer.RangedInitializer), f"unsupported initializer {initializer!r}"
+    ranges = initializer._ranges
+    assert len(ranges) == 2, f"the initializer has {len(ranges)} elements, not the state's two"
+    program = _native.EnvInitializerProgram()
+    for j, element in enumerate(ranges):
+        assert 1 <= len(element) <= _native.MAX_RANGES, f"element {j} has {len(element)} ranges (1 to {_native.MAX_RANGES})"
+        program.counts[j] = len(element)
+        for c, (low, high) in enumerate(element):
+            low, high = _number(low, f"element {j} range {c}"), _number(high, f"element {j} range {c}")
+            assert abs(low) < scalars.FLOAT32_BOUND and abs(high) < scalars.FLOAT32_BOUND, \
+                f"element {j} range {c}: ({low!r}, {high!r}) is outside the float32 range"
+            program.low[j][c] = low
+            program.span[j][c] = float(initializer._highs[j][c] - initializer._lows[j][c])
+            assert math.isfinite(program.span[j][c]) and abs(low + program.span[j][c]) < scalars.FLOAT32_BOUND, \
+                f"element {j} range {c}: ({low!r}, {high!r}) is outside the float32 range"
+    state, inc = initializer_state(initializer)
+    program.state[0], program.state[1] = _native.words128(state)
+    program.inc[0], program.inc[1] = _native.words128(inc)
+    return program
+
+
+def initializer_state(initializer):
+    """(state, inc) of an initializer's numpy PCG64DXSM generator as Python ints."""
+    state = initializer._generator.bit_generator.state
+    assert state["bit_generator"] == "PCG64DXSM", f"the initializer draws from a {state['bit_generator']} generator"
+    assert state["state"]["inc"] & 1, "the generator's increment is even"
+    return state["state"]["state"], state["state"]["inc"]
 
 
 def host_strategy_state(ender, rewarder, num_envs):
