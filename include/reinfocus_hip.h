@@ -492,6 +492,81 @@ int rf_env_configure_initializer(rf_ctx *ctx, const rf_env_initializer_program *
 int rf_env_set_initializer_state(rf_ctx *ctx, const uint64_t state[2], const uint64_t inc[2]);
 int rf_env_get_initializer_state(rf_ctx *ctx, uint64_t state[2], uint64_t inc[2]);
 
+/* ---- snapshots of a device-resident environment ----------------------------------------------------------------------
+ * Everything that decides the results of later rf_env_step*, rf_env_reset(NULL) and rf_env_render calls, taken and put
+ * back bit for bit: to resume a run in another process (the host forms) and to rewind or branch one quickly and often
+ * (the resident forms, whose copy stays in HBM).  No reference counterpart: the reference cannot serialise its RNG
+ * states at all.  Only copies on the ctx's stream; no kernel.
+ *
+ * A snapshot is a blob of rf_env_snapshot_size bytes: the header below (256 bytes), then these arrays, each at the next
+ * multiple of 256 bytes, in this order, arrays of zero length left out (n = environments, little-endian as the device):
+ *    1 state        float32[n][2]                    11 done_index   int32[n]
+ *    2 steps        int32[n]                         12 done_count   int32[1]
+ *    3 diverging    int32[n]                         13 leaf_count   int32[n_enders][n]      (composed contexts)
+ *    4 last_diff    float32[n]                       14 leaf_float   float32[n_enders][n]
+ *    5 old_wrapped  float32[n][2]                    15 history      float32[rows][n]
+ *    6 old_focus    float32[n]                       16 leaf_old     float32[n_rewarders][n]
+ *    7 cam_dyn      float32[n][9]                    17 obs_old      float32[n_old][n]       (observer program)
+ *    8 rect         float32[n][2]                    18 generator    uint64[4]: state, inc   (device initializer)
+ *    9 cam_dyn2     float32[n][9]                    19 RNG states   uint64[rf_num_states][2]
+ *   10 rect2        float32[n][2]
+ * (7-12: the scene sets of the last render and the ranks of the environments that ended; 2-6 are the built-in tasks'
+ * and the built-in observer's, zero where a composed context does not use them.)  The header also carries the two
+ * host-side words of the scene set, rf_env_scene_len and whether that set is the compacted one.  NOT in a snapshot: the frame buffers, the last step's
+ * observations / rewards / flags, the focus sums, timing accumulators, and the count of steps that decides when graph
+ * replay starts (the restoring context keeps its own).  The blob is data: it holds no pointers.
+ *
+ * The header's fingerprint names the configuration the blob belongs to: n, frame height, spp, gray mode, task,
+ * observation width, rf_num_states, whether a device initializer is configured, and 64-bit FNV-1a hashes of the
+ * rf_env_config (with the stop threshold of rf_env_configure_jumps), the rf_env_program, the rf_env_observer_program and
+ * the initializer's ranges as the library holds them -- not of the generator's words, which are content: a restore
+ * brings the increment along.
+ *   rf_env_snapshot_size      bytes of a snapshot of the configured context
+ *   rf_env_snapshot           device -> host_out[bytes]; synchronous
+ *   rf_env_restore            host_in[bytes] -> device, in place: an instantiated step graph stays valid, the next step
+ *                             may be a replayed one.  Also into a context that was configured alike but never reset
+ *                             (resume): the restore makes the one-time allocations rf_env_reset would have made.  Clears
+ *                             the "aborted step" condition.  Synchronous.
+ *   rf_env_snapshot_resident  device -> the ctx's slot (HBM, allocated on first use, freed by rf_env_snapshot_drop,
+ *                             by any rf_env_configure* and by rf_destroy).  A slot costs rf_env_snapshot_size bytes of
+ *                             HBM -- the RNG states are the bulk, 16 bytes per pixel: 4.29 GB for 4096 environments of
+ *                             256 x 256 pixels, once per slot in use.
+ *   rf_env_restore_resident   the slot -> device, in place.  Both resident forms only enqueue: later calls on the ctx
+ *                             are ordered after them on its stream.
+ * Refused (RF_ERR_INVALID, nothing changes): NULL arguments; a context without an environment; bytes other than
+ * rf_env_snapshot_size; a blob with another magic number or version, or whose fingerprint differs from the context's
+ * in any field (the message names it); a slot outside [0, RF_ENV_SNAPSHOT_SLOTS); restoring or dropping an empty slot;
+ * a slot filled under a configuration the context no longer has (rf_seed, rf_env_configure_initializer); a snapshot
+ * before the first rf_env_reset or after an aborted step; a snapshot or restore while a two-phase or planned step is
+ * open. */
+#define RF_ENV_SNAPSHOT_SLOTS 4
+#define RF_ENV_SNAPSHOT_MAGIC 0x313050414e534652ull /* the bytes "RFSNAP01" */
+#define RF_ENV_SNAPSHOT_VERSION 1
+typedef struct rf_env_snapshot_header {
+    uint64_t magic;              /* RF_ENV_SNAPSHOT_MAGIC */
+    uint32_t version;            /* RF_ENV_SNAPSHOT_VERSION */
+    uint32_t header_bytes;       /* 256: where the first array starts */
+    uint64_t total_bytes;        /* rf_env_snapshot_size */
+    /* fingerprint */
+    int32_t n, frame_height, spp, gray_mode;
+    int32_t task;                /* 0 DiscreteSteps, 1 ContinuousJumps, 2 composed */
+    int32_t obs_width;
+    int32_t device_initializer;  /* 0 / 1 */
+    int32_t reserved;            /* 0 */
+    uint64_t n_states;           /* rf_num_states */
+    uint64_t config_hash, program_hash, observer_hash, initializer_hash;
+    /* host-side words of the scene set */
+    int32_t scene_len;           /* rf_env_scene_len */
+    int32_t last_partial;        /* 1: that set is the compacted one of an auto-reset */
+    uint8_t zero[152];
+} rf_env_snapshot_header;
+int rf_env_snapshot_size(rf_ctx *ctx, uint64_t *bytes);
+int rf_env_snapshot(rf_ctx *ctx, void *host_out, uint64_t bytes);
+int rf_env_restore(rf_ctx *ctx, const void *host_in, uint64_t bytes);
+int rf_env_snapshot_resident(rf_ctx *ctx, int slot);
+int rf_env_restore_resident(rf_ctx *ctx, int slot);
+int rf_env_snapshot_drop(rf_ctx *ctx, int slot);
+
 #ifdef __cplusplus
 }
 #endif

@@ -72,6 +72,12 @@ SYMBOLS = (
     "rf_env_configure_initializer",
     "rf_env_set_initializer_state",
     "rf_env_get_initializer_state",
+    "rf_env_snapshot_size",
+    "rf_env_snapshot",
+    "rf_env_restore",
+    "rf_env_snapshot_resident",
+    "rf_env_restore_resident",
+    "rf_env_snapshot_drop",
     "rf_render_kernel_name",
     "rf_pixels_rendered",
     "rf_allocations_poisoned",
@@ -256,6 +262,12 @@ def load():
     lib.rf_env_configure_initializer.argtypes = [vp, ctypes.POINTER(EnvInitializerProgram)]
     lib.rf_env_set_initializer_state.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
     lib.rf_env_get_initializer_state.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    lib.rf_env_snapshot_size.argtypes = [vp, ctypes.POINTER(u64)]
+    lib.rf_env_snapshot.argtypes = [vp, vp, u64]
+    lib.rf_env_restore.argtypes = [vp, vp, u64]
+    lib.rf_env_snapshot_resident.argtypes = [vp, i32]
+    lib.rf_env_restore_resident.argtypes = [vp, i32]
+    lib.rf_env_snapshot_drop.argtypes = [vp, i32]
     lib.rf_render_kernel_name.restype = ctypes.c_char_p
     lib.rf_render_kernel_name.argtypes = [vp]
     lib.rf_pixels_rendered.restype = ctypes.c_ulonglong
@@ -522,6 +534,38 @@ class Context:
         _check(self._lib.rf_env_get_strategy_state(self._h, _ptr(counters), _ptr(floats),
                                                    _ptr(histories) if rows else None, _ptr(old)))
         return counters, floats, histories, old
+
+    # --- snapshots (rf_env_snapshot* / rf_env_restore*) ---------------------------------------
+    def env_snapshot_size(self):
+        """Bytes of a snapshot of the configured context (rf_env_snapshot_size)."""
+        size = ctypes.c_uint64(0)
+        _check(self._lib.rf_env_snapshot_size(self._h, ctypes.byref(size)))
+        return size.value
+
+    def env_snapshot(self):
+        """rf_env_snapshot: everything that decides the environment's future as one uint8 array (the blob of
+        include/reinfocus_hip.h: header, state arrays, generator, RNG states)."""
+        blob = np.empty(self.env_snapshot_size(), dtype=np.uint8)
+        _check(self._lib.rf_env_snapshot(self._h, _ptr(blob), blob.size))
+        return blob
+
+    def env_restore(self, blob):
+        """rf_env_restore: puts a blob of env_snapshot back, in place; refused (AssertionError, nothing changes) unless
+        it was taken under this context's configuration."""
+        blob = np.ascontiguousarray(blob, dtype=np.uint8).reshape(-1)
+        _check(self._lib.rf_env_restore(self._h, _ptr(blob), blob.size))
+
+    def env_snapshot_resident(self, slot=0):
+        """rf_env_snapshot_resident: the same copy into the context's slot in HBM (enqueued, not waited for)."""
+        _check(self._lib.rf_env_snapshot_resident(self._h, int(slot)))
+
+    def env_restore_resident(self, slot=0):
+        """rf_env_restore_resident: the slot's copy back, in place (enqueued, not waited for)."""
+        _check(self._lib.rf_env_restore_resident(self._h, int(slot)))
+
+    def env_snapshot_drop(self, slot=0):
+        """rf_env_snapshot_drop: frees the slot's memory."""
+        _check(self._lib.rf_env_snapshot_drop(self._h, int(slot)))
 
     def env_reset(self, states=None):
         """states None: the context's device initializer draws them (env_configure_initializer)."""

@@ -325,6 +325,7 @@ int rf_destroy(rf_ctx *ctx)
     if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
     if (ctx->env_block) (void)hipFree(ctx->env_block);
     if (ctx->d_init) (void)hipFree(ctx->d_init);
+    rfh::drop_env_snapshots(ctx);
     if (ctx->general_scratch) (void)hipFree(ctx->general_scratch);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;

@@ -286,7 +286,9 @@ int env_configure(rf_ctx *ctx, const rf_env_config *cfg, int task, float stop_th
         RF_HIP(hipFree(ctx->env_block));
         ctx->env_block = nullptr;
     }
+    drop_env_snapshots(ctx); // (they belong to the configuration that ends here)
     ctx->env_ready = false;
+    ctx->env_started = false;
     ctx->env_init = false; // (rf_env_configure_initializer comes after the environment's configuration)
     const size_t n = (size_t)cfg->n;
     // carve one allocation (256-B aligned pieces)
@@ -428,14 +430,6 @@ struct EnvLaunch {
 };
 
 constexpr int kEnvResetNone = -1; // fused_pass: nobody ended, nothing to pack
-
-// rf_env_configure_initializer's allocation (ctx->d_init): the program, then the generator
-constexpr size_t kInitGenOffset = (sizeof(rf::EnvInit) + 255) & ~(size_t)255;
-
-unsigned long long *init_gen(const rf_ctx *ctx)
-{
-    return (unsigned long long *)((char *)ctx->d_init + kInitGenOffset);
-}
 
 // In place of the pool's copy from the host: rows 0 .. rows-1 of the draw that starts at the generator's state, into
 // `out` (float32[rows][2]: the pool, or in rf_env_reset the states themselves).
@@ -963,6 +957,7 @@ int rf_env_reset(rf_ctx *ctx, const float *host_states, float *host_obs)
     RF_HIP(hipStreamSynchronize(ctx->stream));
     ctx->env_scene_len = d.n;
     ctx->env_last_partial = false;
+    ctx->env_started = true;
     return RF_OK;
 }
 

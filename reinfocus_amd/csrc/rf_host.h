@@ -6,6 +6,7 @@
 //                       the frame buffer, the focus measure (launch_focus, rf_focus, rf_step)
 //   rf_abi_general.hip  rf_render_general
 //   rf_abi_env.hip      the device-resident environment step and its schedules
+//   rf_abi_snapshot.hip snapshots of a device-resident environment (rf_env_snapshot* / rf_env_restore*): copies only
 //
 // Every kernel is defined in exactly one unit (the one that launches it); the units share only host functions.
 #pragma once
@@ -98,6 +99,14 @@ struct rf_ctx {
     bool env_graph_fail_once = false; // REINFOCUS_ENV_GRAPH_FAIL=1 (tests): the first instantiation "fails"
     int env_last_branch = RF_ENV_BRANCH_NONE; // rf_env_last_step_branch
     bool env_needs_reset = false; // rf_env_step_abort dropped a half-finished step
+    bool env_started = false; // rf_env_reset (or a restore) has run since the configuration: there is something to snapshot
+    // rf_env_snapshot_resident's slots: a device copy laid out as the host blob is (d == null: empty), the header that
+    // blob would have had, and the generator's increment at that time (the jump table of env_init_host follows it)
+    struct SnapshotSlot {
+        void *d = nullptr;
+        rf_env_snapshot_header head{};
+        unsigned long long inc[2] = {0, 0};
+    } env_slots[RF_ENV_SNAPSHOT_SLOTS];
     rf_env_program env_program{}; // rf_env_configure_composed's program (host copy: action checks, strategy readback)
     rf_env_observer_program env_observer{}; // rf_env_configure_observed's observer program (host copy; n_nodes 0: none)
     int env_obs_width = 4; // columns of the observations: 4, or that program's width
@@ -176,6 +185,17 @@ struct Timed {
 // The captured env step (rf_env_step) holds device pointers and kernel arguments by value: any
 // call that may reallocate a buffer or change the scene / configuration drops it.
 void drop_env_graph(rf_ctx *ctx);
+
+// Frees every resident snapshot slot (a new configuration, rf_destroy); the caller has synchronised the stream.
+void drop_env_snapshots(rf_ctx *ctx);
+
+// rf_env_configure_initializer's allocation (ctx->d_init): the program, then the generator
+constexpr size_t kInitGenOffset = (sizeof(rf::EnvInit) + 255) & ~(size_t)255;
+
+inline unsigned long long *init_gen(const rf_ctx *ctx)
+{
+    return (unsigned long long *)((char *)ctx->d_init + kInitGenOffset);
+}
 
 // states [first, first + count) of the context's array := the states of `seed` at indices first_state_index ...
 // (rf_seed is this for the whole array)

@@ -763,6 +763,78 @@ class _DeviceVectorEnv(_VectorEnvBase):
         """Only the left halves of render(): the 600 px frames of the scene set uploaded last."""
         return self._shard.render(episode_visualizer.HistoryVisualizer.FRAME)
 
+    # -- snapshots (rf_env_snapshot* / rf_env_restore*; reinfocus_amd/environments/snapshot.py) -----------
+    def _snapshots_possible(self):
+        if self.render_mode is not None:
+            raise ValueError(f"{type(self).__name__} with render_mode={self.render_mode!r} has no snapshots: the "
+                             "visualiser's histories live in Python objects, and its 600 px render re-seeds the RNG "
+                             "states a snapshot would hold")
+
+    def _host_generator(self):
+        """The host initializer's bit generator when it is the one that draws the reset states, else None."""
+        return None if self._device_initializer else self._initializer._generator.bit_generator
+
+    def _snapshot_described(self, blob, generator):
+        from reinfocus_amd.environments import snapshot
+
+        return snapshot.EnvSnapshot(blob, type(self).__name__, self.num_envs, self._shard.frame_height,
+                                    self._shard.samples_per_pixel, generator)
+
+    def _host_generators(self):
+        """slot -> the host generator's state when that resident slot was filled"""
+        return self.__dict__.setdefault("_slot_generators", {})
+
+    def snapshot(self):
+        """Everything that decides what later reset() / step() / render_frames() calls return, as an EnvSnapshot (host
+        memory; .save(path) writes it): the library's blob and, when the reset states are drawn on the host, the
+        initializer's generator.  Refused before the first reset(), after a failed step, and with a render_mode."""
+        self._snapshots_possible()
+        generator = self._host_generator()
+        return self._snapshot_described(self._ctx.env_snapshot(), None if generator is None else generator.state)
+
+    def restore(self, snapshot):
+        """Puts a snapshot() back: on the environment it was taken from (rewind), or on an equal one -- the same class
+        and arguments, possibly in another process -- that may not have been reset() yet (resume).  The environment then
+        goes on as the snapshotted one did.  A snapshot that does not fit is refused and nothing changes: ValueError
+        where this environment can tell, AssertionError from the library (the message names the difference)."""
+        self._snapshots_possible()
+        mine = self._snapshot_described(snapshot.blob, None)
+        if snapshot.describe() != mine.describe():
+            raise ValueError(f"the snapshot is of {snapshot.describe()}, this environment is {mine.describe()}")
+        generator = self._host_generator()
+        if (generator is None) != (snapshot.host_generator is None):
+            raise ValueError("the snapshot was taken with device_initializer=%s, this environment has device_initializer=%s"
+                             % (snapshot.host_generator is None, generator is None))
+        if generator is not None and generator.state["bit_generator"] != snapshot.host_generator["bit_generator"]:
+            raise ValueError(f"the snapshot's initializer draws from a {snapshot.host_generator['bit_generator']}, this "
+                             f"environment's from a {generator.state['bit_generator']}")
+        self._ctx.env_restore(snapshot.blob)
+        if generator is not None:
+            generator.state = snapshot.host_generator
+
+    def snapshot_resident(self, slot=0):
+        """snapshot() into the context's slot `slot` (0-3) in device memory, for rewinding often: nothing crosses to the
+        host, and the call only enqueues the copy.  A slot costs as much device memory as the snapshot has bytes --
+        16 bytes per pixel for the RNG states, 4.29 GB at 4096 x 256 x 256 -- until drop_snapshot(slot)."""
+        self._snapshots_possible()
+        generator = self._host_generator()
+        self._ctx.env_snapshot_resident(slot)
+        if generator is not None:
+            self._host_generators()[int(slot)] = generator.state
+
+    def restore_resident(self, slot=0):
+        """Puts the slot's snapshot back (any number of times); an empty slot is refused (AssertionError)."""
+        self._snapshots_possible()
+        self._ctx.env_restore_resident(slot)
+        generator = self._host_generator()
+        if generator is not None:
+            generator.state = self._host_generators()[int(slot)]
+
+    def drop_snapshot(self, slot=0):
+        """Frees the slot's device memory."""
+        self._ctx.env_snapshot_drop(slot)
+        self._host_generators().pop(int(slot), None)
+
     def close(self):
         self._ctx.close()
 
@@ -1071,6 +1143,12 @@ class _ShardedVectorEnv(_VectorEnvBase):
     def render_frames(self):
         """Only the left halves of render(): the 600 px frames every shard's renderer holds."""
         return _ShardSet(self).render(episode_visualizer.HistoryVisualizer.FRAME)
+
+    def _no_snapshots(self, *args, **kwargs):
+        """A sharded environment is several contexts and one host generator whose steps are cut in two: refused."""
+        raise ValueError(f"{type(self).__name__} has no snapshots: they are one context's (DeviceVector* on one device)")
+
+    snapshot = restore = snapshot_resident = restore_resident = drop_snapshot = _no_snapshots
 
     def close(self):
         for thread, shard in zip(self._threads, self._shards):
