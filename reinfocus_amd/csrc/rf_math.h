@@ -475,6 +475,9 @@ RF_HD void sphere_sample(Rng &g, float &q0, float &q1, float &q2)
 // residual; v_rcp_f32 (1 ulp) refined by two fma Newton steps.  Equality with the IEEE
 // results is checked for EVERY float in the range on the GPU (tests/gpucheck).  The host
 // build (tests/hostsim) uses the plain operators: same values by definition.
+// The kernels no longer call these two: unit_dir_y, their only user, takes both values from
+// len_inv_rn_fast below (one v_rsq_f32, no compare).  They stay as the separately proven
+// pair that tests/gpucheck names.
 RF_HD bool in_fast_range(float x)
 {
     uint32_t b;
@@ -512,14 +515,44 @@ RF_HD float rcp_rn_fast(float x) // requires in_fast_range(x)
 #endif
 }
 
+// len = RN(sqrt(sq)) and inv = RN(1 / len) from ONE transcendental: v_rsq_f32 seeds the Goldschmidt / Markstein
+// square root (fmas only: no compare, no select, no integer operation), whose refined h is 1 / (2 len) to about an
+// ulp, so that h scaled by two takes the place of v_rcp_f32 as the seed of the same two Newton steps as in
+// rcp_rn_fast.  The scale is 2 + 2^-22, one ulp more than two: for a len whose significand is all ones, 1 / len lies
+// 2^-25 relative above a rounding midpoint, and the last Newton step lands on the right side of it only when it
+// comes from above (from the seed 2h, a power of two there, it ties to even and stays: the two sq per binade pair
+// below a power of four were wrong by one ulp); everywhere else the seed is as good as before.  Both results are
+// checked against the IEEE operators for EVERY sq in the range on the GPU (tests/lencheck).  Every fma is explicit:
+// nothing here depends on contraction.
+RF_HD void len_inv_rn_fast(float sq, float &len, float &inv) // requires in_fast_range(sq)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    const float y = __builtin_amdgcn_rsqf(sq);
+    float g = sq * y;
+    float h = 0.5f * y;
+    const float r = __builtin_fmaf(-h, g, 0.5f);
+    g = __builtin_fmaf(g, r, g);
+    h = __builtin_fmaf(h, r, h);
+    const float d = __builtin_fmaf(-g, g, sq);
+    len = __builtin_fmaf(d, h, g);
+    const float y0 = h * 0x1.000002p+1f;
+    const float y1 = __builtin_fmaf(__builtin_fmaf(-len, y0, 1.0f), y0, y0);
+    inv = __builtin_fmaf(__builtin_fmaf(-len, y1, 1.0f), y1, y1);
+#else
+    len = __builtin_sqrtf(sq);
+    inv = 1.0f / len;
+#endif
+}
+
 RF_HD float unit_dir_y(float d0, float d1, float d2)
 {
     float sq = sq_len(d0, d1, d2);
     // float32(math.sqrt(sq)): an f64 sqrt rounded to f32 equals the correctly rounded
     // f32 sqrt (53 >= 2*24+2); inv = float32(1) / len with IEEE division.
     if (__builtin_expect(in_fast_range(sq), 1)) {
-        const float len = sqrt_rn_fast(sq); // in [2^-50, 2^50]
-        return d1 * rcp_rn_fast(len);
+        float len, inv; // len in [2^-50, 2^50]
+        len_inv_rn_fast(sq, len, inv);
+        return d1 * inv;
     }
     // generic expansions (need -fhip-fp32-correctly-rounded-divide-sqrt, HIP's default;
     // __fsqrt_rn would be the *native* 1-ulp sqrt)
