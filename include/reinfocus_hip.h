@@ -567,6 +567,65 @@ int rf_env_snapshot_resident(rf_ctx *ctx, int slot);
 int rf_env_restore_resident(rf_ctx *ctx, int slot);
 int rf_env_snapshot_drop(rf_ctx *ctx, int slot);
 
+/* ---- device io: stepping from device arrays without a host synchronisation ---------------------------------------------
+ * rf_env_step / rf_env_step_jumps take host pointers and end in a host synchronisation.  A policy network that runs on
+ * the same GPU would bring its actions to the host only for the library to upload them again, and fetch results it
+ * re-uploads.  The device forms take the actions where they are, in the dtype the network produces, hand the results
+ * to device arrays, and only enqueue: on return nothing has necessarily run.  No reference counterpart.
+ *
+ * Arrays: device memory of the ctx's GPU, contiguous -- d_actions int32[n] (RF_ACTION_I32), int64[n] (RF_ACTION_I64)
+ * or float32[n] (RF_ACTION_F32), d_obs float32[n][W] (W = 4, or the observer program's width), d_rewards float64[n],
+ * d_truncated uint8[n] (0 / 1), d_n_reset int32[1] or NULL.  The library asks the runtime about every pointer
+ * (hipPointerGetAttributes) and refuses, before anything is enqueued and without dereferencing it, whatever is not
+ * device memory of that GPU, is misaligned, or is shorter than the array.  The pointers may differ from call to call.
+ *
+ * Ordering: caller_stream is a hipStream_t (0: the default stream).  The ctx's stream waits for an event recorded on
+ * the caller's stream, the step runs, and the caller's stream waits for an event recorded after it -- so work the
+ * caller enqueues next on that stream sees the results, and memory the caller's allocator hands out again later on
+ * that stream is ordered after the step.  No host synchronisation.  A caller stream that is being captured is refused.
+ *
+ * Actions are checked on the device (env_gather_actions_kernel, one lane per environment), by the rules of the host
+ * forms.  A host form refuses the whole step; a device step cannot, so an invalid action is replaced and recorded:
+ *   int32 / int64 index   valid: 0 <= a < n_actions on the full 64-bit value     invalid: clamped into [0, n_actions - 1]
+ *   float32 jump          valid: -1 <= a <= 1 (ContinuousJumps, ContinuousJump)  invalid: NaN -> 0, else clamped to [-1, 1]
+ *   float32 otherwise     valid: finite                                          invalid: 0
+ * The replacement exists only so that no kernel reads outside the action set or carries a NaN into the states: the
+ * trajectory after an invalid action is NOT a valid one.  The fault word in device memory keeps the earliest step --
+ * steps are counted from the last reset, whole steps of either form -- and the lowest environment within it.  FAULT
+ * RULE: a recorded fault is sticky.  Device steps enqueued before anybody asks keep running on replacement values --
+ * the price of not synchronising.  Once the host has seen it (rf_env_device_status, or any call listed under "deferred
+ * bookkeeping"), every rf_env_step*, rf_env_snapshot* and rf_env_step_device is refused (RF_ERR_INVALID; the message
+ * names step and environment) until rf_env_reset or rf_env_reset_device, which clear it.
+ *
+ * Schedule: the step enqueued in one go -- the fused pass, or with separate launches the full pass and the reset pass
+ * over all n slots, at ANY size (the count-sized schedule of rf_env_step needs a round trip).  From the second step on
+ * the step's body is replayed (where rf_env_step would replay: fused, or small enough for the one-sync schedule)
+ * as a hipGraph of its own that holds none of the caller's pointers; the gather of the
+ * actions and the hand-over of the results are launched around it.  rf_env_last_step_branch says RF_ENV_BRANCH_FUSED,
+ * _FUSED_GRAPH, _ONE_SYNC or _GRAPH, never _COUNT_SIZED.  The graph of the host form is a different one and untouched.
+ *
+ * Deferred bookkeeping: what the host keeps per step that depends on the number k of environments that ended -- the
+ * scene set the renderer holds (rf_env_scene_len, rf_env_render, the header of a snapshot) and the pixels rendered
+ * (rf_pixels_rendered: the device keeps a running total of n + k per device step) -- is settled, with one
+ * synchronisation, by the next of: rf_env_scene_len, rf_env_render, rf_env_snapshot*, rf_env_restore*, rf_timing_read,
+ * rf_env_step / rf_env_step_jumps, rf_env_reset, rf_env_configure*, rf_env_device_status.  rf_pixels_rendered itself
+ * takes no context and reports what has been settled.  Device and host steps may be mixed freely.
+ *
+ *   rf_env_step_device    one whole step.  Refused (RF_ERR_INVALID, nothing enqueued, nothing changes): a context
+ *                         without a device initializer (rf_env_configure_initializer: the host's initializer advances
+ *                         by k, which only a synchronisation can tell it); an open two-phase or planned step; an
+ *                         aborted step; a fault already seen; RF_ACTION_I32 / _I64 on a float32 task and RF_ACTION_F32
+ *                         on an index task; an array the runtime does not vouch for; a capturing caller stream.
+ *   rf_env_reset_device   rf_env_reset(ctx, NULL, obs) with the observations to d_obs: all n states drawn on the
+ *                         device, nothing waited for.  Clears a fault and an aborted step.
+ *   rf_env_device_status  synchronises the ctx's stream, settles the bookkeeping and reports the fault: the step and
+ *                         the environment, or -1 / -1. */
+enum { RF_ACTION_I32 = 0, RF_ACTION_I64 = 1, RF_ACTION_F32 = 2 };
+int rf_env_step_device(rf_ctx *ctx, const void *d_actions, int action_dtype, float *d_obs, double *d_rewards,
+                       uint8_t *d_truncated, int32_t *d_n_reset, void *caller_stream);
+int rf_env_reset_device(rf_ctx *ctx, float *d_obs, void *caller_stream);
+int rf_env_device_status(rf_ctx *ctx, int *fault_step, int *fault_env);
+
 #ifdef __cplusplus
 }
 #endif

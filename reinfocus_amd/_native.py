@@ -24,6 +24,8 @@ RF_ERR_OOM = -4
 GRAY_15BIT = 15
 GRAY_14BIT = 14
 
+ACTION_I32, ACTION_I64, ACTION_F32 = range(3)  # RF_ACTION_*
+
 # every symbol include/reinfocus_hip.h declares
 SYMBOLS = (
     "rf_last_error",
@@ -78,6 +80,9 @@ SYMBOLS = (
     "rf_env_snapshot_resident",
     "rf_env_restore_resident",
     "rf_env_snapshot_drop",
+    "rf_env_step_device",
+    "rf_env_reset_device",
+    "rf_env_device_status",
     "rf_render_kernel_name",
     "rf_pixels_rendered",
     "rf_allocations_poisoned",
@@ -268,6 +273,9 @@ def load():
     lib.rf_env_snapshot_resident.argtypes = [vp, i32]
     lib.rf_env_restore_resident.argtypes = [vp, i32]
     lib.rf_env_snapshot_drop.argtypes = [vp, i32]
+    lib.rf_env_step_device.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
+    lib.rf_env_reset_device.argtypes = [vp, vp, vp]
+    lib.rf_env_device_status.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]
     lib.rf_render_kernel_name.restype = ctypes.c_char_p
     lib.rf_render_kernel_name.argtypes = [vp]
     lib.rf_pixels_rendered.restype = ctypes.c_ulonglong
@@ -574,6 +582,26 @@ class Context:
         obs = np.empty((self._env_n, self._env_obs_width), dtype=np.float32)
         _check(self._lib.rf_env_reset(self._h, None if states is None else _ptr(states), _ptr(obs)))
         return obs
+
+    # --- device io (rf_env_step_device ...): addresses of device memory as plain integers, nothing waited for --------
+    def env_step_device(self, actions_ptr, action_dtype, obs_ptr, rewards_ptr, truncated_ptr, n_reset_ptr, stream):
+        """rf_env_step_device: one whole step from / to device arrays given by address (ACTION_I32 / _I64 / _F32;
+        n_reset_ptr may be None), ordered after and before `stream` (a hipStream_t as an integer).  Only enqueues."""
+        rc = self._lib.rf_env_step_device(self._h, actions_ptr, action_dtype, obs_ptr, rewards_ptr, truncated_ptr,
+                                          n_reset_ptr, stream)
+        if rc != 0:
+            _check(rc)
+
+    def env_reset_device(self, obs_ptr, stream):
+        """rf_env_reset_device: env_reset() with the observations to a device array.  Only enqueues."""
+        _check(self._lib.rf_env_reset_device(self._h, obs_ptr, stream))
+
+    def env_device_status(self):
+        """rf_env_device_status: synchronises, settles what device steps left open; None, or (step, env) of the
+        earliest invalid action since the last reset."""
+        step, env = ctypes.c_int(-1), ctypes.c_int(-1)
+        _check(self._lib.rf_env_device_status(self._h, ctypes.byref(step), ctypes.byref(env)))
+        return None if step.value < 0 else (step.value, env.value)
 
     # the int32 calls and their float32 (_jumps) twins: one body each, given the C function and the actions' dtype
     def _env_step(self, function, dtype, actions, pool):

@@ -77,6 +77,9 @@ void drop_env_graph(rf_ctx *ctx)
     if (ctx->env_graph)
         (void)hipGraphExecDestroy(ctx->env_graph);
     ctx->env_graph = nullptr;
+    if (ctx->env_graph_dev)
+        (void)hipGraphExecDestroy(ctx->env_graph_dev);
+    ctx->env_graph_dev = nullptr;
     ctx->env_steps = 0;
 }
 
@@ -322,6 +325,10 @@ int rf_destroy(rf_ctx *ctx)
     if (ctx->d_sums) (void)hipFree(ctx->d_sums);
     if (ctx->d_var) (void)hipFree(ctx->d_var);
     if (ctx->env_graph) (void)hipGraphExecDestroy(ctx->env_graph);
+    if (ctx->env_graph_dev) (void)hipGraphExecDestroy(ctx->env_graph_dev);
+    if (ctx->io_ev_in) (void)hipEventDestroy(ctx->io_ev_in);
+    if (ctx->io_ev_out) (void)hipEventDestroy(ctx->io_ev_out);
+    if (ctx->d_io_state) (void)hipFree(ctx->d_io_state);
     if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
     if (ctx->env_block) (void)hipFree(ctx->env_block);
     if (ctx->d_init) (void)hipFree(ctx->d_init);
@@ -467,6 +474,8 @@ int rf_timing_read(rf_ctx *ctx, double *render_ms, uint64_t *render_launches, do
 {
     RF_REQUIRE(ctx != nullptr, "rf_timing_read: ctx is NULL");
     RF_HIP(hipSetDevice(ctx->device));
+    if (int rc = resolve_device_steps(ctx)) // (the pixels of device steps belong to the launches counted here)
+        return rc;
     RF_HIP(hipStreamSynchronize(ctx->stream));
     int rc = drain_events(ctx->ev_render, ctx->render_ms, ctx->render_n);
     if (rc == RF_OK)

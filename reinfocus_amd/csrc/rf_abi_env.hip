@@ -8,6 +8,7 @@
 
 #include "rf_env.h"
 #include "rf_env_init.h"
+#include "rf_env_io.h"
 
 using namespace rfh;
 
@@ -281,6 +282,10 @@ int env_configure(rf_ctx *ctx, const rf_env_config *cfg, int task, float stop_th
     RF_REQUIRE(need <= ctx->n_states, "rf_env_configure: %llu pixels but only %llu RNG states (rf_seed first)",
                (unsigned long long)need, (unsigned long long)ctx->n_states);
     drop_env_graph(ctx);
+    if (int rc = resolve_device_steps(ctx)) // (the pixels of the configuration that ends here)
+        return rc;
+    ctx->env_fault_step = ctx->env_fault_env = -1;
+    ctx->env_step_index = 0;
     RF_HIP(hipStreamSynchronize(ctx->stream));
     if (ctx->env_block) {
         RF_HIP(hipFree(ctx->env_block));
@@ -520,6 +525,7 @@ int step_may_start(const rf_ctx *ctx, const T *host_actions, const char *fn, con
     RF_REQUIRE(ctx->env_ready, "%s: rf_env_configure first", fn);
     RF_REQUIRE(ctx->env_pending < 0, "%s: %s", fn, open_step);
     RF_REQUIRE(!ctx->env_needs_reset, "%s: a step was aborted (rf_env_reset first)", fn);
+    RF_REFUSE_FAULTED(ctx, fn);
     return check_actions(ctx, host_actions, fn);
 }
 
@@ -527,8 +533,19 @@ int step_may_start(const rf_ctx *ctx, const T *host_actions, const char *fn, con
 void finish_step(rf_ctx *ctx, int k)
 {
     ctx->env_steps += 1;
+    ctx->env_step_index += 1;
     ctx->env_scene_len = k > 0 ? k : ctx->env_host.n;
     ctx->env_last_partial = k > 0;
+}
+
+// A reset clears a fault: the host's record of it, and the word on the device (in stream order, after the device steps
+// that may still write it).
+int clear_fault(rf_ctx *ctx)
+{
+    ctx->env_fault_step = ctx->env_fault_env = -1;
+    if (ctx->d_io_state)
+        RF_HIP(hipMemsetAsync(&((rf::EnvIoState *)ctx->d_io_state)->fault, 0xFF, sizeof(unsigned long long), ctx->stream));
+    return RF_OK;
 }
 
 bool env_one_sync(const rf_ctx *ctx)
@@ -538,28 +555,12 @@ bool env_one_sync(const rf_ctx *ctx)
     return (long)n * tiles <= ctx->env_one_sync_max;
 }
 
-// Enqueues one whole step on the ctx's stream without waiting for anything: uploads, the fused pass -- or the full
-// pass and the reset pass over all n slots --, the downloads.  Used directly and under stream capture.
-int enqueue_env_step(rf_ctx *ctx, const void *actions, const float *pool, float *obs, double *rewards,
-                     uint8_t *truncated, int *count, uint8_t *host_io = nullptr)
+// What a step enqueued in one go runs between its inputs' arrival and its results' departure: the pool's draw on a
+// context with a device initializer, the fused pass -- or the full pass and the reset pass over all n slots --, the
+// generator's advance.  Reads the actions in ctx->d_actions; used directly and under stream capture.
+int enqueue_env_step_body(rf_ctx *ctx, const EnvLaunch &d)
 {
-    // host_io: the host side is an image of the device's io block (EnvIo: the pinned staging buffer of the replayed
-    // step) -- one copy in, one copy out; otherwise the caller's six separate arrays
-    const EnvLaunch d(ctx, false);
-    const size_t n = (size_t)d.n;
-    const EnvIo io(n, (size_t)ctx->env_obs_width);
-    uint8_t *const d_io = (uint8_t *)ctx->d_pool; // (the io block starts with the pool)
     const bool draw = ctx->env_init; // the pool is drawn here, where its copy would arrive
-    if (host_io && !draw) {
-        RF_HIP(hipMemcpyAsync(d_io, host_io, io.in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    } else if (host_io) {
-        RF_HIP(hipMemcpyAsync(d_io + io.o_actions, host_io + io.o_actions, io.in_bytes - io.o_actions, hipMemcpyHostToDevice,
-                              ctx->stream));
-    } else {
-        RF_HIP(hipMemcpyAsync(ctx->d_actions, actions, n * 4, hipMemcpyHostToDevice, ctx->stream));
-        if (!draw)
-            RF_HIP(hipMemcpyAsync(ctx->d_pool, pool, n * 8, hipMemcpyHostToDevice, ctx->stream));
-    }
     if (draw)
         launch_draw_pool(ctx, ctx->d_pool, d.n);
     int rc;
@@ -574,6 +575,33 @@ int enqueue_env_step(rf_ctx *ctx, const void *actions, const float *pool, float 
         return rc;
     if (draw)
         launch_init_advance(ctx, ctx->env.done_count, 0);
+    return RF_OK;
+}
+
+// Enqueues one whole step on the ctx's stream without waiting for anything: uploads, the body above, the downloads.
+// Used directly and under stream capture.
+int enqueue_env_step(rf_ctx *ctx, const void *actions, const float *pool, float *obs, double *rewards,
+                     uint8_t *truncated, int *count, uint8_t *host_io = nullptr)
+{
+    // host_io: the host side is an image of the device's io block (EnvIo: the pinned staging buffer of the replayed
+    // step) -- one copy in, one copy out; otherwise the caller's six separate arrays
+    const EnvLaunch d(ctx, false);
+    const size_t n = (size_t)d.n;
+    const EnvIo io(n, (size_t)ctx->env_obs_width);
+    uint8_t *const d_io = (uint8_t *)ctx->d_pool; // (the io block starts with the pool)
+    const bool draw = ctx->env_init; // (the body draws the pool where its copy would arrive)
+    if (host_io && !draw) {
+        RF_HIP(hipMemcpyAsync(d_io, host_io, io.in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    } else if (host_io) {
+        RF_HIP(hipMemcpyAsync(d_io + io.o_actions, host_io + io.o_actions, io.in_bytes - io.o_actions, hipMemcpyHostToDevice,
+                              ctx->stream));
+    } else {
+        RF_HIP(hipMemcpyAsync(ctx->d_actions, actions, n * 4, hipMemcpyHostToDevice, ctx->stream));
+        if (!draw)
+            RF_HIP(hipMemcpyAsync(ctx->d_pool, pool, n * 8, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (int rc = enqueue_env_step_body(ctx, d))
+        return rc;
     if (host_io) {
         RF_HIP(hipMemcpyAsync(host_io + io.o_rewards, d_io + io.o_rewards, io.bytes - io.o_rewards, hipMemcpyDeviceToHost,
                               ctx->stream));
@@ -683,6 +711,8 @@ int env_step(rf_ctx *ctx, const T *host_actions, const float *host_pool, float *
     RF_REQUIRE(host_pool || (ctx->env_ready && ctx->env_init), "%s: NULL argument", fn);
     RF_REQUIRE(!host_pool || !(ctx->env_ready && ctx->env_init),
                "%s: the context draws its reset states itself (rf_env_configure_initializer): host_pool must be NULL", fn);
+    if (int rc = resolve_device_steps(ctx)) // (device steps before this one: their bookkeeping, and a fault of theirs)
+        return rc;
     if (int rc = step_may_start(ctx, host_actions, fn, "a two-phase step is open (rf_env_step_end first)"))
         return rc;
     const EnvLaunch d(ctx, false);
@@ -783,7 +813,114 @@ int env_step_plan(rf_ctx *ctx, const T *host_actions, int *host_n_reset, const c
     return RF_OK;
 }
 
+// ---- device steps: rf_env_step_device, rf_env_reset_device (kernels: rf_env_io.h) -----------------------------------
+
+// A caller's array of `bytes` bytes: device memory of the context's GPU, aligned for its elements, and inside one
+// allocation -- asked of the runtime, never dereferenced.
+int check_device_array(const rf_ctx *ctx, const void *p, size_t bytes, size_t align, const char *what, const char *fn)
+{
+    hipPointerAttribute_t attr{};
+    const hipError_t e = hipPointerGetAttributes(&attr, p);
+    if (e != hipSuccess)
+        (void)hipGetLastError(); // (what the runtime says of a pointer it does not know)
+    RF_REQUIRE(e == hipSuccess && attr.type == hipMemoryTypeDevice && attr.device == ctx->device,
+               "%s: %s is not device memory of the context's GPU %d", fn, what, ctx->device);
+    RF_REQUIRE((uintptr_t)p % align == 0, "%s: %s is not aligned to %zu bytes", fn, what, align);
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) == hipSuccess)
+        RF_REQUIRE((const char *)p + bytes <= (const char *)base + size, "%s: %s has fewer than %zu bytes", fn, what, bytes);
+    else
+        (void)hipGetLastError();
+    return RF_OK;
+}
+
+// Calling a device form while the caller's stream is being captured is out of scope: the events below would become
+// nodes of the caller's graph, and the host bookkeeping would run once for any number of replays.
+int refuse_capturing(hipStream_t caller, const char *fn)
+{
+    hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
+    const hipError_t e = hipStreamIsCapturing(caller, &status);
+    if (e != hipSuccess)
+        (void)hipGetLastError();
+    RF_REQUIRE(e == hipSuccess && status == hipStreamCaptureStatusNone,
+               "%s: the caller's stream is being captured (a device step cannot be part of the caller's graph)", fn);
+    return RF_OK;
+}
+
+// The ctx's stream waits for what the caller's stream holds now / the caller's stream waits for what the ctx's holds
+// now: ordering by events only, no host synchronisation.
+int wait_for_caller(rf_ctx *ctx, hipStream_t caller)
+{
+    RF_HIP(hipEventRecord(ctx->io_ev_in, caller));
+    RF_HIP(hipStreamWaitEvent(ctx->stream, ctx->io_ev_in, 0));
+    return RF_OK;
+}
+
+int let_caller_wait(rf_ctx *ctx, hipStream_t caller)
+{
+    RF_HIP(hipEventRecord(ctx->io_ev_out, ctx->stream));
+    RF_HIP(hipStreamWaitEvent(caller, ctx->io_ev_out, 0));
+    return RF_OK;
+}
+
+// The graph of a device step: enqueue_env_step_body alone -- no copy and no pointer of the caller's, so it is valid for
+// whatever arrays the next call brings; the gather before it and the scatter after it are launched around the replay.
+// As for ensure_env_graph, a capture problem disables replay and the step keeps being enqueued call by call.
+int ensure_env_graph_dev(rf_ctx *ctx, const EnvLaunch &d)
+{
+    if (ctx->env_graph_dev)
+        return RF_OK;
+    hipGraph_t captured = nullptr;
+    hipError_t he = hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal);
+    int rc = RF_OK;
+    if (he == hipSuccess) {
+        rc = enqueue_env_step_body(ctx, d);
+        he = hipStreamEndCapture(ctx->stream, &captured);
+        if (he == hipSuccess && rc == RF_OK)
+            he = hipGraphInstantiate(&ctx->env_graph_dev, captured, nullptr, nullptr, 0);
+        if (captured)
+            (void)hipGraphDestroy(captured);
+    }
+    if (he != hipSuccess || rc != RF_OK || !ctx->env_graph_dev) {
+        (void)hipGetLastError();
+        ctx->env_graph_dev = nullptr;
+        ctx->env_graph_enabled = false;
+    }
+    return RF_OK;
+}
+
 } // namespace
+
+namespace rfh {
+
+int resolve_device_steps(rf_ctx *ctx)
+{
+    if (!ctx->io_unresolved)
+        return RF_OK;
+    rf::EnvIoState io{};
+    int k = 0;
+    RF_HIP(hipMemcpyAsync(&io, ctx->d_io_state, sizeof(io), hipMemcpyDeviceToHost, ctx->stream));
+    if (ctx->io_scene_pending)
+        RF_HIP(hipMemcpyAsync(&k, ctx->env.done_count, 4, hipMemcpyDeviceToHost, ctx->stream));
+    RF_HIP(hipStreamSynchronize(ctx->stream));
+    // every device step rendered its n environments, then the k that ended: the running total holds the sum
+    const unsigned long long fh = (unsigned long long)ctx->env_host.frame_height;
+    count_pixels((io.env_renders - ctx->io_renders_seen) * fh * fh);
+    ctx->io_renders_seen = io.env_renders;
+    if (ctx->io_scene_pending) { // finish_step's words, of the last device step
+        ctx->env_scene_len = k > 0 ? k : ctx->env_host.n;
+        ctx->env_last_partial = k > 0;
+    }
+    if (io.fault != rf::kNoFault && ctx->env_fault_step < 0) {
+        ctx->env_fault_step = (int)(io.fault >> 32);
+        ctx->env_fault_env = (int)(io.fault & 0xffffffffull);
+    }
+    ctx->io_unresolved = ctx->io_scene_pending = false;
+    return RF_OK;
+}
+
+} // namespace rfh
 
 extern "C" {
 
@@ -871,6 +1008,19 @@ int rf_env_configure_initializer(rf_ctx *ctx, const rf_env_initializer_program *
     memcpy(ctx->env_gen_host, gen, sizeof(gen));
     RF_HIP(hipMemcpyAsync(ctx->d_init, &ctx->env_init_host, sizeof(rf::EnvInit), hipMemcpyHostToDevice, ctx->stream));
     RF_HIP(hipMemcpyAsync(init_gen(ctx), ctx->env_gen_host, sizeof(gen), hipMemcpyHostToDevice, ctx->stream));
+    // what device steps need besides: the fault word and the running total, and the two events that order a step
+    // against the caller's stream (made here, where waiting is allowed, so that no device step ever allocates)
+    if (int rc = resolve_device_steps(ctx))
+        return rc;
+    if (!ctx->d_io_state)
+        RF_HIP(dev_malloc(&ctx->d_io_state, sizeof(rf::EnvIoState)));
+    if (!ctx->io_ev_in)
+        RF_HIP(hipEventCreateWithFlags(&ctx->io_ev_in, hipEventDisableTiming));
+    if (!ctx->io_ev_out)
+        RF_HIP(hipEventCreateWithFlags(&ctx->io_ev_out, hipEventDisableTiming));
+    const rf::EnvIoState fresh{rf::kNoFault, 0};
+    RF_HIP(hipMemcpyAsync(ctx->d_io_state, &fresh, sizeof(fresh), hipMemcpyHostToDevice, ctx->stream));
+    ctx->io_renders_seen = 0;
     RF_HIP(hipStreamSynchronize(ctx->stream));
     ctx->env_init = true;
     return RF_OK;
@@ -940,9 +1090,14 @@ int rf_env_reset(rf_ctx *ctx, const float *host_states, float *host_obs)
     RF_REQUIRE(host_states != nullptr || (ctx->env_ready && ctx->env_init), "rf_env_reset: NULL argument");
     RF_REQUIRE(ctx->env_ready, "rf_env_reset: rf_env_configure first");
     RF_HIP(hipSetDevice(ctx->device));
+    if (int rc = resolve_device_steps(ctx))
+        return rc;
+    if (int rc = clear_fault(ctx))
+        return rc;
     ctx->env_pending = -1;
     ctx->env_planned = false;
     ctx->env_needs_reset = false;
+    ctx->env_step_index = 0;
     const EnvLaunch d(ctx, true);
     if (host_states) {
         RF_HIP(hipMemcpyAsync(ctx->env.state, host_states, (size_t)d.n * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -1114,6 +1269,7 @@ int rf_env_step_end_given(rf_ctx *ctx, const float *host_pool, const double *hos
         return rc;
     ctx->env_needs_reset = false;
     ctx->env_steps += 1; // (the renderer's scene set is not this step's: rf_env_render_states says what it holds)
+    ctx->env_step_index += 1;
     return RF_OK;
 }
 int rf_env_step_abort(rf_ctx *ctx)
@@ -1134,6 +1290,11 @@ int rf_env_scene_len(rf_ctx *ctx, int *n_envs)
 {
     RF_REQUIRE(ctx != nullptr && n_envs != nullptr, "rf_env_scene_len: NULL argument");
     RF_REQUIRE(ctx->env_ready, "rf_env_scene_len: rf_env_configure first");
+    if (ctx->io_unresolved) { // (the last device step's count decides it)
+        RF_HIP(hipSetDevice(ctx->device));
+        if (int rc = resolve_device_steps(ctx))
+            return rc;
+    }
     *n_envs = ctx->env_scene_len;
     return RF_OK;
 }
@@ -1141,6 +1302,11 @@ int rf_env_scene_len(rf_ctx *ctx, int *n_envs)
 int rf_env_render(rf_ctx *ctx, int frame_height, int spp, uint8_t *host_out)
 {
     RF_REQUIRE(ctx != nullptr, "rf_env_render: ctx is NULL");
+    if (ctx->io_unresolved) { // (which scene set the renderer holds is the last device step's to say)
+        RF_HIP(hipSetDevice(ctx->device));
+        if (int rc = resolve_device_steps(ctx))
+            return rc;
+    }
     RF_REQUIRE(ctx->env_ready && ctx->env_scene_len > 0, "rf_env_render: rf_env_reset first");
     RF_REQUIRE(ctx->env_pending < 0, "rf_env_render: a two-phase step is open (rf_env_step_end first)");
     RF_REQUIRE(frame_height > 0 && spp > 0, "rf_env_render: frame_height, spp must be positive");
@@ -1179,6 +1345,136 @@ int rf_env_get_states(rf_ctx *ctx, float *host_states)
     RF_HIP(hipSetDevice(ctx->device));
     RF_HIP(hipMemcpyAsync(host_states, ctx->env.state, (size_t)ctx->env_host.n * 8, hipMemcpyDeviceToHost, ctx->stream));
     RF_HIP(hipStreamSynchronize(ctx->stream));
+    return RF_OK;
+}
+
+int rf_env_step_device(rf_ctx *ctx, const void *d_actions, int action_dtype, float *d_obs, double *d_rewards,
+                       uint8_t *d_truncated, int32_t *d_n_reset, void *caller_stream)
+{
+    const char *fn = "rf_env_step_device";
+    RF_REQUIRE(ctx != nullptr && d_actions && d_obs && d_rewards && d_truncated, "%s: NULL argument", fn);
+    RF_REQUIRE(action_dtype == RF_ACTION_I32 || action_dtype == RF_ACTION_I64 || action_dtype == RF_ACTION_F32,
+               "%s: unknown action_dtype %d", fn, action_dtype);
+    RF_REQUIRE(ctx->env_ready, "%s: rf_env_configure first", fn);
+    RF_REQUIRE(ctx->env_init, "%s: the context has no device initializer (rf_env_configure_initializer): the host's "
+               "initializer advances by the number of environments that ended, which only a synchronisation can tell it", fn);
+    RF_REQUIRE(ctx->env_pending < 0, "%s: a two-phase or planned step is open", fn);
+    RF_REQUIRE(!ctx->env_needs_reset, "%s: a step was aborted (rf_env_reset first)", fn);
+    RF_REFUSE_FAULTED(ctx, fn);
+    const int task = ctx->env_cfg.task;
+    const bool index_task = task == rf::kEnvTaskSteps || (task == rf::kEnvTaskComposed && composed_discrete(ctx));
+    RF_REQUIRE(index_task == (action_dtype != RF_ACTION_F32), "%s: the context takes %s actions", fn,
+               index_task ? "RF_ACTION_I32 / RF_ACTION_I64" : "RF_ACTION_F32");
+    const int rule = index_task ? rf::kActionRuleIndex
+                     : (task == rf::kEnvTaskJumps || ctx->env_program.transformer == RF_TRANSFORM_CONTINUOUS_JUMP)
+                         ? rf::kActionRuleJump
+                         : rf::kActionRuleFinite;
+    const int n_actions = task == rf::kEnvTaskComposed ? ctx->env_program.n_actions : ctx->env_host.n_actions;
+    RF_HIP(hipSetDevice(ctx->device));
+    const EnvLaunch d(ctx, false);
+    const size_t n = (size_t)d.n, action_bytes = action_dtype == RF_ACTION_I64 ? 8 : 4;
+    int rc = check_device_array(ctx, d_actions, n * action_bytes, action_bytes, "d_actions", fn);
+    if (rc == RF_OK)
+        rc = check_device_array(ctx, d_obs, env_obs_bytes(ctx), 4, "d_obs", fn);
+    if (rc == RF_OK)
+        rc = check_device_array(ctx, d_rewards, n * 8, 8, "d_rewards", fn);
+    if (rc == RF_OK)
+        rc = check_device_array(ctx, d_truncated, n, 1, "d_truncated", fn);
+    if (rc == RF_OK && d_n_reset)
+        rc = check_device_array(ctx, d_n_reset, 4, 4, "d_n_reset", fn);
+    const hipStream_t caller = (hipStream_t)caller_stream;
+    if (rc == RF_OK)
+        rc = refuse_capturing(caller, fn);
+    if (rc != RF_OK)
+        return rc;
+    // the schedule: as rf_env_step's enqueued-in-one-go branch at any size (the count-sized one needs a round trip)
+    const bool fused = fused_step_possible(ctx);
+    // ... replayed where rf_env_step replays: not at the sizes whose host form takes the count-sized schedule
+    bool graph = ctx->env_graph_enabled && !ctx->timing && ctx->env_steps >= 1 && (fused || env_one_sync(ctx));
+    ctx->env_needs_reset = true; // until the whole step is enqueued (a HIP failure below returns early)
+    if (int rc2 = wait_for_caller(ctx, caller))
+        return rc2;
+    if (graph) { // (captured on the ctx's stream, which holds nothing of this step yet but the wait)
+        if (int rc2 = ensure_env_graph_dev(ctx, d))
+            return rc2;
+        graph = ctx->env_graph_dev != nullptr;
+    }
+    rf::EnvIoState *io = (rf::EnvIoState *)ctx->d_io_state;
+    hipLaunchKernelGGL(rf::env_gather_actions_kernel, d.grid, d.block, 0, ctx->stream, d_actions, action_dtype, rule,
+                       n_actions, d.n, (unsigned)ctx->env_step_index, ctx->d_actions, io);
+    if (graph) {
+        RF_HIP(hipGraphLaunch(ctx->env_graph_dev, ctx->stream));
+    } else if (int rc2 = enqueue_env_step_body(ctx, d)) {
+        return rc2;
+    }
+    const int cells = d.n * ctx->env_obs_width, blocks = (cells + 255) / 256;
+    hipLaunchKernelGGL(rf::env_scatter_results_kernel, dim3(blocks < 1024 ? blocks : 1024), dim3(256), 0, ctx->stream,
+                       (const float *)ctx->env.obs, (const double *)ctx->env.reward, (const uint8_t *)ctx->env.truncated,
+                       (const int *)ctx->env.done_count, d.n, ctx->env_obs_width, d_obs, d_rewards, d_truncated, d_n_reset,
+                       io);
+    RF_HIP(hipGetLastError());
+    if (int rc2 = let_caller_wait(ctx, caller))
+        return rc2;
+    ctx->env_needs_reset = false;
+    ctx->env_last_branch = fused ? (graph ? RF_ENV_BRANCH_FUSED_GRAPH : RF_ENV_BRANCH_FUSED)
+                                 : (graph ? RF_ENV_BRANCH_GRAPH : RF_ENV_BRANCH_ONE_SYNC);
+    ctx->env_steps += 1;
+    ctx->env_step_index += 1;
+    ctx->io_unresolved = ctx->io_scene_pending = true; // (finish_step's words wait for somebody to ask)
+    return RF_OK;
+}
+
+int rf_env_reset_device(rf_ctx *ctx, float *d_obs, void *caller_stream)
+{
+    const char *fn = "rf_env_reset_device";
+    RF_REQUIRE(ctx != nullptr && d_obs != nullptr, "%s: NULL argument", fn);
+    RF_REQUIRE(ctx->env_ready, "%s: rf_env_configure first", fn);
+    RF_REQUIRE(ctx->env_init, "%s: the context has no device initializer (rf_env_configure_initializer) to draw the "
+               "states from", fn);
+    RF_HIP(hipSetDevice(ctx->device));
+    const hipStream_t caller = (hipStream_t)caller_stream;
+    if (int rc = check_device_array(ctx, d_obs, env_obs_bytes(ctx), 4, "d_obs", fn))
+        return rc;
+    if (int rc = refuse_capturing(caller, fn))
+        return rc;
+    ctx->env_pending = -1;
+    ctx->env_planned = false;
+    ctx->env_needs_reset = true; // until everything is enqueued
+    if (int rc = wait_for_caller(ctx, caller))
+        return rc;
+    if (int rc = clear_fault(ctx))
+        return rc;
+    const EnvLaunch d(ctx, true);
+    launch_draw_pool(ctx, ctx->env.state, d.n); // initializer.initialize(num_envs), as rf_env_reset(ctx, NULL, obs)
+    launch_init_advance(ctx, nullptr, d.n);
+    if (int rc = full_pass(ctx, d, true, nullptr))
+        return rc;
+    const int cells = d.n * ctx->env_obs_width, blocks = (cells + 255) / 256;
+    hipLaunchKernelGGL(rf::env_scatter_obs_kernel, dim3(blocks < 1024 ? blocks : 1024), dim3(256), 0, ctx->stream,
+                       (const float *)ctx->env.obs, cells, d_obs);
+    RF_HIP(hipGetLastError());
+    if (int rc = let_caller_wait(ctx, caller))
+        return rc;
+    ctx->env_needs_reset = false;
+    ctx->env_step_index = 0;
+    ctx->env_scene_len = d.n; // (known without asking the device; the pixels of earlier device steps stay open)
+    ctx->env_last_partial = false;
+    ctx->io_scene_pending = false;
+    ctx->env_started = true;
+    return RF_OK;
+}
+
+int rf_env_device_status(rf_ctx *ctx, int *fault_step, int *fault_env)
+{
+    const char *fn = "rf_env_device_status";
+    RF_REQUIRE(ctx != nullptr && fault_step != nullptr && fault_env != nullptr, "%s: NULL argument", fn);
+    RF_REQUIRE(ctx->env_ready, "%s: rf_env_configure first", fn);
+    RF_HIP(hipSetDevice(ctx->device));
+    if (int rc = resolve_device_steps(ctx))
+        return rc;
+    RF_HIP(hipStreamSynchronize(ctx->stream));
+    *fault_step = ctx->env_fault_step;
+    *fault_env = ctx->env_fault_env;
     return RF_OK;
 }
 

@@ -149,6 +149,7 @@ int may_snapshot(const rf_ctx *ctx, const char *fn)
     RF_REQUIRE(ctx->env_started, "%s: rf_env_reset first", fn);
     RF_REQUIRE(ctx->env_pending < 0, "%s: a two-phase or planned step is open", fn);
     RF_REQUIRE(!ctx->env_needs_reset, "%s: a step was aborted (rf_env_reset first)", fn);
+    RF_REFUSE_FAULTED(ctx, fn);
     return RF_OK;
 }
 
@@ -229,6 +230,9 @@ int rf_env_snapshot(rf_ctx *ctx, void *host_out, uint64_t bytes)
 {
     const char *fn = "rf_env_snapshot";
     RF_REQUIRE(ctx != nullptr && host_out != nullptr, "%s: NULL argument", fn);
+    RF_HIP(hipSetDevice(ctx->device));
+    if (int rc = resolve_device_steps(ctx)) // (the header holds the scene length)
+        return rc;
     if (int rc = may_snapshot(ctx, fn))
         return rc;
     const Layout layout(ctx);
@@ -251,6 +255,9 @@ int rf_env_restore(rf_ctx *ctx, const void *host_in, uint64_t bytes)
 {
     const char *fn = "rf_env_restore";
     RF_REQUIRE(ctx != nullptr && host_in != nullptr, "%s: NULL argument", fn);
+    RF_HIP(hipSetDevice(ctx->device));
+    if (int rc = resolve_device_steps(ctx)) // (before the scene words it would set are replaced)
+        return rc;
     if (int rc = may_restore(ctx, fn))
         return rc;
     const Layout layout(ctx);
@@ -282,6 +289,9 @@ int rf_env_snapshot_resident(rf_ctx *ctx, int slot)
 {
     const char *fn = "rf_env_snapshot_resident";
     RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", fn);
+    RF_HIP(hipSetDevice(ctx->device));
+    if (int rc = resolve_device_steps(ctx)) // (the header holds the scene length)
+        return rc;
     if (int rc = may_snapshot(ctx, fn))
         return rc;
     if (int rc = check_slot(slot, fn))
@@ -308,6 +318,9 @@ int rf_env_restore_resident(rf_ctx *ctx, int slot)
 {
     const char *fn = "rf_env_restore_resident";
     RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", fn);
+    RF_HIP(hipSetDevice(ctx->device));
+    if (int rc = resolve_device_steps(ctx)) // (before the scene words it would set are replaced)
+        return rc;
     if (int rc = may_restore(ctx, fn))
         return rc;
     if (int rc = check_slot(slot, fn))

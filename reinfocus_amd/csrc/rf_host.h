@@ -120,6 +120,17 @@ struct rf_ctx {
                            // three schedules of separate launches)
     long env_one_sync_max = 65536; // blocks of a full render up to which rf_env_step runs without the mid-step round
                                    // trip (REINFOCUS_ENV_ONE_SYNC_MAX; tests set 0 to reach the count-sized branch at small sizes)
+    // device steps (rf_env_step_device / rf_env_reset_device; kernels in rf_env_io.h): actions and results stay in
+    // device memory, nothing is waited for, and what the host keeps per step is settled later (resolve_device_steps)
+    void *d_io_state = nullptr; // rf::EnvIoState (fault word, running total of rendered environments); allocated by
+                                // rf_env_configure_initializer, which is what makes device steps possible
+    hipEvent_t io_ev_in = nullptr, io_ev_out = nullptr; // the caller's stream -> the ctx's stream -> the caller's stream
+    hipGraphExec_t env_graph_dev = nullptr; // the replayed step's body alone: no copy, no pointer of the caller's
+    bool io_unresolved = false;    // device steps ran whose pixels and faults the host has not accounted yet
+    bool io_scene_pending = false; // ... and the last of them decides env_scene_len / env_last_partial
+    unsigned long long io_renders_seen = 0; // EnvIoState::env_renders as of the last resolution
+    uint64_t env_step_index = 0;   // whole steps of either form since the last reset: the step number of a fault
+    int env_fault_step = -1, env_fault_env = -1; // a resolved fault (>= 0): only a reset makes the environment usable
     const char *render_kernel = "none"; // the render kernel the last launch used (rf_render_kernel_name)
     void *general_scratch = nullptr;    // scene arrays of rf_render_general (grown on demand)
     unsigned general_redo_last = 0;     // pixels the launches of the last rf_render_general left to the fix-up kernel
@@ -185,6 +196,16 @@ struct Timed {
 // The captured env step (rf_env_step) holds device pointers and kernel arguments by value: any
 // call that may reallocate a buffer or change the scene / configuration drops it.
 void drop_env_graph(rf_ctx *ctx);
+
+// Settles what device steps (rf_env_step_device) left open on the host: synchronises the ctx's stream, accounts the
+// pixels they rendered, takes the scene set of the last one (env_scene_len, env_last_partial) and records a fault.
+// Every entry point that reads one of those calls it first; without open device steps it does nothing.
+int resolve_device_steps(rf_ctx *ctx);
+// ... and what such an entry point says once a fault is recorded
+#define RF_REFUSE_FAULTED(ctx, fn)                                                                                  \
+    RF_REQUIRE((ctx)->env_fault_step < 0,                                                                           \
+               "%s: the action of environment %d in step %d was invalid, and the steps since then ran on its "      \
+               "replacement (rf_env_reset or rf_env_reset_device first)", fn, (ctx)->env_fault_env, (ctx)->env_fault_step)
 
 // Frees every resident snapshot slot (a new configuration, rf_destroy); the caller has synchronised the stream.
 void drop_env_snapshots(rf_ctx *ctx);

@@ -744,6 +744,7 @@ class _DeviceVectorEnv(_VectorEnvBase):
         pool = None if self._device_initializer else self._initializer.propose(self.num_envs)
         env_step = self._ctx.env_step_jumps if self._float_actions() else self._ctx.env_step
         observations, rewards, truncated, used = env_step(actions, pool)
+        self._last_used = used
         if used and not self._device_initializer:
             self._initializer.initialize(used)  # consume exactly the rows that were used
         if self._visualizer is not None:  # vector_environment.py:149-156
@@ -762,6 +763,67 @@ class _DeviceVectorEnv(_VectorEnvBase):
     def render_frames(self):
         """Only the left halves of render(): the 600 px frames of the scene set uploaded last."""
         return self._shard.render(episode_visualizer.HistoryVisualizer.FRAME)
+
+    # -- torch tensors in and out, nothing on the host (rf_env_step_device; reinfocus_amd/torch_interop.py) ----------
+    def _tensor_io(self):
+        """The environment's torch_interop.TensorIO, made on first use -- or the ValueError that says why there is none."""
+        io = self.__dict__.get("_tensors")
+        if io is not None:
+            return io
+        if not self._device_initializer:
+            raise ValueError(f"{type(self).__name__} with device_initializer=False has no *_tensors methods: its "
+                             "initializer lives on the host and advances by the number of environments that ended, "
+                             "which only a host synchronisation per step can tell it (pass device_initializer=True)")
+        if self.render_mode is not None:
+            raise ValueError(f"{type(self).__name__} with render_mode={self.render_mode!r} has no *_tensors methods: "
+                             "the visualiser reads states and observations on the host after every step")
+        from reinfocus_amd import torch_interop
+
+        io = self._tensors = torch_interop.TensorIO(self._ctx, self.num_envs, self._ctx._env_obs_width,
+                                                    self._float_actions(), self._ctx.device)
+        return io
+
+    def reset_tensors(self, *, seed=None):
+        """reset() with the observations as a torch.float32 [num_envs, W] tensor on the environment's GPU: (obs, {}).
+        Nothing is waited for (seed=... reseeds the device's generator, which does synchronise).  obs is the
+        environment's own tensor: the next reset_tensors / step_tensors call without out= overwrites it."""
+        io = self._tensor_io()
+        if seed is not None:
+            from reinfocus_amd.environments import strategy_program
+
+            self._reseed(seed)
+            self._ctx.env_set_initializer_state(*strategy_program.initializer_state(self._initializer))
+        return io.reset(), {}
+
+    def step_tensors(self, actions, *, out=None):
+        """step() from a torch tensor of actions on the environment's GPU -- contiguous, shape [num_envs] or
+        [num_envs, 1], torch.int32 / torch.int64 for index tasks, torch.float32 for float tasks; anything else raises
+        TypeError / ValueError before the library is called -- to torch tensors there: (obs float32 [num_envs, W],
+        rewards float64 [num_envs], terminated bool [num_envs] (all False), truncated bool [num_envs], {}).  The step is
+        ordered after what torch's current stream holds, that stream waits for it, and the host waits for nothing.
+
+        Without out= the environment owns ONE set of output tensors and overwrites it in the next call, as vector
+        environments commonly do: clone what must outlive a step.  out=(obs, rewards, truncated) writes into the
+        caller's tensors instead (truncated: torch.bool or torch.uint8).
+
+        Actions are checked on the device.  An invalid one (an index outside the action set, NaN, a jump outside
+        [-1, 1]) cannot refuse the step as step() does: it is replaced, the steps go on, and device_fault() -- or the
+        next step(), snapshot() or render_frames() -- reports it; from then on the environment refuses everything until
+        reset() / reset_tensors().  step() and step_tensors() may be mixed freely."""
+        result = self._tensor_io().step(actions, out)
+        self._last_used = None
+        return result
+
+    def device_fault(self):
+        """None, or (step, env) of the earliest invalid action step_tensors met since the last reset -- steps counted
+        from that reset, the lowest environment within the step.  Synchronises."""
+        return self._tensor_io().fault()
+
+    def last_reset_count(self):
+        """How many environments ended (and were reset) in the last step of either form.  Synchronises."""
+        if self.__dict__.get("_last_used") is None:
+            self._last_used = self._tensor_io().reset_count()
+        return self._last_used
 
     # -- snapshots (rf_env_snapshot* / rf_env_restore*; reinfocus_amd/environments/snapshot.py) -----------
     def _snapshots_possible(self):
@@ -1040,6 +1102,14 @@ class _ShardedVectorEnv(_VectorEnvBase):
     @property
     def _state(self):
         return np.concatenate(self._each(lambda shard: shard.ctx.env_states()))
+
+    def _no_tensors(self, *args, **kwargs):
+        """reset_tensors / step_tensors / device_fault / last_reset_count of the one-device classes."""
+        raise ValueError(f"{type(self).__name__} has no *_tensors methods: a tensor lives on one GPU, the shards' rows "
+                         "are handed out by one host initializer between the two halves of a step, and the host "
+                         "concatenates their results (use a Device* class with device_initializer=True per GPU)")
+
+    reset_tensors = step_tensors = device_fault = last_reset_count = _no_tensors
 
     def reset(self, *, seed=None, options=None, state=None):
         if seed is not None:
