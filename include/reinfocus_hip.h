@@ -508,16 +508,20 @@ int rf_env_get_initializer_state(rf_ctx *ctx, uint64_t state[2], uint64_t inc[2]
  *    6 old_focus    float32[n]                       16 leaf_old     float32[n_rewarders][n]
  *    7 cam_dyn      float32[n][9]                    17 obs_old      float32[n_old][n]       (observer program)
  *    8 rect         float32[n][2]                    18 generator    uint64[4]: state, inc   (device initializer)
- *    9 cam_dyn2     float32[n][9]                    19 RNG states   uint64[rf_num_states][2]
- *   10 rect2        float32[n][2]
+ *    9 cam_dyn2     float32[n][9]                    19 ep_return    float64[n]              (episode records)
+ *   10 rect2        float32[n][2]                    20 ep_length    int32[n]
+ *                                                    21 RNG states   uint64[rf_num_states][2]
  * (7-12: the scene sets of the last render and the ranks of the environments that ended; 2-6 are the built-in tasks'
  * and the built-in observer's, zero where a composed context does not use them.)  The header also carries the two
  * host-side words of the scene set, rf_env_scene_len and whether that set is the compacted one.  NOT in a snapshot: the frame buffers, the last step's
- * observations / rewards / flags, the focus sums, timing accumulators, and the count of steps that decides when graph
+ * observations / rewards / flags and episode records (final_observation / episode_return / episode_length: outputs
+ * like the observations -- only the two accumulators, 19 and 20, are state), the focus sums, timing accumulators, and the count of steps that decides when graph
  * replay starts (the restoring context keeps its own).  The blob is data: it holds no pointers.
  *
  * The header's fingerprint names the configuration the blob belongs to: n, frame height, spp, gray mode, task,
- * observation width, rf_num_states, whether a device initializer is configured, and 64-bit FNV-1a hashes of the
+ * observation width, rf_num_states, whether a device initializer is configured, whether episode records are kept
+ * (rf_env_configure_records: without them arrays 19 and 20 have zero length and the word is 0, so the blob is what it
+ * was before that call existed, byte for byte, and the version stays 1), and 64-bit FNV-1a hashes of the
  * rf_env_config (with the stop threshold of rf_env_configure_jumps), the rf_env_program, the rf_env_observer_program and
  * the initializer's ranges as the library holds them -- not of the generator's words, which are content: a restore
  * brings the increment along.
@@ -552,7 +556,7 @@ typedef struct rf_env_snapshot_header {
     int32_t task;                /* 0 DiscreteSteps, 1 ContinuousJumps, 2 composed */
     int32_t obs_width;
     int32_t device_initializer;  /* 0 / 1 */
-    int32_t reserved;            /* 0 */
+    int32_t episode_records;     /* 0 / 1: rf_env_configure_records (was `reserved`, 0) */
     uint64_t n_states;           /* rf_num_states */
     uint64_t config_hash, program_hash, observer_hash, initializer_hash;
     /* host-side words of the scene set */
@@ -625,6 +629,49 @@ int rf_env_step_device(rf_ctx *ctx, const void *d_actions, int action_dtype, flo
                        uint8_t *d_truncated, int32_t *d_n_reset, void *caller_stream);
 int rf_env_reset_device(rf_ctx *ctx, float *d_obs, void *caller_stream);
 int rf_env_device_status(rf_ctx *ctx, int *fault_step, int *fault_env);
+
+/* ---- episode records: final observations, episode returns and lengths on the device ----------------------------------
+ * Every episode of these environments ends by truncation and the step resets the environment in the same call
+ * (environments/vector_environment.py:137-151): the observation row a step returns for an environment that ended is
+ * already the first one of its next episode (:144-146).  With records on, the step also keeps what a learner reads at
+ * an episode boundary.  No reference counterpart.  Off by default; with it off nothing a caller can observe changes.
+ *
+ * One definition, host twins and device alike.  Per environment e two accumulators, ep_return[e] (float64) and
+ * ep_length[e] (int32); rf_env_reset / rf_env_reset_device zero them.  In a step, once the reward r[e] (the float64
+ * value the step returns) and the flag are computed: ep_return[e] += r[e] (one float64 addition per step, in step
+ * order), ep_length[e] += 1.  Three record arrays are then written for EVERY environment in EVERY step:
+ *   where e ended this step   final_obs[e][0..W) = the observation row the step computed, before the auto-reset
+ *                             overwrote it; returns[e] = ep_return[e]; lengths[e] = ep_length[e]; the accumulators are
+ *                             zeroed
+ *   where it did not          final_obs[e][..] = NaN; returns[e] = NaN; lengths[e] = 0
+ * (W = 4, or the observer program's width.)  The records are outputs, written before they are read, like the
+ * observations: they hold no stale rows, and only the accumulators are state (and part of a snapshot).  Kernels:
+ * env_record_one in csrc/rf_env.h, called by env_post_kernel / env_finish_kernel -- every schedule of the step, the
+ * two-phase and planned halves included.  The replayed hipGraphs hold the arrays' addresses by value: records are
+ * chosen before the first step, so before any capture, and nothing in a graph depends on the caller's pointers (the
+ * hand-over to the caller's arrays is launched after the replay, outside it).
+ *   rf_env_configure_records       on != 0: the context keeps records from now on; 0: it stops.  After any
+ *                                  rf_env_configure* (each of which turns records off again and, as before, drops the
+ *                                  snapshot slots; this call drops them too) and before the first rf_env_reset.  The
+ *                                  arrays are part of the environment's one allocation.  Refused (RF_ERR_INVALID,
+ *                                  nothing changes): a context without an environment, one that has stepped, an open
+ *                                  two-phase or planned step.
+ *   rf_env_get_records             the records of the last step of any form: host_final_obs float32[n][W],
+ *                                  host_returns float64[n], host_lengths int32[n], each of which may be NULL.
+ *                                  Synchronous, ordered on the ctx's stream.  Refused without records, before the
+ *                                  first step after a reset, and while a two-phase or planned step is open.
+ *   rf_env_get_record_accumulators the running accumulators (tests, snapshot checks); either may be NULL.
+ *   rf_env_step_device_records     rf_env_step_device with three more device arrays, each NULL or vouched for by the
+ *                                  runtime exactly as the others: d_final_obs float32[n][W], d_returns float64[n],
+ *                                  d_lengths int32[n], filled by the same hand-over launch (no extra launch).  Refused
+ *                                  when records are off and any of the three is not NULL.  rf_env_step_device is this
+ *                                  function with three NULLs. */
+int rf_env_configure_records(rf_ctx *ctx, int on);
+int rf_env_get_records(rf_ctx *ctx, float *host_final_obs, double *host_returns, int32_t *host_lengths);
+int rf_env_get_record_accumulators(rf_ctx *ctx, double *host_returns, int32_t *host_lengths);
+int rf_env_step_device_records(rf_ctx *ctx, const void *d_actions, int action_dtype, float *d_obs, double *d_rewards,
+                               uint8_t *d_truncated, int32_t *d_n_reset, float *d_final_obs, double *d_returns,
+                               int32_t *d_lengths, void *caller_stream);
 
 #ifdef __cplusplus
 }

@@ -83,6 +83,10 @@ SYMBOLS = (
     "rf_env_step_device",
     "rf_env_reset_device",
     "rf_env_device_status",
+    "rf_env_configure_records",
+    "rf_env_get_records",
+    "rf_env_get_record_accumulators",
+    "rf_env_step_device_records",
     "rf_render_kernel_name",
     "rf_pixels_rendered",
     "rf_allocations_poisoned",
@@ -276,6 +280,10 @@ def load():
     lib.rf_env_step_device.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
     lib.rf_env_reset_device.argtypes = [vp, vp, vp]
     lib.rf_env_device_status.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    lib.rf_env_configure_records.argtypes = [vp, i32]
+    lib.rf_env_get_records.argtypes = [vp, vp, vp, vp]
+    lib.rf_env_get_record_accumulators.argtypes = [vp, vp, vp]
+    lib.rf_env_step_device_records.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.rf_render_kernel_name.restype = ctypes.c_char_p
     lib.rf_render_kernel_name.argtypes = [vp]
     lib.rf_pixels_rendered.restype = ctypes.c_ulonglong
@@ -602,6 +610,39 @@ class Context:
         step, env = ctypes.c_int(-1), ctypes.c_int(-1)
         _check(self._lib.rf_env_device_status(self._h, ctypes.byref(step), ctypes.byref(env)))
         return None if step.value < 0 else (step.value, env.value)
+
+    # --- episode records (rf_env_configure_records ...) ---------------------------------------------------------
+    def env_configure_records(self, on=True):
+        """rf_env_configure_records: the context keeps final observations, episode returns and lengths from now on
+        (after env_configure*, before the first env_reset)."""
+        _check(self._lib.rf_env_configure_records(self._h, 1 if on else 0))
+
+    def env_records(self):
+        """rf_env_get_records: the last step's (final_observation float32[n, W], episode_return float64[n],
+        episode_length int32[n]) as fresh arrays -- rows of environments that did not end are NaN / NaN / 0."""
+        n = self._env_n
+        final_obs = np.empty((n, self._env_obs_width), dtype=np.float32)
+        returns = np.empty(n, dtype=np.float64)
+        lengths = np.empty(n, dtype=np.int32)
+        rc = self._lib.rf_env_get_records(self._h, final_obs.ctypes.data, returns.ctypes.data, lengths.ctypes.data)
+        if rc != 0:
+            _check(rc)
+        return final_obs, returns, lengths
+
+    def env_record_accumulators(self):
+        """rf_env_get_record_accumulators: the running (returns float64[n], lengths int32[n])."""
+        returns = np.empty(self._env_n, dtype=np.float64)
+        lengths = np.empty(self._env_n, dtype=np.int32)
+        _check(self._lib.rf_env_get_record_accumulators(self._h, _ptr(returns), _ptr(lengths)))
+        return returns, lengths
+
+    def env_step_device_records(self, actions_ptr, action_dtype, obs_ptr, rewards_ptr, truncated_ptr, n_reset_ptr,
+                                final_obs_ptr, returns_ptr, lengths_ptr, stream):
+        """rf_env_step_device_records: env_step_device with the episode records to three more device arrays."""
+        rc = self._lib.rf_env_step_device_records(self._h, actions_ptr, action_dtype, obs_ptr, rewards_ptr, truncated_ptr,
+                                                  n_reset_ptr, final_obs_ptr, returns_ptr, lengths_ptr, stream)
+        if rc != 0:
+            _check(rc)
 
     # the int32 calls and their float32 (_jumps) twins: one body each, given the C function and the actions' dtype
     def _env_step(self, function, dtype, actions, pool):

@@ -315,6 +315,11 @@ int env_configure(rf_ctx *ctx, const rf_env_config *cfg, int task, float stop_th
     const int obs_width = observer ? observer->width : 4;
     const EnvIo io(n, (size_t)obs_width);
     const size_t o_io = take(io.bytes);
+    // the episode records' arrays (rf_env_configure_records points EnvState at them; null until then)
+    // (the three outputs as one piece, the float64 array first: one copy fetches them)
+    const size_t rec_bytes = n * 8 + n * (size_t)obs_width * 4 + n * 4;
+    const size_t o_epret = take(n * 8), o_eplen = take(n * 4), o_final = take(rec_bytes);
+    const size_t rec_off[5] = {o_epret, o_eplen, o_final + n * 8, o_final, o_final + n * 8 + n * (size_t)obs_width * 4};
     RF_HIP(dev_malloc(&ctx->env_block, off));
     RF_HIP(hipMemsetAsync(ctx->env_block, 0, off, ctx->stream));
     char *base = (char *)ctx->env_block;
@@ -344,6 +349,16 @@ int env_configure(rf_ctx *ctx, const rf_env_config *cfg, int task, float stop_th
     s.leaf_old = program ? (float *)(base + o_old) : nullptr;
     s.observer = observer ? (const rf_env_observer_program *)(base + o_obsprog) : nullptr;
     s.obs_old = observer ? (float *)(base + o_obsold) : nullptr;
+    s.ep_return = nullptr;
+    s.ep_length = nullptr;
+    s.final_obs = nullptr;
+    s.final_return = nullptr;
+    s.final_length = nullptr;
+    ctx->env_records = false;
+    ctx->env_stepped = false;
+    for (int i = 0; i < 5; ++i)
+        ctx->env_rec_off[i] = rec_off[i];
+    ctx->env_rec_bytes = rec_bytes;
     ctx->env_obs_width = obs_width;
     ctx->env_observer = observer ? *observer : rf_env_observer_program{};
     if (observer) { // (DeltaObserver._old_wrapped_observations starts as NaN; ctx->env_observer outlives the copy)
@@ -534,6 +549,7 @@ void finish_step(rf_ctx *ctx, int k)
 {
     ctx->env_steps += 1;
     ctx->env_step_index += 1;
+    ctx->env_stepped = true;
     ctx->env_scene_len = k > 0 ? k : ctx->env_host.n;
     ctx->env_last_partial = k > 0;
 }
@@ -887,6 +903,92 @@ int ensure_env_graph_dev(rf_ctx *ctx, const EnvLaunch &d)
         ctx->env_graph_dev = nullptr;
         ctx->env_graph_enabled = false;
     }
+    return RF_OK;
+}
+
+// rf_env_step_device / rf_env_step_device_records: the latter's three arrays are NULL for the former
+int env_step_device(rf_ctx *ctx, const void *d_actions, int action_dtype, float *d_obs, double *d_rewards,
+                    uint8_t *d_truncated, int32_t *d_n_reset, float *d_final_obs, double *d_returns, int32_t *d_lengths,
+                    void *caller_stream, const char *fn)
+{
+    RF_REQUIRE(d_actions && d_obs && d_rewards && d_truncated, "%s: NULL argument", fn);
+    RF_REQUIRE(action_dtype == RF_ACTION_I32 || action_dtype == RF_ACTION_I64 || action_dtype == RF_ACTION_F32,
+               "%s: unknown action_dtype %d", fn, action_dtype);
+    RF_REQUIRE(ctx->env_ready, "%s: rf_env_configure first", fn);
+    RF_REQUIRE(ctx->env_init, "%s: the context has no device initializer (rf_env_configure_initializer): the host's "
+               "initializer advances by the number of environments that ended, which only a synchronisation can tell it", fn);
+    RF_REQUIRE(ctx->env_pending < 0, "%s: a two-phase or planned step is open", fn);
+    RF_REQUIRE(!ctx->env_needs_reset, "%s: a step was aborted (rf_env_reset first)", fn);
+    RF_REFUSE_FAULTED(ctx, fn);
+    RF_REQUIRE(ctx->env_records || !(d_final_obs || d_returns || d_lengths),
+               "%s: the context keeps no episode records (rf_env_configure_records)", fn);
+    const int task = ctx->env_cfg.task;
+    const bool index_task = task == rf::kEnvTaskSteps || (task == rf::kEnvTaskComposed && composed_discrete(ctx));
+    RF_REQUIRE(index_task == (action_dtype != RF_ACTION_F32), "%s: the context takes %s actions", fn,
+               index_task ? "RF_ACTION_I32 / RF_ACTION_I64" : "RF_ACTION_F32");
+    const int rule = index_task ? rf::kActionRuleIndex
+                     : (task == rf::kEnvTaskJumps || ctx->env_program.transformer == RF_TRANSFORM_CONTINUOUS_JUMP)
+                         ? rf::kActionRuleJump
+                         : rf::kActionRuleFinite;
+    const int n_actions = task == rf::kEnvTaskComposed ? ctx->env_program.n_actions : ctx->env_host.n_actions;
+    const EnvLaunch d(ctx, false);
+    const size_t n = (size_t)d.n, action_bytes = action_dtype == RF_ACTION_I64 ? 8 : 4;
+    int rc = check_device_array(ctx, d_actions, n * action_bytes, action_bytes, "d_actions", fn);
+    if (rc == RF_OK)
+        rc = check_device_array(ctx, d_obs, env_obs_bytes(ctx), 4, "d_obs", fn);
+    if (rc == RF_OK)
+        rc = check_device_array(ctx, d_rewards, n * 8, 8, "d_rewards", fn);
+    if (rc == RF_OK)
+        rc = check_device_array(ctx, d_truncated, n, 1, "d_truncated", fn);
+    if (rc == RF_OK && d_n_reset)
+        rc = check_device_array(ctx, d_n_reset, 4, 4, "d_n_reset", fn);
+    if (rc == RF_OK && d_final_obs)
+        rc = check_device_array(ctx, d_final_obs, env_obs_bytes(ctx), 4, "d_final_obs", fn);
+    if (rc == RF_OK && d_returns)
+        rc = check_device_array(ctx, d_returns, n * 8, 8, "d_returns", fn);
+    if (rc == RF_OK && d_lengths)
+        rc = check_device_array(ctx, d_lengths, n * 4, 4, "d_lengths", fn);
+    const hipStream_t caller = (hipStream_t)caller_stream;
+    if (rc == RF_OK)
+        rc = refuse_capturing(caller, fn);
+    if (rc != RF_OK)
+        return rc;
+    // the schedule: as rf_env_step's enqueued-in-one-go branch at any size (the count-sized one needs a round trip)
+    const bool fused = fused_step_possible(ctx);
+    // ... replayed where rf_env_step replays: not at the sizes whose host form takes the count-sized schedule
+    bool graph = ctx->env_graph_enabled && !ctx->timing && ctx->env_steps >= 1 && (fused || env_one_sync(ctx));
+    ctx->env_needs_reset = true; // until the whole step is enqueued (a HIP failure below returns early)
+    if (int rc2 = wait_for_caller(ctx, caller))
+        return rc2;
+    if (graph) { // (captured on the ctx's stream, which holds nothing of this step yet but the wait)
+        if (int rc2 = ensure_env_graph_dev(ctx, d))
+            return rc2;
+        graph = ctx->env_graph_dev != nullptr;
+    }
+    rf::EnvIoState *io = (rf::EnvIoState *)ctx->d_io_state;
+    hipLaunchKernelGGL(rf::env_gather_actions_kernel, d.grid, d.block, 0, ctx->stream, d_actions, action_dtype, rule,
+                       n_actions, d.n, (unsigned)ctx->env_step_index, ctx->d_actions, io);
+    if (graph) {
+        RF_HIP(hipGraphLaunch(ctx->env_graph_dev, ctx->stream));
+    } else if (int rc2 = enqueue_env_step_body(ctx, d)) {
+        return rc2;
+    }
+    const int cells = d.n * ctx->env_obs_width, blocks = (cells + 255) / 256;
+    hipLaunchKernelGGL(rf::env_scatter_results_kernel, dim3(blocks < 1024 ? blocks : 1024), dim3(256), 0, ctx->stream,
+                       (const float *)ctx->env.obs, (const double *)ctx->env.reward, (const uint8_t *)ctx->env.truncated,
+                       (const int *)ctx->env.done_count, d.n, ctx->env_obs_width, d_obs, d_rewards, d_truncated, d_n_reset,
+                       io, (const float *)ctx->env.final_obs, (const double *)ctx->env.final_return,
+                       (const int *)ctx->env.final_length, d_final_obs, d_returns, d_lengths);
+    RF_HIP(hipGetLastError());
+    if (int rc2 = let_caller_wait(ctx, caller))
+        return rc2;
+    ctx->env_needs_reset = false;
+    ctx->env_last_branch = fused ? (graph ? RF_ENV_BRANCH_FUSED_GRAPH : RF_ENV_BRANCH_FUSED)
+                                 : (graph ? RF_ENV_BRANCH_GRAPH : RF_ENV_BRANCH_ONE_SYNC);
+    ctx->env_steps += 1;
+    ctx->env_step_index += 1;
+    ctx->env_stepped = true;
+    ctx->io_unresolved = ctx->io_scene_pending = true; // (finish_step's words wait for somebody to ask)
     return RF_OK;
 }
 
@@ -1270,6 +1372,7 @@ int rf_env_step_end_given(rf_ctx *ctx, const float *host_pool, const double *hos
     ctx->env_needs_reset = false;
     ctx->env_steps += 1; // (the renderer's scene set is not this step's: rf_env_render_states says what it holds)
     ctx->env_step_index += 1;
+    ctx->env_stepped = true;
     return RF_OK;
 }
 int rf_env_step_abort(rf_ctx *ctx)
@@ -1351,76 +1454,90 @@ int rf_env_get_states(rf_ctx *ctx, float *host_states)
 int rf_env_step_device(rf_ctx *ctx, const void *d_actions, int action_dtype, float *d_obs, double *d_rewards,
                        uint8_t *d_truncated, int32_t *d_n_reset, void *caller_stream)
 {
-    const char *fn = "rf_env_step_device";
-    RF_REQUIRE(ctx != nullptr && d_actions && d_obs && d_rewards && d_truncated, "%s: NULL argument", fn);
-    RF_REQUIRE(action_dtype == RF_ACTION_I32 || action_dtype == RF_ACTION_I64 || action_dtype == RF_ACTION_F32,
-               "%s: unknown action_dtype %d", fn, action_dtype);
-    RF_REQUIRE(ctx->env_ready, "%s: rf_env_configure first", fn);
-    RF_REQUIRE(ctx->env_init, "%s: the context has no device initializer (rf_env_configure_initializer): the host's "
-               "initializer advances by the number of environments that ended, which only a synchronisation can tell it", fn);
-    RF_REQUIRE(ctx->env_pending < 0, "%s: a two-phase or planned step is open", fn);
-    RF_REQUIRE(!ctx->env_needs_reset, "%s: a step was aborted (rf_env_reset first)", fn);
-    RF_REFUSE_FAULTED(ctx, fn);
-    const int task = ctx->env_cfg.task;
-    const bool index_task = task == rf::kEnvTaskSteps || (task == rf::kEnvTaskComposed && composed_discrete(ctx));
-    RF_REQUIRE(index_task == (action_dtype != RF_ACTION_F32), "%s: the context takes %s actions", fn,
-               index_task ? "RF_ACTION_I32 / RF_ACTION_I64" : "RF_ACTION_F32");
-    const int rule = index_task ? rf::kActionRuleIndex
-                     : (task == rf::kEnvTaskJumps || ctx->env_program.transformer == RF_TRANSFORM_CONTINUOUS_JUMP)
-                         ? rf::kActionRuleJump
-                         : rf::kActionRuleFinite;
-    const int n_actions = task == rf::kEnvTaskComposed ? ctx->env_program.n_actions : ctx->env_host.n_actions;
+    RF_REQUIRE(ctx != nullptr, "rf_env_step_device: NULL argument");
     RF_HIP(hipSetDevice(ctx->device));
-    const EnvLaunch d(ctx, false);
-    const size_t n = (size_t)d.n, action_bytes = action_dtype == RF_ACTION_I64 ? 8 : 4;
-    int rc = check_device_array(ctx, d_actions, n * action_bytes, action_bytes, "d_actions", fn);
-    if (rc == RF_OK)
-        rc = check_device_array(ctx, d_obs, env_obs_bytes(ctx), 4, "d_obs", fn);
-    if (rc == RF_OK)
-        rc = check_device_array(ctx, d_rewards, n * 8, 8, "d_rewards", fn);
-    if (rc == RF_OK)
-        rc = check_device_array(ctx, d_truncated, n, 1, "d_truncated", fn);
-    if (rc == RF_OK && d_n_reset)
-        rc = check_device_array(ctx, d_n_reset, 4, 4, "d_n_reset", fn);
-    const hipStream_t caller = (hipStream_t)caller_stream;
-    if (rc == RF_OK)
-        rc = refuse_capturing(caller, fn);
-    if (rc != RF_OK)
-        return rc;
-    // the schedule: as rf_env_step's enqueued-in-one-go branch at any size (the count-sized one needs a round trip)
-    const bool fused = fused_step_possible(ctx);
-    // ... replayed where rf_env_step replays: not at the sizes whose host form takes the count-sized schedule
-    bool graph = ctx->env_graph_enabled && !ctx->timing && ctx->env_steps >= 1 && (fused || env_one_sync(ctx));
-    ctx->env_needs_reset = true; // until the whole step is enqueued (a HIP failure below returns early)
-    if (int rc2 = wait_for_caller(ctx, caller))
-        return rc2;
-    if (graph) { // (captured on the ctx's stream, which holds nothing of this step yet but the wait)
-        if (int rc2 = ensure_env_graph_dev(ctx, d))
-            return rc2;
-        graph = ctx->env_graph_dev != nullptr;
+    return env_step_device(ctx, d_actions, action_dtype, d_obs, d_rewards, d_truncated, d_n_reset, nullptr, nullptr, nullptr,
+                           caller_stream, "rf_env_step_device");
+}
+
+int rf_env_step_device_records(rf_ctx *ctx, const void *d_actions, int action_dtype, float *d_obs, double *d_rewards,
+                               uint8_t *d_truncated, int32_t *d_n_reset, float *d_final_obs, double *d_returns,
+                               int32_t *d_lengths, void *caller_stream)
+{
+    RF_REQUIRE(ctx != nullptr, "rf_env_step_device_records: NULL argument");
+    RF_HIP(hipSetDevice(ctx->device));
+    return env_step_device(ctx, d_actions, action_dtype, d_obs, d_rewards, d_truncated, d_n_reset, d_final_obs, d_returns,
+                           d_lengths, caller_stream, "rf_env_step_device_records");
+}
+int rf_env_configure_records(rf_ctx *ctx, int on)
+{
+    const char *fn = "rf_env_configure_records";
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", fn);
+    RF_REQUIRE(ctx->env_ready, "%s: rf_env_configure first", fn);
+    RF_REQUIRE(ctx->env_pending < 0, "%s: a two-phase or planned step is open", fn);
+    RF_REQUIRE(!ctx->env_stepped, "%s: the context has stepped (episode records are chosen before the first reset)", fn);
+    RF_HIP(hipSetDevice(ctx->device));
+    if (on != 0 && ctx->h_records_bytes < ctx->env_rec_bytes) { // (rf_env_get_records' pinned block; before anything changes)
+        RF_HIP(hipStreamSynchronize(ctx->stream));
+        if (ctx->h_records)
+            RF_HIP(hipHostFree(ctx->h_records));
+        ctx->h_records = nullptr;
+        ctx->h_records_bytes = 0;
+        RF_HIP(host_malloc((void **)&ctx->h_records, ctx->env_rec_bytes));
+        ctx->h_records_bytes = ctx->env_rec_bytes;
     }
-    rf::EnvIoState *io = (rf::EnvIoState *)ctx->d_io_state;
-    hipLaunchKernelGGL(rf::env_gather_actions_kernel, d.grid, d.block, 0, ctx->stream, d_actions, action_dtype, rule,
-                       n_actions, d.n, (unsigned)ctx->env_step_index, ctx->d_actions, io);
-    if (graph) {
-        RF_HIP(hipGraphLaunch(ctx->env_graph_dev, ctx->stream));
-    } else if (int rc2 = enqueue_env_step_body(ctx, d)) {
-        return rc2;
+    drop_env_graph(ctx); // (a captured step holds EnvState by value)
+    drop_env_snapshots(ctx); // (their layout is the other setting's)
+    rf::EnvState &s = ctx->env;
+    char *base = (char *)ctx->env_block;
+    const bool records = on != 0;
+    s.ep_return = records ? (double *)(base + ctx->env_rec_off[0]) : nullptr;
+    s.ep_length = records ? (int *)(base + ctx->env_rec_off[1]) : nullptr;
+    s.final_obs = records ? (float *)(base + ctx->env_rec_off[2]) : nullptr;
+    s.final_return = records ? (double *)(base + ctx->env_rec_off[3]) : nullptr;
+    s.final_length = records ? (int *)(base + ctx->env_rec_off[4]) : nullptr;
+    if (records) { // (a context that was reset already starts its episodes' accumulators here)
+        const size_t n = (size_t)ctx->env_host.n;
+        RF_HIP(hipMemsetAsync(s.ep_return, 0, n * 8, ctx->stream));
+        RF_HIP(hipMemsetAsync(s.ep_length, 0, n * 4, ctx->stream));
     }
-    const int cells = d.n * ctx->env_obs_width, blocks = (cells + 255) / 256;
-    hipLaunchKernelGGL(rf::env_scatter_results_kernel, dim3(blocks < 1024 ? blocks : 1024), dim3(256), 0, ctx->stream,
-                       (const float *)ctx->env.obs, (const double *)ctx->env.reward, (const uint8_t *)ctx->env.truncated,
-                       (const int *)ctx->env.done_count, d.n, ctx->env_obs_width, d_obs, d_rewards, d_truncated, d_n_reset,
-                       io);
-    RF_HIP(hipGetLastError());
-    if (int rc2 = let_caller_wait(ctx, caller))
-        return rc2;
-    ctx->env_needs_reset = false;
-    ctx->env_last_branch = fused ? (graph ? RF_ENV_BRANCH_FUSED_GRAPH : RF_ENV_BRANCH_FUSED)
-                                 : (graph ? RF_ENV_BRANCH_GRAPH : RF_ENV_BRANCH_ONE_SYNC);
-    ctx->env_steps += 1;
-    ctx->env_step_index += 1;
-    ctx->io_unresolved = ctx->io_scene_pending = true; // (finish_step's words wait for somebody to ask)
+    ctx->env_records = records;
+    return RF_OK;
+}
+
+int rf_env_get_records(rf_ctx *ctx, float *host_final_obs, double *host_returns, int32_t *host_lengths)
+{
+    const char *fn = "rf_env_get_records";
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", fn);
+    RF_REQUIRE(ctx->env_ready && ctx->env_records, "%s: the context keeps no episode records (rf_env_configure_records)", fn);
+    RF_REQUIRE(ctx->env_pending < 0, "%s: a two-phase or planned step is open", fn);
+    RF_REQUIRE(ctx->env_started && ctx->env_step_index > 0, "%s: no step since the last reset", fn);
+    RF_HIP(hipSetDevice(ctx->device));
+    // one copy of the piece [final_return | final_obs | final_length] into the pinned block, one synchronisation
+    const size_t n = (size_t)ctx->env_host.n, obs_bytes = env_obs_bytes(ctx);
+    RF_HIP(hipMemcpyAsync(ctx->h_records, ctx->env.final_return, ctx->env_rec_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    RF_HIP(hipStreamSynchronize(ctx->stream));
+    if (host_returns)
+        memcpy(host_returns, ctx->h_records, n * 8);
+    if (host_final_obs)
+        memcpy(host_final_obs, ctx->h_records + n * 8, obs_bytes);
+    if (host_lengths)
+        memcpy(host_lengths, ctx->h_records + n * 8 + obs_bytes, n * 4);
+    return RF_OK;
+}
+
+int rf_env_get_record_accumulators(rf_ctx *ctx, double *host_returns, int32_t *host_lengths)
+{
+    const char *fn = "rf_env_get_record_accumulators";
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", fn);
+    RF_REQUIRE(ctx->env_ready && ctx->env_records, "%s: the context keeps no episode records (rf_env_configure_records)", fn);
+    RF_HIP(hipSetDevice(ctx->device));
+    const size_t n = (size_t)ctx->env_host.n;
+    if (host_returns)
+        RF_HIP(hipMemcpyAsync(host_returns, ctx->env.ep_return, n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (host_lengths)
+        RF_HIP(hipMemcpyAsync(host_lengths, ctx->env.ep_length, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    RF_HIP(hipStreamSynchronize(ctx->stream));
     return RF_OK;
 }
 

@@ -73,6 +73,10 @@ struct Layout {
             add(s.obs_old, (size_t)ctx->env_observer.n_old * n * 4);
         if (ctx->env_init)
             add(init_gen(ctx), 4 * sizeof(unsigned long long));
+        if (ctx->env_records) { // (the accumulators decide later records; the records themselves are last-step outputs)
+            add(s.ep_return, n * 8);
+            add(s.ep_length, n * 4);
+        }
         add(ctx->d_states, (size_t)ctx->n_states * sizeof(ulonglong2));
     }
 };
@@ -93,6 +97,7 @@ rf_env_snapshot_header make_header(const rf_ctx *ctx, size_t total)
     h.task = ctx->env_cfg.task;
     h.obs_width = ctx->env_obs_width;
     h.device_initializer = ctx->env_init ? 1 : 0;
+    h.episode_records = ctx->env_records ? 1 : 0;
     h.n_states = ctx->n_states;
     h.config_hash = fnv1a(fnv1a(kFnvBasis, &ctx->env_host, sizeof(ctx->env_host)), &ctx->env_cfg.stop_threshold,
                           sizeof(ctx->env_cfg.stop_threshold));
@@ -128,6 +133,7 @@ int check_header(const rf_env_snapshot_header &got, const rf_env_snapshot_header
     RF_SAME(task, "task");
     RF_SAME(obs_width, "observation width");
     RF_SAME(device_initializer, "device initializer =");
+    RF_SAME(episode_records, "episode records =");
     RF_SAME(n_states, "rf_num_states =");
 #undef RF_SAME
     RF_REQUIRE(got.config_hash == want.config_hash, "%s: the snapshot was taken under another rf_env_config", fn);
@@ -135,7 +141,7 @@ int check_header(const rf_env_snapshot_header &got, const rf_env_snapshot_header
     RF_REQUIRE(got.observer_hash == want.observer_hash, "%s: the snapshot was taken under another observer program", fn);
     RF_REQUIRE(got.initializer_hash == want.initializer_hash,
                "%s: the snapshot was taken under another initializer program (ranges)", fn);
-    RF_REQUIRE(got.total_bytes == want.total_bytes && got.reserved == 0, "%s: the snapshot says %llu bytes, not %llu", fn,
+    RF_REQUIRE(got.total_bytes == want.total_bytes, "%s: the snapshot says %llu bytes, not %llu", fn,
                (unsigned long long)got.total_bytes, (unsigned long long)want.total_bytes);
     RF_REQUIRE(got.scene_len >= 1 && got.scene_len <= want.n && (got.last_partial == 0 || got.last_partial == 1),
                "%s: the snapshot's scene set (%d environments, partial %d) is not one of this configuration", fn,
@@ -261,10 +267,17 @@ int rf_env_restore(rf_ctx *ctx, const void *host_in, uint64_t bytes)
     if (int rc = may_restore(ctx, fn))
         return rc;
     const Layout layout(ctx);
-    RF_REQUIRE(bytes == layout.total, "%s: %llu bytes, but a snapshot of this context has %llu (rf_env_snapshot_size)", fn,
-               (unsigned long long)bytes, (unsigned long long)layout.total);
     const char *in = (const char *)host_in;
     rf_env_snapshot_header head;
+    if (bytes >= sizeof(head)) { // (the two settings' blobs differ in size: name the setting, not the size)
+        memcpy(&head, in, sizeof(head));
+        RF_REQUIRE(head.magic != RF_ENV_SNAPSHOT_MAGIC || head.version != RF_ENV_SNAPSHOT_VERSION ||
+                       head.episode_records == (ctx->env_records ? 1 : 0),
+                   "%s: the snapshot was taken with episode records = %d, the context has %d", fn, head.episode_records,
+                   ctx->env_records ? 1 : 0);
+    }
+    RF_REQUIRE(bytes == layout.total, "%s: %llu bytes, but a snapshot of this context has %llu (rf_env_snapshot_size)", fn,
+               (unsigned long long)bytes, (unsigned long long)layout.total);
     memcpy(&head, in, sizeof(head));
     if (int rc = check_header(head, make_header(ctx, layout.total), fn))
         return rc;

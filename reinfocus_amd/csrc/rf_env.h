@@ -416,7 +416,8 @@ __device__ __forceinline__ void env_post_observed(const EnvConfig &c, const EnvS
 
 // observe -> reward -> done flags (vector_environment.py:128-135); `first` = reset() call
 // focus_values == nullptr: the variance comes from the sums the focus kernel left (env_variance)
-__device__ __forceinline__ void env_post_one(const EnvConfig &c, const EnvState &s, const double *focus_values, int first, int e)
+__device__ __forceinline__ void env_post_step(const EnvConfig &c, const EnvState &s, const double *focus_values, int first,
+                                              int e)
 {
     if (s.observer) {
         env_post_observed(c, s, focus_values, first, e);
@@ -478,6 +479,37 @@ __device__ __forceinline__ void env_post_one(const EnvConfig &c, const EnvState 
         trunc = (s.steps[e] >= c.max_steps) || trunc;
     s.truncated[e] = trunc ? 1 : 0;
     s.done[e] = trunc ? 1 : 0;
+}
+
+// Episode records (rf_env_configure_records) of environment e, once the step's row of observations, s.reward[e] and
+// s.done[e] are written and before env_reset_post_one overwrites the row: the accumulators take the step (one float64
+// addition, in step order), and every step writes all three record arrays -- the row, the return and the length where
+// the episode ended (the accumulators then start over), NaN / NaN / 0 where it did not.  `first` (a reset) only zeroes
+// the accumulators and writes the "not ended" records.  The row is copied by a uniform loop of plain loads and stores
+// at the row's address (W is the same for every lane): the thread re-reads only what it wrote itself, as
+// observe_program does, and no array is indexed at run time in registers.
+__device__ __forceinline__ void env_record_one(const EnvState &s, int first, int e)
+{
+    const int width = s.observer ? as_const(s.observer)->width : 4;
+    const bool ended = !first && s.done[e];
+    const float *row = s.obs + (size_t)e * width;
+    float *out = s.final_obs + (size_t)e * width;
+    for (int j = 0; j < width; ++j)
+        out[j] = ended ? row[j] : __builtin_nanf("");
+    const double total = first ? 0.0 : s.ep_return[e] + s.reward[e];
+    const int length = first ? 0 : s.ep_length[e] + 1;
+    s.final_return[e] = ended ? total : __builtin_nan("");
+    s.final_length[e] = ended ? length : 0;
+    s.ep_return[e] = ended ? 0.0 : total;
+    s.ep_length[e] = ended ? 0 : length;
+}
+
+// env_post_step, then the episode records of a context that keeps them
+__device__ __forceinline__ void env_post_one(const EnvConfig &c, const EnvState &s, const double *focus_values, int first, int e)
+{
+    env_post_step(c, s, focus_values, first, e);
+    if (s.ep_return)
+        env_record_one(s, first, e);
 }
 
 __global__ void env_post_kernel(EnvConfig c, EnvState s, const double *focus_values, int first)

@@ -100,18 +100,29 @@ __global__ void env_gather_actions_kernel(const void *actions, int dtype, int ru
 // The step's results from the context's io block into the caller's arrays, as one launch: a grid-stride copy of
 // observations (n x width floats), rewards, flags and -- thread 0 -- the count of environments that ended, which also
 // goes into the running total the host accounts its pixels from once it asks.  Runs after the step on the same
-// stream, outside the replayed graph: the caller's pointers may differ from call to call.
+// stream, outside the replayed graph: the caller's pointers may differ from call to call.  The episode records
+// (final_obs / final_return / final_length, rf_env_step_device_records) go along in the same launch to whichever of
+// out_final_obs / out_final_return / out_final_length is not null -- kernel arguments: uniform branches.
 __global__ void env_scatter_results_kernel(const float *obs, const double *reward, const uint8_t *truncated,
                                            const int *done_count, int n, int width, float *out_obs, double *out_reward,
-                                           uint8_t *out_truncated, int *out_count, EnvIoState *io)
+                                           uint8_t *out_truncated, int *out_count, EnvIoState *io, const float *final_obs,
+                                           const double *final_return, const int *final_length, float *out_final_obs,
+                                           double *out_final_return, int *out_final_length)
 {
     const int stride = gridDim.x * blockDim.x, first = blockIdx.x * blockDim.x + threadIdx.x;
     const int cells = n * width;
     for (int i = first; i < cells; i += stride)
         out_obs[i] = obs[i];
+    if (out_final_obs)
+        for (int i = first; i < cells; i += stride)
+            out_final_obs[i] = final_obs[i];
     for (int i = first; i < n; i += stride) {
         out_reward[i] = reward[i];
         out_truncated[i] = truncated[i];
+        if (out_final_return)
+            out_final_return[i] = final_return[i];
+        if (out_final_length)
+            out_final_length[i] = final_length[i];
     }
     if (first == 0) {
         const int k = *done_count;

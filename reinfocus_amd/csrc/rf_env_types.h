@@ -96,6 +96,13 @@ struct EnvState {            // all device arrays, length n unless noted
     // rf_env_configure_observed only (null otherwise: the built-in observer of mid / scale / old_wrapped above)
     const rf_env_observer_program *observer; // read like `program`; every value in it is float32 or an index already
     float *obs_old;          // [n_old][n] the DELTA nodes' old values, node-major, NaN until the first reset
+    // rf_env_configure_records only (all five null otherwise: a uniform branch on a kernel argument, as `observer`)
+    double *ep_return;       // [n] state: the rewards of the running episode, added in step order
+    int *ep_length;          // [n] state: its steps
+    float *final_obs;        // [n][W] output of every step: the row of `obs` before the auto-reset overwrote it where
+                             // the environment ended, NaN elsewhere
+    double *final_return;    // [n] output: ep_return where the environment ended, NaN elsewhere
+    int *final_length;       // [n] output: ep_length where it ended, 0 elsewhere
 };
 
 } // namespace rf

@@ -100,6 +100,16 @@ struct rf_ctx {
     int env_last_branch = RF_ENV_BRANCH_NONE; // rf_env_last_step_branch
     bool env_needs_reset = false; // rf_env_step_abort dropped a half-finished step
     bool env_started = false; // rf_env_reset (or a restore) has run since the configuration: there is something to snapshot
+    // rf_env_configure_records: every rf_env_configure* carves the five arrays out of env_block (offsets below) and
+    // leaves them unused; the call points EnvState at them (env_records), and any rf_env_configure* turns it off again
+    bool env_records = false;
+    size_t env_rec_off[5] = {0, 0, 0, 0, 0}; // ep_return, ep_length, final_obs, final_return, final_length
+    // the three record arrays are one piece of env_block -- [final_return | final_obs | final_length], env_rec_bytes
+    // from env_rec_off[3] -- so that rf_env_get_records is one copy into this pinned block and one synchronisation
+    size_t env_rec_bytes = 0;
+    uint8_t *h_records = nullptr;
+    size_t h_records_bytes = 0;
+    bool env_stepped = false; // a whole step of any form has run since the configuration
     // rf_env_snapshot_resident's slots: a device copy laid out as the host blob is (d == null: empty), the header that
     // blob would have had, and the generator's increment at that time (the jump table of env_init_host follows it)
     struct SnapshotSlot {

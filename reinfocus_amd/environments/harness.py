@@ -55,6 +55,49 @@ def jump_actions(actions, num_envs):
     return actions
 
 
+RECORD_KEYS = ("final_observation", "episode_return", "episode_length")
+
+
+class _EpisodeRecords:
+    """Episode records of a host twin (episode_records=True), by the one definition the device shares
+    (include/reinfocus_hip.h, "episode records"): per environment a float64 return and an int32 length that take every
+    step's reward in step order; every step reports, for the environments that ended, the observation row before the
+    auto-reset overwrites it, the return and the length (the accumulators then start over), and NaN / NaN / 0 for the
+    others.  A full reset zeroes the accumulators."""
+
+    def __init__(self, num_envs):
+        self._num_envs = num_envs
+        self.reset()
+
+    def reset(self):
+        self.returns = np.zeros(self._num_envs, dtype=np.float64)
+        self.lengths = np.zeros(self._num_envs, dtype=np.int32)
+
+    def step(self, observations, rewards, done):
+        """The step's info: to be called before `observations[done]` is overwritten."""
+        self.returns += np.asarray(rewards, dtype=np.float64)  # (one numpy.float64 addition per environment and step)
+        self.lengths += 1
+        final_observation = np.full(observations.shape, np.nan, dtype=np.float32)
+        final_observation[done] = observations[done]
+        episode_return = np.full(self._num_envs, np.nan, dtype=np.float64)
+        episode_return[done] = self.returns[done]
+        episode_length = np.zeros(self._num_envs, dtype=np.int32)
+        episode_length[done] = self.lengths[done]
+        self.returns[done] = 0.0
+        self.lengths[done] = 0
+        return {"final_observation": final_observation, "episode_return": episode_return,
+                "episode_length": episode_length}
+
+    def accumulators(self):
+        return self.returns.copy(), self.lengths.copy()
+
+
+def _no_single_records(cls, kwargs):
+    if kwargs.get("episode_records"):
+        raise ValueError(f"{cls.__name__} has no episode records (episode_records=): the single-environment shell never "
+                         "resets itself, so no observation is overwritten; use a vector environment")
+
+
 def _gymnasium_bases():
     """(Env base, VectorEnv base): gymnasium's classes when gymnasium is importable -- the
     reference's environments derive from gymnasium.Env (environments/environment.py:19) and
@@ -341,13 +384,17 @@ class _HostGlue:
     ContinuousJumps share.  Not an environment class by itself."""
 
     metadata = {"render_modes": ["rgb_array"], "render_fps": 4}
+    _records = None  # (an _EpisodeRecords with episode_records=True)
 
     def __init__(self, max_episode_steps=20, num_envs=1, render_mode=None, *, frame_height=300,
                  samples_per_pixel=100, seed=None, device=None, first_state_index=0, host_frames=False,
-                 _diverging_only=False):
+                 _diverging_only=False, episode_records=False):
         """host_frames=True: the literal drop-in route (FastRenderer(host_frames=True): frames come back to the
-        host every render and vision.focus_values uploads them again), identical results."""
+        host every render and vision.focus_values uploads them again), identical results.
+        episode_records=True (opt-in): step()'s info holds "final_observation", "episode_return" and "episode_length"
+        (_EpisodeRecords); episode_accumulators() reads the running ones."""
         super().__init__()
+        self._records = _EpisodeRecords(num_envs) if episode_records else None
         ends = (5.0, 10.0)
         target_radius = 0.25
         max_move = 5.0
@@ -388,9 +435,17 @@ class _HostGlue:
         self._ender.reset(self._state)
         observations = self._observer.reset(self._state, None)
         self._rewarder.reset(self._state, observations)
+        if self._records is not None:
+            self._records.reset()
         if self.render_mode == "rgb_array":
             self._visualizer.reset(self._state, observations)
         return observations, {}
+
+    def episode_accumulators(self):
+        """(returns float64[num_envs], lengths int32[num_envs]) of the running episodes (episode_records=True)."""
+        if self._records is None:
+            raise ValueError(f"{type(self).__name__} was built without episode_records=True")
+        return self._records.accumulators()
 
     def _transform(self, states, actions):
         new_states = states.copy()
@@ -407,6 +462,7 @@ class _HostGlue:
         terminated = self._ender.is_terminated()
         truncated = self._ender.is_truncated()
         done = terminated | truncated
+        info = {} if self._records is None else self._records.step(observations, rewards, done)
         if done.any():
             new_state = self._initializer.initialize(done.sum())
             self._state[done] = new_state
@@ -419,7 +475,7 @@ class _HostGlue:
         if self.render_mode == "rgb_array":
             not_done = ~done
             self._visualizer.step(self._state[not_done], observations[not_done], not_done)
-        return observations, rewards, terminated, truncated, {}
+        return observations, rewards, terminated, truncated, info
 
     def render(self):
         """vector_environment.py:166-176 -> HistoryVisualizer.visualize
@@ -452,6 +508,7 @@ class DiscreteSteps(_HostGlue, _EnvBase):
     environments/environment.py): one env, DivergingEnder only, unbatched returns."""
 
     def __init__(self, render_mode=None, **kwargs):
+        _no_single_records(type(self), kwargs)
         super().__init__(num_envs=1, render_mode=render_mode, _diverging_only=True, **kwargs)
         self.action_space = self.single_action_space
         self.observation_space = self.single_observation_space
@@ -480,6 +537,7 @@ class ContinuousJumps(_HostGlue, _EnvBase):
     OnTargetRewarder, episode_rewarder.py:210-292, :361-429)."""
 
     def __init__(self, render_mode=None, **kwargs):
+        _no_single_records(type(self), kwargs)
         super().__init__(num_envs=1, render_mode=render_mode, _diverging_only=True, **kwargs)
         self._stop_threshold = abs(0.25 / 2.0)
         self.single_action_space = spaces.Box(-1, 1, dtype=np.float32)
@@ -654,9 +712,11 @@ class _DeviceVectorEnv(_VectorEnvBase):
 
     metadata = {"render_modes": ["rgb_array"], "render_fps": 4}
     _JUMPS = False
+    _episode_records = False
 
     def __init__(self, max_episode_steps=20, num_envs=1, render_mode=None, *, frame_height=300,
-                 samples_per_pixel=100, seed=None, device=None, first_state_index=0, device_initializer=False):
+                 samples_per_pixel=100, seed=None, device=None, first_state_index=0, device_initializer=False,
+                 episode_records=False):
         super().__init__()
         assert render_mode is None or render_mode in self.metadata["render_modes"]
         self.render_mode = render_mode
@@ -668,6 +728,7 @@ class _DeviceVectorEnv(_VectorEnvBase):
         self._device_initializer = bool(device_initializer)
         self._initializer = self._task_initializer(seed)
         self._configure_initializer()
+        self._configure_records(episode_records)
         self._action_set = None if self._JUMPS else self._shard.action_set
         _device_spaces(self, self._action_set, num_envs)
         self._visualizer = None
@@ -699,6 +760,27 @@ class _DeviceVectorEnv(_VectorEnvBase):
         except Exception:
             self._ctx.close()
             raise
+
+    def _configure_records(self, episode_records):
+        """episode_records=True (opt-in): the context keeps final observations, episode returns and lengths
+        (rf_env_configure_records; the definition is _EpisodeRecords', the kernels' env_record_one).  step()'s info then
+        holds the three arrays (fresh numpy arrays, fetched after the step), step_tensors()'s the same as torch tensors
+        the environment owns, episode_accumulators() reads the running ones, and a snapshot holds the accumulators."""
+        self._episode_records = bool(episode_records)
+        if not self._episode_records:
+            return
+        try:
+            self._ctx.env_configure_records(True)
+        except Exception:
+            self._ctx.close()
+            raise
+
+    def episode_accumulators(self):
+        """(returns float64[num_envs], lengths int32[num_envs]) of the running episodes, from the device
+        (rf_env_get_record_accumulators).  Synchronises."""
+        if not self._episode_records:
+            raise ValueError(f"{type(self).__name__} was built without episode_records=True")
+        return self._ctx.env_record_accumulators()
 
     def initializer_state(self):
         """(state, inc) of the initializer's PCG64DXSM generator as Python ints: the device's with
@@ -752,7 +834,8 @@ class _DeviceVectorEnv(_VectorEnvBase):
             if used:
                 self._visualizer.reset(state[truncated], observations[truncated], truncated)
             self._visualizer.step(state[~truncated], observations[~truncated], ~truncated)
-        return observations, rewards, np.full(self.num_envs, False), truncated, {}
+        info = dict(zip(RECORD_KEYS, self._ctx.env_records())) if self._episode_records else {}
+        return observations, rewards, np.full(self.num_envs, False), truncated, info
 
     def render(self):
         """vector_environment.py:166-176."""
@@ -780,7 +863,7 @@ class _DeviceVectorEnv(_VectorEnvBase):
         from reinfocus_amd import torch_interop
 
         io = self._tensors = torch_interop.TensorIO(self._ctx, self.num_envs, self._ctx._env_obs_width,
-                                                    self._float_actions(), self._ctx.device)
+                                                    self._float_actions(), self._ctx.device, self._episode_records)
         return io
 
     def reset_tensors(self, *, seed=None):
@@ -799,7 +882,10 @@ class _DeviceVectorEnv(_VectorEnvBase):
         """step() from a torch tensor of actions on the environment's GPU -- contiguous, shape [num_envs] or
         [num_envs, 1], torch.int32 / torch.int64 for index tasks, torch.float32 for float tasks; anything else raises
         TypeError / ValueError before the library is called -- to torch tensors there: (obs float32 [num_envs, W],
-        rewards float64 [num_envs], terminated bool [num_envs] (all False), truncated bool [num_envs], {}).  The step is
+        rewards float64 [num_envs], terminated bool [num_envs] (all False), truncated bool [num_envs], info).  info is
+        {} -- or with episode_records=True "final_observation" (float32 [num_envs, W]), "episode_return" (float64
+        [num_envs]) and "episode_length" (int32 [num_envs]) as tensors the environment owns and the next call overwrites,
+        whatever out= says.  The step is
         ordered after what torch's current stream holds, that stream waits for it, and the host waits for nothing.
 
         Without out= the environment owns ONE set of output tensors and overwrites it in the next call, as vector
@@ -840,7 +926,7 @@ class _DeviceVectorEnv(_VectorEnvBase):
         from reinfocus_amd.environments import snapshot
 
         return snapshot.EnvSnapshot(blob, type(self).__name__, self.num_envs, self._shard.frame_height,
-                                    self._shard.samples_per_pixel, generator)
+                                    self._shard.samples_per_pixel, generator, self._episode_records)
 
     def _host_generators(self):
         """slot -> the host generator's state when that resident slot was filled"""
@@ -996,9 +1082,13 @@ class _ShardedVectorEnv(_VectorEnvBase):
 
     def __init__(self, max_episode_steps=20, num_envs=1, render_mode=None, *, devices=None, frame_height=300,
                  samples_per_pixel=100, seed=None, first_state_index=0, exact=False, numa_pin=True,
-                 device_initializer=False):
+                 device_initializer=False, episode_records=False):
         import concurrent.futures
         from reinfocus_amd import _native
+
+        if episode_records:
+            raise ValueError(f"{type(self).__name__} has no episode records (episode_records=): a sharded environment's "
+                             "step is cut in two halves on several contexts; use a Device* class on one device")
 
         if device_initializer:
             raise ValueError(f"{type(self).__name__} draws its reset states on the host; a sharded environment cannot "
@@ -1283,14 +1373,16 @@ class VectorEnvironment(_VectorEnvBase):
     initial states.  DeviceVectorEnvironment is the same environment with the whole step on the GPU."""
 
     metadata = {"render_modes": ["rgb_array"], "render_fps": 4}
+    _records = None  # (as _HostGlue's)
 
     def __init__(self, ender, initializer, rewarder, transformer, num_envs, ends=(5.0, 10.0), max_focus_move=5.0,
                  render_mode=None, *, frame_height=300, samples_per_pixel=100, device=None, observer=None,
-                 focus_observation_index=1):
+                 focus_observation_index=1, episode_records=False):
         super().__init__()
         assert render_mode is None or render_mode in self.metadata["render_modes"]
         self.render_mode = render_mode
         self.num_envs = num_envs
+        self._records = _EpisodeRecords(num_envs) if episode_records else None  # (as _HostGlue's)
         self._ender = ender
         self._initializer = initializer
         self._rewarder = rewarder
@@ -1323,6 +1415,8 @@ class VectorEnvironment(_VectorEnvBase):
         self._ender.reset(self._state)
         observations = self._observer.reset(self._state, None)
         self._rewarder.reset(self._state, observations)
+        if self._records is not None:
+            self._records.reset()
         if self.render_mode == "rgb_array":
             self._visualizer.reset(self._state, observations)
         return observations, {}
@@ -1337,6 +1431,8 @@ class VectorEnvironment(_VectorEnvBase):
         terminated = self._ender.is_terminated()
         truncated = self._ender.is_truncated()
         done = terminated | truncated
+        rewards = np.asarray(rewards, dtype=np.float64)
+        info = {} if self._records is None else self._records.step(observations, rewards, done)
         if done.any():
             new_state = self._initializer.initialize(done.sum())
             self._state[done] = new_state
@@ -1349,7 +1445,9 @@ class VectorEnvironment(_VectorEnvBase):
         if self.render_mode == "rgb_array":
             not_done = ~done
             self._visualizer.step(self._state[not_done], observations[not_done], not_done)
-        return observations, np.asarray(rewards, dtype=np.float64), terminated, truncated, {}
+        return observations, rewards, terminated, truncated, info
+
+    episode_accumulators = _HostGlue.episode_accumulators
 
     def strategy_state(self):
         """The per-leaf strategy state, laid out as DeviceVectorEnvironment.strategy_state returns it."""
@@ -1398,12 +1496,14 @@ class DeviceVectorEnvironment(_DeviceVectorEnv):
 
     def __init__(self, ender, initializer, rewarder, transformer, num_envs, ends=(5.0, 10.0), max_focus_move=5.0,
                  render_mode=None, *, frame_height=300, samples_per_pixel=100, device=None, first_state_index=0,
-                 devices=None, observer=None, focus_observation_index=1, device_initializer=False):
+                 devices=None, observer=None, focus_observation_index=1, device_initializer=False,
+                 episode_records=False):
         from reinfocus_amd.environments import state_transformer, strategy_program
 
         if devices is not None:
             raise ValueError("DeviceVectorEnvironment runs on one device (device=); a composed environment cannot be "
-                             "sharded over several (devices=)")
+                             "sharded over several (devices=)" +
+                             (", and episode records (episode_records=) are one context's" if episode_records else ""))
         _VectorEnvBase.__init__(self)
         assert render_mode is None or render_mode in self.metadata["render_modes"]
         observer_program = None
@@ -1432,6 +1532,7 @@ class DeviceVectorEnvironment(_DeviceVectorEnv):
         self._initializer = initializer
         self._device_initializer = bool(device_initializer)
         self._configure_initializer()
+        self._configure_records(episode_records)
         self.single_action_space = transformer.single_action_space
         self.action_space = transformer.action_space
         self.single_observation_space = single_observation_space

@@ -17,6 +17,7 @@ import numpy as np
 FORMAT = 1
 _KEYS = {"blob", "meta"}
 _META = {"format", "env_class", "num_envs", "frame_height", "samples_per_pixel", "host_generator"}
+_OPTIONAL = {"episode_records"}  # true when the environment keeps episode records; absent otherwise
 
 
 def generator_to_json(state):
@@ -41,7 +42,8 @@ class EnvSnapshot:
     """blob: uint8[rf_env_snapshot_size]; host_generator: the host initializer's bit_generator.state, or None when the
     environment draws its reset states on the device (the generator is in the blob then)."""
 
-    def __init__(self, blob, env_class, num_envs, frame_height, samples_per_pixel, host_generator=None):
+    def __init__(self, blob, env_class, num_envs, frame_height, samples_per_pixel, host_generator=None,
+                 episode_records=False):
         blob = np.asarray(blob)
         assert blob.dtype == np.uint8 and blob.ndim == 1, f"the blob is uint8[bytes], not {blob.dtype}{blob.shape}"
         self.blob = blob
@@ -50,15 +52,19 @@ class EnvSnapshot:
         self.frame_height = int(frame_height)
         self.samples_per_pixel = int(samples_per_pixel)
         self.host_generator = host_generator
+        self.episode_records = bool(episode_records)  # (the blob holds the episode accumulators)
 
     def describe(self):
         return (f"{self.env_class}(num_envs={self.num_envs}, frame_height={self.frame_height}, "
-                f"samples_per_pixel={self.samples_per_pixel})")
+                f"samples_per_pixel={self.samples_per_pixel}, episode_records={self.episode_records})")
 
     def _meta(self):
-        return {"format": FORMAT, "env_class": self.env_class, "num_envs": self.num_envs,
+        meta = {"format": FORMAT, "env_class": self.env_class, "num_envs": self.num_envs,
                 "frame_height": self.frame_height, "samples_per_pixel": self.samples_per_pixel,
                 "host_generator": generator_to_json(self.host_generator)}
+        if self.episode_records:  # (left out when off: such a file is what it was before the flag existed)
+            meta["episode_records"] = True
+        return meta
 
     def save(self, path):
         """Writes the snapshot to `path` (exactly that name; no suffix is added)."""
@@ -82,7 +88,7 @@ class EnvSnapshot:
             meta = json.loads(str(meta))
         except json.JSONDecodeError as error:
             raise ValueError(f"{path}: the metadata is not JSON ({error})") from None
-        if not isinstance(meta, dict) or set(meta) != _META:
+        if not isinstance(meta, dict) or set(meta) - _OPTIONAL != _META:
             raise ValueError(f"{path}: metadata {sorted(meta) if isinstance(meta, dict) else type(meta).__name__}, "
                              f"expected {sorted(_META)}")
         if meta["format"] != FORMAT:
@@ -91,4 +97,7 @@ class EnvSnapshot:
             generator = generator_from_json(meta["host_generator"])
         except (KeyError, TypeError, ValueError) as error:
             raise ValueError(f"{path}: the host generator's state is malformed ({error!r})") from None
-        return cls(blob, meta["env_class"], meta["num_envs"], meta["frame_height"], meta["samples_per_pixel"], generator)
+        if meta.get("episode_records", True) is not True:
+            raise ValueError(f"{path}: episode_records is {meta['episode_records']!r}, not true or absent")
+        return cls(blob, meta["env_class"], meta["num_envs"], meta["frame_height"], meta["samples_per_pixel"], generator,
+                   "episode_records" in meta)

@@ -74,16 +74,27 @@ class SB3Wrapper(_VecEnvBase):
         self._pending_actions = actions
 
     def step_wait(self):
-        """vector_shim.py:63-93.  The environments reset themselves inside step(), so -- as in the
-        reference -- "terminal_observation" is the observation step() returned for that
-        environment, i.e. already the first one of its next episode."""
+        """vector_shim.py:63-93.  The environments reset themselves inside step(), so "terminal_observation" has one of
+        two meanings.  Without episode records -- as in the reference -- it is the observation step() returned for that
+        environment, i.e. already the first one of its next episode.  With an environment built with
+        episode_records=True (its info holds "final_observation", "episode_return" and "episode_length") it is the last
+        observation of the episode that ended, the row the auto-reset overwrote -- what a learner bootstraps a truncated
+        episode from --, and the environments that ended also get "episode": {"r": return, "l": length}, which
+        stable-baselines3 computes rollout/ep_rew_mean from.  The three dense arrays are not copied into the
+        per-environment dicts."""
         assert self._pending_actions is not None
         observations, rewards, terminated, truncated, info = self._env.step(self._pending_actions)
         dones = terminated | truncated
-        per_env_keys = [key for key, value in info.items() if isinstance(value, np.ndarray)]
+        records = all(key in info for key in harness.RECORD_KEYS)
+        per_env_keys = [key for key, value in info.items()
+                        if isinstance(value, np.ndarray) and not (records and key in harness.RECORD_KEYS)]
         infos = [{key: info[key][i] for key in per_env_keys} for i in range(self.num_envs)]
         for i in np.flatnonzero(dones):
-            infos[i]["terminal_observation"] = observations[i]
+            if records:
+                infos[i]["terminal_observation"] = info["final_observation"][i]
+                infos[i]["episode"] = {"r": float(info["episode_return"][i]), "l": int(info["episode_length"][i])}
+            else:
+                infos[i]["terminal_observation"] = observations[i]
         return observations, rewards, dones, infos
 
     def close(self):

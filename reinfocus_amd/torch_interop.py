@@ -56,8 +56,12 @@ class TensorIO:
     tests anything with its env_*_device methods): `num_envs` environments with observations of `obs_width` columns on
     HIP device `device_index`; float_actions: the task takes torch.float32 actions, not torch.int32 / int64 indices."""
 
-    def __init__(self, ctx, num_envs, obs_width, float_actions, device_index):
+    def __init__(self, ctx, num_envs, obs_width, float_actions, device_index, episode_records=False):
+        """episode_records: the context keeps them (rf_env_configure_records) -- step() then goes through
+        rf_env_step_device_records and its info holds the three record tensors, owned like the other outputs."""
         self._ctx = ctx
+        self._records = bool(episode_records)
+        self._owned_records = None
         self._n = int(num_envs)
         self._width = int(obs_width)
         self._float = bool(float_actions)
@@ -123,6 +127,17 @@ class TensorIO:
                            torch.zeros(1, dtype=torch.int32, device=device))
         return self._owned
 
+    def _record_outputs(self):
+        """(final_observation float32 [n, W], episode_return float64 [n], episode_length int32 [n]), made once and
+        overwritten by every step."""
+        if self._owned_records is None:
+            torch = _torch()
+            device = torch.device("cuda", self._index)
+            self._owned_records = (torch.empty((self._n, self._width), dtype=torch.float32, device=device),
+                                   torch.empty(self._n, dtype=torch.float64, device=device),
+                                   torch.empty(self._n, dtype=torch.int32, device=device))
+        return self._owned_records
+
     def _stream(self):
         torch = _torch()
         return torch.cuda.current_stream(torch.device("cuda", self._index)).cuda_stream
@@ -141,10 +156,18 @@ class TensorIO:
         torch = _torch()
         owned = self._outputs()
         obs, rewards, truncated = owned[:3] if out is None else self._checked_out(out)
-        self._ctx.env_step_device(actions.data_ptr(), code, obs.data_ptr(), rewards.data_ptr(), truncated.data_ptr(),
-                                  owned[4].data_ptr(), self._stream())
+        info = {}
+        if self._records:
+            final_obs, returns, lengths = self._record_outputs()
+            self._ctx.env_step_device_records(actions.data_ptr(), code, obs.data_ptr(), rewards.data_ptr(),
+                                              truncated.data_ptr(), owned[4].data_ptr(), final_obs.data_ptr(),
+                                              returns.data_ptr(), lengths.data_ptr(), self._stream())
+            info = {"final_observation": final_obs, "episode_return": returns, "episode_length": lengths}
+        else:
+            self._ctx.env_step_device(actions.data_ptr(), code, obs.data_ptr(), rewards.data_ptr(), truncated.data_ptr(),
+                                      owned[4].data_ptr(), self._stream())
         flags = truncated if truncated.dtype == torch.bool else truncated.view(torch.bool)
-        return obs, rewards, owned[3], flags, {}
+        return obs, rewards, owned[3], flags, info
 
     def fault(self):
         """The synchronising query: None, or (step, env) of the earliest invalid action since the last reset."""
