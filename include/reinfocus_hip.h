@@ -510,7 +510,10 @@ int rf_env_get_initializer_state(rf_ctx *ctx, uint64_t state[2], uint64_t inc[2]
  *    8 rect         float32[n][2]                    18 generator    uint64[4]: state, inc   (device initializer)
  *    9 cam_dyn2     float32[n][9]                    19 ep_return    float64[n]              (episode records)
  *   10 rect2        float32[n][2]                    20 ep_length    int32[n]
- *                                                    21 RNG states   uint64[rf_num_states][2]
+ *                                                    21 view stack   float32[n][V]           (learner view)
+ *                                                    22 view returns float64[n]
+ *                                                    23 view moments float64[3][17]: mean, var, count
+ *                                                    24 RNG states   uint64[rf_num_states][2]
  * (7-12: the scene sets of the last render and the ranks of the environments that ended; 2-6 are the built-in tasks'
  * and the built-in observer's, zero where a composed context does not use them.)  The header also carries the two
  * host-side words of the scene set, rf_env_scene_len and whether that set is the compacted one.  NOT in a snapshot: the frame buffers, the last step's
@@ -521,7 +524,9 @@ int rf_env_get_initializer_state(rf_ctx *ctx, uint64_t state[2], uint64_t inc[2]
  * The header's fingerprint names the configuration the blob belongs to: n, frame height, spp, gray mode, task,
  * observation width, rf_num_states, whether a device initializer is configured, whether episode records are kept
  * (rf_env_configure_records: without them arrays 19 and 20 have zero length and the word is 0, so the blob is what it
- * was before that call existed, byte for byte, and the version stays 1), and 64-bit FNV-1a hashes of the
+ * was before that call existed, byte for byte, and the version stays 1), a hash of the learner view's configuration
+ * (rf_env_configure_view: without a view arrays 21 to 23 have zero length and both view words are 0, so again the blob
+ * is what it was, byte for byte), and 64-bit FNV-1a hashes of the
  * rf_env_config (with the stop threshold of rf_env_configure_jumps), the rf_env_program, the rf_env_observer_program and
  * the initializer's ranges as the library holds them -- not of the generator's words, which are content: a restore
  * brings the increment along.
@@ -562,7 +567,10 @@ typedef struct rf_env_snapshot_header {
     /* host-side words of the scene set */
     int32_t scene_len;           /* rf_env_scene_len */
     int32_t last_partial;        /* 1: that set is the compacted one of an auto-reset */
-    uint8_t zero[152];
+    /* the learner view (rf_env_configure_view; both words were part of `zero`, and are 0 without a view) */
+    uint64_t view_hash;          /* FNV-1a of the rf_env_view_config without `training`; never 0 with a view */
+    int32_t view_training;       /* content, not fingerprint: rf_env_view_set_training's flag, restored with the blob */
+    uint8_t zero[140];
 } rf_env_snapshot_header;
 int rf_env_snapshot_size(rf_ctx *ctx, uint64_t *bytes);
 int rf_env_snapshot(rf_ctx *ctx, void *host_out, uint64_t bytes);
@@ -672,6 +680,80 @@ int rf_env_get_record_accumulators(rf_ctx *ctx, double *host_returns, int32_t *h
 int rf_env_step_device_records(rf_ctx *ctx, const void *d_actions, int action_dtype, float *d_obs, double *d_rewards,
                                uint8_t *d_truncated, int32_t *d_n_reset, float *d_final_obs, double *d_returns,
                                int32_t *d_lengths, void *caller_stream);
+
+/* ---- learner view: VecNormalize followed by VecFrameStack on the device ------------------------------------------------
+ * Every training configuration the reference ships (examples/ppo_*.yml: normalize: true, frame_stack: 5) wraps the
+ * environment in stable-baselines3's VecNormalize and then VecFrameStack.  With a view configured the context computes
+ * what those wrappers hand to the learner, on the step's own outputs, by two kernels (csrc/rf_env_view.h) that follow
+ * the step on the ctx's stream, outside the replayed graphs, which hold none of its pointers.  Off by
+ * default; with it off nothing a caller can observe changes.
+ *
+ * One definition, host twin (harness._LearnerView) and device alike.  n environments, W observation columns (4, or the
+ * observer program's width), k = frame_stack, V = k * W.  All parameters and moments are float64; no FMA contraction.
+ * State: stack float32[n][V] (the newest frame in the last W columns), returns float64[n], and running moments (mean,
+ * var, count) for each of the W columns and for the returns, which start at (0, 1, 1e-4).
+ *   treesum(x[0..n))    x as float64, padded with +0.0 to the next power of two P >= n; y = y[0::2] + y[1::2] until one
+ *                       value is left; that value + (+0.0) (-0.0 becomes +0.0, so further zero padding changes nothing).
+ *   update(moments, x)  N = float64(n); bm = treesum(x) / N; bv = treesum((x - bm) * (x - bm)) / N; delta = bm - mean;
+ *                       tot = count + N; mean' = mean + (delta * N) / tot; m2 = (var * count + bv * N) + (((delta * delta)
+ *                       * count) * N) / tot; var' = m2 / tot; count' = tot  (RunningMeanStd.update_from_moments, left
+ *                       to right).
+ *   normalise(row)      with norm_obs, per column c: float32(clip((float64(row[c]) - mean[c]) / sqrt(var[c] + epsilon),
+ *                       -clip_obs, clip_obs)); without, the row unchanged.
+ * After a reset of any form (a reset never resets the moments): returns = 0; if training and norm_obs, update every
+ * observation column with the reset's observations; o = normalise(obs); stack = 0, then stack[:, -W:] = o.
+ * After a step, given its raw obs (rows of environments that ended are already the first of their next episode),
+ * reward (float64), truncated and -- with episode records -- the raw final_obs:
+ *   1 if training and norm_obs: update every observation column with obs        2 o = normalise(obs)
+ *   3 if training: returns = returns * gamma + reward, then update the return moments with returns
+ *   4 view reward: with norm_reward clip(reward / sqrt(ret_var + epsilon), -clip_reward, clip_reward), else reward
+ *   5 every stack row moves left by W                                            8 stack[:, -W:] = o
+ *   6 with records, where e ended: view_final[e] = concat(stack[e][:V - W], normalise(final_obs[e])), by the moments of
+ *     step 1; NaN elsewhere.  Without records there is no view_final.
+ *   7 where e ended: stack[e] = 0 and returns[e] = 0
+ * This is VecNormalize.step_wait followed by StackedObservations.update, as rl_zoo3 applies them.  ONE DELIBERATE
+ * DIFFERENCE: SB3 takes the batch mean and variance with numpy.mean / numpy.var in the observation's dtype (float32) and
+ * in numpy's own order; the view takes them in float64 with the fixed tree above -- more accurate, and reproducible on
+ * a GPU.  The view observation is `stack`.
+ *
+ *   rf_env_configure_view        cfg != NULL: the context keeps a view from now on; NULL: it stops.  After any
+ *                                rf_env_configure* (each of which turns the view off again, rf_env_configure_records
+ *                                included: ask for records first), before the first rf_env_reset.  Refused
+ *                                (RF_ERR_INVALID, nothing changes): a context without an environment, one that has
+ *                                stepped, an open two-phase or planned step, frame_stack outside 1 to 8, epsilon or a
+ *                                clip that is not finite and positive, gamma outside [0, 1].
+ *   With a view, rf_env_reset, rf_env_reset_device, rf_env_step, rf_env_step_jumps and rf_env_step_device* end by
+ *   enqueueing the view's kernels, on every schedule; what they return stays raw.  The two-phase and planned forms
+ *   (rf_env_step_begin*, _plan*, _run, _end*, rf_env_render_states) are refused while a view is configured.
+ *   rf_env_get_view              the view of the last step or reset: host_obs float32[n][V], host_rewards float64[n]
+ *                                (of a step), host_final float32[n][V] (of a step; refused without episode records).
+ *                                Each may be NULL.  Synchronous: one copy into one pinned block.
+ *   rf_env_view_get_statistics   mean / var / count, float64[W + 1] each, the returns last (what VecNormalize.save
+ *   rf_env_view_set_statistics   keeps); each pointer may be NULL.  Synchronous.
+ *   rf_env_view_set_training     VecNormalize.training: 0 freezes the moments and the returns.
+ *   rf_env_view_get_state        stack float32[n][V] and returns float64[n] (tests); either may be NULL.
+ *   rf_env_step_device_view      rf_env_step_device_records with d_view_obs float32[n][V], d_view_rewards float64[n] and
+ *                                d_view_final float32[n][V], each NULL or vouched for by the runtime exactly as the
+ *                                others and filled by the view's own launch, without a host synchronisation.
+ *                                d_view_final is refused without records; all three without a view.
+ *   rf_env_reset_device_view     rf_env_reset_device with the view observation to d_view_obs (or NULL). */
+typedef struct rf_env_view_config {
+    int32_t frame_stack;            /* 1 to 8 */
+    int32_t norm_obs, norm_reward;  /* 0 / 1 */
+    int32_t training;               /* 0 / 1; the only one rf_env_view_set_training changes later */
+    double gamma, epsilon, clip_obs, clip_reward; /* SB3: 0.99, 1e-8, 10, 10 */
+} rf_env_view_config;
+int rf_env_configure_view(rf_ctx *ctx, const rf_env_view_config *cfg);
+int rf_env_get_view(rf_ctx *ctx, float *host_obs, double *host_rewards, float *host_final);
+int rf_env_view_get_statistics(rf_ctx *ctx, double *mean, double *var, double *count);
+int rf_env_view_set_statistics(rf_ctx *ctx, const double *mean, const double *var, const double *count);
+int rf_env_view_set_training(rf_ctx *ctx, int training);
+int rf_env_view_get_state(rf_ctx *ctx, float *host_stack, double *host_returns);
+int rf_env_step_device_view(rf_ctx *ctx, const void *d_actions, int action_dtype, float *d_obs, double *d_rewards,
+                            uint8_t *d_truncated, int32_t *d_n_reset, float *d_final_obs, double *d_returns,
+                            int32_t *d_lengths, float *d_view_obs, double *d_view_rewards, float *d_view_final,
+                            void *caller_stream);
+int rf_env_reset_device_view(rf_ctx *ctx, float *d_obs, float *d_view_obs, void *caller_stream);
 
 #ifdef __cplusplus
 }

@@ -87,6 +87,14 @@ SYMBOLS = (
     "rf_env_get_records",
     "rf_env_get_record_accumulators",
     "rf_env_step_device_records",
+    "rf_env_configure_view",
+    "rf_env_get_view",
+    "rf_env_view_get_statistics",
+    "rf_env_view_set_statistics",
+    "rf_env_view_set_training",
+    "rf_env_view_get_state",
+    "rf_env_step_device_view",
+    "rf_env_reset_device_view",
     "rf_render_kernel_name",
     "rf_pixels_rendered",
     "rf_allocations_poisoned",
@@ -197,6 +205,14 @@ class EnvInitializerProgram(ctypes.Structure):
                 ("inc", ctypes.c_uint64 * 2)]
 
 
+class EnvViewConfig(ctypes.Structure):
+    """rf_env_view_config (include/reinfocus_hip.h, "learner view"): VecNormalize + VecFrameStack on the device."""
+
+    _fields_ = [("frame_stack", ctypes.c_int32), ("norm_obs", ctypes.c_int32), ("norm_reward", ctypes.c_int32),
+                ("training", ctypes.c_int32), ("gamma", ctypes.c_double), ("epsilon", ctypes.c_double),
+                ("clip_obs", ctypes.c_double), ("clip_reward", ctypes.c_double)]
+
+
 def words128(value):
     """(low word, high word) of a 128-bit integer, as the library takes a PCG64DXSM state or increment."""
     assert 0 <= value < 1 << 128, f"{value!r} is not a 128-bit integer"
@@ -284,6 +300,14 @@ def load():
     lib.rf_env_get_records.argtypes = [vp, vp, vp, vp]
     lib.rf_env_get_record_accumulators.argtypes = [vp, vp, vp]
     lib.rf_env_step_device_records.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.rf_env_configure_view.argtypes = [vp, ctypes.POINTER(EnvViewConfig)]
+    lib.rf_env_get_view.argtypes = [vp, vp, vp, vp]
+    lib.rf_env_view_get_statistics.argtypes = [vp, vp, vp, vp]
+    lib.rf_env_view_set_statistics.argtypes = [vp, vp, vp, vp]
+    lib.rf_env_view_set_training.argtypes = [vp, i32]
+    lib.rf_env_view_get_state.argtypes = [vp, vp, vp]
+    lib.rf_env_step_device_view.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.rf_env_reset_device_view.argtypes = [vp, vp, vp, vp]
     lib.rf_render_kernel_name.restype = ctypes.c_char_p
     lib.rf_render_kernel_name.argtypes = [vp]
     lib.rf_pixels_rendered.restype = ctypes.c_ulonglong
@@ -643,6 +667,66 @@ class Context:
                                                   n_reset_ptr, final_obs_ptr, returns_ptr, lengths_ptr, stream)
         if rc != 0:
             _check(rc)
+
+    # --- learner view (rf_env_configure_view ...) ------------------------------------------------------------------
+    _env_view_stack = 0  # frame_stack of the configured learner view (0: none)
+
+    def env_configure_view(self, config):
+        """rf_env_configure_view: an EnvViewConfig -- the context keeps a learner view from now on (after env_configure*
+        and env_configure_records, before the first env_reset) --, or None: it stops."""
+        _check(self._lib.rf_env_configure_view(self._h, None if config is None else ctypes.byref(config)))
+        self._env_view_stack = 0 if config is None else int(config.frame_stack)
+
+    def env_view(self, rewards=True, final=False):
+        """rf_env_get_view: the view of the last step or reset as fresh arrays -- (obs float32[n, V], rewards float64[n]
+        or None, view_final float32[n, V] or None)."""
+        n, cells = self._env_n, self._env_obs_width * self._env_view_stack
+        obs = np.empty((n, cells), dtype=np.float32)
+        view_rewards = np.empty(n, dtype=np.float64) if rewards else None
+        view_final = np.empty((n, cells), dtype=np.float32) if final else None
+        rc = self._lib.rf_env_get_view(self._h, obs.ctypes.data, view_rewards.ctypes.data if rewards else None,
+                                       view_final.ctypes.data if final else None)
+        if rc != 0:
+            _check(rc)
+        return obs, view_rewards, view_final
+
+    def env_view_statistics(self):
+        """rf_env_view_get_statistics: (mean, var, count), float64[W + 1] each, the returns last."""
+        arrays = [np.empty(self._env_obs_width + 1, dtype=np.float64) for _ in range(3)]
+        _check(self._lib.rf_env_view_get_statistics(self._h, *[_ptr(a) for a in arrays]))
+        return tuple(arrays)
+
+    def env_view_set_statistics(self, mean, var, count):
+        """rf_env_view_set_statistics: float64[W + 1] each, the returns last."""
+        arrays = [np.ascontiguousarray(a, dtype=np.float64) for a in (mean, var, count)]
+        for a in arrays:
+            assert a.shape == (self._env_obs_width + 1,), f"statistics of shape {a.shape}, not ({self._env_obs_width + 1},)"
+        _check(self._lib.rf_env_view_set_statistics(self._h, *[_ptr(a) for a in arrays]))
+
+    def env_view_set_training(self, training):
+        """rf_env_view_set_training: False freezes the moments and the returns."""
+        _check(self._lib.rf_env_view_set_training(self._h, 1 if training else 0))
+
+    def env_view_state(self):
+        """rf_env_view_get_state: (stack float32[n, V], returns float64[n])."""
+        stack = np.empty((self._env_n, self._env_obs_width * self._env_view_stack), dtype=np.float32)
+        returns = np.empty(self._env_n, dtype=np.float64)
+        _check(self._lib.rf_env_view_get_state(self._h, _ptr(stack), _ptr(returns)))
+        return stack, returns
+
+    def env_step_device_view(self, actions_ptr, action_dtype, obs_ptr, rewards_ptr, truncated_ptr, n_reset_ptr,
+                             final_obs_ptr, returns_ptr, lengths_ptr, view_obs_ptr, view_rewards_ptr, view_final_ptr,
+                             stream):
+        """rf_env_step_device_view: env_step_device_records with the learner view to three more device arrays."""
+        rc = self._lib.rf_env_step_device_view(self._h, actions_ptr, action_dtype, obs_ptr, rewards_ptr, truncated_ptr,
+                                               n_reset_ptr, final_obs_ptr, returns_ptr, lengths_ptr, view_obs_ptr,
+                                               view_rewards_ptr, view_final_ptr, stream)
+        if rc != 0:
+            _check(rc)
+
+    def env_reset_device_view(self, obs_ptr, view_obs_ptr, stream):
+        """rf_env_reset_device_view: env_reset_device with the view observation to a device array.  Only enqueues."""
+        _check(self._lib.rf_env_reset_device_view(self._h, obs_ptr, view_obs_ptr, stream))
 
     # the int32 calls and their float32 (_jumps) twins: one body each, given the C function and the actions' dtype
     def _env_step(self, function, dtype, actions, pool):

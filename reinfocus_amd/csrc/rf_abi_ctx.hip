@@ -331,6 +331,8 @@ int rf_destroy(rf_ctx *ctx)
     if (ctx->d_io_state) (void)hipFree(ctx->d_io_state);
     if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
     if (ctx->h_records) (void)hipHostFree(ctx->h_records);
+    if (ctx->h_view) (void)hipHostFree(ctx->h_view);
+    if (ctx->view_block) (void)hipFree(ctx->view_block);
     if (ctx->env_block) (void)hipFree(ctx->env_block);
     if (ctx->d_init) (void)hipFree(ctx->d_init);
     rfh::drop_env_snapshots(ctx);

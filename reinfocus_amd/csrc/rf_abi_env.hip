@@ -9,6 +9,7 @@
 #include "rf_env.h"
 #include "rf_env_init.h"
 #include "rf_env_io.h"
+#include "rf_env_view.h"
 
 using namespace rfh;
 
@@ -44,6 +45,57 @@ bool fused_step_possible(const rf_ctx *ctx)
 {
     return ctx->env_fused && ctx->env_axis;
 }
+
+// ---- the learner view (rf_env_configure_view; kernels in rf_env_view.h) ------------------------------------------------
+// Turns the view off and frees its allocation (any rf_env_configure*; the caller has synchronised the stream or does so
+// here).
+int drop_view(rf_ctx *ctx)
+{
+    ctx->env_view = false;
+    ctx->view_after_step = false;
+    if (ctx->view_block) {
+        RF_HIP(hipStreamSynchronize(ctx->stream));
+        RF_HIP(hipFree(ctx->view_block));
+        ctx->view_block = nullptr;
+    }
+    ctx->view_reward = ctx->view_returns = nullptr;
+    ctx->view_stack = ctx->view_final = nullptr;
+    ctx->view_moments = nullptr;
+    return RF_OK;
+}
+
+// The view's two kernels, after a step's body or (reset) a reset's, on the ctx's stream and outside any replayed graph:
+// env_view_moments_kernel while training -- one block per observation column with norm_obs, one more for the returns in
+// a step --, then env_view_apply_kernel.  out_*: the caller's device arrays of rf_env_step_device_view /
+// rf_env_reset_device_view, or null.
+int enqueue_view(rf_ctx *ctx, bool reset, float *out_obs, double *out_reward, float *out_final)
+{
+    const rf::EnvViewConfig &c = ctx->view_cfg;
+    const int obs_blocks = c.norm_obs ? c.width : 0, blocks = obs_blocks + (reset ? 0 : 1);
+    if (ctx->view_training && blocks > 0) {
+        long long p = 1; // the next power of two >= n; a thread owns p / 1024 leaves (at least one)
+        while (p < c.n)
+            p <<= 1;
+        const int leaves = p > rf::kViewBlock ? (int)(p / rf::kViewBlock) : 1;
+        hipLaunchKernelGGL(rf::env_view_moments_kernel, dim3(blocks), dim3(rf::kViewBlock), 0, ctx->stream, c, obs_blocks,
+                           leaves, (const float *)ctx->env.obs, (const double *)ctx->env.reward, ctx->view_returns,
+                           ctx->view_moments);
+    }
+    const int cells = c.n * c.width;
+    hipLaunchKernelGGL(rf::env_view_apply_kernel, dim3((cells + 255) / 256), dim3(256), 0, ctx->stream, c, reset ? 1 : 0,
+                       (const float *)ctx->env.obs, (const double *)ctx->env.reward, (const uint8_t *)ctx->env.truncated,
+                       (const float *)(ctx->view_final ? ctx->env.final_obs : nullptr),
+                       (const rf::EnvViewMoments *)ctx->view_moments, ctx->view_stack, ctx->view_returns, ctx->view_reward,
+                       ctx->view_final, out_obs, out_reward, out_final);
+    RF_HIP(hipGetLastError());
+    ctx->view_after_step = !reset;
+    return RF_OK;
+}
+
+// The two-phase and planned forms leave a step half done between calls; the view follows whole steps only.
+#define RF_REFUSE_VIEW(ctx, fn)                                                                                    \
+    RF_REQUIRE(!((ctx)->env_ready && (ctx)->env_view),                                                             \
+               "%s: the context has a learner view (rf_env_configure_view): only whole steps", fn)
 
 // The actions of one step, checked on the host before anything is enqueued (a refused step changes no state).  The
 // int32 form (DiscreteSteps-v0, the composed discrete transformers) takes indices into the action set; the float32 form
@@ -292,6 +344,8 @@ int env_configure(rf_ctx *ctx, const rf_env_config *cfg, int task, float stop_th
         ctx->env_block = nullptr;
     }
     drop_env_snapshots(ctx); // (they belong to the configuration that ends here)
+    if (int rc = drop_view(ctx))
+        return rc;
     ctx->env_ready = false;
     ctx->env_started = false;
     ctx->env_init = false; // (rf_env_configure_initializer comes after the environment's configuration)
@@ -782,6 +836,12 @@ int env_step(rf_ctx *ctx, const T *host_actions, const float *host_pool, float *
         ctx->env_last_branch = RF_ENV_BRANCH_COUNT_SIZED;
     }
     finish_step(ctx, k);
+    if (ctx->env_view) { // (after the step's own synchronisation: rf_env_get_view waits for it)
+        if (int rc = enqueue_view(ctx, false, nullptr, nullptr, nullptr)) {
+            ctx->env_needs_reset = true; // the step ran, its view did not
+            return rc;
+        }
+    }
     if (host_n_reset)
         *host_n_reset = k;
     return RF_OK;
@@ -793,6 +853,7 @@ int env_step_begin_checked(rf_ctx *ctx, const T *host_actions, double *host_rewa
 {
     RF_REQUIRE(ctx != nullptr && host_actions && host_rewards && host_truncated && host_n_reset, "%s: NULL argument", fn);
     RF_REFUSE_DEVICE_INITIALIZER(ctx, fn);
+    RF_REFUSE_VIEW(ctx, fn);
     if (int rc = step_may_start(ctx, host_actions, fn, "the previous step was not finished (rf_env_step_end)"))
         return rc;
     drop_env_graph(ctx);
@@ -810,6 +871,7 @@ int env_step_plan(rf_ctx *ctx, const T *host_actions, int *host_n_reset, const c
 {
     RF_REQUIRE(ctx != nullptr && host_actions && host_n_reset, "%s: NULL argument", fn);
     RF_REFUSE_DEVICE_INITIALIZER(ctx, fn);
+    RF_REFUSE_VIEW(ctx, fn);
     if (int rc = step_may_start(ctx, host_actions, fn, "the previous step was not finished"))
         return rc;
     drop_env_graph(ctx);
@@ -909,7 +971,7 @@ int ensure_env_graph_dev(rf_ctx *ctx, const EnvLaunch &d)
 // rf_env_step_device / rf_env_step_device_records: the latter's three arrays are NULL for the former
 int env_step_device(rf_ctx *ctx, const void *d_actions, int action_dtype, float *d_obs, double *d_rewards,
                     uint8_t *d_truncated, int32_t *d_n_reset, float *d_final_obs, double *d_returns, int32_t *d_lengths,
-                    void *caller_stream, const char *fn)
+                    float *d_view_obs, double *d_view_rewards, float *d_view_final, void *caller_stream, const char *fn)
 {
     RF_REQUIRE(d_actions && d_obs && d_rewards && d_truncated, "%s: NULL argument", fn);
     RF_REQUIRE(action_dtype == RF_ACTION_I32 || action_dtype == RF_ACTION_I64 || action_dtype == RF_ACTION_F32,
@@ -922,6 +984,10 @@ int env_step_device(rf_ctx *ctx, const void *d_actions, int action_dtype, float 
     RF_REFUSE_FAULTED(ctx, fn);
     RF_REQUIRE(ctx->env_records || !(d_final_obs || d_returns || d_lengths),
                "%s: the context keeps no episode records (rf_env_configure_records)", fn);
+    RF_REQUIRE(ctx->env_view || !(d_view_obs || d_view_rewards || d_view_final),
+               "%s: the context has no learner view (rf_env_configure_view)", fn);
+    RF_REQUIRE(ctx->env_records || !d_view_final,
+               "%s: d_view_final needs episode records (rf_env_configure_records before rf_env_configure_view)", fn);
     const int task = ctx->env_cfg.task;
     const bool index_task = task == rf::kEnvTaskSteps || (task == rf::kEnvTaskComposed && composed_discrete(ctx));
     RF_REQUIRE(index_task == (action_dtype != RF_ACTION_F32), "%s: the context takes %s actions", fn,
@@ -948,6 +1014,13 @@ int env_step_device(rf_ctx *ctx, const void *d_actions, int action_dtype, float 
         rc = check_device_array(ctx, d_returns, n * 8, 8, "d_returns", fn);
     if (rc == RF_OK && d_lengths)
         rc = check_device_array(ctx, d_lengths, n * 4, 4, "d_lengths", fn);
+    const size_t view_bytes = ctx->env_view ? env_obs_bytes(ctx) * (size_t)ctx->view_cfg.frame_stack : 0;
+    if (rc == RF_OK && d_view_obs)
+        rc = check_device_array(ctx, d_view_obs, view_bytes, 4, "d_view_obs", fn);
+    if (rc == RF_OK && d_view_rewards)
+        rc = check_device_array(ctx, d_view_rewards, n * 8, 8, "d_view_rewards", fn);
+    if (rc == RF_OK && d_view_final)
+        rc = check_device_array(ctx, d_view_final, view_bytes, 4, "d_view_final", fn);
     const hipStream_t caller = (hipStream_t)caller_stream;
     if (rc == RF_OK)
         rc = refuse_capturing(caller, fn);
@@ -980,6 +1053,10 @@ int env_step_device(rf_ctx *ctx, const void *d_actions, int action_dtype, float 
                        io, (const float *)ctx->env.final_obs, (const double *)ctx->env.final_return,
                        (const int *)ctx->env.final_length, d_final_obs, d_returns, d_lengths);
     RF_HIP(hipGetLastError());
+    if (ctx->env_view) {
+        if (int rc2 = enqueue_view(ctx, false, d_view_obs, d_view_rewards, d_view_final))
+            return rc2;
+    }
     if (int rc2 = let_caller_wait(ctx, caller))
         return rc2;
     ctx->env_needs_reset = false;
@@ -989,6 +1066,55 @@ int env_step_device(rf_ctx *ctx, const void *d_actions, int action_dtype, float 
     ctx->env_step_index += 1;
     ctx->env_stepped = true;
     ctx->io_unresolved = ctx->io_scene_pending = true; // (finish_step's words wait for somebody to ask)
+    return RF_OK;
+}
+
+// rf_env_reset_device / rf_env_reset_device_view: d_view_obs is NULL for the former
+int env_reset_device(rf_ctx *ctx, float *d_obs, float *d_view_obs, void *caller_stream, const char *fn)
+{
+    RF_REQUIRE(d_obs != nullptr, "%s: NULL argument", fn);
+    RF_REQUIRE(ctx->env_ready, "%s: rf_env_configure first", fn);
+    RF_REQUIRE(ctx->env_init, "%s: the context has no device initializer (rf_env_configure_initializer) to draw the "
+               "states from", fn);
+    RF_REQUIRE(ctx->env_view || !d_view_obs, "%s: the context has no learner view (rf_env_configure_view)", fn);
+    const hipStream_t caller = (hipStream_t)caller_stream;
+    if (int rc = check_device_array(ctx, d_obs, env_obs_bytes(ctx), 4, "d_obs", fn))
+        return rc;
+    if (d_view_obs) {
+        if (int rc = check_device_array(ctx, d_view_obs, env_obs_bytes(ctx) * (size_t)ctx->view_cfg.frame_stack, 4,
+                                        "d_view_obs", fn))
+            return rc;
+    }
+    if (int rc = refuse_capturing(caller, fn))
+        return rc;
+    ctx->env_pending = -1;
+    ctx->env_planned = false;
+    ctx->env_needs_reset = true; // until everything is enqueued
+    if (int rc = wait_for_caller(ctx, caller))
+        return rc;
+    if (int rc = clear_fault(ctx))
+        return rc;
+    const EnvLaunch d(ctx, true);
+    launch_draw_pool(ctx, ctx->env.state, d.n); // initializer.initialize(num_envs), as rf_env_reset(ctx, NULL, obs)
+    launch_init_advance(ctx, nullptr, d.n);
+    if (int rc = full_pass(ctx, d, true, nullptr))
+        return rc;
+    const int cells = d.n * ctx->env_obs_width, blocks = (cells + 255) / 256;
+    hipLaunchKernelGGL(rf::env_scatter_obs_kernel, dim3(blocks < 1024 ? blocks : 1024), dim3(256), 0, ctx->stream,
+                       (const float *)ctx->env.obs, cells, d_obs);
+    RF_HIP(hipGetLastError());
+    if (ctx->env_view) {
+        if (int rc = enqueue_view(ctx, true, d_view_obs, nullptr, nullptr))
+            return rc;
+    }
+    if (int rc = let_caller_wait(ctx, caller))
+        return rc;
+    ctx->env_needs_reset = false;
+    ctx->env_step_index = 0;
+    ctx->env_scene_len = d.n; // (known without asking the device; the pixels of earlier device steps stay open)
+    ctx->env_last_partial = false;
+    ctx->io_scene_pending = false;
+    ctx->env_started = true;
     return RF_OK;
 }
 
@@ -1215,6 +1341,8 @@ int rf_env_reset(rf_ctx *ctx, const float *host_states, float *host_obs)
     ctx->env_scene_len = d.n;
     ctx->env_last_partial = false;
     ctx->env_started = true;
+    if (ctx->env_view)
+        return enqueue_view(ctx, true, nullptr, nullptr, nullptr);
     return RF_OK;
 }
 
@@ -1263,6 +1391,7 @@ int rf_env_step_end(rf_ctx *ctx, const float *host_pool, float *host_obs)
 {
     RF_REQUIRE(ctx != nullptr && host_obs != nullptr, "rf_env_step_end: NULL argument");
     RF_REFUSE_DEVICE_INITIALIZER(ctx, "rf_env_step_end");
+    RF_REFUSE_VIEW(ctx, "rf_env_step_end");
     RF_REQUIRE(ctx->env_ready && ctx->env_pending >= 0 && !ctx->env_planned, "rf_env_step_end: rf_env_step_begin first");
     RF_REQUIRE(ctx->env_pending == 0 || host_pool != nullptr, "rf_env_step_end: %d environments ended but host_pool is NULL",
                ctx->env_pending);
@@ -1295,6 +1424,7 @@ int rf_env_step_run(rf_ctx *ctx, const float *host_pool, float *host_obs, double
 {
     RF_REQUIRE(ctx != nullptr && host_obs && host_rewards && host_truncated, "rf_env_step_run: NULL argument");
     RF_REFUSE_DEVICE_INITIALIZER(ctx, "rf_env_step_run");
+    RF_REFUSE_VIEW(ctx, "rf_env_step_run");
     RF_REQUIRE(ctx->env_ready && ctx->env_pending >= 0 && ctx->env_planned, "rf_env_step_run: rf_env_step_plan first");
     RF_REQUIRE(ctx->env_pending == 0 || host_pool != nullptr, "rf_env_step_run: %d environments ended but host_pool is NULL",
                ctx->env_pending);
@@ -1332,6 +1462,7 @@ int rf_env_render_states(rf_ctx *ctx, int k, const float *host_states, double *h
 {
     RF_REQUIRE(ctx != nullptr && host_states != nullptr && host_focus != nullptr, "rf_env_render_states: NULL argument");
     RF_REFUSE_DEVICE_INITIALIZER(ctx, "rf_env_render_states");
+    RF_REFUSE_VIEW(ctx, "rf_env_render_states");
     RF_REQUIRE(ctx->env_ready, "rf_env_render_states: rf_env_configure first");
     const rf_env_config &h = ctx->env_host;
     RF_REQUIRE(k > 0 && k <= h.n, "rf_env_render_states: k=%d outside [1, %d]", k, h.n);
@@ -1359,6 +1490,7 @@ int rf_env_step_end_given(rf_ctx *ctx, const float *host_pool, const double *hos
 {
     RF_REQUIRE(ctx != nullptr && host_obs != nullptr, "rf_env_step_end_given: NULL argument");
     RF_REFUSE_DEVICE_INITIALIZER(ctx, "rf_env_step_end_given");
+    RF_REFUSE_VIEW(ctx, "rf_env_step_end_given");
     RF_REQUIRE(ctx->env_ready && ctx->env_pending >= 0 && !ctx->env_planned, "rf_env_step_end_given: rf_env_step_begin first");
     const int k = ctx->env_pending;
     RF_REQUIRE(k == 0 || (host_pool != nullptr && host_focus != nullptr),
@@ -1457,7 +1589,7 @@ int rf_env_step_device(rf_ctx *ctx, const void *d_actions, int action_dtype, flo
     RF_REQUIRE(ctx != nullptr, "rf_env_step_device: NULL argument");
     RF_HIP(hipSetDevice(ctx->device));
     return env_step_device(ctx, d_actions, action_dtype, d_obs, d_rewards, d_truncated, d_n_reset, nullptr, nullptr, nullptr,
-                           caller_stream, "rf_env_step_device");
+                           nullptr, nullptr, nullptr, caller_stream, "rf_env_step_device");
 }
 
 int rf_env_step_device_records(rf_ctx *ctx, const void *d_actions, int action_dtype, float *d_obs, double *d_rewards,
@@ -1467,8 +1599,20 @@ int rf_env_step_device_records(rf_ctx *ctx, const void *d_actions, int action_dt
     RF_REQUIRE(ctx != nullptr, "rf_env_step_device_records: NULL argument");
     RF_HIP(hipSetDevice(ctx->device));
     return env_step_device(ctx, d_actions, action_dtype, d_obs, d_rewards, d_truncated, d_n_reset, d_final_obs, d_returns,
-                           d_lengths, caller_stream, "rf_env_step_device_records");
+                           d_lengths, nullptr, nullptr, nullptr, caller_stream, "rf_env_step_device_records");
 }
+
+int rf_env_step_device_view(rf_ctx *ctx, const void *d_actions, int action_dtype, float *d_obs, double *d_rewards,
+                            uint8_t *d_truncated, int32_t *d_n_reset, float *d_final_obs, double *d_returns,
+                            int32_t *d_lengths, float *d_view_obs, double *d_view_rewards, float *d_view_final,
+                            void *caller_stream)
+{
+    RF_REQUIRE(ctx != nullptr, "rf_env_step_device_view: NULL argument");
+    RF_HIP(hipSetDevice(ctx->device));
+    return env_step_device(ctx, d_actions, action_dtype, d_obs, d_rewards, d_truncated, d_n_reset, d_final_obs, d_returns,
+                           d_lengths, d_view_obs, d_view_rewards, d_view_final, caller_stream, "rf_env_step_device_view");
+}
+
 int rf_env_configure_records(rf_ctx *ctx, int on)
 {
     const char *fn = "rf_env_configure_records";
@@ -1488,6 +1632,8 @@ int rf_env_configure_records(rf_ctx *ctx, int on)
     }
     drop_env_graph(ctx); // (a captured step holds EnvState by value)
     drop_env_snapshots(ctx); // (their layout is the other setting's)
+    if (int rc = drop_view(ctx)) // (a view is configured after the records it reads: view_final exists with them only)
+        return rc;
     rf::EnvState &s = ctx->env;
     char *base = (char *)ctx->env_block;
     const bool records = on != 0;
@@ -1543,41 +1689,178 @@ int rf_env_get_record_accumulators(rf_ctx *ctx, double *host_returns, int32_t *h
 
 int rf_env_reset_device(rf_ctx *ctx, float *d_obs, void *caller_stream)
 {
-    const char *fn = "rf_env_reset_device";
-    RF_REQUIRE(ctx != nullptr && d_obs != nullptr, "%s: NULL argument", fn);
-    RF_REQUIRE(ctx->env_ready, "%s: rf_env_configure first", fn);
-    RF_REQUIRE(ctx->env_init, "%s: the context has no device initializer (rf_env_configure_initializer) to draw the "
-               "states from", fn);
+    RF_REQUIRE(ctx != nullptr, "rf_env_reset_device: NULL argument");
     RF_HIP(hipSetDevice(ctx->device));
-    const hipStream_t caller = (hipStream_t)caller_stream;
-    if (int rc = check_device_array(ctx, d_obs, env_obs_bytes(ctx), 4, "d_obs", fn))
+    return env_reset_device(ctx, d_obs, nullptr, caller_stream, "rf_env_reset_device");
+}
+
+int rf_env_reset_device_view(rf_ctx *ctx, float *d_obs, float *d_view_obs, void *caller_stream)
+{
+    RF_REQUIRE(ctx != nullptr, "rf_env_reset_device_view: NULL argument");
+    RF_HIP(hipSetDevice(ctx->device));
+    return env_reset_device(ctx, d_obs, d_view_obs, caller_stream, "rf_env_reset_device_view");
+}
+
+// ---- the learner view's entry points (include/reinfocus_hip.h, "learner view") -----------------------------------------
+int rf_env_configure_view(rf_ctx *ctx, const rf_env_view_config *cfg)
+{
+    const char *fn = "rf_env_configure_view";
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", fn);
+    RF_REQUIRE(ctx->env_ready, "%s: rf_env_configure first", fn);
+    RF_REQUIRE(ctx->env_pending < 0, "%s: a two-phase or planned step is open", fn);
+    RF_REQUIRE(!ctx->env_stepped, "%s: the context has stepped (a learner view is chosen before the first reset)", fn);
+    if (cfg) {
+        RF_REQUIRE(cfg->frame_stack >= 1 && cfg->frame_stack <= 8, "%s: frame_stack %d outside 1 to 8", fn, cfg->frame_stack);
+        RF_REQUIRE(isfinite(cfg->epsilon) && cfg->epsilon > 0.0, "%s: epsilon %g is not finite and positive", fn, cfg->epsilon);
+        RF_REQUIRE(isfinite(cfg->clip_obs) && cfg->clip_obs > 0.0, "%s: clip_obs %g is not finite and positive", fn,
+                   cfg->clip_obs);
+        RF_REQUIRE(isfinite(cfg->clip_reward) && cfg->clip_reward > 0.0, "%s: clip_reward %g is not finite and positive", fn,
+                   cfg->clip_reward);
+        RF_REQUIRE(cfg->gamma >= 0.0 && cfg->gamma <= 1.0, "%s: gamma %g outside [0, 1]", fn, cfg->gamma); // (false for NaN)
+        RF_REQUIRE(ctx->env_obs_width <= rf::kViewMaxColumns, "%s: %d observation columns (at most %d)", fn,
+                   ctx->env_obs_width, rf::kViewMaxColumns);
+        RF_REQUIRE((long long)ctx->env_host.n * ctx->env_obs_width * cfg->frame_stack < (1ll << 31),
+                   "%s: %d environments x %d columns x %d frames do not fit a 32-bit index", fn, ctx->env_host.n,
+                   ctx->env_obs_width, cfg->frame_stack);
+    }
+    RF_HIP(hipSetDevice(ctx->device));
+    drop_env_snapshots(ctx); // (their layout is the other setting's)
+    if (int rc = drop_view(ctx))
         return rc;
-    if (int rc = refuse_capturing(caller, fn))
-        return rc;
-    ctx->env_pending = -1;
-    ctx->env_planned = false;
-    ctx->env_needs_reset = true; // until everything is enqueued
-    if (int rc = wait_for_caller(ctx, caller))
-        return rc;
-    if (int rc = clear_fault(ctx))
-        return rc;
-    const EnvLaunch d(ctx, true);
-    launch_draw_pool(ctx, ctx->env.state, d.n); // initializer.initialize(num_envs), as rf_env_reset(ctx, NULL, obs)
-    launch_init_advance(ctx, nullptr, d.n);
-    if (int rc = full_pass(ctx, d, true, nullptr))
-        return rc;
-    const int cells = d.n * ctx->env_obs_width, blocks = (cells + 255) / 256;
-    hipLaunchKernelGGL(rf::env_scatter_obs_kernel, dim3(blocks < 1024 ? blocks : 1024), dim3(256), 0, ctx->stream,
-                       (const float *)ctx->env.obs, cells, d_obs);
-    RF_HIP(hipGetLastError());
-    if (int rc = let_caller_wait(ctx, caller))
-        return rc;
-    ctx->env_needs_reset = false;
-    ctx->env_step_index = 0;
-    ctx->env_scene_len = d.n; // (known without asking the device; the pixels of earlier device steps stay open)
-    ctx->env_last_partial = false;
-    ctx->io_scene_pending = false;
-    ctx->env_started = true;
+    if (!cfg)
+        return RF_OK;
+    const size_t n = (size_t)ctx->env_host.n, width = (size_t)ctx->env_obs_width, cells = n * width * (size_t)cfg->frame_stack;
+    const bool records = ctx->env_records;
+    // [view_reward | stack | view_final]: the piece rf_env_get_view copies; then the returns and the moments
+    const size_t out_bytes = n * 8 + cells * 4 + (records ? cells * 4 : 0);
+    const size_t o_returns = (out_bytes + 255) & ~(size_t)255, o_moments = (o_returns + n * 8 + 255) & ~(size_t)255;
+    const size_t bytes = o_moments + sizeof(rf::EnvViewMoments);
+    if (ctx->h_view_bytes < out_bytes) { // (rf_env_get_view's pinned block; before anything changes)
+        RF_HIP(hipStreamSynchronize(ctx->stream));
+        if (ctx->h_view)
+            RF_HIP(hipHostFree(ctx->h_view));
+        ctx->h_view = nullptr;
+        ctx->h_view_bytes = 0;
+        RF_HIP(host_malloc((void **)&ctx->h_view, out_bytes));
+        ctx->h_view_bytes = out_bytes;
+    }
+    RF_HIP(dev_malloc(&ctx->view_block, bytes));
+    RF_HIP(hipMemsetAsync(ctx->view_block, 0, bytes, ctx->stream));
+    char *base = (char *)ctx->view_block;
+    ctx->view_reward = (double *)base;
+    ctx->view_stack = (float *)(base + n * 8);
+    ctx->view_final = records ? (float *)(base + n * 8 + cells * 4) : nullptr;
+    ctx->view_returns = (double *)(base + o_returns);
+    ctx->view_moments = (rf::EnvViewMoments *)(base + o_moments);
+    ctx->view_out_bytes = out_bytes;
+    rf::EnvViewMoments &m = ctx->view_moments_host;
+    for (int i = 0; i < rf::kViewSlots; ++i) { // RunningMeanStd(): mean 0, var 1, count 1e-4 (the slots past W stay so)
+        m.mean[i] = 0.0;
+        m.var[i] = 1.0;
+        m.count[i] = 1e-4;
+    }
+    RF_HIP(hipMemcpyAsync(ctx->view_moments, &m, sizeof(m), hipMemcpyHostToDevice, ctx->stream));
+    RF_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->view_host = *cfg;
+    ctx->view_host.norm_obs = cfg->norm_obs != 0;
+    ctx->view_host.norm_reward = cfg->norm_reward != 0;
+    ctx->view_host.training = cfg->training != 0;
+    ctx->view_cfg = rf::EnvViewConfig{ctx->env_host.n, ctx->env_obs_width, cfg->frame_stack, cfg->norm_obs != 0,
+                                      cfg->norm_reward != 0, cfg->gamma, cfg->epsilon, cfg->clip_obs, cfg->clip_reward};
+    ctx->view_training = cfg->training != 0;
+    ctx->view_after_step = false;
+    ctx->env_view = true;
+    return RF_OK;
+}
+
+int rf_env_get_view(rf_ctx *ctx, float *host_obs, double *host_rewards, float *host_final)
+{
+    const char *fn = "rf_env_get_view";
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", fn);
+    RF_REQUIRE(ctx->env_ready && ctx->env_view, "%s: the context has no learner view (rf_env_configure_view)", fn);
+    RF_REQUIRE(ctx->env_started, "%s: rf_env_reset first", fn);
+    RF_REQUIRE(ctx->view_final || !host_final, "%s: host_final needs episode records (rf_env_configure_records before "
+               "rf_env_configure_view)", fn);
+    RF_REQUIRE(ctx->view_after_step || !(host_rewards || host_final), "%s: no step since the last reset (only host_obs)", fn);
+    RF_HIP(hipSetDevice(ctx->device));
+    // one copy of the piece [view_reward | stack | view_final] into the pinned block, one synchronisation
+    const size_t n = (size_t)ctx->env_host.n, cells_bytes = env_obs_bytes(ctx) * (size_t)ctx->view_cfg.frame_stack;
+    const size_t wanted = host_final ? ctx->view_out_bytes : n * 8 + cells_bytes;
+    RF_HIP(hipMemcpyAsync(ctx->h_view, ctx->view_reward, wanted, hipMemcpyDeviceToHost, ctx->stream));
+    RF_HIP(hipStreamSynchronize(ctx->stream));
+    if (host_rewards)
+        memcpy(host_rewards, ctx->h_view, n * 8);
+    if (host_obs)
+        memcpy(host_obs, ctx->h_view + n * 8, cells_bytes);
+    if (host_final)
+        memcpy(host_final, ctx->h_view + n * 8 + cells_bytes, cells_bytes);
+    return RF_OK;
+}
+
+int rf_env_view_get_statistics(rf_ctx *ctx, double *mean, double *var, double *count)
+{
+    const char *fn = "rf_env_view_get_statistics";
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", fn);
+    RF_REQUIRE(ctx->env_ready && ctx->env_view, "%s: the context has no learner view (rf_env_configure_view)", fn);
+    RF_HIP(hipSetDevice(ctx->device));
+    rf::EnvViewMoments m;
+    RF_HIP(hipMemcpyAsync(&m, ctx->view_moments, sizeof(m), hipMemcpyDeviceToHost, ctx->stream));
+    RF_HIP(hipStreamSynchronize(ctx->stream));
+    const size_t bytes = ((size_t)ctx->env_obs_width + 1) * sizeof(double);
+    if (mean)
+        memcpy(mean, m.mean, bytes);
+    if (var)
+        memcpy(var, m.var, bytes);
+    if (count)
+        memcpy(count, m.count, bytes);
+    return RF_OK;
+}
+
+int rf_env_view_set_statistics(rf_ctx *ctx, const double *mean, const double *var, const double *count)
+{
+    const char *fn = "rf_env_view_set_statistics";
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", fn);
+    RF_REQUIRE(ctx->env_ready && ctx->env_view, "%s: the context has no learner view (rf_env_configure_view)", fn);
+    RF_REQUIRE(ctx->env_pending < 0, "%s: a two-phase or planned step is open", fn);
+    RF_HIP(hipSetDevice(ctx->device));
+    rf::EnvViewMoments &m = ctx->view_moments_host;
+    RF_HIP(hipMemcpyAsync(&m, ctx->view_moments, sizeof(m), hipMemcpyDeviceToHost, ctx->stream));
+    RF_HIP(hipStreamSynchronize(ctx->stream));
+    const size_t bytes = ((size_t)ctx->env_obs_width + 1) * sizeof(double);
+    if (mean)
+        memcpy(m.mean, mean, bytes);
+    if (var)
+        memcpy(m.var, var, bytes);
+    if (count)
+        memcpy(m.count, count, bytes);
+    RF_HIP(hipMemcpyAsync(ctx->view_moments, &m, sizeof(m), hipMemcpyHostToDevice, ctx->stream));
+    RF_HIP(hipStreamSynchronize(ctx->stream));
+    return RF_OK;
+}
+
+int rf_env_view_set_training(rf_ctx *ctx, int training)
+{
+    const char *fn = "rf_env_view_set_training";
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", fn);
+    RF_REQUIRE(ctx->env_ready && ctx->env_view, "%s: the context has no learner view (rf_env_configure_view)", fn);
+    RF_HIP(hipSetDevice(ctx->device)); // (nothing is enqueued: the flag decides what the next step launches)
+    ctx->view_training = training != 0;
+    return RF_OK;
+}
+
+int rf_env_view_get_state(rf_ctx *ctx, float *host_stack, double *host_returns)
+{
+    const char *fn = "rf_env_view_get_state";
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", fn);
+    RF_REQUIRE(ctx->env_ready && ctx->env_view, "%s: the context has no learner view (rf_env_configure_view)", fn);
+    RF_HIP(hipSetDevice(ctx->device));
+    const size_t n = (size_t)ctx->env_host.n;
+    if (host_stack)
+        RF_HIP(hipMemcpyAsync(host_stack, ctx->view_stack, env_obs_bytes(ctx) * (size_t)ctx->view_cfg.frame_stack,
+                              hipMemcpyDeviceToHost, ctx->stream));
+    if (host_returns)
+        RF_HIP(hipMemcpyAsync(host_returns, ctx->view_returns, n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    RF_HIP(hipStreamSynchronize(ctx->stream));
     return RF_OK;
 }
 

@@ -77,9 +77,26 @@ struct Layout {
             add(s.ep_return, n * 8);
             add(s.ep_length, n * 4);
         }
+        if (ctx->env_view) { // (the learner view's state; its rewards and view_final are last-step outputs)
+            add(ctx->view_stack, n * (size_t)ctx->env_obs_width * (size_t)ctx->view_cfg.frame_stack * 4);
+            add(ctx->view_returns, n * 8);
+            add(ctx->view_moments, sizeof(rf::EnvViewMoments));
+        }
         add(ctx->d_states, (size_t)ctx->n_states * sizeof(ulonglong2));
     }
 };
+
+// The fingerprint of the learner view's configuration: everything but `training`, which is content.  0: no view.
+uint64_t view_hash(const rf_ctx *ctx)
+{
+    if (!ctx->env_view)
+        return 0;
+    const rf_env_view_config &v = ctx->view_host;
+    const int32_t words[3] = {v.frame_stack, v.norm_obs, v.norm_reward};
+    const double reals[4] = {v.gamma, v.epsilon, v.clip_obs, v.clip_reward};
+    const uint64_t h = fnv1a(fnv1a(kFnvBasis, words, sizeof(words)), reals, sizeof(reals));
+    return h ? h : 1;
+}
 
 // The header a snapshot of the context taken now would have.
 rf_env_snapshot_header make_header(const rf_ctx *ctx, size_t total)
@@ -113,6 +130,8 @@ rf_env_snapshot_header make_header(const rf_ctx *ctx, size_t total)
     }
     h.scene_len = ctx->env_scene_len;
     h.last_partial = ctx->env_last_partial ? 1 : 0;
+    h.view_hash = view_hash(ctx);
+    h.view_training = ctx->env_view && ctx->view_training ? 1 : 0;
     return h;
 }
 
@@ -141,6 +160,11 @@ int check_header(const rf_env_snapshot_header &got, const rf_env_snapshot_header
     RF_REQUIRE(got.observer_hash == want.observer_hash, "%s: the snapshot was taken under another observer program", fn);
     RF_REQUIRE(got.initializer_hash == want.initializer_hash,
                "%s: the snapshot was taken under another initializer program (ranges)", fn);
+    RF_REQUIRE(got.view_hash == want.view_hash, "%s: the snapshot was taken %s, the context has %s", fn,
+               got.view_hash ? "under another learner view configuration" : "without a learner view",
+               want.view_hash ? "one" : "none");
+    RF_REQUIRE(got.view_training == 0 || got.view_training == 1, "%s: the snapshot's view_training word is %d", fn,
+               got.view_training);
     RF_REQUIRE(got.total_bytes == want.total_bytes, "%s: the snapshot says %llu bytes, not %llu", fn,
                (unsigned long long)got.total_bytes, (unsigned long long)want.total_bytes);
     RF_REQUIRE(got.scene_len >= 1 && got.scene_len <= want.n && (got.last_partial == 0 || got.last_partial == 1),
@@ -204,6 +228,10 @@ void restored(rf_ctx *ctx, const rf_env_snapshot_header &head)
     ctx->env_needs_reset = false;
     ctx->env_planned = false;
     ctx->env_started = true;
+    if (ctx->env_view) { // (the training flag is content; the stack holds whatever the snapshotted context last computed)
+        ctx->view_training = head.view_training != 0;
+        ctx->view_after_step = false;
+    }
 }
 
 } // namespace
@@ -275,6 +303,11 @@ int rf_env_restore(rf_ctx *ctx, const void *host_in, uint64_t bytes)
                        head.episode_records == (ctx->env_records ? 1 : 0),
                    "%s: the snapshot was taken with episode records = %d, the context has %d", fn, head.episode_records,
                    ctx->env_records ? 1 : 0);
+        RF_REQUIRE(head.magic != RF_ENV_SNAPSHOT_MAGIC || head.version != RF_ENV_SNAPSHOT_VERSION ||
+                       head.view_hash == view_hash(ctx),
+                   "%s: the snapshot was taken %s, the context has %s", fn,
+                   head.view_hash ? "under another learner view configuration" : "without a learner view",
+                   ctx->env_view ? "one" : "none");
     }
     RF_REQUIRE(bytes == layout.total, "%s: %llu bytes, but a snapshot of this context has %llu (rf_env_snapshot_size)", fn,
                (unsigned long long)bytes, (unsigned long long)layout.total);

@@ -349,6 +349,18 @@ __global__ void env_pre_kernel(EnvConfig c, EnvState s, const int *actions)
         env_pre_one(c, s, actions, e);
 }
 
+// +0.0f as a value the compiler cannot see through.  Where a reset writes numpy.zeros deltas and normalises them,
+// the subtraction is 0 - mid; with the zero known at compile time the gfx950 backend folds it into a negated operand
+// of the division, and numpy's 0 - (+0) = +0 comes out as -0.  Equal as numbers, not as bits -- and the learner
+// view's normalise (rf_env_view.h) divides what it is handed, sign of zero included.  A zero in a register keeps the
+// subtraction a subtraction.
+__device__ __forceinline__ float opaque_zero()
+{
+    float zero = 0.0f;
+    asm volatile("" : "+v"(zero));
+    return zero;
+}
+
 __device__ __forceinline__ float normalize1(const EnvConfig &c, int k, float v)
 {
     return fminf(fmaxf((v - c.mid[k]) / c.scale[k], -1.0f), 1.0f);
@@ -380,7 +392,7 @@ __device__ __forceinline__ void observe_program(const EnvConfig &c, const EnvSta
             float *old = s.obs_old + (size_t)node.old_first * c.n + e;
             for (int j = 0; j < node.width; ++j) {
                 const float wrapped = row[node.first + j];
-                out[j] = first ? 0.0f : wrapped - old[(size_t)j * c.n];
+                out[j] = first ? opaque_zero() : wrapped - old[(size_t)j * c.n];
                 old[(size_t)j * c.n] = wrapped;
             }
             break;
@@ -660,8 +672,9 @@ __device__ __forceinline__ void env_reset_post_one(const EnvConfig &c, const Env
     s.old_wrapped[2 * e + 1] = w1;
     s.obs[4 * e] = normalize1(c, 0, w0);
     s.obs[4 * e + 1] = normalize1(c, 1, w1);
-    s.obs[4 * e + 2] = normalize1(c, 2, 0.0f);
-    s.obs[4 * e + 3] = normalize1(c, 3, 0.0f);
+    const float zero = opaque_zero(); // (DeltaObserver.reset: numpy.zeros)
+    s.obs[4 * e + 2] = normalize1(c, 2, zero);
+    s.obs[4 * e + 3] = normalize1(c, 3, zero);
     if (c.task == kEnvTaskComposed) {
         const float st[2] = {s.state[2 * e], focus};
         composed_rewarders_reset(c, s, env_program(s), st, e);

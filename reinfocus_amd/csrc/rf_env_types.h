@@ -105,4 +105,21 @@ struct EnvState {            // all device arrays, length n unless noted
     int *final_length;       // [n] output: ep_length where it ended, 0 elsewhere
 };
 
+// The learner view (rf_env_configure_view; kernels in rf_env_view.h)
+constexpr int kViewMaxColumns = 16; // RF_ENV_MAX_OBS_COLUMNS
+constexpr int kViewSlots = kViewMaxColumns + 1; // the observation columns 0 .. W-1, then the returns at index W
+
+// Running moments in float64, as the device keeps them (and a snapshot holds them): slot c < W is observation column
+// c, slot W the discounted returns.
+struct EnvViewMoments {
+    double mean[kViewSlots], var[kViewSlots], count[kViewSlots];
+};
+
+// What both kernels of the view take by value.  Everything is uniform: a scalar.
+struct EnvViewConfig {
+    int n, width, frame_stack; // V = frame_stack * width
+    int norm_obs, norm_reward;
+    double gamma, epsilon, clip_obs, clip_reward;
+};
+
 } // namespace rf

@@ -110,6 +110,23 @@ struct rf_ctx {
     uint8_t *h_records = nullptr;
     size_t h_records_bytes = 0;
     bool env_stepped = false; // a whole step of any form has run since the configuration
+    // rf_env_configure_view: the learner view (kernels: rf_env_view.h, launched from rf_abi_env.hip).  One allocation of its own, view_block:
+    // [view_reward f64 n | stack f32 n x V | view_final f32 n x V] -- the piece rf_env_get_view fetches with one copy
+    // into h_view, view_final only with episode records --, then returns f64 n and the moments, 256-byte aligned each.
+    // Any rf_env_configure* (rf_env_configure_records included) turns the view off again.
+    bool env_view = false;
+    bool view_training = false;     // rf_env_view_set_training; part of a snapshot's header
+    bool view_after_step = false;   // the view's outputs are a step's (rewards and view_final mean something), not a reset's
+    rf_env_view_config view_host{}; // as configured (the fingerprint's hash is over this, without `training`)
+    rf::EnvViewConfig view_cfg{};
+    void *view_block = nullptr;
+    double *view_reward = nullptr, *view_returns = nullptr;
+    float *view_stack = nullptr, *view_final = nullptr; // view_final: null without episode records
+    rf::EnvViewMoments *view_moments = nullptr;
+    rf::EnvViewMoments view_moments_host{}; // what an upload reads (outlives the asynchronous copy)
+    size_t view_out_bytes = 0;      // bytes of the piece rf_env_get_view copies
+    uint8_t *h_view = nullptr;
+    size_t h_view_bytes = 0;
     // rf_env_snapshot_resident's slots: a device copy laid out as the host blob is (d == null: empty), the header that
     // blob would have had, and the generator's increment at that time (the jump table of env_init_host follows it)
     struct SnapshotSlot {

@@ -96,6 +96,209 @@ def _no_single_records(cls, kwargs):
     if kwargs.get("episode_records"):
         raise ValueError(f"{cls.__name__} has no episode records (episode_records=): the single-environment shell never "
                          "resets itself, so no observation is overwritten; use a vector environment")
+    if kwargs.get("learner_view") is not None:
+        raise ValueError(f"{cls.__name__} has no learner view (learner_view=): the single-environment shell has no batch "
+                         "to take moments over; use a vector environment")
+
+
+class LearnerView:
+    """What the reference's PPO configurations wrap the environment in (normalize: true, frame_stack: 5) --
+    stable-baselines3's VecNormalize followed by VecFrameStack -- as an opt-in stage of the environment itself
+    (learner_view=LearnerView(frame_stack=5)): reset() / step() / reset_tensors() / step_tensors() then return the
+    running-moment-normalised, clipped observation stacked frame_stack deep (float32 [n, frame_stack * W]) and the reward
+    divided by the running standard deviation of the discounted return; info holds "raw_observation" and "raw_reward",
+    and with episode_records=True "final_observation" is put through the same two transforms ("raw_final_observation"
+    is the raw row).  The definition is include/reinfocus_hip.h's ("learner view"); defaults are SB3's.  One deliberate
+    difference: the batch moments are taken in float64 by a fixed pairwise tree (treesum), not by numpy.mean / numpy.var
+    in float32."""
+
+    def __init__(self, frame_stack=1, norm_obs=True, norm_reward=True, gamma=0.99, epsilon=1e-8, clip_obs=10.0,
+                 clip_reward=10.0, training=True):
+        self.frame_stack = int(frame_stack)
+        self.norm_obs, self.norm_reward, self.training = bool(norm_obs), bool(norm_reward), bool(training)
+        self.gamma, self.epsilon = float(gamma), float(epsilon)
+        self.clip_obs, self.clip_reward = float(clip_obs), float(clip_reward)
+        if not 1 <= self.frame_stack <= 8:
+            raise ValueError(f"frame_stack {frame_stack!r} outside 1 to 8")
+        for name in ("epsilon", "clip_obs", "clip_reward"):
+            if not (np.isfinite(getattr(self, name)) and getattr(self, name) > 0.0):
+                raise ValueError(f"{name} {getattr(self, name)!r} is not finite and positive")
+        if not 0.0 <= self.gamma <= 1.0:
+            raise ValueError(f"gamma {gamma!r} outside [0, 1]")
+
+    def describe(self):
+        """The configuration without `training` (which may change later), as snapshots compare it."""
+        return (f"LearnerView(frame_stack={self.frame_stack}, norm_obs={self.norm_obs}, norm_reward={self.norm_reward}, "
+                f"gamma={self.gamma!r}, epsilon={self.epsilon!r}, clip_obs={self.clip_obs!r}, "
+                f"clip_reward={self.clip_reward!r})")
+
+    def spaces(self, single_observation_space, num_envs):
+        """(single_observation_space, observation_space) of the view: the bounds are +-clip_obs with norm_obs, else the
+        raw ones, repeated frame_stack times."""
+        low, high = single_observation_space.low, single_observation_space.high
+        if self.norm_obs:
+            low, high = np.full_like(low, -self.clip_obs), np.full_like(high, self.clip_obs)
+        single = spaces.Box(np.tile(low, self.frame_stack).astype(np.float32),
+                            np.tile(high, self.frame_stack).astype(np.float32), dtype=np.float32)
+        return single, spaces.batch_space(single, num_envs)
+
+
+def _checked_view(learner_view):
+    if learner_view is not None and not isinstance(learner_view, LearnerView):
+        raise TypeError(f"learner_view must be a harness.LearnerView or None, not {type(learner_view).__name__}")
+    return learner_view
+
+
+def treesum(x):
+    """The learner view's sum of x[0..n): x as float64, padded with +0.0 to the next power of two, adjacent pairs added
+    until one value is left, and that value + (+0.0) (which turns -0.0 into +0.0, so that any further zero padding gives
+    the same bits).  The order is part of the contract: the device evaluates exactly this tree."""
+    y = np.asarray(x, dtype=np.float64).ravel()
+    size = 1
+    while size < y.size:
+        size *= 2
+    y = np.concatenate([y, np.zeros(size - y.size, dtype=np.float64)])
+    while y.size > 1:
+        y = y[0::2] + y[1::2]
+    return y[0] + np.float64(0.0)
+
+
+class _LearnerView:
+    """The learner view of a host twin (learner_view=), by the one definition the device shares
+    (include/reinfocus_hip.h, "learner view"; kernels in csrc/rf_env_view.h), in numpy float64 without contraction."""
+
+    def __init__(self, config, num_envs, width):
+        self.config = config
+        self.training = config.training
+        self._n, self._width, self._cells = num_envs, width, config.frame_stack * width
+        self.mean = np.zeros(width + 1, dtype=np.float64)
+        self.var = np.ones(width + 1, dtype=np.float64)
+        self.count = np.full(width + 1, 1e-4, dtype=np.float64)
+        self.stack = np.zeros((num_envs, self._cells), dtype=np.float32)
+        self.returns = np.zeros(num_envs, dtype=np.float64)
+
+    def _update(self, slot, x):
+        """RunningMeanStd.update_from_moments, left to right, the batch moments by treesum"""
+        N = np.float64(self._n)
+        bm = treesum(x) / N
+        d = np.asarray(x, dtype=np.float64) - bm
+        bv = treesum(d * d) / N
+        mean, var, count = self.mean[slot], self.var[slot], self.count[slot]
+        delta = bm - mean
+        tot = count + N
+        m2 = (var * count + bv * N) + (((delta * delta) * count) * N) / tot
+        self.mean[slot] = mean + (delta * N) / tot
+        self.var[slot] = m2 / tot
+        self.count[slot] = tot
+
+    def _update_observations(self, observations):
+        if self.training and self.config.norm_obs:
+            for column in range(self._width):
+                self._update(column, observations[:, column])
+
+    def _normalise(self, rows):
+        if not self.config.norm_obs:
+            return np.array(rows, dtype=np.float32)
+        width, clip = self._width, self.config.clip_obs
+        z = (rows.astype(np.float64) - self.mean[:width]) / np.sqrt(self.var[:width] + self.config.epsilon)
+        return np.clip(z, -clip, clip).astype(np.float32)
+
+    def reset(self, observations):
+        """The view observation after a reset (a reset never resets the moments)."""
+        with np.errstate(invalid="ignore"):
+            self.returns = np.zeros(self._n, dtype=np.float64)
+            self._update_observations(observations)
+            self.stack = np.zeros((self._n, self._cells), dtype=np.float32)
+            self.stack[:, self._cells - self._width:] = self._normalise(observations)
+        return self.stack.copy()
+
+    def step(self, observations, rewards, done, final_observation=None):
+        """(view observation, view reward, view_final or None) of a step: `observations` as the step returns them (rows
+        of environments that ended are already the first of their next episode), final_observation the raw record
+        (episode_records=True) or None."""
+        width, cells, config = self._width, self._cells, self.config
+        rewards = np.asarray(rewards, dtype=np.float64)
+        with np.errstate(invalid="ignore"):
+            self._update_observations(observations)                                                    # 1
+            newest = self._normalise(observations)                                                     # 2
+            if self.training:                                                                          # 3
+                self.returns = self.returns * config.gamma + rewards
+                self._update(width, self.returns)
+            view_rewards = rewards.copy()                                                              # 4
+            if config.norm_reward:
+                view_rewards = np.clip(rewards / np.sqrt(self.var[width] + config.epsilon), -config.clip_reward,
+                                       config.clip_reward)
+            self.stack[:, :cells - width] = self.stack[:, width:].copy()                               # 5
+            view_final = None
+            if final_observation is not None:                                                          # 6
+                view_final = np.full((self._n, cells), np.nan, dtype=np.float32)
+                view_final[done, :cells - width] = self.stack[done, :cells - width]
+                view_final[done, cells - width:] = self._normalise(final_observation[done])
+            self.stack[done] = 0.0                                                                     # 7
+            self.returns[done] = 0.0
+            self.stack[:, cells - width:] = newest                                                     # 8
+        return self.stack.copy(), view_rewards, view_final
+
+    def statistics(self):
+        return {"mean": self.mean.copy(), "var": self.var.copy(), "count": self.count.copy()}
+
+    def set_statistics(self, mean, var, count):
+        for name, value in (("mean", mean), ("var", var), ("count", count)):
+            value = np.array(value, dtype=np.float64)
+            assert value.shape == (self._width + 1,), f"{name} has shape {value.shape}, not ({self._width + 1},)"
+            setattr(self, name, value)
+
+
+class _ViewedTwin:
+    """What the host twins with learner_view= share: the view around reset() / step() results, and its accessors."""
+
+    _view = None  # (a _LearnerView with learner_view=)
+
+    def _configure_view(self, learner_view):
+        learner_view = _checked_view(learner_view)
+        if learner_view is None:
+            return
+        self._view = _LearnerView(learner_view, self.num_envs, self.single_observation_space.shape[0])
+        self.single_observation_space, self.observation_space = learner_view.spaces(self.single_observation_space,
+                                                                                    self.num_envs)
+
+    def _viewed_reset(self, observations, info):
+        if self._view is None:
+            return observations, info
+        return self._view.reset(observations), {"raw_observation": observations}
+
+    def _viewed_step(self, observations, rewards, terminated, truncated, info):
+        if self._view is None:
+            return observations, rewards, terminated, truncated, info
+        rewards = np.asarray(rewards, dtype=np.float64)
+        view_obs, view_rewards, view_final = self._view.step(observations, rewards, terminated | truncated,
+                                                             info.get("final_observation"))
+        info = dict(info, raw_observation=observations, raw_reward=rewards)
+        if view_final is not None:
+            info["raw_final_observation"] = info["final_observation"]
+            info["final_observation"] = view_final
+        return view_obs, view_rewards, terminated, truncated, info
+
+    def _the_view(self):
+        if self._view is None:
+            raise ValueError(f"{type(self).__name__} was built without learner_view=")
+        return self._view
+
+    def view_statistics(self):
+        """{"mean", "var", "count"}: float64[W + 1] each, the returns last (what VecNormalize.save keeps)."""
+        return self._the_view().statistics()
+
+    def set_view_statistics(self, statistics):
+        self._the_view().set_statistics(statistics["mean"], statistics["var"], statistics["count"])
+
+    def set_view_training(self, training):
+        """VecNormalize.training: False freezes the moments and the returns."""
+        self._the_view().training = bool(training)
+
+    def view_state(self):
+        """(stack float32[n, V], returns float64[n])"""
+        view = self._the_view()
+        return view.stack.copy(), view.returns.copy()
 
 
 def _gymnasium_bases():
@@ -378,7 +581,7 @@ def _jump_spaces(env, num_envs):
     env.action_space = spaces.batch_space(env.single_action_space, num_envs)
 
 
-class _HostGlue:
+class _HostGlue(_ViewedTwin):
     """The DiscreteSteps task with the reference's numpy glue on the host around the GPU
     render + focus (FocusObserver): everything VectorDiscreteSteps, DiscreteSteps and
     ContinuousJumps share.  Not an environment class by itself."""
@@ -388,11 +591,12 @@ class _HostGlue:
 
     def __init__(self, max_episode_steps=20, num_envs=1, render_mode=None, *, frame_height=300,
                  samples_per_pixel=100, seed=None, device=None, first_state_index=0, host_frames=False,
-                 _diverging_only=False, episode_records=False):
+                 _diverging_only=False, episode_records=False, learner_view=None):
         """host_frames=True: the literal drop-in route (FastRenderer(host_frames=True): frames come back to the
         host every render and vision.focus_values uploads them again), identical results.
         episode_records=True (opt-in): step()'s info holds "final_observation", "episode_return" and "episode_length"
-        (_EpisodeRecords); episode_accumulators() reads the running ones."""
+        (_EpisodeRecords); episode_accumulators() reads the running ones.
+        learner_view=LearnerView(...) (opt-in): reset() / step() return the learner view (_LearnerView)."""
         super().__init__()
         self._records = _EpisodeRecords(num_envs) if episode_records else None
         ends = (5.0, 10.0)
@@ -423,6 +627,7 @@ class _HostGlue:
         self.action_space = spaces.batch_space(self.single_action_space, num_envs)
         self.single_observation_space = self._observer.single_observation_space
         self.observation_space = self._observer.observation_space
+        self._configure_view(learner_view)
         self._state = None
 
     # -- vector_environment.py:75-102 ------------------------------------------------------
@@ -439,7 +644,7 @@ class _HostGlue:
             self._records.reset()
         if self.render_mode == "rgb_array":
             self._visualizer.reset(self._state, observations)
-        return observations, {}
+        return self._viewed_reset(observations, {})
 
     def episode_accumulators(self):
         """(returns float64[num_envs], lengths int32[num_envs]) of the running episodes (episode_records=True)."""
@@ -475,7 +680,7 @@ class _HostGlue:
         if self.render_mode == "rgb_array":
             not_done = ~done
             self._visualizer.step(self._state[not_done], observations[not_done], not_done)
-        return observations, rewards, terminated, truncated, info
+        return self._viewed_step(observations, rewards, terminated, truncated, info)
 
     def render(self):
         """vector_environment.py:166-176 -> HistoryVisualizer.visualize
@@ -713,10 +918,11 @@ class _DeviceVectorEnv(_VectorEnvBase):
     metadata = {"render_modes": ["rgb_array"], "render_fps": 4}
     _JUMPS = False
     _episode_records = False
+    _learner_view = None
 
     def __init__(self, max_episode_steps=20, num_envs=1, render_mode=None, *, frame_height=300,
                  samples_per_pixel=100, seed=None, device=None, first_state_index=0, device_initializer=False,
-                 episode_records=False):
+                 episode_records=False, learner_view=None):
         super().__init__()
         assert render_mode is None or render_mode in self.metadata["render_modes"]
         self.render_mode = render_mode
@@ -731,6 +937,7 @@ class _DeviceVectorEnv(_VectorEnvBase):
         self._configure_records(episode_records)
         self._action_set = None if self._JUMPS else self._shard.action_set
         _device_spaces(self, self._action_set, num_envs)
+        self._configure_view(learner_view)
         self._visualizer = None
         if render_mode == "rgb_array":  # custom_environments.py:229-238
             self._visualizer = episode_visualizer.HistoryVisualizer(
@@ -774,6 +981,50 @@ class _DeviceVectorEnv(_VectorEnvBase):
         except Exception:
             self._ctx.close()
             raise
+
+    def _configure_view(self, learner_view):
+        """learner_view=LearnerView(...) (opt-in): the context keeps the learner view (rf_env_configure_view, after the
+        records it reads; the definition is _LearnerView's, the kernels are csrc/rf_env_view.h's).  To be called once the
+        raw spaces are set: they become the view's."""
+        self._learner_view = _checked_view(learner_view)
+        if self._learner_view is None:
+            return
+        from reinfocus_amd import _native
+
+        view = self._learner_view
+        try:
+            self._ctx.env_configure_view(_native.EnvViewConfig(view.frame_stack, view.norm_obs, view.norm_reward,
+                                                               view.training, view.gamma, view.epsilon, view.clip_obs,
+                                                               view.clip_reward))
+        except Exception:
+            self._ctx.close()
+            raise
+        self.single_observation_space, self.observation_space = view.spaces(self.single_observation_space, self.num_envs)
+
+    def _the_view(self):
+        if self._learner_view is None:
+            raise ValueError(f"{type(self).__name__} was built without learner_view=")
+        return self._learner_view
+
+    def view_statistics(self):
+        """{"mean", "var", "count"}: float64[W + 1] each, the returns last, from the device (what VecNormalize.save
+        keeps).  Synchronises."""
+        self._the_view()
+        return dict(zip(("mean", "var", "count"), self._ctx.env_view_statistics()))
+
+    def set_view_statistics(self, statistics):
+        self._the_view()
+        self._ctx.env_view_set_statistics(statistics["mean"], statistics["var"], statistics["count"])
+
+    def set_view_training(self, training):
+        """VecNormalize.training: False freezes the moments and the returns."""
+        self._the_view()
+        self._ctx.env_view_set_training(training)
+
+    def view_state(self):
+        """(stack float32[n, V], returns float64[n]) from the device.  Synchronises."""
+        self._the_view()
+        return self._ctx.env_view_state()
 
     def episode_accumulators(self):
         """(returns float64[num_envs], lengths int32[num_envs]) of the running episodes, from the device
@@ -819,6 +1070,8 @@ class _DeviceVectorEnv(_VectorEnvBase):
         observations = self._ctx.env_reset(initial)
         if self._visualizer is not None:
             self._visualizer.reset(self._state if initial is None else initial, observations)
+        if self._learner_view is not None:
+            return self._ctx.env_view(rewards=False)[0], {"raw_observation": observations}
         return observations, {}
 
     def step(self, actions):
@@ -835,6 +1088,12 @@ class _DeviceVectorEnv(_VectorEnvBase):
                 self._visualizer.reset(state[truncated], observations[truncated], truncated)
             self._visualizer.step(state[~truncated], observations[~truncated], ~truncated)
         info = dict(zip(RECORD_KEYS, self._ctx.env_records())) if self._episode_records else {}
+        if self._learner_view is not None:  # (one more copy and synchronisation, as the records')
+            info.update(raw_observation=observations, raw_reward=rewards)
+            observations, rewards, view_final = self._ctx.env_view(final=self._episode_records)
+            if view_final is not None:
+                info["raw_final_observation"] = info["final_observation"]
+                info["final_observation"] = view_final
         return observations, rewards, np.full(self.num_envs, False), truncated, info
 
     def render(self):
@@ -863,7 +1122,8 @@ class _DeviceVectorEnv(_VectorEnvBase):
         from reinfocus_amd import torch_interop
 
         io = self._tensors = torch_interop.TensorIO(self._ctx, self.num_envs, self._ctx._env_obs_width,
-                                                    self._float_actions(), self._ctx.device, self._episode_records)
+                                                    self._float_actions(), self._ctx.device, self._episode_records,
+                                                    0 if self._learner_view is None else self._learner_view.frame_stack)
         return io
 
     def reset_tensors(self, *, seed=None):
@@ -876,6 +1136,8 @@ class _DeviceVectorEnv(_VectorEnvBase):
 
             self._reseed(seed)
             self._ctx.env_set_initializer_state(*strategy_program.initializer_state(self._initializer))
+        if self._learner_view is not None:  # (the view observation; info holds the raw one, owned alike)
+            return io.reset_viewed()
         return io.reset(), {}
 
     def step_tensors(self, actions, *, out=None):
@@ -1082,9 +1344,14 @@ class _ShardedVectorEnv(_VectorEnvBase):
 
     def __init__(self, max_episode_steps=20, num_envs=1, render_mode=None, *, devices=None, frame_height=300,
                  samples_per_pixel=100, seed=None, first_state_index=0, exact=False, numa_pin=True,
-                 device_initializer=False, episode_records=False):
+                 device_initializer=False, episode_records=False, learner_view=None):
         import concurrent.futures
         from reinfocus_amd import _native
+
+        if learner_view is not None:
+            raise ValueError(f"{type(self).__name__} has no learner view (learner_view=): a sharded environment's step is "
+                             "cut in two halves on several contexts, and the view's moments are one batch's; use a "
+                             "Device* class on one device")
 
         if episode_records:
             raise ValueError(f"{type(self).__name__} has no episode records (episode_records=): a sharded environment's "
@@ -1358,7 +1625,7 @@ def composed_actions(transformer, actions, num_envs, index_range=True):
     return actions
 
 
-class VectorEnvironment(_VectorEnvBase):
+class VectorEnvironment(_ViewedTwin, _VectorEnvBase):
     """A vector environment composed of the reference's strategy objects (vector_environment.py:19-176): an ender, an
     initializer, a rewarder and a transformer from environments/episode_ender.py, state_initializer.py,
     episode_rewarder.py and state_transformer.py, around the observer both tasks use --
@@ -1377,7 +1644,7 @@ class VectorEnvironment(_VectorEnvBase):
 
     def __init__(self, ender, initializer, rewarder, transformer, num_envs, ends=(5.0, 10.0), max_focus_move=5.0,
                  render_mode=None, *, frame_height=300, samples_per_pixel=100, device=None, observer=None,
-                 focus_observation_index=1, episode_records=False):
+                 focus_observation_index=1, episode_records=False, learner_view=None):
         super().__init__()
         assert render_mode is None or render_mode in self.metadata["render_modes"]
         self.render_mode = render_mode
@@ -1405,6 +1672,7 @@ class VectorEnvironment(_VectorEnvBase):
         self.action_space = transformer.action_space
         self.single_observation_space = self._observer.single_observation_space
         self.observation_space = self._observer.observation_space
+        self._configure_view(learner_view)  # (as _HostGlue's)
         self._state = None
 
     def reset(self, *, seed=None, options=None, state=None):
@@ -1419,7 +1687,7 @@ class VectorEnvironment(_VectorEnvBase):
             self._records.reset()
         if self.render_mode == "rgb_array":
             self._visualizer.reset(self._state, observations)
-        return observations, {}
+        return self._viewed_reset(observations, {})
 
     def step(self, actions):
         assert self._state is not None
@@ -1445,7 +1713,7 @@ class VectorEnvironment(_VectorEnvBase):
         if self.render_mode == "rgb_array":
             not_done = ~done
             self._visualizer.step(self._state[not_done], observations[not_done], not_done)
-        return observations, rewards, terminated, truncated, info
+        return self._viewed_step(observations, rewards, terminated, truncated, info)
 
     episode_accumulators = _HostGlue.episode_accumulators
 
@@ -1497,7 +1765,7 @@ class DeviceVectorEnvironment(_DeviceVectorEnv):
     def __init__(self, ender, initializer, rewarder, transformer, num_envs, ends=(5.0, 10.0), max_focus_move=5.0,
                  render_mode=None, *, frame_height=300, samples_per_pixel=100, device=None, first_state_index=0,
                  devices=None, observer=None, focus_observation_index=1, device_initializer=False,
-                 episode_records=False):
+                 episode_records=False, learner_view=None):
         from reinfocus_amd.environments import state_transformer, strategy_program
 
         if devices is not None:
@@ -1537,6 +1805,7 @@ class DeviceVectorEnvironment(_DeviceVectorEnv):
         self.action_space = transformer.action_space
         self.single_observation_space = single_observation_space
         self.observation_space = spaces.batch_space(self.single_observation_space, num_envs)
+        self._configure_view(learner_view)
         self._visualizer = None
         if render_mode == "rgb_array":
             self._visualizer = episode_visualizer.HistoryVisualizer(num_envs, TARGET, FOCUS, focus_observation_index,

@@ -37,6 +37,14 @@ ENTRY_POINTS = {
 }
 
 
+def _no_host_view(kwargs):
+    """glue="host" is the reference's route, wrapped as the reference wraps it; the learner view (learner_view=) is the
+    device-resident environment's stage (the host classes take the keyword directly, as the twins the tests compare)."""
+    if kwargs.get("learner_view") is not None:
+        raise ValueError('glue="host" has no learner view (learner_view=): wrap the host environment in VecNormalize and '
+                         'VecFrameStack, or use glue="device"')
+
+
 def vector_discrete_steps(max_episode_steps=20, num_envs=1, render_mode=None, *, glue="device", devices=None,
                           **kwargs):
     """vector_entry_point of DiscreteSteps-v0 (examples/__init__.py:9,
@@ -48,6 +56,7 @@ def vector_discrete_steps(max_episode_steps=20, num_envs=1, render_mode=None, *,
         assert glue == "device", "the sharded environment is device-resident"
         return harness.ShardedVectorDiscreteSteps(max_episode_steps, num_envs, render_mode, devices=devices, **kwargs)
     if glue == "host":
+        _no_host_view(kwargs)
         return harness.VectorDiscreteSteps(max_episode_steps, num_envs, render_mode, **kwargs)
     assert glue == "device", f"glue must be 'device' or 'host', not {glue!r}"
     return harness.DeviceVectorDiscreteSteps(max_episode_steps, num_envs, render_mode, **kwargs)
@@ -65,6 +74,7 @@ def vector_continuous_jumps(max_episode_steps=20, num_envs=1, render_mode=None, 
         assert glue == "device", "the sharded environment is device-resident"
         return harness.ShardedVectorContinuousJumps(max_episode_steps, num_envs, render_mode, devices=devices, **kwargs)
     if glue == "host":
+        _no_host_view(kwargs)
         return harness.VectorContinuousJumps(max_episode_steps, num_envs, render_mode, **kwargs)
     assert glue == "device", f"glue must be 'device' or 'host', not {glue!r}"
     return harness.DeviceVectorContinuousJumps(max_episode_steps, num_envs, render_mode, **kwargs)

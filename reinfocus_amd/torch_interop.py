@@ -56,12 +56,18 @@ class TensorIO:
     tests anything with its env_*_device methods): `num_envs` environments with observations of `obs_width` columns on
     HIP device `device_index`; float_actions: the task takes torch.float32 actions, not torch.int32 / int64 indices."""
 
-    def __init__(self, ctx, num_envs, obs_width, float_actions, device_index, episode_records=False):
+    def __init__(self, ctx, num_envs, obs_width, float_actions, device_index, episode_records=False, view_stack=0):
         """episode_records: the context keeps them (rf_env_configure_records) -- step() then goes through
-        rf_env_step_device_records and its info holds the three record tensors, owned like the other outputs."""
+        rf_env_step_device_records and its info holds the three record tensors, owned like the other outputs.
+        view_stack: the frame_stack of the context's learner view (rf_env_configure_view; 0: none) -- step() then goes
+        through rf_env_step_device_view: obs (float32 [n, view_stack * W]) and rewards are the view's -- out= means
+        them --, info holds "raw_observation" and "raw_reward" (and with records the view's "final_observation" next to
+        "raw_final_observation") as owned tensors, and reset_viewed() is the reset."""
         self._ctx = ctx
         self._records = bool(episode_records)
         self._owned_records = None
+        self._view_stack = int(view_stack)
+        self._owned_view = None
         self._n = int(num_envs)
         self._width = int(obs_width)
         self._float = bool(float_actions)
@@ -99,7 +105,7 @@ class TensorIO:
         torch = _torch()
         if not isinstance(out, (tuple, list)) or len(out) != 3:
             raise TypeError("out must be (obs, rewards, truncated)")
-        wanted = (("out[0] (obs)", (torch.float32,), (self._n, self._width)),
+        wanted = (("out[0] (obs)", (torch.float32,), (self._n, self._width * max(self._view_stack, 1))),
                   ("out[1] (rewards)", (torch.float64,), (self._n,)),
                   ("out[2] (truncated)", (torch.bool, torch.uint8), (self._n,)))
         for tensor, (what, dtypes, shape) in zip(out, wanted):
@@ -138,6 +144,19 @@ class TensorIO:
                                    torch.empty(self._n, dtype=torch.int32, device=device))
         return self._owned_records
 
+    def _view_outputs(self):
+        """(view observation float32 [n, V], view reward float64 [n], view final_observation float32 [n, V] or None),
+        made once and overwritten by every step without out=."""
+        if self._owned_view is None:
+            torch = _torch()
+            device = torch.device("cuda", self._index)
+            cells = self._width * self._view_stack
+            self._owned_view = (torch.empty((self._n, cells), dtype=torch.float32, device=device),
+                                torch.empty(self._n, dtype=torch.float64, device=device),
+                                torch.empty((self._n, cells), dtype=torch.float32, device=device) if self._records
+                                else None)
+        return self._owned_view
+
     def _stream(self):
         torch = _torch()
         return torch.cuda.current_stream(torch.device("cuda", self._index)).cuda_stream
@@ -150,9 +169,39 @@ class TensorIO:
         self._ctx.env_reset_device(obs.data_ptr(), self._stream())
         return obs
 
+    def reset_viewed(self):
+        """reset() of a context with a learner view: (view observation, {"raw_observation": obs}), both owned."""
+        _torch()
+        check_one_runtime()
+        raw, view = self._outputs()[0], self._view_outputs()[0]
+        self._ctx.env_reset_device_view(raw.data_ptr(), view.data_ptr(), self._stream())
+        return view, {"raw_observation": raw}
+
+    def _step_viewed(self, actions, code, out):
+        torch = _torch()
+        owned, (view_obs, view_rewards, view_final) = self._outputs(), self._view_outputs()
+        truncated = owned[2]
+        if out is not None:
+            view_obs, view_rewards, truncated = self._checked_out(out)
+        info = {"raw_observation": owned[0], "raw_reward": owned[1]}
+        record_ptrs = (None, None, None)
+        if self._records:
+            final_obs, returns, lengths = self._record_outputs()
+            record_ptrs = (final_obs.data_ptr(), returns.data_ptr(), lengths.data_ptr())
+            info.update(final_observation=view_final, raw_final_observation=final_obs, episode_return=returns,
+                        episode_length=lengths)
+        self._ctx.env_step_device_view(actions.data_ptr(), code, owned[0].data_ptr(), owned[1].data_ptr(),
+                                       truncated.data_ptr(), owned[4].data_ptr(), *record_ptrs, view_obs.data_ptr(),
+                                       view_rewards.data_ptr(), None if view_final is None else view_final.data_ptr(),
+                                       self._stream())
+        flags = truncated if truncated.dtype == torch.bool else truncated.view(torch.bool)
+        return view_obs, view_rewards, owned[3], flags, info
+
     def step(self, actions, out=None):
         code = self.checked_actions(actions)
         check_one_runtime()
+        if self._view_stack:
+            return self._step_viewed(actions, code, out)
         torch = _torch()
         owned = self._outputs()
         obs, rewards, truncated = owned[:3] if out is None else self._checked_out(out)
