@@ -755,6 +755,37 @@ int rf_env_step_device_view(rf_ctx *ctx, const void *d_actions, int action_dtype
                             void *caller_stream);
 int rf_env_reset_device_view(rf_ctx *ctx, float *d_obs, float *d_view_obs, void *caller_stream);
 
+/* ---- rollout: GAE advantages and returns of a PPO rollout in one launch -----------------------------------------------
+ * The consumer of device steps in the reference's PPO configurations is stable-baselines3's RolloutBuffer: T = n_steps
+ * steps of n environments, then GAE(gamma, lambda) advantages and returns (compute_returns_and_advantage), with the
+ * bootstrap of OnPolicyAlgorithm.collect_rollouts for steps that ended by truncation -- which is how every episode here
+ * ends, the step resetting the environment in the same call.  No reference counterpart.  Needs no environment: the
+ * context only says which GPU.
+ *
+ * One definition, numpy twin (environments/rollout.py gae_numpy) and kernel (csrc/rf_rollout.h) alike.  Arrays are
+ * [T][n] row-major: d_rewards float64, d_values float32, d_truncated uint8 (0 / 1), d_final_values float32 or NULL,
+ * d_advantages and d_returns float32; d_last_values float32[n].  g = float32(gamma), gl = float32(gamma * gae_lambda)
+ * with the product taken in float64.  Every operation below is float32, left to right, no FMA contraction:
+ *   r      = float32(rewards[t][e]);  where d_final_values is given and truncated[t][e]: r = r + g * final_values[t][e]
+ *            (a select: final_values of a step that did not end -- NaN in practice -- never reaches the result)
+ *   nnt    = 1.0f - float32(truncated[t][e])     (episode_starts[t+1] == truncated[t], dones == truncated[T-1])
+ *   next_v = last_values[e] if t == T-1 else values[t+1][e]
+ *   delta  = (r + (g * next_v) * nnt) - values[t][e]
+ *   last   = delta + (gl * nnt) * last           (last = 0.0f before t = T-1; t runs T-1 .. 0)
+ *   advantages[t][e] = last;  returns[t][e] = last + values[t][e]
+ * ONE DELIBERATE DIFFERENCE: SB3 adds the bootstrap in whatever dtype the wrapper stack left the rewards in; here it is
+ * a float32 addition after the cast.
+ *
+ *   rf_rollout_advantages   one launch on caller_stream (a hipStream_t; 0: the default stream): every array is the
+ *                           caller's, so nothing is handed over by events and the host waits for nothing.  Refused
+ *                           (RF_ERR_INVALID, nothing enqueued, no pointer dereferenced): T < 1 or n < 1; a NULL array
+ *                           other than d_final_values; an array the runtime does not vouch for on the ctx's GPU, exactly
+ *                           as for device io; an output that overlaps an input or the other output; a capturing caller
+ *                           stream. */
+int rf_rollout_advantages(rf_ctx *ctx, int T, int n, const double *d_rewards, const float *d_values,
+                          const uint8_t *d_truncated, const float *d_final_values, const float *d_last_values, double gamma,
+                          double gae_lambda, float *d_advantages, float *d_returns, void *caller_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -95,6 +95,7 @@ SYMBOLS = (
     "rf_env_view_get_state",
     "rf_env_step_device_view",
     "rf_env_reset_device_view",
+    "rf_rollout_advantages",
     "rf_render_kernel_name",
     "rf_pixels_rendered",
     "rf_allocations_poisoned",
@@ -308,6 +309,7 @@ def load():
     lib.rf_env_view_get_state.argtypes = [vp, vp, vp]
     lib.rf_env_step_device_view.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.rf_env_reset_device_view.argtypes = [vp, vp, vp, vp]
+    lib.rf_rollout_advantages.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, ctypes.c_double, ctypes.c_double, vp, vp, vp]
     lib.rf_render_kernel_name.restype = ctypes.c_char_p
     lib.rf_render_kernel_name.argtypes = [vp]
     lib.rf_pixels_rendered.restype = ctypes.c_ulonglong
@@ -634,6 +636,18 @@ class Context:
         step, env = ctypes.c_int(-1), ctypes.c_int(-1)
         _check(self._lib.rf_env_device_status(self._h, ctypes.byref(step), ctypes.byref(env)))
         return None if step.value < 0 else (step.value, env.value)
+
+    # --- rollout (rf_rollout_advantages): addresses of device memory as plain integers, nothing waited for ------------
+    def rollout_advantages(self, steps, num_envs, rewards_ptr, values_ptr, truncated_ptr, final_values_ptr,
+                           last_values_ptr, gamma, gae_lambda, advantages_ptr, returns_ptr, stream):
+        """rf_rollout_advantages: GAE advantages and returns of [steps][num_envs] device arrays given by address
+        (final_values_ptr may be None: no bootstrap), one launch on `stream` (a hipStream_t as an integer).  Only
+        enqueues."""
+        rc = self._lib.rf_rollout_advantages(self._h, steps, num_envs, rewards_ptr, values_ptr, truncated_ptr,
+                                             final_values_ptr, last_values_ptr, gamma, gae_lambda, advantages_ptr,
+                                             returns_ptr, stream)
+        if rc != 0:
+            _check(rc)
 
     # --- episode records (rf_env_configure_records ...) ---------------------------------------------------------
     def env_configure_records(self, on=True):

@@ -10,6 +10,7 @@
 #include "rf_env_init.h"
 #include "rf_env_io.h"
 #include "rf_env_view.h"
+#include "rf_rollout.h"
 
 using namespace rfh;
 
@@ -1118,6 +1119,13 @@ int env_reset_device(rf_ctx *ctx, float *d_obs, float *d_view_obs, void *caller_
     return RF_OK;
 }
 
+// [a, a + a_bytes) and [b, b + b_bytes) share a byte (addresses compared as integers, nothing dereferenced)
+bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + b_bytes && y < x + a_bytes;
+}
+
 } // namespace
 
 namespace rfh {
@@ -1878,5 +1886,52 @@ int rf_env_device_status(rf_ctx *ctx, int *fault_step, int *fault_env)
     return RF_OK;
 }
 
-} // extern "C"
+int rf_rollout_advantages(rf_ctx *ctx, int T, int n, const double *d_rewards, const float *d_values,
+                          const uint8_t *d_truncated, const float *d_final_values, const float *d_last_values, double gamma,
+                          double gae_lambda, float *d_advantages, float *d_returns, void *caller_stream)
+{
+    const char *fn = "rf_rollout_advantages";
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", fn);
+    RF_REQUIRE(d_rewards && d_values && d_truncated && d_last_values && d_advantages && d_returns, "%s: NULL argument", fn);
+    RF_REQUIRE(T >= 1 && n >= 1, "%s: T = %d and n = %d must both be at least 1", fn, T, n);
+    RF_HIP(hipSetDevice(ctx->device));
+    const size_t cells = (size_t)T * (size_t)n;
+    struct Array {
+        const void *p;
+        size_t bytes, align;
+        const char *what;
+    };
+    const Array inputs[] = {{d_rewards, cells * 8, 8, "d_rewards"},
+                            {d_values, cells * 4, 4, "d_values"},
+                            {d_truncated, cells, 1, "d_truncated"},
+                            {d_final_values, cells * 4, 4, "d_final_values"},
+                            {d_last_values, (size_t)n * 4, 4, "d_last_values"}};
+    const Array outputs[] = {{d_advantages, cells * 4, 4, "d_advantages"}, {d_returns, cells * 4, 4, "d_returns"}};
+    for (const Array &a : inputs) {
+        if (a.p == nullptr) // (d_final_values: no bootstrap)
+            continue;
+        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
+            return rc;
+    }
+    for (const Array &a : outputs) {
+        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
+            return rc;
+        for (const Array &b : inputs)
+            RF_REQUIRE(b.p == nullptr || !ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s (an output "
+                       "must not alias an input: the chain writes a step before the steps before it are read)", fn, a.what,
+                       b.what);
+    }
+    RF_REQUIRE(!ranges_overlap(d_advantages, cells * 4, d_returns, cells * 4), "%s: d_advantages overlaps d_returns", fn);
+    const hipStream_t caller = (hipStream_t)caller_stream;
+    if (int rc = refuse_capturing(caller, fn))
+        return rc;
+    // every array is the caller's, so the launch goes to the caller's stream: no event hand-over, nothing waited for
+    const float g = (float)gamma, gl = (float)(gamma * gae_lambda); // (the product in float64 first, as numpy takes it)
+    const unsigned blocks = (unsigned)(((size_t)n + rf::kRolloutTile - 1) / rf::kRolloutTile);
+    hipLaunchKernelGGL(rf::rollout_gae_kernel, dim3(blocks), dim3(rf::kRolloutThreads), 0, caller, T, n, d_rewards, d_values,
+                       d_truncated, d_final_values, d_last_values, g, gl, d_advantages, d_returns);
+    RF_HIP(hipGetLastError());
+    return RF_OK;
+}
 
+} // extern "C"

@@ -1836,3 +1836,6 @@ class DeviceVectorEnvironment(_DeviceVectorEnv):
 
     def _float_actions(self):
         return not self._discrete
+
+
+from reinfocus_amd.environments.rollout import DeviceRollout, Rollout  # noqa: E402,F401 -- the PPO rollout buffers

@@ -1,0 +1,296 @@
+"""PPO's rollout buffer for the vector environments: n_steps steps of observations, actions, rewards, values and
+log-probabilities, then GAE(gamma, lambda) advantages and returns -- stable-baselines3's RolloutBuffer
+(compute_returns_and_advantage) with the truncation bootstrap of OnPolicyAlgorithm.collect_rollouts, which every
+training configuration of the reference (examples/ppo_*.yml) runs behind VecNormalize and VecFrameStack.
+
+Every episode of these environments ends by truncation, and the step resets the environment in the same call: so
+episode_starts[t + 1] == truncated[t], dones == truncated[T - 1], and a truncated step needs
+reward += gamma * V(final_observation).
+
+One definition of the arithmetic (include/reinfocus_hip.h, "rollout"): gae_numpy below is its numpy float32
+restatement and the oracle; rollout_gae_kernel (csrc/rf_rollout.h) computes the same bits in one launch.
+
+    Rollout        over the numpy twins (VectorDiscreteSteps, VectorContinuousJumps, VectorEnvironment)
+    DeviceRollout  over the device-resident environments, from and to torch tensors on the environment's GPU: the step
+                   writes its results into the buffer's slabs (step_tensors(out=...)), finish() is one kernel launch,
+                   and nothing waits for the host
+
+torch is imported lazily, by DeviceRollout only (reinfocus_amd/torch_interop.py says why import order matters).
+"""
+
+import numpy as np
+
+from reinfocus_amd.environments import spaces
+
+FLAT_KEYS = ("observations", "actions", "values", "log_probs", "advantages", "returns")
+
+
+def gae_numpy(rewards, values, truncated, final_values, last_values, gamma, gae_lambda):
+    """(advantages, returns), float32 [T, n], of rewards float64 [T, n], values float32 [T, n], truncated uint8 [T, n]
+    (0 / 1), final_values float32 [T, n] or None (no bootstrap) and last_values float32 [n]; gamma and gae_lambda are
+    Python floats.  The definition, literally: every operation is a numpy float32 operation, left to right."""
+    f32 = np.float32
+    rewards = np.asarray(rewards, dtype=np.float64)
+    steps, num_envs = rewards.shape
+    values = np.asarray(values, dtype=f32).reshape(steps, num_envs)
+    truncated = np.asarray(truncated, dtype=np.uint8).reshape(steps, num_envs)
+    last_values = np.asarray(last_values, dtype=f32).reshape(num_envs)
+    g = f32(float(gamma))
+    gl = f32(float(gamma) * float(gae_lambda))  # (the product in float64 first)
+    advantages = np.empty((steps, num_envs), dtype=f32)
+    with np.errstate(all="ignore"):
+        r = rewards.astype(f32)
+        if final_values is not None:
+            final_values = np.asarray(final_values, dtype=f32).reshape(steps, num_envs)
+            r = np.where(truncated != 0, r + g * final_values, r)  # a select, never a multiplication by 0 / 1
+        nnt = f32(1.0) - truncated.astype(f32)
+        last = np.zeros(num_envs, dtype=f32)
+        for t in range(steps - 1, -1, -1):
+            next_v = last_values if t == steps - 1 else values[t + 1]
+            delta = (r[t] + (g * next_v) * nnt[t]) - values[t]
+            last = delta + (gl * nnt[t]) * last
+            advantages[t] = last
+        returns = advantages + values
+    assert advantages.dtype == f32 and returns.dtype == f32
+    return advantages, returns
+
+
+def _index_task(env):
+    return isinstance(env.single_action_space, spaces.Discrete)
+
+
+class _Bookkeeping:
+    """What both forms count on the host (plain Python integers: nothing is asked of the device): the step within the
+    rollout, how many of its steps were bootstrapped, and whether a rollout is open."""
+
+    def _configure(self, env, n_steps, gamma, gae_lambda, records):
+        self.env = env
+        self.n_steps = int(n_steps)
+        self.gamma, self.gae_lambda = float(gamma), float(gae_lambda)
+        if self.n_steps < 1:
+            raise ValueError(f"n_steps {n_steps!r} is not at least 1")
+        self.num_envs = int(env.num_envs)
+        self.obs_width = int(env.single_observation_space.shape[0])
+        self._records = bool(records)
+        self._t = None  # (None: no rollout is open)
+        self._bootstrapped = 0
+        self._last_bootstrap = -1
+        self._complete = False  # (row T holds the observation the next rollout begins with)
+
+    def _begin(self, obs):
+        if obs is None and not self._complete:
+            raise ValueError("start() without obs continues the rollout before it, and none has been finished: pass the "
+                             "observation the environment's reset returned")
+        self._t, self._bootstrapped, self._last_bootstrap = 0, 0, -1
+
+    def _next_step(self):
+        if self._t is None:
+            raise ValueError("no rollout is open: start() first")
+        if self._t >= self.n_steps:
+            raise ValueError(f"the rollout already holds its {self.n_steps} steps: finish() it and start() the next")
+        return self._t
+
+    def _bootstrap_step(self):
+        if not self._records:
+            raise ValueError(f"bootstrap() needs info['final_observation'], and {type(self.env).__name__} was built "
+                             "without episode_records=True")
+        if self._t is None or self._t == 0:
+            raise ValueError("bootstrap() stores V(final_observation) of the step just taken, and no step was taken")
+        t = self._t - 1
+        if self._last_bootstrap == t:
+            raise ValueError(f"step {t} of the rollout is bootstrapped already")
+        self._last_bootstrap = t
+        self._bootstrapped += 1
+        return t
+
+    def _finishing(self):
+        """True: every step was bootstrapped; False: none was."""
+        if self._t is None or self._t < self.n_steps:
+            raise ValueError(f"the rollout holds {self._t or 0} of its {self.n_steps} steps")
+        if self._bootstrapped not in (0, self.n_steps):
+            raise ValueError(f"bootstrap() was called for {self._bootstrapped} of the rollout's {self.n_steps} steps: a "
+                             "partially bootstrapped rollout has no defined advantages (call it after every step or "
+                             "after none)")
+        self._complete = True
+        return self._bootstrapped == self.n_steps
+
+    def _finished(self):
+        if not (self._complete and self._t == self.n_steps):
+            raise ValueError("the rollout is not finished: advantages and returns are those of finish()")
+
+
+class Rollout(_Bookkeeping):
+    """The rollout buffer of a numpy twin: the oracle of DeviceRollout, with the same methods over numpy arrays.
+
+        rollout = Rollout(env, n_steps=128)
+        obs, info = env.reset()
+        rollout.start(obs)
+        for _ in range(128):
+            obs, rewards, terminated, truncated, info = rollout.step(actions, values, log_probs)
+            rollout.bootstrap(value_of(info["final_observation"]))      # episode_records=True only
+        advantages, returns = rollout.finish(value_of(obs))
+        for batch in rollout.minibatches(64): ...
+        rollout.start()                                                 # row T becomes row 0
+    """
+
+    def __init__(self, env, n_steps, gamma=0.99, gae_lambda=0.95):
+        self._configure(env, n_steps, gamma, gae_lambda, getattr(env, "_records", None) is not None
+                        or bool(getattr(env, "_episode_records", False)))
+        steps, n = self.n_steps, self.num_envs
+        self.observations = np.zeros((steps + 1, n, self.obs_width), dtype=np.float32)
+        self.actions = np.zeros((steps, n), dtype=np.int64 if _index_task(env) else np.float32)
+        self.rewards = np.zeros((steps, n), dtype=np.float64)
+        self.truncated = np.zeros((steps, n), dtype=np.uint8)
+        self.values, self.log_probs, self.final_values, self.advantages, self.returns = (
+            np.zeros((steps, n), dtype=np.float32) for _ in range(5))
+
+    def start(self, obs=None):
+        self._begin(obs)
+        self.observations[0] = self.observations[self.n_steps] if obs is None else obs
+
+    def step(self, actions, values, log_probs):
+        t = self._next_step()
+        self.actions[t] = np.asarray(actions).reshape(self.num_envs)
+        self.values[t] = np.asarray(values).reshape(self.num_envs)
+        self.log_probs[t] = np.asarray(log_probs).reshape(self.num_envs)
+        result = self.env.step(actions)
+        self.observations[t + 1], self.rewards[t], self.truncated[t] = result[0], result[1], result[3]
+        self._t = t + 1
+        return result
+
+    def bootstrap(self, final_values):
+        self.final_values[self._bootstrap_step()] = np.asarray(final_values).reshape(self.num_envs)
+
+    def finish(self, last_values):
+        final_values = self.final_values if self._finishing() else None
+        self.advantages, self.returns = gae_numpy(self.rewards, self.values, self.truncated, final_values, last_values,
+                                                  self.gamma, self.gae_lambda)
+        return self.advantages, self.returns
+
+    def flat(self):
+        """The rollout as stable-baselines3's swap_and_flatten orders it: index e * T + t."""
+        self._finished()
+        slabs = dict(zip(FLAT_KEYS, (self.observations[:self.n_steps], self.actions, self.values, self.log_probs,
+                                     self.advantages, self.returns)))
+        return {key: slab.swapaxes(0, 1).reshape(self.n_steps * self.num_envs, *slab.shape[2:])
+                for key, slab in slabs.items()}
+
+    def minibatches(self, batch_size, generator=None):
+        """Dicts of flat() rows chosen by one permutation (generator: a numpy.random.Generator); the last one may be
+        shorter."""
+        flat = self.flat()
+        total = self.n_steps * self.num_envs
+        order = (np.random.default_rng() if generator is None else generator).permutation(total)
+        for first in range(0, total, int(batch_size)):
+            index = order[first:first + int(batch_size)]
+            yield {key: rows[index] for key, rows in flat.items()}
+
+
+class DeviceRollout(_Bookkeeping):
+    """The rollout buffer of a device-resident environment (DeviceVectorDiscreteSteps, DeviceVectorContinuousJumps or
+    DeviceVectorEnvironment, each with device_initializer=True; with or without learner_view= and episode_records=), as
+    torch tensors on the environment's GPU.  Used as Rollout is, with reset_tensors() in place of reset(), and bit for
+    bit equal to it.
+
+    The slabs are [T][n] row-major: observations float32 [T + 1, n, V], actions [T, n] in the task's dtype (int64 or
+    float32), rewards float64, truncated uint8, values / log_probs / final_values / advantages / returns float32.
+    step() hands rows of them to step_tensors(out=...), so the environment's own hand-over launch fills the buffer: no
+    copy and no launch is added for the step's outputs.  finish() is one launch of rollout_gae_kernel
+    (rf_rollout_advantages) on torch's current stream.  No method synchronises the host."""
+
+    def __init__(self, env, n_steps, gamma=0.99, gae_lambda=0.95):
+        from reinfocus_amd.environments import harness
+
+        if not isinstance(env, harness._DeviceVectorEnv):
+            if hasattr(env, "_no_tensors"):  # (a sharded environment: its own refusal says why)
+                env._no_tensors()
+            raise TypeError(f"DeviceRollout needs a device-resident environment, not {type(env).__name__} (the numpy "
+                            "twins have Rollout)")
+        io = env._tensor_io()  # (ValueError, as step_tensors': a host initializer, a render_mode)
+        self._configure(env, n_steps, gamma, gae_lambda, env._episode_records)
+        from reinfocus_amd import torch_interop
+
+        torch = self._torch = torch_interop._torch()
+        self._io = io
+        self._ctx = env._ctx
+        self.device = torch.device("cuda", self._ctx.device)
+        steps, n = self.n_steps, self.num_envs
+
+        def slab(dtype, *shape):
+            return torch.zeros(shape or (steps, n), dtype=dtype, device=self.device)
+
+        self.observations = slab(torch.float32, steps + 1, n, self.obs_width)
+        self.actions = slab(torch.int64 if _index_task(env) else torch.float32)
+        self.rewards = slab(torch.float64)
+        self.truncated = slab(torch.uint8)
+        self.values, self.log_probs, self.final_values, self.advantages, self.returns = (
+            slab(torch.float32) for _ in range(5))
+
+    def _row(self, tensor, what):
+        """`tensor` as a float32-or-whatever [n] row on the buffer's GPU (a view, never a host copy)."""
+        if not isinstance(tensor, self._torch.Tensor):
+            raise TypeError(f"{what} must be a torch.Tensor on {self.device}, not {type(tensor).__name__}")
+        self._io._on_device(tensor, what)
+        if tensor.numel() != self.num_envs:
+            raise ValueError(f"{what} have shape {tuple(tensor.shape)}, not ({self.num_envs},) or ({self.num_envs}, 1)")
+        return tensor.reshape(self.num_envs)
+
+    def start(self, obs=None):
+        """Begins a rollout: the first time with the observation reset_tensors() returned, which is copied into row 0;
+        afterwards without, and row T of the rollout before becomes row 0 (one device copy on the current stream)."""
+        self._begin(obs)
+        if obs is None:
+            self.observations[0].copy_(self.observations[self.n_steps])
+        else:
+            self._io._on_device(obs, "obs")
+            self.observations[0].copy_(obs)
+
+    def step(self, actions, values, log_probs):
+        """Stores the three tensors in row t and steps the environment into rows of the slabs; returns what
+        step_tensors returned (its obs, rewards and truncated ARE the buffer's rows)."""
+        t = self._next_step()
+        self._io.checked_actions(actions)  # (before anything is stored)
+        values, log_probs = self._row(values, "values"), self._row(log_probs, "log_probs")
+        self.actions[t].copy_(actions.reshape(self.num_envs))
+        self.values[t].copy_(values)
+        self.log_probs[t].copy_(log_probs)
+        result = self.env.step_tensors(actions, out=(self.observations[t + 1], self.rewards[t], self.truncated[t]))
+        self._t = t + 1
+        return result
+
+    def bootstrap(self, final_values):
+        """Stores V(info["final_observation"]) of the step just taken (NaN where the step did not end an episode: never
+        read).  For every step of a rollout or for none."""
+        final_values = self._row(final_values, "final_values")
+        self.final_values[self._bootstrap_step()].copy_(final_values)
+
+    def finish(self, last_values):
+        """(advantages, returns) of the rollout, given V(observations[T]): one kernel launch, nothing waited for."""
+        last_values = self._row(last_values, "last_values")
+        if last_values.dtype != self._torch.float32 or not last_values.is_contiguous():
+            last_values = last_values.to(self._torch.float32).contiguous()
+        bootstrapped = self._finishing()
+        self._ctx.rollout_advantages(self.n_steps, self.num_envs, self.rewards.data_ptr(), self.values.data_ptr(),
+                                     self.truncated.data_ptr(), self.final_values.data_ptr() if bootstrapped else None,
+                                     last_values.data_ptr(), self.gamma, self.gae_lambda, self.advantages.data_ptr(),
+                                     self.returns.data_ptr(), self._io._stream())
+        return self.advantages, self.returns
+
+    def flat(self):
+        """The rollout as stable-baselines3's swap_and_flatten orders it: index e * T + t.  The slabs are [T][n] (lanes
+        of the kernels run along n), so each entry is the transposed view made contiguous: one device copy each."""
+        self._finished()
+        slabs = dict(zip(FLAT_KEYS, (self.observations[:self.n_steps], self.actions, self.values, self.log_probs,
+                                     self.advantages, self.returns)))
+        return {key: slab.transpose(0, 1).reshape(self.n_steps * self.num_envs, *slab.shape[2:])
+                for key, slab in slabs.items()}
+
+    def minibatches(self, batch_size, generator=None):
+        """Dicts of flat() rows chosen by one torch.randperm on the device (generator: a torch.Generator of that
+        device); the last one may be shorter."""
+        flat = self.flat()
+        total = self.n_steps * self.num_envs
+        order = self._torch.randperm(total, device=self.device, generator=generator)
+        for first in range(0, total, int(batch_size)):
+            index = order[first:first + int(batch_size)]
+            yield {key: rows[index] for key, rows in flat.items()}
