@@ -786,6 +786,73 @@ int rf_rollout_advantages(rf_ctx *ctx, int T, int n, const double *d_rewards, co
                           const uint8_t *d_truncated, const float *d_final_values, const float *d_last_values, double gamma,
                           double gae_lambda, float *d_advantages, float *d_returns, void *caller_stream);
 
+/* ---- policy: the PPO actor-critic forward with sampling in one launch -------------------------------------------------
+ * What turns an observation into the next action, its log-probability and V(obs) in the reference's PPO configurations
+ * is stable-baselines3's MlpPolicy (ActorCriticPolicy with separate pi / vf extractors and a Categorical head).  No
+ * reference counterpart.  Needs no environment: the context only says which GPU.
+ *
+ * One definition, numpy twin (environments/policy.py policy_numpy), host build (tests/policycheck) and kernel
+ * (csrc/rf_policy.h) alike; the scalar functions are csrc/rf_policy_math.h.
+ *
+ * Network.  Two nets, pi and vf, each with 1 or 2 hidden layers of width 1 .. RF_POLICY_MAX_WIDTH; input width
+ * obs_width 1 .. RF_POLICY_MAX_WIDTH; the pi head has n_actions 2 .. RF_POLICY_MAX_ACTIONS outputs (the logits of a
+ * Categorical), the vf head one.  One activation for both nets.  Continuous action spaces (the reference trains
+ * ContinuousJumps with gSDE) are out of scope.
+ * Parameters: one float32 array, every matrix TRANSPOSED ([in][out] row-major: SB3's weight.T), in this order:
+ *   pi: W0^T, b0, (W1^T, b1,) Wa^T [last][n_actions], ba;   vf: W0^T, b0, (W1^T, b1,) Wv^T [last][1], bv
+ * Linear layer: y_j = b_j; for k = 0 .. K-1: y_j = y_j + x_k * W[j][k] -- a float32 multiply, then a float32 add, in
+ * that order, no FMA.  No MFMA: its internal accumulation order is not documented.
+ * Activation: relu(x) = x > 0 ? x : 0 (NaN and -0 become +0), or tanh32(x) = sign(x) * (1 - t) / (1 + t) with
+ * t = exp32(-2 |x|); tanh32(NaN) is NaN.
+ * exp32 (x <= 0; +0 for x < -87, for -inf and for NaN; exp32(0) == 1; never a subnormal) and log32 (on [1, 64]) are the
+ * project's own: float32 + - * / (correctly rounded), comparisons, float <-> int conversions and integer operations on
+ * the exponent field only -- csrc/rf_policy_math.h is the text.
+ * Head.  With logits l_i: m = the first maximum (m = l_0; l_i > m replaces it: a NaN l_0 stays, NaNs elsewhere are never
+ * the maximum), z_i = l_i - m, e_i = exp32(z_i), c_i the sequential float32 partial sums of e, s = c_{A-1},
+ * log_prob_i = z_i - log32(s).  Sampled action: the first i with double(c_i) > u * double(s) (one float64 multiply,
+ * exact conversions), the last index if there is none.  Deterministic action: the first maximum.
+ * NaN and +-inf logits: a -inf or NaN logit next to a finite maximum has e_i = 0 and is never sampled.  Where no e_i is
+ * 1 -- l_0 is NaN, or the maximum is +inf or -inf -- s < 1: the row is degenerate, its action is the first maximum
+ * (sampled or not; its draw is still consumed) and its log_prob is NaN.
+ * Every NaN that is stored (logits, log_probs, values, final_values) is the bit pattern 0x7fc00000.
+ * Random numbers.  u of environment e is draw number e of numpy.random.Generator(PCG64DXSM) in the state `gen` =
+ * {state low, state high, inc low, inc high}: (next64 >> 11) * 2^-53.  The caller advances its generator by n after a
+ * sampled call; a deterministic or values-only call uses none.  No generator state lives on the device.
+ * V(final_observation).  With d_final_obs [n][obs_width] and d_final_values: final_values[e] = V(final_obs[e]), and NaN
+ * where final_obs[e][0] is NaN (the rows episode records write where no episode ended).
+ *
+ *   rf_policy_params_size   floats of the packed parameters of desc; 0 for a desc outside the limits or a NULL ctx
+ *                           (it takes the ctx as every entry point does and makes its GPU current, no more).
+ *   rf_policy_forward       one launch on caller_stream (a hipStream_t; 0: the default stream), nothing allocated,
+ *                           nothing waited for.  Outputs (each may be NULL): d_actions int64[n], d_log_probs float32[n]
+ *                           (needs d_actions), d_values float32[n], d_final_values float32[n] (needs d_final_obs),
+ *                           d_logits float32[n][n_actions]; at least one must be given.  gen is read on the host and
+ *                           needed unless flags has RF_POLICY_DETERMINISTIC or d_actions is NULL.  Refused
+ *                           (RF_ERR_INVALID, nothing enqueued, no device pointer dereferenced): a desc outside the
+ *                           limits, n < 1, unknown flags, an array the runtime does not vouch for on the ctx's GPU
+ *                           (a host pointer, a misaligned one, one that ends past its allocation) exactly as for
+ *                           device io, an output that overlaps an input or another output. */
+#define RF_POLICY_MAX_WIDTH 256
+#define RF_POLICY_MAX_ACTIONS 64
+#define RF_POLICY_RELU 0
+#define RF_POLICY_TANH 1
+#define RF_POLICY_DETERMINISTIC 1
+
+typedef struct rf_policy_desc {
+    int obs_width;   /* 1 .. RF_POLICY_MAX_WIDTH */
+    int n_actions;   /* 2 .. RF_POLICY_MAX_ACTIONS */
+    int activation;  /* RF_POLICY_RELU or RF_POLICY_TANH */
+    int pi_layers;   /* 1 or 2 */
+    int pi_width[2]; /* 1 .. RF_POLICY_MAX_WIDTH each; [1] ignored with one layer */
+    int vf_layers;
+    int vf_width[2];
+} rf_policy_desc;
+
+unsigned long long rf_policy_params_size(rf_ctx *ctx, const rf_policy_desc *desc);
+int rf_policy_forward(rf_ctx *ctx, const rf_policy_desc *desc, const float *d_params, int n, const float *d_obs,
+                      const float *d_final_obs, const unsigned long long gen[4], int flags, long long *d_actions,
+                      float *d_log_probs, float *d_values, float *d_final_values, float *d_logits, void *caller_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -96,6 +96,8 @@ SYMBOLS = (
     "rf_env_step_device_view",
     "rf_env_reset_device_view",
     "rf_rollout_advantages",
+    "rf_policy_params_size",
+    "rf_policy_forward",
     "rf_render_kernel_name",
     "rf_pixels_rendered",
     "rf_allocations_poisoned",
@@ -149,6 +151,18 @@ class EnvRewarder(ctypes.Structure):
     """rf_env_rewarder (include/reinfocus_hip.h)."""
 
     _fields_ = [("kind", ctypes.c_int), ("index0", ctypes.c_int), ("index1", ctypes.c_int), ("p", ctypes.c_double * 3)]
+
+
+class PolicyDesc(ctypes.Structure):
+    """rf_policy_desc (include/reinfocus_hip.h)."""
+
+    _fields_ = [("obs_width", ctypes.c_int), ("n_actions", ctypes.c_int), ("activation", ctypes.c_int),
+                ("pi_layers", ctypes.c_int), ("pi_width", ctypes.c_int * 2), ("vf_layers", ctypes.c_int),
+                ("vf_width", ctypes.c_int * 2)]
+
+    def __init__(self, obs_width=0, n_actions=0, activation=0, pi_layers=0, pi0=0, pi1=0, vf_layers=0, vf0=0, vf1=0):
+        super().__init__(obs_width, n_actions, activation, pi_layers, (ctypes.c_int * 2)(pi0, pi1), vf_layers,
+                         (ctypes.c_int * 2)(vf0, vf1))
 
 
 class EnvProgram(ctypes.Structure):
@@ -310,6 +324,9 @@ def load():
     lib.rf_env_step_device_view.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.rf_env_reset_device_view.argtypes = [vp, vp, vp, vp]
     lib.rf_rollout_advantages.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, ctypes.c_double, ctypes.c_double, vp, vp, vp]
+    lib.rf_policy_params_size.restype = ctypes.c_ulonglong
+    lib.rf_policy_params_size.argtypes = [vp, vp]
+    lib.rf_policy_forward.argtypes = [vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
     lib.rf_render_kernel_name.restype = ctypes.c_char_p
     lib.rf_render_kernel_name.argtypes = [vp]
     lib.rf_pixels_rendered.restype = ctypes.c_ulonglong
@@ -646,6 +663,24 @@ class Context:
         rc = self._lib.rf_rollout_advantages(self._h, steps, num_envs, rewards_ptr, values_ptr, truncated_ptr,
                                              final_values_ptr, last_values_ptr, gamma, gae_lambda, advantages_ptr,
                                              returns_ptr, stream)
+        if rc != 0:
+            _check(rc)
+
+    # --- policy (rf_policy_forward): addresses of device memory as plain integers, nothing waited for -----------------
+    def policy_params_size(self, desc):
+        """rf_policy_params_size: floats of the packed parameters of `desc` (the nine integers of rf_policy_desc in
+        order); 0 for a desc outside the limits."""
+        return int(self._lib.rf_policy_params_size(self._h, ctypes.byref(PolicyDesc(*desc))))
+
+    def policy_forward(self, desc, params_ptr, num_envs, obs_ptr, final_obs_ptr, gen, flags, actions_ptr, log_probs_ptr,
+                       values_ptr, final_values_ptr, logits_ptr, stream):
+        """rf_policy_forward: the actor-critic forward with sampling over device arrays given by address (each output
+        and final_obs_ptr may be None), one launch on `stream` (a hipStream_t as an integer).  desc: the nine integers of
+        rf_policy_desc in order; gen: the generator's four 64-bit words, or None.  Only enqueues."""
+        words = None if gen is None else (ctypes.c_ulonglong * 4)(*gen)
+        rc = self._lib.rf_policy_forward(self._h, ctypes.byref(PolicyDesc(*desc)), params_ptr, num_envs, obs_ptr,
+                                         final_obs_ptr, words, flags, actions_ptr, log_probs_ptr, values_ptr,
+                                         final_values_ptr, logits_ptr, stream)
         if rc != 0:
             _check(rc)
 

@@ -1839,3 +1839,4 @@ class DeviceVectorEnvironment(_DeviceVectorEnv):
 
 
 from reinfocus_amd.environments.rollout import DeviceRollout, Rollout  # noqa: E402,F401 -- the PPO rollout buffers
+from reinfocus_amd.environments.policy import DevicePolicy, MlpPolicySpec, Policy, policy_numpy  # noqa: E402,F401 -- the PPO actor-critic

@@ -1,0 +1,445 @@
+"""PPO's actor-critic for the vector environments: stable-baselines3's MlpPolicy (ActorCriticPolicy with separate pi / vf
+MLPs and a Categorical head) as the reference's PPO configurations (examples/ppo_*.yml) use it for DiscreteSteps-v0 --
+the stage of collection between an observation and the next action, its log-probability, V(obs) and, for the bootstrap
+of a truncated episode, V(final_observation).
+
+One definition of the arithmetic (include/reinfocus_hip.h, "policy"; the scalar functions are csrc/rf_policy_math.h):
+policy_numpy below is its numpy float32 restatement and the oracle; policy_forward_kernel (csrc/rf_policy.h) computes
+the same bits in one launch.  The forward is float32 in a fixed order with the project's own exp32 / log32 -- not
+torch's: that is the one deliberate difference from stable-baselines3.
+
+    MlpPolicySpec  the shape of the network and the packing of its parameters, from and to SB3's state_dict names
+    Policy         the numpy twin: act / values over numpy arrays, draws from numpy's Generator(PCG64DXSM(seed))
+    DevicePolicy   the same methods over torch tensors on a device-resident environment's GPU: one launch per call on
+                   torch's current stream, parameters in one packed tensor, nothing waits for the host
+
+Continuous action spaces (the reference trains ContinuousJumps with gSDE) are out of scope and refused.
+
+torch is imported lazily, by DevicePolicy only (reinfocus_amd/torch_interop.py says why import order matters).
+"""
+
+import numpy as np
+
+from reinfocus_amd.environments import spaces
+
+MAX_WIDTH, MAX_ACTIONS = 256, 64  # RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_ACTIONS
+ACTIVATIONS = {"relu": 0, "tanh": 1}  # RF_POLICY_RELU, RF_POLICY_TANH
+DETERMINISTIC = 1  # RF_POLICY_DETERMINISTIC
+
+f32 = np.float32
+NAN_BITS = 0x7FC00000  # the one NaN the policy ever stores
+_NAN = np.array(NAN_BITS, dtype=np.uint32).view(f32)[()]
+LN2_HI, LN2_LO, LOG2E = f32(0.693359375), f32(-2.12194440e-4), f32(1.44269504)
+SQRT2 = f32(1.41421354)
+_EXP_COEFFICIENTS = tuple(f32(1.0) / f32(d) for d in (5040.0, 720.0, 120.0, 24.0, 6.0))  # then 1/2, 1, 1
+_LOG_COEFFICIENTS = tuple(f32(2.0) / f32(d) for d in (11.0, 9.0, 7.0, 5.0, 3.0))
+
+
+def _bits(x):
+    return np.ascontiguousarray(x, dtype=f32).view(np.uint32)
+
+
+def canonical(x):
+    """x with every NaN replaced by the bit pattern NAN_BITS (what is stored)."""
+    x = np.asarray(x, dtype=f32)
+    return np.where(x != x, _NAN, x)
+
+
+def exp32(x):
+    """rf_policy_math.h exp32, for x <= 0 (and NaN): every operation a numpy float32 operation."""
+    x = np.asarray(x, dtype=f32)
+    with np.errstate(all="ignore"):
+        live = x >= f32(-87.0)
+        xs = np.where(live, x, f32(0.0))  # (the lanes that return 0 compute on 0: no conversion of NaN or -inf)
+        k = (xs * LOG2E - f32(0.5)).astype(np.int32)  # (truncation towards zero, as the C conversion)
+        kf = k.astype(f32)
+        r = (xs - kf * LN2_HI) - kf * LN2_LO
+        p = _EXP_COEFFICIENTS[0]
+        for c in _EXP_COEFFICIENTS[1:]:
+            p = c + r * p
+        p = f32(0.5) + r * p
+        p = f32(1.0) + r * p
+        p = f32(1.0) + r * p
+        scale = np.ascontiguousarray((k + 127) << 23, dtype=np.int32).view(f32)
+        out = np.where(live, p * scale, f32(0.0))
+    assert out.dtype == f32
+    return out
+
+
+def log32(s):
+    """rf_policy_math.h log32, for s in [1, 64]."""
+    s = np.asarray(s, dtype=f32)
+    u = _bits(s)
+    with np.errstate(all="ignore"):
+        e = (u >> 23).astype(np.int32) - 127
+        m = ((u & np.uint32(0x007FFFFF)) | np.uint32(0x3F800000)).view(f32)
+        big = m > SQRT2
+        m = np.where(big, m * f32(0.5), m)
+        e = np.where(big, e + 1, e)
+        f = m - f32(1.0)
+        q = f / (f32(2.0) + f)
+        z = q * q
+        p = _LOG_COEFFICIENTS[0]
+        for c in _LOG_COEFFICIENTS[1:]:
+            p = c + z * p
+        lnm = f32(2.0) * q + q * (z * p)
+        ef = e.astype(f32)
+        out = ef * LN2_HI + (lnm + ef * LN2_LO)
+    assert out.dtype == f32
+    return out.reshape(s.shape)
+
+
+def tanh32(x):
+    """rf_policy_math.h tanh32: sign(x) (1 - t) / (1 + t), t = exp32(-2 |x|); NaN is NaN."""
+    x = np.asarray(x, dtype=f32)
+    u = _bits(x)
+    with np.errstate(all="ignore"):
+        a = (u & np.uint32(0x7FFFFFFF)).view(f32)
+        t = exp32(f32(-2.0) * a)
+        q = (f32(1.0) - t) / (f32(1.0) + t)
+        out = (_bits(q) | (u & np.uint32(0x80000000))).view(f32)
+    return np.where(x != x, _NAN, out.reshape(x.shape))
+
+
+def activation(x, name):
+    if name == "tanh":
+        return tanh32(x)
+    return np.where(x > f32(0.0), x, f32(0.0))  # relu: NaN and -0 become +0
+
+
+def linear(x, weight_t, bias):
+    """y_j = b_j; y_j = y_j + x_k * W[j][k] for k = 0 .. K-1 (x [n, K], weight_t [K, H]: W transposed, bias [H])."""
+    y = np.broadcast_to(bias, (x.shape[0], weight_t.shape[1])).astype(f32)
+    with np.errstate(all="ignore"):
+        for k in range(weight_t.shape[0]):
+            y = y + x[:, k:k + 1] * weight_t[k]
+    assert y.dtype == f32
+    return y
+
+
+def select(c, u):
+    """The sampled index of each row: the first i with double(c_i) > u * double(s), s = c_{A-1}; else the last."""
+    c = np.asarray(c, dtype=f32)
+    above = c.astype(np.float64) > (np.asarray(u, dtype=np.float64) * c[:, -1].astype(np.float64))[:, None]
+    return np.where(above.any(axis=1), above.argmax(axis=1), c.shape[1] - 1).astype(np.int64)
+
+
+def softmax_parts(logits):
+    """(first maximum int64 [n], z = l - m [n, A], partial sums c [n, A], s [n], degenerate bool [n]) of logits."""
+    logits = np.asarray(logits, dtype=f32)
+    n, count = logits.shape
+    with np.errstate(all="ignore"):
+        m = logits[:, 0].copy()
+        first = np.zeros(n, dtype=np.int64)
+        for i in range(1, count):
+            better = logits[:, i] > m
+            m = np.where(better, logits[:, i], m)
+            first = np.where(better, i, first)
+        z = logits - m[:, None]
+        e = exp32(z)
+        c = np.empty((n, count), dtype=f32)
+        s = np.zeros(n, dtype=f32)
+        for i in range(count):
+            s = s + e[:, i]
+            c[:, i] = s
+    return first, z, c, s, ~(s >= f32(1.0))
+
+
+def log_softmax(logits):
+    """log_prob_i = z_i - log32(s) of every action, float32 [n, A]; NaN throughout a degenerate row."""
+    _, z, _, s, degenerate = softmax_parts(logits)
+    with np.errstate(all="ignore"):
+        out = z - log32(np.where(degenerate, f32(1.0), s))[:, None]
+    return np.where(degenerate[:, None], _NAN, canonical(out))
+
+
+def head(logits, u=None):
+    """(actions int64, log_probs float32) of logits [n, A]; u float64 [n] samples, None takes the first maximum."""
+    first, z, c, s, degenerate = softmax_parts(logits)
+    with np.errstate(all="ignore"):
+        actions = first if u is None else np.where(degenerate, first, select(c, u))
+        log_probs = z[np.arange(len(s)), actions] - log32(np.where(degenerate, f32(1.0), s))
+        log_probs = np.where(degenerate, _NAN, canonical(log_probs))
+    assert log_probs.dtype == f32
+    return actions.astype(np.int64), log_probs
+
+
+class MlpPolicySpec:
+    """The shape of the network and the packing rule of its parameters.  Packed: one float32 vector, every matrix
+    transposed ([in][out]), pi first: W0^T, b0, (W1^T, b1,) Wa^T, ba, then vf alike with the value head."""
+
+    def __init__(self, obs_width, n_actions, pi=(64, 64), vf=(64, 64), activation="tanh"):
+        self.obs_width, self.n_actions = int(obs_width), int(n_actions)
+        self.pi, self.vf = tuple(int(w) for w in pi), tuple(int(w) for w in vf)
+        self.activation = activation
+        if activation not in ACTIVATIONS:
+            raise ValueError(f"activation {activation!r} is not one of {sorted(ACTIVATIONS)}")
+        if not 1 <= self.obs_width <= MAX_WIDTH:
+            raise ValueError(f"obs_width {obs_width} is not in 1 .. {MAX_WIDTH}")
+        if not 2 <= self.n_actions <= MAX_ACTIONS:
+            raise ValueError(f"n_actions {n_actions} is not in 2 .. {MAX_ACTIONS}")
+        for name, widths in (("pi", self.pi), ("vf", self.vf)):
+            if len(widths) not in (1, 2) or not all(1 <= w <= MAX_WIDTH for w in widths):
+                raise ValueError(f"{name}={widths!r} is not 1 or 2 hidden layers of width 1 .. {MAX_WIDTH}")
+        self.entries = []  # (state_dict name, packed offset, packed shape, is a weight)
+        at = 0
+        for widths, extractor, head_name, outputs in ((self.pi, "policy_net", "action_net", self.n_actions),
+                                                      (self.vf, "value_net", "value_net", 1)):
+            fan_in = self.obs_width
+            names = [f"mlp_extractor.{extractor}.{2 * i}" for i in range(len(widths))] + [head_name]
+            for name, out in zip(names, widths + (outputs,)):
+                self.entries.append((name + ".weight", at, (fan_in, out), True))
+                at += fan_in * out
+                self.entries.append((name + ".bias", at, (out,), False))
+                at += out
+                fan_in = out
+        self.size = at
+
+    def desc(self):
+        """The fields of rf_policy_desc, in order."""
+        pad = lambda w: list(w) + [0] * (2 - len(w))  # noqa: E731
+        return (self.obs_width, self.n_actions, ACTIVATIONS[self.activation], len(self.pi), *pad(self.pi), len(self.vf),
+                *pad(self.vf))
+
+    def keys(self):
+        return [entry[0] for entry in self.entries]
+
+    def checked(self, state_dict, shape_of):
+        """The entries with their tensors; KeyError / ValueError for a state_dict that is not this network's."""
+        missing = [name for name in self.keys() if name not in state_dict]
+        extra = [name for name in state_dict if name not in self.keys()]
+        if missing or extra:
+            raise KeyError(f"not the state_dict of this network: missing {missing}, unknown {extra}")
+        for name, _, shape, is_weight in self.entries:
+            want = shape[::-1] if is_weight else shape  # (SB3 holds weights [out][in])
+            if tuple(shape_of(state_dict[name])) != want:
+                raise ValueError(f"{name} has shape {tuple(shape_of(state_dict[name]))}, not {want}")
+        return self.entries
+
+    def pack(self, state_dict):
+        """The packed float32 vector of a state_dict of arrays (SB3's names and shapes)."""
+        params = np.zeros(self.size, dtype=f32)
+        for name, at, shape, is_weight in self.checked(state_dict, np.shape):
+            value = np.asarray(state_dict[name], dtype=f32)
+            params[at:at + value.size] = (value.T if is_weight else value).reshape(-1)
+        return params
+
+    def unpack(self, params):
+        """The state_dict (numpy arrays in SB3's shapes) of a packed vector."""
+        params = np.asarray(params, dtype=f32).reshape(self.size)
+        return {name: (params[at:at + int(np.prod(shape))].reshape(shape).T.copy() if is_weight
+                       else params[at:at + shape[0]].copy()) for name, at, shape, is_weight in self.entries}
+
+    def nets(self, params):
+        """((pi layers, pi head), (vf layers, vf head)): each layer (weight_t [in, out], bias [out]) as views."""
+        params = np.asarray(params, dtype=f32).reshape(self.size)
+        views = [params[at:at + int(np.prod(shape))].reshape(shape) for _, at, shape, _ in self.entries]
+        layers = list(zip(views[0::2], views[1::2]))
+        split = len(self.pi) + 1
+        return (layers[:split - 1], layers[split - 1]), (layers[split:-1], layers[-1])
+
+
+def _refuse_box(action_space):
+    if not isinstance(action_space, spaces.Discrete):
+        raise ValueError(f"the policy has a Categorical head over a Discrete action space, not {action_space!r}: "
+                         "continuous action spaces (the reference trains ContinuousJumps with gSDE) are out of scope")
+
+
+def _net(spec, net, x):
+    layers, last = net
+    for weight_t, bias in layers:
+        x = activation(linear(x, weight_t, bias), spec.activation)
+    return linear(x, *last)
+
+
+def policy_numpy(spec, params, obs, final_obs=None, u=None, deterministic=False, values_only=False):
+    """The definition, literally.  obs float32 [n, D], final_obs float32 [n, D] or None, u float64 [n] (the draws of a
+    sampled call).  Returns a dict: "logits" float32 [n, A], "actions" int64 [n], "log_probs" float32 [n] (both None
+    with values_only), "values" float32 [n], "final_values" float32 [n] or None."""
+    obs = np.asarray(obs, dtype=f32).reshape(-1, spec.obs_width)
+    pi, vf = spec.nets(params)
+    out = {"values": canonical(_net(spec, vf, obs)[:, 0]), "final_values": None, "logits": None, "actions": None,
+           "log_probs": None}
+    if final_obs is not None:
+        final_obs = np.asarray(final_obs, dtype=f32).reshape(obs.shape)
+        lead = final_obs[:, 0]
+        out["final_values"] = np.where(lead != lead, _NAN, canonical(_net(spec, vf, final_obs)[:, 0]))
+    if not values_only:
+        logits = _net(spec, pi, obs)
+        if not deterministic and u is None:
+            raise ValueError("a sampled call needs its draws u")
+        out["actions"], out["log_probs"] = head(logits, None if deterministic else u)
+        out["logits"] = canonical(logits)
+    return out
+
+
+def generator_words(bit_generator):
+    """(state low, state high, inc low, inc high) of a numpy PCG64DXSM bit generator: rf_policy_forward's gen."""
+    state = bit_generator.state["state"]
+    mask = (1 << 64) - 1
+    return (state["state"] & mask, state["state"] >> 64, state["inc"] & mask, state["inc"] >> 64)
+
+
+class _Draws:
+    """numpy's Generator(PCG64DXSM(seed)): a sampled call of n consumes exactly n of its random() draws."""
+
+    def _seed(self, seed):
+        self._bit_generator = np.random.PCG64DXSM(seed)
+        self._generator = np.random.Generator(self._bit_generator)
+
+    def rng_state(self):
+        return self._bit_generator.state
+
+    def set_rng_state(self, state):
+        self._bit_generator.state = state
+
+
+class Policy(_Draws):
+    """The numpy twin of DevicePolicy, and its oracle.  Parameters start at zero (a uniform policy, V = 0)."""
+
+    def __init__(self, spec, seed=None):
+        self.spec = spec
+        self.params = np.zeros(spec.size, dtype=f32)
+        self._seed(seed)
+
+    def load_state_dict(self, state_dict):
+        self.params = self.spec.pack(state_dict)
+
+    def state_dict(self):
+        return self.spec.unpack(self.params)
+
+    def act(self, obs, final_obs=None, deterministic=False):
+        """(actions int64 [n], values, log_probs, final_values or None)."""
+        obs = np.asarray(obs, dtype=f32).reshape(-1, self.spec.obs_width)
+        u = None if deterministic else self._generator.random(obs.shape[0])
+        got = policy_numpy(self.spec, self.params, obs, final_obs, u, deterministic)
+        return got["actions"], got["values"], got["log_probs"], got["final_values"]
+
+    def values(self, obs, final_obs=None):
+        """V(obs); with final_obs (V(obs), V(final_obs) -- NaN where final_obs[e][0] is NaN).  No draw is consumed."""
+        got = policy_numpy(self.spec, self.params, obs, final_obs, values_only=True)
+        return got["values"] if final_obs is None else (got["values"], got["final_values"])
+
+
+class DevicePolicy(_Draws):
+    """The policy of a device-resident environment (DeviceVectorDiscreteSteps, or a DeviceVectorEnvironment with a
+    Discrete action space), over torch tensors on the environment's GPU; used as Policy is and bit for bit equal to it.
+
+    Every act() / values() is ONE launch of policy_forward_kernel (rf_policy_forward) on torch's current stream; the
+    generator lives on the host, is advanced there exactly, and its four words travel by value, so nothing waits for
+    the host and nothing races.  `params` is one packed float32 tensor the policy owns; load_state_dict takes device
+    tensors and is transposes and copies on the current stream -- what a learner calls after each update.  Without out=
+    the results are tensors the policy owns and the next call overwrites."""
+
+    def __init__(self, env, spec, seed=None):
+        from reinfocus_amd.environments import harness
+
+        if not isinstance(env, harness._DeviceVectorEnv):
+            if hasattr(env, "_no_tensors"):  # (a sharded environment: its own refusal says why)
+                env._no_tensors()
+            raise TypeError(f"DevicePolicy needs a device-resident environment, not {type(env).__name__} (the numpy "
+                            "twins have Policy)")
+        _refuse_box(env.single_action_space)
+        if env.single_action_space.n != spec.n_actions:
+            raise ValueError(f"the spec has {spec.n_actions} actions, the environment {env.single_action_space.n}")
+        self._io = env._tensor_io()  # (ValueError, as step_tensors': a host initializer, a render_mode)
+        from reinfocus_amd import torch_interop
+
+        self._interop = torch_interop
+        torch = self._torch = torch_interop._torch()
+        self.spec = spec
+        self._ctx = env._ctx
+        self.device = torch.device("cuda", self._ctx.device)
+        self.params = torch.zeros(spec.size, dtype=torch.float32, device=self.device)
+        self._owned = {}
+        self._seed(seed)
+
+    def load_state_dict(self, state_dict):
+        torch = self._torch
+        for name in state_dict:
+            tensor = state_dict[name]
+            if not isinstance(tensor, torch.Tensor) or tensor.dtype != torch.float32:
+                raise TypeError(f"{name} must be a torch.float32 tensor on {self.device}")
+            self._io._on_device(tensor, name)
+        with torch.no_grad():
+            for name, at, shape, is_weight in self.spec.checked(state_dict, lambda t: t.shape):
+                tensor = state_dict[name].detach()
+                cells = tensor.numel()
+                self.params[at:at + cells].view(shape).copy_(tensor.t() if is_weight else tensor)
+
+    def state_dict(self):
+        """Device tensors in SB3's names and shapes (copies)."""
+        out = {}
+        for name, at, shape, is_weight in self.spec.entries:
+            view = self.params[at:at + int(np.prod(shape))].view(shape)
+            out[name] = view.t().contiguous() if is_weight else view.clone()
+        return out
+
+    def _rows(self, tensor, what):
+        torch = self._torch
+        if not isinstance(tensor, torch.Tensor):
+            raise TypeError(f"{what} must be a torch.Tensor on {self.device}, not {type(tensor).__name__}")
+        self._io._on_device(tensor, what)
+        if tensor.dtype != torch.float32 or tensor.dim() != 2 or tensor.shape[1] != self.spec.obs_width:
+            raise ValueError(f"{what} is {tensor.dtype} {tuple(tensor.shape)}, not torch.float32 (n, {self.spec.obs_width})")
+        if not tensor.is_contiguous():
+            raise ValueError(f"{what} is not contiguous")
+        return tensor
+
+    def _out(self, name, given, n, dtype):
+        torch = self._torch
+        if given is None:
+            owned = self._owned.get(name)
+            if owned is None or owned.numel() != n:
+                owned = self._owned[name] = torch.empty(n, dtype=dtype, device=self.device)
+            return owned
+        if not isinstance(given, torch.Tensor):
+            raise TypeError(f"out {name} must be a torch.Tensor, not {type(given).__name__}")
+        self._io._on_device(given, "out " + name)
+        if given.dtype != dtype or tuple(given.shape) != (n,) or not given.is_contiguous():
+            raise ValueError(f"out {name} is {given.dtype} {tuple(given.shape)}, not contiguous {dtype} ({n},)")
+        return given
+
+    def _forward(self, obs, final_obs, gen, flags, actions, log_probs, values, final_values):
+        self._interop.check_one_runtime()
+        pointer = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        self._ctx.policy_forward(self.spec.desc(), self.params.data_ptr(), obs.shape[0], obs.data_ptr(),
+                                 pointer(final_obs), gen, flags, pointer(actions), pointer(log_probs), pointer(values),
+                                 pointer(final_values), None, self._io._stream())
+
+    def act(self, obs, final_obs=None, deterministic=False, out=None):
+        """(actions int64 [n], values, log_probs, final_values or None) of obs float32 [n, D] (and final_obs alike);
+        out=(actions, values, log_probs, final_values or None) writes into the caller's rows.  One launch; a sampled
+        call advances the host generator by n."""
+        torch = self._torch
+        obs = self._rows(obs, "obs")
+        n = obs.shape[0]
+        if final_obs is not None and self._rows(final_obs, "final_obs").shape != obs.shape:
+            raise ValueError(f"final_obs has shape {tuple(final_obs.shape)}, obs {tuple(obs.shape)}")
+        given = (None,) * 4 if out is None else tuple(out)
+        if len(given) != 4:
+            raise TypeError("out must be (actions, values, log_probs, final_values or None)")
+        actions = self._out("actions", given[0], n, torch.int64)
+        values = self._out("values", given[1], n, torch.float32)
+        log_probs = self._out("log_probs", given[2], n, torch.float32)
+        final_values = None if final_obs is None else self._out("final_values", given[3], n, torch.float32)
+        gen = None if deterministic else generator_words(self._bit_generator)
+        self._forward(obs, final_obs, gen, DETERMINISTIC if deterministic else 0, actions, log_probs, values, final_values)
+        if not deterministic:
+            self._bit_generator.advance(n)  # (after the call was taken: a refused call consumes nothing)
+        return actions, values, log_probs, final_values
+
+    def values(self, obs, final_obs=None, out=None):
+        """V(obs); with final_obs (V(obs), V(final_obs)).  out=(values, final_values or None).  One launch, no draw."""
+        torch = self._torch
+        obs = self._rows(obs, "obs")
+        n = obs.shape[0]
+        if final_obs is not None and self._rows(final_obs, "final_obs").shape != obs.shape:
+            raise ValueError(f"final_obs has shape {tuple(final_obs.shape)}, obs {tuple(obs.shape)}")
+        given = (None, None) if out is None else tuple(out)
+        if len(given) != 2:
+            raise TypeError("out must be (values, final_values or None)")
+        values = self._out("last_values", given[0], n, torch.float32)
+        final_values = None if final_obs is None else self._out("final_values", given[1], n, torch.float32)
+        self._forward(obs, final_obs, None, 0, None, None, values, final_values)
+        return values if final_obs is None else (values, final_values)

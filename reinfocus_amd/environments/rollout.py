@@ -15,6 +15,10 @@ restatement and the oracle; rollout_gae_kernel (csrc/rf_rollout.h) computes the 
                    writes its results into the buffer's slabs (step_tensors(out=...)), finish() is one kernel launch,
                    and nothing waits for the host
 
+collect(policy) runs a whole rollout with a policy of environments/policy.py (Policy for Rollout, DevicePolicy for
+DeviceRollout): on the device a step is then one policy launch, which writes rows of the slabs, and the environment's
+step from those rows.
+
 torch is imported lazily, by DeviceRollout only (reinfocus_amd/torch_interop.py says why import order matters).
 """
 
@@ -114,6 +118,13 @@ class _Bookkeeping:
         self._complete = True
         return self._bootstrapped == self.n_steps
 
+    def _collecting(self):
+        if self._t != 0:
+            raise ValueError("collect() runs a whole rollout: start() first, and take no step() before it")
+        if not _index_task(self.env):
+            raise ValueError("collect() takes a policy with a Categorical head, and the environment's action space is "
+                             f"{self.env.single_action_space!r}: continuous action spaces are out of scope")
+
     def _finished(self):
         if not (self._complete and self._t == self.n_steps):
             raise ValueError("the rollout is not finished: advantages and returns are those of finish()")
@@ -166,6 +177,24 @@ class Rollout(_Bookkeeping):
         self.advantages, self.returns = gae_numpy(self.rewards, self.values, self.truncated, final_values, last_values,
                                                   self.gamma, self.gae_lambda)
         return self.advantages, self.returns
+
+    def collect(self, policy, deterministic=False):
+        """The whole rollout after start(), by a policy.Policy: act, step and -- with episode records -- the bootstrap
+        of every step, then finish(V(observations[T])).  V(final_observation) of step t - 1 comes from the act of step t
+        (the last one from the values-only call that gives last_values).  Equal to the explicit loop."""
+        self._collecting()
+        final_obs = None
+        for t in range(self.n_steps):
+            actions, values, log_probs, final_values = policy.act(self.observations[t], final_obs, deterministic)
+            if final_obs is not None:
+                self.bootstrap(final_values)
+            info = self.step(actions, values, log_probs)[4]
+            final_obs = info["final_observation"] if self._records else None
+        if final_obs is None:
+            return self.finish(policy.values(self.observations[self.n_steps]))
+        last_values, final_values = policy.values(self.observations[self.n_steps], final_obs)
+        self.bootstrap(final_values)
+        return self.finish(last_values)
 
     def flat(self):
         """The rollout as stable-baselines3's swap_and_flatten orders it: index e * T + t."""
@@ -225,6 +254,7 @@ class DeviceRollout(_Bookkeeping):
         self.truncated = slab(torch.uint8)
         self.values, self.log_probs, self.final_values, self.advantages, self.returns = (
             slab(torch.float32) for _ in range(5))
+        self._last_values = None  # (collect()'s V(observations[T]), made on first use)
 
     def _row(self, tensor, what):
         """`tensor` as a float32-or-whatever [n] row on the buffer's GPU (a view, never a host copy)."""
@@ -275,6 +305,30 @@ class DeviceRollout(_Bookkeeping):
                                      last_values.data_ptr(), self.gamma, self.gae_lambda, self.advantages.data_ptr(),
                                      self.returns.data_ptr(), self._io._stream())
         return self.advantages, self.returns
+
+    def collect(self, policy, deterministic=False):
+        """The whole rollout after start(), by a policy.DevicePolicy: per step ONE policy launch, which writes
+        actions[t], values[t], log_probs[t] and -- with episode records, from the final_observation of the step before
+        -- final_values[t - 1] straight into the slabs (no row copies), and the environment's step from actions[t];
+        after step T a values-only launch gives last_values and final_values[T - 1]; then finish().  As bytes what the
+        explicit loop of act / step / bootstrap / finish gives, and Rollout.collect with the twin policy.  Nothing
+        waits for the host."""
+        self._collecting()
+        final_obs = None
+        for _ in range(self.n_steps):
+            t = self._next_step()
+            final_out = None if final_obs is None else self.final_values[self._bootstrap_step()]
+            policy.act(self.observations[t], final_obs, deterministic,
+                       out=(self.actions[t], self.values[t], self.log_probs[t], final_out))
+            info = self.env.step_tensors(self.actions[t],
+                                         out=(self.observations[t + 1], self.rewards[t], self.truncated[t]))[4]
+            self._t = t + 1
+            final_obs = info["final_observation"] if self._records else None
+        if self._last_values is None:
+            self._last_values = self._torch.zeros(self.num_envs, dtype=self._torch.float32, device=self.device)
+        final_out = None if final_obs is None else self.final_values[self._bootstrap_step()]
+        policy.values(self.observations[self.n_steps], final_obs, out=(self._last_values, final_out))
+        return self.finish(self._last_values)
 
     def flat(self):
         """The rollout as stable-baselines3's swap_and_flatten orders it: index e * T + t.  The slabs are [T][n] (lanes
