@@ -853,6 +853,84 @@ int rf_policy_forward(rf_ctx *ctx, const rf_policy_desc *desc, const float *d_pa
                       const float *d_final_obs, const unsigned long long gen[4], int flags, long long *d_actions,
                       float *d_log_probs, float *d_values, float *d_final_values, float *d_logits, void *caller_stream);
 
+/* ---- ppo update: one PPO minibatch update on the device: loss, backward, clip, Adam ---------------------------------------
+ * The other half of training in the reference's PPO configurations is stable-baselines3's PPO.train(): per minibatch the
+ * clipped surrogate loss, the value loss and the entropy bonus of the actor-critic of "policy" above, their gradient,
+ * clip_grad_norm_ and one Adam step.  No reference counterpart.  Needs no environment: the context only says which GPU.
+ *
+ * One definition, numpy twin (environments/learner.py ppo_update_numpy), host build (tests/ppocheck) and kernels
+ * (csrc/rf_ppo.h) alike.  Everything is float32, left to right, one rounding per operation, nothing contracted, unless a
+ * step says float64; no MFMA; every reduction has a fixed order.  treesum is the learner view's, above.
+ *
+ * Inputs.  Arrays of N rows (what a rollout's flat() holds): obs float32[N][D], actions int64[N], old_log_probs,
+ * advantages, returns float32[N]; index int64[B], 1 <= B <= RF_PPO_MAX_BATCH: sample b of the minibatch is row
+ * index[b], repeats allowed.  rf_ppo_desc holds the hyper-parameters, by value per call.
+ *  1 Validity.  invalid = some index[b] outside [0, N) or some actions[row] outside [0, A).  Every gather uses
+ *    row = clamp(index[b], 0, N - 1) and a = clamp(actions[row], 0, A - 1): no address outside the arrays is formed.
+ *  2 Advantages.  With normalize_advantage and B > 1: mean = treesum(adv) / B, var = treesum((adv - mean) * (adv - mean))
+ *    / (B - 1), float64 (adv converted exactly); A_b = float32((double(adv_b) - mean) / (sqrt(var) + 1e-8)).  Otherwise
+ *    A_b = adv_b.
+ *  3 Forward.  Both nets of "policy" on obs[row]: linear layers, activation, and for the logits l: m = the first maximum,
+ *    z_i = l_i - m, e_i = exp32(z_i), s the sequential sum of e from +0; lse = log32(s), or NaN where not s >= 1 (a
+ *    degenerate row: it ends in RF_PPO_NONFINITE); logp_i = z_i - lse, p_i = e_i / s.
+ *    H_b = -(sum over i in index order, from +0, of (e_i == 0 ? +0 : p_i * logp_i)).
+ *  4 Loss terms, a as above: d = logp_a - old_log_probs[row]; ratio = d <= 0 ? exp32(d) : 1.0f / exp32(-d);
+ *    c = float32(clip_range), lo = 1.0f - c, hi = 1.0f + c; cl = ratio < lo ? lo : (ratio > hi ? hi : ratio);
+ *    surr1 = A_b * ratio, surr2 = A_b * cl; pg_b = -(surr2 < surr1 ? surr2 : surr1); t = ret - v, vl_b = t * t;
+ *    kl_b = (ratio - 1.0f) - d; r1 = ratio - 1.0f, clipped_b = (r1 < 0 ? -r1 : r1) > c ? 1.0f : 0.0f.
+ *  5 Head gradients (torch's subgradient of min and clamp): g_b = surr1 if (ratio >= lo and ratio <= hi) or
+ *    surr1 < surr2, else +0; Bf = float32(B), ec = float32(ent_coef), vc2 = float32(vf_coef) * 2.0f;
+ *    dlogit_i = ((-g_b) * ((i == a ? 1.0f : 0.0f) - p_i) + (e_i == 0 ? +0 : (ec * p_i) * (logp_i + H_b))) / Bf;
+ *    dv_b = (vc2 * (v - ret)) / Bf.
+ *  6 Backward.  For a layer with outputs o and inputs k (a hidden activation h_k):
+ *    delta_in[k] = act'(h_k) * (sum over o in index order, from +0, of W[o][k] * delta_out[o]) -- a multiply, then an add;
+ *    act' = 1.0f - h * h for tanh, h > 0 ? 1.0f : 0.0f for ReLU (the multiply by it is always performed).
+ *  7 Parameter gradients, in the packed layout: dW[k][j] = sum over b = 0 .. B-1, from +0, of x[b][k] * delta[b][j] (a
+ *    multiply, then an add); db[j] = the same sum of delta[b][j].
+ *  8 Clip.  norm = sqrt(treesum over the P packed gradients of double(g) * double(g)), float64.  (The kernels take the
+ *    tree in two levels, aligned blocks of 256 leaves first: the same tree.)  If invalid, or norm is not finite
+ *    (RF_PPO_NONFINITE -- a deliberate difference from SB3, which would write NaN into every parameter), the update
+ *    changes nothing.  Otherwise q = max_grad_norm / (norm + 1e-6), coef = float32(q < 1.0 ? q : 1.0), g = g * coef
+ *    (always applied, as clip_grad_norm_ does).
+ *  9 Adam (torch's, no weight decay, no amsgrad).  State: a header {step int64, bc1 float64, bc2 float64, 0} of 32 bytes,
+ *    then m float32[P], v float32[P]; all zero is a fresh optimizer.  bc1' = 1.0 - beta1 * (1.0 - bc1), bc2' alike
+ *    (bc = 1 - beta^step without pow), step' = step + 1.  b1 = float32(beta1), ob1 = float32(1.0 - beta1), b2, ob2 alike;
+ *    m = b1 * m + ob1 * g;  v = b2 * v + ob2 * (g * g);  denom = sqrt32(v) / float32(sqrt(bc2')) + float32(adam_eps);
+ *    p = p - float32(learning_rate / bc1') * (m / denom).  Deliberate differences from torch: the running bc and this
+ *    order in place of lerp / addcdiv.
+ * 10 Stats float32[8]: [0..4] = float32(treesum over b / B) of pg, vl, H, kl, clipped (float64 sums of the float32
+ *    terms); [5] = float32(norm) before clipping; [6] = (stats[0] + ec * (-stats[2])) + float32(vf_coef) * stats[1];
+ *    [7] = 0, RF_PPO_INVALID (which takes precedence) or RF_PPO_NONFINITE as a number.  Stored NaNs are 0x7fc00000.  A
+ *    skipped update still writes the stats; parameters, m, v and the header keep their bytes.
+ *
+ *   rf_ppo_state_size      bytes of the optimizer state of desc (32 + 8 P); 0 for a desc outside the limits or NULL ctx
+ *   rf_ppo_workspace_size  bytes of the workspace for minibatches up to max_batch (1 .. RF_PPO_MAX_BATCH); 0 if refused
+ *   rf_ppo_update          three launches on caller_stream, nothing allocated, nothing waited for; d_params, d_state and
+ *                          d_stats (float32[8]) are updated in place, d_workspace is scratch.  Refused (RF_ERR_INVALID,
+ *                          nothing enqueued, no device pointer dereferenced): a desc outside the limits; N < 1; B outside
+ *                          1 .. RF_PPO_MAX_BATCH; a negative or non-finite hyper-parameter, a beta outside [0, 1); a NULL
+ *                          array, one the runtime does not vouch for on the ctx's GPU (a host pointer, a misaligned one --
+ *                          state and workspace to 8 bytes --, one that ends past its allocation: that is how a state or
+ *                          workspace that is too small shows, where the allocation is the caller's own), exactly as for
+ *                          device io; an output (params, state, workspace, stats) that overlaps an input or another
+ *                          output; a capturing caller stream.  The workspace needs rf_ppo_workspace_size(B) bytes. */
+#define RF_PPO_MAX_BATCH 1024
+#define RF_PPO_INVALID 1
+#define RF_PPO_NONFINITE 2
+
+typedef struct rf_ppo_desc {
+    double learning_rate, clip_range, ent_coef, vf_coef, max_grad_norm, beta1, beta2, adam_eps;
+    int normalize_advantage; /* 0 / 1 */
+    int reserved;            /* 0 */
+} rf_ppo_desc;
+
+unsigned long long rf_ppo_state_size(rf_ctx *ctx, const rf_policy_desc *policy);
+unsigned long long rf_ppo_workspace_size(rf_ctx *ctx, const rf_policy_desc *policy, int max_batch);
+int rf_ppo_update(rf_ctx *ctx, const rf_policy_desc *policy, const rf_ppo_desc *ppo, float *d_params, void *d_state,
+                  void *d_workspace, int N, const float *d_obs, const long long *d_actions, const float *d_old_log_probs,
+                  const float *d_advantages, const float *d_returns, int B, const long long *d_index, float *d_stats,
+                  void *caller_stream);
+
 #ifdef __cplusplus
 }
 #endif

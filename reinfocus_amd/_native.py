@@ -98,6 +98,9 @@ SYMBOLS = (
     "rf_rollout_advantages",
     "rf_policy_params_size",
     "rf_policy_forward",
+    "rf_ppo_state_size",
+    "rf_ppo_workspace_size",
+    "rf_ppo_update",
     "rf_render_kernel_name",
     "rf_pixels_rendered",
     "rf_allocations_poisoned",
@@ -163,6 +166,15 @@ class PolicyDesc(ctypes.Structure):
     def __init__(self, obs_width=0, n_actions=0, activation=0, pi_layers=0, pi0=0, pi1=0, vf_layers=0, vf0=0, vf1=0):
         super().__init__(obs_width, n_actions, activation, pi_layers, (ctypes.c_int * 2)(pi0, pi1), vf_layers,
                          (ctypes.c_int * 2)(vf0, vf1))
+
+
+class PpoDesc(ctypes.Structure):
+    """rf_ppo_desc (include/reinfocus_hip.h): the hyper-parameters of one update, by value per call."""
+
+    _fields_ = [("learning_rate", ctypes.c_double), ("clip_range", ctypes.c_double), ("ent_coef", ctypes.c_double),
+                ("vf_coef", ctypes.c_double), ("max_grad_norm", ctypes.c_double), ("beta1", ctypes.c_double),
+                ("beta2", ctypes.c_double), ("adam_eps", ctypes.c_double), ("normalize_advantage", ctypes.c_int),
+                ("reserved", ctypes.c_int)]
 
 
 class EnvProgram(ctypes.Structure):
@@ -327,6 +339,11 @@ def load():
     lib.rf_policy_params_size.restype = ctypes.c_ulonglong
     lib.rf_policy_params_size.argtypes = [vp, vp]
     lib.rf_policy_forward.argtypes = [vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
+    lib.rf_ppo_state_size.restype = ctypes.c_ulonglong
+    lib.rf_ppo_state_size.argtypes = [vp, vp]
+    lib.rf_ppo_workspace_size.restype = ctypes.c_ulonglong
+    lib.rf_ppo_workspace_size.argtypes = [vp, vp, i32]
+    lib.rf_ppo_update.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp]
     lib.rf_render_kernel_name.restype = ctypes.c_char_p
     lib.rf_render_kernel_name.argtypes = [vp]
     lib.rf_pixels_rendered.restype = ctypes.c_ulonglong
@@ -681,6 +698,27 @@ class Context:
         rc = self._lib.rf_policy_forward(self._h, ctypes.byref(PolicyDesc(*desc)), params_ptr, num_envs, obs_ptr,
                                          final_obs_ptr, words, flags, actions_ptr, log_probs_ptr, values_ptr,
                                          final_values_ptr, logits_ptr, stream)
+        if rc != 0:
+            _check(rc)
+
+    # --- ppo update (rf_ppo_update): addresses of device memory as plain integers, nothing waited for -----------------
+    def ppo_state_size(self, desc):
+        """rf_ppo_state_size: bytes of the optimizer state (header, m, v) of the network `desc`; 0 if refused."""
+        return int(self._lib.rf_ppo_state_size(self._h, ctypes.byref(PolicyDesc(*desc))))
+
+    def ppo_workspace_size(self, desc, max_batch):
+        """rf_ppo_workspace_size: bytes of the workspace for minibatches of up to max_batch samples; 0 if refused."""
+        return int(self._lib.rf_ppo_workspace_size(self._h, ctypes.byref(PolicyDesc(*desc)), max_batch))
+
+    def ppo_update(self, desc, hyper, params_ptr, state_ptr, workspace_ptr, rows, obs_ptr, actions_ptr, old_log_probs_ptr,
+                   advantages_ptr, returns_ptr, batch, index_ptr, stats_ptr, stream):
+        """rf_ppo_update: one PPO minibatch update (loss, backward, clip, Adam) over device arrays given by address,
+        three launches on `stream`.  desc: the nine integers of rf_policy_desc; hyper: the nine values of rf_ppo_desc in
+        order (learning_rate, clip_range, ent_coef, vf_coef, max_grad_norm, beta1, beta2, adam_eps,
+        normalize_advantage).  Only enqueues."""
+        rc = self._lib.rf_ppo_update(self._h, ctypes.byref(PolicyDesc(*desc)), ctypes.byref(PpoDesc(*hyper)), params_ptr,
+                                     state_ptr, workspace_ptr, rows, obs_ptr, actions_ptr, old_log_probs_ptr,
+                                     advantages_ptr, returns_ptr, batch, index_ptr, stats_ptr, stream)
         if rc != 0:
             _check(rc)
 

@@ -11,6 +11,7 @@
 #include "rf_env_io.h"
 #include "rf_env_view.h"
 #include "rf_policy.h"
+#include "rf_ppo.h"
 #include "rf_rollout.h"
 
 using namespace rfh;
@@ -2008,6 +2009,98 @@ int rf_policy_forward(rf_ctx *ctx, const rf_policy_desc *desc, const float *d_pa
     hipLaunchKernelGGL(rf::policy_forward_kernel, dim3(tiles, pi && vf ? 2u : 1u), dim3(rf::kPolicyThreads), 0,
                        (hipStream_t)caller_stream, layout, d_params, n, d_obs, d_final_obs, words, sampled ? 1 : 0,
                        pi ? 0 : 1, (int64_t *)d_actions, d_log_probs, d_values, d_final_values, d_logits);
+    RF_HIP(hipGetLastError());
+    return RF_OK;
+}
+
+unsigned long long rf_ppo_state_size(rf_ctx *ctx, const rf_policy_desc *policy)
+{
+    rf::PolicyLayout layout;
+    if (ctx == nullptr || policy == nullptr || !rf::policy_layout(*policy, layout))
+        return 0;
+    if (hipSetDevice(ctx->device) != hipSuccess) // (as every entry point; nothing of the device is needed)
+        (void)hipGetLastError();
+    return 4ull * rf::kPpoStateHeader + 8ull * layout.total;
+}
+
+unsigned long long rf_ppo_workspace_size(rf_ctx *ctx, const rf_policy_desc *policy, int max_batch)
+{
+    rf::PolicyLayout layout;
+    rf::PpoWork work;
+    if (ctx == nullptr || policy == nullptr || !rf::policy_layout(*policy, layout) || !rf::ppo_work(layout, max_batch, work))
+        return 0;
+    if (hipSetDevice(ctx->device) != hipSuccess)
+        (void)hipGetLastError();
+    return 4ull * work.total;
+}
+
+int rf_ppo_update(rf_ctx *ctx, const rf_policy_desc *policy, const rf_ppo_desc *ppo, float *d_params, void *d_state,
+                  void *d_workspace, int N, const float *d_obs, const long long *d_actions, const float *d_old_log_probs,
+                  const float *d_advantages, const float *d_returns, int B, const long long *d_index, float *d_stats,
+                  void *caller_stream)
+{
+    const char *fn = "rf_ppo_update";
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", fn);
+    RF_REQUIRE(policy && ppo && d_params && d_state && d_workspace && d_obs && d_actions && d_old_log_probs && d_advantages
+               && d_returns && d_index && d_stats, "%s: NULL argument", fn);
+    rf::PolicyLayout layout;
+    RF_REQUIRE(rf::policy_layout(*policy, layout),
+               "%s: the desc is outside the limits (obs_width 1 .. %d, 1 or 2 hidden layers of width 1 .. %d per net, "
+               "n_actions 2 .. %d, activation RF_POLICY_RELU or RF_POLICY_TANH)", fn, RF_POLICY_MAX_WIDTH,
+               RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_ACTIONS);
+    RF_REQUIRE(N >= 1 && N <= (1 << 30), "%s: N = %d must be at least 1 (and at most 2^30)", fn, N);
+    RF_REQUIRE(B >= 1 && B <= RF_PPO_MAX_BATCH, "%s: B = %d is not in 1 .. %d", fn, B, RF_PPO_MAX_BATCH);
+    rf::PpoHyper hyper;
+    RF_REQUIRE(rf::ppo_hyper(*ppo, hyper), "%s: a hyper-parameter is negative or not finite, a beta is outside [0, 1) or "
+               "normalize_advantage is not 0 / 1", fn);
+    rf::PpoWork work;
+    RF_REQUIRE(rf::ppo_work(layout, B, work), "%s: no workspace layout for B = %d", fn, B);
+    RF_HIP(hipSetDevice(ctx->device));
+    const size_t rows = (size_t)N;
+    struct Array {
+        const void *p;
+        size_t bytes, align;
+        const char *what;
+    };
+    const Array inputs[] = {{d_obs, rows * (size_t)layout.obs_width * 4, 4, "d_obs"},
+                            {d_actions, rows * 8, 8, "d_actions"},
+                            {d_old_log_probs, rows * 4, 4, "d_old_log_probs"},
+                            {d_advantages, rows * 4, 4, "d_advantages"},
+                            {d_returns, rows * 4, 4, "d_returns"},
+                            {d_index, (size_t)B * 8, 8, "d_index"}};
+    const Array outputs[] = {{d_params, (size_t)layout.total * 4, 4, "d_params"},
+                             {d_state, 4 * (size_t)rf::kPpoStateHeader + 8 * (size_t)layout.total, 8, "d_state"},
+                             {d_workspace, (size_t)work.total * 4, 8, "d_workspace"},
+                             {d_stats, 32, 4, "d_stats"}};
+    for (const Array &a : inputs)
+        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
+            return rc;
+    for (const Array &a : outputs) {
+        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
+            return rc;
+        for (const Array &b : inputs)
+            RF_REQUIRE(!ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s (an output must not alias an "
+                       "input: other blocks still read it)", fn, a.what, b.what);
+        for (const Array &b : outputs)
+            RF_REQUIRE(&b >= &a || !ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s", fn, a.what, b.what);
+    }
+    const hipStream_t caller = (hipStream_t)caller_stream;
+    if (int rc = refuse_capturing(caller, fn))
+        return rc;
+    // Every array is the caller's and the hyper-parameters travel by value: three launches on the caller's stream,
+    // nothing allocated, nothing waited for.  The workspace layout is that of B itself: any workspace made for a larger
+    // max_batch holds it.
+    float *ws = (float *)d_workspace;
+    const unsigned tiles = (unsigned)((B + rf::kPolicyTile - 1) / rf::kPolicyTile);
+    hipLaunchKernelGGL(rf::ppo_backward_kernel, dim3(tiles, 2u), dim3(rf::kPpoThreads), 0, caller, layout, work, hyper,
+                       (const float *)d_params, (const rf::PpoHeader *)d_state, ws, N, d_obs, (const int64_t *)d_actions,
+                       d_old_log_probs, d_advantages, d_returns, B, (const int64_t *)d_index);
+    RF_HIP(hipGetLastError());
+    hipLaunchKernelGGL(rf::ppo_gradient_kernel, dim3(work.partials), dim3(rf::kPpoThreads), 0, caller, layout, work, ws, B);
+    RF_HIP(hipGetLastError());
+    const unsigned slices = (layout.total + rf::kPpoAdamSlice - 1) / rf::kPpoAdamSlice;
+    hipLaunchKernelGGL(rf::ppo_adam_kernel, dim3(slices + 1u), dim3(rf::kPpoThreads), 0, caller, layout.total, work, hyper,
+                       d_params, (float *)d_state, (const float *)ws, B, d_stats);
     RF_HIP(hipGetLastError());
     return RF_OK;
 }

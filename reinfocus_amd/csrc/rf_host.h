@@ -8,6 +8,7 @@
 //   rf_abi_env.hip      the device-resident environment step and its schedules
 //                       and rf_rollout_advantages (rollout_gae_kernel, rf_rollout.h), which shares its pointer checks,
 //                       and rf_policy_forward (policy_forward_kernel, rf_policy.h), which shares them too
+//                       and rf_ppo_update (the three kernels of rf_ppo.h), which shares them as well
 //   rf_abi_snapshot.hip snapshots of a device-resident environment (rf_env_snapshot* / rf_env_restore*): copies only
 //
 // Every kernel is defined in exactly one unit (the one that launches it); the units share only host functions.

@@ -77,6 +77,39 @@ RF_HD bool policy_layout(const rf_policy_desc &d, PolicyLayout &p)
 }
 
 #if defined(__HIPCC__)
+// One hidden layer of a block's tile (shared with ppo_backward_kernel, rf_ppo.h): thread j < H owns unit j with one
+// accumulator per row of the tile; in / out are [k][tile] in LDS.  The caller puts a barrier after it.
+__device__ __forceinline__ void policy_hidden_tile(const float *__restrict__ params, unsigned weight, unsigned bias, int K,
+                                                   int H, int activation, const float (*in)[kPolicyTile],
+                                                   float (*out)[kPolicyTile], int tid)
+{
+    if (tid < H) {
+        const float *__restrict__ w = params + weight + tid;
+        const float b = params[bias + tid];
+        float acc[kPolicyTile];
+#pragma unroll
+        for (int e = 0; e < kPolicyTile; ++e)
+            acc[e] = b;
+#pragma unroll 8
+        for (int k = 0; k < K; ++k) { // (unrolled: 8 independent weight loads in flight per round of latency)
+            const float wk = w[(size_t)k * (size_t)H];
+            const float4 *x = reinterpret_cast<const float4 *>(&in[k][0]);
+            float xs[kPolicyTile];
+#pragma unroll
+            for (int v = 0; v < kPolicyTile / 4; ++v) {
+                const float4 q = x[v];
+                xs[4 * v] = q.x, xs[4 * v + 1] = q.y, xs[4 * v + 2] = q.z, xs[4 * v + 3] = q.w;
+            }
+#pragma unroll
+            for (int e = 0; e < kPolicyTile; ++e)
+                acc[e] = acc[e] + xs[e] * wk;
+        }
+#pragma unroll
+        for (int e = 0; e < kPolicyTile; ++e)
+            out[tid][e] = policy_activation(acc[e], activation);
+    }
+}
+
 __global__ __launch_bounds__(kPolicyThreads) void policy_forward_kernel(
     PolicyLayout L, const float *__restrict__ params, int n, const float *__restrict__ obs,
     const float *__restrict__ final_obs /* or null */, PolicyGen gen, int sampled, int first_net,
@@ -105,31 +138,8 @@ __global__ __launch_bounds__(kPolicyThreads) void policy_forward_kernel(
         int cur = 0, K = D;
         for (int layer = 0; layer < L.layers[net]; ++layer) {
             const int H = L.width[net][layer];
-            if (tid < H) {
-                const float *__restrict__ w = params + L.weight[net][layer] + tid;
-                const float b = params[L.bias[net][layer] + tid];
-                float acc[kPolicyTile];
-#pragma unroll
-                for (int e = 0; e < kPolicyTile; ++e)
-                    acc[e] = b;
-#pragma unroll 8
-                for (int k = 0; k < K; ++k) { // (unrolled: 8 independent weight loads in flight per round of latency)
-                    const float wk = w[(size_t)k * (size_t)H];
-                    const float4 *x = reinterpret_cast<const float4 *>(&s_act[cur][k][0]);
-                    float xs[kPolicyTile];
-#pragma unroll
-                    for (int v = 0; v < kPolicyTile / 4; ++v) {
-                        const float4 q = x[v];
-                        xs[4 * v] = q.x, xs[4 * v + 1] = q.y, xs[4 * v + 2] = q.z, xs[4 * v + 3] = q.w;
-                    }
-#pragma unroll
-                    for (int e = 0; e < kPolicyTile; ++e)
-                        acc[e] = acc[e] + xs[e] * wk;
-                }
-#pragma unroll
-                for (int e = 0; e < kPolicyTile; ++e)
-                    s_act[cur ^ 1][tid][e] = policy_activation(acc[e], L.activation);
-            }
+            policy_hidden_tile(params, L.weight[net][layer], L.bias[net][layer], K, H, L.activation, s_act[cur],
+                               s_act[cur ^ 1], tid);
             __syncthreads();
             cur ^= 1;
             K = H;

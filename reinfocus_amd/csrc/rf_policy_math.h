@@ -8,6 +8,7 @@
 // bit, which no library exp / log does across a CPU and a GPU.
 #pragma once
 
+#include <math.h>
 #include <stdint.h>
 #include <string.h>
 

@@ -372,7 +372,9 @@ class DevicePolicy(_Draws):
         out = {}
         for name, at, shape, is_weight in self.spec.entries:
             view = self.params[at:at + int(np.prod(shape))].view(shape)
-            out[name] = view.t().contiguous() if is_weight else view.clone()
+            # (clone, not contiguous(): the transpose of an [in][1] matrix is contiguous already and would stay a view of
+            # the parameters a learner updates in place)
+            out[name] = view.t().clone(memory_format=self._torch.contiguous_format) if is_weight else view.clone()
         return out
 
     def _rows(self, tensor, what):
