@@ -797,15 +797,15 @@ int rf_rollout_advantages(rf_ctx *ctx, int T, int n, const double *d_rewards, co
  * Network.  Two nets, pi and vf, each with 1 or 2 hidden layers of width 1 .. RF_POLICY_MAX_WIDTH; input width
  * obs_width 1 .. RF_POLICY_MAX_WIDTH; the pi head has n_actions 2 .. RF_POLICY_MAX_ACTIONS outputs (the logits of a
  * Categorical), the vf head one.  One activation for both nets.  Continuous action spaces (the reference trains
- * ContinuousJumps with gSDE) are out of scope.
+ * ContinuousJumps with gSDE) have the Gaussian head of "sde policy" below; this entry point refuses them.
  * Parameters: one float32 array, every matrix TRANSPOSED ([in][out] row-major: SB3's weight.T), in this order:
  *   pi: W0^T, b0, (W1^T, b1,) Wa^T [last][n_actions], ba;   vf: W0^T, b0, (W1^T, b1,) Wv^T [last][1], bv
  * Linear layer: y_j = b_j; for k = 0 .. K-1: y_j = y_j + x_k * W[j][k] -- a float32 multiply, then a float32 add, in
  * that order, no FMA.  No MFMA: its internal accumulation order is not documented.
  * Activation: relu(x) = x > 0 ? x : 0 (NaN and -0 become +0), or tanh32(x) = sign(x) * (1 - t) / (1 + t) with
  * t = exp32(-2 |x|); tanh32(NaN) is NaN.
- * exp32 (x <= 0; +0 for x < -87, for -inf and for NaN; exp32(0) == 1; never a subnormal) and log32 (on [1, 64]) are the
- * project's own: float32 + - * / (correctly rounded), comparisons, float <-> int conversions and integer operations on
+ * exp32 (x <= 0; +0 for x < -87, for -inf and for NaN; exp32(0) == 1; never a subnormal) and log32 (every positive normal number; the Categorical head
+ * calls it on [1, 64]) are the project's own: float32 + - * / (correctly rounded), comparisons, float <-> int conversions and integer operations on
  * the exponent field only -- csrc/rf_policy_math.h is the text.
  * Head.  With logits l_i: m = the first maximum (m = l_0; l_i > m replaces it: a NaN l_0 stays, NaNs elsewhere are never
  * the maximum), z_i = l_i - m, e_i = exp32(z_i), c_i the sequential float32 partial sums of e, s = c_{A-1},
@@ -928,6 +928,79 @@ unsigned long long rf_ppo_state_size(rf_ctx *ctx, const rf_policy_desc *policy);
 unsigned long long rf_ppo_workspace_size(rf_ctx *ctx, const rf_policy_desc *policy, int max_batch);
 int rf_ppo_update(rf_ctx *ctx, const rf_policy_desc *policy, const rf_ppo_desc *ppo, float *d_params, void *d_state,
                   void *d_workspace, int N, const float *d_obs, const long long *d_actions, const float *d_old_log_probs,
+                  const float *d_advantages, const float *d_returns, int B, const long long *d_index, float *d_stats,
+                  void *caller_stream);
+
+/* ---- sde policy: the state-dependent-exploration Gaussian actor-critic and its PPO update ------------------------------
+ * The reference's second task, ContinuousJumps-v0 (Box(-1, 1, (1,))), is trained by its PPO configurations with
+ * use_sde: stable-baselines3's ActorCriticPolicy(use_sde=True), i.e. StateDependentNoiseDistribution with full_std=True,
+ * use_expln=False, squash_output=False, learn_features=False, epsilon=1e-6, for an action of ONE dimension (any other
+ * action width is refused: rf_policy_desc.n_actions must be 1 here).  No reference counterpart.
+ *
+ * One definition, numpy twin (environments/sde.py), host build (tests/sdecheck) and kernels (csrc/rf_sde.h, csrc/rf_ppo.h)
+ * alike; the scalar functions are csrc/rf_policy_math.h.  Everything is float32, one rounding per operation, nothing
+ * contracted, unless a step says float64.
+ *
+ *  S1 Network.  The two MLPs of "policy", unchanged; the pi head has one output, the mean mu.  New parameter log_std[L],
+ *     L = the width of the last pi hidden layer (SB3's log_std [L, 1], state_dict name "log_std").
+ *  S2 Packing.  Everything "policy" packs, at the same offsets (with a pi head of one output), then log_std[L]: P + L floats.
+ *  S3 Scalar functions.  expw32(x) = x <= 0 ? exp32(x) : 1.0f / exp32(-x) (+inf for x > 87 and for NaN).  log32 as above.
+ *     log64: log32's scheme in float64 (twelve series terms, a two-constant ln 2), about 2e-16 relative.
+ *     normal32(u), u a draw j * 2^-53: M. J. Wichura's AS 241 PPND16 evaluated in FLOAT64 (correctly rounded + - * /
+ *     sqrt, nothing contracted: the one scalar function here that is not float32 inside) on a float32 argument, and
+ *     rounded to float32 once at the end.  upper = u >= 0.5; pf = float32(upper ? 1.0 - u : u) (the subtraction is exact),
+ *     raised to 2^-54 if smaller (u = 0 gives about -8.29, finite); p = double(pf).  pf >= 0.075f: q = upper ? 0.5 - p :
+ *     p - 0.5, r = 0.180625 - q * q, x = (q * A(r)) / B(r).  Else r = sqrt(-log64(p)); r <= 5: r = r - 1.6,
+ *     x = C(r) / D(r); else r = r - 5.0, x = E(r) / F(r); x is negated in the lower half.  A .. F are PPND16's
+ *     polynomials by Horner from the leading coefficient (c + r * acc).  normal32 = float32(x); normal32(0.5) is +0.
+ *     It is finite for every draw and never decreases in u: neighbouring float32 arguments move the exact quantile by more
+ *     than 7e-9, a million times the float64 evaluation's error (branch joins included), so the float64 values increase
+ *     strictly and the final rounding keeps their order -- which a float32 evaluation, moving by about one ulp per step of
+ *     p, cannot promise.  Checked on all 444 596 224 pairs of neighbouring float32 arguments of [2^-54, 1/2] in both
+ *     halves (profiles/sde.md); tests/test_sde_logic.py repeats the joins, the ends and a dense sample.
+ *  S4 Shared quantities, h = the activations of the last pi hidden layer: std_k = expw32(log_std_k), std2_k = std_k * std_k;
+ *     var = sum over k in index order, from +0, of (h_k * h_k) * std2_k (multiply, multiply, add);
+ *     sigma = sqrt32(var + 1e-6f).
+ *  S5 Exploration noise.  theta[e][k] = normal32(u) * std_k, u = draw number e * L + k of Generator(PCG64DXSM) in the state
+ *     `gen` (jump-ahead, as "policy" draws); a NaN product (0 * inf) is stored as 0x7fc00000.  theta changes only by a
+ *     reset, which advances the caller's generator by n * L.  No generator state lives on the device.
+ *  S6 Actions.  mu = the pi head (policy's linear layer).  Sampled raw action a = mu + (sum over k in index order, from
+ *     +0, of h_k * theta[e][k]); deterministic: a = mu.  Environment action = a < -1 ? -1 : (a > 1 ? 1 : a): NaN stays
+ *     NaN, so the environment's own check records it.  The rollout keeps the raw action, as SB3 does.
+ *  S7 log_prob = ((-q) - log32(sigma)) - float32(0.9189385332046727), t = a - mu, q = (t * t) / (2.0f * (sigma * sigma));
+ *     entropy = float32(1.4189385332046727) + log32(sigma).  Both are NaN where sigma is not finite.
+ *  S8 Values: V(obs) and V(final_obs) exactly as "policy".  Stored NaNs are 0x7fc00000.
+ * The update is "ppo update" with these steps replaced (2, 4 from d on, 8, 9 and 10 are unchanged, over P + L parameters):
+ *  1' Validity.  invalid = some index[b] outside [0, N) or some actions[row] NaN (actions float32[N], the raw actions).
+ *  3' Forward.  mu, sigma as S4 / S6 on obs[row]; logp = S7 for the stored action; H_b = the entropy of S7.
+ *  5' Head gradients, g_b as step 5, ng = -g_b, t = a - mu, v2 = sigma * sigma:
+ *     dmu_b  = (ng * (t / v2)) / Bf;
+ *     dsig_b = (((ng * ((t * t) / (v2 * sigma) - 1.0f / sigma)) - ec / sigma) / Bf) / sigma.
+ *     A row whose sigma or logp is not finite has dmu_b = dsig_b = NaN: the update ends in RF_PPO_NONFINITE.
+ *  6' Backward.  The pi net gets its gradient through mu only (delta of the head = dmu_b); h is a constant inside var
+ *     (learn_features=False).
+ *  7' dlog_std_k = sum over b = 0 .. B-1, from +0, of ((h[b][k] * h[b][k]) * std2_k) * dsig_b: log_std gets its gradient
+ *     through sigma only, from the policy loss and the entropy term.
+ *
+ *   rf_sde_params_size     floats of the packed parameters (P + L); 0 for a desc outside the limits or a NULL ctx
+ *   rf_sde_noise_reset     one launch: d_theta float32[n][L] from gen and the log_std inside d_params
+ *   rf_sde_forward         one launch.  Outputs (each may be NULL, one must be given): d_actions float32[n] (raw),
+ *                          d_env_actions float32[n] (clamped), d_log_probs, d_values, d_final_values (needs d_final_obs),
+ *                          d_mean, d_sigma float32[n].  d_theta is needed unless flags has RF_POLICY_DETERMINISTIC or no pi
+ *                          output is asked for.  Refusals as rf_policy_forward's.
+ *   rf_sde_state_size, rf_sde_workspace_size, rf_sde_update
+ *                          as their rf_ppo_ siblings, over P + L parameters and float32 actions; the same refusals. */
+unsigned long long rf_sde_params_size(rf_ctx *ctx, const rf_policy_desc *desc);
+int rf_sde_noise_reset(rf_ctx *ctx, const rf_policy_desc *desc, const float *d_params, int n,
+                       const unsigned long long gen[4], float *d_theta, void *caller_stream);
+int rf_sde_forward(rf_ctx *ctx, const rf_policy_desc *desc, const float *d_params, int n, const float *d_obs,
+                   const float *d_final_obs, const float *d_theta, int flags, float *d_actions, float *d_env_actions,
+                   float *d_log_probs, float *d_values, float *d_final_values, float *d_mean, float *d_sigma,
+                   void *caller_stream);
+unsigned long long rf_sde_state_size(rf_ctx *ctx, const rf_policy_desc *policy);
+unsigned long long rf_sde_workspace_size(rf_ctx *ctx, const rf_policy_desc *policy, int max_batch);
+int rf_sde_update(rf_ctx *ctx, const rf_policy_desc *policy, const rf_ppo_desc *ppo, float *d_params, void *d_state,
+                  void *d_workspace, int N, const float *d_obs, const float *d_actions, const float *d_old_log_probs,
                   const float *d_advantages, const float *d_returns, int B, const long long *d_index, float *d_stats,
                   void *caller_stream);
 

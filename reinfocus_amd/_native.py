@@ -101,6 +101,12 @@ SYMBOLS = (
     "rf_ppo_state_size",
     "rf_ppo_workspace_size",
     "rf_ppo_update",
+    "rf_sde_params_size",
+    "rf_sde_noise_reset",
+    "rf_sde_forward",
+    "rf_sde_state_size",
+    "rf_sde_workspace_size",
+    "rf_sde_update",
     "rf_render_kernel_name",
     "rf_pixels_rendered",
     "rf_allocations_poisoned",
@@ -344,6 +350,15 @@ def load():
     lib.rf_ppo_workspace_size.restype = ctypes.c_ulonglong
     lib.rf_ppo_workspace_size.argtypes = [vp, vp, i32]
     lib.rf_ppo_update.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp]
+    lib.rf_sde_params_size.restype = ctypes.c_ulonglong
+    lib.rf_sde_params_size.argtypes = [vp, vp]
+    lib.rf_sde_noise_reset.argtypes = [vp, vp, vp, i32, vp, vp, vp]
+    lib.rf_sde_forward.argtypes = [vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.rf_sde_state_size.restype = ctypes.c_ulonglong
+    lib.rf_sde_state_size.argtypes = [vp, vp]
+    lib.rf_sde_workspace_size.restype = ctypes.c_ulonglong
+    lib.rf_sde_workspace_size.argtypes = [vp, vp, i32]
+    lib.rf_sde_update.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp]
     lib.rf_render_kernel_name.restype = ctypes.c_char_p
     lib.rf_render_kernel_name.argtypes = [vp]
     lib.rf_pixels_rendered.restype = ctypes.c_ulonglong
@@ -717,6 +732,46 @@ class Context:
         order (learning_rate, clip_range, ent_coef, vf_coef, max_grad_norm, beta1, beta2, adam_eps,
         normalize_advantage).  Only enqueues."""
         rc = self._lib.rf_ppo_update(self._h, ctypes.byref(PolicyDesc(*desc)), ctypes.byref(PpoDesc(*hyper)), params_ptr,
+                                     state_ptr, workspace_ptr, rows, obs_ptr, actions_ptr, old_log_probs_ptr,
+                                     advantages_ptr, returns_ptr, batch, index_ptr, stats_ptr, stream)
+        if rc != 0:
+            _check(rc)
+
+    # --- sde policy (rf_sde_*): the Gaussian head's counterparts of the two groups above --------------------------------
+    def sde_params_size(self, desc):
+        """rf_sde_params_size: floats of the packed parameters (log_std included); 0 for a desc outside the limits."""
+        return int(self._lib.rf_sde_params_size(self._h, ctypes.byref(PolicyDesc(*desc))))
+
+    def sde_noise_reset(self, desc, params_ptr, num_envs, gen, theta_ptr, stream):
+        """rf_sde_noise_reset: theta float32 [num_envs][L] from the generator's four words and the log_std inside the
+        parameters, one launch on `stream`.  Only enqueues."""
+        rc = self._lib.rf_sde_noise_reset(self._h, ctypes.byref(PolicyDesc(*desc)), params_ptr, num_envs,
+                                          None if gen is None else (ctypes.c_ulonglong * 4)(*gen), theta_ptr, stream)
+        if rc != 0:
+            _check(rc)
+
+    def sde_forward(self, desc, params_ptr, num_envs, obs_ptr, final_obs_ptr, theta_ptr, flags, actions_ptr,
+                    env_actions_ptr, log_probs_ptr, values_ptr, final_values_ptr, mean_ptr, sigma_ptr, stream):
+        """rf_sde_forward: the Gaussian actor-critic forward over device arrays given by address (each output,
+        final_obs_ptr and theta_ptr may be None), one launch on `stream`.  Only enqueues."""
+        rc = self._lib.rf_sde_forward(self._h, ctypes.byref(PolicyDesc(*desc)), params_ptr, num_envs, obs_ptr, final_obs_ptr,
+                                      theta_ptr, flags, actions_ptr, env_actions_ptr, log_probs_ptr, values_ptr,
+                                      final_values_ptr, mean_ptr, sigma_ptr, stream)
+        if rc != 0:
+            _check(rc)
+
+    def sde_state_size(self, desc):
+        """rf_sde_state_size: bytes of the optimizer state (header, m, v over P + L parameters); 0 if refused."""
+        return int(self._lib.rf_sde_state_size(self._h, ctypes.byref(PolicyDesc(*desc))))
+
+    def sde_workspace_size(self, desc, max_batch):
+        """rf_sde_workspace_size: bytes of the workspace for minibatches of up to max_batch samples; 0 if refused."""
+        return int(self._lib.rf_sde_workspace_size(self._h, ctypes.byref(PolicyDesc(*desc)), max_batch))
+
+    def sde_update(self, desc, hyper, params_ptr, state_ptr, workspace_ptr, rows, obs_ptr, actions_ptr, old_log_probs_ptr,
+                   advantages_ptr, returns_ptr, batch, index_ptr, stats_ptr, stream):
+        """rf_sde_update: rf_ppo_update with the Gaussian head (actions float32, the raw ones).  Only enqueues."""
+        rc = self._lib.rf_sde_update(self._h, ctypes.byref(PolicyDesc(*desc)), ctypes.byref(PpoDesc(*hyper)), params_ptr,
                                      state_ptr, workspace_ptr, rows, obs_ptr, actions_ptr, old_log_probs_ptr,
                                      advantages_ptr, returns_ptr, batch, index_ptr, stats_ptr, stream)
         if rc != 0:

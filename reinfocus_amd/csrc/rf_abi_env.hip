@@ -12,6 +12,7 @@
 #include "rf_env_view.h"
 #include "rf_policy.h"
 #include "rf_ppo.h"
+#include "rf_sde.h"
 #include "rf_rollout.h"
 
 using namespace rfh;
@@ -2034,20 +2035,27 @@ unsigned long long rf_ppo_workspace_size(rf_ctx *ctx, const rf_policy_desc *poli
     return 4ull * work.total;
 }
 
-int rf_ppo_update(rf_ctx *ctx, const rf_policy_desc *policy, const rf_ppo_desc *ppo, float *d_params, void *d_state,
-                  void *d_workspace, int N, const float *d_obs, const long long *d_actions, const float *d_old_log_probs,
-                  const float *d_advantages, const float *d_returns, int B, const long long *d_index, float *d_stats,
-                  void *caller_stream)
+#define RF_SDE_LIMITS "%s: the desc is outside the limits (obs_width 1 .. %d, 1 or 2 hidden layers of width 1 .. %d per net, " \
+                      "n_actions 1: the Gaussian head has one action, activation RF_POLICY_RELU or RF_POLICY_TANH)"
+
+// What rf_ppo_update and rf_sde_update do once they have checked ctx and made its device current: one body, the head
+// chosen by `sde` (the layout, the dtype of the actions, the kernel)
+static int ppo_update_any(const char *fn, bool sde, rf_ctx *ctx, const rf_policy_desc *policy, const rf_ppo_desc *ppo,
+                          float *d_params, void *d_state, void *d_workspace, int N, const float *d_obs, const void *d_actions,
+                          const float *d_old_log_probs, const float *d_advantages, const float *d_returns, int B,
+                          const long long *d_index, float *d_stats, void *caller_stream)
 {
-    const char *fn = "rf_ppo_update";
-    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", fn);
     RF_REQUIRE(policy && ppo && d_params && d_state && d_workspace && d_obs && d_actions && d_old_log_probs && d_advantages
                && d_returns && d_index && d_stats, "%s: NULL argument", fn);
     rf::PolicyLayout layout;
-    RF_REQUIRE(rf::policy_layout(*policy, layout),
-               "%s: the desc is outside the limits (obs_width 1 .. %d, 1 or 2 hidden layers of width 1 .. %d per net, "
-               "n_actions 2 .. %d, activation RF_POLICY_RELU or RF_POLICY_TANH)", fn, RF_POLICY_MAX_WIDTH,
-               RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_ACTIONS);
+    if (sde) {
+        RF_REQUIRE(rf::sde_layout(*policy, layout), RF_SDE_LIMITS, fn, RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_WIDTH);
+    } else {
+        RF_REQUIRE(rf::policy_layout(*policy, layout),
+                   "%s: the desc is outside the limits (obs_width 1 .. %d, 1 or 2 hidden layers of width 1 .. %d per net, "
+                   "n_actions 2 .. %d, activation RF_POLICY_RELU or RF_POLICY_TANH)", fn, RF_POLICY_MAX_WIDTH,
+                   RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_ACTIONS);
+    }
     RF_REQUIRE(N >= 1 && N <= (1 << 30), "%s: N = %d must be at least 1 (and at most 2^30)", fn, N);
     RF_REQUIRE(B >= 1 && B <= RF_PPO_MAX_BATCH, "%s: B = %d is not in 1 .. %d", fn, B, RF_PPO_MAX_BATCH);
     rf::PpoHyper hyper;
@@ -2055,7 +2063,6 @@ int rf_ppo_update(rf_ctx *ctx, const rf_policy_desc *policy, const rf_ppo_desc *
                "normalize_advantage is not 0 / 1", fn);
     rf::PpoWork work;
     RF_REQUIRE(rf::ppo_work(layout, B, work), "%s: no workspace layout for B = %d", fn, B);
-    RF_HIP(hipSetDevice(ctx->device));
     const size_t rows = (size_t)N;
     struct Array {
         const void *p;
@@ -2063,7 +2070,7 @@ int rf_ppo_update(rf_ctx *ctx, const rf_policy_desc *policy, const rf_ppo_desc *
         const char *what;
     };
     const Array inputs[] = {{d_obs, rows * (size_t)layout.obs_width * 4, 4, "d_obs"},
-                            {d_actions, rows * 8, 8, "d_actions"},
+                            {d_actions, rows * (sde ? 4 : 8), sde ? (size_t)4 : (size_t)8, "d_actions"},
                             {d_old_log_probs, rows * 4, 4, "d_old_log_probs"},
                             {d_advantages, rows * 4, 4, "d_advantages"},
                             {d_returns, rows * 4, 4, "d_returns"},
@@ -2092,15 +2099,155 @@ int rf_ppo_update(rf_ctx *ctx, const rf_policy_desc *policy, const rf_ppo_desc *
     // max_batch holds it.
     float *ws = (float *)d_workspace;
     const unsigned tiles = (unsigned)((B + rf::kPolicyTile - 1) / rf::kPolicyTile);
-    hipLaunchKernelGGL(rf::ppo_backward_kernel, dim3(tiles, 2u), dim3(rf::kPpoThreads), 0, caller, layout, work, hyper,
-                       (const float *)d_params, (const rf::PpoHeader *)d_state, ws, N, d_obs, (const int64_t *)d_actions,
-                       d_old_log_probs, d_advantages, d_returns, B, (const int64_t *)d_index);
+    hipLaunchKernelGGL(sde ? rf::ppo_backward_kernel<true> : rf::ppo_backward_kernel<false>, dim3(tiles, 2u),
+                       dim3(rf::kPpoThreads), 0, caller, layout, work, hyper, (const float *)d_params,
+                       (const rf::PpoHeader *)d_state, ws, N, d_obs, d_actions, d_old_log_probs, d_advantages, d_returns, B,
+                       (const int64_t *)d_index);
     RF_HIP(hipGetLastError());
-    hipLaunchKernelGGL(rf::ppo_gradient_kernel, dim3(work.partials), dim3(rf::kPpoThreads), 0, caller, layout, work, ws, B);
+    hipLaunchKernelGGL(rf::ppo_gradient_kernel, dim3(work.partials), dim3(rf::kPpoThreads), 0, caller, layout, work, ws, B,
+                       (const float *)d_params);
     RF_HIP(hipGetLastError());
     const unsigned slices = (layout.total + rf::kPpoAdamSlice - 1) / rf::kPpoAdamSlice;
     hipLaunchKernelGGL(rf::ppo_adam_kernel, dim3(slices + 1u), dim3(rf::kPpoThreads), 0, caller, layout.total, work, hyper,
                        d_params, (float *)d_state, (const float *)ws, B, d_stats);
+    RF_HIP(hipGetLastError());
+    return RF_OK;
+}
+
+int rf_ppo_update(rf_ctx *ctx, const rf_policy_desc *policy, const rf_ppo_desc *ppo, float *d_params, void *d_state,
+                  void *d_workspace, int N, const float *d_obs, const long long *d_actions, const float *d_old_log_probs,
+                  const float *d_advantages, const float *d_returns, int B, const long long *d_index, float *d_stats,
+                  void *caller_stream)
+{
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", "rf_ppo_update");
+    RF_HIP(hipSetDevice(ctx->device));
+    return ppo_update_any("rf_ppo_update", false, ctx, policy, ppo, d_params, d_state, d_workspace, N, d_obs, d_actions,
+                          d_old_log_probs, d_advantages, d_returns, B, d_index, d_stats, caller_stream);
+}
+
+int rf_sde_update(rf_ctx *ctx, const rf_policy_desc *policy, const rf_ppo_desc *ppo, float *d_params, void *d_state,
+                  void *d_workspace, int N, const float *d_obs, const float *d_actions, const float *d_old_log_probs,
+                  const float *d_advantages, const float *d_returns, int B, const long long *d_index, float *d_stats,
+                  void *caller_stream)
+{
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", "rf_sde_update");
+    RF_HIP(hipSetDevice(ctx->device));
+    return ppo_update_any("rf_sde_update", true, ctx, policy, ppo, d_params, d_state, d_workspace, N, d_obs, d_actions,
+                          d_old_log_probs, d_advantages, d_returns, B, d_index, d_stats, caller_stream);
+}
+
+unsigned long long rf_sde_params_size(rf_ctx *ctx, const rf_policy_desc *desc)
+{
+    rf::PolicyLayout layout;
+    if (ctx == nullptr || desc == nullptr || !rf::sde_layout(*desc, layout))
+        return 0;
+    if (hipSetDevice(ctx->device) != hipSuccess) // (as every entry point; nothing of the device is needed)
+        (void)hipGetLastError();
+    return layout.total;
+}
+
+unsigned long long rf_sde_state_size(rf_ctx *ctx, const rf_policy_desc *policy)
+{
+    rf::PolicyLayout layout;
+    if (ctx == nullptr || policy == nullptr || !rf::sde_layout(*policy, layout))
+        return 0;
+    if (hipSetDevice(ctx->device) != hipSuccess)
+        (void)hipGetLastError();
+    return 4ull * rf::kPpoStateHeader + 8ull * layout.total;
+}
+
+unsigned long long rf_sde_workspace_size(rf_ctx *ctx, const rf_policy_desc *policy, int max_batch)
+{
+    rf::PolicyLayout layout;
+    rf::PpoWork work;
+    if (ctx == nullptr || policy == nullptr || !rf::sde_layout(*policy, layout) || !rf::ppo_work(layout, max_batch, work))
+        return 0;
+    if (hipSetDevice(ctx->device) != hipSuccess)
+        (void)hipGetLastError();
+    return 4ull * work.total;
+}
+
+int rf_sde_noise_reset(rf_ctx *ctx, const rf_policy_desc *desc, const float *d_params, int n,
+                       const unsigned long long gen[4], float *d_theta, void *caller_stream)
+{
+    const char *fn = "rf_sde_noise_reset";
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", fn);
+    RF_REQUIRE(desc != nullptr && d_params != nullptr && gen != nullptr && d_theta != nullptr, "%s: NULL argument", fn);
+    rf::PolicyLayout layout;
+    RF_REQUIRE(rf::sde_layout(*desc, layout), RF_SDE_LIMITS, fn, RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_WIDTH);
+    RF_REQUIRE(n >= 1 && n <= (1 << 20), "%s: n = %d must be at least 1 (and at most 2^20)", fn, n);
+    RF_HIP(hipSetDevice(ctx->device));
+    const size_t cells = (size_t)n * (size_t)layout.sde;
+    if (int rc = check_device_array(ctx, d_params, (size_t)layout.total * 4, 4, "d_params", fn))
+        return rc;
+    if (int rc = check_device_array(ctx, d_theta, cells * 4, 4, "d_theta", fn))
+        return rc;
+    RF_REQUIRE(!ranges_overlap(d_theta, cells * 4, d_params, (size_t)layout.total * 4), "%s: d_theta overlaps d_params", fn);
+    rf::PolicyGen words{};
+    for (int i = 0; i < 4; ++i)
+        words.word[i] = gen[i];
+    const unsigned blocks = (unsigned)((cells + rf::kPolicyThreads - 1) / rf::kPolicyThreads);
+    hipLaunchKernelGGL(rf::sde_noise_kernel, dim3(blocks), dim3(rf::kPolicyThreads), 0, (hipStream_t)caller_stream, words,
+                       d_params + layout.log_std, n, (int)layout.sde, d_theta);
+    RF_HIP(hipGetLastError());
+    return RF_OK;
+}
+
+int rf_sde_forward(rf_ctx *ctx, const rf_policy_desc *desc, const float *d_params, int n, const float *d_obs,
+                   const float *d_final_obs, const float *d_theta, int flags, float *d_actions, float *d_env_actions,
+                   float *d_log_probs, float *d_values, float *d_final_values, float *d_mean, float *d_sigma,
+                   void *caller_stream)
+{
+    const char *fn = "rf_sde_forward";
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", fn);
+    RF_REQUIRE(desc != nullptr && d_params != nullptr && d_obs != nullptr, "%s: NULL argument", fn);
+    rf::PolicyLayout layout;
+    RF_REQUIRE(rf::sde_layout(*desc, layout), RF_SDE_LIMITS, fn, RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_WIDTH);
+    RF_REQUIRE(n >= 1 && n <= (1 << 20), "%s: n = %d must be at least 1 (and at most 2^20)", fn, n);
+    RF_REQUIRE((flags & ~RF_POLICY_DETERMINISTIC) == 0, "%s: unknown flags %d", fn, flags);
+    const bool pi = d_actions || d_env_actions || d_log_probs || d_mean || d_sigma;
+    const bool vf = d_values != nullptr || d_final_values != nullptr;
+    RF_REQUIRE(pi || vf, "%s: no output is asked for", fn);
+    RF_REQUIRE(d_final_values == nullptr || d_final_obs != nullptr, "%s: d_final_values needs d_final_obs", fn);
+    const bool sampled = pi && (flags & RF_POLICY_DETERMINISTIC) == 0;
+    RF_REQUIRE(!sampled || d_theta != nullptr, "%s: a sampled call needs d_theta (rf_sde_noise_reset)", fn);
+    RF_HIP(hipSetDevice(ctx->device));
+    const size_t rows = (size_t)n;
+    struct Array {
+        const void *p;
+        size_t bytes, align;
+        const char *what;
+    };
+    const Array inputs[] = {{d_params, (size_t)layout.total * 4, 4, "d_params"},
+                            {d_obs, rows * (size_t)layout.obs_width * 4, 4, "d_obs"},
+                            {d_final_obs, rows * (size_t)layout.obs_width * 4, 4, "d_final_obs"},
+                            {sampled ? d_theta : nullptr, rows * (size_t)layout.sde * 4, 4, "d_theta"}};
+    const Array outputs[] = {{d_actions, rows * 4, 4, "d_actions"},       {d_env_actions, rows * 4, 4, "d_env_actions"},
+                             {d_log_probs, rows * 4, 4, "d_log_probs"},   {d_values, rows * 4, 4, "d_values"},
+                             {d_final_values, rows * 4, 4, "d_final_values"}, {d_mean, rows * 4, 4, "d_mean"},
+                             {d_sigma, rows * 4, 4, "d_sigma"}};
+    for (const Array &a : inputs) {
+        if (a.p == nullptr)
+            continue;
+        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
+            return rc;
+    }
+    for (const Array &a : outputs) {
+        if (a.p == nullptr)
+            continue;
+        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
+            return rc;
+        for (const Array &b : inputs)
+            RF_REQUIRE(b.p == nullptr || !ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s (an output must "
+                       "not alias an input: other blocks still read it)", fn, a.what, b.what);
+        for (const Array &b : outputs)
+            RF_REQUIRE(&b >= &a || b.p == nullptr || !ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s", fn,
+                       a.what, b.what);
+    }
+    const unsigned tiles = (unsigned)((rows + rf::kPolicyTile - 1) / rf::kPolicyTile);
+    hipLaunchKernelGGL(rf::sde_forward_kernel, dim3(tiles, pi && vf ? 2u : 1u), dim3(rf::kPolicyThreads), 0,
+                       (hipStream_t)caller_stream, layout, d_params, n, d_obs, d_final_obs, sampled ? d_theta : nullptr,
+                       pi ? 0 : 1, d_actions, d_env_actions, d_log_probs, d_values, d_final_values, d_mean, d_sigma);
     RF_HIP(hipGetLastError());
     return RF_OK;
 }

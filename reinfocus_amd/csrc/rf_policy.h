@@ -34,17 +34,18 @@ struct PolicyLayout {
     int width[2][2];
     unsigned weight[2][3], bias[2][3]; // [net][hidden layer 0, 1 or (at index `layers`) the head]
     unsigned total;
+    unsigned log_std, sde; // the Gaussian head (sde_layout): log_std [sde] sits at `log_std`, after everything else; else 0
 };
 
 struct PolicyGen {
     uint64_t word[4]; // state low, state high, inc low, inc high
 };
 
-// false: desc is outside the limits of the definition
-RF_HD bool policy_layout(const rf_policy_desc &d, PolicyLayout &p)
+// The packing of both heads; min_actions is 2 for the Categorical head and 1 for the Gaussian one
+RF_HD bool policy_layout_nets(const rf_policy_desc &d, PolicyLayout &p, int min_actions)
 {
     p = PolicyLayout{};
-    if (d.obs_width < 1 || d.obs_width > kPolicyMaxWidth || d.n_actions < 2 || d.n_actions > kPolicyMaxActions)
+    if (d.obs_width < 1 || d.obs_width > kPolicyMaxWidth || d.n_actions < min_actions || d.n_actions > kPolicyMaxActions)
         return false;
     if (d.activation != kPolicyRelu && d.activation != kPolicyTanh)
         return false;
@@ -73,6 +74,23 @@ RF_HD bool policy_layout(const rf_policy_desc &d, PolicyLayout &p)
         }
     }
     p.total = at;
+    return true;
+}
+
+// false: desc is outside the limits of the definition
+RF_HD bool policy_layout(const rf_policy_desc &d, PolicyLayout &p)
+{
+    return policy_layout_nets(d, p, 2);
+}
+
+// The Gaussian head of "sde policy": one action (n_actions must be 1: the mean), log_std [last pi width] packed last
+RF_HD bool sde_layout(const rf_policy_desc &d, PolicyLayout &p)
+{
+    if (d.n_actions != 1 || !policy_layout_nets(d, p, 1))
+        return false;
+    p.log_std = p.total;
+    p.sde = (unsigned)p.width[0][p.layers[0] - 1];
+    p.total = p.log_std + p.sde;
     return true;
 }
 

@@ -1,5 +1,6 @@
 // rf_policy_math.h -- the scalar arithmetic of the actor-critic forward (include/reinfocus_hip.h, "policy"): the
-// project's own exp32 / log32 / tanh32, the activation, the Categorical head and the draw of a lane.
+// project's own exp32 / log32 / tanh32, the activation, the Categorical head and the draw of a lane; and of the Gaussian
+// head of "sde policy": expw32, log64, normal32 (the one function that is float64 inside) and the sde_* functions.
 //
 // Plain C++ like rf_init.h, so that tests/policycheck compiles the very same text for the host and compares it with the
 // numpy twin (environments/policy.py policy_numpy) on the CPU.  exp32 and log32 are built only from float32 + - * /
@@ -66,7 +67,8 @@ RF_HD float exp32(float x)
     return p * bits_f32((uint32_t)(k + 127) << 23);
 }
 
-// ln(s) for s in [1, 64] (the sum of up to 64 terms of [0, 1] of which one is 1).  s = 2^e * m with m in
+// ln(s) for every positive normal s (the Categorical head calls it on [1, 64], the Gaussian head on sigma >= 1e-3).
+// Subnormals, 0, negatives, inf and NaN are outside its domain: the callers test for them first.  s = 2^e * m with m in
 // (sqrt(1/2), sqrt(2)] from the exponent field; f = m - 1 (exact), q = f / (2 + f), z = q * q,
 //   ln m = 2q + q z (2/3 + z (2/5 + z (2/7 + z (2/9 + z 2/11))))
 //   log32 = e * kLn2Hi + (ln m + e * kLn2Lo)
@@ -90,6 +92,136 @@ RF_HD float log32(float s)
     const float lnm = 2.0f * q + q * (z * p);
     const float ef = (float)e;
     return ef * kLn2Hi + (lnm + ef * kLn2Lo);
+}
+
+// exp(x) for either sign, as the update's ratio takes it: exp32(x) for x <= 0, else 1 / exp32(-x) (+inf for x > 87 and
+// for NaN, whose comparison fails: a caller that cares tests the result).
+RF_HD float expw32(float x)
+{
+    return x <= 0.0f ? exp32(x) : 1.0f / exp32(-x);
+}
+
+// ln(s) in float64 for every positive normal double s, by log32's scheme with float64 operations (correctly rounded + - * /
+// on both sides, nothing contracted): s = 2^e * m, m in (sqrt(1/2), sqrt(2)], f = m - 1, q = f / (2 + f), z = q * q,
+//   ln m = 2q + q z (2/3 + z (2/5 + ... + z 2/25)),   log64 = e * kLn2Hi64 + (ln m + e * kLn2Lo64)
+// (kLn2Hi64 has 32 zero low bits: e * kLn2Hi64 is exact).  About 2e-16 relative: normal32 needs it, float32 does not.
+constexpr double kLn2Hi64 = 6.93147180369123816490e-01, kLn2Lo64 = 1.90821492927058770002e-10;
+
+RF_HD double log64(double s)
+{
+    uint64_t u;
+    memcpy(&u, &s, 8);
+    int64_t e = (int64_t)(u >> 52) - 1023;
+    const uint64_t mu = (u & 0x000fffffffffffffull) | 0x3ff0000000000000ull;
+    double m;
+    memcpy(&m, &mu, 8);
+    if (m > 1.4142135623730951) {
+        m = m * 0.5;
+        e = e + 1;
+    }
+    const double f = m - 1.0;
+    const double q = f / (2.0 + f);
+    const double z = q * q;
+    double p = 2.0 / 25.0;
+    p = 2.0 / 23.0 + z * p;
+    p = 2.0 / 21.0 + z * p;
+    p = 2.0 / 19.0 + z * p;
+    p = 2.0 / 17.0 + z * p;
+    p = 2.0 / 15.0 + z * p;
+    p = 2.0 / 13.0 + z * p;
+    p = 2.0 / 11.0 + z * p;
+    p = 2.0 / 9.0 + z * p;
+    p = 2.0 / 7.0 + z * p;
+    p = 2.0 / 5.0 + z * p;
+    p = 2.0 / 3.0 + z * p;
+    const double lnm = 2.0 * q + q * (z * p);
+    const double ef = (double)e;
+    return ef * kLn2Hi64 + (lnm + ef * kLn2Lo64);
+}
+
+// The inverse normal CDF of a draw u = j * 2^-53, j = 0 .. 2^53 - 1, as a float32: M. J. Wichura's AS 241 PPND16
+// evaluated in FLOAT64 on a float32 argument, rounded to float32 once at the end.
+//   p = float32(u) for u < 1/2, float32(1 - u) otherwise (1 - u is exact), raised to 2^-54 so that u = 0 is finite (-8.29);
+//   both halves run the same arithmetic on double(p) and differ in the sign only (q is negated exactly):
+//   p >= 0.075f:  q = p - 1/2 (1/2 - p in the upper half: normal32(1/2) is +0), r = 0.180625 - q * q, x = (q A(r)) / B(r)
+//   else r = sqrt(-log64(p));  r <= 5: r = r - 1.6, x = C(r) / D(r);  else r = r - 5, x = E(r) / F(r); negated in the
+//        lower half.  A .. F by Horner from the leading coefficient (c + r * acc), one float64 rounding per operation.
+// Why float64, where everything else here is float32: the function must not decrease in u.  Neighbouring float32 p lie
+// at least 2^-24 p apart, which moves the exact quantile by more than 7e-9, a million times the float64 evaluation's error
+// and PPND16's own 1e-16, branch joins included: the float64 values are strictly increasing in p, and one final rounding
+// to float32 keeps their order.  (A float32 evaluation moves by 1.5 ulp per step of p near |x| = 0.5 and errs by more.)
+// tests/test_sde_logic.py checks the order on every float32 p around the joins and on a dense sample; profiles/sde.md
+// records the run over all 4.4e8 float32 p of [2^-54, 1/2].
+RF_HD float normal32(double u)
+{
+    const bool upper = u >= 0.5;
+    float pf = upper ? (float)(1.0 - u) : (float)u;
+    if (pf < 5.5511151231257827e-17f)
+        pf = 5.5511151231257827e-17f;
+    const double p = (double)pf;
+    if (pf >= 0.075f) {
+        const double q = upper ? 0.5 - p : p - 0.5;
+        const double r = 0.180625 - q * q;
+        double a = 2.5090809287301226727e+3;
+        a = 3.3430575583588128105e+4 + r * a;
+        a = 6.7265770927008700853e+4 + r * a;
+        a = 4.5921953931549871457e+4 + r * a;
+        a = 1.3731693765509461125e+4 + r * a;
+        a = 1.9715909503065514427e+3 + r * a;
+        a = 1.3314166789178437745e+2 + r * a;
+        a = 3.3871328727963666080e+0 + r * a;
+        double b = 5.2264952788528545610e+3;
+        b = 2.8729085735721942674e+4 + r * b;
+        b = 3.9307895800092710610e+4 + r * b;
+        b = 2.1213794301586595867e+4 + r * b;
+        b = 5.3941960214247511077e+3 + r * b;
+        b = 6.8718700749205790830e+2 + r * b;
+        b = 4.2313330701600911252e+1 + r * b;
+        b = 1.0 + r * b;
+        return (float)((q * a) / b);
+    }
+    double r = sqrt(-log64(p));
+    double x;
+    if (r <= 5.0) {
+        r = r - 1.6;
+        double c = 7.74545014278341407640e-4;
+        c = 2.27238449892691845833e-2 + r * c;
+        c = 2.41780725177450611770e-1 + r * c;
+        c = 1.27045825245236838258e+0 + r * c;
+        c = 3.64784832476320460504e+0 + r * c;
+        c = 5.76949722146069140550e+0 + r * c;
+        c = 4.63033784615654529590e+0 + r * c;
+        c = 1.42343711074968357734e+0 + r * c;
+        double d = 1.05075007164441684324e-9;
+        d = 5.47593808499534494600e-4 + r * d;
+        d = 1.51986665636164571966e-2 + r * d;
+        d = 1.48103976427480074590e-1 + r * d;
+        d = 6.89767334985100004550e-1 + r * d;
+        d = 1.67638483018380384940e+0 + r * d;
+        d = 2.05319162663775882187e+0 + r * d;
+        d = 1.0 + r * d;
+        x = c / d;
+    } else {
+        r = r - 5.0;
+        double e = 2.01033439929228813265e-7;
+        e = 2.71155556874348757815e-5 + r * e;
+        e = 1.24266094738807843860e-3 + r * e;
+        e = 2.65321895265761230930e-2 + r * e;
+        e = 2.96560571828504891230e-1 + r * e;
+        e = 1.78482653991729133580e+0 + r * e;
+        e = 5.46378491116411436990e+0 + r * e;
+        e = 6.65790464350110377720e+0 + r * e;
+        double f = 2.04426310338993978564e-15;
+        f = 1.42151175831644588870e-7 + r * f;
+        f = 1.84631831751005468180e-5 + r * f;
+        f = 7.86869131145613259100e-4 + r * f;
+        f = 1.48753612908506148525e-2 + r * f;
+        f = 1.36929880922735805310e-1 + r * f;
+        f = 5.99832206555887937690e-1 + r * f;
+        f = 1.0 + r * f;
+        x = e / f;
+    }
+    return (float)(upper ? x : -x);
 }
 
 // tanh(x) = sign(x) (1 - t) / (1 + t), t = exp32(-2 |x|): +-0 stays +-0 (t = 1), +-inf is +-1 (t = 0); NaN is NaN.
@@ -162,6 +294,54 @@ RF_HD void policy_head(const float *l, int A, bool deterministic, double u, floa
     const int a = deterministic ? first : policy_select(work, A, u);
     *action = a;
     *log_prob = policy_canonical((l[a] - m) - log32(s));
+}
+
+// ---- the state-dependent-exploration Gaussian head (include/reinfocus_hip.h, "sde policy") ----
+constexpr float kSdeEpsilon = 1e-6f;
+constexpr float kSdeHalfLog2Pi = 0.9189385332046727f, kSdeEntropy0 = 1.4189385332046727f; // 1/2 log 2 pi; 1/2 + that
+
+RF_HD bool sde_finite(float x)
+{
+    return x >= -3.4028234663852886e38f && x <= 3.4028234663852886e38f;
+}
+
+// std2_k = std_k * std_k, std_k = expw32(log_std_k)
+RF_HD float sde_std2(float log_std)
+{
+    const float s = expw32(log_std);
+    return s * s;
+}
+
+// sigma = sqrt32(var + 1e-6), var = the sum over k in index order, from +0, of (h_k * h_k) * std2_k
+RF_HD float sde_sigma(const float *h, int h_stride, const float *std2, int K)
+{
+    float var = 0.0f;
+    for (int k = 0; k < K; ++k) {
+        const float x = h[(size_t)k * (size_t)h_stride];
+        var = var + (x * x) * std2[k];
+    }
+    return sqrtf(var + kSdeEpsilon);
+}
+
+// log N(a; mu, sigma): NaN where sigma is not finite (log32 has no value there)
+RF_HD float sde_log_prob(float a, float mu, float sigma)
+{
+    if (!sde_finite(sigma))
+        return bits_f32(kPolicyNaN);
+    const float t = a - mu;
+    const float q = (t * t) / (2.0f * (sigma * sigma));
+    return policy_canonical(((-q) - log32(sigma)) - kSdeHalfLog2Pi);
+}
+
+RF_HD float sde_entropy(float sigma)
+{
+    return sde_finite(sigma) ? kSdeEntropy0 + log32(sigma) : bits_f32(kPolicyNaN);
+}
+
+// what goes to the environment: the raw action clamped to [-1, 1]; NaN stays NaN
+RF_HD float sde_env_action(float a)
+{
+    return policy_canonical(a < -1.0f ? -1.0f : (a > 1.0f ? 1.0f : a));
 }
 
 // Draw number `lane` after the generator state the host passed: Generator(PCG64DXSM).random()'s (next64 >> 11) * 2^-53

@@ -17,6 +17,9 @@
 //                        reads what another block of its launch writes.
 // No atomics, no grid synchronisation.  The scalar arithmetic is plain C++ (RF_HD): tests/ppocheck loops over the same
 // functions on the host.
+// The Gaussian head of "sde policy" (rf_sde_update) is the same three kernels: ppo_backward_kernel<true> runs sde_pi_sample
+// in place of ppo_pi_sample and leaves one float per sample in the workspace, ppo_gradient_kernel's threads past the two
+// nets sum the log_std gradients from it, and ppo_adam_kernel covers the P + L parameters of sde_layout (tests/sdecheck).
 #pragma once
 
 #include "rf_policy.h"
@@ -73,6 +76,7 @@ struct PpoWork {
     unsigned partials;
     unsigned max_batch;
     unsigned total;
+    unsigned sde;     // [max_batch]: (dLoss / dsigma_b) / sigma_b of the Gaussian head (sde_layout only; taken last)
 };
 
 RF_HD bool ppo_work(const PolicyLayout &L, int max_batch, PpoWork &w)
@@ -103,6 +107,8 @@ RF_HD bool ppo_work(const PolicyLayout &L, int max_batch, PpoWork &w)
     if (w.partials > (unsigned)kPpoMaxPartials)
         return false;
     w.partial = take(2 * w.partials);
+    if (L.sde != 0)
+        w.sde = take(rows);
     w.max_batch = rows;
     w.total = at;
     return true;
@@ -132,6 +138,20 @@ RF_HD float ppo_normalised(float adv, double mean, double var)
     return (float)(((double)adv - mean) / (sqrt(var) + 1e-8));
 }
 
+// Definition steps 4 and 5 from d = log_prob - old_log_prob on, shared by both heads: the loss terms, and g_b
+RF_HD float ppo_surrogate(float d, float adv, float c, float *pg, float *kl, float *clipped)
+{
+    const float ratio = d <= 0.0f ? exp32(d) : 1.0f / exp32(-d);
+    const float lo = 1.0f - c, hi = 1.0f + c;
+    const float cl = ratio < lo ? lo : (ratio > hi ? hi : ratio);
+    const float surr1 = adv * ratio, surr2 = adv * cl;
+    *pg = -(surr2 < surr1 ? surr2 : surr1);
+    const float r1 = ratio - 1.0f;
+    *kl = r1 - d;
+    *clipped = (r1 < 0.0f ? -r1 : r1) > c ? 1.0f : 0.0f;
+    return ((ratio >= lo && ratio <= hi) || surr1 < surr2) ? surr1 : 0.0f;
+}
+
 // Definition steps 3 to 5 of one sample's pi head: logits l[0 .. A-1], its action a (clamped), the stored
 // log-probability, A_b.  work: A floats (the e_i).  dlogit[i * stride] receives the head deltas.
 RF_HD void ppo_pi_sample(const float *l, int A, int a, float old_log_prob, float adv, float c, float ec, float Bf,
@@ -156,17 +176,8 @@ RF_HD void ppo_pi_sample(const float *l, int A, int a, float old_log_prob, float
     }
     const float H = -acc;
     const float d = ((l[a] - m) - lse) - old_log_prob;
-    const float ratio = d <= 0.0f ? exp32(d) : 1.0f / exp32(-d);
-    const float lo = 1.0f - c, hi = 1.0f + c;
-    const float cl = ratio < lo ? lo : (ratio > hi ? hi : ratio);
-    const float surr1 = adv * ratio, surr2 = adv * cl;
-    *pg = -(surr2 < surr1 ? surr2 : surr1);
     *entropy = H;
-    const float r1 = ratio - 1.0f;
-    *kl = r1 - d;
-    *clipped = (r1 < 0.0f ? -r1 : r1) > c ? 1.0f : 0.0f;
-    const float g = ((ratio >= lo && ratio <= hi) || surr1 < surr2) ? surr1 : 0.0f;
-    const float ng = -g;
+    const float ng = -ppo_surrogate(d, adv, c, pg, kl, clipped);
     for (int i = 0; i < A; ++i) {
         const float logp = (l[i] - m) - lse;
         const float p = work[i] / s;
@@ -174,6 +185,24 @@ RF_HD void ppo_pi_sample(const float *l, int A, int a, float old_log_prob, float
         const float ent = work[i] == 0.0f ? 0.0f : (ec * p) * (logp + H);
         dlogit[(size_t)i * (size_t)stride] = (pull + ent) / Bf;
     }
+}
+
+// The same steps of the Gaussian head ("sde policy", steps 3', 5'): the stored raw action a, the mean mu, sigma.
+// dmu is the head delta; dsig = (dLoss / dsigma_b) / sigma_b, what the log_std gradient sums.  A row whose sigma or
+// log_prob is not finite makes both NaN, so the update ends in RF_PPO_NONFINITE.
+RF_HD void sde_pi_sample(float mu, float sigma, float a, float old_log_prob, float adv, float c, float ec, float Bf,
+                         float *dmu, float *dsig, float *pg, float *entropy, float *kl, float *clipped)
+{
+    const float lp = sde_log_prob(a, mu, sigma);
+    *entropy = sde_entropy(sigma);
+    const float ng = -ppo_surrogate(lp - old_log_prob, adv, c, pg, kl, clipped);
+    const float t = a - mu;
+    const float v2 = sigma * sigma;
+    const float dlp_dmu = t / v2;
+    const float dlp_dsig = (t * t) / (v2 * sigma) - 1.0f / sigma;
+    const bool fine = sde_finite(sigma) && sde_finite(lp);
+    *dmu = fine ? (ng * dlp_dmu) / Bf : bits_f32(kPolicyNaN);
+    *dsig = fine ? ((ng * dlp_dsig - ec / sigma) / Bf) / sigma : bits_f32(kPolicyNaN);
 }
 
 RF_HD void ppo_vf_sample(float v, float ret, float vc2, float Bf, float *vl, float *dv)
@@ -223,6 +252,10 @@ RF_HD PpoSource ppo_source(const PolicyLayout &L, const PpoWork &W, unsigned p)
             }
             return s;
         }
+    // past both nets: log_std_j of the Gaussian head, from the last pi activations and the per-sample sigma terms
+    s.k = -2, s.j = (int)(p - L.log_std);
+    s.x = W.h[0][L.layers[0] - 1], s.x_stride = (int)L.sde;
+    s.d = W.sde, s.d_stride = 1;
     return s;
 }
 
@@ -246,6 +279,28 @@ RF_HD float ppo_gradient(const float *ws, const PpoSource &s, int B)
     for (int b = 0; b < B; ++b)
         acc = acc + x[(size_t)b * (size_t)s.x_stride] * d[(size_t)b * (size_t)s.d_stride];
     return acc;
+}
+
+// "sde policy" step 7': dlog_std_j = the sum over b = 0 .. B-1, from +0, of ((h[b][j] * h[b][j]) * std2_j) * dsig[b]
+RF_HD float sde_log_std_gradient(const float *ws, const PpoSource &s, int B, float std2)
+{
+    const float *h = ws + s.x + s.j, *d = ws + s.d;
+    float acc = 0.0f;
+#if defined(__HIPCC__)
+#pragma unroll 8
+#endif
+    for (int b = 0; b < B; ++b) {
+        const float x = h[(size_t)b * (size_t)s.x_stride];
+        acc = acc + ((x * x) * std2) * d[b];
+    }
+    return acc;
+}
+
+RF_HD float ppo_parameter_gradient(const PolicyLayout &L, const PpoWork &W, const float *ws, const float *params, unsigned p,
+                                   int B)
+{
+    const PpoSource s = ppo_source(L, W, p);
+    return s.k == -2 ? sde_log_std_gradient(ws, s, B, sde_std2(params[L.log_std + (unsigned)s.j])) : ppo_gradient(ws, s, B);
 }
 
 // Definition steps 8 and 9: the constants of one update, then one parameter
@@ -359,9 +414,12 @@ __device__ __forceinline__ void ppo_store_tile(float *__restrict__ out, const fl
     }
 }
 
+// kSde: the Gaussian head of "sde policy" (L from sde_layout; actions float32 [N]) in place of the Categorical one
+// (actions int64 [N])
+template <bool kSde>
 __global__ __launch_bounds__(kPpoThreads) void ppo_backward_kernel(
     PolicyLayout L, PpoWork W, PpoHyper hy, const float *__restrict__ params, const PpoHeader *__restrict__ header,
-    float *__restrict__ ws, int N, const float *__restrict__ obs, const int64_t *__restrict__ actions,
+    float *__restrict__ ws, int N, const float *__restrict__ obs, const void *__restrict__ actions_any,
     const float *__restrict__ old_log_probs, const float *__restrict__ advantages, const float *__restrict__ returns,
     int B, const int64_t *__restrict__ index)
 {
@@ -371,6 +429,8 @@ __global__ __launch_bounds__(kPpoThreads) void ppo_backward_kernel(
     __shared__ float s_logit[kPolicyTile][kPolicyMaxActions];
     __shared__ float s_work[kPolicyTile][kPolicyMaxActions];
     __shared__ double s_red[kPpoMaxBatch];
+    const int64_t *__restrict__ actions = static_cast<const int64_t *>(actions_any); // (!kSde)
+    const float *__restrict__ raw_actions = static_cast<const float *>(actions_any); // (kSde)
     const int tid = threadIdx.x;
     const int net = (int)blockIdx.y;
     const int b0 = (int)blockIdx.x * kPolicyTile;
@@ -385,8 +445,13 @@ __global__ __launch_bounds__(kPpoThreads) void ppo_backward_kernel(
             if (b < B) {
                 const int64_t raw = index[b];
                 const int64_t row = ppo_clamp(raw, N);
-                const int64_t action = actions[row];
-                bad |= raw != row || action < 0 || action >= L.n_actions;
+                if (kSde) {
+                    const float action = raw_actions[row];
+                    bad |= raw != row || action != action;
+                } else {
+                    const int64_t action = actions[row];
+                    bad |= raw != row || action < 0 || action >= L.n_actions;
+                }
                 a = (double)advantages[row];
             }
             s_red[b] = a;
@@ -438,6 +503,9 @@ __global__ __launch_bounds__(kPpoThreads) void ppo_backward_kernel(
         s_logit[e][o] = policy_dot(&s_act[cur][0][e], kPolicyTile, params + L.weight[net][layers] + o, O,
                                    params[L.bias[net][layers] + o], K);
     }
+    float *std2 = &s_work[0][0]; // (kSde: the K <= 256 squared standard deviations; s_work is otherwise unused then)
+    if (kSde && net == 0 && tid < K)
+        std2[tid] = sde_std2(params[L.log_std + tid]);
     __syncthreads();
     if (tid < kPolicyTile) { // one lane per sample: the loss terms and the head deltas
         const int b = b0 + tid;
@@ -448,8 +516,17 @@ __global__ __launch_bounds__(kPpoThreads) void ppo_backward_kernel(
                 const float adv = advantages[row];
                 const float A = normalise ? ppo_normalised(adv, mean, var) : adv;
                 float pg, H, kl, clipped;
-                ppo_pi_sample(&s_logit[tid][0], L.n_actions, (int)ppo_clamp(actions[row], L.n_actions), old_log_probs[row], A,
-                              hy.clip, hy.ent, Bf, &s_work[tid][0], &s_head[0][tid], kPolicyTile, &pg, &H, &kl, &clipped);
+                if (kSde) {
+                    const float sigma = sde_sigma(&s_act[cur][0][tid], kPolicyTile, std2, K);
+                    float dmu, dsig;
+                    sde_pi_sample(s_logit[tid][0], sigma, raw_actions[row], old_log_probs[row], A, hy.clip, hy.ent, Bf, &dmu,
+                                  &dsig, &pg, &H, &kl, &clipped);
+                    s_head[0][tid] = dmu;
+                    ws[W.sde + b] = dsig;
+                } else
+                    ppo_pi_sample(&s_logit[tid][0], L.n_actions, (int)ppo_clamp(actions[row], L.n_actions),
+                                  old_log_probs[row], A, hy.clip, hy.ent, Bf, &s_work[tid][0], &s_head[0][tid], kPolicyTile,
+                                  &pg, &H, &kl, &clipped);
                 float *loss = ws + W.loss + b;
                 loss[0] = pg, loss[2 * W.max_batch] = H, loss[3 * W.max_batch] = kl, loss[4 * W.max_batch] = clipped;
             } else {
@@ -479,14 +556,15 @@ __global__ __launch_bounds__(kPpoThreads) void ppo_backward_kernel(
     }
 }
 
-__global__ __launch_bounds__(kPpoThreads) void ppo_gradient_kernel(PolicyLayout L, PpoWork W, float *__restrict__ ws, int B)
+__global__ __launch_bounds__(kPpoThreads) void ppo_gradient_kernel(PolicyLayout L, PpoWork W, float *__restrict__ ws, int B,
+                                                                   const float *__restrict__ params)
 {
     __shared__ double s_red[kPpoLeaves];
     const int tid = threadIdx.x;
     const unsigned p = blockIdx.x * (unsigned)kPpoLeaves + (unsigned)tid;
     double square = 0.0;
     if (p < L.total) {
-        const float g = ppo_gradient(ws, ppo_source(L, W, p), B);
+        const float g = ppo_parameter_gradient(L, W, ws, params, p, B);
         ws[W.grad + p] = g;
         square = (double)g * (double)g;
     }

@@ -13,7 +13,8 @@ torch's: that is the one deliberate difference from stable-baselines3 (DESIGN.md
     DevicePolicy   the same methods over torch tensors on a device-resident environment's GPU: one launch per call on
                    torch's current stream, parameters in one packed tensor, nothing waits for the host
 
-Continuous action spaces (the reference trains ContinuousJumps with gSDE) are out of scope and refused.
+Continuous action spaces (the reference trains ContinuousJumps with gSDE) are out of scope of this head and refused by
+it: environments/sde.py has the Gaussian head for them (SdePolicySpec, SdePolicy, DeviceSdePolicy).
 
 torch is imported lazily, by DevicePolicy only (reinfocus_amd/torch_interop.py says why import order matters).
 """
@@ -67,7 +68,7 @@ def exp32(x):
 
 
 def log32(s):
-    """rf_policy_math.h log32, for s in [1, 64]."""
+    """rf_policy_math.h log32, for every positive normal s."""
     s = np.asarray(s, dtype=f32)
     u = _bits(s)
     with np.errstate(all="ignore"):
@@ -168,6 +169,9 @@ class MlpPolicySpec:
     """The shape of the network and the packing rule of its parameters.  Packed: one float32 vector, every matrix
     transposed ([in][out]), pi first: W0^T, b0, (W1^T, b1,) Wa^T, ba, then vf alike with the value head."""
 
+    kind = "categorical"  # (what Rollout.collect and the learners dispatch on)
+    MIN_ACTIONS = 2
+
     def __init__(self, obs_width, n_actions, pi=(64, 64), vf=(64, 64), activation="tanh"):
         self.obs_width, self.n_actions = int(obs_width), int(n_actions)
         self.pi, self.vf = tuple(int(w) for w in pi), tuple(int(w) for w in vf)
@@ -176,8 +180,8 @@ class MlpPolicySpec:
             raise ValueError(f"activation {activation!r} is not one of {sorted(ACTIVATIONS)}")
         if not 1 <= self.obs_width <= MAX_WIDTH:
             raise ValueError(f"obs_width {obs_width} is not in 1 .. {MAX_WIDTH}")
-        if not 2 <= self.n_actions <= MAX_ACTIONS:
-            raise ValueError(f"n_actions {n_actions} is not in 2 .. {MAX_ACTIONS}")
+        if not self.MIN_ACTIONS <= self.n_actions <= MAX_ACTIONS:
+            raise ValueError(f"n_actions {n_actions} is not in {self.MIN_ACTIONS} .. {MAX_ACTIONS}")
         for name, widths in (("pi", self.pi), ("vf", self.vf)):
             if len(widths) not in (1, 2) or not all(1 <= w <= MAX_WIDTH for w in widths):
                 raise ValueError(f"{name}={widths!r} is not 1 or 2 hidden layers of width 1 .. {MAX_WIDTH}")
@@ -332,16 +336,22 @@ class DevicePolicy(_Draws):
     the results are tensors the policy owns and the next call overwrites."""
 
     def __init__(self, env, spec, seed=None):
+        self._device_env(env)
+        _refuse_box(env.single_action_space)
+        if env.single_action_space.n != spec.n_actions:
+            raise ValueError(f"the spec has {spec.n_actions} actions, the environment {env.single_action_space.n}")
+        self._attach(env, spec, seed)
+
+    def _device_env(self, env):
         from reinfocus_amd.environments import harness
 
         if not isinstance(env, harness._DeviceVectorEnv):
             if hasattr(env, "_no_tensors"):  # (a sharded environment: its own refusal says why)
                 env._no_tensors()
-            raise TypeError(f"DevicePolicy needs a device-resident environment, not {type(env).__name__} (the numpy "
-                            "twins have Policy)")
-        _refuse_box(env.single_action_space)
-        if env.single_action_space.n != spec.n_actions:
-            raise ValueError(f"the spec has {spec.n_actions} actions, the environment {env.single_action_space.n}")
+            raise TypeError(f"{type(self).__name__} needs a device-resident environment, not {type(env).__name__} (the "
+                            "numpy twins have Policy and SdePolicy)")
+
+    def _attach(self, env, spec, seed):
         self._io = env._tensor_io()  # (ValueError, as step_tensors': a host initializer, a render_mode)
         from reinfocus_amd import torch_interop
 

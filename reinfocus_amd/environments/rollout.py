@@ -16,8 +16,9 @@ restatement and the oracle; rollout_gae_kernel (csrc/rf_rollout.h) computes the 
                    and nothing waits for the host
 
 collect(policy) runs a whole rollout with a policy of environments/policy.py (Policy for Rollout, DevicePolicy for
-DeviceRollout): on the device a step is then one policy launch, which writes rows of the slabs, and the environment's
-step from those rows.
+DeviceRollout) or, over a Box(-1, 1, (1,)) action space, of environments/sde.py (SdePolicy, DeviceSdePolicy: the raw
+action goes into the slab, the clamped one to the step, and sde_sample_freq says when the noise is resampled): on the
+device a step is then one policy launch, which writes rows of the slabs, and the environment's step from those rows.
 
 torch is imported lazily, by DeviceRollout only (reinfocus_amd/torch_interop.py says why import order matters).
 """
@@ -118,12 +119,28 @@ class _Bookkeeping:
         self._complete = True
         return self._bootstrapped == self.n_steps
 
-    def _collecting(self):
+    def _collecting(self, policy, sde_sample_freq):
+        """True: `policy` has the Gaussian head of environments/sde.py."""
         if self._t != 0:
             raise ValueError("collect() runs a whole rollout: start() first, and take no step() before it")
-        if not _index_task(self.env):
+        sde = getattr(getattr(policy, "spec", None), "kind", None) == "sde"
+        if sde and _index_task(self.env):
+            raise ValueError("collect() was given a policy with a Gaussian head, and the environment's action space is "
+                             f"{self.env.single_action_space!r}: Discrete action spaces have Policy / DevicePolicy")
+        if not sde and not _index_task(self.env):
             raise ValueError("collect() takes a policy with a Categorical head, and the environment's action space is "
                              f"{self.env.single_action_space!r}: continuous action spaces are out of scope")
+        if int(sde_sample_freq) != sde_sample_freq or (sde_sample_freq < 1 and sde_sample_freq != -1):
+            raise ValueError(f"sde_sample_freq {sde_sample_freq!r} is not -1 or a positive integer")
+        if not sde and sde_sample_freq != -1:
+            raise ValueError("sde_sample_freq belongs to the policies of environments/sde.py")
+        return sde
+
+    @staticmethod
+    def _resample(t, sde_sample_freq):
+        """stable-baselines3's collect_rollouts: reset_noise before the loop, and in it when
+        sde_sample_freq > 0 and t % sde_sample_freq == 0 (so step 0 draws twice, as there)."""
+        return sde_sample_freq > 0 and t % sde_sample_freq == 0
 
     def _finished(self):
         if not (self._complete and self._t == self.n_steps):
@@ -159,12 +176,14 @@ class Rollout(_Bookkeeping):
         self._begin(obs)
         self.observations[0] = self.observations[self.n_steps] if obs is None else obs
 
-    def step(self, actions, values, log_probs):
+    def step(self, actions, values, log_probs, env_actions=None):
+        """env_actions: what the environment is stepped with where that is not what the slab keeps (an sde policy's
+        clamped actions next to its raw ones)."""
         t = self._next_step()
         self.actions[t] = np.asarray(actions).reshape(self.num_envs)
         self.values[t] = np.asarray(values).reshape(self.num_envs)
         self.log_probs[t] = np.asarray(log_probs).reshape(self.num_envs)
-        result = self.env.step(actions)
+        result = self.env.step(actions if env_actions is None else env_actions)
         self.observations[t + 1], self.rewards[t], self.truncated[t] = result[0], result[1], result[3]
         self._t = t + 1
         return result
@@ -178,17 +197,23 @@ class Rollout(_Bookkeeping):
                                                   self.gamma, self.gae_lambda)
         return self.advantages, self.returns
 
-    def collect(self, policy, deterministic=False):
-        """The whole rollout after start(), by a policy.Policy: act, step and -- with episode records -- the bootstrap
-        of every step, then finish(V(observations[T])).  V(final_observation) of step t - 1 comes from the act of step t
-        (the last one from the values-only call that gives last_values).  Equal to the explicit loop."""
-        self._collecting()
+    def collect(self, policy, deterministic=False, sde_sample_freq=-1):
+        """The whole rollout after start(), by a policy.Policy or an sde.SdePolicy: act, step and -- with episode
+        records -- the bootstrap of every step, then finish(V(observations[T])).  V(final_observation) of step t - 1
+        comes from the act of step t (the last one from the values-only call that gives last_values).  Equal to the
+        explicit loop.  With an SdePolicy the noise is reset first and then whenever t % sde_sample_freq == 0 (never
+        again with -1), the slab keeps the raw action and the environment gets the clamped one."""
+        sde = self._collecting(policy, sde_sample_freq)
+        if sde:
+            policy.reset_noise(self.num_envs)
         final_obs = None
         for t in range(self.n_steps):
-            actions, values, log_probs, final_values = policy.act(self.observations[t], final_obs, deterministic)
+            if sde and self._resample(t, sde_sample_freq):
+                policy.reset_noise(self.num_envs)
+            actions, values, log_probs, final_values, *clamped = policy.act(self.observations[t], final_obs, deterministic)
             if final_obs is not None:
                 self.bootstrap(final_values)
-            info = self.step(actions, values, log_probs)[4]
+            info = self.step(actions, values, log_probs, *clamped)[4]
             final_obs = info["final_observation"] if self._records else None
         if final_obs is None:
             return self.finish(policy.values(self.observations[self.n_steps]))
@@ -255,6 +280,7 @@ class DeviceRollout(_Bookkeeping):
         self.values, self.log_probs, self.final_values, self.advantages, self.returns = (
             slab(torch.float32) for _ in range(5))
         self._last_values = None  # (collect()'s V(observations[T]), made on first use)
+        self._env_actions = None  # (collect()'s clamped actions of an sde policy, made on first use)
 
     def _row(self, tensor, what):
         """`tensor` as a float32-or-whatever [n] row on the buffer's GPU (a view, never a host copy)."""
@@ -275,16 +301,19 @@ class DeviceRollout(_Bookkeeping):
             self._io._on_device(obs, "obs")
             self.observations[0].copy_(obs)
 
-    def step(self, actions, values, log_probs):
+    def step(self, actions, values, log_probs, env_actions=None):
         """Stores the three tensors in row t and steps the environment into rows of the slabs; returns what
-        step_tensors returned (its obs, rewards and truncated ARE the buffer's rows)."""
+        step_tensors returned (its obs, rewards and truncated ARE the buffer's rows).  env_actions: as Rollout.step."""
         t = self._next_step()
         self._io.checked_actions(actions)  # (before anything is stored)
+        if env_actions is not None:
+            self._io.checked_actions(env_actions)
         values, log_probs = self._row(values, "values"), self._row(log_probs, "log_probs")
         self.actions[t].copy_(actions.reshape(self.num_envs))
         self.values[t].copy_(values)
         self.log_probs[t].copy_(log_probs)
-        result = self.env.step_tensors(actions, out=(self.observations[t + 1], self.rewards[t], self.truncated[t]))
+        result = self.env.step_tensors(actions if env_actions is None else env_actions,
+                                       out=(self.observations[t + 1], self.rewards[t], self.truncated[t]))
         self._t = t + 1
         return result
 
@@ -306,21 +335,29 @@ class DeviceRollout(_Bookkeeping):
                                      self.returns.data_ptr(), self._io._stream())
         return self.advantages, self.returns
 
-    def collect(self, policy, deterministic=False):
-        """The whole rollout after start(), by a policy.DevicePolicy: per step ONE policy launch, which writes
+    def collect(self, policy, deterministic=False, sde_sample_freq=-1):
+        """The whole rollout after start(), by a policy.DevicePolicy or an sde.DeviceSdePolicy (whose noise is reset as
+        Rollout.collect says -- one launch each time --, whose raw action goes into actions[t] and whose clamped one,
+        a row the rollout owns, to the step): per step ONE policy launch, which writes
         actions[t], values[t], log_probs[t] and -- with episode records, from the final_observation of the step before
         -- final_values[t - 1] straight into the slabs (no row copies), and the environment's step from actions[t];
         after step T a values-only launch gives last_values and final_values[T - 1]; then finish().  As bytes what the
         explicit loop of act / step / bootstrap / finish gives, and Rollout.collect with the twin policy.  Nothing
         waits for the host."""
-        self._collecting()
+        sde = self._collecting(policy, sde_sample_freq)
+        if sde:
+            policy.reset_noise(self.num_envs)
+            if self._env_actions is None:
+                self._env_actions = self._torch.zeros(self.num_envs, dtype=self._torch.float32, device=self.device)
         final_obs = None
         for _ in range(self.n_steps):
             t = self._next_step()
             final_out = None if final_obs is None else self.final_values[self._bootstrap_step()]
-            policy.act(self.observations[t], final_obs, deterministic,
-                       out=(self.actions[t], self.values[t], self.log_probs[t], final_out))
-            info = self.env.step_tensors(self.actions[t],
+            if sde and self._resample(t, sde_sample_freq):
+                policy.reset_noise(self.num_envs)
+            out = (self.actions[t], self.values[t], self.log_probs[t], final_out)
+            policy.act(self.observations[t], final_obs, deterministic, out=out + (self._env_actions,) if sde else out)
+            info = self.env.step_tensors(self._env_actions if sde else self.actions[t],
                                          out=(self.observations[t + 1], self.rewards[t], self.truncated[t]))[4]
             self._t = t + 1
             final_obs = info["final_observation"] if self._records else None
