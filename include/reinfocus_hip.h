@@ -1004,6 +1004,66 @@ int rf_sde_update(rf_ctx *ctx, const rf_policy_desc *policy, const rf_ppo_desc *
                   const float *d_advantages, const float *d_returns, int B, const long long *d_index, float *d_stats,
                   void *caller_stream);
 
+/* ---- lstm policy: the recurrent PPO actor-critic forward with its state and sampling in one launch ---------------------
+ * The reference's other two training configurations (examples/ppo_lstm_*.yml) run policy: 'MlpLstmPolicy', sb3-contrib's
+ * RecurrentPPO with RecurrentActorCriticPolicy at its defaults: lstm_hidden_size=256, n_lstm_layers=1, shared_lstm=False,
+ * enable_critic_lstm=True.  No reference counterpart.  Needs no environment: the context only says which GPU.
+ * Out of scope: back-propagation through time (the update), the Gaussian (sde) head on top of the LSTM, n_lstm_layers > 1,
+ * shared_lstm=True, enable_critic_lstm=False.
+ *
+ * One definition, numpy twin (environments/lstm.py lstm_numpy), host build (tests/lstmcheck) and kernel (csrc/rf_lstm.h)
+ * alike; the scalar functions are csrc/rf_policy_math.h.  Everything is float32, one rounding per operation, nothing
+ * contracted; no MFMA.
+ *
+ *  L1 Network.  Two nets, pi and vf; each is ONE LSTM layer of input width obs_width D (1 .. RF_POLICY_MAX_WIDTH) and
+ *     lstm_hidden units H (1 .. RF_POLICY_MAX_WIDTH, the same for both nets), followed by the MLP of "policy" (1 or 2 hidden
+ *     layers, input width H) and its head: Categorical over n_actions for pi, one output for vf, exactly as "policy".
+ *  L2 Cell: torch.nn.LSTM's, gates in torch's order q = i, f, g, o.  For unit j and gate q:
+ *     a = b_ih[q][j];  a = a + b_hh[q][j];  for k = 0 .. D-1: a = a + x_k * W_ih[q][j][k];
+ *     for k = 0 .. H-1: a = a + h_k * W_hh[q][j][k]  -- a float32 multiply, then a float32 add, in that order, no FMA.
+ *     i = sigmoid32(a_i), f = sigmoid32(a_f), g = tanh32(a_g), o = sigmoid32(a_o);
+ *     c' = f * c + i * g (two multiplies, then one add);  h' = o * tanh32(c').  h' is the MLP's input.
+ *  L3 sigmoid32(x): t = exp32(-|x|) (exp32 is defined for arguments <= 0 only); x >= 0 ? 1 / (1 + t) : t / (1 + t);
+ *     sigmoid32(NaN) is NaN.  tanh32 and exp32 as "policy".
+ *  L4 Episode starts.  episode_starts uint8[n]; any non-zero byte is a start: that environment's h and c of BOTH nets are
+ *     replaced by +0.0 before the cell -- a select, not sb3-contrib's multiplication by (1 - start): a NaN or inf in a dead
+ *     state does not survive a reset (a deliberate difference).
+ *  L5 State.  float32 [2 nets: pi, vf][2: h, c][n][H].  A forward reads d_state_in and, if d_state_out is given, writes
+ *     h' and c' of both nets there.  d_state_out may be d_state_in itself (an update in place) or a range that does not
+ *     overlap it; any other overlap is refused.
+ *  L6 V(final_observation).  With d_final_obs and d_final_values a second pass of the vf net runs on final_obs, from
+ *     d_state_in as it is (NOT masked by episode_starts); it stores no state; final_values[e] is NaN where
+ *     final_obs[e][0] is NaN, as "policy".  (RecurrentPPO.collect_rollouts bootstraps a truncated step with
+ *     predict_values(terminal_obs, lstm_states.vf) on the states the forward of that step returned; here
+ *     V(final_observation) of step t - 1 comes from the call of step t, whose d_state_in are those states.)
+ *  L7 Values-only call (d_values and / or d_final_values, no pi output, no d_state_out): sb3-contrib's
+ *     predict_values(obs, lstm_states.vf, episode_starts): the vf net only, masked by episode_starts; no state is stored.
+ *     d_state_out with no pi or vf output of the pass over obs is allowed and advances the state only.
+ *  L8 Parameters: one float32 array, every matrix TRANSPOSED ([in][out] row-major: weight.T), per net, pi first:
+ *     W_ih^T [D][4H], W_hh^T [H][4H], b_ih [4H], b_hh [4H], then what "policy" packs for that net with input width H.
+ *     Both biases stay separate (state_dict() round-trips; a later update trains them as torch does).  Names:
+ *     lstm_actor. / lstm_critic. weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0; mlp_extractor.policy_net.*,
+ *     mlp_extractor.value_net.*, action_net.*, value_net.*.
+ *  L9 Head, draws, NaN and +-inf logits: exactly as "policy".  Every NaN that is stored (the state included) is 0x7fc00000.
+ *
+ *   rf_lstm_params_size    floats of the packed parameters of desc; 0 for a desc outside the limits or a NULL ctx
+ *   rf_lstm_state_size     floats of the state of n environments (4 n H); 0 if refused or n < 1
+ *   rf_lstm_forward        one launch on caller_stream, nothing allocated, nothing waited for.  d_episode_starts and
+ *                          d_state_in are needed; of d_state_out and the outputs of rf_policy_forward (each may be NULL)
+ *                          at least one must be given.  Refusals as rf_policy_forward's, all before anything is enqueued;
+ *                          also lstm_hidden outside its limits and a d_state_out that overlaps d_state_in without being it. */
+typedef struct rf_lstm_policy_desc {
+    rf_policy_desc policy; /* obs_width is the LSTMs' input width; the MLPs' input width is lstm_hidden */
+    int lstm_hidden;       /* 1 .. RF_POLICY_MAX_WIDTH */
+} rf_lstm_policy_desc;
+
+unsigned long long rf_lstm_params_size(rf_ctx *ctx, const rf_lstm_policy_desc *desc);
+unsigned long long rf_lstm_state_size(rf_ctx *ctx, const rf_lstm_policy_desc *desc, int n);
+int rf_lstm_forward(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const float *d_params, int n, const float *d_obs,
+                    const uint8_t *d_episode_starts, const float *d_final_obs, const float *d_state_in, float *d_state_out,
+                    const unsigned long long gen[4], int flags, long long *d_actions, float *d_log_probs, float *d_values,
+                    float *d_final_values, float *d_logits, void *caller_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -107,6 +107,9 @@ SYMBOLS = (
     "rf_sde_state_size",
     "rf_sde_workspace_size",
     "rf_sde_update",
+    "rf_lstm_params_size",
+    "rf_lstm_state_size",
+    "rf_lstm_forward",
     "rf_render_kernel_name",
     "rf_pixels_rendered",
     "rf_allocations_poisoned",
@@ -172,6 +175,16 @@ class PolicyDesc(ctypes.Structure):
     def __init__(self, obs_width=0, n_actions=0, activation=0, pi_layers=0, pi0=0, pi1=0, vf_layers=0, vf0=0, vf1=0):
         super().__init__(obs_width, n_actions, activation, pi_layers, (ctypes.c_int * 2)(pi0, pi1), vf_layers,
                          (ctypes.c_int * 2)(vf0, vf1))
+
+
+class LstmPolicyDesc(ctypes.Structure):
+    """rf_lstm_policy_desc (include/reinfocus_hip.h): the rf_policy_desc, then lstm_hidden."""
+
+    _fields_ = [("policy", PolicyDesc), ("lstm_hidden", ctypes.c_int)]
+
+    def __init__(self, *desc):
+        """The nine integers of rf_policy_desc in order, then lstm_hidden."""
+        super().__init__(PolicyDesc(*desc[:9]), *desc[9:])
 
 
 class PpoDesc(ctypes.Structure):
@@ -359,6 +372,11 @@ def load():
     lib.rf_sde_workspace_size.restype = ctypes.c_ulonglong
     lib.rf_sde_workspace_size.argtypes = [vp, vp, i32]
     lib.rf_sde_update.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp]
+    lib.rf_lstm_params_size.restype = ctypes.c_ulonglong
+    lib.rf_lstm_params_size.argtypes = [vp, vp]
+    lib.rf_lstm_state_size.restype = ctypes.c_ulonglong
+    lib.rf_lstm_state_size.argtypes = [vp, vp, i32]
+    lib.rf_lstm_forward.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
     lib.rf_render_kernel_name.restype = ctypes.c_char_p
     lib.rf_render_kernel_name.argtypes = [vp]
     lib.rf_pixels_rendered.restype = ctypes.c_ulonglong
@@ -774,6 +792,28 @@ class Context:
         rc = self._lib.rf_sde_update(self._h, ctypes.byref(PolicyDesc(*desc)), ctypes.byref(PpoDesc(*hyper)), params_ptr,
                                      state_ptr, workspace_ptr, rows, obs_ptr, actions_ptr, old_log_probs_ptr,
                                      advantages_ptr, returns_ptr, batch, index_ptr, stats_ptr, stream)
+        if rc != 0:
+            _check(rc)
+
+    # --- lstm policy (rf_lstm_*): the recurrent actor-critic's forward with its state -----------------------------------
+    def lstm_params_size(self, desc):
+        """rf_lstm_params_size: floats of the packed parameters of `desc` (the nine integers of rf_policy_desc in order,
+        then lstm_hidden); 0 for a desc outside the limits."""
+        return int(self._lib.rf_lstm_params_size(self._h, ctypes.byref(LstmPolicyDesc(*desc))))
+
+    def lstm_state_size(self, desc, num_envs):
+        """rf_lstm_state_size: floats of the state [2][2][num_envs][lstm_hidden]; 0 if refused."""
+        return int(self._lib.rf_lstm_state_size(self._h, ctypes.byref(LstmPolicyDesc(*desc)), num_envs))
+
+    def lstm_forward(self, desc, params_ptr, num_envs, obs_ptr, episode_starts_ptr, final_obs_ptr, state_in_ptr,
+                     state_out_ptr, gen, flags, actions_ptr, log_probs_ptr, values_ptr, final_values_ptr, logits_ptr, stream):
+        """rf_lstm_forward: the recurrent actor-critic forward over device arrays given by address (final_obs_ptr,
+        state_out_ptr and each output may be None), one launch on `stream`.  gen: the generator's four 64-bit words, or
+        None.  Only enqueues."""
+        words = None if gen is None else (ctypes.c_ulonglong * 4)(*gen)
+        rc = self._lib.rf_lstm_forward(self._h, ctypes.byref(LstmPolicyDesc(*desc)), params_ptr, num_envs, obs_ptr,
+                                       episode_starts_ptr, final_obs_ptr, state_in_ptr, state_out_ptr, words, flags,
+                                       actions_ptr, log_probs_ptr, values_ptr, final_values_ptr, logits_ptr, stream)
         if rc != 0:
             _check(rc)
 

@@ -13,6 +13,7 @@
 #include "rf_policy.h"
 #include "rf_ppo.h"
 #include "rf_sde.h"
+#include "rf_lstm.h"
 #include "rf_rollout.h"
 
 using namespace rfh;
@@ -2248,6 +2249,109 @@ int rf_sde_forward(rf_ctx *ctx, const rf_policy_desc *desc, const float *d_param
     hipLaunchKernelGGL(rf::sde_forward_kernel, dim3(tiles, pi && vf ? 2u : 1u), dim3(rf::kPolicyThreads), 0,
                        (hipStream_t)caller_stream, layout, d_params, n, d_obs, d_final_obs, sampled ? d_theta : nullptr,
                        pi ? 0 : 1, d_actions, d_env_actions, d_log_probs, d_values, d_final_values, d_mean, d_sigma);
+    RF_HIP(hipGetLastError());
+    return RF_OK;
+}
+
+unsigned long long rf_lstm_params_size(rf_ctx *ctx, const rf_lstm_policy_desc *desc)
+{
+    rf::LstmLayout layout;
+    if (ctx == nullptr || desc == nullptr || !rf::lstm_layout(*desc, layout))
+        return 0;
+    if (hipSetDevice(ctx->device) != hipSuccess) // (as every entry point; nothing of the device is needed)
+        (void)hipGetLastError();
+    return layout.total;
+}
+
+unsigned long long rf_lstm_state_size(rf_ctx *ctx, const rf_lstm_policy_desc *desc, int n)
+{
+    rf::LstmLayout layout;
+    if (ctx == nullptr || desc == nullptr || n < 1 || !rf::lstm_layout(*desc, layout))
+        return 0;
+    if (hipSetDevice(ctx->device) != hipSuccess)
+        (void)hipGetLastError();
+    return rf::lstm_state_floats(n, layout.hidden);
+}
+
+int rf_lstm_forward(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const float *d_params, int n, const float *d_obs,
+                    const uint8_t *d_episode_starts, const float *d_final_obs, const float *d_state_in, float *d_state_out,
+                    const unsigned long long gen[4], int flags, long long *d_actions, float *d_log_probs, float *d_values,
+                    float *d_final_values, float *d_logits, void *caller_stream)
+{
+    const char *fn = "rf_lstm_forward";
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", fn);
+    RF_REQUIRE(desc != nullptr && d_params != nullptr && d_obs != nullptr && d_episode_starts != nullptr &&
+               d_state_in != nullptr, "%s: NULL argument", fn);
+    rf::LstmLayout layout;
+    RF_REQUIRE(rf::lstm_layout(*desc, layout),
+               "%s: the desc is outside the limits (obs_width and lstm_hidden 1 .. %d, 1 or 2 hidden layers of width 1 .. %d "
+               "per net, n_actions 2 .. %d, activation RF_POLICY_RELU or RF_POLICY_TANH)", fn, RF_POLICY_MAX_WIDTH,
+               RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_ACTIONS);
+    RF_REQUIRE(n >= 1 && n <= (1 << 30), "%s: n = %d must be at least 1 (and at most 2^30)", fn, n);
+    RF_REQUIRE((flags & ~RF_POLICY_DETERMINISTIC) == 0, "%s: unknown flags %d", fn, flags);
+    RF_REQUIRE(d_actions || d_values || d_final_values || d_logits || d_state_out, "%s: no output is asked for", fn);
+    RF_REQUIRE(d_log_probs == nullptr || d_actions != nullptr, "%s: d_log_probs are those of d_actions, which is NULL", fn);
+    RF_REQUIRE(d_final_values == nullptr || d_final_obs != nullptr, "%s: d_final_values needs d_final_obs", fn);
+    const bool sampled = d_actions != nullptr && (flags & RF_POLICY_DETERMINISTIC) == 0;
+    RF_REQUIRE(!sampled || gen != nullptr, "%s: a sampled call needs gen", fn);
+    RF_HIP(hipSetDevice(ctx->device));
+    const size_t rows = (size_t)n;
+    const size_t state_bytes = rf::lstm_state_floats(n, layout.hidden) * 4;
+    struct Array {
+        const void *p;
+        size_t bytes, align;
+        const char *what;
+    };
+    const Array inputs[] = {{d_params, (size_t)layout.total * 4, 4, "d_params"},
+                            {d_obs, rows * (size_t)layout.obs_width * 4, 4, "d_obs"},
+                            {d_episode_starts, rows, 1, "d_episode_starts"},
+                            {d_final_obs, rows * (size_t)layout.obs_width * 4, 4, "d_final_obs"},
+                            {d_state_in, state_bytes, 4, "d_state_in"}};
+    const Array outputs[] = {{d_actions, rows * 8, 8, "d_actions"},
+                             {d_log_probs, rows * 4, 4, "d_log_probs"},
+                             {d_values, rows * 4, 4, "d_values"},
+                             {d_final_values, rows * 4, 4, "d_final_values"},
+                             {d_logits, rows * (size_t)layout.mlp.n_actions * 4, 4, "d_logits"},
+                             {d_state_out, state_bytes, 4, "d_state_out"}};
+    for (const Array &a : inputs) {
+        if (a.p == nullptr)
+            continue;
+        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
+            return rc;
+    }
+    for (const Array &a : outputs) {
+        if (a.p == nullptr)
+            continue;
+        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
+            return rc;
+        for (const Array &b : inputs) {
+            if (&a == &outputs[5] && &b == &inputs[4]) { // d_state_out against d_state_in
+                // in place (a block reads its own rows of the state before it writes them), or apart
+                RF_REQUIRE(a.p == b.p || !ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: d_state_out overlaps d_state_in "
+                           "without being it (the same pointer updates the state in place; any other overlap would have a "
+                           "block overwrite rows another still reads)", fn);
+                continue;
+            }
+            RF_REQUIRE(b.p == nullptr || !ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s (an output must "
+                       "not alias an input: other blocks still read it)", fn, a.what, b.what);
+        }
+        for (const Array &b : outputs)
+            RF_REQUIRE(&b >= &a || b.p == nullptr || !ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s", fn,
+                       a.what, b.what);
+    }
+    // As rf_policy_forward: every array is the caller's and gen is read here, by value: one launch on the caller's stream.
+    rf::PolicyGen words{};
+    if (sampled)
+        for (int i = 0; i < 4; ++i)
+            words.word[i] = gen[i];
+    // with d_state_out both cells run, whatever is asked of the heads: the state of both nets advances together
+    const bool pi = d_actions != nullptr || d_logits != nullptr || d_state_out != nullptr;
+    const bool vf = d_values != nullptr || d_final_values != nullptr || d_state_out != nullptr;
+    const unsigned tiles = (unsigned)((rows + rf::kPolicyTile - 1) / rf::kPolicyTile);
+    hipLaunchKernelGGL(rf::lstm_forward_kernel, dim3(tiles, pi && vf ? 2u : 1u), dim3(rf::kPolicyThreads), 0,
+                       (hipStream_t)caller_stream, layout, d_params, n, d_obs, d_episode_starts, d_final_obs, d_state_in,
+                       d_state_out, words, sampled ? 1 : 0, pi ? 0 : 1, (int64_t *)d_actions, d_log_probs, d_values,
+                       d_final_values, d_logits);
     RF_HIP(hipGetLastError());
     return RF_OK;
 }

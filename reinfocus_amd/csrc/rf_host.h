@@ -10,6 +10,7 @@
 //                       and rf_policy_forward (policy_forward_kernel, rf_policy.h), which shares them too
 //                       and rf_ppo_update (the three kernels of rf_ppo.h), which shares them as well
 //                       and rf_sde_noise_reset / rf_sde_forward (rf_sde.h) / rf_sde_update (rf_ppo.h's Gaussian head)
+//                       and rf_lstm_forward (lstm_forward_kernel, rf_lstm.h)
 //   rf_abi_snapshot.hip snapshots of a device-resident environment (rf_env_snapshot* / rf_env_restore*): copies only
 //
 // Every kernel is defined in exactly one unit (the one that launches it); the units share only host functions.

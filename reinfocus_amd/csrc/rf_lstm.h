@@ -1,0 +1,225 @@
+// rf_lstm.h -- the recurrent PPO actor-critic forward with its state and sampling in one launch
+// (include/reinfocus_hip.h, "lstm policy"): sb3-contrib's RecurrentActorCriticPolicy with one LSTM layer per net
+// (lstm_actor, lstm_critic), then the MLPs and heads of "policy", in the fixed float32 order of the definition
+// (rf_policy_math.h holds the scalar functions, shared with the host build of tests/lstmcheck), bit for bit equal to the
+// numpy twin (environments/lstm.py lstm_numpy).
+//
+// The organisation is rf_policy.h's.  A block of kPolicyThreads threads owns ONE net (blockIdx.y: pi or vf) and a tile of
+// kPolicyTile consecutive environments.  The cell: thread j owns unit j with its four gates, one accumulator per gate and
+// environment of the tile (32, indexed by the constants of unrolled loops: registers), so nothing is exchanged between
+// threads before c' and h'; W_ih and W_hh are stored transposed, [k][4H], so the four weight loads of a wave per k are
+// runs of 64 consecutive floats; x and h of the tile live in LDS as [k][tile] and are read as broadcasts; h' goes to LDS
+// as the MLP's input, and from there on the block runs policy_hidden_tile, policy_dot and policy_head unchanged.  The vf
+// block's pass over final_obs runs FIRST: it reads state_in, which the pass over obs may overwrite in place.  No atomics;
+// the ragged last tile computes on zeros and stores nothing.
+// LstmLayout and lstm_layout are plain C++: tests/lstmcheck packs its host loop by the same offsets.
+#pragma once
+
+#include "rf_policy.h"
+
+namespace rf {
+
+// A checked rf_lstm_policy_desc as the kernel reads it: offsets in floats into the parameters.  Per net (pi, then vf):
+// W_ih^T [D][4H], W_hh^T [H][4H], b_ih [4H], b_hh [4H], then what "policy" packs for that net with input width H
+struct LstmLayout {
+    PolicyLayout mlp; // the two MLPs and their heads (obs_width = lstm_hidden), offsets into the whole array
+    int obs_width, hidden;
+    unsigned w_ih[2], w_hh[2], b_ih[2], b_hh[2];
+    unsigned total;
+};
+
+// false: desc is outside the limits of the definition
+RF_HD bool lstm_layout(const rf_lstm_policy_desc &d, LstmLayout &p)
+{
+    p = LstmLayout{};
+    const int D = d.policy.obs_width, H = d.lstm_hidden;
+    if (D < 1 || D > kPolicyMaxWidth || H < 1 || H > kPolicyMaxWidth)
+        return false;
+    rf_policy_desc mlp = d.policy;
+    mlp.obs_width = H;
+    if (!policy_layout(mlp, p.mlp))
+        return false;
+    p.obs_width = D;
+    p.hidden = H;
+    const unsigned gates = 4u * (unsigned)H;
+    const unsigned cell = gates * (unsigned)(D + H) + 2u * gates;
+    const unsigned pi_mlp = p.mlp.weight[1][0]; // (policy_layout packs the pi MLP first, from 0)
+    for (int net = 0; net < 2; ++net) {
+        const unsigned base = net == 0 ? 0u : cell + pi_mlp;
+        p.w_ih[net] = base;
+        p.w_hh[net] = p.w_ih[net] + (unsigned)D * gates;
+        p.b_ih[net] = p.w_hh[net] + (unsigned)H * gates;
+        p.b_hh[net] = p.b_ih[net] + gates;
+        for (int l = 0; l <= p.mlp.layers[net]; ++l) {
+            p.mlp.weight[net][l] += (unsigned)(net + 1) * cell;
+            p.mlp.bias[net][l] += (unsigned)(net + 1) * cell;
+        }
+    }
+    p.total = p.mlp.total + 2u * cell;
+    p.mlp.total = p.total;
+    return true;
+}
+
+// floats of the state [2 nets][2: h, c][n][H]
+RF_HD size_t lstm_state_floats(int n, int H)
+{
+    return (size_t)4 * (size_t)n * (size_t)H;
+}
+
+// element (net, which: 0 h / 1 c, env, unit) of a state
+RF_HD size_t lstm_state_at(int net, int which, int n, int H, int env, int unit)
+{
+    return ((size_t)(net * 2 + which) * (size_t)n + (size_t)env) * (size_t)H + (size_t)unit;
+}
+
+// torch.nn.LSTM's cell from the four gate sums (torch's order i, f, g, o) and the cell state c:
+//   i = sigmoid32(a_i), f = sigmoid32(a_f), g = tanh32(a_g), o = sigmoid32(a_o)
+//   c' = f * c + i * g (two multiplies, then one add),  h' = o * tanh32(c')
+RF_HD void lstm_cell(float ai, float af, float ag, float ao, float c, float *h1, float *c1)
+{
+    const float i = sigmoid32(ai), f = sigmoid32(af), g = tanh32(ag), o = sigmoid32(ao);
+    const float fc = f * c;
+    const float ig = i * g;
+    const float cn = fc + ig;
+    *c1 = cn;
+    *h1 = o * tanh32(cn);
+}
+
+#if defined(__HIPCC__)
+// acc[q][e] = acc[q][e] + in[k][e] * W^T[k][q * H + j] for k = 0 .. K-1, j = tid: the four gates of unit j over the tile
+__device__ __forceinline__ void lstm_gates_tile(const float *__restrict__ params, unsigned weight, int K, int H,
+                                                const float (*in)[kPolicyTile], float (&acc)[4][kPolicyTile], int tid)
+{
+    const float *__restrict__ w = params + weight + tid;
+    const size_t row = (size_t)4 * (size_t)H;
+#pragma unroll 4
+    for (int k = 0; k < K; ++k) { // (unrolled: 16 independent weight loads in flight per round of latency)
+        float wk[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            wk[q] = w[(size_t)k * row + (size_t)q * (size_t)H];
+        const float4 *x = reinterpret_cast<const float4 *>(&in[k][0]);
+        float xs[kPolicyTile];
+#pragma unroll
+        for (int v = 0; v < kPolicyTile / 4; ++v) {
+            const float4 t = x[v];
+            xs[4 * v] = t.x, xs[4 * v + 1] = t.y, xs[4 * v + 2] = t.z, xs[4 * v + 3] = t.w;
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int e = 0; e < kPolicyTile; ++e)
+                acc[q][e] = acc[q][e] + xs[e] * wk[q];
+    }
+}
+
+__global__ __launch_bounds__(kPolicyThreads) void lstm_forward_kernel(
+    LstmLayout L, const float *__restrict__ params, int n, const float *__restrict__ obs,
+    const uint8_t *__restrict__ starts, const float *__restrict__ final_obs /* or null */, const float *state_in,
+    float *state_out /* null, state_in itself, or a range that does not overlap it */, PolicyGen gen, int sampled,
+    int first_net, int64_t *__restrict__ actions, float *__restrict__ log_probs, float *__restrict__ values,
+    float *__restrict__ final_values, float *__restrict__ logits)
+{
+    __shared__ __align__(16) float s_x[kPolicyMaxWidth][kPolicyTile];      // the tile's observations, [k][environment]
+    __shared__ __align__(16) float s_act[2][kPolicyMaxWidth][kPolicyTile]; // [1]: h; [0]: h', then the MLP's activations
+    __shared__ float s_logit[kPolicyTile][kPolicyMaxActions];
+    __shared__ float s_sum[kPolicyTile][kPolicyMaxActions];
+    const int tid = threadIdx.x;
+    const int net = (int)blockIdx.y + first_net;
+    const int e0 = (int)blockIdx.x * kPolicyTile;
+    const int D = L.obs_width, H = L.hidden;
+    for (int turn = 0; turn < 2; ++turn) { // (block-uniform: every thread reaches every barrier)
+        const int pass = 1 - turn;         // 1: final_obs from state_in as it is; 0: obs, masked by starts, stores the state
+        if (pass == 1 && (net == 0 || final_values == nullptr))
+            continue;
+        const bool heads = pass == 1 || (net == 0 ? actions != nullptr || logits != nullptr : values != nullptr);
+        if (!heads && state_out == nullptr)
+            continue;
+        const float *__restrict__ in = pass == 0 ? obs : final_obs;
+        // the tile's rows are consecutive in memory: element i of the tile is row i / D, column i % D
+        for (int i = tid; i < D * kPolicyTile; i += kPolicyThreads) {
+            const int e = i / D, k = i - e * D;
+            s_x[k][e] = e0 + e < n ? in[(size_t)e0 * (size_t)D + (size_t)i] : 0.0f;
+        }
+        for (int i = tid; i < H * kPolicyTile; i += kPolicyThreads) {
+            const int e = i / H, k = i - e * H, env = e0 + e;
+            // an episode start replaces the state by +0: a select, so no NaN or inf of a dead state survives it
+            const bool kept = env < n && (pass == 1 || starts[env] == 0);
+            s_act[1][k][e] = kept ? state_in[lstm_state_at(net, 0, n, H, env, k)] : 0.0f;
+        }
+        __syncthreads();
+        if (tid < H) {
+            float acc[4][kPolicyTile];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float bi = params[L.b_ih[net] + (unsigned)(q * H + tid)];
+                const float bh = params[L.b_hh[net] + (unsigned)(q * H + tid)];
+#pragma unroll
+                for (int e = 0; e < kPolicyTile; ++e)
+                    acc[q][e] = bi + bh;
+            }
+            lstm_gates_tile(params, L.w_ih[net], D, H, s_x, acc, tid);
+            lstm_gates_tile(params, L.w_hh[net], H, H, s_act[1], acc, tid);
+#pragma unroll
+            for (int e = 0; e < kPolicyTile; ++e) {
+                const int env = e0 + e;
+                const bool kept = env < n && (pass == 1 || starts[env] == 0);
+                const float c = kept ? state_in[lstm_state_at(net, 1, n, H, env, tid)] : 0.0f;
+                float h1, c1;
+                lstm_cell(acc[0][e], acc[1][e], acc[2][e], acc[3][e], c, &h1, &c1);
+                s_act[0][tid][e] = h1;
+                if (pass == 0 && state_out != nullptr && env < n) {
+                    state_out[lstm_state_at(net, 0, n, H, env, tid)] = policy_canonical(h1);
+                    state_out[lstm_state_at(net, 1, n, H, env, tid)] = policy_canonical(c1);
+                }
+            }
+        }
+        __syncthreads();
+        if (!heads)
+            continue;
+        int cur = 0, K = H;
+        for (int layer = 0; layer < L.mlp.layers[net]; ++layer) {
+            const int W = L.mlp.width[net][layer];
+            policy_hidden_tile(params, L.mlp.weight[net][layer], L.mlp.bias[net][layer], K, W, L.mlp.activation, s_act[cur],
+                               s_act[cur ^ 1], tid);
+            __syncthreads();
+            cur ^= 1;
+            K = W;
+        }
+        const int head = L.mlp.layers[net];
+        const int O = net == 0 ? L.mlp.n_actions : 1;
+        for (int i = tid; i < O * kPolicyTile; i += kPolicyThreads) {
+            const int e = i / O, o = i - e * O;
+            const float y = policy_dot(&s_act[cur][0][e], kPolicyTile, params + L.mlp.weight[net][head] + o, O,
+                                       params[L.mlp.bias[net][head] + o], K);
+            const int env = e0 + e;
+            if (net == 0) {
+                s_logit[e][o] = y;
+                if (logits != nullptr && env < n)
+                    logits[(size_t)env * (size_t)O + (size_t)o] = policy_canonical(y);
+            } else if (env < n) {
+                if (pass == 0)
+                    values[env] = policy_canonical(y);
+                else {
+                    const float lead = in[(size_t)env * (size_t)D];
+                    final_values[env] = lead != lead ? bits_f32(kPolicyNaN) : policy_canonical(y);
+                }
+            }
+        }
+        __syncthreads();
+        if (net == 0 && actions != nullptr && tid < kPolicyTile && e0 + tid < n) {
+            const int env = e0 + tid;
+            const double u = sampled ? policy_draw(gen.word, (uint64_t)env) : 0.0;
+            int64_t action;
+            float log_prob;
+            policy_head(&s_logit[tid][0], L.mlp.n_actions, !sampled, u, &s_sum[tid][0], &action, &log_prob);
+            actions[env] = action;
+            if (log_probs != nullptr)
+                log_probs[env] = log_prob;
+        }
+        __syncthreads(); // (the next pass overwrites what the heads have read)
+    }
+}
+#endif
+
+} // namespace rf

@@ -1,6 +1,7 @@
 // rf_policy_math.h -- the scalar arithmetic of the actor-critic forward (include/reinfocus_hip.h, "policy"): the
 // project's own exp32 / log32 / tanh32, the activation, the Categorical head and the draw of a lane; and of the Gaussian
-// head of "sde policy": expw32, log64, normal32 (the one function that is float64 inside) and the sde_* functions.
+// head of "sde policy": expw32, log64, normal32 (the one function that is float64 inside) and the sde_* functions; and
+// sigmoid32, the gates of "lstm policy" (rf_lstm.h has the cell).
 //
 // Plain C++ like rf_init.h, so that tests/policycheck compiles the very same text for the host and compares it with the
 // numpy twin (environments/policy.py policy_numpy) on the CPU.  exp32 and log32 are built only from float32 + - * /
@@ -234,6 +235,17 @@ RF_HD float tanh32(float x)
     const float t = exp32(-2.0f * a);
     const float q = (1.0f - t) / (1.0f + t);
     return bits_f32(f32_bits(q) | (u & 0x80000000u));
+}
+
+// sigmoid(x) = 1 / (1 + t) for x >= 0 and t / (1 + t) below, t = exp32(-|x|) (exp32 is defined for arguments <= 0 only):
+// +-0 gives 1/2, +inf 1, -inf +0 (t = 0), and so does every x < -87; NaN is NaN.  The LSTM cell's gates ("lstm policy").
+RF_HD float sigmoid32(float x)
+{
+    if (x != x)
+        return bits_f32(kPolicyNaN);
+    const float a = bits_f32(f32_bits(x) & 0x7fffffffu);
+    const float t = exp32(-a);
+    return x >= 0.0f ? 1.0f / (1.0f + t) : t / (1.0f + t);
 }
 
 constexpr int kPolicyRelu = 0, kPolicyTanh = 1;

@@ -1842,3 +1842,4 @@ from reinfocus_amd.environments.rollout import DeviceRollout, Rollout  # noqa: E
 from reinfocus_amd.environments.policy import DevicePolicy, MlpPolicySpec, Policy, policy_numpy  # noqa: E402,F401 -- the PPO actor-critic
 from reinfocus_amd.environments.learner import DeviceLearner, Learner, ppo_update_numpy  # noqa: E402,F401 -- the PPO minibatch update
 from reinfocus_amd.environments.sde import DeviceSdePolicy, SdePolicy, SdePolicySpec, sde_numpy  # noqa: E402,F401 -- the gSDE actor-critic
+from reinfocus_amd.environments.lstm import DeviceLstmPolicy, LstmPolicy, LstmPolicySpec, lstm_numpy  # noqa: E402,F401 -- the recurrent actor-critic

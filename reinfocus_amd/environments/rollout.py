@@ -19,6 +19,9 @@ collect(policy) runs a whole rollout with a policy of environments/policy.py (Po
 DeviceRollout) or, over a Box(-1, 1, (1,)) action space, of environments/sde.py (SdePolicy, DeviceSdePolicy: the raw
 action goes into the slab, the clamped one to the step, and sde_sample_freq says when the noise is resampled): on the
 device a step is then one policy launch, which writes rows of the slabs, and the environment's step from those rows.
+With a recurrent policy of environments/lstm.py (LstmPolicy, DeviceLstmPolicy) collect() also keeps what sb3-contrib's
+RecurrentRolloutBuffer hands to the update -- episode_starts uint8 [T + 1, n] and lstm_states float32
+[T + 1, 2, 2, n, H], made on first use with such a policy --; flat() and minibatches() are unchanged.
 
 torch is imported lazily, by DeviceRollout only (reinfocus_amd/torch_interop.py says why import order matters).
 """
@@ -81,12 +84,18 @@ class _Bookkeeping:
         self._bootstrapped = 0
         self._last_bootstrap = -1
         self._complete = False  # (row T holds the observation the next rollout begins with)
+        self._fresh = self._lstm = False
+        # what collect() keeps of a recurrent policy (environments/lstm.py), made on first use with one: episode_starts
+        # uint8 [T + 1, n] and lstm_states float32 [T + 1, 2, 2, n, H] -- what sb3-contrib's RecurrentRolloutBuffer hands
+        # to the update.  A rollout that never sees such a policy allocates neither.
+        self.episode_starts = self.lstm_states = None
 
     def _begin(self, obs):
         if obs is None and not self._complete:
             raise ValueError("start() without obs continues the rollout before it, and none has been finished: pass the "
                              "observation the environment's reset returned")
         self._t, self._bootstrapped, self._last_bootstrap = 0, 0, -1
+        self._fresh = obs is not None  # (every environment starts an episode: row 0 of an lstm policy's episode_starts)
 
     def _next_step(self):
         if self._t is None:
@@ -123,7 +132,9 @@ class _Bookkeeping:
         """True: `policy` has the Gaussian head of environments/sde.py."""
         if self._t != 0:
             raise ValueError("collect() runs a whole rollout: start() first, and take no step() before it")
-        sde = getattr(getattr(policy, "spec", None), "kind", None) == "sde"
+        kind = getattr(getattr(policy, "spec", None), "kind", None)
+        sde = kind == "sde"
+        self._lstm = kind == "lstm"  # (a recurrent policy of environments/lstm.py: collect() keeps its states)
         if sde and _index_task(self.env):
             raise ValueError("collect() was given a policy with a Gaussian head, and the environment's action space is "
                              f"{self.env.single_action_space!r}: Discrete action spaces have Policy / DevicePolicy")
@@ -202,24 +213,54 @@ class Rollout(_Bookkeeping):
         records -- the bootstrap of every step, then finish(V(observations[T])).  V(final_observation) of step t - 1
         comes from the act of step t (the last one from the values-only call that gives last_values).  Equal to the
         explicit loop.  With an SdePolicy the noise is reset first and then whenever t % sde_sample_freq == 0 (never
-        again with -1), the slab keeps the raw action and the environment gets the clamped one."""
+        again with -1), the slab keeps the raw action and the environment gets the clamped one.  With an LstmPolicy row 0
+        of episode_starts is all ones after start(obs) and the row T of the rollout before after start(), row 0 of
+        lstm_states is the policy's state, step t goes from lstm_states[t] to lstm_states[t + 1] with episode_starts[t],
+        episode_starts[t + 1] = truncated[t], and afterwards the policy's state is row T."""
         sde = self._collecting(policy, sde_sample_freq)
         if sde:
             policy.reset_noise(self.num_envs)
+        if self._lstm:
+            self._recurrent_rows(policy)
         final_obs = None
         for t in range(self.n_steps):
             if sde and self._resample(t, sde_sample_freq):
                 policy.reset_noise(self.num_envs)
-            actions, values, log_probs, final_values, *clamped = policy.act(self.observations[t], final_obs, deterministic)
+            if self._lstm:
+                actions, values, log_probs, final_values = policy.act(
+                    self.observations[t], self.episode_starts[t], final_obs, deterministic,
+                    states=(self.lstm_states[t], self.lstm_states[t + 1]))
+                clamped = ()
+            else:
+                actions, values, log_probs, final_values, *clamped = policy.act(self.observations[t], final_obs,
+                                                                                deterministic)
             if final_obs is not None:
                 self.bootstrap(final_values)
             info = self.step(actions, values, log_probs, *clamped)[4]
+            if self._lstm:
+                self.episode_starts[t + 1] = self.truncated[t]
             final_obs = info["final_observation"] if self._records else None
+        last = (self.observations[self.n_steps],)
+        if self._lstm:
+            policy.set_lstm_state(self.lstm_states[self.n_steps])
+            last += (self.episode_starts[self.n_steps],)
         if final_obs is None:
-            return self.finish(policy.values(self.observations[self.n_steps]))
-        last_values, final_values = policy.values(self.observations[self.n_steps], final_obs)
+            return self.finish(policy.values(*last))
+        last_values, final_values = policy.values(*last, final_obs)
         self.bootstrap(final_values)
         return self.finish(last_values)
+
+    def _recurrent_rows(self, policy):
+        """Row 0 of the two slabs a recurrent policy's collect() keeps (made on first use): every environment starts an
+        episode after start(obs), after start() those do that the last step of the rollout before ended; the states
+        are the policy's."""
+        hidden = policy.spec.lstm_hidden
+        if self.lstm_states is None or self.lstm_states.shape[-1] != hidden:
+            self.episode_starts = np.zeros((self.n_steps + 1, self.num_envs), dtype=np.uint8)
+            self.lstm_states = np.zeros((self.n_steps + 1, 2, 2, self.num_envs, hidden), dtype=np.float32)
+        self.episode_starts[0] = 1 if self._fresh else self.truncated[self.n_steps - 1]
+        state = policy.lstm_state()
+        self.lstm_states[0] = 0.0 if state is None else state
 
     def flat(self):
         """The rollout as stable-baselines3's swap_and_flatten orders it: index e * T + t."""
@@ -342,13 +383,17 @@ class DeviceRollout(_Bookkeeping):
         actions[t], values[t], log_probs[t] and -- with episode records, from the final_observation of the step before
         -- final_values[t - 1] straight into the slabs (no row copies), and the environment's step from actions[t];
         after step T a values-only launch gives last_values and final_values[T - 1]; then finish().  As bytes what the
-        explicit loop of act / step / bootstrap / finish gives, and Rollout.collect with the twin policy.  Nothing
-        waits for the host."""
+        explicit loop of act / step / bootstrap / finish gives, and Rollout.collect with the twin policy.  With a
+        DeviceLstmPolicy the launch of step t also goes from lstm_states[t] to lstm_states[t + 1]; it reads truncated[t - 1]
+        as its episode starts, and episode_starts[1:] is one copy of the truncated slab after the loop.  Nothing waits for
+        the host."""
         sde = self._collecting(policy, sde_sample_freq)
         if sde:
             policy.reset_noise(self.num_envs)
             if self._env_actions is None:
                 self._env_actions = self._torch.zeros(self.num_envs, dtype=self._torch.float32, device=self.device)
+        if self._lstm:
+            self._recurrent_rows(policy)
         final_obs = None
         for _ in range(self.n_steps):
             t = self._next_step()
@@ -356,7 +401,13 @@ class DeviceRollout(_Bookkeeping):
             if sde and self._resample(t, sde_sample_freq):
                 policy.reset_noise(self.num_envs)
             out = (self.actions[t], self.values[t], self.log_probs[t], final_out)
-            policy.act(self.observations[t], final_obs, deterministic, out=out + (self._env_actions,) if sde else out)
+            if self._lstm:
+                # episode_starts[t + 1] IS truncated[t]: the call reads the step's own row, and the slab is filled by one
+                # copy after the loop -- no launch per step, nothing waited for
+                policy.act(self.observations[t], self.episode_starts[0] if t == 0 else self.truncated[t - 1], final_obs,
+                           deterministic, out=out, states=(self.lstm_states[t], self.lstm_states[t + 1]))
+            else:
+                policy.act(self.observations[t], final_obs, deterministic, out=out + (self._env_actions,) if sde else out)
             info = self.env.step_tensors(self._env_actions if sde else self.actions[t],
                                          out=(self.observations[t + 1], self.rewards[t], self.truncated[t]))[4]
             self._t = t + 1
@@ -364,8 +415,28 @@ class DeviceRollout(_Bookkeeping):
         if self._last_values is None:
             self._last_values = self._torch.zeros(self.num_envs, dtype=self._torch.float32, device=self.device)
         final_out = None if final_obs is None else self.final_values[self._bootstrap_step()]
-        policy.values(self.observations[self.n_steps], final_obs, out=(self._last_values, final_out))
+        if self._lstm:
+            self.episode_starts[1:].copy_(self.truncated)
+            policy.set_lstm_state(self.lstm_states[self.n_steps])
+            policy.values(self.observations[self.n_steps], self.truncated[self.n_steps - 1], final_obs,
+                          out=(self._last_values, final_out))
+        else:
+            policy.values(self.observations[self.n_steps], final_obs, out=(self._last_values, final_out))
         return self.finish(self._last_values)
+
+    def _recurrent_rows(self, policy):
+        """As Rollout._recurrent_rows, in device copies on the current stream."""
+        torch = self._torch
+        hidden = policy.spec.lstm_hidden
+        if self.lstm_states is None or self.lstm_states.shape[-1] != hidden:
+            self.episode_starts = torch.zeros((self.n_steps + 1, self.num_envs), dtype=torch.uint8, device=self.device)
+            self.lstm_states = torch.zeros((self.n_steps + 1, 2, 2, self.num_envs, hidden), dtype=torch.float32,
+                                           device=self.device)
+        if self._fresh:
+            self.episode_starts[0].fill_(1)
+        else:
+            self.episode_starts[0].copy_(self.truncated[self.n_steps - 1])
+        self.lstm_states[0].copy_(policy.lstm_state())
 
     def flat(self):
         """The rollout as stable-baselines3's swap_and_flatten orders it: index e * T + t.  The slabs are [T][n] (lanes
