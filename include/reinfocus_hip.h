@@ -1008,8 +1008,8 @@ int rf_sde_update(rf_ctx *ctx, const rf_policy_desc *policy, const rf_ppo_desc *
  * The reference's other two training configurations (examples/ppo_lstm_*.yml) run policy: 'MlpLstmPolicy', sb3-contrib's
  * RecurrentPPO with RecurrentActorCriticPolicy at its defaults: lstm_hidden_size=256, n_lstm_layers=1, shared_lstm=False,
  * enable_critic_lstm=True.  No reference counterpart.  Needs no environment: the context only says which GPU.
- * Out of scope: back-propagation through time (the update), the Gaussian (sde) head on top of the LSTM, n_lstm_layers > 1,
- * shared_lstm=True, enable_critic_lstm=False.
+ * The update (back-propagation through time) is "lstm update" below.  Out of scope: the Gaussian (sde) head on top of the
+ * LSTM, n_lstm_layers > 1, shared_lstm=True, enable_critic_lstm=False.
  *
  * One definition, numpy twin (environments/lstm.py lstm_numpy), host build (tests/lstmcheck) and kernel (csrc/rf_lstm.h)
  * alike; the scalar functions are csrc/rf_policy_math.h.  Everything is float32, one rounding per operation, nothing
@@ -1063,6 +1063,66 @@ int rf_lstm_forward(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const float *d
                     const uint8_t *d_episode_starts, const float *d_final_obs, const float *d_state_in, float *d_state_out,
                     const unsigned long long gen[4], int flags, long long *d_actions, float *d_log_probs, float *d_values,
                     float *d_final_values, float *d_logits, void *caller_stream);
+
+/* ---- lstm update: one recurrent PPO minibatch update on the device: sequences, BPTT, clip, Adam ------------------------
+ * The other half of training in the reference's recurrent configurations (examples/ppo_lstm_*.yml) is sb3-contrib's
+ * RecurrentPPO.train(): per minibatch the loss of "ppo update" on the actor-critic of "lstm policy", its gradient by
+ * back-propagation through the MLPs and through time, clip_grad_norm_ and one Adam step.  No reference counterpart.  Needs
+ * no environment: the context only says which GPU.  Categorical head only; one LSTM layer per net.
+ *
+ * One definition, numpy twin (environments/lstm_learner.py lstm_update_numpy), host build (tests/lstmppocheck) and kernels
+ * (csrc/rf_lstm_ppo.h) alike.  Everything is float32, left to right, one rounding per operation, nothing contracted,
+ * unless a step says float64; no MFMA; every reduction has a fixed order.
+ *
+ * Inputs.  A rollout of T = n_steps steps of n = num_envs environments, N = n * T: the five arrays of flat() (observations
+ * float32[N][D], actions int64[N], log_probs, advantages, returns float32[N]; row r = e * T + t) and the rollout's two
+ * recurrent slabs in their own layout, episode_starts uint8[T + 1][n] and lstm_states float32[T + 1][2 nets][2: h, c][n][H].
+ *  U1 Minibatch.  sb3-contrib never permutes rows, it rotates them: the minibatch is B consecutive rows of flat()'s order
+ *     starting at `first` and wrapping, r_b = (first + b) mod N, 1 <= B <= min(N, RF_PPO_MAX_BATCH), 0 <= first < N (host
+ *     integers: what is outside is refused on the host).  e = r_b / T, t = r_b mod T.
+ *  U2 Sequences.  Row b starts a sequence iff b == 0, or t == 0 (the environment changes), or episode_starts[t][e] != 0.
+ *     The state that enters a sequence starting at (t, e) is lstm_states[t][net][h | c][e][:], or +0 where
+ *     episode_starts[t][e] != 0 -- a select, as L4: a NaN of a dead state never enters.  It is a constant: no gradient
+ *     flows into it.  Every other row takes h' and c' of row b - 1.
+ *  U3 Validity.  invalid = some actions[r_b] outside [0, A); a = clamp(actions[r_b], 0, A - 1).
+ *  U4 Forward.  Per row and net the cell of L2 on observations[r_b] from (h, c) of U2, which gives the gate values i, f, g,
+ *     o, c' and h'; then the net's MLP and head on h' as "ppo update" step 3.
+ *  U5 Advantages, loss terms and head deltas: "ppo update" steps 2, 4 and 5, over the B rows in minibatch order.
+ *  U6 Backward through the MLPs: "ppo update" step 6, and one more product through the first MLP matrix W0^T [H][out]:
+ *     dh_mlp[b][k] = sum over o in index order, from +0, of W0^T[k][o] * delta0[b][o] (the LSTM's output has no activation
+ *     derivative: no further multiply).
+ *  U7 BPTT.  Within each sequence, from its last row to its first, per net and unit j, with dh_rec = dc_next = +0 at the
+ *     sequence's last row (both additions are still performed):
+ *       dh = dh_mlp[b][j] + dh_rec[j];  tc = tanh32(c');  do = dh * tc;  dc = (dh * o) * (1 - tc * tc) + dc_next;
+ *       da_i = (dc * g) * (i * (1 - i));  da_f = (dc * c_prev) * (f * (1 - f));  da_g = (dc * i) * (1 - g * g);
+ *       da_o = do * (o * (1 - o));  dc_next of the row before = dc * f;
+ *       dh_rec[k] of the row before: four chains, one per gate q, over j = 0 .. H-1 ascending from +0,
+ *       acc_q = acc_q + W_hh^T[k][q * H + j] * da_q[j], joined as (acc_i + acc_f) + (acc_g + acc_o).
+ *     c_prev of a sequence's first row is its entering c.
+ *  U8 Parameter gradients, each one chain over b = 0 .. B-1 ascending from +0 (a multiply, then an add):
+ *     dW_ih^T[k][col] of x[b][k] * da[b][col]; dW_hh^T[k][col] of h_prev[b][k] * da[b][col] (h_prev of a sequence's first row
+ *     is its entering h); db_ih[col] = db_hh[col] of da[b][col]; the MLPs' as "ppo update" step 7 with h' as the first
+ *     layer's input.  Packing: L8.  A NaN gradient is stored as 0x7fc00000.
+ *  U9 "ppo update" steps 8 to 10 over the P packed parameters of L8: the float64 tree-summed norm, the skip rule
+ *     (RF_PPO_INVALID for U3, RF_PPO_NONFINITE for a norm that is not finite: parameters and optimizer state keep their
+ *     bytes), clip, Adam, stats and flags.  The optimizer state is "ppo update"'s: 32 bytes of header, m[P], v[P].
+ *
+ *   rf_lstm_ppo_state_size      bytes of the optimizer state (32 + 8 P); 0 for a desc outside the limits or a NULL ctx
+ *   rf_lstm_ppo_workspace_size  bytes of the workspace for minibatches up to max_batch (1 .. RF_PPO_MAX_BATCH); 0 if refused
+ *   rf_lstm_ppo_update          six launches on caller_stream, nothing allocated, nothing waited for; d_params, d_state and
+ *                               d_stats (float32[8]) are updated in place, d_workspace is scratch.  Refused (RF_ERR_INVALID,
+ *                               nothing enqueued, no device pointer dereferenced): what rf_ppo_update and rf_lstm_forward
+ *                               refuse (a desc or lstm_hidden outside the limits, n_steps or num_envs < 1, a hyper-parameter,
+ *                               a NULL array, one the runtime does not vouch for on the ctx's GPU -- the two slabs in their
+ *                               [T + 1] lengths --, an output that overlaps an input or another output, a capturing caller
+ *                               stream), and B or first outside the limits of U1. */
+unsigned long long rf_lstm_ppo_state_size(rf_ctx *ctx, const rf_lstm_policy_desc *desc);
+unsigned long long rf_lstm_ppo_workspace_size(rf_ctx *ctx, const rf_lstm_policy_desc *desc, int max_batch);
+int rf_lstm_ppo_update(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const rf_ppo_desc *ppo, float *d_params, void *d_state,
+                       void *d_workspace, int n_steps, int num_envs, const float *d_observations, const long long *d_actions,
+                       const float *d_log_probs, const float *d_advantages, const float *d_returns,
+                       const uint8_t *d_episode_starts, const float *d_lstm_states, int first, int B, float *d_stats,
+                       void *caller_stream);
 
 #ifdef __cplusplus
 }

@@ -110,6 +110,9 @@ SYMBOLS = (
     "rf_lstm_params_size",
     "rf_lstm_state_size",
     "rf_lstm_forward",
+    "rf_lstm_ppo_state_size",
+    "rf_lstm_ppo_workspace_size",
+    "rf_lstm_ppo_update",
     "rf_render_kernel_name",
     "rf_pixels_rendered",
     "rf_allocations_poisoned",
@@ -377,6 +380,11 @@ def load():
     lib.rf_lstm_state_size.restype = ctypes.c_ulonglong
     lib.rf_lstm_state_size.argtypes = [vp, vp, i32]
     lib.rf_lstm_forward.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
+    lib.rf_lstm_ppo_state_size.restype = ctypes.c_ulonglong
+    lib.rf_lstm_ppo_state_size.argtypes = [vp, vp]
+    lib.rf_lstm_ppo_workspace_size.restype = ctypes.c_ulonglong
+    lib.rf_lstm_ppo_workspace_size.argtypes = [vp, vp, i32]
+    lib.rf_lstm_ppo_update.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp]
     lib.rf_render_kernel_name.restype = ctypes.c_char_p
     lib.rf_render_kernel_name.argtypes = [vp]
     lib.rf_pixels_rendered.restype = ctypes.c_ulonglong
@@ -814,6 +822,30 @@ class Context:
         rc = self._lib.rf_lstm_forward(self._h, ctypes.byref(LstmPolicyDesc(*desc)), params_ptr, num_envs, obs_ptr,
                                        episode_starts_ptr, final_obs_ptr, state_in_ptr, state_out_ptr, words, flags,
                                        actions_ptr, log_probs_ptr, values_ptr, final_values_ptr, logits_ptr, stream)
+        if rc != 0:
+            _check(rc)
+
+    # --- lstm update (rf_lstm_ppo_*): the recurrent PPO minibatch update ------------------------------------------------
+    def lstm_ppo_state_size(self, desc):
+        """rf_lstm_ppo_state_size: bytes of the optimizer state (header, m, v) of the recurrent network `desc`; 0 if
+        refused."""
+        return int(self._lib.rf_lstm_ppo_state_size(self._h, ctypes.byref(LstmPolicyDesc(*desc))))
+
+    def lstm_ppo_workspace_size(self, desc, max_batch):
+        """rf_lstm_ppo_workspace_size: bytes of the workspace for minibatches of up to max_batch rows; 0 if refused."""
+        return int(self._lib.rf_lstm_ppo_workspace_size(self._h, ctypes.byref(LstmPolicyDesc(*desc)), max_batch))
+
+    def lstm_ppo_update(self, desc, hyper, params_ptr, state_ptr, workspace_ptr, n_steps, num_envs, obs_ptr, actions_ptr,
+                        log_probs_ptr, advantages_ptr, returns_ptr, episode_starts_ptr, lstm_states_ptr, first, batch,
+                        stats_ptr, stream):
+        """rf_lstm_ppo_update: one recurrent PPO minibatch update (sequences, forward, loss, BPTT, clip, Adam) over rows
+        (first + b) mod (n_steps * num_envs), b < batch, of flat()'s arrays and the rollout's episode_starts and
+        lstm_states slabs, all device arrays given by address; six launches on `stream`.  desc and hyper as lstm_forward's
+        and ppo_update's.  Only enqueues."""
+        rc = self._lib.rf_lstm_ppo_update(self._h, ctypes.byref(LstmPolicyDesc(*desc)), ctypes.byref(PpoDesc(*hyper)),
+                                          params_ptr, state_ptr, workspace_ptr, n_steps, num_envs, obs_ptr, actions_ptr,
+                                          log_probs_ptr, advantages_ptr, returns_ptr, episode_starts_ptr, lstm_states_ptr,
+                                          first, batch, stats_ptr, stream)
         if rc != 0:
             _check(rc)
 

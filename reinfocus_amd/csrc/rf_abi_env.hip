@@ -14,6 +14,7 @@
 #include "rf_ppo.h"
 #include "rf_sde.h"
 #include "rf_lstm.h"
+#include "rf_lstm_ppo.h"
 #include "rf_rollout.h"
 
 using namespace rfh;
@@ -2352,6 +2353,115 @@ int rf_lstm_forward(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const float *d
                        (hipStream_t)caller_stream, layout, d_params, n, d_obs, d_episode_starts, d_final_obs, d_state_in,
                        d_state_out, words, sampled ? 1 : 0, pi ? 0 : 1, (int64_t *)d_actions, d_log_probs, d_values,
                        d_final_values, d_logits);
+    RF_HIP(hipGetLastError());
+    return RF_OK;
+}
+
+#define RF_LSTM_LIMITS "%s: the desc is outside the limits (obs_width and lstm_hidden 1 .. %d, 1 or 2 hidden layers of width " \
+                       "1 .. %d per net, n_actions 2 .. %d, activation RF_POLICY_RELU or RF_POLICY_TANH)"
+
+unsigned long long rf_lstm_ppo_state_size(rf_ctx *ctx, const rf_lstm_policy_desc *desc)
+{
+    rf::LstmLayout layout;
+    if (ctx == nullptr || desc == nullptr || !rf::lstm_layout(*desc, layout))
+        return 0;
+    if (hipSetDevice(ctx->device) != hipSuccess) // (as every entry point; nothing of the device is needed)
+        (void)hipGetLastError();
+    return 4ull * rf::kPpoStateHeader + 8ull * layout.total;
+}
+
+unsigned long long rf_lstm_ppo_workspace_size(rf_ctx *ctx, const rf_lstm_policy_desc *desc, int max_batch)
+{
+    rf::LstmLayout layout;
+    rf::LstmPpoWork work;
+    if (ctx == nullptr || desc == nullptr || !rf::lstm_layout(*desc, layout) || !rf::lstm_ppo_work(layout, max_batch, work))
+        return 0;
+    if (hipSetDevice(ctx->device) != hipSuccess)
+        (void)hipGetLastError();
+    return 4ull * work.total;
+}
+
+int rf_lstm_ppo_update(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const rf_ppo_desc *ppo, float *d_params, void *d_state,
+                       void *d_workspace, int n_steps, int num_envs, const float *d_observations, const long long *d_actions,
+                       const float *d_log_probs, const float *d_advantages, const float *d_returns,
+                       const uint8_t *d_episode_starts, const float *d_lstm_states, int first, int B, float *d_stats,
+                       void *caller_stream)
+{
+    const char *fn = "rf_lstm_ppo_update";
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", fn);
+    RF_HIP(hipSetDevice(ctx->device));
+    RF_REQUIRE(desc && ppo && d_params && d_state && d_workspace && d_observations && d_actions && d_log_probs &&
+               d_advantages && d_returns && d_episode_starts && d_lstm_states && d_stats, "%s: NULL argument", fn);
+    rf::LstmLayout layout;
+    RF_REQUIRE(rf::lstm_layout(*desc, layout), RF_LSTM_LIMITS, fn, RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_WIDTH,
+               RF_POLICY_MAX_ACTIONS);
+    RF_REQUIRE(n_steps >= 1 && num_envs >= 1 && (long long)n_steps * (long long)num_envs <= (1ll << 30),
+               "%s: n_steps = %d and num_envs = %d must be at least 1 (and their product at most 2^30)", fn, n_steps, num_envs);
+    const int N = n_steps * num_envs;
+    const int most = N < RF_PPO_MAX_BATCH ? N : RF_PPO_MAX_BATCH;
+    RF_REQUIRE(B >= 1 && B <= most, "%s: B = %d is not in 1 .. %d (min(n_steps * num_envs, %d))", fn, B, most,
+               RF_PPO_MAX_BATCH);
+    RF_REQUIRE(first >= 0 && first < N, "%s: first = %d is not in 0 .. %d", fn, first, N - 1);
+    rf::PpoHyper hyper;
+    RF_REQUIRE(rf::ppo_hyper(*ppo, hyper), "%s: a hyper-parameter is negative or not finite, a beta is outside [0, 1) or "
+               "normalize_advantage is not 0 / 1", fn);
+    rf::LstmPpoWork work;
+    RF_REQUIRE(rf::lstm_ppo_work(layout, B, work), "%s: no workspace layout for B = %d", fn, B);
+    const size_t rows = (size_t)N, slab = (size_t)(n_steps + 1) * (size_t)num_envs;
+    struct Array {
+        const void *p;
+        size_t bytes, align;
+        const char *what;
+    };
+    const Array inputs[] = {{d_observations, rows * (size_t)layout.obs_width * 4, 4, "d_observations"},
+                            {d_actions, rows * 8, 8, "d_actions"},
+                            {d_log_probs, rows * 4, 4, "d_log_probs"},
+                            {d_advantages, rows * 4, 4, "d_advantages"},
+                            {d_returns, rows * 4, 4, "d_returns"},
+                            {d_episode_starts, slab, 1, "d_episode_starts"},
+                            {d_lstm_states, slab * 4 * (size_t)layout.hidden * 4, 4, "d_lstm_states"}};
+    const Array outputs[] = {{d_params, (size_t)layout.total * 4, 4, "d_params"},
+                             {d_state, 4 * (size_t)rf::kPpoStateHeader + 8 * (size_t)layout.total, 8, "d_state"},
+                             {d_workspace, (size_t)work.total * 4, 8, "d_workspace"},
+                             {d_stats, 32, 4, "d_stats"}};
+    for (const Array &a : inputs)
+        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
+            return rc;
+    for (const Array &a : outputs) {
+        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
+            return rc;
+        for (const Array &b : inputs)
+            RF_REQUIRE(!ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s (an output must not alias an "
+                       "input: other blocks still read it)", fn, a.what, b.what);
+        for (const Array &b : outputs)
+            RF_REQUIRE(&b >= &a || !ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s", fn, a.what, b.what);
+    }
+    const hipStream_t caller = (hipStream_t)caller_stream;
+    if (int rc = refuse_capturing(caller, fn))
+        return rc;
+    // As rf_ppo_update: every array is the caller's and the hyper-parameters travel by value: six launches on the
+    // caller's stream, nothing allocated, nothing waited for.  The workspace layout is that of B itself.
+    float *ws = (float *)d_workspace;
+    const dim3 threads(rf::kPpoThreads);
+    hipLaunchKernelGGL(rf::lstm_ppo_forward_kernel, dim3((unsigned)B, 2u), threads, 0, caller, layout, work,
+                       (const float *)d_params, ws, n_steps, num_envs, d_observations, d_episode_starts, d_lstm_states, first,
+                       B);
+    RF_HIP(hipGetLastError());
+    const unsigned tiles = (unsigned)((B + rf::kPolicyTile - 1) / rf::kPolicyTile);
+    hipLaunchKernelGGL(rf::lstm_ppo_mlp_kernel, dim3(tiles, 2u), threads, 0, caller, layout, work, hyper,
+                       (const float *)d_params, (const rf::PpoHeader *)d_state, ws, N, (const int64_t *)d_actions,
+                       d_log_probs, d_advantages, d_returns, first, B);
+    RF_HIP(hipGetLastError());
+    hipLaunchKernelGGL(rf::lstm_ppo_bptt_kernel, dim3((unsigned)B, 2u), threads, 0, caller, layout, work,
+                       (const float *)d_params, ws, n_steps, num_envs, d_episode_starts, first, B);
+    RF_HIP(hipGetLastError());
+    hipLaunchKernelGGL(rf::lstm_ppo_gradient_kernel, dim3(work.mlp.partials), threads, 0, caller, layout, work, ws, B);
+    RF_HIP(hipGetLastError());
+    hipLaunchKernelGGL(rf::lstm_ppo_norm_kernel, dim3(work.supers), dim3(rf::kLstmPpoGroup), 0, caller, work, ws);
+    RF_HIP(hipGetLastError());
+    const unsigned slices = (layout.total + rf::kPpoAdamSlice - 1) / rf::kPpoAdamSlice;
+    hipLaunchKernelGGL(rf::ppo_adam_kernel, dim3(slices + 1u), threads, 0, caller, layout.total,
+                       rf::lstm_ppo_adam_work(work), hyper, d_params, (float *)d_state, (const float *)ws, B, d_stats);
     RF_HIP(hipGetLastError());
     return RF_OK;
 }

@@ -11,6 +11,7 @@
 //                       and rf_ppo_update (the three kernels of rf_ppo.h), which shares them as well
 //                       and rf_sde_noise_reset / rf_sde_forward (rf_sde.h) / rf_sde_update (rf_ppo.h's Gaussian head)
 //                       and rf_lstm_forward (lstm_forward_kernel, rf_lstm.h)
+//                       and rf_lstm_ppo_update (the five kernels of rf_lstm_ppo.h, then rf_ppo.h's ppo_adam_kernel)
 //   rf_abi_snapshot.hip snapshots of a device-resident environment (rf_env_snapshot* / rf_env_restore*): copies only
 //
 // Every kernel is defined in exactly one unit (the one that launches it); the units share only host functions.

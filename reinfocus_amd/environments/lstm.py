@@ -14,8 +14,8 @@ multiplies the state by (1 - start).
     LstmPolicy       the numpy twin: act / values over numpy arrays, the state float32 [2 nets][2: h, c][n][H]
     DeviceLstmPolicy the same over torch tensors on a device-resident environment's GPU: one launch per call
 
-Out of scope, and refused or absent: back-propagation through time (the update), the Gaussian (sde) head on top of the
-LSTM (Box action spaces), n_lstm_layers > 1, shared_lstm=True, enable_critic_lstm=False.
+The update (back-propagation through time) is environments/lstm_learner.py.  Out of scope, and refused or absent: the
+Gaussian (sde) head on top of the LSTM (Box action spaces), n_lstm_layers > 1, shared_lstm=True, enable_critic_lstm=False.
 
 torch is imported lazily, by DeviceLstmPolicy only (reinfocus_amd/torch_interop.py says why import order matters).
 """

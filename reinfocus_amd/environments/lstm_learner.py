@@ -1,0 +1,464 @@
+"""Recurrent PPO's minibatch update for the actor-critic of environments/lstm.py: sb3-contrib's RecurrentPPO.train() --
+the sequences of a minibatch, the forward through both LSTMs from the stored states, the loss of environments/learner.py,
+its gradient by back-propagation through the MLPs and through time, clip_grad_norm_ and one Adam step per minibatch --
+the stage of training after a recurrent rollout's collect().
+
+One definition of the arithmetic (include/reinfocus_hip.h, "lstm update"; the scalar functions are csrc/rf_lstm_ppo.h):
+lstm_update_numpy below is its numpy restatement and the oracle; rf_lstm_ppo_update computes the same bits in six
+launches and updates the parameters in place.
+
+    sequence_rows        the sequence rule: which rows of a rotated minibatch start a sequence, and from which state
+    lstm_gradient_numpy  definition steps U1 to U8: the packed gradient, the loss terms, the validity flag
+    lstm_update_numpy    the whole update
+    LstmLearner          the numpy twin over an lstm.LstmPolicy and a rollout.Rollout collected with it
+    DeviceLstmLearner    the same methods over an lstm.DeviceLstmPolicy and a rollout.DeviceRollout: every update is
+                         enqueued on torch's current stream, the stats are rows of one device tensor, nothing waits for
+                         the host
+
+sb3-contrib never permutes the rows of a recurrent rollout: per epoch it rotates flat()'s order by one split index and
+cuts it into consecutive minibatches.  A minibatch is therefore (first, count): rows (first + b) mod N, b < count.
+
+Limits: the Categorical head, one LSTM layer per net of 1 .. 256 units, minibatches of 1 .. min(N, 1024) rows.
+
+torch is imported lazily, by DeviceLstmLearner only (reinfocus_amd/torch_interop.py says why import order matters).
+"""
+
+import numpy as np
+
+from reinfocus_amd.environments import lstm as lstm_module
+from reinfocus_amd.environments.learner import (BATCH_KEYS, INVALID, MAX_BATCH, NONFINITE, STATE_HEADER, Hyper, _back, _Hyper,
+                                                _normalised, _surrogate, checked_hyper, fresh_state, pack_state, state_parts)
+from reinfocus_amd.environments.lstm import sigmoid32
+from reinfocus_amd.environments.policy import _NAN, activation, canonical, exp32, f32, linear, log32, softmax_parts, tanh32
+
+PART_KEYS = BATCH_KEYS + ("episode_starts", "lstm_states", "n_steps", "num_envs")  # what an update reads of a rollout
+f64 = np.float64
+
+__all__ = ["DeviceLstmLearner", "Hyper", "LstmLearner", "PART_KEYS", "lstm_gradient_numpy", "lstm_update_numpy",
+           "parts_of", "sequence_rows"]
+
+
+def _checked_minibatch(n_steps, num_envs, first, count):
+    n_steps, num_envs, first, count = int(n_steps), int(num_envs), int(first), int(count)
+    if n_steps < 1 or num_envs < 1:
+        raise ValueError(f"n_steps {n_steps} and num_envs {num_envs} must be at least 1")
+    total = n_steps * num_envs
+    if not 1 <= count <= min(total, MAX_BATCH):
+        raise ValueError(f"a minibatch of {count} rows is not in 1 .. {min(total, MAX_BATCH)} (min(N, {MAX_BATCH}))")
+    if not 0 <= first < total:
+        raise ValueError(f"first {first} is not in 0 .. {total - 1}")
+    return n_steps, num_envs, first, count
+
+
+def sequence_rows(episode_starts, n_steps, num_envs, first, count):
+    """Definition steps U1 and U2: per minibatch row b the tuple (r, e, t, starts, zero) -- flat() row r = (first + b)
+    mod N of environment e at step t; starts: the row starts a sequence (b == 0, t == 0 or episode_starts[t][e] != 0);
+    zero: the state entering it is +0 (episode_starts[t][e] != 0), not lstm_states[t][..][e] (meaningless unless starts)."""
+    n_steps, num_envs, first, count = _checked_minibatch(n_steps, num_envs, first, count)
+    episode_starts = np.asarray(episode_starts).reshape(n_steps + 1, num_envs)
+    rows = []
+    for b in range(count):
+        r = (first + b) % (n_steps * num_envs)
+        e, t = divmod(r, n_steps)
+        flagged = bool(episode_starts[t, e] != 0)
+        rows.append((r, e, t, b == 0 or t == 0 or flagged, flagged))
+    return rows
+
+
+def _cell_rows(x, rows, states, lstm):
+    """Definition step U4's cells of one net over the minibatch: (h_prev, c_prev, gates [B, 4, H], c1, h1)."""
+    w_ih_t, w_hh_t, b_ih, b_hh = lstm
+    hidden = w_hh_t.shape[0]
+    count = len(rows)
+    start = linear(x, w_ih_t, b_ih + b_hh)  # (the chain of every row up to its h terms: b_ih + b_hh, then x_k * W_ih)
+    h_prev, c_prev, c1, h1 = (np.zeros((count, hidden), dtype=f32) for _ in range(4))
+    gates = np.zeros((count, 4, hidden), dtype=f32)
+    h = c = None
+    for b, (_, e, t, starts, zero) in enumerate(rows):
+        if starts:  # a select: a NaN of a dead state never enters
+            h = np.zeros(hidden, dtype=f32) if zero else states[0][t, e]
+            c = np.zeros(hidden, dtype=f32) if zero else states[1][t, e]
+        h_prev[b], c_prev[b] = h, c
+        a = linear(h[None, :], w_hh_t, start[b][None, :])[0].reshape(4, hidden)
+        i, f, g, o = sigmoid32(a[0]), sigmoid32(a[1]), tanh32(a[2]), sigmoid32(a[3])
+        fc = f * c
+        ig = i * g
+        c = fc + ig
+        h = o * tanh32(c)
+        gates[b], c1[b], h1[b] = (i, f, g, o), c, h
+    assert h1.dtype == f32 and c1.dtype == f32 and gates.dtype == f32
+    return h_prev, c_prev, gates, c1, h1
+
+
+def _mlp_backward(spec, layers, last, acts, delta_head):
+    """Definition step U6: (the MLP's deltas per layer, the head's last; dh_mlp [B, H])."""
+    matrices = [weight_t for weight_t, _ in layers] + [last[0]]
+    deltas = [None] * len(layers) + [delta_head]
+    for layer in range(len(layers) - 1, -1, -1):
+        deltas[layer] = _back(spec, matrices[layer + 1], deltas[layer + 1], acts[layer + 1])
+    dh = np.zeros(acts[0].shape, dtype=f32)
+    for o in range(matrices[0].shape[1]):  # no activation derivative: the LSTM's output has none
+        dh = dh + matrices[0][:, o][None, :] * deltas[0][:, o:o + 1]
+    assert dh.dtype == f32
+    return deltas, dh
+
+
+def _bptt(rows, w_hh_t, dh_mlp, c_prev, gates, c1):
+    """Definition step U7: da [B, 4, H]."""
+    count, hidden = dh_mlp.shape
+    by_gate = w_hh_t.reshape(hidden, 4, hidden).transpose(1, 0, 2)  # [q][k][j]
+    da = np.zeros((count, 4, hidden), dtype=f32)
+    one = f32(1.0)
+    ends = [b for b in range(count) if rows[b][3]][1:] + [count]
+    begins = [b for b in range(count) if rows[b][3]]
+    for begin, end in zip(begins, ends):
+        dh_rec = np.zeros(hidden, dtype=f32)
+        dc_next = np.zeros(hidden, dtype=f32)
+        for b in range(end - 1, begin - 1, -1):
+            i, f, g, o = gates[b]
+            dh = dh_mlp[b] + dh_rec
+            tc = tanh32(c1[b])
+            d_o = dh * tc
+            dc = (dh * o) * (one - tc * tc) + dc_next
+            da[b, 0] = (dc * g) * (i * (one - i))
+            da[b, 1] = (dc * c_prev[b]) * (f * (one - f))
+            da[b, 2] = (dc * i) * (one - g * g)
+            da[b, 3] = d_o * (o * (one - o))
+            dc_next = dc * f
+            if b == begin:
+                break
+            acc = np.zeros((4, hidden), dtype=f32)  # [q][k]
+            for j in range(hidden):
+                acc = acc + by_gate[:, :, j] * da[b, :, j][:, None]
+            dh_rec = (acc[0] + acc[1]) + (acc[2] + acc[3])
+    assert da.dtype == f32
+    return da
+
+
+def _chain(x, delta):
+    """Definition step U8 for one matrix and its bias: sums over b ascending from +0 of x[b][k] * delta[b][j]."""
+    weight = np.zeros((x.shape[1], delta.shape[1]), dtype=f32)
+    bias = np.zeros(delta.shape[1], dtype=f32)
+    for b in range(x.shape[0]):
+        weight = weight + x[b][:, None] * delta[b][None, :]
+        bias = bias + delta[b]
+    return weight, bias
+
+
+def _parts(parts):
+    """parts_of(rollout) for a rollout; a dict with PART_KEYS as it is."""
+    if hasattr(parts, "flat"):
+        parts = parts_of(parts)
+    return parts
+
+
+def parts_of(rollout):
+    """What an update reads of a finished rollout collected with a recurrent policy: flat()'s five arrays, the two
+    recurrent slabs in their own [T + 1, ...] layout, n_steps and num_envs."""
+    if getattr(rollout, "lstm_states", None) is None or getattr(rollout, "episode_starts", None) is None:
+        raise ValueError("the rollout has no lstm_states: it was not collected with a recurrent policy (collect() with an "
+                         "LstmPolicy / DeviceLstmPolicy keeps episode_starts and lstm_states; Learner / DeviceLearner train "
+                         "the feed-forward policies)")
+    flat = rollout.flat()
+    parts = {key: flat[key] for key in BATCH_KEYS}
+    parts.update(episode_starts=rollout.episode_starts, lstm_states=rollout.lstm_states, n_steps=rollout.n_steps,
+                 num_envs=rollout.num_envs)
+    return parts
+
+
+def lstm_gradient_numpy(spec, params, batch, episode_starts, lstm_states, n_steps, num_envs, first, count, hyper):
+    """Definition steps U1 to U8: (packed gradient float32 [P], the five loss terms float32 [5, B], invalid bool).  batch:
+    a dict with flat()'s keys (N = n_steps * num_envs rows each); episode_starts uint8 [T + 1, n]; lstm_states float32
+    [T + 1, 2, 2, n, H]; the minibatch is rows (first + b) mod N, b < count."""
+    hyper = checked_hyper(hyper)
+    n_steps, num_envs, first, count = _checked_minibatch(n_steps, num_envs, first, count)
+    total = n_steps * num_envs
+    hidden = spec.lstm_hidden
+    obs = np.asarray(batch["observations"], dtype=f32).reshape(total, spec.obs_width)
+    lstm_states = np.asarray(lstm_states, dtype=f32).reshape(n_steps + 1, 2, 2, num_envs, hidden)
+    rows = sequence_rows(episode_starts, n_steps, num_envs, first, count)
+    index = np.array([row[0] for row in rows], dtype=np.int64)
+    raw_actions = np.asarray(batch["actions"], dtype=np.int64).reshape(total)[index]
+    a = np.clip(raw_actions, 0, spec.n_actions - 1)
+    invalid = bool((a != raw_actions).any())
+    adv = np.asarray(batch["advantages"], dtype=f32).reshape(total)[index]
+    old = np.asarray(batch["log_probs"], dtype=f32).reshape(total)[index]
+    ret = np.asarray(batch["returns"], dtype=f32).reshape(total)[index]
+    x = obs[index]
+    params = np.asarray(params, dtype=f32).reshape(spec.size)
+    with np.errstate(all="ignore"):
+        adv = _normalised(adv, hyper, count)
+        cells, mlps, heads = [], [], []
+        for net, (lstm, layers, last) in enumerate(spec.nets(params)):
+            states = (lstm_states[:, net, 0], lstm_states[:, net, 1])  # [T + 1, n, H] each
+            cells.append(_cell_rows(x, rows, states, lstm))
+            acts = [cells[-1][4]]
+            for weight_t, bias in layers:
+                acts.append(activation(linear(acts[-1], weight_t, bias), spec.activation))
+            mlps.append(acts)
+            heads.append(linear(acts[-1], *last))
+        logits, v = heads[0], heads[1][:, 0]
+        _, z, _, s, degenerate = softmax_parts(logits)
+        e = exp32(z)
+        lse = np.where(degenerate, _NAN, log32(np.where(degenerate, f32(1.0), s)))
+        logp = z - lse[:, None]
+        p = e / s[:, None]
+        acc = np.zeros(count, dtype=f32)
+        for i in range(spec.n_actions):
+            acc = acc + np.where(e[:, i] == f32(0.0), f32(0.0), p[:, i] * logp[:, i])
+        entropy = -acc
+        every = np.arange(count)
+        c, ec, vc = f32(hyper.clip_range), f32(hyper.ent_coef), f32(hyper.vf_coef)
+        pg, kl, clipped, g = _surrogate(logp[every, a] - old, adv, c)
+        t = ret - v
+        vl = t * t
+        count_f = f32(count)
+        onehot = np.zeros((count, spec.n_actions), dtype=f32)
+        onehot[every, a] = f32(1.0)
+        pull = (-g)[:, None] * (onehot - p)
+        ent = np.where(e == f32(0.0), f32(0.0), (ec * p) * (logp + entropy[:, None]))
+        dlogit = (pull + ent) / count_f
+        dv = ((vc * f32(2.0)) * (v - ret)) / count_f
+        pieces = []
+        for net, (delta_head, (lstm, layers, last)) in enumerate(zip((dlogit, dv[:, None]), spec.nets(params))):
+            h_prev, c_prev, gates, c1, _ = cells[net]
+            deltas, dh_mlp = _mlp_backward(spec, layers, last, mlps[net], delta_head)
+            da = _bptt(rows, lstm[1], dh_mlp, c_prev, gates, c1).reshape(count, 4 * hidden)
+            w_ih, b_ih = _chain(x, da)
+            w_hh, _ = _chain(h_prev, da)
+            pieces += [w_ih.reshape(-1), w_hh.reshape(-1), b_ih, b_ih]
+            for acts_in, delta in zip(mlps[net], deltas):
+                weight, bias = _chain(acts_in, delta)
+                pieces += [weight.reshape(-1), bias]
+    grad = canonical(np.concatenate(pieces))
+    terms = np.stack([pg, vl, entropy, kl, clipped])
+    assert grad.dtype == f32 and grad.size == spec.size and terms.dtype == f32
+    return grad, terms, invalid
+
+
+def lstm_update_numpy(spec, params, state, batch, episode_starts, lstm_states, n_steps, num_envs, first, count, hyper):
+    """The definition, literally.  params float32 [P] and state (the packed optimizer state of learner.py) are not
+    modified; the other arguments as lstm_gradient_numpy's.  Returns (new params, new state, stats float32 [8])."""
+    from reinfocus_amd.environments.harness import treesum
+
+    hyper = checked_hyper(hyper)
+    params = np.asarray(params, dtype=f32).reshape(spec.size)
+    grad, terms, invalid = lstm_gradient_numpy(spec, params, batch, episode_starts, lstm_states, n_steps, num_envs, first,
+                                               count, hyper)
+    count = terms.shape[1]
+    step, bc1, bc2, m, v = state_parts(spec, state)
+    with np.errstate(all="ignore"):
+        wide = grad.astype(f64)
+        norm = np.sqrt(treesum(wide * wide))
+        flags = INVALID if invalid else (0 if np.isfinite(norm) else NONFINITE)
+        stats = np.zeros(8, dtype=f32)
+        for i in range(5):
+            stats[i] = canonical(f32(treesum(terms[i]) / f64(count)))
+        stats[5] = canonical(f32(norm))
+        stats[6] = canonical((stats[0] + f32(hyper.ent_coef) * (-stats[2])) + f32(hyper.vf_coef) * stats[1])
+        stats[7] = f32(flags)
+        if flags:
+            return params.copy(), np.array(state, dtype=f32, copy=True).reshape(-1), stats
+        q = f64(hyper.max_grad_norm) / (norm + f64(1e-6))
+        coef = f32(q if q < 1.0 else 1.0)
+        b1, ob1 = f32(hyper.beta1), f32(f64(1.0) - f64(hyper.beta1))
+        b2, ob2 = f32(hyper.beta2), f32(f64(1.0) - f64(hyper.beta2))
+        bc1 = f64(1.0) - f64(hyper.beta1) * (f64(1.0) - bc1)
+        bc2 = f64(1.0) - f64(hyper.beta2) * (f64(1.0) - bc2)
+        g = grad * coef
+        m = b1 * m + ob1 * g
+        v = b2 * v + ob2 * (g * g)
+        denom = np.sqrt(v) / f32(np.sqrt(bc2)) + f32(hyper.adam_eps)
+        new = params - f32(f64(hyper.learning_rate) / bc1) * (m / denom)
+    assert new.dtype == f32 and m.dtype == f32 and v.dtype == f32
+    return new, pack_state(spec, step + 1, bc1, bc2, m, v), stats
+
+
+class _Splits(_Hyper):
+    """What both learners share: the hyper-parameters of learner._Hyper and sb3-contrib's minibatches of an epoch."""
+
+    def _refuse_rollout(self, rollout):
+        lstm_module._refuse_box(rollout.env.single_action_space)
+
+    @staticmethod
+    def _minibatches(total, n_epochs, batch_size, splits, generator):
+        """[(first, count)] of every update of train(), in order: per epoch one split index (row e of splits, else
+        generator.integers(N): a host draw, no synchronisation), then first = (split + i * batch_size) mod N and
+        count = min(batch_size, N - i * batch_size)."""
+        n_epochs, batch_size, per_epoch = _Hyper._batches(total, n_epochs, batch_size)
+        if splits is not None:
+            splits = [int(s) for s in np.asarray(splits).reshape(-1)]
+            if len(splits) != n_epochs or not all(0 <= s < total for s in splits):
+                raise ValueError(f"splits must be {n_epochs} integers in 0 .. {total - 1}, one per epoch")
+        elif generator is None:
+            generator = np.random.default_rng()
+        out = []
+        for epoch in range(n_epochs):
+            split = splits[epoch] if splits is not None else int(generator.integers(total))
+            out += [((split + i * batch_size) % total, min(batch_size, total - i * batch_size)) for i in range(per_epoch)]
+        return out
+
+
+class LstmLearner(_Splits):
+    """The numpy twin of DeviceLstmLearner, and its oracle: updates policy.params (an lstm.LstmPolicy's) in place."""
+
+    def __init__(self, policy, learning_rate=3e-4, clip_range=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5,
+                 normalize_advantage=True, betas=(0.9, 0.999), adam_eps=1e-5):
+        if not isinstance(policy, lstm_module.LstmPolicy):
+            raise TypeError(f"LstmLearner needs an LstmPolicy, not {type(policy).__name__} (a DeviceLstmPolicy has "
+                            "DeviceLstmLearner, the feed-forward policies Learner)")
+        self.policy, self.spec = policy, policy.spec
+        self._configure(learning_rate, clip_range, ent_coef, vf_coef, max_grad_norm, normalize_advantage, betas, adam_eps)
+        self.state = fresh_state(self.spec)
+
+    def update(self, rollout_or_parts, first, count):
+        """One minibatch update from rows (first + b) mod N, b < count, of a finished recurrent rollout (or of
+        parts_of(rollout): a dict with PART_KEYS); returns the stats float32 [8]."""
+        parts = _parts(rollout_or_parts)
+        params, self.state, stats = lstm_update_numpy(
+            self.spec, self.policy.params, self.state, parts, parts["episode_starts"], parts["lstm_states"],
+            parts["n_steps"], parts["num_envs"], first, count, self.hyper())
+        self.policy.params[:] = params
+        return stats
+
+    def train(self, rollout, n_epochs, batch_size, splits=None, generator=None):
+        """n_epochs passes over a finished recurrent rollout in minibatches of batch_size consecutive rows (the last one
+        may be shorter): stats float32 [n_epochs * ceil(N / batch_size), 8].  Per epoch one split index: row e of splits (a
+        sequence of n_epochs ints) if given, else generator.integers(N) (generator: a numpy.random.Generator)."""
+        self._refuse_rollout(rollout)
+        parts = parts_of(rollout)
+        total = parts["n_steps"] * parts["num_envs"]
+        batches = self._minibatches(total, n_epochs, batch_size, splits, generator)
+        stats = np.zeros((len(batches), 8), dtype=f32)
+        for i, (first, count) in enumerate(batches):
+            stats[i] = self.update(parts, first, count)
+        return stats
+
+    def state_dict(self):
+        """The optimizer: step, the running bias corrections bc1 / bc2 (1 - beta^step) and copies of m and v."""
+        step, bc1, bc2, m, v = state_parts(self.spec, self.state)
+        return {"step": step, "bc1": float(bc1), "bc2": float(bc2), "m": m.copy(), "v": v.copy()}
+
+    def load_state_dict(self, state):
+        self.state = pack_state(self.spec, int(state["step"]), float(state["bc1"]), float(state["bc2"]),
+                                np.asarray(state["m"], dtype=f32).reshape(self.spec.size),
+                                np.asarray(state["v"], dtype=f32).reshape(self.spec.size))
+
+
+class DeviceLstmLearner(_Splits):
+    """The learner of an lstm.DeviceLstmPolicy, over torch tensors on its GPU; used as LstmLearner is and bit for bit
+    equal to it.  update() is rf_lstm_ppo_update: six launches on torch's current stream, which change policy.params in
+    place -- the next collect() on the same stream sees them.  train() enqueues every update of every epoch back to
+    back; the split indices are host integers and the stats are rows of one device tensor.  No method synchronises the
+    host (state_dict() reads the step and does)."""
+
+    def __init__(self, policy, learning_rate=3e-4, clip_range=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5,
+                 normalize_advantage=True, betas=(0.9, 0.999), adam_eps=1e-5):
+        if not isinstance(policy, lstm_module.DeviceLstmPolicy):
+            raise TypeError(f"DeviceLstmLearner needs a DeviceLstmPolicy, not {type(policy).__name__} (an LstmPolicy has "
+                            "LstmLearner, the feed-forward policies DeviceLearner)")
+        self.policy, self.spec = policy, policy.spec
+        self._configure(learning_rate, clip_range, ent_coef, vf_coef, max_grad_norm, normalize_advantage, betas, adam_eps)
+        self._torch, self._interop, self._io, self._ctx = policy._torch, policy._interop, policy._io, policy._ctx
+        self.device = policy.device
+        torch = self._torch
+        if self._ctx.lstm_ppo_state_size(self.spec.desc()) != 4 * (STATE_HEADER + 2 * self.spec.size):
+            raise RuntimeError("rf_lstm_ppo_state_size disagrees with the packed optimizer state")
+        self.state = torch.zeros(STATE_HEADER + 2 * self.spec.size, dtype=torch.float32, device=self.device)
+        self._workspace, self._workspace_batch = None, 0
+        self._stats = None
+
+    def _checked(self, parts, first, count):
+        """(n_steps, num_envs, first, count) of an update whose tensors are what rf_lstm_ppo_update reads."""
+        torch = self._torch
+        n_steps, num_envs, first, count = _checked_minibatch(parts["n_steps"], parts["num_envs"], first, count)
+        total, hidden = n_steps * num_envs, self.spec.lstm_hidden
+        if isinstance(parts.get("actions"), torch.Tensor) and parts["actions"].dtype == torch.float32:
+            raise ValueError("the update has a Categorical head over int64 actions, not a float32 action slab: the Gaussian "
+                             "(sde) head on top of the LSTM is out of scope")
+        wanted = {"observations": (torch.float32, (total, self.spec.obs_width)), "actions": (torch.int64, (total,)),
+                  "log_probs": (torch.float32, (total,)), "advantages": (torch.float32, (total,)),
+                  "returns": (torch.float32, (total,)), "episode_starts": (torch.uint8, (n_steps + 1, num_envs)),
+                  "lstm_states": (torch.float32, (n_steps + 1, 2, 2, num_envs, hidden))}
+        for key, (dtype, shape) in wanted.items():
+            tensor = parts[key]
+            if not isinstance(tensor, torch.Tensor):
+                raise TypeError(f"{key} must be a torch.Tensor on {self.device}, not {type(tensor).__name__}")
+            self._io._on_device(tensor, key)
+            if tensor.dtype != dtype or tuple(tensor.shape) != shape or not tensor.is_contiguous():
+                raise ValueError(f"{key} is {tensor.dtype} {tuple(tensor.shape)}, not contiguous {dtype} {shape}")
+        return n_steps, num_envs, first, count
+
+    def _room(self, batch):
+        if batch > self._workspace_batch:
+            size = self._ctx.lstm_ppo_workspace_size(self.spec.desc(), batch)
+            if size == 0:
+                raise RuntimeError(f"rf_lstm_ppo_workspace_size refuses a minibatch of {batch}")
+            self._workspace = self._torch.zeros(size // 4, dtype=self._torch.float32, device=self.device)
+            self._workspace_batch = batch
+
+    def _enqueue(self, parts, n_steps, num_envs, first, count, stats, hyper):
+        self._ctx.lstm_ppo_update(self.spec.desc(), hyper, self.policy.params.data_ptr(), self.state.data_ptr(),
+                                  self._workspace.data_ptr(), n_steps, num_envs, parts["observations"].data_ptr(),
+                                  parts["actions"].data_ptr(), parts["log_probs"].data_ptr(),
+                                  parts["advantages"].data_ptr(), parts["returns"].data_ptr(),
+                                  parts["episode_starts"].data_ptr(), parts["lstm_states"].data_ptr(), first, count,
+                                  stats.data_ptr(), self._io._stream())
+
+    def _own(self, rollout):
+        if getattr(rollout, "device", None) != self.device:
+            raise ValueError(f"the rollout lives on {getattr(rollout, 'device', 'the host')}, the policy on {self.device}")
+
+    def update(self, rollout_or_parts, first, count):
+        """One minibatch update from rows (first + b) mod N, b < count, of a finished recurrent DeviceRollout (or of
+        parts_of(rollout)); returns the stats, a float32 [8] tensor the learner owns and the next update() overwrites."""
+        if hasattr(rollout_or_parts, "flat"):
+            self._own(rollout_or_parts)
+        parts = _parts(rollout_or_parts)
+        n_steps, num_envs, first, count = self._checked(parts, first, count)
+        self._interop.check_one_runtime()
+        self._room(count)
+        if self._stats is None:
+            self._stats = self._torch.zeros(8, dtype=self._torch.float32, device=self.device)
+        self._enqueue(parts, n_steps, num_envs, first, count, self._stats, self.hyper())
+        return self._stats
+
+    def train(self, rollout, n_epochs, batch_size, splits=None, generator=None):
+        """As LstmLearner.train, over a finished recurrent DeviceRollout of the policy's GPU; the split indices are host
+        integers (splits, else generator.integers(N) of a numpy.random.Generator: a host draw costs no synchronisation).
+        Every update is enqueued back to back; returns the stats as one device tensor [n_epochs * ceil(N / batch_size), 8]
+        that is complete when the stream reaches this point.  Nothing waits for the host."""
+        torch = self._torch
+        self._refuse_rollout(rollout)
+        self._own(rollout)
+        parts = parts_of(rollout)
+        total = parts["n_steps"] * parts["num_envs"]
+        batches = self._minibatches(total, n_epochs, batch_size, splits, generator)
+        n_steps, num_envs, _, _ = self._checked(parts, *batches[0])
+        self._interop.check_one_runtime()
+        self._room(max(count for _, count in batches))
+        hyper = self.hyper()
+        stats = torch.zeros((len(batches), 8), dtype=torch.float32, device=self.device)
+        for i, (first, count) in enumerate(batches):
+            self._enqueue(parts, n_steps, num_envs, first, count, stats[i], hyper)
+        return stats
+
+    def state_dict(self):
+        """The optimizer: step, bc1, bc2 (read from the device: this synchronises) and clones of m and v."""
+        head = self.state[:STATE_HEADER].cpu().numpy()
+        size = self.spec.size
+        return {"step": int(head.view(np.int64)[0]), "bc1": float(head.view(f64)[1]), "bc2": float(head.view(f64)[2]),
+                "m": self.state[STATE_HEADER:STATE_HEADER + size].clone(), "v": self.state[STATE_HEADER + size:].clone()}
+
+    def load_state_dict(self, state):
+        torch = self._torch
+        size = self.spec.size
+        for key in ("m", "v"):
+            tensor = state[key]
+            if not isinstance(tensor, torch.Tensor) or tensor.dtype != torch.float32 or tensor.numel() != size:
+                raise ValueError(f"{key} must be a torch.float32 tensor of {size} elements on {self.device}")
+            self._io._on_device(tensor, key)
+        head = pack_state(self.spec, int(state["step"]), float(state["bc1"]), float(state["bc2"]), 0.0, 0.0)[:STATE_HEADER]
+        self.state[:STATE_HEADER].copy_(torch.from_numpy(head.copy()))
+        self.state[STATE_HEADER:STATE_HEADER + size].copy_(state["m"].reshape(size))
+        self.state[STATE_HEADER + size:].copy_(state["v"].reshape(size))
