@@ -335,6 +335,39 @@ __device__ __forceinline__ int coop_finish2m(CoopLds2 &lds, int parity, int *cnt
             }
         }
     };
+    // The same for a wave that took its slots with one atomic (WAVE_SLOTS).  `fits` (wave-uniform, a scalar): the wave's
+    // range of slots ends within the list, so every straggler is parked and the per-lane `slot < cap` compare of each
+    // set has nothing to decide.  One copy of the stores for both cases; only the masks differ.
+    auto park_wave = [&](bool fits) {
+        if (fits) {
+#pragma unroll
+            for (int j = 0; j < kSets; ++j)
+                parked[j] = need[j];
+        } else {
+#pragma unroll
+            for (int j = 0; j < kSets; ++j)
+                parked[j] = need[j] & lanes_where(slot[j] < kCoopCap * 16);
+        }
+#pragma unroll
+        for (int j = 0; j < kSets; ++j) {
+            if (lane_in(parked[j]))
+                *entry16(state, slot[j]) = make_uint4(g[j].a_lo, g[j].a_hi, g[j].b_lo, g[j].b_hi);
+        }
+        if (fits)
+            return;
+#pragma unroll
+        for (int j = 0; j < kSets; ++j) {
+            if (lane_in(need[j] & ~parked[j])) { // overflow of the packed list: finish in place
+                if (DIM == 2) {
+                    while (!disc_attempt(g[j], w[j])) {
+                    }
+                } else {
+                    while (!sphere_attempt(g[j], w[j])) {
+                    }
+                }
+            }
+        }
+    };
     int all = 0; // stragglers of this wave (WAVE_SLOTS)
     if (WAVE_SLOTS) {
         int pop[kSets];
@@ -356,6 +389,10 @@ __device__ __forceinline__ int coop_finish2m(CoopLds2 &lds, int parity, int *cnt
             if ((tid & 63) == 0)
                 base = atomicAdd(cnt, all * 16);
             base = __builtin_amdgcn_readfirstlane(base);
+            // The wave's slots are [base, base + all * 16): when that range ends within the list -- a scalar compare;
+            // always, but for the blocks with more stragglers than the list holds -- every straggler is parked and
+            // park()'s per-lane `slot < cap` compare, one per set, has nothing to decide.
+            const bool fits = base + all * 16 <= kCoopCap * 16; // wave-uniform
 #pragma unroll
             for (int j = 0; j < kSets; ++j) {
                 const int rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(need[j] >> 32),
@@ -363,7 +400,7 @@ __device__ __forceinline__ int coop_finish2m(CoopLds2 &lds, int parity, int *cnt
                 slot[j] = base + rank * 16;
                 base += pop[j] * 16;
             }
-            park();
+            park_wave(fits);
         }
     } else {
 #pragma unroll
@@ -432,16 +469,36 @@ __device__ __forceinline__ void disc_tails_wave(uint4 *region, const lanemask (&
         return;
     int slot[kSets];
     lanemask packed[kSets];
+    // All stragglers fit when there are no more of them than slots -- a scalar compare of the popcounts' sum; with 64
+    // slots all but ~1e-5 of the wave-samples -- and then every one is packed: the per-lane `slot < end` compare of each
+    // set has nothing to decide.
+    const bool fits = total <= kDiscWaveSlots; // wave-uniform
 #pragma unroll
     for (int j = 0; j < kSets; ++j) {
         const int rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(need[j] >> 32),
                                                         __builtin_amdgcn_mbcnt_lo((unsigned)need[j], 0));
         slot[j] = (wbase + first[j] + rank) * 16; // byte offset of the entry
-        packed[j] = need[j] & lanes_where(slot[j] < (wbase + kDiscWaveSlots) * 16);
+    }
+    if (fits) {
+#pragma unroll
+        for (int j = 0; j < kSets; ++j)
+            packed[j] = need[j];
+    } else {
+#pragma unroll
+        for (int j = 0; j < kSets; ++j)
+            packed[j] = need[j] & lanes_where(slot[j] < (wbase + kDiscWaveSlots) * 16);
+    }
+#pragma unroll
+    for (int j = 0; j < kSets; ++j) {
         if (lane_in(packed[j]))
             *entry16(region, slot[j]) = make_uint4(g[j].a_lo, g[j].a_hi, g[j].b_lo, g[j].b_hi);
-        if (lane_in(need[j] & ~packed[j])) { // more stragglers in one wave than slots (p ~ 1e-5 with 64): in place
-            while (!disc_attempt(g[j], w[j])) {
+    }
+    if (!fits) {
+#pragma unroll
+        for (int j = 0; j < kSets; ++j) {
+            if (lane_in(need[j] & ~packed[j])) { // more stragglers in one wave than slots (p ~ 1e-5 with 64): in place
+                while (!disc_attempt(g[j], w[j])) {
+                }
             }
         }
     }
@@ -613,9 +670,9 @@ __device__ __forceinline__ void render_tile_coop2(const RenderArgs &a_in, CoopLd
             cam9[i] = as_const(scene_cam + (size_t)e * 9)[i];
         rect2[0] = as_const(scene_rect + (size_t)e * 2)[0];
         rect2[1] = as_const(scene_rect + (size_t)e * 2)[1];
-        env0 = make_pixel_env(cam9, rect2);
+        env0 = make_pixel_env(cam9, rect2, lens_bound(a.cs));
     } else {
-        env0 = make_pixel_env(scene_cam + (size_t)e * 9, scene_rect + (size_t)e * 2);
+        env0 = make_pixel_env(scene_cam + (size_t)e * 9, scene_rect + (size_t)e * 2, lens_bound(a.cs));
     }
     // block-uniform values computed with vector instructions: keep them in scalar registers
     auto uniform = [](float v) { // (the builtin alone is folded away for values known to be uniform)
@@ -642,6 +699,7 @@ __device__ __forceinline__ void render_tile_coop2(const RenderArgs &a_in, CoopLd
         live_m[j] = lanes_where(geometry(tid).x_of(j) < a.w) & lanes_where(geometry(tid).y_of(j) < a.h);
     // per-environment conditions as scalars (a uniform `bool` is a lane mask that vector instructions test)
     const int tmiss_s = __builtin_amdgcn_readfirstlane((int)env0.tmiss);
+    const int dir_fast_s = __builtin_amdgcn_readfirstlane((int)env0.dir_fast);
     for (int k = 0; k < a.spp; ++k) {
         const PixelEnv &env = env0;
         uint32_t w[kSets][6];
@@ -716,7 +774,7 @@ __device__ __forceinline__ void render_tile_coop2(const RenderArgs &a_in, CoopLd
             const bool hit = lane_in(hit_m[j]);
             if (hit)
                 sphere_finish(w[j], q0, q1, q2);
-            const Colour c = sample_axis_shade(hit, red[j], rdx[j], rdy[j], rdz[j], q0, q1, q2);
+            const Colour c = sample_axis_shade(dir_fast_s, hit, red[j], rdx[j], rdy[j], rdz[j], q0, q1, q2);
             if (j < kColourLds) {
                 // (read + add + write: the LDS unit's own float add, ds_add_f32, is bit-identical and 2.5x slower end to end)
                 lds_colour[j][0][tid] = add2_not_negzero(lds_colour[j][0][tid], c.r);

@@ -683,7 +683,42 @@ struct PixelEnv {
     float den;  // rectangle.py:168  x_max - x_min = half - (-half)
     float rden; // RN(1 / den), for div_by_const
     bool fast_div; // den in [2^-40, 2^40]: no intermediate of div_by_const can underflow
+    bool dir_fast; // every shading direction of this environment has sq_len in [2^-100, 2^100): dir_fast_env below
 };
+
+// An upper bound of |cs.lens_radius| in float32, for dir_fast_env.  RN32(|r|) lies at most half an ulp below |r| and
+// RN32(1 + 2^-23 times it) at least one ulp above RN32(|r|) (normal range; below it the bound does not matter).  A NaN
+// stays one, and so does an infinity as far as the comparisons of dir_fast_env go.
+RF_HD float lens_bound(const CamStatic &cs)
+{
+    return __builtin_fabsf((float)cs.lens_radius) * 0x1.000002p+0f;
+}
+
+// The per-environment form of in_fast_range(sq_len(d)) for the canonical camera frame: true only when EVERY direction
+// sample_axis_shade normalises for this environment has its squared length in [2^-100, 2^100), so that the per-lane
+// test of unit_dir_y can be left out (len_inv_rn_fast needs exactly that range).  lens_r >= |lens radius|.
+//   hit lanes shade (q0, q1, 1 + q2), q an accepted sphere draw: |q|^2 < 1 and every component is a multiple of 2^-24,
+//     so q2 >= -1 + 2^-24, 1 + q2 >= 2^-24 (the float sum is exact or rounds within [1, 2)), |q0|, |q1| < 1, 1 + q2 < 2:
+//     sq in [2^-48, 6) whatever the environment is.
+//   miss lanes shade (rdx, rdy, llz) of sample_axis_point: rdx = RN(RN(llx + RN(hx s)) - ox) with s in [0, 1] and
+//     |ox| <= lens_r (lens_offset: a disc coordinate in [-1, 1] times the radius, rounded), hence
+//     |rdx| <= (|llx| + |hx| + lens_r)(1 + 2^-22) =: Bx (1 + 2^-22), and rdy likewise with lly, vy and t.  The flag asks
+//     for Bx, By <= 2^48 (as float sums: their own rounding is another 2^-23) and 2^-49 <= |llz| <= 2^48.  Then
+//     sq_len = RN(RN(RN(rdx^2) + RN(rdy^2)) + RN(llz^2)) >= RN(llz^2) >= 2^-98 (rounding is monotone, the other terms
+//     are >= 0) and <= 3 * 2^96 (1 + 2^-20) < 2^98; no product overflows, and one that underflows only adds +0.
+//   Lanes outside the frame (s or t beyond 1) may leave the range: len_inv_rn_fast gives them some value, possibly a
+//   NaN, and no instruction traps; nothing of such a lane is stored.
+// Every comparison has to be TRUE: a NaN or an infinity anywhere makes the flag false.
+// tests/dirfast checks the claim at every threshold; tests/test_dir_fast_bound.py also that every FastCameras focus
+// gets the flag.
+RF_HD bool dir_fast_env(const CamDyn &d, float lens_r)
+{
+    constexpr float kLo = 0x1p-49f, kHi = 0x1p+48f;
+    const float az = __builtin_fabsf(d.llz);
+    const float bx = (__builtin_fabsf(d.llx) + __builtin_fabsf(d.hx)) + lens_r;
+    const float by = (__builtin_fabsf(d.lly) + __builtin_fabsf(d.vy)) + lens_r;
+    return az >= kLo && az <= kHi && bx <= kHi && by <= kHi;
+}
 
 // Correctly rounded a / d for a divisor known in advance (Markstein): with r = RN(1/d),
 // q0 = RN(a*r) is within 1 ulp of a/d, the residual a - q0*d is exact in one fma, and
@@ -697,7 +732,9 @@ RF_HD float div_by_const(float a, float d, float rd)
     return __builtin_fmaf(rem, rd, q0);
 }
 
-RF_HD PixelEnv make_pixel_env(const float *cd, const float *rc)
+// lens_r: lens_bound(cs) of the camera the environment is rendered with; a caller that does not say (the host twin of
+// tests/hostsim) gets dir_fast == false, the guarded normalisation: the same values.
+RF_HD PixelEnv make_pixel_env(const float *cd, const float *rc, float lens_r = __builtin_inff())
 {
     PixelEnv e;
     e.dyn = CamDyn{cd[0], cd[1], cd[2], cd[3], cd[4], cd[5], cd[6], cd[7], cd[8]};
@@ -707,6 +744,7 @@ RF_HD PixelEnv make_pixel_env(const float *cd, const float *rc)
     e.den = e.rect.half - (-e.rect.half);
     e.rden = 1.0f / e.den;
     e.fast_div = e.den >= 9.094947017729282e-13f && e.den <= 1099511627776.0f;
+    e.dir_fast = dir_fast_env(e.dyn, lens_r);
     return e;
 }
 
@@ -775,10 +813,22 @@ RF_HD AxisPre sample_axis_ray(float p0, float p1, const PixelEnv &e, const CamSt
 // physics.fast_find_colour's tail (physics.py:183-193) for a hit (scattered direction
 // N + q = (q0, q1, 1 + q2), attenuation red or green) or a miss (primary direction).
 // (hit / red given apart from the ray: render_kernel_coop2 keeps them as lane masks in scalar registers)
-RF_HD Colour sample_axis_shade(bool hit, bool red, float rdx, float rdy, float rdz, float q0, float q1, float q2)
+// dir_fast: PixelEnv::dir_fast of the environment, as an integer the caller keeps in a scalar register (a uniform `bool`
+// hoisted out of a sample loop is a lane mask): with it the direction's length is known to be in len_inv_rn_fast's
+// range and unit_dir_y's per-lane test of it -- an integer add, a compare and the exec bookkeeping of its branch per
+// pixel set and sample -- is left out.
+RF_HD Colour sample_axis_shade(int dir_fast, bool hit, bool red, float rdx, float rdy, float rdz, float q0, float q1,
+                               float q2)
 {
     const float dx = hit ? q0 : rdx, dy = hit ? q1 : rdy, dz = hit ? 1.0f + q2 : rdz;
-    const float ud1 = unit_dir_y(dx, dy, dz);
+    float ud1;
+    if (dir_fast) { // per-environment condition: uniform across the block
+        float len, inv;
+        len_inv_rn_fast(sq_len(dx, dy, dz), len, inv);
+        ud1 = dy * inv;
+    } else {
+        ud1 = unit_dir_y(dx, dy, dz);
+    }
     const float white = sky_white(ud1);
     Colour c;
     if (hit) {
@@ -794,9 +844,9 @@ RF_HD Colour sample_axis_shade(bool hit, bool red, float rdx, float rdy, float r
     }
     return c;
 }
-RF_HD Colour sample_axis_shade(const AxisPre &r, float q0, float q1, float q2)
+RF_HD Colour sample_axis_shade(int dir_fast, const AxisPre &r, float q0, float q1, float q2)
 {
-    return sample_axis_shade(r.hit, r.red, r.dx, r.dy, r.dz, q0, q1, q2);
+    return sample_axis_shade(dir_fast, r.hit, r.red, r.dx, r.dy, r.dz, q0, q1, q2);
 }
 
 RF_HD AxisPre sample_axis_pre(Rng &g, const PixelEnv &e, const CamStatic &cs, float s, float t,
@@ -814,7 +864,7 @@ RF_HD Colour sample_axis(Rng &g, const PixelEnv &e, const CamStatic &cs, float s
     float q0 = 0.0f, q1 = 0.0f, q2 = 0.0f;
     if (r.hit)
         sphere_sample(g, q0, q1, q2);
-    return sample_axis_shade(r, q0, q1, q2);
+    return sample_axis_shade((int)e.dir_fast, r, q0, q1, q2);
 }
 
 // what the jittered coordinates need to know about the frame, computed once on the host (kernel arguments: scalar

@@ -61,7 +61,7 @@ __global__ __launch_bounds__(kBlock) void render_kernel(RenderArgs a)
         uint8_t *const frames = (TWO && pass + 1 < passes) ? a.frames2 : a.frames;
         float cr = 0.0f, cg = 0.0f, cb = 0.0f;
         if (live) {
-            const PixelEnv env = make_pixel_env(cam + (size_t)e * 9, rect + (size_t)e * 2);
+            const PixelEnv env = make_pixel_env(cam + (size_t)e * 9, rect + (size_t)e * 2, lens_bound(a.cs));
             render_pixel<AXIS, POW2>(g, x, y, a.spp, a.fc, env, a.cs, a.tab, cr, cg, cb);
         }
 

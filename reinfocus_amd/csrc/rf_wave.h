@@ -240,9 +240,9 @@ __global__ __launch_bounds__(64, WaveTune<K>::occupancy) void render_kernel_wave
             cam9[i] = as_const(scene_cam + (size_t)e * 9)[i];
         rect2[0] = as_const(scene_rect + (size_t)e * 2)[0];
         rect2[1] = as_const(scene_rect + (size_t)e * 2)[1];
-        env0 = make_pixel_env(cam9, rect2);
+        env0 = make_pixel_env(cam9, rect2, lens_bound(a.cs));
     } else {
-        env0 = make_pixel_env(scene_cam + (size_t)e * 9, scene_rect + (size_t)e * 2);
+        env0 = make_pixel_env(scene_cam + (size_t)e * 9, scene_rect + (size_t)e * 2, lens_bound(a.cs));
     }
     auto uniform = [](float v) {
         int bits = __builtin_bit_cast(int, v);
@@ -265,6 +265,7 @@ __global__ __launch_bounds__(64, WaveTune<K>::occupancy) void render_kernel_wave
     for (int j = 0; j < K; ++j)
         live_m[j] = lanes_where(pixel_of(tid, j) < a.hw);
     const int tmiss_s = __builtin_amdgcn_readfirstlane((int)env0.tmiss);
+    const int dir_fast_s = __builtin_amdgcn_readfirstlane((int)env0.dir_fast);
     const int log2w = POW2 ? __builtin_ctz((unsigned)a.w) : 0;
     wave_lds_order();
     for (int k = 0; k < a.spp; ++k) {
@@ -352,7 +353,7 @@ __global__ __launch_bounds__(64, WaveTune<K>::occupancy) void render_kernel_wave
             const bool hit = lane_in(hit_m[j]);
             if (hit)
                 sphere_finish(w[j], q0, q1, q2);
-            const Colour c = sample_axis_shade(hit, red[j], rdx[j], rdy[j], rdz[j], q0, q1, q2);
+            const Colour c = sample_axis_shade(dir_fast_s, hit, red[j], rdx[j], rdy[j], rdz[j], q0, q1, q2);
             if (j < kColourLdsW) {
                 lds.colour[j][0][tid] = add2_not_negzero(lds.colour[j][0][tid], c.r);
                 lds.colour[j][1][tid] = add2_not_negzero(lds.colour[j][1][tid], c.g);
