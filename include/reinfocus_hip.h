@@ -1008,8 +1008,8 @@ int rf_sde_update(rf_ctx *ctx, const rf_policy_desc *policy, const rf_ppo_desc *
  * The reference's other two training configurations (examples/ppo_lstm_*.yml) run policy: 'MlpLstmPolicy', sb3-contrib's
  * RecurrentPPO with RecurrentActorCriticPolicy at its defaults: lstm_hidden_size=256, n_lstm_layers=1, shared_lstm=False,
  * enable_critic_lstm=True.  No reference counterpart.  Needs no environment: the context only says which GPU.
- * The update (back-propagation through time) is "lstm update" below.  Out of scope: the Gaussian (sde) head on top of the
- * LSTM, n_lstm_layers > 1, shared_lstm=True, enable_critic_lstm=False.
+ * The update (back-propagation through time) is "lstm update" below; the Gaussian (sde) head on top of the LSTM is "lstm
+ * sde policy" further down.  Out of scope: n_lstm_layers > 1, shared_lstm=True, enable_critic_lstm=False.
  *
  * One definition, numpy twin (environments/lstm.py lstm_numpy), host build (tests/lstmcheck) and kernel (csrc/rf_lstm.h)
  * alike; the scalar functions are csrc/rf_policy_math.h.  Everything is float32, one rounding per operation, nothing
@@ -1120,6 +1120,66 @@ unsigned long long rf_lstm_ppo_state_size(rf_ctx *ctx, const rf_lstm_policy_desc
 unsigned long long rf_lstm_ppo_workspace_size(rf_ctx *ctx, const rf_lstm_policy_desc *desc, int max_batch);
 int rf_lstm_ppo_update(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const rf_ppo_desc *ppo, float *d_params, void *d_state,
                        void *d_workspace, int n_steps, int num_envs, const float *d_observations, const long long *d_actions,
+                       const float *d_log_probs, const float *d_advantages, const float *d_returns,
+                       const uint8_t *d_episode_starts, const float *d_lstm_states, int first, int B, float *d_stats,
+                       void *caller_stream);
+
+/* ---- lstm sde policy: the Gaussian (gSDE) head on top of the recurrent actor-critic -----------------------------------------
+ * The reference's last training configuration (examples/ppo_lstm_untuned.yml, ContinuousJumps-v0: policy 'MlpLstmPolicy'
+ * with use_sde: True): sb3-contrib's RecurrentActorCriticPolicy(use_sde=True) for ONE action dimension, at the defaults
+ * "lstm policy" and "sde policy" already fix -- one nn.LSTM layer per net, enable_critic_lstm=True, shared_lstm=False,
+ * full_std=True, learn_features=False, use_expln=False, squash_output=False, epsilon = 1e-6.  The noise features are the
+ * activations of the last pi MLP layer, AFTER the LSTM, so log_std and theta have L = the last pi width entries.  No
+ * reference counterpart.  Written as deltas of the two sections it composes; numpy twin environments/lstm_sde.py, host
+ * build tests/lstmsdecheck, kernel lstm_forward_kernel<true> (csrc/rf_lstm.h).
+ *
+ *  Forward.  L1 to L8 of "lstm policy" (cell, episode starts, state, V(final_observation), values-only call), with a pi head
+ *     of one output (rf_policy_desc.n_actions must be 1) and, on h = the last pi activations, S4 (std2, var, sigma), S6
+ *     (mu, raw and clamped action), S7 (log_prob) and S8 of "sde policy".
+ *  Noise.  theta float32[n][L] is S5: draw e * L + k of `gen`, with log_std read from THIS policy's parameters.
+ *  Packing.  L8 for both nets with n_actions == 1, then log_std[L] last of everything: P + L floats.  Names: L8's, and
+ *     "log_std".
+ * Still out of scope: more than one action dimension, n_lstm_layers > 1, shared_lstm=True, enable_critic_lstm=False,
+ * learn_features=True, use_expln, squash_output.
+ *
+ *   rf_lstm_sde_params_size  floats of the packed parameters (P + L); 0 for a desc outside the limits or a NULL ctx
+ *   rf_lstm_sde_noise_reset  one launch (rf_sde_noise_reset's kernel): d_theta float32[n][L] from gen and the log_std
+ *                            inside d_params
+ *   rf_lstm_sde_forward      one launch.  Inputs as rf_lstm_forward's, with d_theta in place of gen (needed unless flags has
+ *                            RF_POLICY_DETERMINISTIC or no pi output is asked for); outputs as rf_sde_forward's, and
+ *                            d_state_out (each may be NULL, one must be given).  Refusals as the two siblings', all before
+ *                            anything is enqueued; an n_actions other than 1 is refused as well. */
+unsigned long long rf_lstm_sde_params_size(rf_ctx *ctx, const rf_lstm_policy_desc *desc);
+int rf_lstm_sde_noise_reset(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const float *d_params, int n,
+                            const unsigned long long gen[4], float *d_theta, void *caller_stream);
+int rf_lstm_sde_forward(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const float *d_params, int n, const float *d_obs,
+                        const uint8_t *d_episode_starts, const float *d_final_obs, const float *d_state_in,
+                        float *d_state_out, const float *d_theta, int flags, float *d_actions, float *d_env_actions,
+                        float *d_log_probs, float *d_values, float *d_final_values, float *d_mean, float *d_sigma,
+                        void *caller_stream);
+
+/* ---- lstm sde update: the recurrent PPO minibatch update with the Gaussian head ----------------------------------------------
+ * U1 to U9 of "lstm update" with these steps of "sde policy" in place of U3 and of the Categorical parts of U4 to U6
+ * (actions float32[N], the raw actions; numpy twin environments/lstm_learner.py, host build tests/lstmsdecheck, kernels
+ * lstm_ppo_mlp_kernel<true> and lstm_ppo_gradient_kernel<true> of csrc/rf_lstm_ppo.h; the other four launches are "lstm
+ * update"'s, unchanged):
+ *  1' Validity.  invalid = some actions[r_b] NaN.
+ *  3' Forward.  mu = the pi head on the last pi activations h of row b; sigma as S4; logp and H_b as S7.
+ *  5' Head gradients dmu_b, dsig_b as "sde policy".  A row whose sigma or logp is not finite has both NaN: the update ends
+ *     in RF_PPO_NONFINITE and parameters and optimizer state keep their bytes.
+ *  6' Backward.  The pi MLP, and through it dh_mlp and the pi LSTM (U6, U7), get their gradient through mu only (delta of
+ *     the head = dmu_b); h is a constant inside var.
+ *  7' dlog_std_k = sum over b = 0 .. B-1 in minibatch order, from +0, of ((h[b][k] * h[b][k]) * std2_k) * dsig_b: log_std
+ *     gets its gradient through sigma only.
+ * U8's packing and U9 run over the P + L floats of "lstm sde policy"; the optimizer state is 32 + 8 (P + L) bytes.
+ *
+ *   rf_lstm_sde_state_size, rf_lstm_sde_workspace_size, rf_lstm_sde_update
+ *                            as their rf_lstm_ppo_ siblings, over P + L parameters and float32 actions; six launches; the
+ *                            same refusals, and an n_actions other than 1. */
+unsigned long long rf_lstm_sde_state_size(rf_ctx *ctx, const rf_lstm_policy_desc *desc);
+unsigned long long rf_lstm_sde_workspace_size(rf_ctx *ctx, const rf_lstm_policy_desc *desc, int max_batch);
+int rf_lstm_sde_update(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const rf_ppo_desc *ppo, float *d_params, void *d_state,
+                       void *d_workspace, int n_steps, int num_envs, const float *d_observations, const float *d_actions,
                        const float *d_log_probs, const float *d_advantages, const float *d_returns,
                        const uint8_t *d_episode_starts, const float *d_lstm_states, int first, int B, float *d_stats,
                        void *caller_stream);

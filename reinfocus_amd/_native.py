@@ -113,6 +113,12 @@ SYMBOLS = (
     "rf_lstm_ppo_state_size",
     "rf_lstm_ppo_workspace_size",
     "rf_lstm_ppo_update",
+    "rf_lstm_sde_params_size",
+    "rf_lstm_sde_noise_reset",
+    "rf_lstm_sde_forward",
+    "rf_lstm_sde_state_size",
+    "rf_lstm_sde_workspace_size",
+    "rf_lstm_sde_update",
     "rf_render_kernel_name",
     "rf_pixels_rendered",
     "rf_allocations_poisoned",
@@ -385,6 +391,15 @@ def load():
     lib.rf_lstm_ppo_workspace_size.restype = ctypes.c_ulonglong
     lib.rf_lstm_ppo_workspace_size.argtypes = [vp, vp, i32]
     lib.rf_lstm_ppo_update.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp]
+    lib.rf_lstm_sde_params_size.restype = ctypes.c_ulonglong
+    lib.rf_lstm_sde_params_size.argtypes = [vp, vp]
+    lib.rf_lstm_sde_noise_reset.argtypes = [vp, vp, vp, i32, vp, vp, vp]
+    lib.rf_lstm_sde_forward.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.rf_lstm_sde_state_size.restype = ctypes.c_ulonglong
+    lib.rf_lstm_sde_state_size.argtypes = [vp, vp]
+    lib.rf_lstm_sde_workspace_size.restype = ctypes.c_ulonglong
+    lib.rf_lstm_sde_workspace_size.argtypes = [vp, vp, i32]
+    lib.rf_lstm_sde_update.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp]
     lib.rf_render_kernel_name.restype = ctypes.c_char_p
     lib.rf_render_kernel_name.argtypes = [vp]
     lib.rf_pixels_rendered.restype = ctypes.c_ulonglong
@@ -843,6 +858,50 @@ class Context:
         lstm_states slabs, all device arrays given by address; six launches on `stream`.  desc and hyper as lstm_forward's
         and ppo_update's.  Only enqueues."""
         rc = self._lib.rf_lstm_ppo_update(self._h, ctypes.byref(LstmPolicyDesc(*desc)), ctypes.byref(PpoDesc(*hyper)),
+                                          params_ptr, state_ptr, workspace_ptr, n_steps, num_envs, obs_ptr, actions_ptr,
+                                          log_probs_ptr, advantages_ptr, returns_ptr, episode_starts_ptr, lstm_states_ptr,
+                                          first, batch, stats_ptr, stream)
+        if rc != 0:
+            _check(rc)
+
+    # --- lstm sde policy and update (rf_lstm_sde_*): the Gaussian head on top of the recurrent actor-critic -------------
+    def lstm_sde_params_size(self, desc):
+        """rf_lstm_sde_params_size: floats of the packed parameters (log_std included); 0 for a desc outside the limits."""
+        return int(self._lib.rf_lstm_sde_params_size(self._h, ctypes.byref(LstmPolicyDesc(*desc))))
+
+    def lstm_sde_noise_reset(self, desc, params_ptr, num_envs, gen, theta_ptr, stream):
+        """rf_lstm_sde_noise_reset: theta float32 [num_envs][L] from the generator's four words and the log_std inside the
+        parameters; one launch on `stream`.  Only enqueues."""
+        rc = self._lib.rf_lstm_sde_noise_reset(self._h, ctypes.byref(LstmPolicyDesc(*desc)), params_ptr, num_envs,
+                                               (ctypes.c_ulonglong * 4)(*gen), theta_ptr, stream)
+        if rc != 0:
+            _check(rc)
+
+    def lstm_sde_forward(self, desc, params_ptr, num_envs, obs_ptr, episode_starts_ptr, final_obs_ptr, state_in_ptr,
+                         state_out_ptr, theta_ptr, flags, actions_ptr, env_actions_ptr, log_probs_ptr, values_ptr,
+                         final_values_ptr, mean_ptr, sigma_ptr, stream):
+        """rf_lstm_sde_forward: lstm_forward with the Gaussian head (theta_ptr in place of gen; final_obs_ptr, state_out_ptr,
+        theta_ptr and each output may be None), one launch on `stream`.  Only enqueues."""
+        rc = self._lib.rf_lstm_sde_forward(self._h, ctypes.byref(LstmPolicyDesc(*desc)), params_ptr, num_envs, obs_ptr,
+                                           episode_starts_ptr, final_obs_ptr, state_in_ptr, state_out_ptr, theta_ptr, flags,
+                                           actions_ptr, env_actions_ptr, log_probs_ptr, values_ptr, final_values_ptr,
+                                           mean_ptr, sigma_ptr, stream)
+        if rc != 0:
+            _check(rc)
+
+    def lstm_sde_state_size(self, desc):
+        """rf_lstm_sde_state_size: bytes of the optimizer state (header, m, v over P + L parameters); 0 if refused."""
+        return int(self._lib.rf_lstm_sde_state_size(self._h, ctypes.byref(LstmPolicyDesc(*desc))))
+
+    def lstm_sde_workspace_size(self, desc, max_batch):
+        """rf_lstm_sde_workspace_size: bytes of the workspace for minibatches of up to max_batch rows; 0 if refused."""
+        return int(self._lib.rf_lstm_sde_workspace_size(self._h, ctypes.byref(LstmPolicyDesc(*desc)), max_batch))
+
+    def lstm_sde_update(self, desc, hyper, params_ptr, state_ptr, workspace_ptr, n_steps, num_envs, obs_ptr, actions_ptr,
+                        log_probs_ptr, advantages_ptr, returns_ptr, episode_starts_ptr, lstm_states_ptr, first, batch,
+                        stats_ptr, stream):
+        """rf_lstm_sde_update: lstm_ppo_update with the Gaussian head (actions float32, the raw ones).  Only enqueues."""
+        rc = self._lib.rf_lstm_sde_update(self._h, ctypes.byref(LstmPolicyDesc(*desc)), ctypes.byref(PpoDesc(*hyper)),
                                           params_ptr, state_ptr, workspace_ptr, n_steps, num_envs, obs_ptr, actions_ptr,
                                           log_probs_ptr, advantages_ptr, returns_ptr, episode_starts_ptr, lstm_states_ptr,
                                           first, batch, stats_ptr, stream)

@@ -2349,10 +2349,125 @@ int rf_lstm_forward(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const float *d
     const bool pi = d_actions != nullptr || d_logits != nullptr || d_state_out != nullptr;
     const bool vf = d_values != nullptr || d_final_values != nullptr || d_state_out != nullptr;
     const unsigned tiles = (unsigned)((rows + rf::kPolicyTile - 1) / rf::kPolicyTile);
-    hipLaunchKernelGGL(rf::lstm_forward_kernel, dim3(tiles, pi && vf ? 2u : 1u), dim3(rf::kPolicyThreads), 0,
+    hipLaunchKernelGGL(rf::lstm_forward_kernel<false>, dim3(tiles, pi && vf ? 2u : 1u), dim3(rf::kPolicyThreads), 0,
                        (hipStream_t)caller_stream, layout, d_params, n, d_obs, d_episode_starts, d_final_obs, d_state_in,
                        d_state_out, words, sampled ? 1 : 0, pi ? 0 : 1, (int64_t *)d_actions, d_log_probs, d_values,
-                       d_final_values, d_logits);
+                       d_final_values, d_logits, rf::LstmNoSde{});
+    RF_HIP(hipGetLastError());
+    return RF_OK;
+}
+
+#define RF_LSTM_SDE_LIMITS "%s: the desc is outside the limits (obs_width and lstm_hidden 1 .. %d, 1 or 2 hidden layers of " \
+                           "width 1 .. %d per net, n_actions 1: the Gaussian head has one action, activation RF_POLICY_RELU " \
+                           "or RF_POLICY_TANH)"
+
+unsigned long long rf_lstm_sde_params_size(rf_ctx *ctx, const rf_lstm_policy_desc *desc)
+{
+    rf::LstmLayout layout;
+    if (ctx == nullptr || desc == nullptr || !rf::lstm_sde_layout(*desc, layout))
+        return 0;
+    if (hipSetDevice(ctx->device) != hipSuccess) // (as every entry point; nothing of the device is needed)
+        (void)hipGetLastError();
+    return layout.total;
+}
+
+int rf_lstm_sde_noise_reset(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const float *d_params, int n,
+                            const unsigned long long gen[4], float *d_theta, void *caller_stream)
+{
+    const char *fn = "rf_lstm_sde_noise_reset";
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", fn);
+    RF_REQUIRE(desc != nullptr && d_params != nullptr && gen != nullptr && d_theta != nullptr, "%s: NULL argument", fn);
+    rf::LstmLayout layout;
+    RF_REQUIRE(rf::lstm_sde_layout(*desc, layout), RF_LSTM_SDE_LIMITS, fn, RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_WIDTH);
+    RF_REQUIRE(n >= 1 && n <= (1 << 20), "%s: n = %d must be at least 1 (and at most 2^20)", fn, n);
+    RF_HIP(hipSetDevice(ctx->device));
+    const size_t cells = (size_t)n * (size_t)layout.mlp.sde;
+    if (int rc = check_device_array(ctx, d_params, (size_t)layout.total * 4, 4, "d_params", fn))
+        return rc;
+    if (int rc = check_device_array(ctx, d_theta, cells * 4, 4, "d_theta", fn))
+        return rc;
+    RF_REQUIRE(!ranges_overlap(d_theta, cells * 4, d_params, (size_t)layout.total * 4), "%s: d_theta overlaps d_params", fn);
+    rf::PolicyGen words{};
+    for (int i = 0; i < 4; ++i)
+        words.word[i] = gen[i];
+    // sde_noise_kernel as rf_sde_noise_reset launches it, with this layout's log_std
+    const unsigned blocks = (unsigned)((cells + rf::kPolicyThreads - 1) / rf::kPolicyThreads);
+    hipLaunchKernelGGL(rf::sde_noise_kernel, dim3(blocks), dim3(rf::kPolicyThreads), 0, (hipStream_t)caller_stream, words,
+                       d_params + layout.mlp.log_std, n, (int)layout.mlp.sde, d_theta);
+    RF_HIP(hipGetLastError());
+    return RF_OK;
+}
+
+int rf_lstm_sde_forward(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const float *d_params, int n, const float *d_obs,
+                        const uint8_t *d_episode_starts, const float *d_final_obs, const float *d_state_in,
+                        float *d_state_out, const float *d_theta, int flags, float *d_actions, float *d_env_actions,
+                        float *d_log_probs, float *d_values, float *d_final_values, float *d_mean, float *d_sigma,
+                        void *caller_stream)
+{
+    const char *fn = "rf_lstm_sde_forward";
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", fn);
+    RF_REQUIRE(desc != nullptr && d_params != nullptr && d_obs != nullptr && d_episode_starts != nullptr &&
+               d_state_in != nullptr, "%s: NULL argument", fn);
+    rf::LstmLayout layout;
+    RF_REQUIRE(rf::lstm_sde_layout(*desc, layout), RF_LSTM_SDE_LIMITS, fn, RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_WIDTH);
+    RF_REQUIRE(n >= 1 && n <= (1 << 20), "%s: n = %d must be at least 1 (and at most 2^20)", fn, n);
+    RF_REQUIRE((flags & ~RF_POLICY_DETERMINISTIC) == 0, "%s: unknown flags %d", fn, flags);
+    const bool pi_out = d_actions || d_env_actions || d_log_probs || d_mean || d_sigma;
+    RF_REQUIRE(pi_out || d_values || d_final_values || d_state_out, "%s: no output is asked for", fn);
+    RF_REQUIRE(d_final_values == nullptr || d_final_obs != nullptr, "%s: d_final_values needs d_final_obs", fn);
+    const bool sampled = pi_out && (flags & RF_POLICY_DETERMINISTIC) == 0;
+    RF_REQUIRE(!sampled || d_theta != nullptr, "%s: a sampled call needs d_theta (rf_lstm_sde_noise_reset)", fn);
+    RF_HIP(hipSetDevice(ctx->device));
+    const size_t rows = (size_t)n;
+    const size_t state_bytes = rf::lstm_state_floats(n, layout.hidden) * 4;
+    struct Array {
+        const void *p;
+        size_t bytes, align;
+        const char *what;
+    };
+    const Array inputs[] = {{d_params, (size_t)layout.total * 4, 4, "d_params"},
+                            {d_obs, rows * (size_t)layout.obs_width * 4, 4, "d_obs"},
+                            {d_episode_starts, rows, 1, "d_episode_starts"},
+                            {d_final_obs, rows * (size_t)layout.obs_width * 4, 4, "d_final_obs"},
+                            {sampled ? d_theta : nullptr, rows * (size_t)layout.mlp.sde * 4, 4, "d_theta"},
+                            {d_state_in, state_bytes, 4, "d_state_in"}};
+    const Array outputs[] = {{d_actions, rows * 4, 4, "d_actions"},       {d_env_actions, rows * 4, 4, "d_env_actions"},
+                             {d_log_probs, rows * 4, 4, "d_log_probs"},   {d_values, rows * 4, 4, "d_values"},
+                             {d_final_values, rows * 4, 4, "d_final_values"}, {d_mean, rows * 4, 4, "d_mean"},
+                             {d_sigma, rows * 4, 4, "d_sigma"},           {d_state_out, state_bytes, 4, "d_state_out"}};
+    for (const Array &a : inputs) {
+        if (a.p == nullptr)
+            continue;
+        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
+            return rc;
+    }
+    for (const Array &a : outputs) {
+        if (a.p == nullptr)
+            continue;
+        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
+            return rc;
+        for (const Array &b : inputs) {
+            if (&a == &outputs[7] && &b == &inputs[5]) { // d_state_out against d_state_in: in place, or apart
+                RF_REQUIRE(a.p == b.p || !ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: d_state_out overlaps d_state_in "
+                           "without being it (the same pointer updates the state in place; any other overlap would have a "
+                           "block overwrite rows another still reads)", fn);
+                continue;
+            }
+            RF_REQUIRE(b.p == nullptr || !ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s (an output must "
+                       "not alias an input: other blocks still read it)", fn, a.what, b.what);
+        }
+        for (const Array &b : outputs)
+            RF_REQUIRE(&b >= &a || b.p == nullptr || !ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s", fn,
+                       a.what, b.what);
+    }
+    // As rf_lstm_forward: one launch on the caller's stream; with d_state_out both cells run, whatever is asked of the heads
+    const bool pi = pi_out || d_state_out != nullptr;
+    const bool vf = d_values != nullptr || d_final_values != nullptr || d_state_out != nullptr;
+    const unsigned tiles = (unsigned)((rows + rf::kPolicyTile - 1) / rf::kPolicyTile);
+    hipLaunchKernelGGL(rf::lstm_forward_kernel<true>, dim3(tiles, pi && vf ? 2u : 1u), dim3(rf::kPolicyThreads), 0,
+                       (hipStream_t)caller_stream, layout, d_params, n, d_obs, d_episode_starts, d_final_obs, d_state_in,
+                       d_state_out, rf::PolicyGen{}, 0, pi ? 0 : 1, d_actions, d_log_probs, d_values, d_final_values, d_mean,
+                       rf::LstmSde{sampled ? d_theta : nullptr, d_env_actions, d_sigma});
     RF_HIP(hipGetLastError());
     return RF_OK;
 }
@@ -2381,20 +2496,23 @@ unsigned long long rf_lstm_ppo_workspace_size(rf_ctx *ctx, const rf_lstm_policy_
     return 4ull * work.total;
 }
 
-int rf_lstm_ppo_update(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const rf_ppo_desc *ppo, float *d_params, void *d_state,
-                       void *d_workspace, int n_steps, int num_envs, const float *d_observations, const long long *d_actions,
-                       const float *d_log_probs, const float *d_advantages, const float *d_returns,
-                       const uint8_t *d_episode_starts, const float *d_lstm_states, int first, int B, float *d_stats,
-                       void *caller_stream)
+// rf_lstm_ppo_update and rf_lstm_sde_update: one body; `sde` selects lstm_sde_layout, float32 actions and the Gaussian
+// instantiations of the MLP and gradient kernels
+static int lstm_update_any(const char *fn, bool sde, rf_ctx *ctx, const rf_lstm_policy_desc *desc, const rf_ppo_desc *ppo,
+                           float *d_params, void *d_state, void *d_workspace, int n_steps, int num_envs,
+                           const float *d_observations, const void *d_actions, const float *d_log_probs,
+                           const float *d_advantages, const float *d_returns, const uint8_t *d_episode_starts,
+                           const float *d_lstm_states, int first, int B, float *d_stats, void *caller_stream)
 {
-    const char *fn = "rf_lstm_ppo_update";
-    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", fn);
-    RF_HIP(hipSetDevice(ctx->device));
     RF_REQUIRE(desc && ppo && d_params && d_state && d_workspace && d_observations && d_actions && d_log_probs &&
                d_advantages && d_returns && d_episode_starts && d_lstm_states && d_stats, "%s: NULL argument", fn);
     rf::LstmLayout layout;
-    RF_REQUIRE(rf::lstm_layout(*desc, layout), RF_LSTM_LIMITS, fn, RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_WIDTH,
-               RF_POLICY_MAX_ACTIONS);
+    if (sde) {
+        RF_REQUIRE(rf::lstm_sde_layout(*desc, layout), RF_LSTM_SDE_LIMITS, fn, RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_WIDTH);
+    } else {
+        RF_REQUIRE(rf::lstm_layout(*desc, layout), RF_LSTM_LIMITS, fn, RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_WIDTH,
+                   RF_POLICY_MAX_ACTIONS);
+    }
     RF_REQUIRE(n_steps >= 1 && num_envs >= 1 && (long long)n_steps * (long long)num_envs <= (1ll << 30),
                "%s: n_steps = %d and num_envs = %d must be at least 1 (and their product at most 2^30)", fn, n_steps, num_envs);
     const int N = n_steps * num_envs;
@@ -2414,7 +2532,7 @@ int rf_lstm_ppo_update(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const rf_pp
         const char *what;
     };
     const Array inputs[] = {{d_observations, rows * (size_t)layout.obs_width * 4, 4, "d_observations"},
-                            {d_actions, rows * 8, 8, "d_actions"},
+                            {d_actions, rows * (sde ? 4 : 8), sde ? (size_t)4 : (size_t)8, "d_actions"},
                             {d_log_probs, rows * 4, 4, "d_log_probs"},
                             {d_advantages, rows * 4, 4, "d_advantages"},
                             {d_returns, rows * 4, 4, "d_returns"},
@@ -2448,14 +2566,15 @@ int rf_lstm_ppo_update(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const rf_pp
                        B);
     RF_HIP(hipGetLastError());
     const unsigned tiles = (unsigned)((B + rf::kPolicyTile - 1) / rf::kPolicyTile);
-    hipLaunchKernelGGL(rf::lstm_ppo_mlp_kernel, dim3(tiles, 2u), threads, 0, caller, layout, work, hyper,
-                       (const float *)d_params, (const rf::PpoHeader *)d_state, ws, N, (const int64_t *)d_actions,
+    hipLaunchKernelGGL(sde ? rf::lstm_ppo_mlp_kernel<true> : rf::lstm_ppo_mlp_kernel<false>, dim3(tiles, 2u), threads, 0,
+                       caller, layout, work, hyper, (const float *)d_params, (const rf::PpoHeader *)d_state, ws, N, d_actions,
                        d_log_probs, d_advantages, d_returns, first, B);
     RF_HIP(hipGetLastError());
     hipLaunchKernelGGL(rf::lstm_ppo_bptt_kernel, dim3((unsigned)B, 2u), threads, 0, caller, layout, work,
                        (const float *)d_params, ws, n_steps, num_envs, d_episode_starts, first, B);
     RF_HIP(hipGetLastError());
-    hipLaunchKernelGGL(rf::lstm_ppo_gradient_kernel, dim3(work.mlp.partials), threads, 0, caller, layout, work, ws, B);
+    hipLaunchKernelGGL(sde ? rf::lstm_ppo_gradient_kernel<true> : rf::lstm_ppo_gradient_kernel<false>,
+                       dim3(work.mlp.partials), threads, 0, caller, layout, work, ws, B, (const float *)d_params);
     RF_HIP(hipGetLastError());
     hipLaunchKernelGGL(rf::lstm_ppo_norm_kernel, dim3(work.supers), dim3(rf::kLstmPpoGroup), 0, caller, work, ws);
     RF_HIP(hipGetLastError());
@@ -2464,6 +2583,54 @@ int rf_lstm_ppo_update(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const rf_pp
                        rf::lstm_ppo_adam_work(work), hyper, d_params, (float *)d_state, (const float *)ws, B, d_stats);
     RF_HIP(hipGetLastError());
     return RF_OK;
+}
+
+int rf_lstm_ppo_update(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const rf_ppo_desc *ppo, float *d_params, void *d_state,
+                       void *d_workspace, int n_steps, int num_envs, const float *d_observations, const long long *d_actions,
+                       const float *d_log_probs, const float *d_advantages, const float *d_returns,
+                       const uint8_t *d_episode_starts, const float *d_lstm_states, int first, int B, float *d_stats,
+                       void *caller_stream)
+{
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", "rf_lstm_ppo_update");
+    RF_HIP(hipSetDevice(ctx->device));
+    return lstm_update_any("rf_lstm_ppo_update", false, ctx, desc, ppo, d_params, d_state, d_workspace, n_steps, num_envs,
+                           d_observations, d_actions, d_log_probs, d_advantages, d_returns, d_episode_starts, d_lstm_states,
+                           first, B, d_stats, caller_stream);
+}
+
+unsigned long long rf_lstm_sde_state_size(rf_ctx *ctx, const rf_lstm_policy_desc *desc)
+{
+    rf::LstmLayout layout;
+    if (ctx == nullptr || desc == nullptr || !rf::lstm_sde_layout(*desc, layout))
+        return 0;
+    if (hipSetDevice(ctx->device) != hipSuccess) // (as every entry point; nothing of the device is needed)
+        (void)hipGetLastError();
+    return 4ull * rf::kPpoStateHeader + 8ull * layout.total;
+}
+
+unsigned long long rf_lstm_sde_workspace_size(rf_ctx *ctx, const rf_lstm_policy_desc *desc, int max_batch)
+{
+    rf::LstmLayout layout;
+    rf::LstmPpoWork work;
+    if (ctx == nullptr || desc == nullptr || !rf::lstm_sde_layout(*desc, layout) ||
+        !rf::lstm_ppo_work(layout, max_batch, work))
+        return 0;
+    if (hipSetDevice(ctx->device) != hipSuccess)
+        (void)hipGetLastError();
+    return 4ull * work.total;
+}
+
+int rf_lstm_sde_update(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const rf_ppo_desc *ppo, float *d_params, void *d_state,
+                       void *d_workspace, int n_steps, int num_envs, const float *d_observations, const float *d_actions,
+                       const float *d_log_probs, const float *d_advantages, const float *d_returns,
+                       const uint8_t *d_episode_starts, const float *d_lstm_states, int first, int B, float *d_stats,
+                       void *caller_stream)
+{
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", "rf_lstm_sde_update");
+    RF_HIP(hipSetDevice(ctx->device));
+    return lstm_update_any("rf_lstm_sde_update", true, ctx, desc, ppo, d_params, d_state, d_workspace, n_steps, num_envs,
+                           d_observations, d_actions, d_log_probs, d_advantages, d_returns, d_episode_starts, d_lstm_states,
+                           first, B, d_stats, caller_stream);
 }
 
 } // extern "C"

@@ -15,6 +15,8 @@
 // LstmLayout and lstm_layout are plain C++: tests/lstmcheck packs its host loop by the same offsets.
 #pragma once
 
+#include <type_traits>
+
 #include "rf_policy.h"
 
 namespace rf {
@@ -28,8 +30,8 @@ struct LstmLayout {
     unsigned total;
 };
 
-// false: desc is outside the limits of the definition
-RF_HD bool lstm_layout(const rf_lstm_policy_desc &d, LstmLayout &p)
+// The packing of both heads: `sde` packs the MLPs by sde_layout (a pi head of one output, log_std last of everything)
+RF_HD bool lstm_layout_nets(const rf_lstm_policy_desc &d, LstmLayout &p, bool sde)
 {
     p = LstmLayout{};
     const int D = d.policy.obs_width, H = d.lstm_hidden;
@@ -37,7 +39,7 @@ RF_HD bool lstm_layout(const rf_lstm_policy_desc &d, LstmLayout &p)
         return false;
     rf_policy_desc mlp = d.policy;
     mlp.obs_width = H;
-    if (!policy_layout(mlp, p.mlp))
+    if (!(sde ? sde_layout(mlp, p.mlp) : policy_layout(mlp, p.mlp)))
         return false;
     p.obs_width = D;
     p.hidden = H;
@@ -57,7 +59,22 @@ RF_HD bool lstm_layout(const rf_lstm_policy_desc &d, LstmLayout &p)
     }
     p.total = p.mlp.total + 2u * cell;
     p.mlp.total = p.total;
+    if (sde)
+        p.mlp.log_std += 2u * cell; // (past both nets of the whole array)
     return true;
+}
+
+// false: desc is outside the limits of the definition
+RF_HD bool lstm_layout(const rf_lstm_policy_desc &d, LstmLayout &p)
+{
+    return lstm_layout_nets(d, p, false);
+}
+
+// "lstm sde policy": lstm_layout over sde_layout -- n_actions must be 1, mlp.sde = L = the last pi width, and
+// mlp.log_std [L] sits after both nets, so the packed array has P + L floats
+RF_HD bool lstm_sde_layout(const rf_lstm_policy_desc &d, LstmLayout &p)
+{
+    return lstm_layout_nets(d, p, true);
 }
 
 // floats of the state [2 nets][2: h, c][n][H]
@@ -113,13 +130,37 @@ __device__ __forceinline__ void lstm_gates_tile(const float *__restrict__ params
     }
 }
 
+// What only the Gaussian head of lstm_forward_kernel<true> is given: theta float32 [n][L] (null: deterministic) in place of
+// gen and sampled, and two more outputs.  The Categorical instantiation takes the empty LstmNoSde in its place, so its
+// arguments are what they were.
+struct LstmSde {
+    const float *theta;
+    float *env_actions, *sigma;
+};
+struct LstmNoSde {
+    static constexpr const float *theta = nullptr;
+    static constexpr float *env_actions = nullptr, *sigma = nullptr;
+};
+template <bool kSde> struct LstmSdeOf {
+    using type = LstmNoSde;
+};
+template <> struct LstmSdeOf<true> {
+    using type = LstmSde;
+};
+
+// kSde: the Gaussian head of "lstm sde policy" (L from lstm_sde_layout) in place of the Categorical one.  actions_any is
+// then float32 [n] (the raw actions) and `logits` receives the mean.
+template <bool kSde>
 __global__ __launch_bounds__(kPolicyThreads) void lstm_forward_kernel(
     LstmLayout L, const float *__restrict__ params, int n, const float *__restrict__ obs,
     const uint8_t *__restrict__ starts, const float *__restrict__ final_obs /* or null */, const float *state_in,
     float *state_out /* null, state_in itself, or a range that does not overlap it */, PolicyGen gen, int sampled,
-    int first_net, int64_t *__restrict__ actions, float *__restrict__ log_probs, float *__restrict__ values,
-    float *__restrict__ final_values, float *__restrict__ logits)
+    int first_net, typename std::conditional<kSde, float, int64_t>::type *__restrict__ actions,
+    float *__restrict__ log_probs, float *__restrict__ values, float *__restrict__ final_values,
+    float *__restrict__ logits, typename LstmSdeOf<kSde>::type sde)
 {
+    const float *__restrict__ theta = sde.theta;
+    float *__restrict__ env_actions = sde.env_actions, *__restrict__ sigma = sde.sigma;
     __shared__ __align__(16) float s_x[kPolicyMaxWidth][kPolicyTile];      // the tile's observations, [k][environment]
     __shared__ __align__(16) float s_act[2][kPolicyMaxWidth][kPolicyTile]; // [1]: h; [0]: h', then the MLP's activations
     __shared__ float s_logit[kPolicyTile][kPolicyMaxActions];
@@ -132,7 +173,9 @@ __global__ __launch_bounds__(kPolicyThreads) void lstm_forward_kernel(
         const int pass = 1 - turn;         // 1: final_obs from state_in as it is; 0: obs, masked by starts, stores the state
         if (pass == 1 && (net == 0 || final_values == nullptr))
             continue;
-        const bool heads = pass == 1 || (net == 0 ? actions != nullptr || logits != nullptr : values != nullptr);
+        bool heads = pass == 1 || (net == 0 ? actions != nullptr || logits != nullptr : values != nullptr);
+        if constexpr (kSde) // (each pi output of the Gaussian head may be asked for by itself)
+            heads = heads || (net == 0 && (env_actions != nullptr || log_probs != nullptr || sigma != nullptr));
         if (!heads && state_out == nullptr)
             continue;
         const float *__restrict__ in = pass == 0 ? obs : final_obs;
@@ -206,16 +249,40 @@ __global__ __launch_bounds__(kPolicyThreads) void lstm_forward_kernel(
                 }
             }
         }
-        __syncthreads();
-        if (net == 0 && actions != nullptr && tid < kPolicyTile && e0 + tid < n) {
-            const int env = e0 + tid;
-            const double u = sampled ? policy_draw(gen.word, (uint64_t)env) : 0.0;
-            int64_t action;
-            float log_prob;
-            policy_head(&s_logit[tid][0], L.mlp.n_actions, !sampled, u, &s_sum[tid][0], &action, &log_prob);
-            actions[env] = action;
-            if (log_probs != nullptr)
-                log_probs[env] = log_prob;
+        if constexpr (kSde) {
+            float *std2 = &s_sum[0][0]; // (the K <= 256 squared standard deviations: s_sum is otherwise unused here)
+            if (net == 0 && tid < K)
+                std2[tid] = sde_std2(params[L.mlp.log_std + tid]);
+            __syncthreads();
+            if (net == 0 && tid < kPolicyTile && e0 + tid < n) { // one lane per environment: sde_forward_kernel's head
+                const int env = e0 + tid;
+                const float *h = &s_act[cur][0][tid];
+                const float mu = s_logit[tid][0];
+                const float s = sde_sigma(h, kPolicyTile, std2, K);
+                float a = mu;
+                if (theta != nullptr)
+                    a = mu + policy_dot(h, kPolicyTile, theta + (size_t)env * (size_t)K, 1, 0.0f, K);
+                if (actions != nullptr)
+                    actions[env] = policy_canonical(a);
+                if (env_actions != nullptr)
+                    env_actions[env] = sde_env_action(a);
+                if (log_probs != nullptr)
+                    log_probs[env] = sde_log_prob(a, mu, s);
+                if (sigma != nullptr)
+                    sigma[env] = policy_canonical(s);
+            }
+        } else {
+            __syncthreads();
+            if (net == 0 && actions != nullptr && tid < kPolicyTile && e0 + tid < n) {
+                const int env = e0 + tid;
+                const double u = sampled ? policy_draw(gen.word, (uint64_t)env) : 0.0;
+                int64_t action;
+                float log_prob;
+                policy_head(&s_logit[tid][0], L.mlp.n_actions, !sampled, u, &s_sum[tid][0], &action, &log_prob);
+                actions[env] = action;
+                if (log_probs != nullptr)
+                    log_probs[env] = log_prob;
+            }
         }
         __syncthreads(); // (the next pass overwrites what the heads have read)
     }

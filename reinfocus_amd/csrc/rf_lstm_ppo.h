@@ -99,6 +99,8 @@ RF_HD bool lstm_ppo_work(const LstmLayout &L, int max_batch, LstmPpoWork &w)
         w.dh[net] = take(rows * H);
         w.da[net] = take(rows * 4u * H);
     }
+    if (M.sde != 0) // (lstm_sde_layout only; taken last, so every other offset is the Categorical layout's)
+        w.mlp.sde = take(rows);
     w.total = at;
     w.mlp.total = at;
     return true;
@@ -198,8 +200,8 @@ RF_HD float lstm_bptt_rec(const float *w, const float *da, int H)
     return (acc[0] + acc[1]) + (acc[2] + acc[3]);
 }
 
-// ppo_source over the recurrent nets: where packed parameter p < L.total gets its gradient from
-RF_HD PpoSource lstm_ppo_source(const LstmLayout &L, const LstmPpoWork &W, unsigned p)
+// ppo_source over the two recurrent nets: where packed parameter p of the cells, MLPs and heads gets its gradient from
+RF_HD PpoSource lstm_ppo_source_nets(const LstmLayout &L, const LstmPpoWork &W, unsigned p)
 {
     PpoSource s{};
     const PolicyLayout &M = L.mlp;
@@ -235,7 +237,29 @@ RF_HD PpoSource lstm_ppo_source(const LstmLayout &L, const LstmPpoWork &W, unsig
             return s;
         }
     }
-    return s; // (p >= L.total: no caller asks)
+    return s; // (p past both nets: no caller asks)
+}
+
+// ... and over everything packed, p < L.total: past both nets (lstm_sde_layout only) log_std_j of the Gaussian head gets
+// it from the last pi activations and the per-row sigma terms (k == -2, as ppo_source)
+RF_HD PpoSource lstm_ppo_source(const LstmLayout &L, const LstmPpoWork &W, unsigned p)
+{
+    const PolicyLayout &M = L.mlp;
+    if (M.sde == 0 || p < M.log_std)
+        return lstm_ppo_source_nets(L, W, p);
+    PpoSource s{};
+    s.k = -2, s.j = (int)(p - M.log_std);
+    s.x = W.mlp.h[0][M.layers[0] - 1], s.x_stride = (int)M.sde;
+    s.d = W.mlp.sde, s.d_stride = 1;
+    return s;
+}
+
+// Definition step U8 for one packed parameter (params: for std2_j of a log_std entry)
+RF_HD float lstm_ppo_parameter_gradient(const LstmLayout &L, const LstmPpoWork &W, const float *ws, const float *params,
+                                        unsigned p, int B)
+{
+    const PpoSource s = lstm_ppo_source(L, W, p);
+    return s.k == -2 ? sde_log_std_gradient(ws, s, B, sde_std2(params[L.mlp.log_std + (unsigned)s.j])) : ppo_gradient(ws, s, B);
 }
 
 #if defined(__HIPCC__)
@@ -361,11 +385,16 @@ __device__ __forceinline__ void lstm_ppo_back_input_tile(const float *__restrict
     }
 }
 
+// kSde: the Gaussian head of "lstm sde update" (L from lstm_sde_layout; actions float32 [N], the raw ones) in place of the
+// Categorical one (actions int64 [N]), as ppo_backward_kernel<kSde>
+template <bool kSde>
 __global__ __launch_bounds__(kPpoThreads) void lstm_ppo_mlp_kernel(
     LstmLayout L, LstmPpoWork W, PpoHyper hy, const float *__restrict__ params, const PpoHeader *__restrict__ header,
-    float *__restrict__ ws, int N, const int64_t *__restrict__ actions, const float *__restrict__ old_log_probs,
+    float *__restrict__ ws, int N, const void *__restrict__ actions_any, const float *__restrict__ old_log_probs,
     const float *__restrict__ advantages, const float *__restrict__ returns, int first, int B)
 {
+    const int64_t *__restrict__ actions = static_cast<const int64_t *>(actions_any); // (!kSde)
+    const float *__restrict__ raw_actions = static_cast<const float *>(actions_any); // (kSde)
     __shared__ __align__(16) float s_act[2][kPolicyMaxWidth][kPolicyTile];   // h' / activations, [k][sample]
     __shared__ __align__(16) float s_delta[2][kPolicyMaxWidth][kPolicyTile]; // deltas of the hidden layers
     __shared__ __align__(16) float s_head[kPolicyMaxActions][kPolicyTile];   // deltas of the head, [o][sample]
@@ -386,8 +415,13 @@ __global__ __launch_bounds__(kPpoThreads) void lstm_ppo_mlp_kernel(
             double a = 0.0;
             if (b < B) {
                 const int row = lstm_ppo_row(first, b, N);
-                const int64_t action = actions[row];
-                bad |= action < 0 || action >= M.n_actions;
+                if (kSde) {
+                    const float action = raw_actions[row];
+                    bad |= action != action;
+                } else {
+                    const int64_t action = actions[row];
+                    bad |= action < 0 || action >= M.n_actions;
+                }
                 a = (double)advantages[row];
             }
             s_red[b] = a;
@@ -433,6 +467,9 @@ __global__ __launch_bounds__(kPpoThreads) void lstm_ppo_mlp_kernel(
         s_logit[e][o] = policy_dot(&s_act[cur][0][e], kPolicyTile, params + M.weight[net][layers] + o, O,
                                    params[M.bias[net][layers] + o], K);
     }
+    float *std2 = &s_work[0][0]; // (kSde: the K <= 256 squared standard deviations; s_work is otherwise unused then)
+    if (kSde && net == 0 && tid < K)
+        std2[tid] = sde_std2(params[M.log_std + tid]);
     __syncthreads();
     if (tid < kPolicyTile) { // one lane per sample: the loss terms and the head deltas
         const int b = b0 + tid;
@@ -443,8 +480,17 @@ __global__ __launch_bounds__(kPpoThreads) void lstm_ppo_mlp_kernel(
                 const float adv = advantages[row];
                 const float A = normalise ? ppo_normalised(adv, mean, var) : adv;
                 float pg, Hb, kl, clipped;
-                ppo_pi_sample(&s_logit[tid][0], M.n_actions, (int)ppo_clamp(actions[row], M.n_actions), old_log_probs[row], A,
-                              hy.clip, hy.ent, Bf, &s_work[tid][0], &s_head[0][tid], kPolicyTile, &pg, &Hb, &kl, &clipped);
+                if (kSde) {
+                    const float sigma = sde_sigma(&s_act[cur][0][tid], kPolicyTile, std2, K);
+                    float dmu, dsig;
+                    sde_pi_sample(s_logit[tid][0], sigma, raw_actions[row], old_log_probs[row], A, hy.clip, hy.ent, Bf, &dmu,
+                                  &dsig, &pg, &Hb, &kl, &clipped);
+                    s_head[0][tid] = dmu;
+                    ws[W.mlp.sde + b] = dsig;
+                } else
+                    ppo_pi_sample(&s_logit[tid][0], M.n_actions, (int)ppo_clamp(actions[row], M.n_actions),
+                                  old_log_probs[row], A, hy.clip, hy.ent, Bf, &s_work[tid][0], &s_head[0][tid], kPolicyTile,
+                                  &pg, &Hb, &kl, &clipped);
                 float *loss = ws + W.mlp.loss + b;
                 loss[0] = pg, loss[2 * W.mlp.max_batch] = Hb, loss[3 * W.mlp.max_batch] = kl;
                 loss[4 * W.mlp.max_batch] = clipped;
@@ -517,15 +563,18 @@ __global__ __launch_bounds__(kPpoThreads) void lstm_ppo_bptt_kernel(LstmLayout L
     }
 }
 
+// kSde: the threads past both nets sum the log_std gradients (sde_log_std_gradient, which needs params for std2_j)
+template <bool kSde>
 __global__ __launch_bounds__(kPpoThreads) void lstm_ppo_gradient_kernel(LstmLayout L, LstmPpoWork W, float *__restrict__ ws,
-                                                                        int B)
+                                                                        int B, const float *__restrict__ params)
 {
     __shared__ double s_red[kPpoLeaves];
     const int tid = threadIdx.x;
     const unsigned p = blockIdx.x * (unsigned)kPpoLeaves + (unsigned)tid;
     double square = 0.0;
     if (p < L.total) {
-        const float g = policy_canonical(ppo_gradient(ws, lstm_ppo_source(L, W, p), B));
+        const float g = policy_canonical(kSde ? lstm_ppo_parameter_gradient(L, W, ws, params, p, B)
+                                              : ppo_gradient(ws, lstm_ppo_source_nets(L, W, p), B));
         ws[W.mlp.grad + p] = g;
         square = (double)g * (double)g;
     }

@@ -1844,3 +1844,4 @@ from reinfocus_amd.environments.learner import DeviceLearner, Learner, ppo_updat
 from reinfocus_amd.environments.sde import DeviceSdePolicy, SdePolicy, SdePolicySpec, sde_numpy  # noqa: E402,F401 -- the gSDE actor-critic
 from reinfocus_amd.environments.lstm import DeviceLstmPolicy, LstmPolicy, LstmPolicySpec, lstm_numpy  # noqa: E402,F401 -- the recurrent actor-critic
 from reinfocus_amd.environments.lstm_learner import DeviceLstmLearner, LstmLearner, lstm_gradient_numpy, lstm_update_numpy  # noqa: E402,F401 -- the recurrent PPO minibatch update
+from reinfocus_amd.environments.lstm_sde import DeviceLstmSdePolicy, LstmSdePolicy, LstmSdePolicySpec, lstm_sde_numpy  # noqa: E402,F401 -- its Gaussian (gSDE) head

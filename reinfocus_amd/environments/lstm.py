@@ -14,8 +14,9 @@ multiplies the state by (1 - start).
     LstmPolicy       the numpy twin: act / values over numpy arrays, the state float32 [2 nets][2: h, c][n][H]
     DeviceLstmPolicy the same over torch tensors on a device-resident environment's GPU: one launch per call
 
-The update (back-propagation through time) is environments/lstm_learner.py.  Out of scope, and refused or absent: the
-Gaussian (sde) head on top of the LSTM (Box action spaces), n_lstm_layers > 1, shared_lstm=True, enable_critic_lstm=False.
+The update (back-propagation through time) is environments/lstm_learner.py; the Gaussian (sde) head on top of the LSTM
+(Box action spaces) is environments/lstm_sde.py.  Out of scope, and refused or absent: n_lstm_layers > 1,
+shared_lstm=True, enable_critic_lstm=False.
 
 torch is imported lazily, by DeviceLstmPolicy only (reinfocus_amd/torch_interop.py says why import order matters).
 """
@@ -117,7 +118,7 @@ def _refuse_box(action_space):
     if not isinstance(action_space, spaces.Discrete):
         raise ValueError(f"the lstm policy has a Categorical head over a Discrete action space, not {action_space!r}: the "
                          "Gaussian (sde) head on top of the LSTM (ppo_lstm_untuned.yml's ContinuousJumps entry) is out of "
-                         "scope")
+                         "scope for this class: LstmSdePolicy / DeviceLstmSdePolicy (environments/lstm_sde.py) have it")
 
 
 def _mlp(spec, layers, last, x):

@@ -18,7 +18,11 @@ launches and updates the parameters in place.
 sb3-contrib never permutes the rows of a recurrent rollout: per epoch it rotates flat()'s order by one split index and
 cuts it into consecutive minibatches.  A minibatch is therefore (first, count): rows (first + b) mod N, b < count.
 
-Limits: the Categorical head, one LSTM layer per net of 1 .. 256 units, minibatches of 1 .. min(N, 1024) rows.
+The head is the policy's: Categorical for an lstm.LstmPolicy (int64 actions), or -- for an lstm_sde.LstmSdePolicy, whose
+spec has kind "lstm_sde" -- the Gaussian head of environments/sde.py over float32 raw actions and P + L parameters
+("lstm sde update": rf_lstm_sde_update).
+
+Limits: one LSTM layer per net of 1 .. 256 units, minibatches of 1 .. min(N, 1024) rows.
 
 torch is imported lazily, by DeviceLstmLearner only (reinfocus_amd/torch_interop.py says why import order matters).
 """
@@ -178,9 +182,17 @@ def lstm_gradient_numpy(spec, params, batch, episode_starts, lstm_states, n_step
     lstm_states = np.asarray(lstm_states, dtype=f32).reshape(n_steps + 1, 2, 2, num_envs, hidden)
     rows = sequence_rows(episode_starts, n_steps, num_envs, first, count)
     index = np.array([row[0] for row in rows], dtype=np.int64)
-    raw_actions = np.asarray(batch["actions"], dtype=np.int64).reshape(total)[index]
-    a = np.clip(raw_actions, 0, spec.n_actions - 1)
-    invalid = bool((a != raw_actions).any())
+    gaussian = spec.kind == "lstm_sde"
+    if gaussian:
+        if np.asarray(batch["actions"]).dtype.kind in "iub":  # (as DeviceLstmLearner refuses it: no silent cast of indices)
+            raise ValueError("the update has a Gaussian head over float32 raw actions, not an int64 action slab: Discrete "
+                             "action spaces have LstmPolicy")
+        a = np.asarray(batch["actions"], dtype=f32).reshape(total)[index]
+        invalid = bool((a != a).any())
+    else:
+        raw_actions = np.asarray(batch["actions"], dtype=np.int64).reshape(total)[index]
+        a = np.clip(raw_actions, 0, spec.n_actions - 1)
+        invalid = bool((a != raw_actions).any())
     adv = np.asarray(batch["advantages"], dtype=f32).reshape(total)[index]
     old = np.asarray(batch["log_probs"], dtype=f32).reshape(total)[index]
     ret = np.asarray(batch["returns"], dtype=f32).reshape(total)[index]
@@ -197,28 +209,49 @@ def lstm_gradient_numpy(spec, params, batch, episode_starts, lstm_states, n_step
                 acts.append(activation(linear(acts[-1], weight_t, bias), spec.activation))
             mlps.append(acts)
             heads.append(linear(acts[-1], *last))
-        logits, v = heads[0], heads[1][:, 0]
-        _, z, _, s, degenerate = softmax_parts(logits)
-        e = exp32(z)
-        lse = np.where(degenerate, _NAN, log32(np.where(degenerate, f32(1.0), s)))
-        logp = z - lse[:, None]
-        p = e / s[:, None]
-        acc = np.zeros(count, dtype=f32)
-        for i in range(spec.n_actions):
-            acc = acc + np.where(e[:, i] == f32(0.0), f32(0.0), p[:, i] * logp[:, i])
-        entropy = -acc
-        every = np.arange(count)
+        v = heads[1][:, 0]
         c, ec, vc = f32(hyper.clip_range), f32(hyper.ent_coef), f32(hyper.vf_coef)
-        pg, kl, clipped, g = _surrogate(logp[every, a] - old, adv, c)
+        count_f = f32(count)
         t = ret - v
         vl = t * t
-        count_f = f32(count)
-        onehot = np.zeros((count, spec.n_actions), dtype=f32)
-        onehot[every, a] = f32(1.0)
-        pull = (-g)[:, None] * (onehot - p)
-        ent = np.where(e == f32(0.0), f32(0.0), (ec * p) * (logp + entropy[:, None]))
-        dlogit = (pull + ent) / count_f
         dv = ((vc * f32(2.0)) * (v - ret)) / count_f
+        dlog_std = []
+        if gaussian:  # "sde policy" steps 3', 5' and 7' on the last pi activations
+            from reinfocus_amd.environments import sde
+
+            mu, h = heads[0][:, 0], mlps[0][-1]
+            std2 = sde.std2_of(params[spec.log_std_at:])
+            sigma = sde.sigma_of(h, std2)
+            logp = sde.log_prob_of(a, mu, sigma)
+            entropy = sde.entropy_of(sigma)
+            pg, kl, clipped, g = _surrogate(logp - old, adv, c)
+            ng, t, v2 = -g, a - mu, sigma * sigma
+            fine = np.isfinite(sigma) & np.isfinite(logp)
+            dmu = np.where(fine, (ng * (t / v2)) / count_f, _NAN)
+            dsig = np.where(fine, (((ng * ((t * t) / (v2 * sigma) - f32(1.0) / sigma)) - ec / sigma) / count_f) / sigma, _NAN)
+            dlogit = dmu[:, None]
+            acc = np.zeros(spec.latent, dtype=f32)
+            for b in range(count):
+                acc = acc + ((h[b] * h[b]) * std2) * dsig[b]
+            dlog_std = [acc]
+        else:
+            logits = heads[0]
+            _, z, _, s, degenerate = softmax_parts(logits)
+            e = exp32(z)
+            lse = np.where(degenerate, _NAN, log32(np.where(degenerate, f32(1.0), s)))
+            logp = z - lse[:, None]
+            p = e / s[:, None]
+            acc = np.zeros(count, dtype=f32)
+            for i in range(spec.n_actions):
+                acc = acc + np.where(e[:, i] == f32(0.0), f32(0.0), p[:, i] * logp[:, i])
+            entropy = -acc
+            every = np.arange(count)
+            pg, kl, clipped, g = _surrogate(logp[every, a] - old, adv, c)
+            onehot = np.zeros((count, spec.n_actions), dtype=f32)
+            onehot[every, a] = f32(1.0)
+            pull = (-g)[:, None] * (onehot - p)
+            ent = np.where(e == f32(0.0), f32(0.0), (ec * p) * (logp + entropy[:, None]))
+            dlogit = (pull + ent) / count_f
         pieces = []
         for net, (delta_head, (lstm, layers, last)) in enumerate(zip((dlogit, dv[:, None]), spec.nets(params))):
             h_prev, c_prev, gates, c1, _ = cells[net]
@@ -230,8 +263,8 @@ def lstm_gradient_numpy(spec, params, batch, episode_starts, lstm_states, n_step
             for acts_in, delta in zip(mlps[net], deltas):
                 weight, bias = _chain(acts_in, delta)
                 pieces += [weight.reshape(-1), bias]
-    grad = canonical(np.concatenate(pieces))
-    terms = np.stack([pg, vl, entropy, kl, clipped])
+    grad = canonical(np.concatenate(pieces + dlog_std))
+    terms = np.stack([pg, vl, entropy, kl, clipped]).astype(f32)
     assert grad.dtype == f32 and grad.size == spec.size and terms.dtype == f32
     return grad, terms, invalid
 
@@ -278,7 +311,12 @@ class _Splits(_Hyper):
     """What both learners share: the hyper-parameters of learner._Hyper and sb3-contrib's minibatches of an epoch."""
 
     def _refuse_rollout(self, rollout):
-        lstm_module._refuse_box(rollout.env.single_action_space)
+        if self.spec.kind == "lstm_sde":
+            from reinfocus_amd.environments import lstm_sde
+
+            lstm_sde._refuse_discrete(rollout.env.single_action_space)
+        else:
+            lstm_module._refuse_box(rollout.env.single_action_space)
 
     @staticmethod
     def _minibatches(total, n_epochs, batch_size, splits, generator):
@@ -300,7 +338,8 @@ class _Splits(_Hyper):
 
 
 class LstmLearner(_Splits):
-    """The numpy twin of DeviceLstmLearner, and its oracle: updates policy.params (an lstm.LstmPolicy's) in place."""
+    """The numpy twin of DeviceLstmLearner, and its oracle: updates policy.params (an lstm.LstmPolicy's, or an
+    lstm_sde.LstmSdePolicy's with the Gaussian head) in place."""
 
     def __init__(self, policy, learning_rate=3e-4, clip_range=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5,
                  normalize_advantage=True, betas=(0.9, 0.999), adam_eps=1e-5):
@@ -346,8 +385,8 @@ class LstmLearner(_Splits):
 
 
 class DeviceLstmLearner(_Splits):
-    """The learner of an lstm.DeviceLstmPolicy, over torch tensors on its GPU; used as LstmLearner is and bit for bit
-    equal to it.  update() is rf_lstm_ppo_update: six launches on torch's current stream, which change policy.params in
+    """The learner of an lstm.DeviceLstmPolicy or an lstm_sde.DeviceLstmSdePolicy, over torch tensors on its GPU; used as
+    LstmLearner is and bit for bit equal to it.  update() is rf_lstm_ppo_update (rf_lstm_sde_update): six launches on torch's current stream, which change policy.params in
     place -- the next collect() on the same stream sees them.  train() enqueues every update of every epoch back to
     back; the split indices are host integers and the stats are rows of one device tensor.  No method synchronises the
     host (state_dict() reads the step and does)."""
@@ -362,8 +401,10 @@ class DeviceLstmLearner(_Splits):
         self._torch, self._interop, self._io, self._ctx = policy._torch, policy._interop, policy._io, policy._ctx
         self.device = policy.device
         torch = self._torch
-        if self._ctx.lstm_ppo_state_size(self.spec.desc()) != 4 * (STATE_HEADER + 2 * self.spec.size):
-            raise RuntimeError("rf_lstm_ppo_state_size disagrees with the packed optimizer state")
+        self._sde = self.spec.kind == "lstm_sde"  # (the Gaussian head: rf_lstm_sde_* over P + L parameters)
+        state_size = self._ctx.lstm_sde_state_size if self._sde else self._ctx.lstm_ppo_state_size
+        if state_size(self.spec.desc()) != 4 * (STATE_HEADER + 2 * self.spec.size):
+            raise RuntimeError("rf_lstm_ppo_state_size / rf_lstm_sde_state_size disagrees with the packed optimizer state")
         self.state = torch.zeros(STATE_HEADER + 2 * self.spec.size, dtype=torch.float32, device=self.device)
         self._workspace, self._workspace_batch = None, 0
         self._stats = None
@@ -373,10 +414,16 @@ class DeviceLstmLearner(_Splits):
         torch = self._torch
         n_steps, num_envs, first, count = _checked_minibatch(parts["n_steps"], parts["num_envs"], first, count)
         total, hidden = n_steps * num_envs, self.spec.lstm_hidden
-        if isinstance(parts.get("actions"), torch.Tensor) and parts["actions"].dtype == torch.float32:
-            raise ValueError("the update has a Categorical head over int64 actions, not a float32 action slab: the Gaussian "
-                             "(sde) head on top of the LSTM is out of scope")
-        wanted = {"observations": (torch.float32, (total, self.spec.obs_width)), "actions": (torch.int64, (total,)),
+        if isinstance(parts.get("actions"), torch.Tensor):
+            if not self._sde and parts["actions"].dtype == torch.float32:
+                raise ValueError("the update has a Categorical head over int64 actions, not a float32 action slab: the "
+                                 "Gaussian (sde) head on top of the LSTM is out of scope for a DeviceLstmPolicy (a "
+                                 "DeviceLstmSdePolicy has it)")
+            if self._sde and parts["actions"].dtype == torch.int64:
+                raise ValueError("the update has a Gaussian head over float32 raw actions, not an int64 action slab: "
+                                 "Discrete action spaces have DeviceLstmPolicy")
+        wanted = {"observations": (torch.float32, (total, self.spec.obs_width)),
+                  "actions": (torch.float32 if self._sde else torch.int64, (total,)),
                   "log_probs": (torch.float32, (total,)), "advantages": (torch.float32, (total,)),
                   "returns": (torch.float32, (total,)), "episode_starts": (torch.uint8, (n_steps + 1, num_envs)),
                   "lstm_states": (torch.float32, (n_steps + 1, 2, 2, num_envs, hidden))}
@@ -391,19 +438,20 @@ class DeviceLstmLearner(_Splits):
 
     def _room(self, batch):
         if batch > self._workspace_batch:
-            size = self._ctx.lstm_ppo_workspace_size(self.spec.desc(), batch)
+            workspace_size = self._ctx.lstm_sde_workspace_size if self._sde else self._ctx.lstm_ppo_workspace_size
+            size = workspace_size(self.spec.desc(), batch)
             if size == 0:
-                raise RuntimeError(f"rf_lstm_ppo_workspace_size refuses a minibatch of {batch}")
+                raise RuntimeError(f"rf_lstm_ppo_workspace_size / rf_lstm_sde_workspace_size refuses a minibatch of {batch}")
             self._workspace = self._torch.zeros(size // 4, dtype=self._torch.float32, device=self.device)
             self._workspace_batch = batch
 
     def _enqueue(self, parts, n_steps, num_envs, first, count, stats, hyper):
-        self._ctx.lstm_ppo_update(self.spec.desc(), hyper, self.policy.params.data_ptr(), self.state.data_ptr(),
-                                  self._workspace.data_ptr(), n_steps, num_envs, parts["observations"].data_ptr(),
-                                  parts["actions"].data_ptr(), parts["log_probs"].data_ptr(),
-                                  parts["advantages"].data_ptr(), parts["returns"].data_ptr(),
-                                  parts["episode_starts"].data_ptr(), parts["lstm_states"].data_ptr(), first, count,
-                                  stats.data_ptr(), self._io._stream())
+        update = self._ctx.lstm_sde_update if self._sde else self._ctx.lstm_ppo_update
+        update(self.spec.desc(), hyper, self.policy.params.data_ptr(), self.state.data_ptr(), self._workspace.data_ptr(),
+               n_steps, num_envs, parts["observations"].data_ptr(), parts["actions"].data_ptr(),
+               parts["log_probs"].data_ptr(), parts["advantages"].data_ptr(), parts["returns"].data_ptr(),
+               parts["episode_starts"].data_ptr(), parts["lstm_states"].data_ptr(), first, count, stats.data_ptr(),
+               self._io._stream())
 
     def _own(self, rollout):
         if getattr(rollout, "device", None) != self.device:

@@ -19,7 +19,8 @@ collect(policy) runs a whole rollout with a policy of environments/policy.py (Po
 DeviceRollout) or, over a Box(-1, 1, (1,)) action space, of environments/sde.py (SdePolicy, DeviceSdePolicy: the raw
 action goes into the slab, the clamped one to the step, and sde_sample_freq says when the noise is resampled): on the
 device a step is then one policy launch, which writes rows of the slabs, and the environment's step from those rows.
-With a recurrent policy of environments/lstm.py (LstmPolicy, DeviceLstmPolicy) collect() also keeps what sb3-contrib's
+With a recurrent policy of environments/lstm.py (LstmPolicy, DeviceLstmPolicy) or, over the Box space, of
+environments/lstm_sde.py (LstmSdePolicy, DeviceLstmSdePolicy: both rules at once) collect() also keeps what sb3-contrib's
 RecurrentRolloutBuffer hands to the update -- episode_starts uint8 [T + 1, n] and lstm_states float32
 [T + 1, 2, 2, n, H], made on first use with such a policy --; flat() and minibatches() are unchanged.
 
@@ -133,8 +134,9 @@ class _Bookkeeping:
         if self._t != 0:
             raise ValueError("collect() runs a whole rollout: start() first, and take no step() before it")
         kind = getattr(getattr(policy, "spec", None), "kind", None)
-        sde = kind == "sde"
-        self._lstm = kind == "lstm"  # (a recurrent policy of environments/lstm.py: collect() keeps its states)
+        sde = kind in ("sde", "lstm_sde")
+        # (a recurrent policy of environments/lstm.py or lstm_sde.py: collect() keeps its states)
+        self._lstm = kind in ("lstm", "lstm_sde")
         if sde and _index_task(self.env):
             raise ValueError("collect() was given a policy with a Gaussian head, and the environment's action space is "
                              f"{self.env.single_action_space!r}: Discrete action spaces have Policy / DevicePolicy")
@@ -144,7 +146,7 @@ class _Bookkeeping:
         if int(sde_sample_freq) != sde_sample_freq or (sde_sample_freq < 1 and sde_sample_freq != -1):
             raise ValueError(f"sde_sample_freq {sde_sample_freq!r} is not -1 or a positive integer")
         if not sde and sde_sample_freq != -1:
-            raise ValueError("sde_sample_freq belongs to the policies of environments/sde.py")
+            raise ValueError("sde_sample_freq belongs to the policies of environments/sde.py and lstm_sde.py")
         return sde
 
     @staticmethod
@@ -227,10 +229,9 @@ class Rollout(_Bookkeeping):
             if sde and self._resample(t, sde_sample_freq):
                 policy.reset_noise(self.num_envs)
             if self._lstm:
-                actions, values, log_probs, final_values = policy.act(
+                actions, values, log_probs, final_values, *clamped = policy.act(
                     self.observations[t], self.episode_starts[t], final_obs, deterministic,
                     states=(self.lstm_states[t], self.lstm_states[t + 1]))
-                clamped = ()
             else:
                 actions, values, log_probs, final_values, *clamped = policy.act(self.observations[t], final_obs,
                                                                                 deterministic)
@@ -401,13 +402,15 @@ class DeviceRollout(_Bookkeeping):
             if sde and self._resample(t, sde_sample_freq):
                 policy.reset_noise(self.num_envs)
             out = (self.actions[t], self.values[t], self.log_probs[t], final_out)
+            if sde:
+                out += (self._env_actions,)
             if self._lstm:
                 # episode_starts[t + 1] IS truncated[t]: the call reads the step's own row, and the slab is filled by one
                 # copy after the loop -- no launch per step, nothing waited for
                 policy.act(self.observations[t], self.episode_starts[0] if t == 0 else self.truncated[t - 1], final_obs,
                            deterministic, out=out, states=(self.lstm_states[t], self.lstm_states[t + 1]))
             else:
-                policy.act(self.observations[t], final_obs, deterministic, out=out + (self._env_actions,) if sde else out)
+                policy.act(self.observations[t], final_obs, deterministic, out=out)
             info = self.env.step_tensors(self._env_actions if sde else self.actions[t],
                                          out=(self.observations[t + 1], self.rewards[t], self.truncated[t]))[4]
             self._t = t + 1
