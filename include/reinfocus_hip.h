@@ -1009,7 +1009,8 @@ int rf_sde_update(rf_ctx *ctx, const rf_policy_desc *policy, const rf_ppo_desc *
  * RecurrentPPO with RecurrentActorCriticPolicy at its defaults: lstm_hidden_size=256, n_lstm_layers=1, shared_lstm=False,
  * enable_critic_lstm=True.  No reference counterpart.  Needs no environment: the context only says which GPU.
  * The update (back-propagation through time) is "lstm update" below; the Gaussian (sde) head on top of the LSTM is "lstm
- * sde policy" further down.  Out of scope: n_lstm_layers > 1, shared_lstm=True, enable_critic_lstm=False.
+ * sde policy" further down; enable_critic_lstm=False (a feed-forward critic) is "lstm critic" at the end.  Out of scope:
+ * n_lstm_layers > 1, shared_lstm=True, lstm_hidden_size > RF_POLICY_MAX_WIDTH.
  *
  * One definition, numpy twin (environments/lstm.py lstm_numpy), host build (tests/lstmcheck) and kernel (csrc/rf_lstm.h)
  * alike; the scalar functions are csrc/rf_policy_math.h.  Everything is float32, one rounding per operation, nothing
@@ -1139,8 +1140,8 @@ int rf_lstm_ppo_update(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const rf_pp
  *  Noise.  theta float32[n][L] is S5: draw e * L + k of `gen`, with log_std read from THIS policy's parameters.
  *  Packing.  L8 for both nets with n_actions == 1, then log_std[L] last of everything: P + L floats.  Names: L8's, and
  *     "log_std".
- * Still out of scope: more than one action dimension, n_lstm_layers > 1, shared_lstm=True, enable_critic_lstm=False,
- * learn_features=True, use_expln, squash_output.
+ * enable_critic_lstm=False is "lstm critic" below.  Still out of scope: more than one action dimension, n_lstm_layers > 1,
+ * shared_lstm=True, lstm_hidden_size > RF_POLICY_MAX_WIDTH, learn_features=True, use_expln, squash_output.
  *
  *   rf_lstm_sde_params_size  floats of the packed parameters (P + L); 0 for a desc outside the limits or a NULL ctx
  *   rf_lstm_sde_noise_reset  one launch (rf_sde_noise_reset's kernel): d_theta float32[n][L] from gen and the log_std
@@ -1183,6 +1184,82 @@ int rf_lstm_sde_update(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const rf_pp
                        const float *d_log_probs, const float *d_advantages, const float *d_returns,
                        const uint8_t *d_episode_starts, const float *d_lstm_states, int first, int B, float *d_stats,
                        void *caller_stream);
+
+/* ---- lstm critic: the recurrent actor-critic with a feed-forward critic (enable_critic_lstm=False) --------------------------
+ * sb3-contrib's RecurrentActorCriticPolicy(enable_critic_lstm=False, shared_lstm=False), which rl_zoo3's sampler for
+ * RecurrentPPO draws in half of its trials: the policy has no lstm_critic but critic = nn.Linear(features_dim,
+ * lstm_hidden_size); forward, evaluate_actions and predict_values compute latent_vf = critic(features) -- no activation, no
+ * state, no episode-start mask -- and hand it to the vf MLP and value_net as before; the actor is unchanged; the returned
+ * lstm_states.vf is a copy of lstm_states.pi.  No reference counterpart.  Written as deltas of "lstm policy" (L1 - L9), "lstm
+ * update" (U1 - U9) and their two sde siblings; numpy twins environments/lstm.py, lstm_sde.py and lstm_learner.py (a spec
+ * with enable_critic_lstm=False), host build tests/lstmcriticcheck, kernels lstm_forward_kernel<., true> (csrc/rf_lstm.h),
+ * lstm_ppo_forward_kernel<true> and lstm_ppo_gradient_kernel<., true> (csrc/rf_lstm_ppo.h).  Everything is float32, a
+ * multiply and then an add in index order, nothing contracted; no MFMA.
+ *
+ *  C1 Network.  The pi net is L1's.  The vf net is ONE linear layer D -> H, then the vf MLP (input width H) and its head,
+ *     exactly as today.
+ *  C2 Linear layer.  For unit j: a = bias[j]; for k = 0 .. D-1: a = a + x_k * W[j][k].  No activation: this a is the vf
+ *     MLP's input ("policy"'s linear layer).
+ *  C3 Starts and state.  episode_starts and the state have no influence on any value.  The state keeps its shape, float32
+ *     [2][2][n][H]; a forward that stores a state writes the pi net's h' and c' into BOTH halves (sb3-contrib's
+ *     lstm_states_vf = lstm_states_pi); nothing ever reads the vf half; a state updated in place stays legal.
+ *  C4 V(final_observation) is the vf MLP on critic(final_obs), NaN where final_obs[e][0] is NaN (L6's rule).  A values-only
+ *     call (L7) is the vf net on obs.  It reads neither d_state_in nor d_episode_starts; both pointers are still checked.
+ *  C5 Packing.  The pi net as L8.  The vf net: critic.weight^T [D][H], critic.bias [H], then what "policy" packs for the vf
+ *     MLP and head: P' = P - [4H (D + H) + 8H] + [D H + H] floats.  Names: critic.weight (torch shape [H, D]) and
+ *     critic.bias in place of the four lstm_critic.* ones.  With the sde head log_std[L] stays last of everything.
+ *  C6 Update, forward.  U2's sequences exist for the pi net only.  For the vf net row b's MLP input is C2 on
+ *     observations[r_b].  The vf half of lstm_states is never read; episode_starts reaches the value path nowhere.
+ *  C7 Update, backward.  U6 runs unchanged for both nets; for the vf net dh_mlp[b][j] is the delta of the linear layer's
+ *     output.  U7 (BPTT) runs for the pi net only.  U8 gains dW^T[k][j], one chain over b = 0 .. B-1 ascending from +0 of
+ *     x[b][k] * dh_mlp_vf[b][j], and dbias[j], the same chain of dh_mlp_vf[b][j].  Every other piece is as today.
+ *  C8 Norm, skip, clip, Adam.  U9 over the P' packed floats of C5 (P' + L with sde); the optimizer state is 32 + 8 P' bytes
+ *     (32 + 8 (P' + L)).  The workspace has no h_prev, c_prev, gates, c' or da of the vf net: it is smaller than the LSTM
+ *     critic's at the same batch.
+ *  Gaussian head.  Steps 1', 3', 5', 6' and 7' of "lstm sde update" and the noise of "lstm sde policy" apply unchanged: they
+ *     touch only the pi net.
+ * Still out of scope: shared_lstm=True (critic values other than the two below are refused, which leaves room for it),
+ * n_lstm_layers > 1, lstm_hidden_size > RF_POLICY_MAX_WIDTH.
+ *
+ * Every entry point below is its rf_lstm_ sibling over rf_lstm_critic_desc: with critic == RF_LSTM_CRITIC_LSTM it IS the
+ * sibling (the same launches, the same bytes); with RF_LSTM_CRITIC_LINEAR it computes the definition above, a forward in
+ * one launch, an update in six.  The same arguments, the same refusals, all before anything is enqueued; any other critic
+ * is refused as a desc outside the limits.  (rf_lstm_state_size needs no sibling: the state keeps its shape.) */
+#define RF_LSTM_CRITIC_LSTM 0
+#define RF_LSTM_CRITIC_LINEAR 1
+
+typedef struct rf_lstm_critic_desc {
+    rf_lstm_policy_desc lstm;
+    int critic; /* RF_LSTM_CRITIC_LSTM or RF_LSTM_CRITIC_LINEAR */
+} rf_lstm_critic_desc;
+
+unsigned long long rf_lstm_critic_params_size(rf_ctx *ctx, const rf_lstm_critic_desc *desc);
+int rf_lstm_critic_forward(rf_ctx *ctx, const rf_lstm_critic_desc *desc, const float *d_params, int n, const float *d_obs,
+                           const uint8_t *d_episode_starts, const float *d_final_obs, const float *d_state_in,
+                           float *d_state_out, const unsigned long long gen[4], int flags, long long *d_actions,
+                           float *d_log_probs, float *d_values, float *d_final_values, float *d_logits, void *caller_stream);
+unsigned long long rf_lstm_critic_ppo_state_size(rf_ctx *ctx, const rf_lstm_critic_desc *desc);
+unsigned long long rf_lstm_critic_ppo_workspace_size(rf_ctx *ctx, const rf_lstm_critic_desc *desc, int max_batch);
+int rf_lstm_critic_ppo_update(rf_ctx *ctx, const rf_lstm_critic_desc *desc, const rf_ppo_desc *ppo, float *d_params,
+                              void *d_state, void *d_workspace, int n_steps, int num_envs, const float *d_observations,
+                              const long long *d_actions, const float *d_log_probs, const float *d_advantages,
+                              const float *d_returns, const uint8_t *d_episode_starts, const float *d_lstm_states, int first,
+                              int B, float *d_stats, void *caller_stream);
+unsigned long long rf_lstm_critic_sde_params_size(rf_ctx *ctx, const rf_lstm_critic_desc *desc);
+int rf_lstm_critic_sde_noise_reset(rf_ctx *ctx, const rf_lstm_critic_desc *desc, const float *d_params, int n,
+                                   const unsigned long long gen[4], float *d_theta, void *caller_stream);
+int rf_lstm_critic_sde_forward(rf_ctx *ctx, const rf_lstm_critic_desc *desc, const float *d_params, int n, const float *d_obs,
+                               const uint8_t *d_episode_starts, const float *d_final_obs, const float *d_state_in,
+                               float *d_state_out, const float *d_theta, int flags, float *d_actions, float *d_env_actions,
+                               float *d_log_probs, float *d_values, float *d_final_values, float *d_mean, float *d_sigma,
+                               void *caller_stream);
+unsigned long long rf_lstm_critic_sde_state_size(rf_ctx *ctx, const rf_lstm_critic_desc *desc);
+unsigned long long rf_lstm_critic_sde_workspace_size(rf_ctx *ctx, const rf_lstm_critic_desc *desc, int max_batch);
+int rf_lstm_critic_sde_update(rf_ctx *ctx, const rf_lstm_critic_desc *desc, const rf_ppo_desc *ppo, float *d_params,
+                              void *d_state, void *d_workspace, int n_steps, int num_envs, const float *d_observations,
+                              const float *d_actions, const float *d_log_probs, const float *d_advantages,
+                              const float *d_returns, const uint8_t *d_episode_starts, const float *d_lstm_states, int first,
+                              int B, float *d_stats, void *caller_stream);
 
 #ifdef __cplusplus
 }

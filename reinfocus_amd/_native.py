@@ -119,6 +119,17 @@ SYMBOLS = (
     "rf_lstm_sde_state_size",
     "rf_lstm_sde_workspace_size",
     "rf_lstm_sde_update",
+    "rf_lstm_critic_params_size",
+    "rf_lstm_critic_forward",
+    "rf_lstm_critic_ppo_state_size",
+    "rf_lstm_critic_ppo_workspace_size",
+    "rf_lstm_critic_ppo_update",
+    "rf_lstm_critic_sde_params_size",
+    "rf_lstm_critic_sde_noise_reset",
+    "rf_lstm_critic_sde_forward",
+    "rf_lstm_critic_sde_state_size",
+    "rf_lstm_critic_sde_workspace_size",
+    "rf_lstm_critic_sde_update",
     "rf_render_kernel_name",
     "rf_pixels_rendered",
     "rf_allocations_poisoned",
@@ -194,6 +205,19 @@ class LstmPolicyDesc(ctypes.Structure):
     def __init__(self, *desc):
         """The nine integers of rf_policy_desc in order, then lstm_hidden."""
         super().__init__(PolicyDesc(*desc[:9]), *desc[9:])
+
+
+LSTM_CRITIC_LSTM, LSTM_CRITIC_LINEAR = 0, 1  # RF_LSTM_CRITIC_LSTM, RF_LSTM_CRITIC_LINEAR
+
+
+class LstmCriticDesc(ctypes.Structure):
+    """rf_lstm_critic_desc (include/reinfocus_hip.h, "lstm critic"): the rf_lstm_policy_desc, then critic."""
+
+    _fields_ = [("lstm", LstmPolicyDesc), ("critic", ctypes.c_int)]
+
+    def __init__(self, *desc):
+        """The ten integers of rf_lstm_policy_desc in order, then critic (LSTM_CRITIC_LSTM or LSTM_CRITIC_LINEAR)."""
+        super().__init__(LstmPolicyDesc(*desc[:10]), *desc[10:])
 
 
 class PpoDesc(ctypes.Structure):
@@ -400,6 +424,13 @@ def load():
     lib.rf_lstm_sde_workspace_size.restype = ctypes.c_ulonglong
     lib.rf_lstm_sde_workspace_size.argtypes = [vp, vp, i32]
     lib.rf_lstm_sde_update.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp]
+    for head in ("", "sde_"):  # "lstm critic": each sibling has its rf_lstm_ function's arguments over another desc
+        for name in ("params_size", "forward") + (("noise_reset",) if head else ()):
+            ours, theirs = getattr(lib, f"rf_lstm_critic_{head}{name}"), getattr(lib, f"rf_lstm_{head}{name}")
+            ours.restype, ours.argtypes = theirs.restype, theirs.argtypes
+        for name in ("state_size", "workspace_size", "update"):
+            ours, theirs = getattr(lib, f"rf_lstm_critic_{head or 'ppo_'}{name}"), getattr(lib, f"rf_lstm_{head or 'ppo_'}{name}")
+            ours.restype, ours.argtypes = theirs.restype, theirs.argtypes
     lib.rf_render_kernel_name.restype = ctypes.c_char_p
     lib.rf_render_kernel_name.argtypes = [vp]
     lib.rf_pixels_rendered.restype = ctypes.c_ulonglong
@@ -905,6 +936,70 @@ class Context:
                                           params_ptr, state_ptr, workspace_ptr, n_steps, num_envs, obs_ptr, actions_ptr,
                                           log_probs_ptr, advantages_ptr, returns_ptr, episode_starts_ptr, lstm_states_ptr,
                                           first, batch, stats_ptr, stream)
+        if rc != 0:
+            _check(rc)
+
+    # --- lstm critic (rf_lstm_critic_*): the recurrent entry points over rf_lstm_critic_desc ----------------------------
+    # `desc` is the eleven integers of rf_lstm_critic_desc (rf_lstm_policy_desc's ten, then critic); every other argument
+    # is the sibling's.  Only the update and forward calls enqueue.
+    def lstm_critic_params_size(self, desc, sde=False):
+        """rf_lstm_critic_params_size (rf_lstm_critic_sde_params_size with sde): floats of the packed parameters; 0 if
+        refused."""
+        call = self._lib.rf_lstm_critic_sde_params_size if sde else self._lib.rf_lstm_critic_params_size
+        return int(call(self._h, ctypes.byref(LstmCriticDesc(*desc))))
+
+    def lstm_critic_state_size(self, desc, sde=False):
+        """rf_lstm_critic_ppo_state_size / rf_lstm_critic_sde_state_size: bytes of the optimizer state; 0 if refused."""
+        call = self._lib.rf_lstm_critic_sde_state_size if sde else self._lib.rf_lstm_critic_ppo_state_size
+        return int(call(self._h, ctypes.byref(LstmCriticDesc(*desc))))
+
+    def lstm_critic_workspace_size(self, desc, max_batch, sde=False):
+        """rf_lstm_critic_ppo_workspace_size / rf_lstm_critic_sde_workspace_size: bytes of the workspace; 0 if refused."""
+        call = self._lib.rf_lstm_critic_sde_workspace_size if sde else self._lib.rf_lstm_critic_ppo_workspace_size
+        return int(call(self._h, ctypes.byref(LstmCriticDesc(*desc)), max_batch))
+
+    def lstm_critic_forward(self, desc, params_ptr, num_envs, obs_ptr, episode_starts_ptr, final_obs_ptr, state_in_ptr,
+                            state_out_ptr, gen, flags, actions_ptr, log_probs_ptr, values_ptr, final_values_ptr, logits_ptr,
+                            stream):
+        """rf_lstm_critic_forward: lstm_forward over rf_lstm_critic_desc.  Only enqueues."""
+        words = None if gen is None else (ctypes.c_ulonglong * 4)(*gen)
+        rc = self._lib.rf_lstm_critic_forward(self._h, ctypes.byref(LstmCriticDesc(*desc)), params_ptr, num_envs, obs_ptr,
+                                              episode_starts_ptr, final_obs_ptr, state_in_ptr, state_out_ptr, words, flags,
+                                              actions_ptr, log_probs_ptr, values_ptr, final_values_ptr, logits_ptr, stream)
+        if rc != 0:
+            _check(rc)
+
+    def lstm_critic_ppo_update(self, desc, hyper, params_ptr, state_ptr, workspace_ptr, n_steps, num_envs, obs_ptr,
+                               actions_ptr, log_probs_ptr, advantages_ptr, returns_ptr, episode_starts_ptr, lstm_states_ptr,
+                               first, batch, stats_ptr, stream, sde=False):
+        """rf_lstm_critic_ppo_update (rf_lstm_critic_sde_update with sde: float32 raw actions): lstm_ppo_update /
+        lstm_sde_update over rf_lstm_critic_desc.  Only enqueues."""
+        call = self._lib.rf_lstm_critic_sde_update if sde else self._lib.rf_lstm_critic_ppo_update
+        rc = call(self._h, ctypes.byref(LstmCriticDesc(*desc)), ctypes.byref(PpoDesc(*hyper)), params_ptr, state_ptr,
+                  workspace_ptr, n_steps, num_envs, obs_ptr, actions_ptr, log_probs_ptr, advantages_ptr, returns_ptr,
+                  episode_starts_ptr, lstm_states_ptr, first, batch, stats_ptr, stream)
+        if rc != 0:
+            _check(rc)
+
+    def lstm_critic_sde_update(self, *args):
+        """rf_lstm_critic_sde_update: lstm_critic_ppo_update with the Gaussian head."""
+        self.lstm_critic_ppo_update(*args, sde=True)
+
+    def lstm_critic_sde_noise_reset(self, desc, params_ptr, num_envs, gen, theta_ptr, stream):
+        """rf_lstm_critic_sde_noise_reset: lstm_sde_noise_reset over rf_lstm_critic_desc.  Only enqueues."""
+        rc = self._lib.rf_lstm_critic_sde_noise_reset(self._h, ctypes.byref(LstmCriticDesc(*desc)), params_ptr, num_envs,
+                                                      (ctypes.c_ulonglong * 4)(*gen), theta_ptr, stream)
+        if rc != 0:
+            _check(rc)
+
+    def lstm_critic_sde_forward(self, desc, params_ptr, num_envs, obs_ptr, episode_starts_ptr, final_obs_ptr, state_in_ptr,
+                                state_out_ptr, theta_ptr, flags, actions_ptr, env_actions_ptr, log_probs_ptr, values_ptr,
+                                final_values_ptr, mean_ptr, sigma_ptr, stream):
+        """rf_lstm_critic_sde_forward: lstm_sde_forward over rf_lstm_critic_desc.  Only enqueues."""
+        rc = self._lib.rf_lstm_critic_sde_forward(self._h, ctypes.byref(LstmCriticDesc(*desc)), params_ptr, num_envs, obs_ptr,
+                                                  episode_starts_ptr, final_obs_ptr, state_in_ptr, state_out_ptr, theta_ptr,
+                                                  flags, actions_ptr, env_actions_ptr, log_probs_ptr, values_ptr,
+                                                  final_values_ptr, mean_ptr, sigma_ptr, stream)
         if rc != 0:
             _check(rc)
 

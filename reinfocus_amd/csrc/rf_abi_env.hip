@@ -2254,14 +2254,44 @@ int rf_sde_forward(rf_ctx *ctx, const rf_policy_desc *desc, const float *d_param
     return RF_OK;
 }
 
-unsigned long long rf_lstm_params_size(rf_ctx *ctx, const rf_lstm_policy_desc *desc)
+// The recurrent entry points are written once, over (desc, sde, critic): the rf_lstm_ / rf_lstm_sde_ ones are these with
+// RF_LSTM_CRITIC_LSTM, their rf_lstm_critic_ siblings hand in rf_lstm_critic_desc.critic ("lstm critic").  Each extern "C"
+// wrapper checks ctx and selects its device; the bodies below do everything else.
+static bool lstm_layout_any(const rf_lstm_policy_desc *desc, bool sde, int critic, rf::LstmLayout &layout)
+{
+    return desc != nullptr && rf::lstm_layout_nets(*desc, layout, sde, critic);
+}
+
+// floats of the packed parameters; 0 if refused
+static unsigned long long lstm_params_size_any(rf_ctx *ctx, const rf_lstm_policy_desc *desc, bool sde, int critic)
 {
     rf::LstmLayout layout;
-    if (ctx == nullptr || desc == nullptr || !rf::lstm_layout(*desc, layout))
+    return ctx != nullptr && lstm_layout_any(desc, sde, critic, layout) ? layout.total : 0;
+}
+
+// bytes of the optimizer state; 0 if refused
+static unsigned long long lstm_state_size_any(rf_ctx *ctx, const rf_lstm_policy_desc *desc, bool sde, int critic)
+{
+    rf::LstmLayout layout;
+    return ctx != nullptr && lstm_layout_any(desc, sde, critic, layout) ? 4ull * rf::kPpoStateHeader + 8ull * layout.total : 0;
+}
+
+// bytes of the update's workspace; 0 if refused
+static unsigned long long lstm_workspace_size_any(rf_ctx *ctx, const rf_lstm_policy_desc *desc, bool sde, int critic,
+                                                  int max_batch)
+{
+    rf::LstmLayout layout;
+    rf::LstmPpoWork work;
+    if (ctx == nullptr || !lstm_layout_any(desc, sde, critic, layout) || !rf::lstm_ppo_work(layout, max_batch, work))
         return 0;
-    if (hipSetDevice(ctx->device) != hipSuccess) // (as every entry point; nothing of the device is needed)
+    return 4ull * work.total;
+}
+
+unsigned long long rf_lstm_params_size(rf_ctx *ctx, const rf_lstm_policy_desc *desc)
+{
+    if (ctx != nullptr && hipSetDevice(ctx->device) != hipSuccess) // (as every entry point; nothing of the device is needed)
         (void)hipGetLastError();
-    return layout.total;
+    return lstm_params_size_any(ctx, desc, false, RF_LSTM_CRITIC_LSTM);
 }
 
 unsigned long long rf_lstm_state_size(rf_ctx *ctx, const rf_lstm_policy_desc *desc, int n)
@@ -2274,20 +2304,20 @@ unsigned long long rf_lstm_state_size(rf_ctx *ctx, const rf_lstm_policy_desc *de
     return rf::lstm_state_floats(n, layout.hidden);
 }
 
-int rf_lstm_forward(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const float *d_params, int n, const float *d_obs,
-                    const uint8_t *d_episode_starts, const float *d_final_obs, const float *d_state_in, float *d_state_out,
-                    const unsigned long long gen[4], int flags, long long *d_actions, float *d_log_probs, float *d_values,
-                    float *d_final_values, float *d_logits, void *caller_stream)
+// rf_lstm_forward and rf_lstm_critic_forward: one body
+static int lstm_forward_any(const char *fn, int critic, rf_ctx *ctx, const rf_lstm_policy_desc *desc, const float *d_params,
+                            int n, const float *d_obs, const uint8_t *d_episode_starts, const float *d_final_obs,
+                            const float *d_state_in, float *d_state_out, const unsigned long long gen[4], int flags,
+                            long long *d_actions, float *d_log_probs, float *d_values, float *d_final_values,
+                            float *d_logits, void *caller_stream)
 {
-    const char *fn = "rf_lstm_forward";
-    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", fn);
     RF_REQUIRE(desc != nullptr && d_params != nullptr && d_obs != nullptr && d_episode_starts != nullptr &&
                d_state_in != nullptr, "%s: NULL argument", fn);
     rf::LstmLayout layout;
-    RF_REQUIRE(rf::lstm_layout(*desc, layout),
+    RF_REQUIRE(lstm_layout_any(desc, false, critic, layout),
                "%s: the desc is outside the limits (obs_width and lstm_hidden 1 .. %d, 1 or 2 hidden layers of width 1 .. %d "
-               "per net, n_actions 2 .. %d, activation RF_POLICY_RELU or RF_POLICY_TANH)", fn, RF_POLICY_MAX_WIDTH,
-               RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_ACTIONS);
+               "per net, n_actions 2 .. %d, activation RF_POLICY_RELU or RF_POLICY_TANH, critic RF_LSTM_CRITIC_LSTM or "
+               "RF_LSTM_CRITIC_LINEAR)", fn, RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_ACTIONS);
     RF_REQUIRE(n >= 1 && n <= (1 << 30), "%s: n = %d must be at least 1 (and at most 2^30)", fn, n);
     RF_REQUIRE((flags & ~RF_POLICY_DETERMINISTIC) == 0, "%s: unknown flags %d", fn, flags);
     RF_REQUIRE(d_actions || d_values || d_final_values || d_logits || d_state_out, "%s: no output is asked for", fn);
@@ -2345,11 +2375,14 @@ int rf_lstm_forward(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const float *d
     if (sampled)
         for (int i = 0; i < 4; ++i)
             words.word[i] = gen[i];
-    // with d_state_out both cells run, whatever is asked of the heads: the state of both nets advances together
+    // with d_state_out both cells run, whatever is asked of the heads: the state of both nets advances together (the
+    // linear critic has no cell: its block runs for a value only, and the pi block stores both halves of the state)
+    const bool linear = critic == RF_LSTM_CRITIC_LINEAR;
     const bool pi = d_actions != nullptr || d_logits != nullptr || d_state_out != nullptr;
-    const bool vf = d_values != nullptr || d_final_values != nullptr || d_state_out != nullptr;
+    const bool vf = d_values != nullptr || d_final_values != nullptr || (!linear && d_state_out != nullptr);
     const unsigned tiles = (unsigned)((rows + rf::kPolicyTile - 1) / rf::kPolicyTile);
-    hipLaunchKernelGGL(rf::lstm_forward_kernel<false>, dim3(tiles, pi && vf ? 2u : 1u), dim3(rf::kPolicyThreads), 0,
+    const auto kernel = linear ? rf::lstm_forward_kernel<false, true> : rf::lstm_forward_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(tiles, pi && vf ? 2u : 1u), dim3(rf::kPolicyThreads), 0,
                        (hipStream_t)caller_stream, layout, d_params, n, d_obs, d_episode_starts, d_final_obs, d_state_in,
                        d_state_out, words, sampled ? 1 : 0, pi ? 0 : 1, (int64_t *)d_actions, d_log_probs, d_values,
                        d_final_values, d_logits, rf::LstmNoSde{});
@@ -2357,28 +2390,37 @@ int rf_lstm_forward(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const float *d
     return RF_OK;
 }
 
+int rf_lstm_forward(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const float *d_params, int n, const float *d_obs,
+                    const uint8_t *d_episode_starts, const float *d_final_obs, const float *d_state_in, float *d_state_out,
+                    const unsigned long long gen[4], int flags, long long *d_actions, float *d_log_probs, float *d_values,
+                    float *d_final_values, float *d_logits, void *caller_stream)
+{
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", "rf_lstm_forward");
+    RF_HIP(hipSetDevice(ctx->device));
+    return lstm_forward_any("rf_lstm_forward", RF_LSTM_CRITIC_LSTM, ctx, desc, d_params, n, d_obs, d_episode_starts,
+                            d_final_obs, d_state_in, d_state_out, gen, flags, d_actions, d_log_probs, d_values,
+                            d_final_values, d_logits, caller_stream);
+}
+
 #define RF_LSTM_SDE_LIMITS "%s: the desc is outside the limits (obs_width and lstm_hidden 1 .. %d, 1 or 2 hidden layers of " \
                            "width 1 .. %d per net, n_actions 1: the Gaussian head has one action, activation RF_POLICY_RELU " \
-                           "or RF_POLICY_TANH)"
+                           "or RF_POLICY_TANH, critic RF_LSTM_CRITIC_LSTM or RF_LSTM_CRITIC_LINEAR)"
 
 unsigned long long rf_lstm_sde_params_size(rf_ctx *ctx, const rf_lstm_policy_desc *desc)
 {
-    rf::LstmLayout layout;
-    if (ctx == nullptr || desc == nullptr || !rf::lstm_sde_layout(*desc, layout))
-        return 0;
-    if (hipSetDevice(ctx->device) != hipSuccess) // (as every entry point; nothing of the device is needed)
+    if (ctx != nullptr && hipSetDevice(ctx->device) != hipSuccess) // (as every entry point; nothing of the device is needed)
         (void)hipGetLastError();
-    return layout.total;
+    return lstm_params_size_any(ctx, desc, true, RF_LSTM_CRITIC_LSTM);
 }
 
-int rf_lstm_sde_noise_reset(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const float *d_params, int n,
-                            const unsigned long long gen[4], float *d_theta, void *caller_stream)
+// rf_lstm_sde_noise_reset and rf_lstm_critic_sde_noise_reset: one body
+static int lstm_sde_noise_reset_any(const char *fn, int critic, rf_ctx *ctx, const rf_lstm_policy_desc *desc,
+                                    const float *d_params, int n, const unsigned long long gen[4], float *d_theta,
+                                    void *caller_stream)
 {
-    const char *fn = "rf_lstm_sde_noise_reset";
-    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", fn);
     RF_REQUIRE(desc != nullptr && d_params != nullptr && gen != nullptr && d_theta != nullptr, "%s: NULL argument", fn);
     rf::LstmLayout layout;
-    RF_REQUIRE(rf::lstm_sde_layout(*desc, layout), RF_LSTM_SDE_LIMITS, fn, RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_WIDTH);
+    RF_REQUIRE(lstm_layout_any(desc, true, critic, layout), RF_LSTM_SDE_LIMITS, fn, RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_WIDTH);
     RF_REQUIRE(n >= 1 && n <= (1 << 20), "%s: n = %d must be at least 1 (and at most 2^20)", fn, n);
     RF_HIP(hipSetDevice(ctx->device));
     const size_t cells = (size_t)n * (size_t)layout.mlp.sde;
@@ -2398,18 +2440,26 @@ int rf_lstm_sde_noise_reset(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const 
     return RF_OK;
 }
 
-int rf_lstm_sde_forward(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const float *d_params, int n, const float *d_obs,
-                        const uint8_t *d_episode_starts, const float *d_final_obs, const float *d_state_in,
-                        float *d_state_out, const float *d_theta, int flags, float *d_actions, float *d_env_actions,
-                        float *d_log_probs, float *d_values, float *d_final_values, float *d_mean, float *d_sigma,
-                        void *caller_stream)
+int rf_lstm_sde_noise_reset(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const float *d_params, int n,
+                            const unsigned long long gen[4], float *d_theta, void *caller_stream)
 {
-    const char *fn = "rf_lstm_sde_forward";
-    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", fn);
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", "rf_lstm_sde_noise_reset");
+    RF_HIP(hipSetDevice(ctx->device));
+    return lstm_sde_noise_reset_any("rf_lstm_sde_noise_reset", RF_LSTM_CRITIC_LSTM, ctx, desc, d_params, n, gen, d_theta,
+                                    caller_stream);
+}
+
+// rf_lstm_sde_forward and rf_lstm_critic_sde_forward: one body
+static int lstm_sde_forward_any(const char *fn, int critic, rf_ctx *ctx, const rf_lstm_policy_desc *desc,
+                                const float *d_params, int n, const float *d_obs, const uint8_t *d_episode_starts,
+                                const float *d_final_obs, const float *d_state_in, float *d_state_out, const float *d_theta,
+                                int flags, float *d_actions, float *d_env_actions, float *d_log_probs, float *d_values,
+                                float *d_final_values, float *d_mean, float *d_sigma, void *caller_stream)
+{
     RF_REQUIRE(desc != nullptr && d_params != nullptr && d_obs != nullptr && d_episode_starts != nullptr &&
                d_state_in != nullptr, "%s: NULL argument", fn);
     rf::LstmLayout layout;
-    RF_REQUIRE(rf::lstm_sde_layout(*desc, layout), RF_LSTM_SDE_LIMITS, fn, RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_WIDTH);
+    RF_REQUIRE(lstm_layout_any(desc, true, critic, layout), RF_LSTM_SDE_LIMITS, fn, RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_WIDTH);
     RF_REQUIRE(n >= 1 && n <= (1 << 20), "%s: n = %d must be at least 1 (and at most 2^20)", fn, n);
     RF_REQUIRE((flags & ~RF_POLICY_DETERMINISTIC) == 0, "%s: unknown flags %d", fn, flags);
     const bool pi_out = d_actions || d_env_actions || d_log_probs || d_mean || d_sigma;
@@ -2461,10 +2511,12 @@ int rf_lstm_sde_forward(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const floa
                        a.what, b.what);
     }
     // As rf_lstm_forward: one launch on the caller's stream; with d_state_out both cells run, whatever is asked of the heads
+    const bool linear = critic == RF_LSTM_CRITIC_LINEAR;
     const bool pi = pi_out || d_state_out != nullptr;
-    const bool vf = d_values != nullptr || d_final_values != nullptr || d_state_out != nullptr;
+    const bool vf = d_values != nullptr || d_final_values != nullptr || (!linear && d_state_out != nullptr);
     const unsigned tiles = (unsigned)((rows + rf::kPolicyTile - 1) / rf::kPolicyTile);
-    hipLaunchKernelGGL(rf::lstm_forward_kernel<true>, dim3(tiles, pi && vf ? 2u : 1u), dim3(rf::kPolicyThreads), 0,
+    const auto kernel = linear ? rf::lstm_forward_kernel<true, true> : rf::lstm_forward_kernel<true>;
+    hipLaunchKernelGGL(kernel, dim3(tiles, pi && vf ? 2u : 1u), dim3(rf::kPolicyThreads), 0,
                        (hipStream_t)caller_stream, layout, d_params, n, d_obs, d_episode_starts, d_final_obs, d_state_in,
                        d_state_out, rf::PolicyGen{}, 0, pi ? 0 : 1, d_actions, d_log_probs, d_values, d_final_values, d_mean,
                        rf::LstmSde{sampled ? d_theta : nullptr, d_env_actions, d_sigma});
@@ -2472,33 +2524,40 @@ int rf_lstm_sde_forward(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const floa
     return RF_OK;
 }
 
+int rf_lstm_sde_forward(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const float *d_params, int n, const float *d_obs,
+                        const uint8_t *d_episode_starts, const float *d_final_obs, const float *d_state_in,
+                        float *d_state_out, const float *d_theta, int flags, float *d_actions, float *d_env_actions,
+                        float *d_log_probs, float *d_values, float *d_final_values, float *d_mean, float *d_sigma,
+                        void *caller_stream)
+{
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", "rf_lstm_sde_forward");
+    RF_HIP(hipSetDevice(ctx->device));
+    return lstm_sde_forward_any("rf_lstm_sde_forward", RF_LSTM_CRITIC_LSTM, ctx, desc, d_params, n, d_obs, d_episode_starts,
+                                d_final_obs, d_state_in, d_state_out, d_theta, flags, d_actions, d_env_actions, d_log_probs,
+                                d_values, d_final_values, d_mean, d_sigma, caller_stream);
+}
+
 #define RF_LSTM_LIMITS "%s: the desc is outside the limits (obs_width and lstm_hidden 1 .. %d, 1 or 2 hidden layers of width " \
-                       "1 .. %d per net, n_actions 2 .. %d, activation RF_POLICY_RELU or RF_POLICY_TANH)"
+                       "1 .. %d per net, n_actions 2 .. %d, activation RF_POLICY_RELU or RF_POLICY_TANH, critic " \
+                       "RF_LSTM_CRITIC_LSTM or RF_LSTM_CRITIC_LINEAR)"
 
 unsigned long long rf_lstm_ppo_state_size(rf_ctx *ctx, const rf_lstm_policy_desc *desc)
 {
-    rf::LstmLayout layout;
-    if (ctx == nullptr || desc == nullptr || !rf::lstm_layout(*desc, layout))
-        return 0;
-    if (hipSetDevice(ctx->device) != hipSuccess) // (as every entry point; nothing of the device is needed)
+    if (ctx != nullptr && hipSetDevice(ctx->device) != hipSuccess) // (as every entry point; nothing of the device is needed)
         (void)hipGetLastError();
-    return 4ull * rf::kPpoStateHeader + 8ull * layout.total;
+    return lstm_state_size_any(ctx, desc, false, RF_LSTM_CRITIC_LSTM);
 }
 
 unsigned long long rf_lstm_ppo_workspace_size(rf_ctx *ctx, const rf_lstm_policy_desc *desc, int max_batch)
 {
-    rf::LstmLayout layout;
-    rf::LstmPpoWork work;
-    if (ctx == nullptr || desc == nullptr || !rf::lstm_layout(*desc, layout) || !rf::lstm_ppo_work(layout, max_batch, work))
-        return 0;
-    if (hipSetDevice(ctx->device) != hipSuccess)
+    if (ctx != nullptr && hipSetDevice(ctx->device) != hipSuccess)
         (void)hipGetLastError();
-    return 4ull * work.total;
+    return lstm_workspace_size_any(ctx, desc, false, RF_LSTM_CRITIC_LSTM, max_batch);
 }
 
-// rf_lstm_ppo_update and rf_lstm_sde_update: one body; `sde` selects lstm_sde_layout, float32 actions and the Gaussian
-// instantiations of the MLP and gradient kernels
-static int lstm_update_any(const char *fn, bool sde, rf_ctx *ctx, const rf_lstm_policy_desc *desc, const rf_ppo_desc *ppo,
+// rf_lstm_ppo_update, rf_lstm_sde_update and their rf_lstm_critic_ siblings: one body; `sde` selects lstm_sde_layout,
+// float32 actions and the Gaussian instantiations of the MLP and gradient kernels; `critic` the vf net ("lstm critic")
+static int lstm_update_any(const char *fn, bool sde, int critic, rf_ctx *ctx, const rf_lstm_policy_desc *desc, const rf_ppo_desc *ppo,
                            float *d_params, void *d_state, void *d_workspace, int n_steps, int num_envs,
                            const float *d_observations, const void *d_actions, const float *d_log_probs,
                            const float *d_advantages, const float *d_returns, const uint8_t *d_episode_starts,
@@ -2508,9 +2567,10 @@ static int lstm_update_any(const char *fn, bool sde, rf_ctx *ctx, const rf_lstm_
                d_advantages && d_returns && d_episode_starts && d_lstm_states && d_stats, "%s: NULL argument", fn);
     rf::LstmLayout layout;
     if (sde) {
-        RF_REQUIRE(rf::lstm_sde_layout(*desc, layout), RF_LSTM_SDE_LIMITS, fn, RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_WIDTH);
+        RF_REQUIRE(lstm_layout_any(desc, true, critic, layout), RF_LSTM_SDE_LIMITS, fn, RF_POLICY_MAX_WIDTH,
+                   RF_POLICY_MAX_WIDTH);
     } else {
-        RF_REQUIRE(rf::lstm_layout(*desc, layout), RF_LSTM_LIMITS, fn, RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_WIDTH,
+        RF_REQUIRE(lstm_layout_any(desc, false, critic, layout), RF_LSTM_LIMITS, fn, RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_WIDTH,
                    RF_POLICY_MAX_ACTIONS);
     }
     RF_REQUIRE(n_steps >= 1 && num_envs >= 1 && (long long)n_steps * (long long)num_envs <= (1ll << 30),
@@ -2561,20 +2621,25 @@ static int lstm_update_any(const char *fn, bool sde, rf_ctx *ctx, const rf_lstm_
     // caller's stream, nothing allocated, nothing waited for.  The workspace layout is that of B itself.
     float *ws = (float *)d_workspace;
     const dim3 threads(rf::kPpoThreads);
-    hipLaunchKernelGGL(rf::lstm_ppo_forward_kernel, dim3((unsigned)B, 2u), threads, 0, caller, layout, work,
+    // (the linear critic: B pi walks and the vf net's tiles of rows in the first launch, the pi net's BPTT alone in the third)
+    const bool linear = critic == RF_LSTM_CRITIC_LINEAR;
+    const unsigned tiles = (unsigned)((B + rf::kPolicyTile - 1) / rf::kPolicyTile);
+    const unsigned walks = linear ? 1u : 2u;
+    const auto forward = linear ? rf::lstm_ppo_forward_kernel<true> : rf::lstm_ppo_forward_kernel<false>;
+    hipLaunchKernelGGL(forward, dim3((unsigned)B + (linear ? tiles : 0u), walks), threads, 0, caller, layout, work,
                        (const float *)d_params, ws, n_steps, num_envs, d_observations, d_episode_starts, d_lstm_states, first,
                        B);
     RF_HIP(hipGetLastError());
-    const unsigned tiles = (unsigned)((B + rf::kPolicyTile - 1) / rf::kPolicyTile);
     hipLaunchKernelGGL(sde ? rf::lstm_ppo_mlp_kernel<true> : rf::lstm_ppo_mlp_kernel<false>, dim3(tiles, 2u), threads, 0,
                        caller, layout, work, hyper, (const float *)d_params, (const rf::PpoHeader *)d_state, ws, N, d_actions,
                        d_log_probs, d_advantages, d_returns, first, B);
     RF_HIP(hipGetLastError());
-    hipLaunchKernelGGL(rf::lstm_ppo_bptt_kernel, dim3((unsigned)B, 2u), threads, 0, caller, layout, work,
+    hipLaunchKernelGGL(rf::lstm_ppo_bptt_kernel, dim3((unsigned)B, walks), threads, 0, caller, layout, work,
                        (const float *)d_params, ws, n_steps, num_envs, d_episode_starts, first, B);
     RF_HIP(hipGetLastError());
-    hipLaunchKernelGGL(sde ? rf::lstm_ppo_gradient_kernel<true> : rf::lstm_ppo_gradient_kernel<false>,
-                       dim3(work.mlp.partials), threads, 0, caller, layout, work, ws, B, (const float *)d_params);
+    const auto gradient = linear ? (sde ? rf::lstm_ppo_gradient_kernel<true, true> : rf::lstm_ppo_gradient_kernel<false, true>)
+                                 : (sde ? rf::lstm_ppo_gradient_kernel<true> : rf::lstm_ppo_gradient_kernel<false>);
+    hipLaunchKernelGGL(gradient, dim3(work.mlp.partials), threads, 0, caller, layout, work, ws, B, (const float *)d_params);
     RF_HIP(hipGetLastError());
     hipLaunchKernelGGL(rf::lstm_ppo_norm_kernel, dim3(work.supers), dim3(rf::kLstmPpoGroup), 0, caller, work, ws);
     RF_HIP(hipGetLastError());
@@ -2593,31 +2658,23 @@ int rf_lstm_ppo_update(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const rf_pp
 {
     RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", "rf_lstm_ppo_update");
     RF_HIP(hipSetDevice(ctx->device));
-    return lstm_update_any("rf_lstm_ppo_update", false, ctx, desc, ppo, d_params, d_state, d_workspace, n_steps, num_envs,
+    return lstm_update_any("rf_lstm_ppo_update", false, RF_LSTM_CRITIC_LSTM, ctx, desc, ppo, d_params, d_state, d_workspace, n_steps, num_envs,
                            d_observations, d_actions, d_log_probs, d_advantages, d_returns, d_episode_starts, d_lstm_states,
                            first, B, d_stats, caller_stream);
 }
 
 unsigned long long rf_lstm_sde_state_size(rf_ctx *ctx, const rf_lstm_policy_desc *desc)
 {
-    rf::LstmLayout layout;
-    if (ctx == nullptr || desc == nullptr || !rf::lstm_sde_layout(*desc, layout))
-        return 0;
-    if (hipSetDevice(ctx->device) != hipSuccess) // (as every entry point; nothing of the device is needed)
+    if (ctx != nullptr && hipSetDevice(ctx->device) != hipSuccess) // (as every entry point; nothing of the device is needed)
         (void)hipGetLastError();
-    return 4ull * rf::kPpoStateHeader + 8ull * layout.total;
+    return lstm_state_size_any(ctx, desc, true, RF_LSTM_CRITIC_LSTM);
 }
 
 unsigned long long rf_lstm_sde_workspace_size(rf_ctx *ctx, const rf_lstm_policy_desc *desc, int max_batch)
 {
-    rf::LstmLayout layout;
-    rf::LstmPpoWork work;
-    if (ctx == nullptr || desc == nullptr || !rf::lstm_sde_layout(*desc, layout) ||
-        !rf::lstm_ppo_work(layout, max_batch, work))
-        return 0;
-    if (hipSetDevice(ctx->device) != hipSuccess)
+    if (ctx != nullptr && hipSetDevice(ctx->device) != hipSuccess)
         (void)hipGetLastError();
-    return 4ull * work.total;
+    return lstm_workspace_size_any(ctx, desc, true, RF_LSTM_CRITIC_LSTM, max_batch);
 }
 
 int rf_lstm_sde_update(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const rf_ppo_desc *ppo, float *d_params, void *d_state,
@@ -2628,9 +2685,117 @@ int rf_lstm_sde_update(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const rf_pp
 {
     RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", "rf_lstm_sde_update");
     RF_HIP(hipSetDevice(ctx->device));
-    return lstm_update_any("rf_lstm_sde_update", true, ctx, desc, ppo, d_params, d_state, d_workspace, n_steps, num_envs,
+    return lstm_update_any("rf_lstm_sde_update", true, RF_LSTM_CRITIC_LSTM, ctx, desc, ppo, d_params, d_state, d_workspace, n_steps, num_envs,
                            d_observations, d_actions, d_log_probs, d_advantages, d_returns, d_episode_starts, d_lstm_states,
                            first, B, d_stats, caller_stream);
+}
+
+// ---- "lstm critic": the siblings over rf_lstm_critic_desc -- thin wrappers around the bodies above --------------------------
+unsigned long long rf_lstm_critic_params_size(rf_ctx *ctx, const rf_lstm_critic_desc *desc)
+{
+    if (ctx != nullptr && hipSetDevice(ctx->device) != hipSuccess) // (as every entry point; nothing of the device is needed)
+        (void)hipGetLastError();
+    return desc == nullptr ? 0 : lstm_params_size_any(ctx, &desc->lstm, false, desc->critic);
+}
+
+int rf_lstm_critic_forward(rf_ctx *ctx, const rf_lstm_critic_desc *desc, const float *d_params, int n, const float *d_obs,
+                           const uint8_t *d_episode_starts, const float *d_final_obs, const float *d_state_in,
+                           float *d_state_out, const unsigned long long gen[4], int flags, long long *d_actions,
+                           float *d_log_probs, float *d_values, float *d_final_values, float *d_logits, void *caller_stream)
+{
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", "rf_lstm_critic_forward");
+    RF_REQUIRE(desc != nullptr, "%s: NULL argument", "rf_lstm_critic_forward");
+    RF_HIP(hipSetDevice(ctx->device));
+    return lstm_forward_any("rf_lstm_critic_forward", desc->critic, ctx, &desc->lstm, d_params, n, d_obs, d_episode_starts,
+                            d_final_obs, d_state_in, d_state_out, gen, flags, d_actions, d_log_probs, d_values,
+                            d_final_values, d_logits, caller_stream);
+}
+
+unsigned long long rf_lstm_critic_ppo_state_size(rf_ctx *ctx, const rf_lstm_critic_desc *desc)
+{
+    if (ctx != nullptr && hipSetDevice(ctx->device) != hipSuccess)
+        (void)hipGetLastError();
+    return desc == nullptr ? 0 : lstm_state_size_any(ctx, &desc->lstm, false, desc->critic);
+}
+
+unsigned long long rf_lstm_critic_ppo_workspace_size(rf_ctx *ctx, const rf_lstm_critic_desc *desc, int max_batch)
+{
+    if (ctx != nullptr && hipSetDevice(ctx->device) != hipSuccess)
+        (void)hipGetLastError();
+    return desc == nullptr ? 0 : lstm_workspace_size_any(ctx, &desc->lstm, false, desc->critic, max_batch);
+}
+
+int rf_lstm_critic_ppo_update(rf_ctx *ctx, const rf_lstm_critic_desc *desc, const rf_ppo_desc *ppo, float *d_params,
+                              void *d_state, void *d_workspace, int n_steps, int num_envs, const float *d_observations,
+                              const long long *d_actions, const float *d_log_probs, const float *d_advantages,
+                              const float *d_returns, const uint8_t *d_episode_starts, const float *d_lstm_states, int first,
+                              int B, float *d_stats, void *caller_stream)
+{
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", "rf_lstm_critic_ppo_update");
+    RF_REQUIRE(desc != nullptr, "%s: NULL argument", "rf_lstm_critic_ppo_update");
+    RF_HIP(hipSetDevice(ctx->device));
+    return lstm_update_any("rf_lstm_critic_ppo_update", false, desc->critic, ctx, &desc->lstm, ppo, d_params, d_state,
+                           d_workspace, n_steps, num_envs, d_observations, d_actions, d_log_probs, d_advantages, d_returns,
+                           d_episode_starts, d_lstm_states, first, B, d_stats, caller_stream);
+}
+
+unsigned long long rf_lstm_critic_sde_params_size(rf_ctx *ctx, const rf_lstm_critic_desc *desc)
+{
+    if (ctx != nullptr && hipSetDevice(ctx->device) != hipSuccess)
+        (void)hipGetLastError();
+    return desc == nullptr ? 0 : lstm_params_size_any(ctx, &desc->lstm, true, desc->critic);
+}
+
+int rf_lstm_critic_sde_noise_reset(rf_ctx *ctx, const rf_lstm_critic_desc *desc, const float *d_params, int n,
+                                   const unsigned long long gen[4], float *d_theta, void *caller_stream)
+{
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", "rf_lstm_critic_sde_noise_reset");
+    RF_REQUIRE(desc != nullptr, "%s: NULL argument", "rf_lstm_critic_sde_noise_reset");
+    RF_HIP(hipSetDevice(ctx->device));
+    return lstm_sde_noise_reset_any("rf_lstm_critic_sde_noise_reset", desc->critic, ctx, &desc->lstm, d_params, n, gen,
+                                    d_theta, caller_stream);
+}
+
+int rf_lstm_critic_sde_forward(rf_ctx *ctx, const rf_lstm_critic_desc *desc, const float *d_params, int n, const float *d_obs,
+                               const uint8_t *d_episode_starts, const float *d_final_obs, const float *d_state_in,
+                               float *d_state_out, const float *d_theta, int flags, float *d_actions, float *d_env_actions,
+                               float *d_log_probs, float *d_values, float *d_final_values, float *d_mean, float *d_sigma,
+                               void *caller_stream)
+{
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", "rf_lstm_critic_sde_forward");
+    RF_REQUIRE(desc != nullptr, "%s: NULL argument", "rf_lstm_critic_sde_forward");
+    RF_HIP(hipSetDevice(ctx->device));
+    return lstm_sde_forward_any("rf_lstm_critic_sde_forward", desc->critic, ctx, &desc->lstm, d_params, n, d_obs,
+                                d_episode_starts, d_final_obs, d_state_in, d_state_out, d_theta, flags, d_actions,
+                                d_env_actions, d_log_probs, d_values, d_final_values, d_mean, d_sigma, caller_stream);
+}
+
+unsigned long long rf_lstm_critic_sde_state_size(rf_ctx *ctx, const rf_lstm_critic_desc *desc)
+{
+    if (ctx != nullptr && hipSetDevice(ctx->device) != hipSuccess)
+        (void)hipGetLastError();
+    return desc == nullptr ? 0 : lstm_state_size_any(ctx, &desc->lstm, true, desc->critic);
+}
+
+unsigned long long rf_lstm_critic_sde_workspace_size(rf_ctx *ctx, const rf_lstm_critic_desc *desc, int max_batch)
+{
+    if (ctx != nullptr && hipSetDevice(ctx->device) != hipSuccess)
+        (void)hipGetLastError();
+    return desc == nullptr ? 0 : lstm_workspace_size_any(ctx, &desc->lstm, true, desc->critic, max_batch);
+}
+
+int rf_lstm_critic_sde_update(rf_ctx *ctx, const rf_lstm_critic_desc *desc, const rf_ppo_desc *ppo, float *d_params,
+                              void *d_state, void *d_workspace, int n_steps, int num_envs, const float *d_observations,
+                              const float *d_actions, const float *d_log_probs, const float *d_advantages,
+                              const float *d_returns, const uint8_t *d_episode_starts, const float *d_lstm_states, int first,
+                              int B, float *d_stats, void *caller_stream)
+{
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", "rf_lstm_critic_sde_update");
+    RF_REQUIRE(desc != nullptr, "%s: NULL argument", "rf_lstm_critic_sde_update");
+    RF_HIP(hipSetDevice(ctx->device));
+    return lstm_update_any("rf_lstm_critic_sde_update", true, desc->critic, ctx, &desc->lstm, ppo, d_params, d_state,
+                           d_workspace, n_steps, num_envs, d_observations, d_actions, d_log_probs, d_advantages, d_returns,
+                           d_episode_starts, d_lstm_states, first, B, d_stats, caller_stream);
 }
 
 } // extern "C"

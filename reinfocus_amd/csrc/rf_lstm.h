@@ -12,6 +12,10 @@
 // as the MLP's input, and from there on the block runs policy_hidden_tile, policy_dot and policy_head unchanged.  The vf
 // block's pass over final_obs runs FIRST: it reads state_in, which the pass over obs may overwrite in place.  No atomics;
 // the ragged last tile computes on zeros and stores nothing.
+// "lstm critic" (enable_critic_lstm=False) is the kLinear instantiation: its vf block runs ONE linear layer D -> H in
+// policy_hidden_tile's organisation without an activation (lstm_linear_tile) in place of the cell -- it loads no h and no
+// c and reads neither the state nor the episode starts --, and its pi block stores h' and c' into both halves of the
+// state.  The instantiations with the LSTM critic are compiled from the same text with every such branch folded away.
 // LstmLayout and lstm_layout are plain C++: tests/lstmcheck packs its host loop by the same offsets.
 #pragma once
 
@@ -22,20 +26,28 @@
 namespace rf {
 
 // A checked rf_lstm_policy_desc as the kernel reads it: offsets in floats into the parameters.  Per net (pi, then vf):
-// W_ih^T [D][4H], W_hh^T [H][4H], b_ih [4H], b_hh [4H], then what "policy" packs for that net with input width H
+// W_ih^T [D][4H], W_hh^T [H][4H], b_ih [4H], b_hh [4H], then what "policy" packs for that net with input width H.
+// critic == kLstmCriticLinear ("lstm critic"): the vf net has critic.weight^T [D][H] at w_ih[1] and critic.bias [H] at
+// b_ih[1] in place of its cell; w_hh[1] and b_hh[1] are b_ih[1] and name nothing.
+constexpr int kLstmCriticLstm = RF_LSTM_CRITIC_LSTM, kLstmCriticLinear = RF_LSTM_CRITIC_LINEAR;
+
 struct LstmLayout {
     PolicyLayout mlp; // the two MLPs and their heads (obs_width = lstm_hidden), offsets into the whole array
     int obs_width, hidden;
     unsigned w_ih[2], w_hh[2], b_ih[2], b_hh[2];
     unsigned total;
+    int critic; // kLstmCriticLstm or kLstmCriticLinear (no instantiation with the LSTM critic reads it)
 };
 
-// The packing of both heads: `sde` packs the MLPs by sde_layout (a pi head of one output, log_std last of everything)
-RF_HD bool lstm_layout_nets(const rf_lstm_policy_desc &d, LstmLayout &p, bool sde)
+// The packing of both heads: `sde` packs the MLPs by sde_layout (a pi head of one output, log_std last of everything);
+// `critic` is rf_lstm_critic_desc's (any value but the two modes is refused)
+RF_HD bool lstm_layout_nets(const rf_lstm_policy_desc &d, LstmLayout &p, bool sde, int critic)
 {
     p = LstmLayout{};
     const int D = d.policy.obs_width, H = d.lstm_hidden;
     if (D < 1 || D > kPolicyMaxWidth || H < 1 || H > kPolicyMaxWidth)
+        return false;
+    if (critic != kLstmCriticLstm && critic != kLstmCriticLinear)
         return false;
     rf_policy_desc mlp = d.policy;
     mlp.obs_width = H;
@@ -45,23 +57,37 @@ RF_HD bool lstm_layout_nets(const rf_lstm_policy_desc &d, LstmLayout &p, bool sd
     p.hidden = H;
     const unsigned gates = 4u * (unsigned)H;
     const unsigned cell = gates * (unsigned)(D + H) + 2u * gates;
+    const bool linear = critic == kLstmCriticLinear;
+    const unsigned cells = cell + (linear ? (unsigned)(D * H + H) : cell); // (what precedes the vf MLP beyond the pi MLP)
     const unsigned pi_mlp = p.mlp.weight[1][0]; // (policy_layout packs the pi MLP first, from 0)
     for (int net = 0; net < 2; ++net) {
         const unsigned base = net == 0 ? 0u : cell + pi_mlp;
         p.w_ih[net] = base;
-        p.w_hh[net] = p.w_ih[net] + (unsigned)D * gates;
-        p.b_ih[net] = p.w_hh[net] + (unsigned)H * gates;
-        p.b_hh[net] = p.b_ih[net] + gates;
+        if (net == 1 && linear) {
+            p.b_ih[net] = base + (unsigned)(D * H);
+            p.w_hh[net] = p.b_hh[net] = p.b_ih[net];
+        } else {
+            p.w_hh[net] = p.w_ih[net] + (unsigned)D * gates;
+            p.b_ih[net] = p.w_hh[net] + (unsigned)H * gates;
+            p.b_hh[net] = p.b_ih[net] + gates;
+        }
         for (int l = 0; l <= p.mlp.layers[net]; ++l) {
-            p.mlp.weight[net][l] += (unsigned)(net + 1) * cell;
-            p.mlp.bias[net][l] += (unsigned)(net + 1) * cell;
+            p.mlp.weight[net][l] += net == 0 ? cell : cells;
+            p.mlp.bias[net][l] += net == 0 ? cell : cells;
         }
     }
-    p.total = p.mlp.total + 2u * cell;
+    p.total = p.mlp.total + cells;
     p.mlp.total = p.total;
     if (sde)
-        p.mlp.log_std += 2u * cell; // (past both nets of the whole array)
+        p.mlp.log_std += cells; // (past both nets of the whole array)
+    p.critic = critic;
     return true;
+}
+
+// ... with the LSTM critic, as before "lstm critic"
+RF_HD bool lstm_layout_nets(const rf_lstm_policy_desc &d, LstmLayout &p, bool sde)
+{
+    return lstm_layout_nets(d, p, sde, kLstmCriticLstm);
 }
 
 // false: desc is outside the limits of the definition
@@ -148,9 +174,44 @@ template <> struct LstmSdeOf<true> {
     using type = LstmSde;
 };
 
+// "lstm critic" C2 for a block's tile: out[j][e] = bias[j] + sum over k in index order of in[k][e] * W^T[k][j], no
+// activation -- policy_hidden_tile's organisation (thread j < H owns unit j, one accumulator per row of the tile; in / out
+// are [k][tile] in LDS).  The caller puts a barrier after it.
+__device__ __forceinline__ void lstm_linear_tile(const float *__restrict__ params, unsigned weight, unsigned bias, int K,
+                                                 int H, const float (*in)[kPolicyTile], float (*out)[kPolicyTile], int tid)
+{
+    if (tid < H) {
+        const float *__restrict__ w = params + weight + tid;
+        const float b = params[bias + tid];
+        float acc[kPolicyTile];
+#pragma unroll
+        for (int e = 0; e < kPolicyTile; ++e)
+            acc[e] = b;
+#pragma unroll 8
+        for (int k = 0; k < K; ++k) { // (unrolled: 8 independent weight loads in flight per round of latency)
+            const float wk = w[(size_t)k * (size_t)H];
+            const float4 *x = reinterpret_cast<const float4 *>(&in[k][0]);
+            float xs[kPolicyTile];
+#pragma unroll
+            for (int v = 0; v < kPolicyTile / 4; ++v) {
+                const float4 q = x[v];
+                xs[4 * v] = q.x, xs[4 * v + 1] = q.y, xs[4 * v + 2] = q.z, xs[4 * v + 3] = q.w;
+            }
+#pragma unroll
+            for (int e = 0; e < kPolicyTile; ++e)
+                acc[e] = acc[e] + xs[e] * wk;
+        }
+#pragma unroll
+        for (int e = 0; e < kPolicyTile; ++e)
+            out[tid][e] = acc[e];
+    }
+}
+
 // kSde: the Gaussian head of "lstm sde policy" (L from lstm_sde_layout) in place of the Categorical one.  actions_any is
 // then float32 [n] (the raw actions) and `logits` receives the mean.
-template <bool kSde>
+// kLinear: "lstm critic" (L.critic == kLstmCriticLinear): the vf block is the linear layer, the pi block stores both halves
+// of the state; a launch asks for the vf block only where a value is wanted.
+template <bool kSde, bool kLinear = false>
 __global__ __launch_bounds__(kPolicyThreads) void lstm_forward_kernel(
     LstmLayout L, const float *__restrict__ params, int n, const float *__restrict__ obs,
     const uint8_t *__restrict__ starts, const float *__restrict__ final_obs /* or null */, const float *state_in,
@@ -176,7 +237,7 @@ __global__ __launch_bounds__(kPolicyThreads) void lstm_forward_kernel(
         bool heads = pass == 1 || (net == 0 ? actions != nullptr || logits != nullptr : values != nullptr);
         if constexpr (kSde) // (each pi output of the Gaussian head may be asked for by itself)
             heads = heads || (net == 0 && (env_actions != nullptr || log_probs != nullptr || sigma != nullptr));
-        if (!heads && state_out == nullptr)
+        if (!heads && (state_out == nullptr || (kLinear && net == 1))) // (the linear critic has no state to advance)
             continue;
         const float *__restrict__ in = pass == 0 ? obs : final_obs;
         // the tile's rows are consecutive in memory: element i of the tile is row i / D, column i % D
@@ -184,14 +245,17 @@ __global__ __launch_bounds__(kPolicyThreads) void lstm_forward_kernel(
             const int e = i / D, k = i - e * D;
             s_x[k][e] = e0 + e < n ? in[(size_t)e0 * (size_t)D + (size_t)i] : 0.0f;
         }
-        for (int i = tid; i < H * kPolicyTile; i += kPolicyThreads) {
-            const int e = i / H, k = i - e * H, env = e0 + e;
-            // an episode start replaces the state by +0: a select, so no NaN or inf of a dead state survives it
-            const bool kept = env < n && (pass == 1 || starts[env] == 0);
-            s_act[1][k][e] = kept ? state_in[lstm_state_at(net, 0, n, H, env, k)] : 0.0f;
-        }
+        if (!(kLinear && net == 1)) // (the linear critic reads neither the state nor the episode starts)
+            for (int i = tid; i < H * kPolicyTile; i += kPolicyThreads) {
+                const int e = i / H, k = i - e * H, env = e0 + e;
+                // an episode start replaces the state by +0: a select, so no NaN or inf of a dead state survives it
+                const bool kept = env < n && (pass == 1 || starts[env] == 0);
+                s_act[1][k][e] = kept ? state_in[lstm_state_at(net, 0, n, H, env, k)] : 0.0f;
+            }
         __syncthreads();
-        if (tid < H) {
+        if (kLinear && net == 1) {
+            lstm_linear_tile(params, L.w_ih[1], L.b_ih[1], D, H, s_x, s_act[0], tid);
+        } else if (tid < H) {
             float acc[4][kPolicyTile];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -214,6 +278,10 @@ __global__ __launch_bounds__(kPolicyThreads) void lstm_forward_kernel(
                 if (pass == 0 && state_out != nullptr && env < n) {
                     state_out[lstm_state_at(net, 0, n, H, env, tid)] = policy_canonical(h1);
                     state_out[lstm_state_at(net, 1, n, H, env, tid)] = policy_canonical(c1);
+                    if constexpr (kLinear) { // (net == 0: sb3-contrib's lstm_states_vf = lstm_states_pi; nothing reads it)
+                        state_out[lstm_state_at(1, 0, n, H, env, tid)] = policy_canonical(h1);
+                        state_out[lstm_state_at(1, 1, n, H, env, tid)] = policy_canonical(c1);
+                    }
                 }
             }
         }

@@ -28,6 +28,13 @@
 // every da, and the norm every gradient -- each a dependency between blocks, and there is no grid synchronisation here.
 // No atomics, nothing allocated, nothing waited for.  The scalar arithmetic is plain C++ (RF_HD): tests/lstmppocheck
 // loops over the same functions on the host.
+// "lstm critic" (L.critic == kLstmCriticLinear: a feed-forward critic) keeps the six launches and drops one of the two
+// walks and one of the two BPTTs: lstm_ppo_forward_kernel<true> has a grid of B + ceil(B / 8) blocks, the first B walk the
+// pi sequences as before and the others each take a tile of kPolicyTile rows of the vf net's linear layer (no sequence
+// scan, no state: rows are independent) and leave it as h1[1]; lstm_ppo_mlp_kernel is unchanged, its dh[1] is then the
+// delta of the linear layer's output; lstm_ppo_bptt_kernel is launched for the pi net only; lstm_ppo_gradient_kernel<.,
+// true> reads lstm_ppo_source_critic, which knows critic.weight^T and critic.bias.  The workspace has no h_prev, c_prev,
+// gates, c' or da of the vf net.  The instantiations with the LSTM critic keep the code they had.
 #pragma once
 
 #include "rf_lstm.h"
@@ -58,6 +65,7 @@ struct LstmPpoWork {
     unsigned total;
 };
 
+// (with L.critic == kLstmCriticLinear the vf net has h1 and dh only; its other offsets stay 0 and name nothing)
 RF_HD bool lstm_ppo_work(const LstmLayout &L, int max_batch, LstmPpoWork &w)
 {
     w = LstmPpoWork{};
@@ -91,13 +99,17 @@ RF_HD bool lstm_ppo_work(const LstmLayout &L, int max_batch, LstmPpoWork &w)
     w.super = take(2 * w.supers);
     w.x = take(rows * (unsigned)L.obs_width);
     for (int net = 0; net < 2; ++net) {
-        w.h_prev[net] = take(rows * H);
-        w.c_prev[net] = take(rows * H);
-        w.gates[net] = take(rows * 4u * H);
-        w.c1[net] = take(rows * H);
+        const bool cell = net == 0 || L.critic != kLstmCriticLinear;
+        if (cell) {
+            w.h_prev[net] = take(rows * H);
+            w.c_prev[net] = take(rows * H);
+            w.gates[net] = take(rows * 4u * H);
+            w.c1[net] = take(rows * H);
+        }
         w.h1[net] = take(rows * H);
         w.dh[net] = take(rows * H);
-        w.da[net] = take(rows * 4u * H);
+        if (cell)
+            w.da[net] = take(rows * 4u * H);
     }
     if (M.sde != 0) // (lstm_sde_layout only; taken last, so every other offset is the Categorical layout's)
         w.mlp.sde = take(rows);
@@ -240,13 +252,51 @@ RF_HD PpoSource lstm_ppo_source_nets(const LstmLayout &L, const LstmPpoWork &W, 
     return s; // (p past both nets: no caller asks)
 }
 
+// "lstm critic" C7: lstm_ppo_source_nets with the two pieces of the vf net's linear layer in place of its cell --
+// critic.weight^T [D][H] from the observations and dh[1] (the delta of the layer's output), critic.bias [H] from dh[1]
+RF_HD PpoSource lstm_ppo_source_critic(const LstmLayout &L, const LstmPpoWork &W, unsigned p)
+{
+    const PolicyLayout &M = L.mlp;
+    const int D = L.obs_width, H = L.hidden;
+    if (p < L.w_ih[1])
+        return lstm_ppo_source_nets(L, W, p); // (the pi net, packed first: its cell, MLP and head)
+    PpoSource s{};
+    if (p < L.b_ih[1] + (unsigned)H) { // the linear layer: critic.weight^T, critic.bias
+        s.d = W.dh[1], s.d_stride = H;
+        if (p < L.b_ih[1]) {
+            const unsigned at = p - L.w_ih[1];
+            s.x = W.x, s.x_stride = D, s.k = (int)(at / (unsigned)H), s.j = (int)(at % (unsigned)H);
+        } else {
+            s.k = -1, s.j = (int)(p - L.b_ih[1]);
+        }
+        return s;
+    }
+    for (int l = 0; l <= M.layers[1]; ++l) { // the vf MLP and head, with the layer's output h1[1] as the first input
+        const int out = l < M.layers[1] ? M.width[1][l] : 1;
+        if (p >= M.bias[1][l] + (unsigned)out)
+            continue;
+        s.d = W.mlp.d[1][l], s.d_stride = out;
+        s.x = l == 0 ? W.h1[1] : W.mlp.h[1][l - 1];
+        s.x_stride = l == 0 ? H : M.width[1][l - 1];
+        if (p >= M.bias[1][l]) {
+            s.k = -1, s.j = (int)(p - M.bias[1][l]);
+        } else {
+            const unsigned at = p - M.weight[1][l];
+            s.k = (int)(at / (unsigned)out), s.j = (int)(at % (unsigned)out);
+        }
+        return s;
+    }
+    return s; // (p past both nets: no caller asks)
+}
+
 // ... and over everything packed, p < L.total: past both nets (lstm_sde_layout only) log_std_j of the Gaussian head gets
-// it from the last pi activations and the per-row sigma terms (k == -2, as ppo_source)
-RF_HD PpoSource lstm_ppo_source(const LstmLayout &L, const LstmPpoWork &W, unsigned p)
+// it from the last pi activations and the per-row sigma terms (k == -2, as ppo_source).  kLinear: the critic mode, a
+// compile-time constant for the kernels; lstm_ppo_source below reads it from the layout for the host.
+template <bool kLinear> RF_HD PpoSource lstm_ppo_source_of(const LstmLayout &L, const LstmPpoWork &W, unsigned p)
 {
     const PolicyLayout &M = L.mlp;
     if (M.sde == 0 || p < M.log_std)
-        return lstm_ppo_source_nets(L, W, p);
+        return kLinear ? lstm_ppo_source_critic(L, W, p) : lstm_ppo_source_nets(L, W, p);
     PpoSource s{};
     s.k = -2, s.j = (int)(p - M.log_std);
     s.x = W.mlp.h[0][M.layers[0] - 1], s.x_stride = (int)M.sde;
@@ -254,12 +304,25 @@ RF_HD PpoSource lstm_ppo_source(const LstmLayout &L, const LstmPpoWork &W, unsig
     return s;
 }
 
+RF_HD PpoSource lstm_ppo_source(const LstmLayout &L, const LstmPpoWork &W, unsigned p)
+{
+    return L.critic == kLstmCriticLinear ? lstm_ppo_source_of<true>(L, W, p) : lstm_ppo_source_of<false>(L, W, p);
+}
+
 // Definition step U8 for one packed parameter (params: for std2_j of a log_std entry)
+template <bool kLinear>
+RF_HD float lstm_ppo_parameter_gradient_of(const LstmLayout &L, const LstmPpoWork &W, const float *ws, const float *params,
+                                           unsigned p, int B)
+{
+    const PpoSource s = lstm_ppo_source_of<kLinear>(L, W, p);
+    return s.k == -2 ? sde_log_std_gradient(ws, s, B, sde_std2(params[L.mlp.log_std + (unsigned)s.j])) : ppo_gradient(ws, s, B);
+}
+
 RF_HD float lstm_ppo_parameter_gradient(const LstmLayout &L, const LstmPpoWork &W, const float *ws, const float *params,
                                         unsigned p, int B)
 {
-    const PpoSource s = lstm_ppo_source(L, W, p);
-    return s.k == -2 ? sde_log_std_gradient(ws, s, B, sde_std2(params[L.mlp.log_std + (unsigned)s.j])) : ppo_gradient(ws, s, B);
+    return L.critic == kLstmCriticLinear ? lstm_ppo_parameter_gradient_of<true>(L, W, ws, params, p, B)
+                                         : lstm_ppo_parameter_gradient_of<false>(L, W, ws, params, p, B);
 }
 
 #if defined(__HIPCC__)
@@ -293,10 +356,30 @@ __device__ __forceinline__ void lstm_gates_row(const float *__restrict__ params,
     }
 }
 
+// kLinear: "lstm critic" -- the grid is B + ceil(B / kPolicyTile) blocks by 1: block b < B walks the pi sequence that
+// starts at row b, block B + i takes rows [8 i, 8 i + 8) of the vf net's linear layer
+template <bool kLinear = false>
 __global__ __launch_bounds__(kPpoThreads) void lstm_ppo_forward_kernel(
     LstmLayout L, LstmPpoWork W, const float *__restrict__ params, float *__restrict__ ws, int T, int n,
     const float *__restrict__ obs, const uint8_t *__restrict__ starts, const float *__restrict__ states, int first, int B)
 {
+    if constexpr (kLinear) {
+        if ((int)blockIdx.x >= B) { // (block-uniform)
+            __shared__ __align__(16) float s_in[kPolicyMaxWidth][kPolicyTile];  // the tile's observations, [k][row]
+            __shared__ __align__(16) float s_out[kPolicyMaxWidth][kPolicyTile]; // the layer's outputs, [j][row]
+            const int tid = threadIdx.x, D = L.obs_width, H = L.hidden, N = T * n;
+            const int b0 = ((int)blockIdx.x - B) * kPolicyTile;
+            for (int i = tid; i < D * kPolicyTile; i += kPpoThreads) { // (the ragged tile computes on zeros, stores nothing)
+                const int e = i / D, k = i - e * D;
+                s_in[k][e] = b0 + e < B ? obs[(size_t)lstm_ppo_row(first, b0 + e, N) * (size_t)D + (size_t)k] : 0.0f;
+            }
+            __syncthreads();
+            lstm_linear_tile(params, L.w_ih[1], L.b_ih[1], D, H, s_in, s_out, tid);
+            __syncthreads();
+            ppo_store_tile(ws + W.h1[1], s_out, H, b0, B, tid);
+            return;
+        }
+    }
     __shared__ float s_x[kPolicyMaxWidth];
     __shared__ float s_h[kPolicyMaxWidth];
     const int b0 = (int)blockIdx.x, net = (int)blockIdx.y, tid = threadIdx.x;
@@ -564,7 +647,8 @@ __global__ __launch_bounds__(kPpoThreads) void lstm_ppo_bptt_kernel(LstmLayout L
 }
 
 // kSde: the threads past both nets sum the log_std gradients (sde_log_std_gradient, which needs params for std2_j)
-template <bool kSde>
+// kLinear: "lstm critic" -- the sources of lstm_ppo_source_critic
+template <bool kSde, bool kLinear = false>
 __global__ __launch_bounds__(kPpoThreads) void lstm_ppo_gradient_kernel(LstmLayout L, LstmPpoWork W, float *__restrict__ ws,
                                                                         int B, const float *__restrict__ params)
 {
@@ -573,8 +657,14 @@ __global__ __launch_bounds__(kPpoThreads) void lstm_ppo_gradient_kernel(LstmLayo
     const unsigned p = blockIdx.x * (unsigned)kPpoLeaves + (unsigned)tid;
     double square = 0.0;
     if (p < L.total) {
-        const float g = policy_canonical(kSde ? lstm_ppo_parameter_gradient(L, W, ws, params, p, B)
-                                              : ppo_gradient(ws, lstm_ppo_source_nets(L, W, p), B));
+        float raw;
+        if constexpr (kSde)
+            raw = lstm_ppo_parameter_gradient_of<kLinear>(L, W, ws, params, p, B);
+        else if constexpr (kLinear)
+            raw = ppo_gradient(ws, lstm_ppo_source_critic(L, W, p), B);
+        else
+            raw = ppo_gradient(ws, lstm_ppo_source_nets(L, W, p), B);
+        const float g = policy_canonical(raw);
         ws[W.mlp.grad + p] = g;
         square = (double)g * (double)g;
     }

@@ -15,8 +15,10 @@ multiplies the state by (1 - start).
     DeviceLstmPolicy the same over torch tensors on a device-resident environment's GPU: one launch per call
 
 The update (back-propagation through time) is environments/lstm_learner.py; the Gaussian (sde) head on top of the LSTM
-(Box action spaces) is environments/lstm_sde.py.  Out of scope, and refused or absent: n_lstm_layers > 1,
-shared_lstm=True, enable_critic_lstm=False.
+(Box action spaces) is environments/lstm_sde.py.  enable_critic_lstm=False (sb3-contrib's keyword, which rl_zoo3's sampler
+draws in half of its trials) is the spec's: the vf net is then critic = nn.Linear(D, H) in front of its MLP, with no state
+and no episode-start mask ("lstm critic"), and every class here works from the spec.  Out of scope, and refused or absent:
+n_lstm_layers > 1, shared_lstm=True, lstm_hidden > 256.
 
 torch is imported lazily, by DeviceLstmPolicy only (reinfocus_amd/torch_interop.py says why import order matters).
 """
@@ -29,6 +31,26 @@ from reinfocus_amd.environments.policy import (DETERMINISTIC, MAX_WIDTH, _NAN, _
                                                head, linear, tanh32)
 
 LSTM_PARTS = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")
+CRITIC_LSTM, CRITIC_LINEAR = 0, 1  # RF_LSTM_CRITIC_LSTM, RF_LSTM_CRITIC_LINEAR
+
+
+def recurrent_entries(obs_width, hidden, pi_entries, vf_entries, enable_critic_lstm):
+    """(entries, size) of both nets: per net (pi first) the LSTM -- or, for the vf net of enable_critic_lstm=False,
+    critic.weight^T [D][H] and critic.bias [H] -- then the net's own MLP entries, moved to where they are packed."""
+    entries, at = [], 0
+    lstm_shapes = ((obs_width, 4 * hidden), (hidden, 4 * hidden), (4 * hidden,), (4 * hidden,))
+    for lstm, own in (("lstm_actor", pi_entries), ("lstm_critic", vf_entries)):
+        if lstm == "lstm_critic" and not enable_critic_lstm:
+            first = (("critic.weight", (obs_width, hidden)), ("critic.bias", (hidden,)))
+        else:
+            first = tuple((f"{lstm}.{part}", shape) for part, shape in zip(LSTM_PARTS, lstm_shapes))
+        for name, shape in first:
+            entries.append((name, at, shape, len(shape) == 2))
+            at += int(np.prod(shape))
+        for name, _, shape, is_weight in own:
+            entries.append((name, at, shape, is_weight))
+            at += int(np.prod(shape))
+    return entries, at
 
 
 def sigmoid32(x):
@@ -68,11 +90,14 @@ def lstm_layer(x, h, c, w_ih_t, w_hh_t, b_ih, b_hh):
 class LstmPolicySpec(policy_module.MlpPolicySpec):
     """The shape of the recurrent network and the packing rule of its parameters.  Packed: one float32 vector, every
     matrix transposed ([in][out]), per net (pi first): W_ih^T [D][4H], W_hh^T [H][4H], b_ih, b_hh, then the net's MLP and
-    head as MlpPolicySpec packs them with input width H."""
+    head as MlpPolicySpec packs them with input width H.  enable_critic_lstm=False ("lstm critic"): the vf net packs
+    critic.weight^T [D][H] and critic.bias [H] in place of its LSTM."""
 
     kind = "lstm"  # (what Rollout.collect dispatches on)
 
-    def __init__(self, obs_width, n_actions, lstm_hidden=256, pi=(64, 64), vf=(64, 64), activation="tanh"):
+    def __init__(self, obs_width, n_actions, lstm_hidden=256, pi=(64, 64), vf=(64, 64), activation="tanh",
+                 enable_critic_lstm=True):
+        self.enable_critic_lstm = bool(enable_critic_lstm)
         self.lstm_hidden = int(lstm_hidden)
         if not 1 <= self.lstm_hidden <= MAX_WIDTH:
             raise ValueError(f"lstm_hidden {lstm_hidden} is not in 1 .. {MAX_WIDTH}")
@@ -81,37 +106,48 @@ class LstmPolicySpec(policy_module.MlpPolicySpec):
         mlp = policy_module.MlpPolicySpec(self.lstm_hidden, n_actions, pi=pi, vf=vf, activation=activation)  # (its checks)
         self.obs_width, self.n_actions = int(obs_width), mlp.n_actions
         self.pi, self.vf, self.activation = mlp.pi, mlp.vf, mlp.activation
-        width, hidden = self.obs_width, self.lstm_hidden
-        self.entries = []  # (state_dict name, packed offset, packed shape, is a weight)
-        at = 0
         split = 2 * (len(self.pi) + 1)  # (the entries of the pi MLP and head)
-        for lstm, own in (("lstm_actor", mlp.entries[:split]), ("lstm_critic", mlp.entries[split:])):
-            for part, shape in zip(LSTM_PARTS, ((width, 4 * hidden), (hidden, 4 * hidden), (4 * hidden,), (4 * hidden,))):
-                self.entries.append((f"{lstm}.{part}", at, shape, len(shape) == 2))
-                at += int(np.prod(shape))
-            for name, _, shape, is_weight in own:
-                self.entries.append((name, at, shape, is_weight))
-                at += int(np.prod(shape))
-        self.size = at
+        # (state_dict name, packed offset, packed shape, is a weight)
+        self.entries, self.size = recurrent_entries(self.obs_width, self.lstm_hidden, mlp.entries[:split], mlp.entries[split:],
+                                                    self.enable_critic_lstm)
 
     def desc(self):
         """The fields of rf_lstm_policy_desc, in order: rf_policy_desc's nine, then lstm_hidden."""
         return super().desc() + (self.lstm_hidden,)
 
+    def critic_desc(self):
+        """The fields of rf_lstm_critic_desc, in order: desc()'s ten, then critic."""
+        return self.desc() + (CRITIC_LSTM if self.enable_critic_lstm else CRITIC_LINEAR,)
+
+    def checked(self, state_dict, shape_of):
+        """MlpPolicySpec.checked; a state_dict of the other critic mode is refused by name."""
+        other = "critic." if self.enable_critic_lstm else "lstm_critic."
+        wrong = [name for name in state_dict if name.startswith(other)]
+        if wrong:
+            raise KeyError(f"{wrong} belong to enable_critic_lstm={not self.enable_critic_lstm}; this spec has "
+                           f"enable_critic_lstm={self.enable_critic_lstm}")
+        return super().checked(state_dict, shape_of)
+
     def state_shape(self, num_envs):
         return (2, 2, int(num_envs), self.lstm_hidden)
 
     def nets(self, params):
-        """((pi lstm, pi layers, pi head), (vf ...)): lstm = (w_ih_t, w_hh_t, b_ih, b_hh); each layer (weight_t, bias)."""
+        """((pi lstm, pi layers, pi head), (vf ...)): lstm = (w_ih_t, w_hh_t, b_ih, b_hh) -- for the vf net of
+        enable_critic_lstm=False (weight_t [D, H], bias [H]) of `critic` --; each layer (weight_t, bias)."""
         params = np.asarray(params, dtype=f32).reshape(self.size)
-        views = [params[at:at + int(np.prod(shape))].reshape(shape) for _, at, shape, _ in self.entries]
+        views = [params[at:at + int(np.prod(shape))].reshape(shape) for _, at, shape, _ in self.entries[:self._net_entries()]]
         out, first = [], 0
-        for widths in (self.pi, self.vf):
-            lstm = tuple(views[first:first + 4])
-            layers = list(zip(views[first + 4:first + 6 + 2 * len(widths):2], views[first + 5:first + 6 + 2 * len(widths):2]))
+        for net, widths in enumerate((self.pi, self.vf)):
+            parts = 4 if net == 0 or self.enable_critic_lstm else 2
+            lstm = tuple(views[first:first + parts])
+            after = first + parts
+            layers = list(zip(views[after:after + 2 + 2 * len(widths):2], views[after + 1:after + 2 + 2 * len(widths):2]))
             out.append((lstm, layers[:-1], layers[-1]))
-            first += 6 + 2 * len(widths)
+            first = after + 2 + 2 * len(widths)
         return tuple(out)
+
+    def _net_entries(self):
+        return len(self.entries)
 
 
 def _refuse_box(action_space):
@@ -127,6 +163,25 @@ def _mlp(spec, layers, last, x):
     return linear(x, *last)
 
 
+def vf_latents(spec, nets, obs, masked, state, final_obs):
+    """What the vf MLP reads: (latent of obs, c' of the vf cell or None, latent of final_obs or None).  With the LSTM critic
+    h' of the cell from the masked state (final_obs: from the state as it is); with enable_critic_lstm=False ("lstm
+    critic" C2 - C4) critic(obs) and critic(final_obs): no activation, no state, no episode starts."""
+    if not spec.enable_critic_lstm:
+        return linear(obs, *nets[1][0]), None, None if final_obs is None else linear(final_obs, *nets[1][0])
+    h_vf, c_vf = lstm_layer(obs, masked[1, 0], masked[1, 1], *nets[1][0])
+    h_final = None if final_obs is None else lstm_layer(final_obs, state[1, 0], state[1, 1], *nets[1][0])[0]
+    return h_vf, c_vf, h_final
+
+
+def next_state(spec, h_pi, c_pi, h_vf, c_vf):
+    """The state a forward stores; with enable_critic_lstm=False both halves are the pi net's (sb3-contrib's
+    lstm_states_vf = lstm_states_pi)."""
+    if not spec.enable_critic_lstm:
+        h_vf, c_vf = h_pi, c_pi
+    return canonical(np.stack([np.stack([h_pi, c_pi]), np.stack([h_vf, c_vf])]))
+
+
 def lstm_numpy(spec, params, obs, episode_starts, state, final_obs=None, u=None, deterministic=False, values_only=False):
     """The definition, literally.  obs float32 [n, D], episode_starts uint8 [n] (non-zero: a start), state float32
     [2, 2, n, H], final_obs float32 [n, D] or None, u float64 [n] (the draws of a sampled call).  Returns a dict: "logits"
@@ -139,12 +194,12 @@ def lstm_numpy(spec, params, obs, episode_starts, state, final_obs=None, u=None,
     masked = np.where(starts[None, None, :, None], f32(0.0), state)  # a select: no NaN or inf of a dead state survives
     nets = spec.nets(params)
     out = {"values": None, "final_values": None, "logits": None, "actions": None, "log_probs": None, "state": None}
-    h_vf, c_vf = lstm_layer(obs, masked[1, 0], masked[1, 1], *nets[1][0])
-    out["values"] = canonical(_mlp(spec, nets[1][1], nets[1][2], h_vf)[:, 0])
     if final_obs is not None:
         final_obs = np.asarray(final_obs, dtype=f32).reshape(obs.shape)
+    h_vf, c_vf, h_final = vf_latents(spec, nets, obs, masked, state, final_obs)  # (final_obs: from the unmasked state)
+    out["values"] = canonical(_mlp(spec, nets[1][1], nets[1][2], h_vf)[:, 0])
+    if final_obs is not None:
         lead = final_obs[:, 0]
-        h_final, _ = lstm_layer(final_obs, state[1, 0], state[1, 1], *nets[1][0])  # (from the state as it is: unmasked)
         out["final_values"] = np.where(lead != lead, _NAN, canonical(_mlp(spec, nets[1][1], nets[1][2], h_final)[:, 0]))
     if values_only:
         return out
@@ -154,7 +209,7 @@ def lstm_numpy(spec, params, obs, episode_starts, state, final_obs=None, u=None,
         raise ValueError("a sampled call needs its draws u")
     out["actions"], out["log_probs"] = head(logits, None if deterministic else u)
     out["logits"] = canonical(logits)
-    out["state"] = canonical(np.stack([np.stack([h_pi, c_pi]), np.stack([h_vf, c_vf])]))
+    out["state"] = next_state(spec, h_pi, c_pi, h_vf, c_vf)
     return out
 
 
@@ -229,6 +284,8 @@ class DeviceLstmPolicy(policy_module.DevicePolicy):
             raise ValueError(f"the spec has {spec.n_actions} actions, the environment {env.single_action_space.n}")
         self._attach(env, spec, seed)
         self.num_envs = int(env.num_envs)
+        if not spec.enable_critic_lstm and self._ctx.lstm_critic_params_size(spec.critic_desc()) != spec.size:
+            raise RuntimeError("rf_lstm_critic_params_size disagrees with the packed parameters")
         self._state = self._torch.zeros(spec.state_shape(self.num_envs), dtype=self._torch.float32, device=self.device)
 
     def _checked_state(self, state, what):
@@ -276,10 +333,12 @@ class DeviceLstmPolicy(policy_module.DevicePolicy):
                  final_values):
         self._interop.check_one_runtime()
         pointer = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        self._ctx.lstm_forward(self.spec.desc(), self.params.data_ptr(), obs.shape[0], obs.data_ptr(),
-                               episode_starts.data_ptr(), pointer(final_obs), state_in.data_ptr(), pointer(state_out), gen,
-                               flags, pointer(actions), pointer(log_probs), pointer(values), pointer(final_values), None,
-                               self._io._stream())
+        # (enable_critic_lstm=False: the sibling entry point over rf_lstm_critic_desc, lstm_forward_kernel<false, true>)
+        linear = not self.spec.enable_critic_lstm
+        forward = self._ctx.lstm_critic_forward if linear else self._ctx.lstm_forward
+        forward(self.spec.critic_desc() if linear else self.spec.desc(), self.params.data_ptr(), obs.shape[0], obs.data_ptr(),
+                episode_starts.data_ptr(), pointer(final_obs), state_in.data_ptr(), pointer(state_out), gen, flags,
+                pointer(actions), pointer(log_probs), pointer(values), pointer(final_values), None, self._io._stream())
 
     def act(self, obs, episode_starts, final_obs=None, deterministic=False, out=None, states=None):
         """(actions int64 [n], values, log_probs, final_values or None) of obs float32 [n, D], episode_starts uint8 or

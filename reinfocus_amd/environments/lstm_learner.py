@@ -20,7 +20,10 @@ cuts it into consecutive minibatches.  A minibatch is therefore (first, count): 
 
 The head is the policy's: Categorical for an lstm.LstmPolicy (int64 actions), or -- for an lstm_sde.LstmSdePolicy, whose
 spec has kind "lstm_sde" -- the Gaussian head of environments/sde.py over float32 raw actions and P + L parameters
-("lstm sde update": rf_lstm_sde_update).
+("lstm sde update": rf_lstm_sde_update).  The critic is the spec's too: with enable_critic_lstm=False ("lstm critic") the
+vf net has no sequences and no BPTT -- its MLP reads critic(observations[r_b]), the vf half of lstm_states is never read,
+and critic.weight / critic.bias get their gradient from the observations and the delta of the layer's output
+(rf_lstm_critic_ppo_update / rf_lstm_critic_sde_update).
 
 Limits: one LSTM layer per net of 1 .. 256 units, minibatches of 1 .. min(N, 1024) rows.
 
@@ -201,10 +204,15 @@ def lstm_gradient_numpy(spec, params, batch, episode_starts, lstm_states, n_step
     with np.errstate(all="ignore"):
         adv = _normalised(adv, hyper, count)
         cells, mlps, heads = [], [], []
+        feedforward = not spec.enable_critic_lstm  # ("lstm critic": the vf net is one linear layer, rows are independent)
         for net, (lstm, layers, last) in enumerate(spec.nets(params)):
-            states = (lstm_states[:, net, 0], lstm_states[:, net, 1])  # [T + 1, n, H] each
-            cells.append(_cell_rows(x, rows, states, lstm))
-            acts = [cells[-1][4]]
+            if net == 1 and feedforward:
+                cells.append(None)
+                acts = [linear(x, *lstm)]
+            else:
+                states = (lstm_states[:, net, 0], lstm_states[:, net, 1])  # [T + 1, n, H] each
+                cells.append(_cell_rows(x, rows, states, lstm))
+                acts = [cells[-1][4]]
             for weight_t, bias in layers:
                 acts.append(activation(linear(acts[-1], weight_t, bias), spec.activation))
             mlps.append(acts)
@@ -254,12 +262,16 @@ def lstm_gradient_numpy(spec, params, batch, episode_starts, lstm_states, n_step
             dlogit = (pull + ent) / count_f
         pieces = []
         for net, (delta_head, (lstm, layers, last)) in enumerate(zip((dlogit, dv[:, None]), spec.nets(params))):
-            h_prev, c_prev, gates, c1, _ = cells[net]
             deltas, dh_mlp = _mlp_backward(spec, layers, last, mlps[net], delta_head)
-            da = _bptt(rows, lstm[1], dh_mlp, c_prev, gates, c1).reshape(count, 4 * hidden)
-            w_ih, b_ih = _chain(x, da)
-            w_hh, _ = _chain(h_prev, da)
-            pieces += [w_ih.reshape(-1), w_hh.reshape(-1), b_ih, b_ih]
+            if cells[net] is None:  # C7: dh_mlp is the delta of the linear layer's output
+                weight, bias = _chain(x, dh_mlp)
+                pieces += [weight.reshape(-1), bias]
+            else:
+                h_prev, c_prev, gates, c1, _ = cells[net]
+                da = _bptt(rows, lstm[1], dh_mlp, c_prev, gates, c1).reshape(count, 4 * hidden)
+                w_ih, b_ih = _chain(x, da)
+                w_hh, _ = _chain(h_prev, da)
+                pieces += [w_ih.reshape(-1), w_hh.reshape(-1), b_ih, b_ih]
             for acts_in, delta in zip(mlps[net], deltas):
                 weight, bias = _chain(acts_in, delta)
                 pieces += [weight.reshape(-1), bias]
@@ -402,8 +414,12 @@ class DeviceLstmLearner(_Splits):
         self.device = policy.device
         torch = self._torch
         self._sde = self.spec.kind == "lstm_sde"  # (the Gaussian head: rf_lstm_sde_* over P + L parameters)
-        state_size = self._ctx.lstm_sde_state_size if self._sde else self._ctx.lstm_ppo_state_size
-        if state_size(self.spec.desc()) != 4 * (STATE_HEADER + 2 * self.spec.size):
+        self._linear = not self.spec.enable_critic_lstm  # (the sibling entry points over rf_lstm_critic_desc: "lstm critic")
+        if self._linear:
+            state_bytes = self._ctx.lstm_critic_state_size(self.spec.critic_desc(), sde=self._sde)
+        else:
+            state_bytes = (self._ctx.lstm_sde_state_size if self._sde else self._ctx.lstm_ppo_state_size)(self.spec.desc())
+        if state_bytes != 4 * (STATE_HEADER + 2 * self.spec.size):
             raise RuntimeError("rf_lstm_ppo_state_size / rf_lstm_sde_state_size disagrees with the packed optimizer state")
         self.state = torch.zeros(STATE_HEADER + 2 * self.spec.size, dtype=torch.float32, device=self.device)
         self._workspace, self._workspace_batch = None, 0
@@ -438,16 +454,22 @@ class DeviceLstmLearner(_Splits):
 
     def _room(self, batch):
         if batch > self._workspace_batch:
-            workspace_size = self._ctx.lstm_sde_workspace_size if self._sde else self._ctx.lstm_ppo_workspace_size
-            size = workspace_size(self.spec.desc(), batch)
+            if self._linear:
+                size = self._ctx.lstm_critic_workspace_size(self.spec.critic_desc(), batch, sde=self._sde)
+            else:
+                workspace_size = self._ctx.lstm_sde_workspace_size if self._sde else self._ctx.lstm_ppo_workspace_size
+                size = workspace_size(self.spec.desc(), batch)
             if size == 0:
                 raise RuntimeError(f"rf_lstm_ppo_workspace_size / rf_lstm_sde_workspace_size refuses a minibatch of {batch}")
             self._workspace = self._torch.zeros(size // 4, dtype=self._torch.float32, device=self.device)
             self._workspace_batch = batch
 
     def _enqueue(self, parts, n_steps, num_envs, first, count, stats, hyper):
-        update = self._ctx.lstm_sde_update if self._sde else self._ctx.lstm_ppo_update
-        update(self.spec.desc(), hyper, self.policy.params.data_ptr(), self.state.data_ptr(), self._workspace.data_ptr(),
+        if self._linear:
+            update = self._ctx.lstm_critic_sde_update if self._sde else self._ctx.lstm_critic_ppo_update
+        else:
+            update = self._ctx.lstm_sde_update if self._sde else self._ctx.lstm_ppo_update
+        update(self.spec.critic_desc() if self._linear else self.spec.desc(), hyper, self.policy.params.data_ptr(), self.state.data_ptr(), self._workspace.data_ptr(),
                n_steps, num_envs, parts["observations"].data_ptr(), parts["actions"].data_ptr(),
                parts["log_probs"].data_ptr(), parts["advantages"].data_ptr(), parts["returns"].data_ptr(),
                parts["episode_starts"].data_ptr(), parts["lstm_states"].data_ptr(), first, count, stats.data_ptr(),

@@ -13,8 +13,9 @@ environments/lstm_learner.py's, which takes the head from the spec's kind.
     LstmSdePolicy        the numpy twin: reset_noise / act / values over numpy arrays, the state float32 [2, 2, n, H]
     DeviceLstmSdePolicy  the same over torch tensors on a device-resident environment's GPU: one launch per call
 
-Still out of scope, and refused or absent: more than one action dimension, n_lstm_layers > 1, shared_lstm=True,
-enable_critic_lstm=False, learn_features=True, use_expln, squash_output.
+enable_critic_lstm=False is the spec's, as LstmPolicySpec's ("lstm critic": the head touches only the pi net).  Still out
+of scope, and refused or absent: more than one action dimension, n_lstm_layers > 1, shared_lstm=True, lstm_hidden > 256,
+learn_features=True, use_expln, squash_output.
 
 torch is imported lazily, by DeviceLstmSdePolicy only (reinfocus_amd/torch_interop.py says why import order matters).
 """
@@ -24,7 +25,7 @@ import numpy as np
 from reinfocus_amd.environments import lstm as lstm_module
 from reinfocus_amd.environments import policy as policy_module
 from reinfocus_amd.environments import sde as sde_module
-from reinfocus_amd.environments.lstm import LSTM_PARTS, lstm_layer
+from reinfocus_amd.environments.lstm import lstm_layer, next_state, recurrent_entries, vf_latents
 from reinfocus_amd.environments.policy import _NAN, DETERMINISTIC, MAX_WIDTH, activation, canonical, f32, linear
 from reinfocus_amd.environments.sde import env_actions_of, log_prob_of, noise_numpy, sigma_of, std2_of
 
@@ -35,7 +36,9 @@ class LstmSdePolicySpec(lstm_module.LstmPolicySpec):
 
     kind = "lstm_sde"  # (what Rollout.collect and the learners dispatch on)
 
-    def __init__(self, obs_width, lstm_hidden=256, pi=(64, 64), vf=(64, 64), activation="tanh", log_std_init=0.0):
+    def __init__(self, obs_width, lstm_hidden=256, pi=(64, 64), vf=(64, 64), activation="tanh", log_std_init=0.0,
+                 enable_critic_lstm=True):
+        self.enable_critic_lstm = bool(enable_critic_lstm)
         self.lstm_hidden = int(lstm_hidden)
         if not 1 <= self.lstm_hidden <= MAX_WIDTH:
             raise ValueError(f"lstm_hidden {lstm_hidden} is not in 1 .. {MAX_WIDTH}")
@@ -45,20 +48,16 @@ class LstmSdePolicySpec(lstm_module.LstmPolicySpec):
         self.obs_width, self.n_actions = int(obs_width), 1
         self.pi, self.vf, self.activation = mlp.pi, mlp.vf, mlp.activation
         self.log_std_init = float(log_std_init)
-        width, hidden = self.obs_width, self.lstm_hidden
-        self.entries = []  # (state_dict name, packed offset, packed shape, is a weight)
-        at = 0
         split = 2 * (len(self.pi) + 1)  # (the entries of the pi MLP and head)
-        for lstm, own in (("lstm_actor", mlp.entries[:split]), ("lstm_critic", mlp.entries[split:-1])):
-            for part, shape in zip(LSTM_PARTS, ((width, 4 * hidden), (hidden, 4 * hidden), (4 * hidden,), (4 * hidden,))):
-                self.entries.append((f"{lstm}.{part}", at, shape, len(shape) == 2))
-                at += int(np.prod(shape))
-            for name, _, shape, is_weight in own:
-                self.entries.append((name, at, shape, is_weight))
-                at += int(np.prod(shape))
+        # (state_dict name, packed offset, packed shape, is a weight)
+        self.entries, at = recurrent_entries(self.obs_width, self.lstm_hidden, mlp.entries[:split], mlp.entries[split:-1],
+                                             self.enable_critic_lstm)
         self.log_std_at, self.latent = at, self.pi[-1]
         self.entries.append(("log_std", at, (1, self.latent), True))  # (SB3's [L, 1] is this, transposed)
         self.size = at + self.latent
+
+    def _net_entries(self):
+        return len(self.entries) - 1  # (log_std is no net's)
 
     def initial(self):
         params = np.zeros(self.size, dtype=f32)
@@ -93,12 +92,12 @@ def lstm_sde_numpy(spec, params, obs, episode_starts, state, final_obs=None, the
     masked = np.where(starts[None, None, :, None], f32(0.0), state)  # a select: no NaN or inf of a dead state survives
     nets = spec.nets(params)
     out = dict.fromkeys(("actions", "env_actions", "log_probs", "mean", "sigma", "values", "final_values", "state"))
-    h_vf, c_vf = lstm_layer(obs, masked[1, 0], masked[1, 1], *nets[1][0])
-    out["values"] = canonical(linear(_mlp(spec, nets[1][1], h_vf), *nets[1][2])[:, 0])
     if final_obs is not None:
         final_obs = np.asarray(final_obs, dtype=f32).reshape(obs.shape)
+    h_vf, c_vf, h_final = vf_latents(spec, nets, obs, masked, state, final_obs)  # (final_obs: from the unmasked state)
+    out["values"] = canonical(linear(_mlp(spec, nets[1][1], h_vf), *nets[1][2])[:, 0])
+    if final_obs is not None:
         lead = final_obs[:, 0]
-        h_final, _ = lstm_layer(final_obs, state[1, 0], state[1, 1], *nets[1][0])  # (from the state as it is: unmasked)
         out["final_values"] = np.where(lead != lead, _NAN,
                                        canonical(linear(_mlp(spec, nets[1][1], h_final), *nets[1][2])[:, 0]))
     if values_only:
@@ -116,7 +115,7 @@ def lstm_sde_numpy(spec, params, obs, episode_starts, state, final_obs=None, the
             a = mu + sde_module._rowdot(h, theta)
     out["actions"], out["env_actions"] = canonical(a), env_actions_of(a)
     out["log_probs"], out["mean"], out["sigma"] = log_prob_of(a, mu, sigma), canonical(mu), canonical(sigma)
-    out["state"] = canonical(np.stack([np.stack([h_pi, c_pi]), np.stack([h_vf, c_vf])]))
+    out["state"] = next_state(spec, h_pi, c_pi, h_vf, c_vf)
     return out
 
 
@@ -182,8 +181,11 @@ class DeviceLstmSdePolicy(lstm_module.DeviceLstmPolicy):
             raise TypeError(f"DeviceLstmSdePolicy needs an LstmSdePolicySpec, not {type(spec).__name__}")
         self._attach(env, spec, seed)
         self.num_envs = int(env.num_envs)
-        if self._ctx.lstm_sde_params_size(spec.desc()) != spec.size:
-            raise RuntimeError("rf_lstm_sde_params_size disagrees with the packed parameters")
+        self._linear = not spec.enable_critic_lstm  # (the sibling entry points over rf_lstm_critic_desc: "lstm critic")
+        size = self._ctx.lstm_critic_params_size(spec.critic_desc(), sde=True) if self._linear \
+            else self._ctx.lstm_sde_params_size(spec.desc())
+        if size != spec.size:
+            raise RuntimeError("rf_lstm_sde_params_size / rf_lstm_critic_sde_params_size disagrees with the packed parameters")
         self.params.copy_(self._torch.from_numpy(spec.initial()))
         self._state = self._torch.zeros(spec.state_shape(self.num_envs), dtype=self._torch.float32, device=self.device)
         self._theta = None
@@ -197,9 +199,9 @@ class DeviceLstmSdePolicy(lstm_module.DeviceLstmPolicy):
         self._interop.check_one_runtime()
         if self._theta is None:
             self._theta = torch.zeros((self.num_envs, self.spec.latent), dtype=torch.float32, device=self.device)
-        self._ctx.lstm_sde_noise_reset(self.spec.desc(), self.params.data_ptr(), self.num_envs,
-                                       policy_module.generator_words(self._bit_generator), self._theta.data_ptr(),
-                                       self._io._stream())
+        reset = self._ctx.lstm_critic_sde_noise_reset if self._linear else self._ctx.lstm_sde_noise_reset
+        reset(self.spec.critic_desc() if self._linear else self.spec.desc(), self.params.data_ptr(), self.num_envs,
+              policy_module.generator_words(self._bit_generator), self._theta.data_ptr(), self._io._stream())
         self._bit_generator.advance(self.num_envs * self.spec.latent)  # (after the call was taken)
 
     def noise(self):
@@ -220,10 +222,11 @@ class DeviceLstmSdePolicy(lstm_module.DeviceLstmPolicy):
                  values, final_values):
         self._interop.check_one_runtime()
         pointer = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        self._ctx.lstm_sde_forward(self.spec.desc(), self.params.data_ptr(), obs.shape[0], obs.data_ptr(),
-                                   episode_starts.data_ptr(), pointer(final_obs), state_in.data_ptr(), pointer(state_out),
-                                   pointer(theta), flags, pointer(actions), pointer(env_actions), pointer(log_probs),
-                                   pointer(values), pointer(final_values), None, None, self._io._stream())
+        forward = self._ctx.lstm_critic_sde_forward if self._linear else self._ctx.lstm_sde_forward
+        forward(self.spec.critic_desc() if self._linear else self.spec.desc(), self.params.data_ptr(), obs.shape[0],
+                obs.data_ptr(), episode_starts.data_ptr(), pointer(final_obs), state_in.data_ptr(), pointer(state_out),
+                pointer(theta), flags, pointer(actions), pointer(env_actions), pointer(log_probs), pointer(values),
+                pointer(final_values), None, None, self._io._stream())
 
     def act(self, obs, episode_starts, final_obs=None, deterministic=False, out=None, states=None):
         """(actions float32 [n] (raw), values, log_probs, final_values or None, env_actions float32 [n] (clamped)) of obs
