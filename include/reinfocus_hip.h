@@ -1261,6 +1261,66 @@ int rf_lstm_critic_sde_update(rf_ctx *ctx, const rf_lstm_critic_desc *desc, cons
                               const float *d_returns, const uint8_t *d_episode_starts, const float *d_lstm_states, int first,
                               int B, float *d_stats, void *caller_stream);
 
+/* ---- population: G independent PPO learners in lock-step, one launch per stage --------------------------------------------
+ * The reference trains with n_envs 8 and runs its hyper-parameter search as 20 such trials side by side; at 8 environments
+ * a forward is one or two blocks and an update three launch-bound kernels.  A population is G learners of ONE architecture
+ * (the Categorical head of "policy") over one environment of n = G m lanes, each stage of all of them one launch.  No
+ * reference counterpart.  Written as deltas of "policy" and "ppo update": the arithmetic of a group is exactly theirs, only
+ * addressing changes.  numpy twins environments/population.py (G of the existing twins over slices), kernels
+ * policy_forward_grouped_kernel (csrc/rf_policy.h) and ppo_backward_grouped_kernel, ppo_gradient_grouped_kernel,
+ * ppo_adam_grouped_kernel (csrc/rf_ppo.h), each the ungrouped kernel's body behind a group dimension of the grid.
+ *
+ *  G1 Environments.  Group g of G owns environments [g m, (g + 1) m): rows [g m, (g + 1) m) of every array of a forward.
+ *     Tiles of 8 rows are cut per group (a tile never spans two groups; no result depends on it).
+ *  G2 Parameters.  d_params is float32 [G][P]: group g reads and updates params[g P .. (g + 1) P).
+ *  G3 Draws.  d_gens is uint64 [G][4], the words of G generators as rf_policy_forward's gen; `consumed` travels by value.
+ *     Row e of group g (e local, 0 .. m - 1) takes draw number consumed + e of generator g: what a stand-alone
+ *     rf_policy_forward over the group's m rows takes whose generator was advanced by `consumed` before.  The caller adds m
+ *     to consumed after a sampled call; the table is written at seeding only.
+ *  G4 Update rows.  The arrays of an update have G N rows, group g owning rows [g N, (g + 1) N) -- with N = m T these are
+ *     the group's rows of a rollout's flat(), which orders rows e T + t.  d_index is int64 [G][B] of rows LOCAL to the
+ *     group, each in [0, N); validity, clamping and the gathers of steps 1 .. 3 are per group with the group's N.
+ *     1 <= B <= min(N, RF_PPO_MAX_BATCH).
+ *  G5 Hyper-parameters.  d_hyper is a device array of G rf_ppo_hyper, what rf_ppo_desc becomes: the float64 fields
+ *     unchanged, clip_range, ent_coef and vf_coef converted to float32.  They are read on the device, so the entry point
+ *     cannot check them: the caller vouches that each is what rf_ppo_update would accept.
+ *  G6 State and workspace.  d_state is G optimizer states of "ppo update" back to back (32 + 8 P bytes each), the workspace
+ *     G workspaces of rf_ppo_workspace_size(B) bytes each: the float64 trees of steps 2, 8 and 10 are per group and have
+ *     the shape of the ungrouped tree for the same B and P.
+ *  G7 Stats and skips.  d_stats is float32 [G][8].  A group whose minibatch is invalid or whose gradient norm is not finite
+ *     is skipped and flagged in its own stats[7] exactly as step 8 says; the other groups are untouched by it.
+ * Limits: G 1 .. RF_POPULATION_MAX_GROUPS (the grid's y / z limit), m >= 1, G m <= 2^30 (G N alike), B as in G4.
+ * Out of scope: per-group gamma / gae_lambda (a rollout's GAE keeps its scalars), per-group learner-view statistics, the
+ * sde and lstm heads, groups that differ in architecture, m, T or B.
+ *
+ *   rf_policy_forward_grouped      rf_policy_forward over (G, m) in place of n: one launch, grid (ceil(m / 8), nets, G);
+ *                                  the same outputs over G m rows, the same refusals (with d_gens, a device array, in
+ *                                  place of gen, needed when the call samples), and G or m outside the limits.
+ *   rf_ppo_grouped_state_size      G (32 + 8 P) bytes; 0 for a desc outside the limits, G outside its limits, m < 1 or a
+ *                                  NULL ctx
+ *   rf_ppo_grouped_workspace_size  G rf_ppo_workspace_size(policy, B) bytes; 0 if that is, for G < 1, m < 1, T < 1 or
+ *                                  B > m T
+ *   rf_ppo_update_grouped          rf_ppo_update over (G, m, T) in place of N, N = m T rows per group: three launches
+ *                                  whatever G is, the same refusals over the G-fold arrays, and B > N. */
+#define RF_POPULATION_MAX_GROUPS 65535
+
+typedef struct rf_ppo_hyper {
+    double learning_rate, max_grad_norm, beta1, beta2, adam_eps;
+    float clip_range, ent_coef, vf_coef;
+    int normalize_advantage; /* 0 / 1 */
+} rf_ppo_hyper;               /* 56 bytes */
+
+int rf_policy_forward_grouped(rf_ctx *ctx, const rf_policy_desc *desc, int G, int m, const float *d_params,
+                              const float *d_obs, const float *d_final_obs, const unsigned long long *d_gens,
+                              unsigned long long consumed, int flags, long long *d_actions, float *d_log_probs,
+                              float *d_values, float *d_final_values, float *d_logits, void *caller_stream);
+unsigned long long rf_ppo_grouped_state_size(rf_ctx *ctx, const rf_policy_desc *policy, int G, int m);
+unsigned long long rf_ppo_grouped_workspace_size(rf_ctx *ctx, const rf_policy_desc *policy, int G, int m, int T, int B);
+int rf_ppo_update_grouped(rf_ctx *ctx, const rf_policy_desc *policy, int G, int m, int T, const rf_ppo_hyper *d_hyper,
+                          float *d_params, void *d_state, void *d_workspace, const float *d_obs, const long long *d_actions,
+                          const float *d_old_log_probs, const float *d_advantages, const float *d_returns, int B,
+                          const long long *d_index, float *d_stats, void *caller_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -101,6 +101,10 @@ SYMBOLS = (
     "rf_ppo_state_size",
     "rf_ppo_workspace_size",
     "rf_ppo_update",
+    "rf_policy_forward_grouped",
+    "rf_ppo_grouped_state_size",
+    "rf_ppo_grouped_workspace_size",
+    "rf_ppo_update_grouped",
     "rf_sde_params_size",
     "rf_sde_noise_reset",
     "rf_sde_forward",
@@ -396,6 +400,13 @@ def load():
     lib.rf_ppo_workspace_size.restype = ctypes.c_ulonglong
     lib.rf_ppo_workspace_size.argtypes = [vp, vp, i32]
     lib.rf_ppo_update.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp]
+    lib.rf_policy_forward_grouped.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, ctypes.c_ulonglong, i32, vp, vp, vp, vp, vp,
+                                              vp]
+    lib.rf_ppo_grouped_state_size.restype = ctypes.c_ulonglong
+    lib.rf_ppo_grouped_state_size.argtypes = [vp, vp, i32, i32]
+    lib.rf_ppo_grouped_workspace_size.restype = ctypes.c_ulonglong
+    lib.rf_ppo_grouped_workspace_size.argtypes = [vp, vp, i32, i32, i32, i32]
+    lib.rf_ppo_update_grouped.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]
     lib.rf_sde_params_size.restype = ctypes.c_ulonglong
     lib.rf_sde_params_size.argtypes = [vp, vp]
     lib.rf_sde_noise_reset.argtypes = [vp, vp, vp, i32, vp, vp, vp]
@@ -806,6 +817,39 @@ class Context:
         rc = self._lib.rf_ppo_update(self._h, ctypes.byref(PolicyDesc(*desc)), ctypes.byref(PpoDesc(*hyper)), params_ptr,
                                      state_ptr, workspace_ptr, rows, obs_ptr, actions_ptr, old_log_probs_ptr,
                                      advantages_ptr, returns_ptr, batch, index_ptr, stats_ptr, stream)
+        if rc != 0:
+            _check(rc)
+
+    # --- population (rf_*_grouped): the two groups above over G groups of m environments, one launch per stage ----------
+    def policy_forward_grouped(self, desc, groups, per_group, params_ptr, obs_ptr, final_obs_ptr, gens_ptr, consumed, flags,
+                               actions_ptr, log_probs_ptr, values_ptr, final_values_ptr, logits_ptr, stream):
+        """rf_policy_forward_grouped: policy_forward over groups x per_group rows, parameters [groups][P]; gens_ptr: the
+        device table uint64 [groups][4] of the generators' words (or None), consumed: the draws each has given so far.
+        Only enqueues."""
+        rc = self._lib.rf_policy_forward_grouped(self._h, ctypes.byref(PolicyDesc(*desc)), groups, per_group, params_ptr,
+                                                 obs_ptr, final_obs_ptr, gens_ptr, consumed, flags, actions_ptr,
+                                                 log_probs_ptr, values_ptr, final_values_ptr, logits_ptr, stream)
+        if rc != 0:
+            _check(rc)
+
+    def ppo_grouped_state_size(self, desc, groups, per_group):
+        """rf_ppo_grouped_state_size: bytes of the optimizer states of `groups` networks `desc`; 0 if refused."""
+        return int(self._lib.rf_ppo_grouped_state_size(self._h, ctypes.byref(PolicyDesc(*desc)), groups, per_group))
+
+    def ppo_grouped_workspace_size(self, desc, groups, per_group, steps, batch):
+        """rf_ppo_grouped_workspace_size: bytes of the workspaces of `groups` minibatches of `batch` samples out of
+        per_group x steps rows each; 0 if refused."""
+        return int(self._lib.rf_ppo_grouped_workspace_size(self._h, ctypes.byref(PolicyDesc(*desc)), groups, per_group,
+                                                           steps, batch))
+
+    def ppo_update_grouped(self, desc, groups, per_group, steps, hyper_ptr, params_ptr, state_ptr, workspace_ptr, obs_ptr,
+                           actions_ptr, old_log_probs_ptr, advantages_ptr, returns_ptr, batch, index_ptr, stats_ptr, stream):
+        """rf_ppo_update_grouped: ppo_update of `groups` learners at once, three launches on `stream`; every array holds
+        the groups' pieces back to back (per_group x steps rows each), hyper_ptr: the device array of rf_ppo_hyper,
+        index_ptr: int64 [groups][batch] of rows local to each group.  Only enqueues."""
+        rc = self._lib.rf_ppo_update_grouped(self._h, ctypes.byref(PolicyDesc(*desc)), groups, per_group, steps, hyper_ptr,
+                                             params_ptr, state_ptr, workspace_ptr, obs_ptr, actions_ptr, old_log_probs_ptr,
+                                             advantages_ptr, returns_ptr, batch, index_ptr, stats_ptr, stream)
         if rc != 0:
             _check(rc)
 

@@ -2009,9 +2009,10 @@ int rf_policy_forward(rf_ctx *ctx, const rf_policy_desc *desc, const float *d_pa
             words.word[i] = gen[i];
     const bool pi = d_actions != nullptr || d_logits != nullptr, vf = d_values != nullptr || d_final_values != nullptr;
     const unsigned tiles = (unsigned)((rows + rf::kPolicyTile - 1) / rf::kPolicyTile);
-    hipLaunchKernelGGL(rf::policy_forward_kernel, dim3(tiles, pi && vf ? 2u : 1u), dim3(rf::kPolicyThreads), 0,
+    hipLaunchKernelGGL(rf::policy_forward_kernel<false>, dim3(tiles, pi && vf ? 2u : 1u), dim3(rf::kPolicyThreads), 0,
                        (hipStream_t)caller_stream, layout, d_params, n, d_obs, d_final_obs, words, sampled ? 1 : 0,
-                       pi ? 0 : 1, (int64_t *)d_actions, d_log_probs, d_values, d_final_values, d_logits);
+                       pi ? 0 : 1, (int64_t *)d_actions, d_log_probs, d_values, d_final_values, d_logits,
+                       (const rf::PolicyGen *)nullptr, (uint64_t)0);
     RF_HIP(hipGetLastError());
     return RF_OK;
 }
@@ -2104,14 +2105,14 @@ static int ppo_update_any(const char *fn, bool sde, rf_ctx *ctx, const rf_policy
     hipLaunchKernelGGL(sde ? rf::ppo_backward_kernel<true> : rf::ppo_backward_kernel<false>, dim3(tiles, 2u),
                        dim3(rf::kPpoThreads), 0, caller, layout, work, hyper, (const float *)d_params,
                        (const rf::PpoHeader *)d_state, ws, N, d_obs, d_actions, d_old_log_probs, d_advantages, d_returns, B,
-                       (const int64_t *)d_index);
+                       (const int64_t *)d_index, (const rf::PpoHyper *)nullptr);
     RF_HIP(hipGetLastError());
-    hipLaunchKernelGGL(rf::ppo_gradient_kernel, dim3(work.partials), dim3(rf::kPpoThreads), 0, caller, layout, work, ws, B,
-                       (const float *)d_params);
+    hipLaunchKernelGGL(rf::ppo_gradient_kernel<false>, dim3(work.partials), dim3(rf::kPpoThreads), 0, caller, layout, work, ws,
+                       B, (const float *)d_params);
     RF_HIP(hipGetLastError());
     const unsigned slices = (layout.total + rf::kPpoAdamSlice - 1) / rf::kPpoAdamSlice;
-    hipLaunchKernelGGL(rf::ppo_adam_kernel, dim3(slices + 1u), dim3(rf::kPpoThreads), 0, caller, layout.total, work, hyper,
-                       d_params, (float *)d_state, (const float *)ws, B, d_stats);
+    hipLaunchKernelGGL(rf::ppo_adam_kernel<false>, dim3(slices + 1u), dim3(rf::kPpoThreads), 0, caller, layout.total, work,
+                       hyper, d_params, (float *)d_state, (const float *)ws, B, d_stats, (const rf::PpoHyper *)nullptr);
     RF_HIP(hipGetLastError());
     return RF_OK;
 }
@@ -2125,6 +2126,169 @@ int rf_ppo_update(rf_ctx *ctx, const rf_policy_desc *policy, const rf_ppo_desc *
     RF_HIP(hipSetDevice(ctx->device));
     return ppo_update_any("rf_ppo_update", false, ctx, policy, ppo, d_params, d_state, d_workspace, N, d_obs, d_actions,
                           d_old_log_probs, d_advantages, d_returns, B, d_index, d_stats, caller_stream);
+}
+
+// ---- population (include/reinfocus_hip.h): the two entry points above over G groups, one launch per stage ----------------
+
+#define RF_POLICY_LIMITS "%s: the desc is outside the limits (obs_width 1 .. %d, 1 or 2 hidden layers of width 1 .. %d per " \
+                         "net, n_actions 2 .. %d, activation RF_POLICY_RELU or RF_POLICY_TANH)"
+
+int rf_policy_forward_grouped(rf_ctx *ctx, const rf_policy_desc *desc, int G, int m, const float *d_params,
+                              const float *d_obs, const float *d_final_obs, const unsigned long long *d_gens,
+                              unsigned long long consumed, int flags, long long *d_actions, float *d_log_probs,
+                              float *d_values, float *d_final_values, float *d_logits, void *caller_stream)
+{
+    const char *fn = "rf_policy_forward_grouped";
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", fn);
+    RF_REQUIRE(desc != nullptr && d_params != nullptr && d_obs != nullptr, "%s: NULL argument", fn);
+    rf::PolicyLayout layout;
+    RF_REQUIRE(rf::policy_layout(*desc, layout), RF_POLICY_LIMITS, fn, RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_WIDTH,
+               RF_POLICY_MAX_ACTIONS);
+    RF_REQUIRE(rf::population_rows(G, m), "%s: G = %d must be in 1 .. %d, m = %d at least 1 and G m at most 2^30", fn, G,
+               RF_POPULATION_MAX_GROUPS, m);
+    RF_REQUIRE((flags & ~RF_POLICY_DETERMINISTIC) == 0, "%s: unknown flags %d", fn, flags);
+    RF_REQUIRE(d_actions || d_values || d_final_values || d_logits, "%s: no output is asked for", fn);
+    RF_REQUIRE(d_log_probs == nullptr || d_actions != nullptr, "%s: d_log_probs are those of d_actions, which is NULL", fn);
+    RF_REQUIRE(d_final_values == nullptr || d_final_obs != nullptr, "%s: d_final_values needs d_final_obs", fn);
+    const bool sampled = d_actions != nullptr && (flags & RF_POLICY_DETERMINISTIC) == 0;
+    RF_REQUIRE(!sampled || d_gens != nullptr, "%s: a sampled call needs d_gens", fn);
+    RF_HIP(hipSetDevice(ctx->device));
+    const size_t rows = (size_t)G * (size_t)m;
+    struct Array {
+        const void *p;
+        size_t bytes, align;
+        const char *what;
+    };
+    const Array inputs[] = {{d_params, (size_t)G * (size_t)layout.total * 4, 4, "d_params"},
+                            {d_obs, rows * (size_t)layout.obs_width * 4, 4, "d_obs"},
+                            {d_final_obs, rows * (size_t)layout.obs_width * 4, 4, "d_final_obs"},
+                            {sampled ? d_gens : nullptr, (size_t)G * 32, 8, "d_gens"}};
+    const Array outputs[] = {{d_actions, rows * 8, 8, "d_actions"},
+                             {d_log_probs, rows * 4, 4, "d_log_probs"},
+                             {d_values, rows * 4, 4, "d_values"},
+                             {d_final_values, rows * 4, 4, "d_final_values"},
+                             {d_logits, rows * (size_t)layout.n_actions * 4, 4, "d_logits"}};
+    for (const Array &a : inputs) {
+        if (a.p == nullptr)
+            continue;
+        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
+            return rc;
+    }
+    for (const Array &a : outputs) {
+        if (a.p == nullptr)
+            continue;
+        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
+            return rc;
+        for (const Array &b : inputs)
+            RF_REQUIRE(b.p == nullptr || !ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s (an output must "
+                       "not alias an input: other blocks still read it)", fn, a.what, b.what);
+        for (const Array &b : outputs)
+            RF_REQUIRE(&b >= &a || b.p == nullptr || !ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s", fn,
+                       a.what, b.what);
+    }
+    // As rf_policy_forward: one launch on the caller's stream, nothing allocated, nothing waited for; the generators'
+    // words are read on the device and the draw count travels by value.
+    static_assert(sizeof(rf::PolicyGen) == 32, "d_gens is uint64 [G][4]");
+    const bool pi = d_actions != nullptr || d_logits != nullptr, vf = d_values != nullptr || d_final_values != nullptr;
+    const unsigned tiles = (unsigned)(((size_t)m + rf::kPolicyTile - 1) / rf::kPolicyTile);
+    hipLaunchKernelGGL(rf::policy_forward_kernel<true>, dim3(tiles, pi && vf ? 2u : 1u, (unsigned)G),
+                       dim3(rf::kPolicyThreads), 0, (hipStream_t)caller_stream, layout, d_params, m, d_obs, d_final_obs,
+                       rf::PolicyGen{}, sampled ? 1 : 0, pi ? 0 : 1, (int64_t *)d_actions, d_log_probs, d_values,
+                       d_final_values, d_logits, (const rf::PolicyGen *)(sampled ? d_gens : nullptr), (uint64_t)consumed);
+    RF_HIP(hipGetLastError());
+    return RF_OK;
+}
+
+unsigned long long rf_ppo_grouped_state_size(rf_ctx *ctx, const rf_policy_desc *policy, int G, int m)
+{
+    if (ctx == nullptr || policy == nullptr)
+        return 0;
+    if (hipSetDevice(ctx->device) != hipSuccess) // (as every entry point; nothing of the device is needed)
+        (void)hipGetLastError();
+    return rf::population_state_bytes(*policy, G, m);
+}
+
+unsigned long long rf_ppo_grouped_workspace_size(rf_ctx *ctx, const rf_policy_desc *policy, int G, int m, int T, int B)
+{
+    if (ctx == nullptr || policy == nullptr)
+        return 0;
+    if (hipSetDevice(ctx->device) != hipSuccess)
+        (void)hipGetLastError();
+    return rf::population_workspace_bytes(*policy, G, m, T, B);
+}
+
+int rf_ppo_update_grouped(rf_ctx *ctx, const rf_policy_desc *policy, int G, int m, int T, const rf_ppo_hyper *d_hyper,
+                          float *d_params, void *d_state, void *d_workspace, const float *d_obs, const long long *d_actions,
+                          const float *d_old_log_probs, const float *d_advantages, const float *d_returns, int B,
+                          const long long *d_index, float *d_stats, void *caller_stream)
+{
+    const char *fn = "rf_ppo_update_grouped";
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", fn);
+    RF_HIP(hipSetDevice(ctx->device));
+    RF_REQUIRE(policy && d_hyper && d_params && d_state && d_workspace && d_obs && d_actions && d_old_log_probs
+               && d_advantages && d_returns && d_index && d_stats, "%s: NULL argument", fn);
+    rf::PolicyLayout layout;
+    RF_REQUIRE(rf::policy_layout(*policy, layout), RF_POLICY_LIMITS, fn, RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_WIDTH,
+               RF_POLICY_MAX_ACTIONS);
+    RF_REQUIRE(m >= 1 && T >= 1 && rf::population_rows(G, (long long)m * (long long)T),
+               "%s: G = %d must be in 1 .. %d, m = %d and T = %d at least 1 and G m T at most 2^30", fn, G,
+               RF_POPULATION_MAX_GROUPS, m, T);
+    const int N = m * T;
+    RF_REQUIRE(B >= 1 && B <= RF_PPO_MAX_BATCH && B <= N, "%s: B = %d is not in 1 .. min(m T = %d, %d)", fn, B, N,
+               RF_PPO_MAX_BATCH);
+    rf::PpoWork work;
+    RF_REQUIRE(rf::ppo_work(layout, B, work), "%s: no workspace layout for B = %d", fn, B);
+    const size_t groups = (size_t)G, rows = groups * (size_t)N;
+    const size_t state_floats = (size_t)rf::kPpoStateHeader + 2 * (size_t)layout.total;
+    struct Array {
+        const void *p;
+        size_t bytes, align;
+        const char *what;
+    };
+    const Array inputs[] = {{d_obs, rows * (size_t)layout.obs_width * 4, 4, "d_obs"},
+                            {d_actions, rows * 8, 8, "d_actions"},
+                            {d_old_log_probs, rows * 4, 4, "d_old_log_probs"},
+                            {d_advantages, rows * 4, 4, "d_advantages"},
+                            {d_returns, rows * 4, 4, "d_returns"},
+                            {d_index, groups * (size_t)B * 8, 8, "d_index"},
+                            {d_hyper, groups * sizeof(rf_ppo_hyper), 8, "d_hyper"}};
+    const Array outputs[] = {{d_params, groups * (size_t)layout.total * 4, 4, "d_params"},
+                             {d_state, groups * state_floats * 4, 8, "d_state"},
+                             {d_workspace, groups * (size_t)work.total * 4, 8, "d_workspace"},
+                             {d_stats, groups * 32, 4, "d_stats"}};
+    for (const Array &a : inputs)
+        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
+            return rc;
+    for (const Array &a : outputs) {
+        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
+            return rc;
+        for (const Array &b : inputs)
+            RF_REQUIRE(!ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s (an output must not alias an "
+                       "input: other blocks still read it)", fn, a.what, b.what);
+        for (const Array &b : outputs)
+            RF_REQUIRE(&b >= &a || !ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s", fn, a.what, b.what);
+    }
+    const hipStream_t caller = (hipStream_t)caller_stream;
+    if (int rc = refuse_capturing(caller, fn))
+        return rc;
+    // As rf_ppo_update: three launches on the caller's stream, nothing allocated, nothing waited for; the workspace of a
+    // group has the layout of B itself.
+    float *ws = (float *)d_workspace;
+    const rf::PpoHyper *hypers = (const rf::PpoHyper *)d_hyper;
+    const unsigned tiles = (unsigned)((B + rf::kPolicyTile - 1) / rf::kPolicyTile);
+    const auto backward = rf::ppo_backward_kernel<false, true>;
+    hipLaunchKernelGGL(backward, dim3(tiles, 2u, (unsigned)G), dim3(rf::kPpoThreads), 0, caller, layout, work, rf::PpoHyper{},
+                       (const float *)d_params, (const rf::PpoHeader *)d_state, ws, N, d_obs, (const void *)d_actions,
+                       d_old_log_probs, d_advantages, d_returns, B, (const int64_t *)d_index, hypers);
+    RF_HIP(hipGetLastError());
+    hipLaunchKernelGGL(rf::ppo_gradient_kernel<true>, dim3(work.partials, (unsigned)G), dim3(rf::kPpoThreads), 0, caller,
+                       layout, work, ws, B, (const float *)d_params);
+    RF_HIP(hipGetLastError());
+    const unsigned slices = (layout.total + rf::kPpoAdamSlice - 1) / rf::kPpoAdamSlice;
+    hipLaunchKernelGGL(rf::ppo_adam_kernel<true>, dim3(slices + 1u, (unsigned)G), dim3(rf::kPpoThreads), 0, caller,
+                       layout.total, work, rf::PpoHyper{}, d_params, (float *)d_state, (const float *)ws, B, d_stats, hypers);
+    RF_HIP(hipGetLastError());
+    return RF_OK;
 }
 
 int rf_sde_update(rf_ctx *ctx, const rf_policy_desc *policy, const rf_ppo_desc *ppo, float *d_params, void *d_state,
@@ -2644,8 +2808,9 @@ static int lstm_update_any(const char *fn, bool sde, int critic, rf_ctx *ctx, co
     hipLaunchKernelGGL(rf::lstm_ppo_norm_kernel, dim3(work.supers), dim3(rf::kLstmPpoGroup), 0, caller, work, ws);
     RF_HIP(hipGetLastError());
     const unsigned slices = (layout.total + rf::kPpoAdamSlice - 1) / rf::kPpoAdamSlice;
-    hipLaunchKernelGGL(rf::ppo_adam_kernel, dim3(slices + 1u), threads, 0, caller, layout.total,
-                       rf::lstm_ppo_adam_work(work), hyper, d_params, (float *)d_state, (const float *)ws, B, d_stats);
+    hipLaunchKernelGGL(rf::ppo_adam_kernel<false>, dim3(slices + 1u), threads, 0, caller, layout.total,
+                       rf::lstm_ppo_adam_work(work), hyper, d_params, (float *)d_state, (const float *)ws, B, d_stats,
+                       (const rf::PpoHyper *)nullptr);
     RF_HIP(hipGetLastError());
     return RF_OK;
 }

@@ -128,15 +128,35 @@ __device__ __forceinline__ void policy_hidden_tile(const float *__restrict__ par
     }
 }
 
+// kGrouped ("population"): grid (ceil(n / kPolicyTile), nets, G) with n the environments of ONE group.  Block (., ., g) is
+// a block of the ungrouped kernel over group g's rows -- rows [g n, (g + 1) n) of every array -- with the parameters
+// params + g P and the generator gens[g], whose draw number consumed + (row - g n) the row takes.  Tiles are cut per
+// group: none spans two groups, and the ragged last tile of each group computes on zeros.  Ungrouped, gens and consumed
+// are unused and the code is what it was without them.
+template <bool kGrouped>
 __global__ __launch_bounds__(kPolicyThreads) void policy_forward_kernel(
     PolicyLayout L, const float *__restrict__ params, int n, const float *__restrict__ obs,
     const float *__restrict__ final_obs /* or null */, PolicyGen gen, int sampled, int first_net,
     int64_t *__restrict__ actions, float *__restrict__ log_probs, float *__restrict__ values,
-    float *__restrict__ final_values, float *__restrict__ logits)
+    float *__restrict__ final_values, float *__restrict__ logits, const PolicyGen *__restrict__ gens /* [G] or null */,
+    uint64_t consumed)
 {
     __shared__ __align__(16) float s_act[2][kPolicyMaxWidth][kPolicyTile]; // inputs / activations, [k][environment]
     __shared__ float s_logit[kPolicyTile][kPolicyMaxActions];
     __shared__ float s_sum[kPolicyTile][kPolicyMaxActions];
+    if (kGrouped) { // (block-uniform: every pointer moves to the group's piece; null stays null)
+        const size_t g = blockIdx.z, row = g * (size_t)n, cell = row * (size_t)L.obs_width;
+        params += g * (size_t)L.total;
+        obs += cell;
+        final_obs = final_obs != nullptr ? final_obs + cell : nullptr;
+        actions = actions != nullptr ? actions + row : nullptr;
+        log_probs = log_probs != nullptr ? log_probs + row : nullptr;
+        values = values != nullptr ? values + row : nullptr;
+        final_values = final_values != nullptr ? final_values + row : nullptr;
+        logits = logits != nullptr ? logits + row * (size_t)L.n_actions : nullptr;
+        if (sampled)
+            gen = gens[g];
+    }
     const int tid = threadIdx.x;
     const int net = (int)blockIdx.y + first_net;
     const int e0 = (int)blockIdx.x * kPolicyTile;
@@ -185,7 +205,7 @@ __global__ __launch_bounds__(kPolicyThreads) void policy_forward_kernel(
         __syncthreads();
         if (net == 0 && actions != nullptr && tid < kPolicyTile && e0 + tid < n) {
             const int env = e0 + tid;
-            const double u = sampled ? policy_draw(gen.word, (uint64_t)env) : 0.0;
+            const double u = sampled ? policy_draw(gen.word, kGrouped ? consumed + (uint64_t)env : (uint64_t)env) : 0.0;
             int64_t action;
             float log_prob;
             policy_head(&s_logit[tid][0], L.n_actions, !sampled, u, &s_sum[tid][0], &action, &log_prob);

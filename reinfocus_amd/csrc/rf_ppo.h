@@ -46,6 +46,7 @@ struct PpoHyper {
     float clip, ent, vf;
     int normalize;
 };
+static_assert(sizeof(PpoHyper) == sizeof(rf_ppo_hyper) && sizeof(PpoHyper) == 56, "rf_ppo_hyper is PpoHyper (population)");
 
 // false: a hyper-parameter is negative or not finite, or a beta is outside [0, 1)
 RF_HD bool ppo_hyper(const rf_ppo_desc &d, PpoHyper &h)
@@ -112,6 +113,32 @@ RF_HD bool ppo_work(const PolicyLayout &L, int max_batch, PpoWork &w)
     w.max_batch = rows;
     w.total = at;
     return true;
+}
+
+// "population": G groups of `rows` rows each; false outside the limits of the definition
+RF_HD bool population_rows(int G, long long rows)
+{
+    return G >= 1 && G <= RF_POPULATION_MAX_GROUPS && rows >= 1 && (long long)G * rows <= (1ll << 30);
+}
+
+// What rf_ppo_grouped_state_size and rf_ppo_grouped_workspace_size return for a ctx (0: refused): G times the ungrouped
+// sizes, for minibatches of B out of the m T rows of a group
+RF_HD unsigned long long population_state_bytes(const rf_policy_desc &d, int G, int m)
+{
+    PolicyLayout L;
+    if (!policy_layout(d, L) || !population_rows(G, m))
+        return 0;
+    return (unsigned long long)G * (4ull * kPpoStateHeader + 8ull * L.total);
+}
+
+RF_HD unsigned long long population_workspace_bytes(const rf_policy_desc &d, int G, int m, int T, int B)
+{
+    PolicyLayout L;
+    PpoWork W;
+    if (!policy_layout(d, L) || m < 1 || T < 1 || !population_rows(G, (long long)m * (long long)T)
+        || (long long)B > (long long)m * (long long)T || !ppo_work(L, B, W))
+        return 0;
+    return (unsigned long long)G * 4ull * W.total;
 }
 
 RF_HD int64_t ppo_clamp(int64_t i, int64_t n)
@@ -416,13 +443,32 @@ __device__ __forceinline__ void ppo_store_tile(float *__restrict__ out, const fl
 
 // kSde: the Gaussian head of "sde policy" (L from sde_layout; actions float32 [N]) in place of the Categorical one
 // (actions int64 [N])
-template <bool kSde>
+// kGrouped ("population", all three kernels): a group dimension on the grid (blockIdx.z here, blockIdx.y in the other two).
+// A block of group g is a block of the ungrouped kernel over the group's own N rows (rows [g N, (g + 1) N) of every
+// array), parameters params + g P, optimizer state + g (kPpoStateHeader + 2 P) floats (`header` is the first group's),
+// workspace ws + g W.total (W.total is even: float64 data stays aligned), hyper-parameters hypers[g], index + g B (rows
+// local to the group) and stats + 8 g.  No block reads what a block of another group writes.  Ungrouped, hypers is unused
+// and the code is what it was without it.
+template <bool kSde, bool kGrouped = false>
 __global__ __launch_bounds__(kPpoThreads) void ppo_backward_kernel(
     PolicyLayout L, PpoWork W, PpoHyper hy, const float *__restrict__ params, const PpoHeader *__restrict__ header,
     float *__restrict__ ws, int N, const float *__restrict__ obs, const void *__restrict__ actions_any,
     const float *__restrict__ old_log_probs, const float *__restrict__ advantages, const float *__restrict__ returns,
-    int B, const int64_t *__restrict__ index)
+    int B, const int64_t *__restrict__ index, const PpoHyper *__restrict__ hypers /* [G] or null */)
 {
+    static_assert(!(kSde && kGrouped), "a population has the Categorical head");
+    if (kGrouped) { // (block-uniform)
+        const size_t g = blockIdx.z, row = g * (size_t)N;
+        hy = hypers[g];
+        params += g * (size_t)L.total;
+        header = reinterpret_cast<const PpoHeader *>(reinterpret_cast<const float *>(header)
+                                                     + g * ((size_t)kPpoStateHeader + 2 * (size_t)L.total));
+        ws += g * (size_t)W.total;
+        obs += row * (size_t)L.obs_width;
+        actions_any = static_cast<const int64_t *>(actions_any) + row;
+        old_log_probs += row, advantages += row, returns += row;
+        index += g * (size_t)B;
+    }
     __shared__ __align__(16) float s_act[2][kPolicyMaxWidth][kPolicyTile];   // inputs / activations, [k][sample]
     __shared__ __align__(16) float s_delta[2][kPolicyMaxWidth][kPolicyTile]; // deltas of the hidden layers
     __shared__ __align__(16) float s_head[kPolicyMaxActions][kPolicyTile];   // deltas of the head, [o][sample]
@@ -556,10 +602,15 @@ __global__ __launch_bounds__(kPpoThreads) void ppo_backward_kernel(
     }
 }
 
+template <bool kGrouped>
 __global__ __launch_bounds__(kPpoThreads) void ppo_gradient_kernel(PolicyLayout L, PpoWork W, float *__restrict__ ws, int B,
                                                                    const float *__restrict__ params)
 {
     __shared__ double s_red[kPpoLeaves];
+    if (kGrouped) {
+        ws += (size_t)blockIdx.y * (size_t)W.total;
+        params += (size_t)blockIdx.y * (size_t)L.total;
+    }
     const int tid = threadIdx.x;
     const unsigned p = blockIdx.x * (unsigned)kPpoLeaves + (unsigned)tid;
     double square = 0.0;
@@ -579,11 +630,21 @@ __global__ __launch_bounds__(kPpoThreads) void ppo_gradient_kernel(PolicyLayout 
         reinterpret_cast<double *>(ws + W.partial)[blockIdx.x] = s_red[0];
 }
 
+template <bool kGrouped>
 __global__ __launch_bounds__(kPpoThreads) void ppo_adam_kernel(unsigned P, PpoWork W, PpoHyper hy, float *__restrict__ params,
                                                                float *__restrict__ state, const float *__restrict__ ws,
-                                                               int B, float *__restrict__ stats)
+                                                               int B, float *__restrict__ stats,
+                                                               const PpoHyper *__restrict__ hypers /* [G] or null */)
 {
     __shared__ double s_red[kPpoMaxPartials];
+    if (kGrouped) {
+        const size_t g = blockIdx.y;
+        hy = hypers[g];
+        params += g * (size_t)P;
+        state += g * ((size_t)kPpoStateHeader + 2 * (size_t)P);
+        ws += g * (size_t)W.total;
+        stats += 8 * g;
+    }
     const int tid = threadIdx.x;
     const double *partial = reinterpret_cast<const double *>(ws + W.partial);
     const int size = ppo_pow2((int)W.partials);

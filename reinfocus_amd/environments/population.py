@@ -1,0 +1,547 @@
+"""A population of G independent PPO learners in lock-step over ONE vector environment of n = G m lanes: seed sweeps, the
+reference's side-by-side hyper-parameter trials (where they share an architecture), population-based training.  The
+reference trains with n_envs 8; at 8 environments a forward is one or two blocks and an update three launch-bound kernels,
+so G separate policy / learner objects cost G (1 + 3 updates) launches per iteration on an idle device.  Here every stage
+of all G learners is one launch.
+
+One definition (include/reinfocus_hip.h, "population"): the arithmetic of a group is exactly that of "policy" and "ppo
+update"; only addressing changes.  Group g owns environments [g m, (g + 1) m), parameters params[g], its own generator,
+optimizer state, hyper-parameters and stats, and rows [g m T, (g + 1) m T) of a rollout's flat() (which orders rows
+e T + t, so the rows of consecutive environments are contiguous).
+
+    PopulationPolicy         the numpy twin: literally G policy.Policy over slices, and the oracle
+    PopulationLearner        the numpy twin: literally G learner.Learner over slices
+    DevicePopulationPolicy   act / values over all n rows in ONE launch (rf_policy_forward_grouped); spec.kind is the mlp
+                             kind, so Rollout.collect / DeviceRollout.collect take it as they take a Policy / DevicePolicy
+    DevicePopulationLearner  update / train: three launches per minibatch whatever G is (rf_ppo_update_grouped)
+
+The Categorical head (MlpPolicySpec) only.  Out of scope: per-group gamma / gae_lambda (the rollout's GAE keeps its
+scalars), per-group LearnerView statistics (with learner_view= the running moments are taken over all lanes: groups share
+one normaliser), the sde, lstm and lstm-sde heads, groups that differ in architecture, m, T or batch size.
+
+torch is imported lazily, by the device classes only (reinfocus_amd/torch_interop.py says why import order matters).
+"""
+
+import numpy as np
+
+from reinfocus_amd.environments import learner as learner_module
+from reinfocus_amd.environments import policy as policy_module
+from reinfocus_amd.environments.learner import MAX_BATCH, STATE_HEADER, f64
+from reinfocus_amd.environments.policy import DETERMINISTIC, f32
+
+MAX_GROUPS = 65535  # RF_POPULATION_MAX_GROUPS
+# rf_ppo_hyper: what one group's kernels read of its hyper-parameters (56 bytes)
+HYPER_RECORD = np.dtype([("learning_rate", f64), ("max_grad_norm", f64), ("beta1", f64), ("beta2", f64), ("adam_eps", f64),
+                         ("clip_range", f32), ("ent_coef", f32), ("vf_coef", f32), ("normalize_advantage", np.int32)])
+assert HYPER_RECORD.itemsize == 56
+
+
+def _checked_population(spec, groups, seeds):
+    if getattr(spec, "kind", None) != policy_module.MlpPolicySpec.kind:
+        raise ValueError(f"a population has the Categorical head of MlpPolicySpec, not a spec of kind "
+                         f"{getattr(spec, 'kind', None)!r}: the sde and lstm heads are out of scope")
+    groups = int(groups)
+    if not 1 <= groups <= MAX_GROUPS:
+        raise ValueError(f"groups {groups} is not in 1 .. {MAX_GROUPS}")
+    seeds = list(seeds) if isinstance(seeds, (list, tuple, np.ndarray)) else None
+    if seeds is None or len(seeds) != groups:
+        raise ValueError(f"seeds must be a sequence of one seed per group ({groups}), not "
+                         f"{'a scalar' if seeds is None else len(seeds)}")
+    return groups, seeds
+
+
+def _per_group(lanes, groups):
+    """m of n = G m; ValueError where the groups do not divide the lanes."""
+    if lanes < groups or lanes % groups != 0:
+        raise ValueError(f"{lanes} environments are not divisible into {groups} groups of at least one")
+    return lanes // groups
+
+
+def per_group(value, groups, name):
+    """`value` as a list of one entry per group: a scalar for all, or a sequence of length G."""
+    if isinstance(value, (list, tuple, np.ndarray)):
+        if len(value) != groups:
+            raise ValueError(f"{name} has {len(value)} entries, the population {groups} groups")
+        return list(value)
+    return [value] * groups
+
+
+def _betas_per_group(betas, groups):
+    betas = list(betas)
+    if len(betas) == 2 and not any(isinstance(b, (list, tuple, np.ndarray)) for b in betas):
+        return [tuple(betas)] * groups
+    if len(betas) != groups or not all(len(b) == 2 for b in betas):
+        raise ValueError(f"betas is a pair, or one pair per group ({groups})")
+    return [tuple(b) for b in betas]
+
+
+class _GroupHyper:
+    """The hyper-parameters as plain attributes, each a scalar (for every group) or a sequence of one value per group;
+    they may be changed between calls."""
+
+    def _configure(self, learning_rate, clip_range, ent_coef, vf_coef, max_grad_norm, normalize_advantage, betas, adam_eps):
+        self.learning_rate, self.clip_range, self.ent_coef, self.vf_coef = learning_rate, clip_range, ent_coef, vf_coef
+        self.max_grad_norm, self.normalize_advantage, self.betas, self.adam_eps = (max_grad_norm, normalize_advantage,
+                                                                                   betas, adam_eps)
+        self.hypers()
+
+    def hypers(self):
+        """One learner.Hyper per group; ValueError for what rf_ppo_update refuses or a sequence of the wrong length."""
+        groups = self.groups
+        columns = [per_group(getattr(self, name), groups, name)
+                   for name in ("learning_rate", "clip_range", "ent_coef", "vf_coef", "max_grad_norm")]
+        betas = _betas_per_group(self.betas, groups)
+        eps = per_group(self.adam_eps, groups, "adam_eps")
+        normalize = per_group(self.normalize_advantage, groups, "normalize_advantage")
+        return [learner_module.checked_hyper((*(column[g] for column in columns), betas[g][0], betas[g][1], eps[g],
+                                              normalize[g])) for g in range(groups)]
+
+    def _batches(self, rows, n_epochs, batch_size):
+        n_epochs, batch_size = int(n_epochs), int(batch_size)
+        if n_epochs < 1 or not 1 <= batch_size <= MAX_BATCH:
+            raise ValueError(f"n_epochs {n_epochs} must be at least 1 and batch_size {batch_size} in 1 .. {MAX_BATCH}")
+        if batch_size > rows:
+            raise ValueError(f"batch_size {batch_size} is more than the {rows} rows (m T) of one group")
+        return n_epochs, batch_size, -(-rows // batch_size)
+
+
+def hyper_records(hypers):
+    """The G rf_ppo_hyper records of a list of learner.Hyper, as the kernels read them."""
+    records = np.zeros(len(hypers), dtype=HYPER_RECORD)
+    for g, hyper in enumerate(hypers):
+        records[g] = (hyper.learning_rate, hyper.max_grad_norm, hyper.beta1, hyper.beta2, hyper.adam_eps,
+                      f32(hyper.clip_range), f32(hyper.ent_coef), f32(hyper.vf_coef), hyper.normalize_advantage)
+    return records
+
+
+class PopulationPolicy:
+    """The numpy twin of DevicePopulationPolicy, and its oracle: G policy.Policy, group g seeded with seeds[g], over
+    slices of the rows.  `params` is one array [G][P]; policies[g].params is its row g."""
+
+    def __init__(self, spec, groups, seeds):
+        self.groups, seeds = _checked_population(spec, groups, seeds)
+        self.spec = spec
+        self.params = np.zeros((self.groups, spec.size), dtype=f32)
+        self.policies = [policy_module.Policy(spec, seed) for seed in seeds]
+        for g, member in enumerate(self.policies):
+            member.params = self.params[g]
+
+    def _groups_of(self, group):
+        if group is None:
+            return range(self.groups)
+        if not 0 <= int(group) < self.groups:
+            raise IndexError(f"group {group} is not in 0 .. {self.groups - 1}")
+        return [int(group)]
+
+    def load_state_dict(self, state_dict, group=None):
+        """Into group `group`, or into every group with None."""
+        packed = self.spec.pack(state_dict)
+        for g in self._groups_of(group):
+            self.params[g] = packed
+
+    def state_dict(self, group=0):
+        return self.spec.unpack(self.params[self._groups_of(group)[0]])
+
+    def _split(self, obs, final_obs):
+        obs = np.asarray(obs, dtype=f32).reshape(-1, self.spec.obs_width)
+        m = _per_group(obs.shape[0], self.groups)
+        if final_obs is not None:
+            final_obs = np.asarray(final_obs, dtype=f32).reshape(obs.shape)
+        return [(obs[g * m:(g + 1) * m], None if final_obs is None else final_obs[g * m:(g + 1) * m])
+                for g in range(self.groups)]
+
+    def act(self, obs, final_obs=None, deterministic=False):
+        """(actions int64 [n], values, log_probs, final_values or None) over all n = G m rows: group g's rows by
+        policies[g], which draws m of its own generator's numbers unless deterministic."""
+        parts = [member.act(rows, final_rows, deterministic)
+                 for member, (rows, final_rows) in zip(self.policies, self._split(obs, final_obs))]
+        return tuple(None if parts[0][i] is None else np.concatenate([part[i] for part in parts]) for i in range(4))
+
+    def values(self, obs, final_obs=None):
+        parts = [member.values(rows, final_rows)
+                 for member, (rows, final_rows) in zip(self.policies, self._split(obs, final_obs))]
+        if final_obs is None:
+            return np.concatenate(parts)
+        return np.concatenate([part[0] for part in parts]), np.concatenate([part[1] for part in parts])
+
+    def rng_state(self):
+        """The G generator states, in group order."""
+        return [member.rng_state() for member in self.policies]
+
+    def set_rng_state(self, states):
+        states = list(states)
+        if len(states) != self.groups:
+            raise ValueError(f"{len(states)} generator states for {self.groups} groups")
+        for member, state in zip(self.policies, states):
+            member.set_rng_state(state)
+
+
+class PopulationLearner(_GroupHyper):
+    """The numpy twin of DevicePopulationLearner, and its oracle: G learner.Learner, learners[g] over policies[g] and the
+    group's rows."""
+
+    def __init__(self, policy, learning_rate=3e-4, clip_range=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5,
+                 normalize_advantage=True, betas=(0.9, 0.999), adam_eps=1e-5):
+        if not isinstance(policy, PopulationPolicy):
+            raise TypeError(f"PopulationLearner needs a PopulationPolicy, not {type(policy).__name__} (a "
+                            "DevicePopulationPolicy has DevicePopulationLearner)")
+        self.policy, self.spec, self.groups = policy, policy.spec, policy.groups
+        self._configure(learning_rate, clip_range, ent_coef, vf_coef, max_grad_norm, normalize_advantage, betas, adam_eps)
+        self.learners = [learner_module.Learner(member) for member in policy.policies]
+
+    def _hand_down(self):
+        for member, hyper in zip(self.learners, self.hypers()):
+            member.learning_rate, member.clip_range, member.ent_coef, member.vf_coef = hyper[:4]
+            member.max_grad_norm, member.betas, member.adam_eps = hyper.max_grad_norm, (hyper.beta1, hyper.beta2), hyper.adam_eps
+            member.normalize_advantage = bool(hyper.normalize_advantage)
+
+    def _pieces(self, flat):
+        rows = _per_group(np.asarray(flat["actions"]).shape[0], self.groups)
+        return rows, [{key: np.asarray(flat[key])[g * rows:(g + 1) * rows] for key in learner_module.BATCH_KEYS}
+                      for g in range(self.groups)]
+
+    def update(self, flat, index):
+        """One minibatch update of every group: index int64 [G][B] of rows local to each group's piece of flat().
+        Returns the stats float32 [G][8]."""
+        index = np.asarray(index, dtype=np.int64)
+        if index.ndim != 2 or index.shape[0] != self.groups:
+            raise ValueError(f"index has shape {index.shape}, not ({self.groups}, B)")
+        rows, pieces = self._pieces(flat)
+        if index.shape[1] > rows:
+            raise ValueError(f"a minibatch of {index.shape[1]} is more than the {rows} rows of one group")
+        self._hand_down()
+        return np.stack([member.update(piece, index[g]) for g, (member, piece) in enumerate(zip(self.learners, pieces))])
+
+    def train(self, rollout, n_epochs, batch_size, permutations=None, generator=None):
+        """n_epochs passes of every group over its rows of a finished rollout, in minibatches of batch_size (the last one
+        may be shorter): stats float32 [n_epochs * ceil(m T / batch_size)][G][8].  Per epoch and group one permutation of
+        the group's m T local rows: permutations[epoch][g] (int64 [n_epochs][G][m T]) if given, else
+        generator.permutation(m T), drawn epoch by epoch and in group order."""
+        policy_module._refuse_box(rollout.env.single_action_space)
+        flat = rollout.flat()
+        rows = _per_group(np.asarray(flat["actions"]).shape[0], self.groups)
+        n_epochs, batch_size, per_epoch = self._batches(rows, n_epochs, batch_size)
+        if permutations is not None:
+            permutations = np.asarray(permutations, dtype=np.int64).reshape(n_epochs, self.groups, rows)
+        elif generator is None:
+            generator = np.random.default_rng()
+        stats = np.zeros((n_epochs * per_epoch, self.groups, 8), dtype=f32)
+        for epoch in range(n_epochs):
+            order = permutations[epoch] if permutations is not None else np.stack(
+                [generator.permutation(rows).astype(np.int64) for _ in range(self.groups)])
+            for i in range(per_epoch):
+                stats[epoch * per_epoch + i] = self.update(flat, order[:, i * batch_size:(i + 1) * batch_size])
+        return stats
+
+    def state_dict(self):
+        """The G optimizers: lists step, bc1, bc2 and arrays m, v [G][P]."""
+        parts = [member.state_dict() for member in self.learners]
+        return {"step": [part["step"] for part in parts], "bc1": [part["bc1"] for part in parts],
+                "bc2": [part["bc2"] for part in parts], "m": np.stack([part["m"] for part in parts]),
+                "v": np.stack([part["v"] for part in parts])}
+
+    def load_state_dict(self, state):
+        for g, member in enumerate(self.learners):
+            member.load_state_dict({"step": state["step"][g], "bc1": state["bc1"][g], "bc2": state["bc2"][g],
+                                    "m": np.asarray(state["m"])[g], "v": np.asarray(state["v"])[g]})
+
+
+class DevicePopulationPolicy:
+    """The policies of G groups of m environments each of one device-resident environment (n = G m), over torch tensors on
+    its GPU; used as PopulationPolicy is and bit for bit equal to it, group by group equal to a stand-alone
+    DevicePolicy(seed=seeds[g]) over the group's m environments.
+
+    Every act() / values() is ONE launch (rf_policy_forward_grouped), grid (ceil(m / 8), nets, G).  `params` is one
+    float32 tensor [G][P].  The generators' words live in a device table written at seeding and at set_rng_state only;
+    the number of draws each generator has given travels by value (every sampled act() takes m of each), so no call
+    copies or waits.  rng_state() is computed on the host from the seeds and that count."""
+
+    _device_env = policy_module.DevicePolicy._device_env
+    _rows = policy_module.DevicePolicy._rows
+    _out = policy_module.DevicePolicy._out
+
+    def __init__(self, env, spec, groups, seeds):
+        self._device_env(env)
+        policy_module._refuse_box(env.single_action_space)
+        self.groups, seeds = _checked_population(spec, groups, seeds)
+        if env.single_action_space.n != spec.n_actions:
+            raise ValueError(f"the spec has {spec.n_actions} actions, the environment {env.single_action_space.n}")
+        self.num_envs = int(env.num_envs)
+        self.per_group = _per_group(self.num_envs, self.groups)
+        self._io = env._tensor_io()  # (ValueError, as step_tensors': a host initializer, a render_mode)
+        from reinfocus_amd import torch_interop
+
+        self._interop = torch_interop
+        torch = self._torch = torch_interop._torch()
+        self.spec = spec
+        self._ctx = env._ctx
+        self.device = torch.device("cuda", self._ctx.device)
+        self.params = torch.zeros((self.groups, spec.size), dtype=torch.float32, device=self.device)
+        self._owned = {}
+        self._table = torch.zeros((self.groups, 4), dtype=torch.int64, device=self.device)  # (the bits of uint64 words)
+        self._set_generators([np.random.PCG64DXSM(seed) for seed in seeds])
+
+    def _set_generators(self, generators):
+        self._generators, self._consumed = generators, 0
+        words = np.array([policy_module.generator_words(generator) for generator in generators], dtype=np.uint64)
+        self._table.copy_(self._torch.from_numpy(words.view(np.int64)))
+
+    def rng_state(self):
+        """What G stand-alone policies would return, in group order: each seed's generator advanced by the draws taken."""
+        states = []
+        for generator in self._generators:
+            now = np.random.PCG64DXSM()
+            now.state = generator.state
+            states.append(now.advance(self._consumed).state)
+        return states
+
+    def set_rng_state(self, states):
+        states = list(states)
+        if len(states) != self.groups:
+            raise ValueError(f"{len(states)} generator states for {self.groups} groups")
+        generators = []
+        for state in states:
+            generator = np.random.PCG64DXSM()
+            generator.state = state
+            generators.append(generator)
+        self._set_generators(generators)
+
+    _groups_of = PopulationPolicy._groups_of
+
+    def load_state_dict(self, state_dict, group=None):
+        """Device tensors in SB3's names and shapes into group `group`, or into every group with None."""
+        torch = self._torch
+        groups = self._groups_of(group)
+        for name in state_dict:
+            tensor = state_dict[name]
+            if not isinstance(tensor, torch.Tensor) or tensor.dtype != torch.float32:
+                raise TypeError(f"{name} must be a torch.float32 tensor on {self.device}")
+            self._io._on_device(tensor, name)
+        with torch.no_grad():
+            for name, at, shape, is_weight in self.spec.checked(state_dict, lambda t: t.shape):
+                tensor = state_dict[name].detach()
+                for g in groups:
+                    self.params[g, at:at + tensor.numel()].view(shape).copy_(tensor.t() if is_weight else tensor)
+
+    def state_dict(self, group=0):
+        """Group `group`'s parameters as device tensors in SB3's names and shapes (copies)."""
+        row = self.params[self._groups_of(group)[0]]
+        out = {}
+        for name, at, shape, is_weight in self.spec.entries:
+            view = row[at:at + int(np.prod(shape))].view(shape)
+            out[name] = view.t().clone(memory_format=self._torch.contiguous_format) if is_weight else view.clone()
+        return out
+
+    def _all_rows(self, obs, final_obs):
+        obs = self._rows(obs, "obs")
+        if obs.shape[0] != self.num_envs:
+            raise ValueError(f"obs has {obs.shape[0]} rows, the population {self.groups} groups of {self.per_group} "
+                             f"environments ({self.num_envs})")
+        if final_obs is not None and self._rows(final_obs, "final_obs").shape != obs.shape:
+            raise ValueError(f"final_obs has shape {tuple(final_obs.shape)}, obs {tuple(obs.shape)}")
+        return obs
+
+    def _forward(self, obs, final_obs, sampled, flags, actions, log_probs, values, final_values):
+        self._interop.check_one_runtime()
+        pointer = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        self._ctx.policy_forward_grouped(self.spec.desc(), self.groups, self.per_group, self.params.data_ptr(),
+                                         obs.data_ptr(), pointer(final_obs), self._table.data_ptr() if sampled else None,
+                                         self._consumed, flags, pointer(actions), pointer(log_probs), pointer(values),
+                                         pointer(final_values), None, self._io._stream())
+
+    def act(self, obs, final_obs=None, deterministic=False, out=None):
+        """DevicePolicy.act over all n = G m rows, group g's rows with params[g] and its own generator.  One launch; a
+        sampled call takes m draws of every generator."""
+        torch = self._torch
+        obs = self._all_rows(obs, final_obs)
+        n = self.num_envs
+        given = (None,) * 4 if out is None else tuple(out)
+        if len(given) != 4:
+            raise TypeError("out must be (actions, values, log_probs, final_values or None)")
+        actions = self._out("actions", given[0], n, torch.int64)
+        values = self._out("values", given[1], n, torch.float32)
+        log_probs = self._out("log_probs", given[2], n, torch.float32)
+        final_values = None if final_obs is None else self._out("final_values", given[3], n, torch.float32)
+        self._forward(obs, final_obs, not deterministic, DETERMINISTIC if deterministic else 0, actions, log_probs, values,
+                      final_values)
+        if not deterministic:
+            self._consumed += self.per_group  # (after the call was taken: a refused call consumes nothing)
+        return actions, values, log_probs, final_values
+
+    def values(self, obs, final_obs=None, out=None):
+        """DevicePolicy.values over all n rows.  One launch, no draw."""
+        torch = self._torch
+        obs = self._all_rows(obs, final_obs)
+        given = (None, None) if out is None else tuple(out)
+        if len(given) != 2:
+            raise TypeError("out must be (values, final_values or None)")
+        values = self._out("last_values", given[0], self.num_envs, torch.float32)
+        final_values = None if final_obs is None else self._out("final_values", given[1], self.num_envs, torch.float32)
+        self._forward(obs, final_obs, False, 0, None, None, values, final_values)
+        return values if final_obs is None else (values, final_values)
+
+
+class DevicePopulationLearner(_GroupHyper):
+    """The learners of a DevicePopulationPolicy, over torch tensors on its GPU; used as PopulationLearner is and bit for
+    bit equal to it.  update() is rf_ppo_update_grouped: three launches on torch's current stream whatever G is, which
+    change policy.params in place.  The hyper-parameters are packed into one device tensor (G rf_ppo_hyper) when an
+    update is enqueued, from pinned memory and only when they changed.  train() enqueues every update of every epoch back
+    to back.  No method synchronises the host (state_dict() reads the steps and does)."""
+
+    def __init__(self, policy, learning_rate=3e-4, clip_range=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5,
+                 normalize_advantage=True, betas=(0.9, 0.999), adam_eps=1e-5):
+        if not isinstance(policy, DevicePopulationPolicy):
+            raise TypeError(f"DevicePopulationLearner needs a DevicePopulationPolicy, not {type(policy).__name__} (a "
+                            "PopulationPolicy has PopulationLearner, a DevicePolicy DeviceLearner)")
+        self.policy, self.spec, self.groups = policy, policy.spec, policy.groups
+        self._configure(learning_rate, clip_range, ent_coef, vf_coef, max_grad_norm, normalize_advantage, betas, adam_eps)
+        self._torch, self._interop, self._io, self._ctx = policy._torch, policy._interop, policy._io, policy._ctx
+        self.device = policy.device
+        torch = self._torch
+        self._state_floats = STATE_HEADER + 2 * self.spec.size
+        if self._ctx.ppo_grouped_state_size(self.spec.desc(), self.groups, policy.per_group) \
+                != 4 * self.groups * self._state_floats:
+            raise RuntimeError("rf_ppo_grouped_state_size disagrees with the packed optimizer states")
+        self.state = torch.zeros((self.groups, self._state_floats), dtype=torch.float32, device=self.device)
+        self._workspace, self._workspace_key = None, None
+        self._stats = None
+        self._hyper, self._hyper_key = None, None
+
+    def _packed_hyper(self):
+        """The device tensor of G rf_ppo_hyper (as float64 words: 8-byte aligned), rewritten when an attribute changed."""
+        torch = self._torch
+        hypers = self.hypers()
+        key = tuple(hypers)
+        if key != self._hyper_key:
+            words = torch.from_numpy(hyper_records(hypers).view(f64).copy()).pin_memory()
+            if self._hyper is None:
+                self._hyper = torch.zeros(words.numel(), dtype=torch.float64, device=self.device)
+            self._hyper.copy_(words, non_blocking=True)  # (stream-ordered: updates enqueued before keep what they read)
+            self._hyper_key = key
+        return self._hyper
+
+    def _checked(self, flat, index):
+        """(steps T, batch B) of flat() tensors of G m T rows and an index [G][B]."""
+        torch = self._torch
+        wanted = {"observations": torch.float32, "actions": torch.int64, "log_probs": torch.float32,
+                  "advantages": torch.float32, "returns": torch.float32}
+        total = None
+        for key, dtype in wanted.items():
+            tensor = flat[key]
+            if not isinstance(tensor, torch.Tensor):
+                raise TypeError(f"{key} must be a torch.Tensor on {self.device}, not {type(tensor).__name__}")
+            self._io._on_device(tensor, key)
+            shape = (tensor.shape[0], self.spec.obs_width) if key == "observations" else (tensor.shape[0],)
+            if tensor.dtype != dtype or tuple(tensor.shape) != shape or not tensor.is_contiguous():
+                raise ValueError(f"{key} is {tensor.dtype} {tuple(tensor.shape)}, not contiguous {dtype} {shape}")
+            if total is not None and tensor.shape[0] != total:
+                raise ValueError(f"{key} has {tensor.shape[0]} rows, the others {total}")
+            total = tensor.shape[0]
+        lanes = self.policy.num_envs
+        if total < lanes or total % lanes != 0:
+            raise ValueError(f"flat() has {total} rows, no multiple of the population's {lanes} environments")
+        steps = total // lanes
+        if not isinstance(index, torch.Tensor):
+            raise TypeError(f"index must be a torch.Tensor on {self.device}, not {type(index).__name__}")
+        self._io._on_device(index, "index")
+        rows = steps * self.policy.per_group
+        if index.dtype != torch.int64 or index.dim() != 2 or index.shape[0] != self.groups or not index.is_contiguous() \
+                or not 1 <= index.shape[1] <= min(MAX_BATCH, rows):
+            raise ValueError(f"index is {index.dtype} {tuple(index.shape)}, not contiguous torch.int64 ({self.groups}, "
+                             f"1 .. {min(MAX_BATCH, rows)})")
+        return steps, index.shape[1]
+
+    def _room(self, steps, batch):
+        key = (steps, batch)
+        if key != self._workspace_key:
+            size = self._ctx.ppo_grouped_workspace_size(self.spec.desc(), self.groups, self.policy.per_group, steps, batch)
+            if size == 0:
+                raise RuntimeError(f"rf_ppo_grouped_workspace_size refuses minibatches of {batch} out of "
+                                   f"{steps * self.policy.per_group} rows")
+            if self._workspace is None or self._workspace.numel() < size // 4:
+                self._workspace = self._torch.zeros(size // 4, dtype=self._torch.float32, device=self.device)
+            self._workspace_key = key
+
+    def _enqueue(self, flat, steps, index, stats, hyper):
+        self._ctx.ppo_update_grouped(self.spec.desc(), self.groups, self.policy.per_group, steps, hyper.data_ptr(),
+                                     self.policy.params.data_ptr(), self.state.data_ptr(), self._workspace.data_ptr(),
+                                     flat["observations"].data_ptr(), flat["actions"].data_ptr(),
+                                     flat["log_probs"].data_ptr(), flat["advantages"].data_ptr(),
+                                     flat["returns"].data_ptr(), index.shape[1], index.data_ptr(), stats.data_ptr(),
+                                     self._io._stream())
+
+    def update(self, flat, index):
+        """One minibatch update of every group from rows index[g] (int64 device tensor [G][B], local to the group) of its
+        piece of flat(); returns the stats, a float32 [G][8] tensor the learner owns and the next update() overwrites."""
+        steps, batch = self._checked(flat, index)
+        self._interop.check_one_runtime()
+        self._room(steps, batch)
+        if self._stats is None:
+            self._stats = self._torch.zeros((self.groups, 8), dtype=self._torch.float32, device=self.device)
+        self._enqueue(flat, steps, index, self._stats, self._packed_hyper())
+        return self._stats
+
+    def train(self, rollout, n_epochs, batch_size, permutations=None, generator=None):
+        """As PopulationLearner.train, over a finished DeviceRollout of the policy's GPU: permutations is an int64 device
+        tensor [n_epochs][G][m T] of local rows, else per epoch one device permutation per group (the argsort of one
+        uniform draw [G][m T]; generator: a torch.Generator of that device).  Returns the stats as one device tensor
+        [n_epochs * ceil(m T / batch_size)][G][8].  Nothing waits for the host."""
+        torch = self._torch
+        policy_module._refuse_box(rollout.env.single_action_space)
+        if getattr(rollout, "device", None) != self.device:
+            raise ValueError(f"the rollout lives on {getattr(rollout, 'device', 'the host')}, the policy on {self.device}")
+        flat = rollout.flat()
+        total = flat["actions"].shape[0]
+        rows = _per_group(total, self.groups)
+        n_epochs, batch_size, per_epoch = self._batches(rows, n_epochs, batch_size)
+        if permutations is not None:
+            if not isinstance(permutations, torch.Tensor) or permutations.dtype != torch.int64 \
+                    or tuple(permutations.shape) != (n_epochs, self.groups, rows) or not permutations.is_contiguous():
+                raise ValueError(f"permutations must be a contiguous torch.int64 tensor ({n_epochs}, {self.groups}, {rows})")
+            self._io._on_device(permutations, "permutations")
+        full = rows // batch_size
+
+        def minibatches(order):
+            """The epoch's index tensors [G][B], each contiguous: the full ones from one copy, then the short one."""
+            cut = order[:, :full * batch_size].reshape(self.groups, full, batch_size).transpose(0, 1).contiguous()
+            return [cut[i] for i in range(full)] + ([order[:, full * batch_size:].contiguous()] if per_epoch > full else [])
+
+        first = minibatches(permutations[0] if permutations is not None
+                            else torch.zeros((self.groups, rows), dtype=torch.int64, device=self.device))
+        steps, _ = self._checked(flat, first[0])
+        self._interop.check_one_runtime()
+        hyper = self._packed_hyper()
+        stats = torch.zeros((n_epochs * per_epoch, self.groups, 8), dtype=torch.float32, device=self.device)
+        for epoch in range(n_epochs):
+            if permutations is not None:
+                batches = first if epoch == 0 else minibatches(permutations[epoch])
+            else:
+                batches = minibatches(torch.argsort(torch.rand((self.groups, rows), device=self.device,
+                                                               generator=generator), dim=1))
+            for i, index in enumerate(batches):
+                self._room(steps, index.shape[1])
+                self._enqueue(flat, steps, index, stats[epoch * per_epoch + i], hyper)
+        return stats
+
+    def state_dict(self):
+        """The G optimizers: lists step, bc1, bc2 (read from the device: this synchronises) and clones of m, v [G][P]."""
+        head = self.state[:, :STATE_HEADER].contiguous().cpu().numpy()
+        size = self.spec.size
+        return {"step": [int(row.view(np.int64)[0]) for row in head], "bc1": [float(row.view(f64)[1]) for row in head],
+                "bc2": [float(row.view(f64)[2]) for row in head],
+                "m": self.state[:, STATE_HEADER:STATE_HEADER + size].clone(), "v": self.state[:, STATE_HEADER + size:].clone()}
+
+    def load_state_dict(self, state):
+        torch = self._torch
+        size = self.spec.size
+        for key in ("m", "v"):
+            tensor = state[key]
+            if not isinstance(tensor, torch.Tensor) or tensor.dtype != torch.float32 or tensor.numel() != self.groups * size:
+                raise ValueError(f"{key} must be a torch.float32 tensor ({self.groups}, {size}) on {self.device}")
+            self._io._on_device(tensor, key)
+        heads = np.stack([learner_module.pack_state(self.spec, int(state["step"][g]), float(state["bc1"][g]),
+                                                    float(state["bc2"][g]), 0.0, 0.0)[:STATE_HEADER]
+                          for g in range(self.groups)])
+        self.state[:, :STATE_HEADER].copy_(torch.from_numpy(heads.copy()))
+        self.state[:, STATE_HEADER:STATE_HEADER + size].copy_(state["m"].reshape(self.groups, size))
+        self.state[:, STATE_HEADER + size:].copy_(state["v"].reshape(self.groups, size))

@@ -1,0 +1,104 @@
+"""GPU tests of the population (harness.DevicePopulationPolicy / DevicePopulationLearner, rf_policy_forward_grouped,
+rf_ppo_update_grouped; the grouped instantiations of the kernels of csrc/rf_policy.h and csrc/rf_ppo.h) against the numpy
+twins (harness.PopulationPolicy / PopulationLearner) bit for bit, and on some cases against stand-alone DevicePolicy /
+DeviceLearner objects and rf_policy_forward launches on the same device: every array is compared as bytes.
+
+As tests/test_gpu_policy.py: the cases need torch and the library in one process, so they run in ONE fresh child process
+that imports torch first (tests/population_io_cases.py), started once per session; each test below looks its case up.
+tests/test_population_logic.py holds the twins to G independent existing twins on the CPU, on the same inputs."""
+
+import json
+import os
+import subprocess
+import sys
+
+import pytest
+
+from tests import helpers
+from tests import population_io_cases as cases
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def recorded(tmp_path_factory):
+    path = str(tmp_path_factory.mktemp("population") / "cases.jsonl")
+    # a fresh process (never an exec of this one), ended by its own time limit
+    done = subprocess.run([sys.executable, "-m", "tests.population_io_cases", path], cwd=helpers.ROOT, capture_output=True,
+                          text=True, timeout=600)
+    records = {}
+    if os.path.exists(path):
+        for line in open(path):
+            record = json.loads(line)
+            records[record["id"]] = record
+    return records, f"exit status {done.returncode}\n{done.stderr[-3000:]}"
+
+
+def _passed(recorded, name):
+    records, ending = recorded
+    assert name in records, f"the child process ended before case {name}: {ending}"
+    assert records[name]["ok"], records[name]["message"]
+
+
+def test_child_ran_every_case(recorded):
+    _passed(recorded, "finished")
+
+
+@pytest.mark.parametrize("per_group", cases.PER_GROUP)
+@pytest.mark.parametrize("groups", cases.GROUPS)
+@pytest.mark.parametrize("index", range(len(cases.NETWORKS)), ids=lambda i: "-".join(str(v) for v in cases.NETWORKS[i]))
+def test_grouped_forward_equals_the_twin_population(index, groups, per_group, recorded):
+    """rf_policy_forward_grouped on hostile device tensors, every group with parameters of its own: sampled with 0 and
+    2^32 + 5 draws taken before, deterministic, and values only; final_obs with NaN rows among live ones; every output a
+    slice of a larger slab whose guard rows keep their sentinel.  m: group borders inside what would be one ungrouped
+    tile, exactly one tile, a ragged second tile.  With G = 5 also G stand-alone rf_policy_forward launches give the same
+    bytes, and every group's values differ from what group 0's parameters give on its rows."""
+    _passed(recorded, f"forward/{index}/{groups}/{per_group}")
+
+
+@pytest.mark.parametrize("batch", [shape[0] for shape in cases.UPDATE_SHAPES])
+@pytest.mark.parametrize("index", range(len(cases.NETWORKS)), ids=lambda i: "-".join(str(v) for v in cases.NETWORKS[i]))
+def test_grouped_update_equals_the_twin_population(index, batch, recorded):
+    """rf_ppo_update_grouped, three groups whose hyper-parameters all differ, over two epochs of chained updates with
+    m T = 12 (B = 5, 8) or 44 (B = 13), so the last minibatch of an epoch is short; P = 59 and P = 1324 (past kPpoLeaves
+    and kPpoAdamSlice): parameters, optimizer states and stats as bytes after every update.  The group with
+    learning_rate 0 keeps its parameters byte for byte while its Adam moments move as the twin's."""
+    _passed(recorded, f"update/{index}/{batch}")
+
+
+def test_a_skipped_group_leaves_the_others_alone(recorded):
+    """One group's index reaches into the next group's rows, another's minibatch holds a NaN observation: exactly those
+    carry RF_PPO_INVALID / RF_PPO_NONFINITE and keep parameters and optimizer state; the other two equal the twin."""
+    _passed(recorded, "isolation")
+
+
+def test_refusals_come_before_anything_is_enqueued(recorded):
+    """Host pointers (arrays, the generator table, the hyper-parameters), G or m outside the limits, B > m T, misaligned
+    and overlapping arrays, a desc outside the limits: every output keeps its bytes, and the unchanged call is taken."""
+    _passed(recorded, "kernel-refusals")
+
+
+def test_one_group_is_the_ungrouped_path(recorded):
+    """G = 1 next to DevicePolicy / DeviceLearner with the same seed: act() sampled and deterministic, values(), three
+    chained updates, rng_state(), parameters and optimizer state, bit for bit."""
+    _passed(recorded, "one-group")
+
+
+def test_collect_and_train_equal_the_twins(recorded):
+    """DeviceVectorDiscreteSteps at 6 envs x 16 x 16 px x 1 sample with device_initializer and episode_records, G = 3: two
+    iterations of DeviceRollout.collect + train(n_epochs=2, batch_size=4) equal VectorDiscreteSteps with Rollout +
+    PopulationPolicy + PopulationLearner: every slab, flat(), stats, parameters, optimizer states, generator states.
+    Then a second learner resumed from state_dict() repeats a train() bit for bit, and a train() that draws its own
+    permutations on the device flags nothing."""
+    _passed(recorded, "end-to-end")
+
+
+def test_the_classes_refuse_with_a_message(recorded):
+    """n not divisible by the groups, too few and too many seeds, a Box action space, G m != the rows of obs, wrong dtypes
+    and types, overlapping out=, a rollout that lives on the host, batch_size > m T, index of the wrong shape or dtype:
+    tensors compared unchanged afterwards, no draw consumed."""
+    _passed(recorded, "surface")
+
+
+def test_a_sharded_environment_is_refused(recorded):
+    _passed(recorded, "sharded")
