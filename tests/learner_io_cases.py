@@ -29,6 +29,12 @@ NETWORKS = ((1, (1,), (1,), 2, "relu"),
             (20, (64, 64), (64, 64), 13, "tanh"),
             (256, (256, 256), (256, 256), 64, "relu"),
             (20, (5, 256), (256,), 13, "relu"))
+# at the limits of rf_ppo.h: the last minibatch whose s_red reductions take a single trip; the first past it, with a ragged
+# last tile; no power of two and no multiple of the tile; RF_PPO_MAX_BATCH itself, the workspace at its largest.  On the
+# least network and on stable-baselines3's default; on the network with every limit at once 513 alone (the twin's three
+# updates and the host build's take 3.7 s there and 7.7 s at 1024, which is left out; 0.2 s on the default network)
+LIMIT_BATCHES = (512, 513, 1000, 1024)
+LIMIT_CASES = tuple((index, count) for index in (0, 2) for count in LIMIT_BATCHES) + ((3, 513),)
 UPDATES = 3
 # per update: (max_grad_norm, learning_rate): a norm that clips, one that does not, one that clips
 SCHEDULE = ((0.5, 1e-2), (1e6, 3e-4), (0.05, 1e-2))
@@ -189,7 +195,9 @@ def _guards_kept(whole):
 class _Device:
     """One update's device arrays: outputs between guards, inputs as they are."""
 
-    def __init__(self, torch, ctx, spec, params, state, batch):
+    def __init__(self, torch, ctx, spec, params, state, batch, max_batch=None):
+        """The workspace has exactly rf_ppo_workspace_size(max_batch) bytes between its guards (RF_PPO_MAX_BATCH's
+        where none is given)."""
         from reinfocus_amd.environments import learner
 
         self.torch, self.ctx, self.spec = torch, ctx, spec
@@ -198,9 +206,9 @@ class _Device:
         self.whole["state"], self.state = _guarded(torch, state)
         self.whole["stats"], self.stats = _guarded(torch, np.zeros(8, dtype=np.float32))
         self.stats.view(torch.int32).fill_(SENTINEL)
-        floats = ctx.ppo_workspace_size(spec.desc(), learner.MAX_BATCH) // 4
+        floats = ctx.ppo_workspace_size(spec.desc(), max_batch or learner.MAX_BATCH) // 4
         assert floats > 0 and ctx.ppo_state_size(spec.desc()) == 4 * state.size
-        assert ctx.ppo_workspace_size(spec.desc(), 65) <= 4 * floats
+        assert ctx.ppo_workspace_size(spec.desc(), min(65, max_batch or 65)) <= 4 * floats
         self.whole["workspace"], self.workspace = _guarded(torch, np.zeros(floats, dtype=np.float32))
         self.load(batch)
 
@@ -239,18 +247,19 @@ def _same_update(got, want, what):
     assert bits(got[2]) == bits(want[2]), f"{what}: stats differ: {got[2]} / {want[2]}"
 
 
-def kernel_case(torch, ctx, index, count):
+def kernel_case(torch, ctx, index, count, max_batch=None):
     """rf_ppo_update against ppo_update_numpy as bytes over UPDATES consecutive updates."""
     from reinfocus_amd.environments import learner
 
     spec, params, batch, indices = update_inputs(index, count)
     want = twin_updates(index, count)
-    device = _Device(torch, ctx, spec, params, learner.fresh_state(spec), batch)
+    device = _Device(torch, ctx, spec, params, learner.fresh_state(spec), batch, max_batch)
     for update in range(UPDATES):
         device.call(torch.from_numpy(indices[update]).cuda(), hyper_of(update))
         _same_update(device.outputs(), want[update], f"update {update}")
     assert device.guards_kept(), "a guard was written"
-    assert want[2][2][5] > SCHEDULE[2][0] and want[1][2][5] < SCHEDULE[1][0]  # (one norm that clips, one that does not)
+    # one norm that clips, one that does not (at the batch limits tests/test_learner_logic.py says which cases hold it)
+    assert max_batch or want[2][2][5] > SCHEDULE[2][0] and want[1][2][5] < SCHEDULE[1][0]
 
 
 def skip_case(torch, ctx):
@@ -327,6 +336,12 @@ def refusal_case(torch, ctx):
     refused("fewer than", params=end - 4 * (spec.size - 1))
     refused("fewer than", state=end - 8 * spec.size)  # (a state that is too small)
     refused("fewer than", workspace=end - 1024)  # (a workspace that is too small)
+    # a workspace sized for 512 rows offered for 513, which index the same rows again; sized for 513 it would do
+    again = torch.from_numpy(np.resize(indices[0], 513)).cuda()
+    sized = ctx.ppo_workspace_size(spec.desc(), 512)
+    assert 0 < sized < ctx.ppo_workspace_size(spec.desc(), 513) and ctx.ppo_workspace_size(spec.desc(), 1025) == 0
+    refused("fewer than", workspace=end - sized, batch=513, index=again.data_ptr())
+    refused("is not in 1 ..", workspace=end - sized, batch=1025, index=again.data_ptr())
     refused("fewer than", stats=end - 16)
     refused("d_params overlaps d_obs", params=device.batch["observations"].data_ptr())
     refused("d_stats overlaps d_returns", stats=device.batch["returns"].data_ptr())
@@ -498,6 +513,9 @@ def run_cases(path):
         for count in BATCHES:
             with record.case(f"kernel/{index}/{count}"):
                 kernel_case(torch, ctx, index, count)
+    for index, count in LIMIT_CASES:
+        with record.case(f"kernel/{index}/{count}"):
+            kernel_case(torch, ctx, index, count, count)
     with record.case("skips"):
         skip_case(torch, ctx)
     with record.case("refusals"):

@@ -47,6 +47,16 @@ def layouts_of(index):
     return lstm_learner_cases.layouts_of(index)
 
 
+def limit_layouts_of(index):
+    """lstm_learner_io_cases.LIMIT_LAYOUTS for the linear critic, whose forward grid has B + ceil(B / 8) blocks: tuned and
+    depth (9 tiles at B = 65 and 68) on both networks below the limits, wave (128 tiles at B = 1024, 65 at 513) on
+    ppo_lstm_tuned.yml's alone; the 17-row sequence on the network with every limit."""
+    kinds = {TUNED: ("tuned", "depth", "wave"), ODD: ("tuned", "depth")}.get(index, ())
+    if index == LIMITS:
+        return ["depth/0/17"]
+    return [name for name in lstm_learner_cases.LIMIT_LAYOUTS if name.split("/")[0] in kinds and name != "depth/0/17"]
+
+
 def spec_of(head, network, enable_critic_lstm=False, log_std_init=0.0):
     from reinfocus_amd.environments import lstm, lstm_sde
 
@@ -471,7 +481,7 @@ def run_cases(path):
     with record.case("value-path"):
         value_path_case(torch, real)
     for index in GPU_NETWORKS:
-        for name in layouts_of(index):
+        for name in layouts_of(index) + limit_layouts_of(index):
             with record.case(f"update/categorical/{index}/{name}"):
                 lstm_learner_cases.kernel_case(torch, ctx, lib, index, name)
             with record.case(f"update/sde/{index}/{name}"):

@@ -41,20 +41,61 @@ LAYOUTS = {f"mixed/{first}/{count}": (STEPS, ENVS, "mixed", first, count)
 LAYOUTS["every/3/15"] = (STEPS, ENVS, "every", 3, ROWS)
 LAYOUTS["single/0/9"] = (9, 1, "none", 0, 9)
 
+# at the limits of rf_lstm_ppo.h (the same form; each family says which of its networks runs which, limit_layouts_of):
+#   tuned/    ppo_lstm_tuned.yml's T = 8, n = 8, no flagged start: every sequence has exactly the 8 rows whose weights both
+#             walks load before the first is used; B = 8 (at first 3 a 5-row tail and a 3-row head), B = 64 = N (8 tiles)
+#   depth/    T = 17, n = 4, one flagged start per environment (starts_of): sequences of 1, 8, 9, 16 and 17 rows; B = 65,
+#             B = 68 = N from row 5 (a wrap), and B = 17 for the network with every limit at once
+#   untuned/  ppo_lstm_untuned.yml's T = 128, n = 8, B = 128, starts drawn from a fixed seed: one whole environment that
+#             enters from its stored state, and rows 100 .. 227 across an environment boundary
+#   wave/     T = 16, n = 64, N = 1024: every row a start at B = 1024 (1024 one-row sequences, 128 tiles, the second trip
+#             of the loss reductions), and no flagged start at B = 513 (33 sequences)
+LIMIT_LAYOUTS = {"tuned/0/8": (8, 8, "none", 0, 8), "tuned/3/8": (8, 8, "none", 3, 8), "tuned/0/64": (8, 8, "none", 0, 64),
+                 "depth/0/65": (17, 4, "depth", 0, 65), "depth/5/68": (17, 4, "depth", 5, 68),
+                 "depth/0/17": (17, 4, "depth", 0, 17),
+                 "untuned/0/128": (128, 8, "drawn", 0, 128), "untuned/100/128": (128, 8, "drawn", 100, 128),
+                 "wave/7/1024": (16, 64, "every", 7, 1024), "wave/0/513": (16, 64, "none", 0, 513)}
+LAYOUTS.update(LIMIT_LAYOUTS)
+DEPTH_STARTS = ((0, 0, 1), (1, 1, 2), (8, 2, 255), (16, 3, 1))  # (step, environment, byte)
+DRAWN_SEED, DRAWN_SHARE = 1, 3 / 128
+
 
 def layouts_of(index):
-    return [name for name, layout in LAYOUTS.items() if index != LIMITS or layout[4] <= 2]
+    return [name for name, layout in LAYOUTS.items() if name not in LIMIT_LAYOUTS and (index != LIMITS or layout[4] <= 2)]
+
+
+def limit_layouts_of(index):
+    """TUNED runs every limit layout but the one of 17 rows; sb3-contrib's default network (H = 256) the two untuned ones,
+    ppo_lstm_untuned.yml's real shape; the network with every limit at once the 17-row sequence alone."""
+    if index == TUNED:
+        return [name for name in LIMIT_LAYOUTS if name != "depth/0/17"]
+    if index == DEFAULT:
+        return ["untuned/0/128", "untuned/100/128"]
+    return ["depth/0/17"] if index == LIMITS else []
 
 
 def starts_of(kind, n_steps, num_envs):
     """uint8 [T + 1, n].  mixed (T = 5, n = 3): environment 0 starts at t = 0 (byte 1) and t = 2 (byte 2), environment 1
-    runs four rows from its stored, non-zero state and starts at t = 4 (byte 255), environment 2 starts at t = 0 and 3."""
+    runs four rows from its stored, non-zero state and starts at t = 4 (byte 255), environment 2 starts at t = 0 and 3.
+    depth (T = 17, n = 4): environment 0 starts at t = 0 (one sequence of 17 rows), environment 1 at t = 1 (1 and 16
+    rows, the first from its stored state), environment 2 at t = 8 (8 and 9), environment 3 at t = 16 (16 and 1).
+    drawn: every byte of rows 0 .. T - 1 is a start with probability DRAWN_SHARE, by turns 1, 2 and 255, from
+    DRAWN_SEED; environment 0's first row is none."""
     starts = np.zeros((n_steps + 1, num_envs), dtype=np.uint8)
     if kind == "every":
         starts[...] = np.array([1, 2, 255], dtype=np.uint8)[np.arange(starts.size) % 3].reshape(starts.shape)
     elif kind == "mixed":
         starts[0, 0], starts[2, 0], starts[4, 1], starts[0, 2], starts[3, 2] = 1, 2, 255, 1, 1
         starts[n_steps] = 1  # (row T is never read)
+    elif kind == "depth":
+        for step, env, byte in DEPTH_STARTS:
+            starts[step, env] = byte
+    elif kind == "drawn":
+        drawn = np.random.default_rng(DRAWN_SEED).random((n_steps, num_envs)) < DRAWN_SHARE
+        drawn[0, 0] = False
+        starts[:n_steps][drawn] = np.array([1, 2, 255], dtype=np.uint8)[np.arange(int(drawn.sum())) % 3]
+    else:
+        assert kind == "none", kind
     return starts
 
 
@@ -198,7 +239,9 @@ _guarded, _guards_kept = learner_cases._guarded, learner_cases._guards_kept
 class _Device:
     """One update's device arrays: outputs between guards, inputs as they are."""
 
-    def __init__(self, torch, ctx, lib, spec, params, state, batch, starts, states, n_steps, num_envs):
+    def __init__(self, torch, ctx, lib, spec, params, state, batch, starts, states, n_steps, num_envs, max_batch=None):
+        """The workspace has exactly rf_lstm_ppo_workspace_size(max_batch) bytes between its guards (N's where none is
+        given)."""
         self.torch, self.ctx, self.lib, self.spec = torch, ctx, lib, spec
         self.n_steps, self.num_envs = n_steps, num_envs
         self.whole = {}
@@ -207,7 +250,7 @@ class _Device:
         self.whole["stats"], self.stats = _guarded(torch, np.zeros(8, dtype=np.float32))
         self.stats.view(torch.int32).fill_(SENTINEL)
         total = n_steps * num_envs
-        floats = ctx.lstm_ppo_workspace_size(spec.desc(), total) // 4
+        floats = ctx.lstm_ppo_workspace_size(spec.desc(), max_batch or total) // 4
         assert floats > 0 and ctx.lstm_ppo_state_size(spec.desc()) == 4 * state.size
         assert ctx.lstm_ppo_workspace_size(spec.desc(), 1) <= 4 * floats
         self.whole["workspace"], self.workspace = _guarded(torch, np.zeros(floats, dtype=np.float32))
@@ -253,12 +296,14 @@ def _same_update(got, want, what):
 
 
 def kernel_case(torch, ctx, lib, index, name):
-    """rf_lstm_ppo_update against lstm_update_numpy as bytes over UPDATES consecutive updates, the gradient included."""
+    """rf_lstm_ppo_update against lstm_update_numpy as bytes over UPDATES consecutive updates, the gradient included; a
+    limit layout's workspace is sized for its B, not for N."""
     from reinfocus_amd.environments import learner
 
     spec, params, batch, starts, states, n_steps, num_envs, first, count = layout_inputs(index, name)
     want = twin_updates(index, name)
-    device = _Device(torch, ctx, lib, spec, params, learner.fresh_state(spec), batch, starts, states, n_steps, num_envs)
+    device = _Device(torch, ctx, lib, spec, params, learner.fresh_state(spec), batch, starts, states, n_steps, num_envs,
+                     count if name in LIMIT_LAYOUTS else None)
     for update in range(UPDATES):
         device.call(first, count, hyper_of(update))
         _same_update(device.outputs() + (device.gradient(count),), want[update], f"update {update}")
@@ -529,7 +574,7 @@ def run_cases(path):
     ctx = _native.Context(0)
     lib = hostcheck()
     for index in range(len(NETWORKS)):
-        for name in layouts_of(index):
+        for name in layouts_of(index) + limit_layouts_of(index):
             with record.case(f"kernel/{index}/{name}"):
                 kernel_case(torch, ctx, lib, index, name)
     with record.case("refusals"):

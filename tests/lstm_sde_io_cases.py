@@ -50,8 +50,19 @@ def sizes_of(index):
     return (1, TILE + 1) if index == LIMITS else SIZES
 
 
+LIMIT_LAYOUTS = lstm_learner_cases.LIMIT_LAYOUTS
+
+
 def layouts_of(index):
-    return [name for name, layout in LAYOUTS.items() if index != LIMITS or layout[4] <= 2]
+    return [name for name, layout in LAYOUTS.items() if name not in LIMIT_LAYOUTS and (index != LIMITS or layout[4] <= 2)]
+
+
+def limit_layouts_of(index):
+    """lstm_learner_io_cases.LIMIT_LAYOUTS under the Gaussian head: tuned, depth and untuned on the H = 16 network (8-row
+    sequences; 1, 8, 9, 16 and 17 rows; more than 64 rows at B = 128); the 17-row sequence on the network with every limit."""
+    if index == SMALL:
+        return [name for name in LIMIT_LAYOUTS if name.split("/")[0] in ("tuned", "depth", "untuned") and name != "depth/0/17"]
+    return ["depth/0/17"] if index == LIMITS else []
 
 
 def spec_of(network, log_std_init=0.0):
@@ -371,14 +382,14 @@ def kernel_case(torch, ctx, index, n):
 class _Device(lstm_learner_cases._Device):
     """One update's device arrays, for rf_lstm_sde_update."""
 
-    def __init__(self, torch, ctx, lib, spec, params, state, batch, starts, states, n_steps, num_envs):
+    def __init__(self, torch, ctx, lib, spec, params, state, batch, starts, states, n_steps, num_envs, max_batch=None):
         self.torch, self.ctx, self.lib, self.spec = torch, ctx, lib, spec
         self.n_steps, self.num_envs = n_steps, num_envs
         self.whole = {}
         self.whole["params"], self.params = _guarded(torch, params)
         self.whole["state"], self.state = _guarded(torch, state)
         self.whole["stats"], self.stats = _sentinels(torch, 8)
-        total = n_steps * num_envs
+        total = max_batch or n_steps * num_envs  # (the workspace's max_batch: N, or a limit layout's B)
         floats = ctx.lstm_sde_workspace_size(spec.desc(), total) // 4
         assert floats > 0 and ctx.lstm_sde_state_size(spec.desc()) == 4 * state.size == 32 + 8 * spec.size
         assert ctx.lstm_sde_workspace_size(spec.desc(), 1) <= 4 * floats
@@ -410,12 +421,14 @@ _same_update = lstm_learner_cases._same_update
 
 
 def update_case(torch, ctx, lib, index, name):
-    """rf_lstm_sde_update against lstm_update_numpy as bytes over UPDATES consecutive updates, the gradient included."""
+    """rf_lstm_sde_update against lstm_update_numpy as bytes over UPDATES consecutive updates, the gradient included; a
+    limit layout's workspace is sized for its B, not for N."""
     from reinfocus_amd.environments import learner
 
     spec, params, batch, starts, states, n_steps, num_envs, first, count = layout_inputs(index, name)
     want = twin_updates(index, name)
-    device = _Device(torch, ctx, lib, spec, params, learner.fresh_state(spec), batch, starts, states, n_steps, num_envs)
+    device = _Device(torch, ctx, lib, spec, params, learner.fresh_state(spec), batch, starts, states, n_steps, num_envs,
+                     count if name in LIMIT_LAYOUTS else None)
     for update in range(UPDATES):
         device.call(first, count, hyper_of(update))
         _same_update(device.outputs() + (device.gradient(count),), want[update], f"update {update}")
@@ -844,7 +857,7 @@ def run_cases(path):
     with record.case("forward-refusals"):
         forward_refusal_case(torch, ctx)
     for index in range(len(NETWORKS)):
-        for name in layouts_of(index):
+        for name in layouts_of(index) + limit_layouts_of(index):
             with record.case(f"update/{index}/{name}"):
                 update_case(torch, ctx, lib, index, name)
     with record.case("skip"):

@@ -30,6 +30,16 @@ T = 4
 UPDATE_GROUPS = 3
 UPDATE_SHAPES = ((5, 3), (8, 3), (13, 11))  # (B, m): m T = 12 or 44, so the last minibatch of an epoch is short
 EPOCHS = 2
+# wide: (network, G, m) of forwards with a group index past 4 -- 64 and 65 groups of the reference's n_envs = 8 (exactly one
+# tile each) on both networks, 512 groups of 8 and of 1 on the first (tools/bench_population.py's largest G)
+WIDE_FORWARD = ((0, 64, 8), (1, 64, 8), (0, 65, 8), (1, 65, 8), (0, 512, 8), (0, 512, 1))
+# ppo_tuned.yml's first shape for 64 groups on NETWORKS[1]: m = 8, T = 32, B = 64, so 4 minibatches per epoch; one row of
+# group 31 holds a NaN observation
+WIDE_UPDATE = dict(index=1, groups=64, per_group=8, steps=32, batch=64, nan_group=31, nan_row=100)
+# the limit: RF_POPULATION_MAX_GROUPS groups of one row on the least network; group g has parameter set g % 7, observation
+# block g % 5 and hyper-parameter set g % 3, so neighbours differ in all three and g % 105 names the combination
+LIMIT_GROUPS, LIMIT_PERIODS = 65535, (7, 5, 3)
+LIMIT_NETWORK = (1, (1,), (1,), 2, "relu")
 E2E = dict(envs=6, groups=3, steps=rollout_cases.T, epochs=2, batch=4, iterations=2)
 GAMMA, GAE_LAMBDA = rollout_cases.GAMMA, rollout_cases.GAE_LAMBDA
 
@@ -89,13 +99,27 @@ def group_hypers(groups):
                 betas=[(0.9 - 0.1 * g, 0.999 - 0.01 * g) for g in range(groups)], adam_eps=list(1e-5 * (1 + lanes)))
 
 
-def update_batch(index, groups, per_group, seed=0):
+def wide_hypers(groups):
+    """group_hypers' pattern for more groups than its betas allow: its first five lanes repeat with periods 5, 4 and 3 (so
+    neighbours differ in every hyper-parameter), the learning rate falls with g % 7, and group 1 alone has learning_rate 0."""
+    five = group_hypers(5)
+
+    def cycled(name, period):
+        return [five[name][g % period] for g in range(groups)]
+
+    return dict(learning_rate=[0.0 if g == 1 else 1e-2 / (1 + g % 7) for g in range(groups)],
+                clip_range=cycled("clip_range", 5), ent_coef=cycled("ent_coef", 4), vf_coef=cycled("vf_coef", 5),
+                max_grad_norm=cycled("max_grad_norm", 3), normalize_advantage=cycled("normalize_advantage", 2),
+                betas=cycled("betas", 5), adam_eps=cycled("adam_eps", 4))
+
+
+def update_batch(index, groups, per_group, seed=0, steps=T):
     """flat()'s arrays for G groups of m T rows; the stored log-probabilities are the twin's own, shifted so that the
     ratios lie inside the clip range and past both bounds."""
     from reinfocus_amd.environments import policy
 
     spec, twin = twin_policy(index, groups, base=300)
-    rows = per_group * T
+    rows = per_group * steps
     total = groups * rows
     rng = np.random.default_rng(1000 * index + 10 * per_group + seed)
     obs = rng.standard_normal((total, spec.obs_width)).astype(F32)
@@ -141,6 +165,117 @@ def twin_updates(index, batch, per_group):
         stats = learner.update(flat, rows)
         seen.append((twin.params.copy(), twin_states(learner), stats.copy()))
     return seen
+
+
+def wide_update_inputs():
+    """(spec, twin, flat, hypers' keywords, the index arrays of two epochs) of WIDE_UPDATE."""
+    w = WIDE_UPDATE
+    spec, twin, flat = update_batch(w["index"], w["groups"], w["per_group"], seed=9, steps=w["steps"])
+    rows = w["per_group"] * w["steps"]
+    flat["observations"][w["nan_group"] * rows + w["nan_row"], 3] = np.nan
+    return spec, twin, flat, wide_hypers(w["groups"]), minibatches(update_permutations(w["groups"], rows, 71), w["batch"])
+
+
+@functools.lru_cache(maxsize=None)
+def wide_twin_updates():
+    """Per update (params [G][P], states [G][S], stats [G][8]) of the twin population on WIDE_UPDATE."""
+    from reinfocus_amd.environments import harness
+
+    spec, twin, flat, hypers, order = wide_update_inputs()
+    learner = harness.PopulationLearner(twin, **hypers)
+    seen = []
+    for rows in order:
+        stats = learner.update(flat, rows)
+        seen.append((twin.params.copy(), twin_states(learner), stats.copy()))
+    return seen
+
+
+def wide_update_promises(want, before):
+    """What WIDE_UPDATE's twin results hold: group 31 carries RF_PPO_NONFINITE in exactly the one update of each epoch
+    whose minibatch holds the NaN row and keeps its bytes over it; group 1 (learning_rate 0) never moves; every other
+    update of every group is taken."""
+    from reinfocus_amd.environments import learner
+
+    w = WIDE_UPDATE
+    order = wide_update_inputs()[4]
+    assert len(order) == 2 * (w["per_group"] * w["steps"] // w["batch"]) == 8 and all(rows.shape == (64, 64) for rows in order)
+    hit = [update for update, rows in enumerate(order) if w["nan_row"] in rows[w["nan_group"]]]
+    assert len(hit) == 2 and hit[0] < 4 <= hit[1]
+    for update, (params, states, stats) in enumerate(want):
+        flags = stats[:, 7].copy()
+        assert flags[w["nan_group"]] == (learner.NONFINITE if update in hit else 0), update
+        flags[w["nan_group"]] = 0
+        assert (flags == 0).all(), update
+        earlier = before if update == 0 else want[update - 1][0]
+        assert (bits(params[w["nan_group"]]) == bits(earlier[w["nan_group"]])) == (update in hit), update
+        if update in hit and update > 0:
+            assert bits(states[w["nan_group"]]) == bits(want[update - 1][1][w["nan_group"]])
+    params = want[-1][0]
+    assert bits(params[1]) == bits(before[1]) and all(bits(params[g]) != bits(before[g]) for g in (0, 30, 31, 32, 63))
+
+
+# ---- the limit: 65535 groups of one row --------------------------------------------------------------------------------
+def limit_spec():
+    return policy_cases.spec_of(LIMIT_NETWORK)
+
+
+@functools.lru_cache(maxsize=None)
+def limit_parts():
+    """(7 packed parameter sets, 5 observation blocks -- one row each: obs, final_obs, action, log_prob, advantage,
+    return --, 3 hyper-parameter sets).  Weights and observations are positive, so the one ReLU unit of either net is
+    alive and every output depends on both; adam_eps is large, so the first Adam step depends on the gradient's size."""
+    from reinfocus_amd.environments import learner
+
+    spec = limit_spec()
+    rng = np.random.default_rng(65535)
+    params = [np.abs(spec.pack(policy_cases.state_dict(spec, 700 + k))) + F32(0.25 + 0.125 * k) for k in range(LIMIT_PERIODS[0])]
+    blocks = []
+    for j in range(LIMIT_PERIODS[1]):
+        blocks.append(dict(observations=np.array([[0.5 + 0.75 * j]], dtype=F32), final=np.array([[3.0 - 0.5 * j]], dtype=F32),
+                           actions=np.array([j % 2], dtype=np.int64), log_probs=np.array([-0.7 + 0.1 * j], dtype=F32),
+                           advantages=rng.standard_normal(1).astype(F32), returns=rng.standard_normal(1).astype(F32)))
+    hypers = [learner.Hyper(learning_rate=1e-2 / (1 + h), clip_range=0.1 + 0.1 * h, ent_coef=0.01 * (1 + h),
+                            vf_coef=0.5 + 0.25 * h, max_grad_norm=(1e6, 0.5, 0.05)[h], beta1=0.9 - 0.1 * h,
+                            beta2=0.999 - 0.01 * h, adam_eps=(0.1, 0.3, 1.0)[h], normalize_advantage=h % 2)
+              for h in range(LIMIT_PERIODS[2])]
+    return params, blocks, hypers
+
+
+@functools.lru_cache(maxsize=None)
+def limit_results():
+    """For each of the 105 combinations c (parameter set c % 7, block c % 5, hyper-parameters c % 3), by the existing
+    twin functions: the deterministic forward's (actions, values, log_probs, final_values) and the first update's
+    (params, state, stats) from a fresh optimizer."""
+    from reinfocus_amd.environments import learner, policy
+
+    spec = limit_spec()
+    params, blocks, hypers = limit_parts()
+    forwards, updates = [], []
+    for c in range(105):
+        k, j, h = (c % period for period in LIMIT_PERIODS)
+        got = policy.policy_numpy(spec, params[k], blocks[j]["observations"], blocks[j]["final"], None, True)
+        forwards.append(tuple(got[name] for name in ORDER))
+        batch = {key: blocks[j][key] for key in learner.BATCH_KEYS}
+        updates.append(learner.ppo_update_numpy(spec, params[k], learner.fresh_state(spec), batch, np.zeros(1, dtype=np.int64),
+                                                hypers[h]))
+    return forwards, updates
+
+
+def limit_arrays(groups=LIMIT_GROUPS):
+    """What group g gets and what it must give, for g = 0 .. groups - 1: (inputs dict, wanted forward outputs in ORDER,
+    wanted (params [G][P], states [G][S], stats [G][8]))."""
+    from reinfocus_amd.environments import learner, population
+
+    params, blocks, hypers = limit_parts()
+    forwards, updates = limit_results()
+    g = np.arange(groups)
+    k, j, h, c = g % LIMIT_PERIODS[0], g % LIMIT_PERIODS[1], g % LIMIT_PERIODS[2], g % 105
+    inputs = {"params": np.stack(params)[k], "hyper": population.hyper_records(hypers)[h]}
+    for key in ("observations", "final") + tuple(k for k in learner.BATCH_KEYS if k != "observations"):
+        inputs[key] = np.concatenate([block[key] for block in blocks])[j]
+    wanted_forward = tuple(np.concatenate([forward[i] for forward in forwards])[c] for i in range(len(ORDER)))
+    wanted_update = tuple(np.stack([update[i] for update in updates])[c] for i in range(3))
+    return inputs, wanted_forward, wanted_update
 
 
 def isolation_inputs():
@@ -297,31 +432,52 @@ def forward_case(torch, ctx, index, groups, per_group):
         everywhere = policy.policy_numpy(spec, twin.params[0], obs_h, values_only=True)["values"]
         for g in range(1, groups):
             rows = slice(g * per_group, (g + 1) * per_group)
+            if per_group == 1 and not np.isfinite(everywhere[rows]).all():
+                continue  # (a group's only row is a hostile one whose value is NaN or infinite under any parameters)
             assert bits(everywhere[rows]) != bits(want[1][rows]), f"group {g} does not tell its parameters from group 0's"
 
 
 class _Learner:
     """Device copies of a twin population's parameters and batch, fresh optimizer states, and rf_ppo_update_grouped."""
 
-    def __init__(self, torch, ctx, spec, twin, flat, per_group, hypers, batch_most):
+    def __init__(self, torch, ctx, spec, twin, flat, per_group, hypers, batch_most, steps=T, guarded=False):
+        """twin: a PopulationPolicy, or the packed parameters [G][P] themselves; hypers: learner.Hyper per group, or the
+        packed records.  guarded: parameters and optimizer states lie between guard rows of one group's size, and the
+        workspace has exactly rf_ppo_grouped_workspace_size's bytes between guard floats; update() checks them all."""
         from reinfocus_amd.environments import learner, population
 
-        self.torch, self.ctx, self.spec, self.groups, self.per_group = torch, ctx, spec, twin.groups, per_group
-        self.params = torch.from_numpy(twin.params.copy()).cuda()
+        params = twin if isinstance(twin, np.ndarray) else twin.params
+        self.torch, self.ctx, self.spec, self.groups, self.per_group = torch, ctx, spec, params.shape[0], per_group
+        self.steps, self.whole = steps, []
+        self.params = self._slab(params.shape[1] if guarded else 0, params.reshape(-1))
         state_bytes = ctx.ppo_grouped_state_size(spec.desc(), self.groups, per_group)
         assert state_bytes == self.groups * 4 * (learner.STATE_HEADER + 2 * spec.size)
-        self.state = torch.zeros(state_bytes // 4, dtype=torch.float32, device="cuda")
-        size = ctx.ppo_grouped_workspace_size(spec.desc(), self.groups, per_group, T, batch_most)
+        self.state = self._slab(state_bytes // 4 // self.groups if guarded else 0, np.zeros(state_bytes // 4, dtype=F32))
+        size = ctx.ppo_grouped_workspace_size(spec.desc(), self.groups, per_group, steps, batch_most)
         assert size == self.groups * ctx.ppo_workspace_size(spec.desc(), batch_most) and size > 0
-        self.workspace = torch.zeros(size // 4, dtype=torch.float32, device="cuda")
+        self.workspace = self._slab(16 if guarded else 0, np.zeros(size // 4, dtype=F32))
+        self.params = self.params.view(self.groups, -1)
         self.flat = {key: torch.from_numpy(np.ascontiguousarray(flat[key])).cuda() for key in learner.BATCH_KEYS}
-        records = population.hyper_records(hypers)
+        records = hypers if isinstance(hypers, np.ndarray) else population.hyper_records(hypers)
         self.hyper = torch.from_numpy(records.view(np.float64).copy()).cuda()
         self.stats = torch.full((self.groups + 2, 8), SENTINEL, dtype=torch.int32, device="cuda").view(torch.float32)
 
+    def _slab(self, guard, array):
+        whole = self.torch.full((array.size + 2 * guard,), SENTINEL, dtype=self.torch.int32, device="cuda").view(
+            self.torch.float32)
+        view = whole[guard:guard + array.size]
+        view.copy_(self.torch.from_numpy(np.ascontiguousarray(array, dtype=F32)))
+        if guard:
+            self.whole.append((whole, guard))
+        return view
+
+    def guards_kept(self):
+        return all(_untouched(whole[:guard]) and _untouched(whole[-guard:]) for whole, guard in self.whole)
+
     def update(self, index, changed=()):
         index = self.torch.from_numpy(np.ascontiguousarray(index)).cuda()
-        a = dict(desc=self.spec.desc(), groups=self.groups, per_group=self.per_group, steps=T, hyper=self.hyper.data_ptr(),
+        a = dict(desc=self.spec.desc(), groups=self.groups, per_group=self.per_group, steps=self.steps,
+                 hyper=self.hyper.data_ptr(),
                  params=self.params.data_ptr(), state=self.state.data_ptr(), workspace=self.workspace.data_ptr(),
                  obs=self.flat["observations"].data_ptr(), actions=self.flat["actions"].data_ptr(),
                  log_probs=self.flat["log_probs"].data_ptr(), advantages=self.flat["advantages"].data_ptr(),
@@ -333,6 +489,7 @@ class _Learner:
                                     a["batch"], a["index"], a["stats"], self.torch.cuda.current_stream().cuda_stream)
         self.torch.cuda.synchronize()
         assert _untouched(self.stats[0]) and _untouched(self.stats[self.groups + 1]), "a guard row of the stats was written"
+        assert self.guards_kept(), "a guard of the parameters, the states or the workspace was written"
         return (self.params.cpu().numpy(), self.state.cpu().numpy().reshape(self.groups, -1),
                 self.stats[1:self.groups + 1].cpu().numpy())
 
@@ -359,6 +516,68 @@ def update_case(torch, ctx, index, batch, per_group):
     params, states, stats = want[-1]
     assert (stats[:, 7] == 0).all() and bits(params[1]) == bits(before[1]) and bits(params[0]) != bits(before[0])
     assert np.abs(states[1][learner.STATE_HEADER:]).max() > 0  # (m and v of the group with learning_rate 0 moved)
+
+
+def wide_update_case(torch, ctx):
+    """rf_ppo_update_grouped at G = 64 on ppo_tuned.yml's first shape (WIDE_UPDATE) against the twin population over two
+    epochs of chained updates: every group's parameters, state and stats as bytes after each; what the twin's results
+    promise (group 31 flagged and kept in two updates, group 1 never moving) is wide_update_promises'."""
+    want = wide_twin_updates()
+    spec, twin, flat, hypers, order = wide_update_inputs()
+    w = WIDE_UPDATE
+    from reinfocus_amd.environments import harness
+
+    device = _Learner(torch, ctx, spec, twin, flat, w["per_group"], harness.PopulationLearner(twin, **hypers).hypers(),
+                      w["batch"], steps=w["steps"], guarded=True)
+    for update, index_rows in enumerate(order):
+        got = device.update(index_rows)
+        for g in (0, w["nan_group"] - 1, w["nan_group"], w["nan_group"] + 1, w["groups"] - 1):
+            _same_update(tuple(x[g] for x in got), tuple(x[g] for x in want[update]), f"update {update}, group {g}")
+        _same_update(got, want[update], f"update {update}")
+    wide_update_promises(want, twin.params)
+
+
+def limit_case(torch, ctx):
+    """RF_POPULATION_MAX_GROUPS groups of one row on the least network: one deterministic forward with values and final
+    values, and one grouped update of fresh optimizers, every output byte of every group against the result of its
+    combination (limit_arrays).  Then 65536 groups: refused by both entry points and both size functions, nothing written."""
+    from reinfocus_amd.environments import learner, policy
+
+    spec, groups = limit_spec(), LIMIT_GROUPS
+    inputs, wanted_forward, wanted_update = limit_arrays()
+    params, obs, final_obs = (torch.from_numpy(inputs[key]).cuda() for key in ("params", "observations", "final"))
+    whole, out = _guarded(torch, groups)
+    _forward(torch, ctx, spec, groups, 1, params, obs, final_obs, None, 0, policy.DETERMINISTIC, out)
+    torch.cuda.synchronize()
+    for name, wanted in zip(ORDER, wanted_forward):
+        got = out[name].cpu().numpy()
+        differ = np.flatnonzero((got.view(np.uint8).reshape(groups, -1) != wanted.view(np.uint8).reshape(groups, -1)).any(axis=1))
+        assert differ.size == 0, f"{name} differ in {differ.size} groups, first {differ[:4]}"
+        assert _untouched(whole[name][0]) and _untouched(whole[name][groups + 1]), f"a guard row of {name} was written"
+    flat = {key: inputs[key] for key in learner.BATCH_KEYS}
+    device = _Learner(torch, ctx, spec, inputs["params"], flat, 1, inputs["hyper"], 1, steps=1, guarded=True)
+    got = device.update(np.zeros((groups, 1), dtype=np.int64))
+    for name, x, y in zip(("params", "states", "stats"), got, wanted_update):
+        differ = np.flatnonzero((x.view(np.uint32) != y.view(np.uint32)).any(axis=1))
+        assert differ.size == 0, f"{name} differ in {differ.size} groups, first {differ[:4]}"
+    # one group more
+    kept = [t.clone() for t in (device.params, device.state, device.stats)]
+    many = groups + 1
+    assert ctx.ppo_grouped_state_size(spec.desc(), many, 1) == 0 == ctx.ppo_grouped_workspace_size(spec.desc(), many, 1, 1, 1)
+    for call in (lambda: device.update(np.zeros((groups, 1), dtype=np.int64), dict(groups=many)),
+                 lambda: _forward(torch, ctx, spec, many, 1, params, obs, final_obs, None, 0, policy.DETERMINISTIC, out)):
+        try:
+            call()
+        except AssertionError as caught:  # (RF_ERR_INVALID)
+            assert "must be in 1" in str(caught), str(caught)
+        else:
+            raise AssertionError("65536 groups were taken")
+    torch.cuda.synchronize()
+    for tensor, copy in zip((device.params, device.state, device.stats), kept):
+        assert torch.equal(tensor.view(torch.int32), copy.view(torch.int32)), "a refused update wrote an output"
+    for name, wanted in zip(ORDER, wanted_forward):
+        assert bits(out[name].cpu().numpy()) == bits(wanted), f"a refused forward wrote {name}"
+    assert device.guards_kept()
 
 
 def isolation_case(torch, ctx):
@@ -641,6 +860,13 @@ def run_cases(path):
         for batch, per_group in UPDATE_SHAPES:
             with record.case(f"update/{index}/{batch}"):
                 update_case(torch, ctx, index, batch, per_group)
+    for index, groups, per_group in WIDE_FORWARD:
+        with record.case(f"forward/{index}/{groups}/{per_group}"):
+            forward_case(torch, ctx, index, groups, per_group)
+    with record.case("update/wide"):
+        wide_update_case(torch, ctx)
+    with record.case("limit"):
+        limit_case(torch, ctx)
     with record.case("isolation"):
         isolation_case(torch, ctx)
     with record.case("kernel-refusals"):

@@ -29,6 +29,10 @@ NETWORKS = ((3, (1,), (2, 2), "tanh"),
             (20, (64, 64), (64,), "tanh"),
             (20, (256, 256), (256, 256), "relu"))
 BATCHES = (1, 2, 64, 512)  # one sample, a pair, 8 tiles, the reference's minibatch (and a two-level Adam reduction)
+# at the limits, as learner_io_cases.LIMIT_CASES (512 is above): the first size whose reductions take a second trip, one
+# that is no multiple of the tile, RF_PPO_MAX_BATCH; on the single-unit latent and SB3's default in both activations, and
+# at 513 on the widest
+LIMIT_CASES = tuple((index, count) for index in (0, 1, 2) for count in (513, 1000, 1024)) + ((3, 513),)
 UPDATES, SCHEDULE, SHIFTS = learner_cases.UPDATES, learner_cases.SCHEDULE, learner_cases.SHIFTS
 OFFSETS = policy_cases.OFFSETS
 SEED, SENTINEL, GUARD = policy_cases.SEED, policy_cases.SENTINEL, learner_cases.GUARD
@@ -273,7 +277,7 @@ def forward_case(torch, ctx, index, n):
 class _Device(learner_cases._Device):
     """One update's device arrays, for rf_sde_update."""
 
-    def __init__(self, torch, ctx, spec, params, state, batch):
+    def __init__(self, torch, ctx, spec, params, state, batch, max_batch=None):
         from reinfocus_amd.environments import learner
 
         self.torch, self.ctx, self.spec = torch, ctx, spec
@@ -281,9 +285,9 @@ class _Device(learner_cases._Device):
         self.whole["params"], self.params = _guarded(torch, params)
         self.whole["state"], self.state = _guarded(torch, state)
         self.whole["stats"], self.stats = _sentinels(torch, 8)
-        floats = ctx.sde_workspace_size(spec.desc(), learner.MAX_BATCH) // 4
+        floats = ctx.sde_workspace_size(spec.desc(), max_batch or learner.MAX_BATCH) // 4
         assert floats > 0 and ctx.sde_state_size(spec.desc()) == 4 * state.size
-        assert ctx.sde_workspace_size(spec.desc(), 65) <= 4 * floats
+        assert ctx.sde_workspace_size(spec.desc(), min(65, max_batch or 65)) <= 4 * floats
         self.whole["workspace"], self.workspace = _guarded(torch, np.zeros(floats, dtype=np.float32))
         self.load(batch)
 
@@ -302,13 +306,14 @@ class _Device(learner_cases._Device):
 _same_update = learner_cases._same_update
 
 
-def update_case(torch, ctx, index, count):
-    """rf_sde_update against the twin as bytes over UPDATES consecutive updates."""
+def update_case(torch, ctx, index, count, max_batch=None):
+    """rf_sde_update against the twin as bytes over UPDATES consecutive updates; with max_batch the workspace has exactly
+    rf_sde_workspace_size(max_batch) bytes between its guards."""
     from reinfocus_amd.environments import learner
 
     spec, params, batch, indices = update_inputs(index, count)
     want = twin_updates(index, count)
-    device = _Device(torch, ctx, spec, params, learner.fresh_state(spec), batch)
+    device = _Device(torch, ctx, spec, params, learner.fresh_state(spec), batch, max_batch)
     for update in range(UPDATES):
         device.call(torch.from_numpy(indices[update]).cuda(), hyper_of(update))
         _same_update(device.outputs(), want[update], f"update {update}")
@@ -383,6 +388,12 @@ def refusal_case(torch, ctx):
     update("fewer than", actions=end - 4 * (device.rows - 1))
     update("fewer than", params=end - 4 * (spec.size - 1))  # (room for P but not for P + L would show here, too)
     update("fewer than", state=end - 8 * spec.size)
+    # a workspace sized for 512 rows offered for 513, which index the same rows again
+    again = torch.from_numpy(np.resize(indices[0][:count], 513)).cuda()
+    sized = ctx.sde_workspace_size(spec.desc(), 512)
+    assert 0 < sized < ctx.sde_workspace_size(spec.desc(), 513) and ctx.sde_workspace_size(spec.desc(), 1025) == 0
+    update("fewer than", workspace=end - sized, batch=513, index=again.data_ptr())
+    update("is not in 1 ..", workspace=end - sized, batch=1025, index=again.data_ptr())
     update("d_params overlaps d_obs", params=device.batch["observations"].data_ptr())
     update("d_state overlaps d_params", state=device.params.data_ptr())
     update("d_stats overlaps d_workspace", stats=device.workspace.data_ptr())
@@ -609,6 +620,9 @@ def run_cases(path):
         for count in BATCHES:
             with record.case(f"update/{index}/{count}"):
                 update_case(torch, ctx, index, count)
+    for index, count in LIMIT_CASES:
+        with record.case(f"update/{index}/{count}"):
+            update_case(torch, ctx, index, count, count)
     with record.case("skips"):
         skip_case(torch, ctx)
     with record.case("refusals"):

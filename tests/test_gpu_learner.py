@@ -7,7 +7,8 @@ that imports torch first (tests/learner_io_cases.py), started once per session; 
 tests/test_learner_logic.py holds the twin to the host build of the kernels' own header on the CPU, on the same inputs.
 The refusal of a capturing caller stream is not tested, as for the rollout.
 
-Development run on an MI355X: all 43 tests pass, the child process takes 3.5 s."""
+Development run on an MI355X: all 52 tests pass, the child process takes 4.4 s (3.2 s before the cases at the batch limits:
+512, 513, 1000 and 1024 rows)."""
 
 import json
 import os
@@ -56,6 +57,16 @@ def test_update_equals_ppo_update_numpy(index, count, recorded):
     _passed(recorded, f"kernel/{index}/{count}")
 
 
+@pytest.mark.parametrize("index,count", cases.LIMIT_CASES,
+                         ids=lambda v: "-".join(str(x) for x in cases.NETWORKS[v]) if v < len(cases.NETWORKS) else str(v))
+def test_update_equals_ppo_update_numpy_at_the_batch_limits(index, count, recorded):
+    """The same at 512 rows (the last minibatch whose block reductions over s_red[kPpoMaxBatch] take one trip), 513 (the
+    first past it: a second trip and a last tile of one row), 1000 (no power of two, no multiple of the tile) and 1024
+    (RF_PPO_MAX_BATCH), on the least network and on stable-baselines3's default, and at 513 on the network with every
+    limit at once.  The workspace has exactly rf_ppo_workspace_size(B) bytes between its guards."""
+    _passed(recorded, f"kernel/{index}/{count}")
+
+
 def test_skipped_updates_change_nothing_on_the_device(recorded):
     """An index past the end and a negative one, an action past the end and a negative one, infinite returns: parameters
     and state keep their bytes, the stats carry the flag, and the next valid update is taken."""
@@ -63,7 +74,7 @@ def test_skipped_updates_change_nothing_on_the_device(recorded):
 
 
 def test_refusals_come_before_anything_is_enqueued(recorded):
-    """A desc outside the limits, N = 0, B = 0 and 1025, every hyper-parameter negative and NaN, an infinite one, betas of
+    """A desc outside the limits, N = 0, B = 0 and 1025, a workspace sized for 512 rows offered for 513, every hyper-parameter negative and NaN, an infinite one, betas of
     1 and above, every pointer NULL and a host pointer, misaligned pointers, arrays, state and workspace that end past
     their allocation, outputs over inputs and over each other: parameters, state and stats keep their bytes every time,
     and the unchanged call is taken afterwards."""

@@ -10,7 +10,7 @@ the siblings' own device cases in this mode (their specs built with enable_criti
 state NaN, every rf_lstm_* call routed to its rf_lstm_critic_* sibling), and three cases of its own.
 tests/test_lstm_critic_logic.py holds the twins to the host build of the kernels' own headers on the CPU.
 
-Development run on an MI355X: all 159 tests pass, the child process takes 8.6 s."""
+Development run on an MI355X: all 185 tests pass, the child process takes 14.4 s (7.9 s before the limit layouts)."""
 
 import json
 import os
@@ -80,6 +80,20 @@ def test_update_equals_the_twin(head, index, name, recorded):
     9-row sequence; the network with every limit at B <= 2), the vf half of lstm_states NaN throughout: parameters,
     optimizer state, stats and the gradient left in the workspace as bytes; the guards around every output keep their
     sentinel."""
+    _passed(recorded, f"update/{head}/{index}/{name}")
+
+
+LIMIT_CASES = [(index, name) for index in cases.GPU_NETWORKS for name in cases.limit_layouts_of(index)]
+
+
+@pytest.mark.parametrize("index,name", LIMIT_CASES, ids=[f"{cases.NETWORKS[i][1]}-{name}" for i, name in LIMIT_CASES])
+@pytest.mark.parametrize("head", cases.HEADS)
+def test_update_equals_the_twin_at_the_limits(head, index, name, recorded):
+    """The same on lstm_learner_io_cases.LIMIT_LAYOUTS, the workspace sized for B exactly: tuned (8-row sequences; B = 8 and
+    64) and depth (sequences of 1, 8, 9, 16 and 17 rows; B = 65 and 68, so the critic's forward grid of B + ceil(B / 8)
+    blocks has 9 tiles) on both networks below the limits; wave (T = 16, n = 64: B = 1024 of one-row sequences, 128 tiles
+    and the second trip of the loss reductions, and B = 513 in 33 sequences) on ppo_lstm_tuned.yml's; one 17-row sequence
+    on the network with every limit."""
     _passed(recorded, f"update/{head}/{index}/{name}")
 
 

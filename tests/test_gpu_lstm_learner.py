@@ -7,7 +7,8 @@ that imports torch first (tests/lstm_learner_io_cases.py), started once per sess
 test below looks its case up.  tests/test_lstm_learner_logic.py holds the twin to the host build of the kernels' own
 header and to torch's autograd on the CPU, on the same inputs.
 
-Development run on an MI355X: all 121 tests pass, the child process takes 10 s."""
+Development run on an MI355X: all 133 tests pass, the child process takes 20 s (9.6 s before the limit layouts; of the 10 s
+they add, 8 are the numpy twin's on the two T = 128, H = 256 cases, which the child computes on the CPU)."""
 
 import json
 import os
@@ -56,6 +57,22 @@ def test_kernels_equal_lstm_update_numpy(index, name, recorded):
     wrap, environment boundaries, start bytes 1, 2 and 255, sequences of one row and of four rows from a stored
     state); every row a start; one sequence of 9 rows (longer than a tile) that spans the minibatch.  The network with
     every limit at once runs at B = 1 and 2."""
+    _passed(recorded, f"kernel/{index}/{name}")
+
+
+@pytest.mark.parametrize("index,name", [(index, name) for index in range(len(cases.NETWORKS))
+                                        for name in cases.limit_layouts_of(index)],
+                         ids=lambda v: v if isinstance(v, str) else "-".join(str(x) for x in cases.NETWORKS[v]))
+def test_kernels_equal_lstm_update_numpy_at_the_limits(index, name, recorded):
+    """The same on tests/lstm_learner_io_cases.py's LIMIT_LAYOUTS, the workspace sized for B exactly.
+    tuned (T = 8, n = 8, ppo_lstm_tuned.yml's): every sequence has the 8 rows both walks prefetch, at B = 8 (first 0, and
+    first 3: a 5-row tail and a 3-row head) and B = 64 = N (8 tiles, 8 sequences).  depth (T = 17, n = 4): sequences of 1,
+    8, 9, 16 and 17 rows at B = 65 and at B = 68 = N from row 5, which wraps.  untuned (T = 128, n = 8, B = 128,
+    ppo_lstm_untuned.yml's): drawn starts, a sequence longer than 64 rows and one of one row, a whole environment from
+    its stored state and rows 100 .. 227 across an environment boundary -- on ppo_lstm_tuned.yml's network and on
+    sb3-contrib's default (H = 256).  wave (T = 16, n = 64): 1024 one-row sequences at B = 1024 = RF_PPO_MAX_BATCH (the
+    widest forward and BPTT grids, 128 MLP tiles, the second trip of the loss reductions) and 33 sequences at B = 513.
+    The network with every limit at once runs one sequence of 17 rows."""
     _passed(recorded, f"kernel/{index}/{name}")
 
 

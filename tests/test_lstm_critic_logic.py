@@ -106,6 +106,29 @@ def test_update_of_the_header_equals_the_twin(head, index, hostcheck):
         assert all(stats[7] == 0 for _, _, stats, _ in want) and bits(want[-1][0]) != bits(want[0][0])
 
 
+LIMIT_CASES = [(index, name) for index in cases.GPU_NETWORKS for name in cases.limit_layouts_of(index)]
+
+
+@pytest.mark.parametrize("index,name", LIMIT_CASES, ids=[f"{cases.NETWORKS[i][1]}-{name}" for i, name in LIMIT_CASES])
+@pytest.mark.parametrize("head", cases.HEADS)
+def test_update_of_the_header_equals_the_twin_at_the_limits(head, index, name, hostcheck):
+    """The same on the limit layouts of tests/lstm_learner_io_cases.py (whose CPU test asserts their sequence lengths):
+    tuned and depth on both networks below the limits, wave (B = 1024 and 513) on ppo_lstm_tuned.yml's, one 17-row sequence
+    on the network with every limit."""
+    spec, params, batch, starts, states, n_steps, num_envs, first, count = cases.layout_inputs(head, index, name)
+    want = cases.twin_updates(head, index, name)
+    state = learner.fresh_state(spec)
+    for update in range(cases.UPDATES):
+        got = cases.host_update(hostcheck, head, spec, params, state, batch, starts, states, n_steps, num_envs, first,
+                                count, cases.hyper_of(update))
+        for what, x, y in zip(("params", "state", "stats", "gradient"), got, want[update]):
+            assert bits(x) == bits(y), f"{name}, update {update}: {what} differ"
+        params, state = got[0], got[1]
+    assert learner.state_parts(spec, state)[0] == cases.UPDATES and np.isfinite(want[-1][2]).all()
+    assert all(stats[7] == 0 for _, _, stats, _ in want) and bits(want[-1][0]) != bits(want[0][0])
+    assert np.isnan(states[:, 1]).all()  # (the vf half of lstm_states is NaN throughout here, too)
+
+
 # ---- 2: the packing -------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("head", cases.HEADS)
 def test_packing_of_an_odd_width_network(head, hostcheck):

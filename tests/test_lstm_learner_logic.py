@@ -1,11 +1,14 @@
 """CPU tests of the recurrent PPO minibatch update's definition (include/reinfocus_hip.h, "lstm update"): the numpy twin
 (lstm_learner.lstm_update_numpy) against the host build of the kernels' own header (tests/lstmppocheck) as bytes, on the
-networks and sequence layouts of the GPU tests; against torch's autograd through torch.nn.LSTM, clip_grad_norm_ and Adam on
+networks and sequence layouts of the GPU tests (the limit layouts among them: sequences of exactly 8, of 16, 17, 68 and 100
+rows, 1024 one-row sequences, what each promises asserted against a plain restatement of the rule); against torch's autograd through torch.nn.LSTM, clip_grad_norm_ and Adam on
 the CPU; the sequence rule against a plain restatement; the loss and skip cases; the numpy LstmLearner; the binding.
 
 The autograd comparison of a development run (printed by the test; profiles/lstm_update.md records it):
     (4, 16, relu):    grad twin 1.89e-08 / torch 1.27e-08; after 1 update 5.84e-08 / 5.84e-08; after 10 updates 2.53e-07 / 2.53e-07
     (7, 65, tanh):    grad twin 4.20e-08 / torch 3.26e-08; after 1 update 5.95e-08 / 5.95e-08; after 10 updates 2.63e-07 / 2.63e-07
+    (4, 16, relu) on T = 128, n = 8, B = 128 (sequences of 22, 1, 9, 68 and 28 rows):
+                      grad twin 1.71e-08 / torch 9.61e-09; after 1 update 5.85e-08 / 5.85e-08; after 10 updates 3.60e-07 / 3.60e-07
 """
 
 import ctypes
@@ -75,6 +78,79 @@ def test_update_of_the_header_equals_the_twin(index, hostcheck):
         assert learner.state_parts(spec, state)[0] == cases.UPDATES and np.isfinite(want[-1][2]).all()
 
 
+LIMIT_CASES = [(index, name) for index in range(len(cases.NETWORKS)) for name in cases.limit_layouts_of(index)]
+
+
+@pytest.mark.parametrize("index,name", LIMIT_CASES, ids=[f"{index}-{name}" for index, name in LIMIT_CASES])
+def test_update_of_the_header_equals_the_twin_at_the_limits(index, name, hostcheck):
+    """The same on the limit layouts (cases.LIMIT_LAYOUTS), one case each: sequences of exactly 8, of 16, 17 and more than
+    64 rows, 1024 one-row sequences, minibatches past 512 rows.  The host build walks rows in plain loops; the tiles, the
+    prefetch and the grids are the GPU test's."""
+    spec, params, batch, starts, states, n_steps, num_envs, first, count = cases.layout_inputs(index, name)
+    want = cases.twin_updates(index, name)
+    state = learner.fresh_state(spec)
+    for update in range(cases.UPDATES):
+        got = host_update(hostcheck, spec, params, state, batch, starts, states, n_steps, num_envs, first, count,
+                          cases.hyper_of(update))
+        same(got, want[update], f"{name}, update {update}")
+        params, state = got[0], got[1]
+    assert learner.state_parts(spec, state)[0] == cases.UPDATES and np.isfinite(want[-1][2]).all()
+    assert all(stats[7] == 0 for _, _, stats, _ in want) and n_steps * num_envs <= learner.MAX_BATCH
+
+
+def lengths_of(name):
+    """(sequence lengths, restated rows) of a layout's minibatch, by the restatement of the rule; the twin's
+    sequence_rows and the header's agree with it."""
+    n_steps, num_envs, kind, first, count = cases.LAYOUTS[name]
+    starts = cases.starts_of(kind, n_steps, num_envs)
+    rows = cases.restated_rows(starts, n_steps, num_envs, first, count)
+    twin = lstm_learner.sequence_rows(starts, n_steps, num_envs, first, count)
+    assert [(r, s, ("zero" if zero else ("stored", t, e)) if s else None) for r, e, t, s, zero in twin] == rows
+    begins = [b for b, row in enumerate(rows) if row[1]]
+    return [int(v) for v in np.diff(begins + [count])], rows
+
+
+def test_limit_layouts_hold_what_they_promise(hostcheck):
+    """tuned: every sequence has 8 rows, but a 5-row tail and a 3-row head at first 3, none enters from zero.  depth:
+    sequences of 1, 8, 9, 16 and 17 rows, start bytes 1, 2 and 255, a wrap at first 5.  untuned: a sequence longer than 64
+    rows and one of one row; the first minibatch is one whole environment entered from a stored non-zero state, the
+    second crosses an environment boundary.  wave: 1024 one-row sequences from zero; 33 sequences without a flag."""
+    assert lengths_of("tuned/0/8")[0] == [8] and lengths_of("tuned/3/8")[0] == [5, 3]
+    lengths, rows = lengths_of("tuned/0/64")
+    assert lengths == [8] * 8 and all(row[2] != "zero" for row in rows) and cases.TILE == 8
+    lengths, rows = lengths_of("depth/0/65")
+    assert lengths == [17, 1, 16, 8, 9, 14] and {1, 8, 9, 16, 17} <= set(lengths)
+    assert [row[2] for row in rows if row[1]] == ["zero", ("stored", 0, 1), "zero", ("stored", 0, 2), "zero", ("stored", 0, 3)]
+    lengths, rows = lengths_of("depth/5/68")
+    assert lengths == [12, 1, 16, 8, 9, 16, 1, 5] and [row[0] for row in rows][62:64] == [67, 0] and rows[63][2] == "zero"
+    assert lengths_of("depth/0/17")[0] == [17]
+    starts = cases.starts_of("depth", 17, 4)
+    assert sorted(starts[starts != 0]) == [1, 1, 2, 255] and (starts != 0).sum(axis=0).tolist() == [1, 1, 1, 1]
+    lengths, rows = lengths_of("untuned/0/128")
+    assert max(lengths) > 64 and 1 in lengths and sum(lengths) == 128
+    assert rows[0] == (0, True, ("stored", 0, 0)) and all(row[0] < 128 for row in rows)
+    states = cases.layout_inputs(cases.TUNED, "untuned/0/128")[4]
+    assert np.abs(states[0, :, :, 0]).min() > 0
+    lengths, rows = lengths_of("untuned/100/128")
+    assert max(lengths) > 64 and [row[0] for row in rows][27:29] == [127, 128] and rows[28][1]
+    starts = cases.starts_of("drawn", 128, 8)
+    episodes = (starts[:128] != 0).sum(axis=0)
+    assert episodes.min() >= 1 and episodes.max() <= 8 and {1, 2, 255} <= set(starts.reshape(-1).tolist())
+    lengths, rows = lengths_of("wave/7/1024")
+    assert lengths == [1] * 1024 and all(row[2] == "zero" for row in rows) and rows[-1][0] == 6
+    assert lengths_of("wave/0/513")[0] == [16] * 32 + [1]
+    for name in cases.LIMIT_LAYOUTS:  # (the header's rule, too)
+        n_steps, num_envs, kind, first, count = cases.LAYOUTS[name]
+        flat = np.ascontiguousarray(cases.starts_of(kind, n_steps, num_envs))
+        row, start, end = (np.zeros(count, dtype=np.int32) for _ in range(3))
+        hostcheck.lpc_sequences(flat.ctypes.data, n_steps, num_envs, first, count, row.ctypes.data, start.ctypes.data,
+                                end.ctypes.data)
+        want = lengths_of(name)[1]
+        assert list(row) == [w[0] for w in want] and [bool(v) for v in start] == [w[1] for w in want], name
+    norms = [stats[5] for _, _, stats, _ in cases.twin_updates(cases.TUNED, "wave/7/1024")]
+    assert norms[1] < learner_schedule()[1][0] and norms[2] > learner_schedule()[2][0]
+
+
 def test_layouts_hold_what_they_promise():
     """A ragged tile, a wrap, an environment boundary, a length-1 sequence, a sequence longer than a tile, a sequence of
     four rows that enters from a stored non-zero state; a norm that clips and one that does not."""
@@ -106,18 +182,22 @@ def learner_schedule():
 AUTOGRAD_STEPS, AUTOGRAD_ENVS, AUTOGRAD_FIRST = 8, 4, 5
 
 
-def autograd_inputs(index):
+def autograd_inputs(index, untuned=False):
     """A rollout of 8 steps of 4 environments taken as ONE minibatch of 32 rows rotated by 5 (so it wraps inside an
     environment); environment 1 runs all 8 rows from a stored non-zero state, the others start episodes inside.  The
-    stored log-probabilities are the twin's own plus normal noise of scale 0.15."""
+    stored log-probabilities are the twin's own plus normal noise of scale 0.15.  untuned: the rollout of cases' untuned
+    layouts instead (T = 128, n = 8, the drawn starts)."""
     spec = cases.spec_of(cases.NETWORKS[index])
     state = lstm_cases.state_dict(spec, 60 + index)
     params = spec.pack(state)
-    n_steps, num_envs = AUTOGRAD_STEPS, AUTOGRAD_ENVS
+    n_steps, num_envs = (128, 8) if untuned else (AUTOGRAD_STEPS, AUTOGRAD_ENVS)
     total = n_steps * num_envs
     rng = np.random.default_rng(index)
     starts = np.zeros((n_steps + 1, num_envs), dtype=np.uint8)
-    starts[0, 0], starts[3, 0], starts[5, 2], starts[0, 3], starts[6, 3] = 1, 1, 1, 1, 1
+    if untuned:
+        starts = cases.starts_of("drawn", n_steps, num_envs)
+    else:
+        starts[0, 0], starts[3, 0], starts[5, 2], starts[0, 3], starts[6, 3] = 1, 1, 1, 1, 1
     states = (0.5 * rng.standard_normal((n_steps + 1,) + spec.state_shape(num_envs))).astype(F32)
     batch = {"observations": rng.standard_normal((total, spec.obs_width)).astype(F32),
              "actions": rng.integers(0, spec.n_actions, total).astype(np.int64),
@@ -136,13 +216,28 @@ def test_gradient_and_updates_are_no_further_from_float64_than_four_times_torch(
     inputs -- the rule and the factor of tests/test_learner_logic.py.  And back-propagation through time is there: with
     the gradient through h_prev / c_prev cut, torch's float64 gradient of weight_hh_l0 of either net moves by more than
     that bound, so an update truncated to one step cannot pass.  Both distances are printed."""
-    spec, state, params, batch, starts, states = autograd_inputs(index)
-    n_steps, num_envs, first, count = AUTOGRAD_STEPS, AUTOGRAD_ENVS, AUTOGRAD_FIRST, AUTOGRAD_STEPS * AUTOGRAD_ENVS
+    held_to_float64(index, False, AUTOGRAD_STEPS, AUTOGRAD_ENVS, AUTOGRAD_FIRST, AUTOGRAD_STEPS * AUTOGRAD_ENVS, 4, tmp_path,
+                    hostcheck)
+
+
+def test_the_same_rule_through_sequences_longer_than_64_rows(tmp_path, hostcheck):
+    """The rule above with the same factor on the untuned layout (T = 128, n = 8, B = 128 from row 0: ppo_lstm_untuned.yml's
+    shape) on ppo_lstm_tuned.yml's network (H = 16): back-propagation through sequences of 22 rows (entered from a stored
+    non-zero state), 1, 9, 68 and 28 rows, against torch's float64 run; cutting the recurrence still moves torch's float64
+    gradient of weight_hh_l0 by more than the bound.  Both distances are printed (profiles/lstm_update.md records a run)."""
+    held_to_float64(cases.TUNED, True, 128, 8, 0, 128, 65, tmp_path, hostcheck)
+
+
+def held_to_float64(index, untuned, n_steps, num_envs, first, count, longest, tmp_path, hostcheck):
+    """longest: some sequence must have at least that many rows."""
+    spec, state, params, batch, starts, states = autograd_inputs(index, untuned)
     rows = lstm_learner.sequence_rows(starts, n_steps, num_envs, first, count)
     begins = [b for b, row in enumerate(rows) if row[3]]
     lengths = np.diff(begins + [count])
+    print(f"{cases.NETWORKS[index]}: sequence lengths {list(lengths)}")
     assert any(length >= 4 and not rows[b][4] and np.abs(states[rows[b][2], :, :, rows[b][1]]).min() > 0
                for b, length in zip(begins, lengths)), "no sequence of 4 rows enters from a non-zero state"
+    assert max(lengths) >= longest, f"no sequence has {longest} rows"
     hyper = learner.Hyper(3e-4, 0.2, 0.01, 0.5, 0.5, 0.9, 0.999, 1e-5, 1)
     updates = 10
     np.savez(tmp_path / "in.npz", names=np.array(spec.keys()), activation=spec.activation, obs=batch["observations"],
@@ -171,16 +266,18 @@ def test_gradient_and_updates_are_no_further_from_float64_than_four_times_torch(
     ours["last"] = params
     assert bits(host_update(hostcheck, spec, spec.pack(state), learner.fresh_state(spec), batch, starts, states, n_steps,
                             num_envs, first, count, hyper)[3]) == bits(grad)
-    bound = None
+    bound, distances = None, []
     for kind in ("grad", "first", "last"):
         exact = theirs[kind + "64"]
         assert theirs[kind + "32"].dtype == F32 and exact.dtype == np.float64
         twin = np.abs(ours[kind].astype(np.float64) - exact).max()
         torch = np.abs(theirs[kind + "32"].astype(np.float64) - exact).max()
-        print(f"{cases.NETWORKS[index]}: {kind}: twin {twin:.3e}, torch {torch:.3e}, ratio {twin / torch:.2f}")
-        assert twin <= 4.0 * torch, (kind, twin, torch)
+        print(f"{cases.NETWORKS[index]}, {count} rows: {kind}: twin {twin:.3e}, torch {torch:.3e}, ratio {twin / torch:.2f}")
+        distances.append((kind, twin, torch))
         if kind == "grad":
             bound = 4.0 * torch
+    for kind, twin, torch in distances:  # (after all three were printed)
+        assert twin <= 4.0 * torch, (kind, twin, torch)
     for name, at, shape, _ in spec.entries:
         if name.endswith("weight_hh_l0"):
             size = int(np.prod(shape))

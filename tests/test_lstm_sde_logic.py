@@ -149,6 +149,27 @@ def test_update_of_the_header_equals_the_twin(index, hostcheck):
         assert learner.state_parts(spec, state)[0] == cases.UPDATES and np.isfinite(want[-1][2]).all()
 
 
+LIMIT_CASES = [(index, name) for index in range(len(cases.NETWORKS)) for name in cases.limit_layouts_of(index)]
+
+
+@pytest.mark.parametrize("index,name", LIMIT_CASES, ids=[f"{NETWORK_IDS[index]}-{name}" for index, name in LIMIT_CASES])
+def test_update_of_the_header_equals_the_twin_at_the_limits(index, name, hostcheck):
+    """The same on the limit layouts of tests/lstm_learner_io_cases.py (whose CPU test asserts their sequence lengths):
+    sequences of exactly 8 rows, of 1, 8, 9, 16 and 17, and of more than 64 rows at B = 128, on the H = 16 network; one
+    17-row sequence on the network with every limit."""
+    spec, params, batch, starts, states, n_steps, num_envs, first, count = cases.layout_inputs(index, name)
+    want = cases.twin_updates(index, name)
+    state = learner.fresh_state(spec)
+    for update in range(cases.UPDATES):
+        got = host_update(hostcheck, spec, params, state, batch, starts, states, n_steps, num_envs, first, count,
+                          cases.hyper_of(update))
+        same(got, want[update], f"{name}, update {update}")
+        params, state = got[0], got[1]
+    assert learner.state_parts(spec, state)[0] == cases.UPDATES and np.isfinite(want[-1][2]).all()
+    assert all(stats[7] == 0 for _, _, stats, _ in want)
+    assert (np.abs(batch["actions"]) > 1).any()  # (raw actions past +-1 are still among the stored ones)
+
+
 def test_inputs_hold_what_they_promise():
     """Raw actions past +-1 among the stored ones; a log_std row of -100, 0 and +3; ratios on both sides of the clip
     range; log_std has a gradient; a norm that clips and one that does not."""

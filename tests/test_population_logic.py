@@ -1,7 +1,9 @@
 """CPU tests of the population (include/reinfocus_hip.h, "population"; environments/population.py): the numpy twins
 PopulationPolicy / PopulationLearner against G independent existing twins (policy.Policy, learner.Learner) with the same
 seeds, hyper-parameters and permutations, bit for bit; the size rules of the grouped entry points and the layout of the
-hyper-parameter record, through the host build of the kernels' own header (tests/popcheck); every refusal; the binding."""
+hyper-parameter record, through the host build of the kernels' own header (tests/popcheck); every refusal; the binding.
+At 64, 65 and 512 groups, too (the forward), at 64 groups on ppo_tuned.yml's first shape (the update), and the 105
+combinations that stand for the 65535 groups of the limit case are pairwise distinct."""
 
 import ctypes
 import os
@@ -80,6 +82,17 @@ def test_population_policy_equals_independent_policies(index, groups, per_group)
         assert all(bits(spread[g]) != bits(spread[0]) for g in range(1, groups))
 
 
+@pytest.mark.parametrize("index,groups,per_group", cases.WIDE_FORWARD)
+def test_wide_population_policy_equals_independent_policies(index, groups, per_group):
+    """The same at 64, 65 and 512 groups (cases.WIDE_FORWARD): what the GPU test compares rf_policy_forward_grouped with
+    at group indices past 4 is G stand-alone policies, each with parameters and a generator of its own."""
+    test_population_policy_equals_independent_policies(index, groups, per_group)
+    spec, twin = cases.twin_policy(index, groups)
+    assert len({bits(row) for row in twin.params}) == groups and len(set(cases.seeds_of(groups))) == groups
+    final_values = cases.wanted_forward(index, groups, per_group, 0, True)[0][3]
+    assert np.isnan(final_values).any() and not np.isnan(final_values).all()
+
+
 def test_rng_state_round_trip_and_state_dicts():
     spec, twin = cases.twin_policy(0, 5)
     obs, _ = cases.forward_inputs(0, 5, 3)
@@ -129,6 +142,61 @@ def test_population_learner_equals_independent_learners(index, batch, per_group)
     assert (stats[:, 7] == 0).all() and len({bits(row) for row in stats[:, :7]}) == groups
     assert bits(params[1]) == bits(before[1]) and bits(params[0]) != bits(before[0]) and bits(params[2]) != bits(before[2])
     assert np.abs(states[1][learner.STATE_HEADER:]).max() > 0
+
+
+def test_wide_population_learner_equals_independent_learners():
+    """cases.WIDE_UPDATE -- 64 groups on ppo_tuned.yml's first shape (m = 8, T = 32, B = 64), two epochs of four chained
+    updates, hyper-parameters that differ between neighbours (cases.wide_hypers) -- against learner.Learner per group, for
+    groups 0, 1, 30 .. 32 and 63; group 31 is flagged RF_PPO_NONFINITE in the one update of each epoch that holds its NaN
+    row and keeps its bytes there, group 1 has learning_rate 0."""
+    w = cases.WIDE_UPDATE
+    want = cases.wide_twin_updates()
+    spec, twin, flat, hypers, order = cases.wide_update_inputs()
+    cases.wide_update_promises(want, twin.params)
+    rows = w["per_group"] * w["steps"]
+    hyper_list = harness.PopulationLearner(twin, **hypers).hypers()
+    for g, (one, other) in enumerate(zip(hyper_list, hyper_list[1:])):
+        assert all(x != y for x, y in zip(one, other)), f"groups {g} and {g + 1} share a hyper-parameter"
+    assert [h.learning_rate == 0 for h in hyper_list] == [g == 1 for g in range(w["groups"])]
+    members = _members(w["index"], w["groups"], base=300)
+    for g in (0, 1, 30, 31, 32, 63):
+        h = hyper_list[g]
+        member = harness.Learner(members[g], learning_rate=h.learning_rate, clip_range=h.clip_range, ent_coef=h.ent_coef,
+                                 vf_coef=h.vf_coef, max_grad_norm=h.max_grad_norm,
+                                 normalize_advantage=bool(h.normalize_advantage), betas=(h.beta1, h.beta2), adam_eps=h.adam_eps)
+        piece = {key: flat[key][g * rows:(g + 1) * rows] for key in learner.BATCH_KEYS}
+        for update, index_rows in enumerate(order):
+            stats = member.update(piece, index_rows[g])
+            assert bits(want[update][2][g]) == bits(stats), f"update {update}, group {g}: stats differ"
+            assert bits(want[update][0][g]) == bits(member.policy.params), f"update {update}, group {g}: params differ"
+            assert bits(want[update][1][g]) == bits(member.state), f"update {update}, group {g}: state differs"
+
+
+def test_the_105_combinations_of_the_group_limit_are_distinct(popcheck, ppocheck):
+    """cases.limit_results: the 35 (parameter set, observation block) pairs give 35 different values, log-probabilities
+    and final values; the 105 combinations give 105 different updated parameters, optimizer states and stats, all taken.
+    limit_arrays hands group g combination g % 105, so neighbouring groups differ in parameters, observations and
+    hyper-parameters.  The size functions of the header take 65535 groups of that shape and refuse 65536."""
+    forwards, updates = cases.limit_results()
+    for i, name in enumerate(cases.ORDER):
+        assert name == "actions" or len({bits(forward[i]) for forward in forwards}) == 35, name
+    assert np.isfinite(np.concatenate([np.concatenate(forward[1:]) for forward in forwards])).all()
+    for i, name in enumerate(("params", "state", "stats")):
+        assert len({bits(update[i]) for update in updates}) == 105, name
+    assert all(update[2][7] == 0 for update in updates)
+    params, blocks, hypers = cases.limit_parts()
+    assert all(bits(update[0]) != bits(params[c % 7]) for c, update in enumerate(updates))
+    inputs, wanted_forward, wanted_update = cases.limit_arrays()
+    assert inputs["params"].shape == (65535, 10) and wanted_update[1].shape == (65535, learner.STATE_HEADER + 20)
+    for key in ("params", "observations", "hyper"):
+        rows = inputs[key].reshape(65535, -1)
+        assert all(rows[g].tobytes() != rows[g + 1].tobytes() for g in range(0, 65534, 257)), key
+    assert bits(wanted_update[0][65534]) == bits(updates[65534 % 105][0]) and 65534 % 105 == 14
+    assert bits(wanted_forward[1][247:248]) == bits(forwards[37][1]) and 247 % 105 == 37
+    desc = ctypes.byref(_native.PolicyDesc(*cases.limit_spec().desc()))
+    assert popcheck.pop_state_size(desc, 65535, 1) == 65535 * ppocheck.ppc_state_size(desc) > 0
+    assert popcheck.pop_workspace_size(desc, 65535, 1, 1, 1) == 65535 * ppocheck.ppc_workspace_size(desc, 1) > 0
+    assert popcheck.pop_state_size(desc, 65536, 1) == 0 and popcheck.pop_workspace_size(desc, 65536, 1, 1, 1) == 0
 
 
 def test_population_train_equals_independent_trains():

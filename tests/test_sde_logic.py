@@ -1,6 +1,6 @@
 """CPU tests of the sde policy's definition (include/reinfocus_hip.h, "sde policy"): the numpy twin (environments/sde.py,
 learner.sde_gradient_numpy) against the host build of the kernels' own headers (tests/sdecheck) as bytes, on the networks
-and batches of the GPU tests; normal32 and log32 against float64; the update against torch's Normal, autograd,
+and batches of the GPU tests (513, 1000 and 1024 rows among them); normal32 and log32 against float64; the update against torch's Normal, autograd,
 clip_grad_norm_ and Adam on the CPU; the log_std gradient alone; packing and the refusals of the surface.
 
 Measured on the development machine (profiles/sde.md records the run): normal32's largest absolute error is 4.60e-7 (at
@@ -129,6 +129,23 @@ def test_update_of_the_header_equals_the_twin(index, count, sdecheck):
         params, state, stats = host_update(sdecheck, spec, params, state, batch, indices[update], cases.hyper_of(update))
         same((params, state, stats), want[update], f"update {update}")
     assert learner.state_parts(spec, state)[0] == cases.UPDATES and np.isfinite(want[-1][2]).all()
+
+
+@pytest.mark.parametrize("index,count", cases.LIMIT_CASES,
+                         ids=lambda v: "-".join(str(x) for x in cases.NETWORKS[v]) if v < len(cases.NETWORKS) else str(v))
+def test_update_of_the_header_equals_the_twin_at_the_batch_limits(index, count, sdecheck):
+    """513, 1000 and 1024 rows (cases.LIMIT_CASES): the twin's order of summation past 512 rows against the host build's
+    plain loops.  The index still repeats a row and some index holds the last row; the schedule still clips once and
+    once not."""
+    test_update_of_the_header_equals_the_twin(index, count, sdecheck)
+    spec, params, batch, indices = cases.update_inputs(index, count)
+    assert batch["actions"].shape[0] == count + 3 and all(chosen.size == count for chosen in indices)
+    assert indices[0][-1] == indices[0][0] and any(count + 2 in chosen for chosen in indices)
+    norms = [stats[5] for _, _, stats in cases.twin_updates(index, count)]
+    assert norms[1] < cases.SCHEDULE[1][0] and norms[2] > cases.SCHEDULE[2][0]
+    desc = ctypes.byref(_native.PolicyDesc(*spec.desc()))
+    assert sdecheck.sdc_workspace_size(desc, 512) < sdecheck.sdc_workspace_size(desc, 513)
+    assert sdecheck.sdc_workspace_size(desc, 1024) > 0 and sdecheck.sdc_workspace_size(desc, 1025) == 0
 
 
 def test_hostile_minibatches_hold_what_they_promise():
