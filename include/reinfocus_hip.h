@@ -513,6 +513,7 @@ int rf_env_get_initializer_state(rf_ctx *ctx, uint64_t state[2], uint64_t inc[2]
  *                                                    21 view stack   float32[n][V]           (learner view)
  *                                                    22 view returns float64[n]
  *                                                    23 view moments float64[3][17]: mean, var, count
+ *                                                       (a grouped view, "population view": float64[G][3][17])
  *                                                    24 RNG states   uint64[rf_num_states][2]
  * (7-12: the scene sets of the last render and the ranks of the environments that ended; 2-6 are the built-in tasks'
  * and the built-in observer's, zero where a composed context does not use them.)  The header also carries the two
@@ -568,9 +569,11 @@ typedef struct rf_env_snapshot_header {
     int32_t scene_len;           /* rf_env_scene_len */
     int32_t last_partial;        /* 1: that set is the compacted one of an auto-reset */
     /* the learner view (rf_env_configure_view; both words were part of `zero`, and are 0 without a view) */
-    uint64_t view_hash;          /* FNV-1a of the rf_env_view_config without `training`; never 0 with a view */
+    uint64_t view_hash;          /* FNV-1a of the rf_env_view_config without `training`; never 0 with a view.  Grouped:
+                                    of that without `gamma`, then G and the G gammas */
     int32_t view_training;       /* content, not fingerprint: rf_env_view_set_training's flag, restored with the blob */
-    uint8_t zero[140];
+    int32_t view_groups;         /* G of rf_env_configure_view_grouped; 0 (as when it was part of `zero`) ungrouped */
+    uint8_t zero[136];
 } rf_env_snapshot_header;
 int rf_env_snapshot_size(rf_ctx *ctx, uint64_t *bytes);
 int rf_env_snapshot(rf_ctx *ctx, void *host_out, uint64_t bytes);
@@ -754,6 +757,59 @@ int rf_env_step_device_view(rf_ctx *ctx, const void *d_actions, int action_dtype
                             int32_t *d_lengths, float *d_view_obs, double *d_view_rewards, float *d_view_final,
                             void *caller_stream);
 int rf_env_reset_device_view(rf_ctx *ctx, float *d_obs, float *d_view_obs, void *caller_stream);
+
+/* ---- population view: a normaliser and GAE discounts per group of a population -----------------------------------------
+ * The population ("population", below) trains G PPO learners in lock-step over one environment of n = G m lanes, group g
+ * owning lanes [g m, (g + 1) m); write g(e) = e / m.  For those G learners to be G independent trials -- the
+ * reference's examples/optimize_hyperparameters.py runs trials of n_envs: 8 with normalize: true, and gamma and
+ * gae_lambda are among the first things rl_zoo3's sample_ppo_params draws -- each group has running moments of its own
+ * and discounts of its own.  One definition, host twins (harness._GroupedLearnerView: literally G _LearnerView objects
+ * over lane slices; rollout.gae_numpy_grouped) and device alike.
+ *
+ * State and parameters: moments float64 [G][3][17] (mean, var, count), every group starting at (0, 1, 1e-4); gamma
+ * float64 [G].  The definition of "learner view" changes only as follows:
+ *   update(moments[g], x[g m .. (g + 1) m))  N = float64(m); treesum runs over the group's m leaves, padded with +0.0 to
+ *                       P_m, the next power of two >= m (treesum itself is unchanged, its final + (+0.0) included).
+ *   step 3              returns[e] = returns[e] * gamma[g(e)] + reward[e], then one update of slot W per group, from that
+ *                       group's returns.
+ *   normalise           by moments[g(e)]; the view reward by moments[g(e)].var[W].
+ * The stack shift, view_final, the zeroing of ended lanes, training, epsilon and the clips are unchanged and common to
+ * all groups.  GAE ("rollout") changes only in that g and gl are per lane: g = float32(gamma[g(e)]),
+ * gl = float32(gamma[g(e)] * gae_lambda[g(e)]) with the product taken in float64, also in the bootstrap
+ * r + g * final_values.  With G = 1 every result is bit for bit the ungrouped one.  VecNormalize's gamma (here) and the
+ * rollout's gamma (d_discounts) are passed separately; rl_zoo3 sets both from the trial's gamma.
+ *
+ * Kernels (csrc/rf_env_view.h, csrc/rf_rollout.h): a step still makes one moments launch and one apply launch.  Groups
+ * of at most 64 lanes (P_m <= 64) take env_view_moments_packed_kernel -- 256 / P_m groups of one slot per 256-thread
+ * block, the tree a xor-butterfly inside the segment's wave, no LDS and no barrier --, wider groups
+ * env_view_moments_kernel<true> with one block per (slot, group).
+ *
+ *   rf_env_configure_view_grouped       rf_env_configure_view with `groups` groups; gammas: host double[groups], or NULL
+ *                                       for cfg->gamma in every group (cfg->gamma is otherwise not used).  Refused with
+ *                                       nothing changed: everything rf_env_configure_view refuses, a NULL cfg, groups
+ *                                       outside 1 .. RF_POPULATION_MAX_GROUPS, n not divisible by groups, a gamma outside
+ *                                       [0, 1].  rf_env_configure_view and rf_env_view_config do not change.
+ *   rf_env_view_get_statistics_grouped  mean / var / count, float64 [G][W + 1] each; each pointer may be NULL.  The
+ *   rf_env_view_set_statistics_grouped  ungrouped accessors are refused on a context configured with the grouped call,
+ *                                       these on any other.
+ *   rf_rollout_advantages_grouped       rf_rollout_advantages with d_discounts, device float32 [groups][2] holding
+ *                                       (g, gl) per group, 8-byte aligned, the caller's and vouched for like the other
+ *                                       arrays, in place of the two scalars.  Refusals: rf_rollout_advantages's, a NULL
+ *                                       d_discounts, groups outside 1 .. RF_POPULATION_MAX_GROUPS, n not divisible by groups.
+ * Snapshots: for a grouped context array 23 is float64 [G][3][17], the header's view_groups word is G, and view_hash also
+ * covers G and the gammas; ungrouped blobs stay byte for byte what they are.  A grouped blob into an ungrouped context,
+ * or into one with other gammas, is refused with nothing changed, and so is the reverse.
+ *
+ * Out of scope: the sde, lstm and lstm-sde heads; groups that differ in m, T, B or architecture; SB3Wrapper; and the
+ * environment's shared reset-state generator -- lanes that end are ranked across all groups, so which reset state a lane
+ * draws depends on other groups' episode ends.  The independence claimed here covers what the learner is given the raw
+ * step; it does not cover the environment's draws. */
+int rf_env_configure_view_grouped(rf_ctx *ctx, const rf_env_view_config *cfg, int groups, const double *gammas);
+int rf_env_view_get_statistics_grouped(rf_ctx *ctx, double *mean, double *var, double *count);
+int rf_env_view_set_statistics_grouped(rf_ctx *ctx, const double *mean, const double *var, const double *count);
+int rf_rollout_advantages_grouped(rf_ctx *ctx, int T, int n, int groups, const double *d_rewards, const float *d_values,
+                                  const uint8_t *d_truncated, const float *d_final_values, const float *d_last_values,
+                                  const float *d_discounts, float *d_advantages, float *d_returns, void *caller_stream);
 
 /* ---- rollout: GAE advantages and returns of a PPO rollout in one launch -----------------------------------------------
  * The consumer of device steps in the reference's PPO configurations is stable-baselines3's RolloutBuffer: T = n_steps
@@ -1290,8 +1346,8 @@ int rf_lstm_critic_sde_update(rf_ctx *ctx, const rf_lstm_critic_desc *desc, cons
  *  G7 Stats and skips.  d_stats is float32 [G][8].  A group whose minibatch is invalid or whose gradient norm is not finite
  *     is skipped and flagged in its own stats[7] exactly as step 8 says; the other groups are untouched by it.
  * Limits: G 1 .. RF_POPULATION_MAX_GROUPS (the grid's y / z limit), m >= 1, G m <= 2^30 (G N alike), B as in G4.
- * Out of scope: per-group gamma / gae_lambda (a rollout's GAE keeps its scalars), per-group learner-view statistics, the
- * sde and lstm heads, groups that differ in architecture, m, T or B.
+ * A normaliser and GAE discounts per group: "population view", above.  Out of scope: the sde and lstm heads, groups that
+ * differ in architecture, m, T or B.
  *
  *   rf_policy_forward_grouped      rf_policy_forward over (G, m) in place of n: one launch, grid (ceil(m / 8), nets, G);
  *                                  the same outputs over G m rows, the same refusals (with d_gens, a device array, in

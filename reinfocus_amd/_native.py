@@ -96,6 +96,10 @@ SYMBOLS = (
     "rf_env_step_device_view",
     "rf_env_reset_device_view",
     "rf_rollout_advantages",
+    "rf_env_configure_view_grouped",
+    "rf_env_view_get_statistics_grouped",
+    "rf_env_view_set_statistics_grouped",
+    "rf_rollout_advantages_grouped",
     "rf_policy_params_size",
     "rf_policy_forward",
     "rf_ppo_state_size",
@@ -392,6 +396,10 @@ def load():
     lib.rf_env_step_device_view.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.rf_env_reset_device_view.argtypes = [vp, vp, vp, vp]
     lib.rf_rollout_advantages.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, ctypes.c_double, ctypes.c_double, vp, vp, vp]
+    lib.rf_env_configure_view_grouped.argtypes = [vp, ctypes.POINTER(EnvViewConfig), i32, vp]
+    lib.rf_env_view_get_statistics_grouped.argtypes = [vp, vp, vp, vp]
+    lib.rf_env_view_set_statistics_grouped.argtypes = [vp, vp, vp, vp]
+    lib.rf_rollout_advantages_grouped.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.rf_policy_params_size.restype = ctypes.c_ulonglong
     lib.rf_policy_params_size.argtypes = [vp, vp]
     lib.rf_policy_forward.argtypes = [vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
@@ -781,6 +789,16 @@ class Context:
         if rc != 0:
             _check(rc)
 
+    def rollout_advantages_grouped(self, steps, num_envs, groups, rewards_ptr, values_ptr, truncated_ptr, final_values_ptr,
+                                   last_values_ptr, discounts_ptr, advantages_ptr, returns_ptr, stream):
+        """rf_rollout_advantages_grouped: rollout_advantages with the discounts of `groups` groups of consecutive
+        environments, device float32 [groups][2] holding (g, gl), in place of the two scalars.  Only enqueues."""
+        rc = self._lib.rf_rollout_advantages_grouped(self._h, steps, num_envs, groups, rewards_ptr, values_ptr,
+                                                     truncated_ptr, final_values_ptr, last_values_ptr, discounts_ptr,
+                                                     advantages_ptr, returns_ptr, stream)
+        if rc != 0:
+            _check(rc)
+
     # --- policy (rf_policy_forward): addresses of device memory as plain integers, nothing waited for -----------------
     def policy_params_size(self, desc):
         """rf_policy_params_size: floats of the packed parameters of `desc` (the nine integers of rf_policy_desc in
@@ -1082,12 +1100,39 @@ class Context:
 
     # --- learner view (rf_env_configure_view ...) ------------------------------------------------------------------
     _env_view_stack = 0  # frame_stack of the configured learner view (0: none)
+    _env_view_groups = 0  # G of a grouped learner view (0: none, or ungrouped)
 
     def env_configure_view(self, config):
         """rf_env_configure_view: an EnvViewConfig -- the context keeps a learner view from now on (after env_configure*
         and env_configure_records, before the first env_reset) --, or None: it stops."""
         _check(self._lib.rf_env_configure_view(self._h, None if config is None else ctypes.byref(config)))
         self._env_view_stack = 0 if config is None else int(config.frame_stack)
+        self._env_view_groups = 0
+
+    def env_configure_view_grouped(self, config, groups, gammas=None):
+        """rf_env_configure_view_grouped: env_configure_view with `groups` groups of n / groups consecutive environments,
+        each with running moments of its own and its own gamma (gammas: `groups` values, or None for config.gamma)."""
+        if gammas is not None:
+            gammas = np.ascontiguousarray(gammas, dtype=np.float64)
+            assert gammas.shape == (groups,), f"gammas of shape {gammas.shape}, not ({groups},)"
+        _check(self._lib.rf_env_configure_view_grouped(self._h, ctypes.byref(config), groups,
+                                                       None if gammas is None else _ptr(gammas)))
+        self._env_view_stack = int(config.frame_stack)
+        self._env_view_groups = int(groups)
+
+    def env_view_statistics_grouped(self):
+        """rf_env_view_get_statistics_grouped: (mean, var, count), float64[G, W + 1] each, the returns last."""
+        arrays = [np.empty((max(self._env_view_groups, 1), self._env_obs_width + 1), dtype=np.float64) for _ in range(3)]
+        _check(self._lib.rf_env_view_get_statistics_grouped(self._h, *[_ptr(a) for a in arrays]))
+        return tuple(arrays)
+
+    def env_view_set_statistics_grouped(self, mean, var, count):
+        """rf_env_view_set_statistics_grouped: float64[G, W + 1] each, the returns last."""
+        arrays = [np.ascontiguousarray(a, dtype=np.float64) for a in (mean, var, count)]
+        shape = (max(self._env_view_groups, 1), self._env_obs_width + 1)
+        for a in arrays:
+            assert a.shape == shape, f"statistics of shape {a.shape}, not {shape}"
+        _check(self._lib.rf_env_view_set_statistics_grouped(self._h, *[_ptr(a) for a in arrays]))
 
     def env_view(self, rewards=True, final=False):
         """rf_env_get_view: the view of the last step or reset as fresh arrays -- (obs float32[n, V], rewards float64[n]

@@ -67,32 +67,52 @@ int drop_view(rf_ctx *ctx)
     ctx->view_reward = ctx->view_returns = nullptr;
     ctx->view_stack = ctx->view_final = nullptr;
     ctx->view_moments = nullptr;
+    ctx->view_groups = 0;
+    ctx->view_grp = rf::EnvViewGroups{};
+    ctx->view_gammas.clear();
     return RF_OK;
 }
 
 // The view's two kernels, after a step's body or (reset) a reset's, on the ctx's stream and outside any replayed graph:
 // env_view_moments_kernel while training -- one block per observation column with norm_obs, one more for the returns in
 // a step --, then env_view_apply_kernel.  out_*: the caller's device arrays of rf_env_step_device_view /
-// rf_env_reset_device_view, or null.
+// rf_env_reset_device_view, or null.  A grouped view (rf_env_configure_view_grouped) takes the kGrouped instantiations:
+// the moments by env_view_moments_packed_kernel where a group fits a wave (P_m <= 64), else one block per (slot, group).
+// Either way one moments launch and one apply launch.
 int enqueue_view(rf_ctx *ctx, bool reset, float *out_obs, double *out_reward, float *out_final)
 {
     const rf::EnvViewConfig &c = ctx->view_cfg;
+    const rf::EnvViewGroups &grp = ctx->view_grp;
+    const bool grouped = ctx->view_groups > 0;
     const int obs_blocks = c.norm_obs ? c.width : 0, blocks = obs_blocks + (reset ? 0 : 1);
     if (ctx->view_training && blocks > 0) {
-        long long p = 1; // the next power of two >= n; a thread owns p / 1024 leaves (at least one)
-        while (p < c.n)
+        long long p = 1; // the next power of two >= n (grouped: >= m); a thread owns p / 1024 leaves (at least one)
+        while (p < (grouped ? grp.m : c.n))
             p <<= 1;
         const int leaves = p > rf::kViewBlock ? (int)(p / rf::kViewBlock) : 1;
-        hipLaunchKernelGGL(rf::env_view_moments_kernel, dim3(blocks), dim3(rf::kViewBlock), 0, ctx->stream, c, obs_blocks,
-                           leaves, (const float *)ctx->env.obs, (const double *)ctx->env.reward, ctx->view_returns,
-                           ctx->view_moments);
+        if (!grouped) {
+            hipLaunchKernelGGL(rf::env_view_moments_kernel<false>, dim3(blocks), dim3(rf::kViewBlock), 0, ctx->stream, c,
+                               obs_blocks, leaves, (const float *)ctx->env.obs, (const double *)ctx->env.reward,
+                               ctx->view_returns, ctx->view_moments, grp);
+        } else if (p <= rf::kViewPackedMax) {
+            const unsigned threads = (unsigned)grp.groups << grp.log2_pm; // <= 65535 * 64
+            hipLaunchKernelGGL(rf::env_view_moments_packed_kernel,
+                               dim3((threads + rf::kViewPackedBlock - 1) / rf::kViewPackedBlock, blocks),
+                               dim3(rf::kViewPackedBlock), 0, ctx->stream, c, obs_blocks, (const float *)ctx->env.obs,
+                               (const double *)ctx->env.reward, ctx->view_returns, ctx->view_moments, grp);
+        } else {
+            hipLaunchKernelGGL(rf::env_view_moments_kernel<true>, dim3(blocks, grp.groups), dim3(rf::kViewBlock), 0,
+                               ctx->stream, c, obs_blocks, leaves, (const float *)ctx->env.obs,
+                               (const double *)ctx->env.reward, ctx->view_returns, ctx->view_moments, grp);
+        }
     }
     const int cells = c.n * c.width;
-    hipLaunchKernelGGL(rf::env_view_apply_kernel, dim3((cells + 255) / 256), dim3(256), 0, ctx->stream, c, reset ? 1 : 0,
+    const auto apply = grouped ? rf::env_view_apply_kernel<true> : rf::env_view_apply_kernel<false>;
+    hipLaunchKernelGGL(apply, dim3((cells + 255) / 256), dim3(256), 0, ctx->stream, c, reset ? 1 : 0,
                        (const float *)ctx->env.obs, (const double *)ctx->env.reward, (const uint8_t *)ctx->env.truncated,
                        (const float *)(ctx->view_final ? ctx->env.final_obs : nullptr),
                        (const rf::EnvViewMoments *)ctx->view_moments, ctx->view_stack, ctx->view_returns, ctx->view_reward,
-                       ctx->view_final, out_obs, out_reward, out_final);
+                       ctx->view_final, out_obs, out_reward, out_final, grp);
     RF_HIP(hipGetLastError());
     ctx->view_after_step = !reset;
     return RF_OK;
@@ -1715,9 +1735,10 @@ int rf_env_reset_device_view(rf_ctx *ctx, float *d_obs, float *d_view_obs, void 
 }
 
 // ---- the learner view's entry points (include/reinfocus_hip.h, "learner view") -----------------------------------------
-int rf_env_configure_view(rf_ctx *ctx, const rf_env_view_config *cfg)
+// rf_env_configure_view (groups = 0) and rf_env_configure_view_grouped (groups >= 1; gammas: host double[groups], or
+// NULL for cfg->gamma everywhere)
+static int configure_view(rf_ctx *ctx, const rf_env_view_config *cfg, int groups, const double *gammas, const char *fn)
 {
-    const char *fn = "rf_env_configure_view";
     RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", fn);
     RF_REQUIRE(ctx->env_ready, "%s: rf_env_configure first", fn);
     RF_REQUIRE(ctx->env_pending < 0, "%s: a two-phase or planned step is open", fn);
@@ -1735,6 +1756,14 @@ int rf_env_configure_view(rf_ctx *ctx, const rf_env_view_config *cfg)
         RF_REQUIRE((long long)ctx->env_host.n * ctx->env_obs_width * cfg->frame_stack < (1ll << 31),
                    "%s: %d environments x %d columns x %d frames do not fit a 32-bit index", fn, ctx->env_host.n,
                    ctx->env_obs_width, cfg->frame_stack);
+        if (groups) {
+            RF_REQUIRE(groups >= 1 && groups <= RF_POPULATION_MAX_GROUPS, "%s: groups %d outside 1 to %d", fn, groups,
+                       RF_POPULATION_MAX_GROUPS);
+            RF_REQUIRE(ctx->env_host.n % groups == 0, "%s: %d groups do not divide %d environments", fn, groups,
+                       ctx->env_host.n);
+            for (int g = 0; gammas && g < groups; ++g)
+                RF_REQUIRE(gammas[g] >= 0.0 && gammas[g] <= 1.0, "%s: gamma %g of group %d outside [0, 1]", fn, gammas[g], g);
+        }
     }
     RF_HIP(hipSetDevice(ctx->device));
     drop_env_snapshots(ctx); // (their layout is the other setting's)
@@ -1744,10 +1773,13 @@ int rf_env_configure_view(rf_ctx *ctx, const rf_env_view_config *cfg)
         return RF_OK;
     const size_t n = (size_t)ctx->env_host.n, width = (size_t)ctx->env_obs_width, cells = n * width * (size_t)cfg->frame_stack;
     const bool records = ctx->env_records;
-    // [view_reward | stack | view_final]: the piece rf_env_get_view copies; then the returns and the moments
+    // [view_reward | stack | view_final]: the piece rf_env_get_view copies; then the returns and the moments (grouped:
+    // one EnvViewMoments per group, then the groups' gammas)
+    const size_t sets = groups ? (size_t)groups : 1;
     const size_t out_bytes = n * 8 + cells * 4 + (records ? cells * 4 : 0);
     const size_t o_returns = (out_bytes + 255) & ~(size_t)255, o_moments = (o_returns + n * 8 + 255) & ~(size_t)255;
-    const size_t bytes = o_moments + sizeof(rf::EnvViewMoments);
+    const size_t o_gammas = (o_moments + sets * sizeof(rf::EnvViewMoments) + 255) & ~(size_t)255;
+    const size_t bytes = groups ? o_gammas + sets * 8 : o_moments + sizeof(rf::EnvViewMoments);
     if (ctx->h_view_bytes < out_bytes) { // (rf_env_get_view's pinned block; before anything changes)
         RF_HIP(hipStreamSynchronize(ctx->stream));
         if (ctx->h_view)
@@ -1772,7 +1804,17 @@ int rf_env_configure_view(rf_ctx *ctx, const rf_env_view_config *cfg)
         m.var[i] = 1.0;
         m.count[i] = 1e-4;
     }
-    RF_HIP(hipMemcpyAsync(ctx->view_moments, &m, sizeof(m), hipMemcpyHostToDevice, ctx->stream));
+    if (groups) {
+        ctx->view_moments_groups.assign(sets, m);
+        ctx->view_gammas.assign(sets, cfg->gamma);
+        if (gammas)
+            ctx->view_gammas.assign(gammas, gammas + sets);
+        RF_HIP(hipMemcpyAsync(ctx->view_moments, ctx->view_moments_groups.data(), sets * sizeof(m), hipMemcpyHostToDevice,
+                              ctx->stream));
+        RF_HIP(hipMemcpyAsync(base + o_gammas, ctx->view_gammas.data(), sets * 8, hipMemcpyHostToDevice, ctx->stream));
+    } else {
+        RF_HIP(hipMemcpyAsync(ctx->view_moments, &m, sizeof(m), hipMemcpyHostToDevice, ctx->stream));
+    }
     RF_HIP(hipStreamSynchronize(ctx->stream));
     ctx->view_host = *cfg;
     ctx->view_host.norm_obs = cfg->norm_obs != 0;
@@ -1780,10 +1822,36 @@ int rf_env_configure_view(rf_ctx *ctx, const rf_env_view_config *cfg)
     ctx->view_host.training = cfg->training != 0;
     ctx->view_cfg = rf::EnvViewConfig{ctx->env_host.n, ctx->env_obs_width, cfg->frame_stack, cfg->norm_obs != 0,
                                       cfg->norm_reward != 0, cfg->gamma, cfg->epsilon, cfg->clip_obs, cfg->clip_reward};
+    ctx->view_groups = groups;
+    if (groups) {
+        const int m_lanes = ctx->env_host.n / groups;
+        int log2_pm = 0;
+        while ((1ll << log2_pm) < m_lanes)
+            ++log2_pm;
+        ctx->view_grp = rf::EnvViewGroups{groups, m_lanes, log2_pm, (const double *)(base + o_gammas)};
+    }
     ctx->view_training = cfg->training != 0;
     ctx->view_after_step = false;
     ctx->env_view = true;
     return RF_OK;
+}
+
+int rf_env_configure_view(rf_ctx *ctx, const rf_env_view_config *cfg)
+{
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", "rf_env_configure_view");
+    RF_HIP(hipSetDevice(ctx->device));
+    return configure_view(ctx, cfg, 0, nullptr, "rf_env_configure_view");
+}
+
+int rf_env_configure_view_grouped(rf_ctx *ctx, const rf_env_view_config *cfg, int groups, const double *gammas)
+{
+    const char *fn = "rf_env_configure_view_grouped";
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", fn);
+    RF_HIP(hipSetDevice(ctx->device));
+    RF_REQUIRE(cfg != nullptr, "%s: cfg is NULL (rf_env_configure_view(ctx, NULL) turns a view off)", fn);
+    RF_REQUIRE(groups >= 1 && groups <= RF_POPULATION_MAX_GROUPS, "%s: groups %d outside 1 to %d", fn, groups,
+               RF_POPULATION_MAX_GROUPS);
+    return configure_view(ctx, cfg, groups, gammas, fn);
 }
 
 int rf_env_get_view(rf_ctx *ctx, float *host_obs, double *host_rewards, float *host_final)
@@ -1815,6 +1883,7 @@ int rf_env_view_get_statistics(rf_ctx *ctx, double *mean, double *var, double *c
     const char *fn = "rf_env_view_get_statistics";
     RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", fn);
     RF_REQUIRE(ctx->env_ready && ctx->env_view, "%s: the context has no learner view (rf_env_configure_view)", fn);
+    RF_REQUIRE(ctx->view_groups == 0, "%s: the learner view is grouped (rf_env_view_get_statistics_grouped)", fn);
     RF_HIP(hipSetDevice(ctx->device));
     rf::EnvViewMoments m;
     RF_HIP(hipMemcpyAsync(&m, ctx->view_moments, sizeof(m), hipMemcpyDeviceToHost, ctx->stream));
@@ -1834,6 +1903,7 @@ int rf_env_view_set_statistics(rf_ctx *ctx, const double *mean, const double *va
     const char *fn = "rf_env_view_set_statistics";
     RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", fn);
     RF_REQUIRE(ctx->env_ready && ctx->env_view, "%s: the context has no learner view (rf_env_configure_view)", fn);
+    RF_REQUIRE(ctx->view_groups == 0, "%s: the learner view is grouped (rf_env_view_set_statistics_grouped)", fn);
     RF_REQUIRE(ctx->env_pending < 0, "%s: a two-phase or planned step is open", fn);
     RF_HIP(hipSetDevice(ctx->device));
     rf::EnvViewMoments &m = ctx->view_moments_host;
@@ -1847,6 +1917,58 @@ int rf_env_view_set_statistics(rf_ctx *ctx, const double *mean, const double *va
     if (count)
         memcpy(m.count, count, bytes);
     RF_HIP(hipMemcpyAsync(ctx->view_moments, &m, sizeof(m), hipMemcpyHostToDevice, ctx->stream));
+    RF_HIP(hipStreamSynchronize(ctx->stream));
+    return RF_OK;
+}
+
+// float64 [G][W + 1] each, the returns last; each pointer may be NULL.  Synchronous.
+int rf_env_view_get_statistics_grouped(rf_ctx *ctx, double *mean, double *var, double *count)
+{
+    const char *fn = "rf_env_view_get_statistics_grouped";
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", fn);
+    RF_REQUIRE(ctx->env_ready && ctx->env_view, "%s: the context has no learner view (rf_env_configure_view)", fn);
+    RF_REQUIRE(ctx->view_groups > 0, "%s: the learner view is not grouped (rf_env_configure_view_grouped)", fn);
+    RF_HIP(hipSetDevice(ctx->device));
+    std::vector<rf::EnvViewMoments> sets((size_t)ctx->view_groups);
+    RF_HIP(hipMemcpyAsync(sets.data(), ctx->view_moments, sets.size() * sizeof(rf::EnvViewMoments), hipMemcpyDeviceToHost,
+                          ctx->stream));
+    RF_HIP(hipStreamSynchronize(ctx->stream));
+    const size_t row = (size_t)ctx->env_obs_width + 1;
+    for (size_t g = 0; g < sets.size(); ++g) {
+        if (mean)
+            memcpy(mean + g * row, sets[g].mean, row * sizeof(double));
+        if (var)
+            memcpy(var + g * row, sets[g].var, row * sizeof(double));
+        if (count)
+            memcpy(count + g * row, sets[g].count, row * sizeof(double));
+    }
+    return RF_OK;
+}
+
+int rf_env_view_set_statistics_grouped(rf_ctx *ctx, const double *mean, const double *var, const double *count)
+{
+    const char *fn = "rf_env_view_set_statistics_grouped";
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", fn);
+    RF_REQUIRE(ctx->env_ready && ctx->env_view, "%s: the context has no learner view (rf_env_configure_view)", fn);
+    RF_REQUIRE(ctx->view_groups > 0, "%s: the learner view is not grouped (rf_env_configure_view_grouped)", fn);
+    RF_REQUIRE(ctx->env_pending < 0, "%s: a two-phase or planned step is open", fn);
+    RF_HIP(hipSetDevice(ctx->device));
+    std::vector<rf::EnvViewMoments> &sets = ctx->view_moments_groups;
+    sets.resize((size_t)ctx->view_groups);
+    RF_HIP(hipMemcpyAsync(sets.data(), ctx->view_moments, sets.size() * sizeof(rf::EnvViewMoments), hipMemcpyDeviceToHost,
+                          ctx->stream));
+    RF_HIP(hipStreamSynchronize(ctx->stream));
+    const size_t row = (size_t)ctx->env_obs_width + 1;
+    for (size_t g = 0; g < sets.size(); ++g) {
+        if (mean)
+            memcpy(sets[g].mean, mean + g * row, row * sizeof(double));
+        if (var)
+            memcpy(sets[g].var, var + g * row, row * sizeof(double));
+        if (count)
+            memcpy(sets[g].count, count + g * row, row * sizeof(double));
+    }
+    RF_HIP(hipMemcpyAsync(ctx->view_moments, sets.data(), sets.size() * sizeof(rf::EnvViewMoments), hipMemcpyHostToDevice,
+                          ctx->stream));
     RF_HIP(hipStreamSynchronize(ctx->stream));
     return RF_OK;
 }
@@ -1891,14 +2013,22 @@ int rf_env_device_status(rf_ctx *ctx, int *fault_step, int *fault_env)
     return RF_OK;
 }
 
-int rf_rollout_advantages(rf_ctx *ctx, int T, int n, const double *d_rewards, const float *d_values,
-                          const uint8_t *d_truncated, const float *d_final_values, const float *d_last_values, double gamma,
-                          double gae_lambda, float *d_advantages, float *d_returns, void *caller_stream)
+// rf_rollout_advantages (groups = 0: the scalars) and rf_rollout_advantages_grouped (groups >= 1: d_discounts)
+static int rollout_advantages(rf_ctx *ctx, int T, int n, int groups, const double *d_rewards, const float *d_values,
+                              const uint8_t *d_truncated, const float *d_final_values, const float *d_last_values,
+                              double gamma, double gae_lambda, const float *d_discounts, float *d_advantages,
+                              float *d_returns, void *caller_stream, const char *fn)
 {
-    const char *fn = "rf_rollout_advantages";
     RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", fn);
-    RF_REQUIRE(d_rewards && d_values && d_truncated && d_last_values && d_advantages && d_returns, "%s: NULL argument", fn);
+    RF_REQUIRE(d_rewards && d_values && d_truncated && d_last_values && d_advantages && d_returns &&
+                   (groups == 0 || d_discounts),
+               "%s: NULL argument", fn);
     RF_REQUIRE(T >= 1 && n >= 1, "%s: T = %d and n = %d must both be at least 1", fn, T, n);
+    if (groups) {
+        RF_REQUIRE(groups >= 1 && groups <= RF_POPULATION_MAX_GROUPS, "%s: groups %d outside 1 to %d", fn, groups,
+                   RF_POPULATION_MAX_GROUPS);
+        RF_REQUIRE(n % groups == 0, "%s: %d groups do not divide %d environments", fn, groups, n);
+    }
     RF_HIP(hipSetDevice(ctx->device));
     const size_t cells = (size_t)T * (size_t)n;
     struct Array {
@@ -1910,10 +2040,11 @@ int rf_rollout_advantages(rf_ctx *ctx, int T, int n, const double *d_rewards, co
                             {d_values, cells * 4, 4, "d_values"},
                             {d_truncated, cells, 1, "d_truncated"},
                             {d_final_values, cells * 4, 4, "d_final_values"},
-                            {d_last_values, (size_t)n * 4, 4, "d_last_values"}};
+                            {d_last_values, (size_t)n * 4, 4, "d_last_values"},
+                            {groups ? d_discounts : nullptr, (size_t)groups * 8, 8, "d_discounts"}};
     const Array outputs[] = {{d_advantages, cells * 4, 4, "d_advantages"}, {d_returns, cells * 4, 4, "d_returns"}};
     for (const Array &a : inputs) {
-        if (a.p == nullptr) // (d_final_values: no bootstrap)
+        if (a.p == nullptr) // (d_final_values: no bootstrap; d_discounts: the scalars)
             continue;
         if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
             return rc;
@@ -1933,10 +2064,39 @@ int rf_rollout_advantages(rf_ctx *ctx, int T, int n, const double *d_rewards, co
     // every array is the caller's, so the launch goes to the caller's stream: no event hand-over, nothing waited for
     const float g = (float)gamma, gl = (float)(gamma * gae_lambda); // (the product in float64 first, as numpy takes it)
     const unsigned blocks = (unsigned)(((size_t)n + rf::kRolloutTile - 1) / rf::kRolloutTile);
-    hipLaunchKernelGGL(rf::rollout_gae_kernel, dim3(blocks), dim3(rf::kRolloutThreads), 0, caller, T, n, d_rewards, d_values,
-                       d_truncated, d_final_values, d_last_values, g, gl, d_advantages, d_returns);
+    if (groups)
+        hipLaunchKernelGGL(rf::rollout_gae_kernel<true>, dim3(blocks), dim3(rf::kRolloutThreads), 0, caller, T, n, d_rewards,
+                           d_values, d_truncated, d_final_values, d_last_values, 0.0f, 0.0f, d_advantages, d_returns,
+                           (const float2 *)d_discounts, n / groups);
+    else
+        hipLaunchKernelGGL(rf::rollout_gae_kernel<false>, dim3(blocks), dim3(rf::kRolloutThreads), 0, caller, T, n, d_rewards,
+                           d_values, d_truncated, d_final_values, d_last_values, g, gl, d_advantages, d_returns,
+                           (const float2 *)nullptr, 0);
     RF_HIP(hipGetLastError());
     return RF_OK;
+}
+
+int rf_rollout_advantages(rf_ctx *ctx, int T, int n, const double *d_rewards, const float *d_values,
+                          const uint8_t *d_truncated, const float *d_final_values, const float *d_last_values, double gamma,
+                          double gae_lambda, float *d_advantages, float *d_returns, void *caller_stream)
+{
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", "rf_rollout_advantages");
+    RF_HIP(hipSetDevice(ctx->device));
+    return rollout_advantages(ctx, T, n, 0, d_rewards, d_values, d_truncated, d_final_values, d_last_values, gamma,
+                              gae_lambda, nullptr, d_advantages, d_returns, caller_stream, "rf_rollout_advantages");
+}
+
+int rf_rollout_advantages_grouped(rf_ctx *ctx, int T, int n, int groups, const double *d_rewards, const float *d_values,
+                                  const uint8_t *d_truncated, const float *d_final_values, const float *d_last_values,
+                                  const float *d_discounts, float *d_advantages, float *d_returns, void *caller_stream)
+{
+    const char *fn = "rf_rollout_advantages_grouped";
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", fn);
+    RF_HIP(hipSetDevice(ctx->device));
+    RF_REQUIRE(groups >= 1 && groups <= RF_POPULATION_MAX_GROUPS, "%s: groups %d outside 1 to %d", fn, groups,
+               RF_POPULATION_MAX_GROUPS);
+    return rollout_advantages(ctx, T, n, groups, d_rewards, d_values, d_truncated, d_final_values, d_last_values, 0.0, 0.0,
+                              d_discounts, d_advantages, d_returns, caller_stream, fn);
 }
 
 unsigned long long rf_policy_params_size(rf_ctx *ctx, const rf_policy_desc *desc)

@@ -80,7 +80,8 @@ struct Layout {
         if (ctx->env_view) { // (the learner view's state; its rewards and view_final are last-step outputs)
             add(ctx->view_stack, n * (size_t)ctx->env_obs_width * (size_t)ctx->view_cfg.frame_stack * 4);
             add(ctx->view_returns, n * 8);
-            add(ctx->view_moments, sizeof(rf::EnvViewMoments));
+            // (a grouped view: float64 [G][3][17], one set of moments per group)
+            add(ctx->view_moments, (ctx->view_groups ? (size_t)ctx->view_groups : 1) * sizeof(rf::EnvViewMoments));
         }
         add(ctx->d_states, (size_t)ctx->n_states * sizeof(ulonglong2));
     }
@@ -95,7 +96,20 @@ uint64_t view_hash(const rf_ctx *ctx)
     const int32_t words[3] = {v.frame_stack, v.norm_obs, v.norm_reward};
     const double reals[4] = {v.gamma, v.epsilon, v.clip_obs, v.clip_reward};
     const uint64_t h = fnv1a(fnv1a(kFnvBasis, words, sizeof(words)), reals, sizeof(reals));
-    return h ? h : 1;
+    const uint64_t ungrouped = h ? h : 1;
+    if (ctx->view_groups == 0)
+        return ungrouped;
+    // A grouped view (rf_env_configure_view_grouped): the same words, then G and the groups' gammas -- what cfg->gamma
+    // was does not count, every group has its own.  Never 0 and never what this configuration hashes to ungrouped; the
+    // header's view_groups word (0 ungrouped) tells the two kinds apart whatever the hashes are.
+    const double grouped_reals[3] = {v.epsilon, v.clip_obs, v.clip_reward};
+    const int32_t groups = ctx->view_groups;
+    uint64_t x = fnv1a(fnv1a(kFnvBasis, words, sizeof(words)), grouped_reals, sizeof(grouped_reals));
+    x = fnv1a(fnv1a(x, "groups", 6), &groups, sizeof(groups));
+    x = fnv1a(x, ctx->view_gammas.data(), ctx->view_gammas.size() * sizeof(double));
+    while (x == 0 || x == ungrouped)
+        ++x;
+    return x;
 }
 
 // The header a snapshot of the context taken now would have.
@@ -132,6 +146,7 @@ rf_env_snapshot_header make_header(const rf_ctx *ctx, size_t total)
     h.last_partial = ctx->env_last_partial ? 1 : 0;
     h.view_hash = view_hash(ctx);
     h.view_training = ctx->env_view && ctx->view_training ? 1 : 0;
+    h.view_groups = ctx->env_view ? ctx->view_groups : 0;
     return h;
 }
 
@@ -163,6 +178,9 @@ int check_header(const rf_env_snapshot_header &got, const rf_env_snapshot_header
     RF_REQUIRE(got.view_hash == want.view_hash, "%s: the snapshot was taken %s, the context has %s", fn,
                got.view_hash ? "under another learner view configuration" : "without a learner view",
                want.view_hash ? "one" : "none");
+    RF_REQUIRE(got.view_groups == want.view_groups, "%s: the snapshot was taken under %s learner view (%d groups), the "
+               "context has %s (%d)", fn, got.view_groups ? "a grouped" : "an ungrouped", got.view_groups,
+               want.view_groups ? "a grouped one" : "an ungrouped one", want.view_groups);
     RF_REQUIRE(got.view_training == 0 || got.view_training == 1, "%s: the snapshot's view_training word is %d", fn,
                got.view_training);
     RF_REQUIRE(got.total_bytes == want.total_bytes, "%s: the snapshot says %llu bytes, not %llu", fn,

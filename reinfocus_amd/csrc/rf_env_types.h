@@ -122,4 +122,13 @@ struct EnvViewConfig {
     double gamma, epsilon, clip_obs, clip_reward;
 };
 
+// The groups of a grouped view (rf_env_configure_view_grouped; "population view"): group g owns lanes [g m, (g + 1) m)
+// and moments[g]; its returns are discounted by gamma[g].  Read by the kGrouped instantiations of the view's kernels
+// only; all zero without groups.
+struct EnvViewGroups {
+    int groups, m;       // m = n / groups
+    int log2_pm;         // P_m = 1 << log2_pm, the next power of two >= m
+    const double *gamma; // [groups], device memory
+};
+
 } // namespace rf

@@ -89,19 +89,33 @@ __device__ __forceinline__ void view_update(EnvViewMoments *m, int slot, double 
 // while training.  Two passes, mean and then squared deviations, each a treesum: thread t owns the aligned run of
 // `leaves` = max(P / 1024, 1) leaves that starts at t * leaves (P the next power of two >= n), reads past n are +0.0.
 // Thread 0 then applies the update.  Holds for any n: the run of leaves per thread grows, the block does not.
+//
+// kGrouped ("population view", groups of more than 64 lanes): blockIdx.y is the group, the block's batch is that
+// group's m lanes [g m, (g + 1) m) -- P is P_m, N is m --, the returns are discounted by gamma[g], and the update goes
+// to moments[g].  A template parameter, not a run-time flag: the ungrouped instantiation is the kernel of before,
+// instruction for instruction.
+template <bool kGrouped>
 __global__ __launch_bounds__(kViewBlock) void env_view_moments_kernel(EnvViewConfig c, int obs_blocks, int leaves,
                                                                       const float *obs, const double *reward,
-                                                                      double *returns, EnvViewMoments *moments)
+                                                                      double *returns, EnvViewMoments *moments,
+                                                                      EnvViewGroups grp)
 {
     __shared__ double wave_sums[16];
     const bool is_returns = (int)blockIdx.x >= obs_blocks;
     const int column = blockIdx.x; // (of an observation block)
     const long long first = (long long)threadIdx.x * leaves;
-    const long long n = c.n;
+    const long long n = kGrouped ? grp.m : c.n;
     const size_t width = (size_t)c.width;
+    if (kGrouped) { // this group's lanes and moments
+        const size_t base = (size_t)blockIdx.y * (size_t)grp.m;
+        obs += base * width;
+        reward += base;
+        returns += base;
+        moments += blockIdx.y;
+    }
     double s;
     if (is_returns) {
-        const double gamma = c.gamma;
+        const double gamma = kGrouped ? grp.gamma[blockIdx.y] : c.gamma;
         s = view_thread_tree(leaves, [&](int i) {
             const long long g = first + i;
             if (g >= n)
@@ -116,7 +130,7 @@ __global__ __launch_bounds__(kViewBlock) void env_view_moments_kernel(EnvViewCon
             return g < n ? (double)obs[(size_t)g * width + column] : 0.0;
         });
     }
-    const double N = (double)c.n;
+    const double N = (double)(kGrouped ? grp.m : c.n);
     const double bm = view_block_treesum(s, wave_sums) / N;
     if (is_returns) {
         s = view_thread_tree(leaves, [&](int i) {
@@ -140,6 +154,54 @@ __global__ __launch_bounds__(kViewBlock) void env_view_moments_kernel(EnvViewCon
         view_update(moments, is_returns ? c.width : column, bm, bv, N);
 }
 
+constexpr int kViewPackedBlock = 256; // threads of env_view_moments_packed_kernel's block: 4 waves
+constexpr int kViewPackedMax = 64; // the widest segment: one wave
+
+// The same two passes for groups of at most 64 lanes (P_m <= 64; the reference's m is 8), where the kernel above would
+// spend a 1024-thread block and four barriers on m values once per (slot, group).  Lanes are packed: the aligned
+// segment of P_m consecutive threads number s = (blockIdx.x * 256 + threadIdx.x) / P_m is group s, the lane with index
+// l inside it holds leaf l of that group -- +0.0 where l >= m or the group does not exist --, and blockIdx.y is the
+// slot as blockIdx.x is above.  P_m divides 64, so a segment never crosses a wave: the tree is the xor-butterfly over
+// offsets 1 .. P_m / 2 (after step s every lane holds the sub-tree of its aligned run of 2^s lanes; both partners
+// compute the same bits), then + 0.0.  No LDS, no barrier; every lane of a wave reaches every butterfly step, idle
+// lanes touch no memory.  m = 1 is the segment of one lane without a butterfly step.  Lane 0 of a segment applies the
+// update to moments[g].
+__global__ __launch_bounds__(kViewPackedBlock) void env_view_moments_packed_kernel(EnvViewConfig c, int obs_blocks,
+                                                                                   const float *obs, const double *reward,
+                                                                                   double *returns,
+                                                                                   EnvViewMoments *moments,
+                                                                                   EnvViewGroups grp)
+{
+    const bool is_returns = (int)blockIdx.y >= obs_blocks;
+    const int column = blockIdx.y; // (of an observation block)
+    const int thread = blockIdx.x * kViewPackedBlock + threadIdx.x; // < groups * P_m + 256 <= 2^22 + 256
+    const int pm = 1 << grp.log2_pm;
+    const int g = thread >> grp.log2_pm, leaf = thread & (pm - 1);
+    const bool live = g < grp.groups && leaf < grp.m;
+    const size_t e = live ? (size_t)g * (size_t)grp.m + (size_t)leaf : 0; // (dereferenced only where live)
+    double x = 0.0;
+    if (live) {
+        if (is_returns) {
+            x = returns[e] * grp.gamma[g] + reward[e];
+            returns[e] = x;
+        } else {
+            x = (double)obs[e * (size_t)c.width + column];
+        }
+    }
+    const double N = (double)grp.m;
+    double s = x;
+    for (int off = 1; off < pm; off <<= 1)
+        s += __shfl_xor(s, off, 64);
+    const double bm = (s + 0.0) / N;
+    const double d = x - bm;
+    s = live ? d * d : 0.0;
+    for (int off = 1; off < pm; off <<= 1)
+        s += __shfl_xor(s, off, 64);
+    const double bv = (s + 0.0) / N;
+    if (live && leaf == 0)
+        view_update(moments + g, is_returns ? c.width : column, bm, bv, N);
+}
+
 __device__ __forceinline__ double view_clip(double z, double limit)
 {
     return z < -limit ? -limit : (z > limit ? limit : z); // (a NaN passes through, as numpy.clip lets it)
@@ -159,16 +221,20 @@ __device__ __forceinline__ float view_normalise(const EnvViewConfig &c, const En
 // of e's stack row, so the shift is in place without a hazard.  `stack` is the view observation; view_reward and
 // view_final ([n][V], null without episode records: raw_final is then null too) are the step's other outputs.  The
 // caller's arrays out_obs / out_reward / out_final (rf_env_step_device_view; each may be null) get the same values in
-// the same launch.
+// the same launch.  kGrouped ("population view"): environment e is normalised by the moments of its group,
+// moments[e / m]; nothing else differs, and the ungrouped instantiation is the kernel of before.
+template <bool kGrouped>
 __global__ void env_view_apply_kernel(EnvViewConfig c, int reset, const float *obs, const double *reward,
                                       const uint8_t *truncated, const float *raw_final, const EnvViewMoments *moments,
                                       float *stack, double *returns, double *view_reward, float *view_final,
-                                      float *out_obs, double *out_reward, float *out_final)
+                                      float *out_obs, double *out_reward, float *out_final, EnvViewGroups grp)
 {
     const int cell = blockIdx.x * blockDim.x + threadIdx.x;
     if (cell >= c.n * c.width)
         return;
     const int e = cell / c.width, column = cell - e * c.width;
+    if (kGrouped)
+        moments += e / grp.m;
     const bool ended = !reset && truncated[e];
     const bool fresh = reset || ended; // the stack starts over
     const size_t row = (size_t)e * c.frame_stack * c.width;

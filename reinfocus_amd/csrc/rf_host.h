@@ -131,6 +131,12 @@ struct rf_ctx {
     rf::EnvViewMoments *view_moments = nullptr;
     rf::EnvViewMoments view_moments_host{}; // what an upload reads (outlives the asynchronous copy)
     size_t view_out_bytes = 0;      // bytes of the piece rf_env_get_view copies
+    // rf_env_configure_view_grouped ("population view"): view_moments is then EnvViewMoments[view_groups], followed in
+    // view_block by the groups' gammas float64[view_groups].  0: the ungrouped view.
+    int view_groups = 0;
+    rf::EnvViewGroups view_grp{};   // what the kGrouped kernels take by value (all zero without groups)
+    std::vector<double> view_gammas;                     // as configured (part of the fingerprint's hash)
+    std::vector<rf::EnvViewMoments> view_moments_groups; // what a grouped upload reads
     uint8_t *h_view = nullptr;
     size_t h_view_bytes = 0;
     // rf_env_snapshot_resident's slots: a device copy laid out as the host blob is (d == null: empty), the header that

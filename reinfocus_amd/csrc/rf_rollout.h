@@ -27,10 +27,16 @@ constexpr int kRolloutTile = 64; // environments of one block: one lane each
 constexpr int kRolloutChunk = 32; // steps of one LDS chunk (3 arrays x 32 x 64 x 4 B = 24 KiB per block)
 constexpr int kRolloutThreads = 256;
 
+// kGrouped ("population view": rf_rollout_advantages_grouped): the n environments are groups of m consecutive ones
+// with discounts of their own, discounts[e / m] = (g, gl) -- a tile of 64 lanes may span groups, and only these two
+// coefficients differ per lane; the arguments g and gl are not read.  A template parameter, not a run-time flag: the
+// ungrouped instantiation is the kernel of before, instruction for instruction.
+template <bool kGrouped>
 __global__ __launch_bounds__(kRolloutThreads) void rollout_gae_kernel(
     int T, int n, const double *__restrict__ rewards, const float *__restrict__ values,
     const uint8_t *__restrict__ truncated, const float *__restrict__ final_values /* or null */,
-    const float *__restrict__ last_values, float g, float gl, float *__restrict__ advantages, float *__restrict__ returns)
+    const float *__restrict__ last_values, float g, float gl, float *__restrict__ advantages, float *__restrict__ returns,
+    const float2 *__restrict__ discounts /* [n / m], kGrouped only */, int m)
 {
     __shared__ float s_delta[kRolloutChunk][kRolloutTile];
     __shared__ float s_coef[kRolloutChunk][kRolloutTile];
@@ -38,6 +44,11 @@ __global__ __launch_bounds__(kRolloutThreads) void rollout_gae_kernel(
     const int lane = threadIdx.x % kRolloutTile, wave = threadIdx.x / kRolloutTile;
     const int e = blockIdx.x * kRolloutTile + lane;
     const bool live = e < n; // (the ragged last tile: its idle lanes touch no memory, and reach every barrier)
+    if (kGrouped && live) { // this lane's coefficients
+        const float2 mine = discounts[e / m];
+        g = mine.x;
+        gl = mine.y;
+    }
     float last = 0.0f;
     for (int hi = T; hi > 0; hi -= kRolloutChunk) { // the chunk holds steps lo .. hi-1
         const int lo = hi > kRolloutChunk ? hi - kRolloutChunk : 0;

@@ -110,12 +110,37 @@ class LearnerView:
     and with episode_records=True "final_observation" is put through the same two transforms ("raw_final_observation"
     is the raw row).  The definition is include/reinfocus_hip.h's ("learner view"); defaults are SB3's.  One deliberate
     difference: the batch moments are taken in float64 by a fixed pairwise tree (treesum), not by numpy.mean / numpy.var
-    in float32."""
+    in float32.
+
+    groups=G (opt-in; include/reinfocus_hip.h, "population view"): the n lanes are G groups of m = n / G consecutive
+    lanes, as the population (environments/population.py) owns them, and every group has running moments of its own --
+    taken over its own m lanes -- and a gamma of its own (gamma: a scalar for all groups, or G values): G independent
+    VecNormalize wrappers in one environment.  This gamma is VecNormalize's, the discount of the returns whose variance
+    scales the reward; the rollout's gamma (rollout.Rollout / DeviceRollout) is passed separately -- rl_zoo3 sets both
+    from the trial's gamma."""
 
     def __init__(self, frame_stack=1, norm_obs=True, norm_reward=True, gamma=0.99, epsilon=1e-8, clip_obs=10.0,
-                 clip_reward=10.0, training=True):
+                 clip_reward=10.0, training=True, groups=None):
         self.frame_stack = int(frame_stack)
         self.norm_obs, self.norm_reward, self.training = bool(norm_obs), bool(norm_reward), bool(training)
+        self.groups, self.gammas = None, None
+        if groups is None:
+            if np.ndim(gamma) != 0:
+                raise ValueError(f"gamma {gamma!r} is a sequence, and that needs groups= (one gamma per group)")
+        else:
+            self.groups = int(groups)
+            if self.groups != groups or not 1 <= self.groups <= MAX_VIEW_GROUPS:
+                raise ValueError(f"groups {groups!r} is not in 1 .. {MAX_VIEW_GROUPS}")
+            values = np.asarray(gamma, dtype=np.float64)
+            if values.ndim == 0:
+                values = np.full(self.groups, float(values), dtype=np.float64)
+            if values.shape != (self.groups,):
+                raise ValueError(f"gamma has shape {values.shape}: a scalar or {self.groups} values, one per group")
+            self.gammas = tuple(float(value) for value in values)
+            for value in self.gammas:
+                if not 0.0 <= value <= 1.0:
+                    raise ValueError(f"gamma {value!r} outside [0, 1]")
+            gamma = self.gammas[0]
         self.gamma, self.epsilon = float(gamma), float(epsilon)
         self.clip_obs, self.clip_reward = float(clip_obs), float(clip_reward)
         if not 1 <= self.frame_stack <= 8:
@@ -128,9 +153,25 @@ class LearnerView:
 
     def describe(self):
         """The configuration without `training` (which may change later), as snapshots compare it."""
+        if self.groups is not None:
+            return (f"LearnerView(frame_stack={self.frame_stack}, norm_obs={self.norm_obs}, "
+                    f"norm_reward={self.norm_reward}, groups={self.groups}, gamma={self.gammas!r}, "
+                    f"epsilon={self.epsilon!r}, clip_obs={self.clip_obs!r}, clip_reward={self.clip_reward!r})")
         return (f"LearnerView(frame_stack={self.frame_stack}, norm_obs={self.norm_obs}, norm_reward={self.norm_reward}, "
                 f"gamma={self.gamma!r}, epsilon={self.epsilon!r}, clip_obs={self.clip_obs!r}, "
                 f"clip_reward={self.clip_reward!r})")
+
+    def group(self, index):
+        """The ungrouped LearnerView of group `index`: what a stand-alone trial over that group's lanes would have."""
+        return LearnerView(self.frame_stack, self.norm_obs, self.norm_reward, self.gammas[index], self.epsilon,
+                           self.clip_obs, self.clip_reward, self.training)
+
+    def group_size(self, num_envs, who):
+        """m = num_envs / groups of a grouped view; a num_envs the groups do not divide is refused."""
+        if num_envs % self.groups != 0:
+            raise ValueError(f"{who} has {num_envs} environments, which the learner view's {self.groups} groups do not "
+                             "divide (group g owns lanes [g m, (g + 1) m))")
+        return num_envs // self.groups
 
     def spaces(self, single_observation_space, num_envs):
         """(single_observation_space, observation_space) of the view: the bounds are +-clip_obs with norm_obs, else the
@@ -141,6 +182,9 @@ class LearnerView:
         single = spaces.Box(np.tile(low, self.frame_stack).astype(np.float32),
                             np.tile(high, self.frame_stack).astype(np.float32), dtype=np.float32)
         return single, spaces.batch_space(single, num_envs)
+
+
+MAX_VIEW_GROUPS = 65535  # RF_POPULATION_MAX_GROUPS
 
 
 def _checked_view(learner_view):
@@ -249,16 +293,91 @@ class _LearnerView:
             setattr(self, name, value)
 
 
+class _GroupedLearnerView:
+    """The learner view with groups=G (include/reinfocus_hip.h, "population view"), literally: G _LearnerView objects,
+    group g's over lanes [g m, (g + 1) m) with gamma[g], results concatenated -- as PopulationPolicy is G Policy
+    objects.  The oracle of the grouped kernels (csrc/rf_env_view.h)."""
+
+    def __init__(self, config, num_envs, width):
+        self.config = config
+        self._m = config.group_size(num_envs, "the environment")
+        self._n, self._width, self._cells = num_envs, width, config.frame_stack * width
+        self.views = [_LearnerView(config.group(g), self._m, width) for g in range(config.groups)]
+
+    def _lanes(self, g):
+        return slice(g * self._m, (g + 1) * self._m)
+
+    @property
+    def training(self):
+        return self.views[0].training
+
+    @training.setter
+    def training(self, value):
+        for view in self.views:
+            view.training = value
+
+    @property
+    def stack(self):
+        return np.concatenate([view.stack for view in self.views])
+
+    @property
+    def returns(self):
+        return np.concatenate([view.returns for view in self.views])
+
+    def reset(self, observations):
+        return np.concatenate([view.reset(observations[self._lanes(g)]) for g, view in enumerate(self.views)])
+
+    def step(self, observations, rewards, done, final_observation=None):
+        rewards = np.asarray(rewards, dtype=np.float64)
+        parts = [view.step(observations[self._lanes(g)], rewards[self._lanes(g)], done[self._lanes(g)],
+                           None if final_observation is None else final_observation[self._lanes(g)])
+                 for g, view in enumerate(self.views)]
+        view_obs, view_rewards, view_final = (list(column) for column in zip(*parts))
+        return (np.concatenate(view_obs), np.concatenate(view_rewards),
+                None if final_observation is None else np.concatenate(view_final))
+
+    def statistics(self, group=None):
+        """float64 [G, W + 1] each; with group=g that group's (W + 1,) rows."""
+        if group is not None:
+            return self.views[_checked_group(group, len(self.views))].statistics()
+        rows = [view.statistics() for view in self.views]
+        return {key: np.stack([row[key] for row in rows]) for key in ("mean", "var", "count")}
+
+    def set_statistics(self, mean, var, count, group=None):
+        if group is not None:
+            self.views[_checked_group(group, len(self.views))].set_statistics(mean, var, count)
+            return
+        arrays = [np.array(value, dtype=np.float64) for value in (mean, var, count)]
+        for value in arrays:
+            assert value.shape == (len(self.views), self._width + 1), (
+                f"statistics of shape {value.shape}, not ({len(self.views)}, {self._width + 1})")
+        for g, view in enumerate(self.views):
+            view.set_statistics(*(value[g] for value in arrays))
+
+
+def _checked_group(group, groups):
+    if groups is None:
+        raise ValueError("group= belongs to a learner view with groups=")
+    if int(group) != group or not 0 <= group < groups:
+        raise ValueError(f"group {group!r} is not in 0 .. {groups - 1}")
+    return int(group)
+
+
 class _ViewedTwin:
     """What the host twins with learner_view= share: the view around reset() / step() results, and its accessors."""
 
-    _view = None  # (a _LearnerView with learner_view=)
+    _view = None  # (a _LearnerView, or with groups= a _GroupedLearnerView, with learner_view=)
 
     def _configure_view(self, learner_view):
         learner_view = _checked_view(learner_view)
         if learner_view is None:
             return
-        self._view = _LearnerView(learner_view, self.num_envs, self.single_observation_space.shape[0])
+        width = self.single_observation_space.shape[0]
+        if learner_view.groups is None:
+            self._view = _LearnerView(learner_view, self.num_envs, width)
+        else:
+            learner_view.group_size(self.num_envs, type(self).__name__)
+            self._view = _GroupedLearnerView(learner_view, self.num_envs, width)
         self.single_observation_space, self.observation_space = learner_view.spaces(self.single_observation_space,
                                                                                     self.num_envs)
 
@@ -284,12 +403,22 @@ class _ViewedTwin:
             raise ValueError(f"{type(self).__name__} was built without learner_view=")
         return self._view
 
-    def view_statistics(self):
-        """{"mean", "var", "count"}: float64[W + 1] each, the returns last (what VecNormalize.save keeps)."""
-        return self._the_view().statistics()
+    def view_statistics(self, group=None):
+        """{"mean", "var", "count"}: float64[W + 1] each, the returns last (what VecNormalize.save keeps).  With a
+        grouped view float64[G, W + 1] each, or with group=g that group's (W + 1,) rows: that trial's VecNormalize."""
+        view = self._the_view()
+        if group is None:
+            return view.statistics()
+        _checked_group(group, view.config.groups)
+        return view.statistics(group)
 
-    def set_view_statistics(self, statistics):
-        self._the_view().set_statistics(statistics["mean"], statistics["var"], statistics["count"])
+    def set_view_statistics(self, statistics, group=None):
+        view = self._the_view()
+        if group is None:
+            view.set_statistics(statistics["mean"], statistics["var"], statistics["count"])
+            return
+        _checked_group(group, view.config.groups)
+        view.set_statistics(statistics["mean"], statistics["var"], statistics["count"], group)
 
     def set_view_training(self, training):
         """VecNormalize.training: False freezes the moments and the returns."""
@@ -993,9 +1122,13 @@ class _DeviceVectorEnv(_VectorEnvBase):
 
         view = self._learner_view
         try:
-            self._ctx.env_configure_view(_native.EnvViewConfig(view.frame_stack, view.norm_obs, view.norm_reward,
-                                                               view.training, view.gamma, view.epsilon, view.clip_obs,
-                                                               view.clip_reward))
+            config = _native.EnvViewConfig(view.frame_stack, view.norm_obs, view.norm_reward, view.training, view.gamma,
+                                           view.epsilon, view.clip_obs, view.clip_reward)
+            if view.groups is None:
+                self._ctx.env_configure_view(config)
+            else:  # (rf_env_configure_view_grouped: moments and a gamma per group of n / G lanes)
+                view.group_size(self.num_envs, type(self).__name__)
+                self._ctx.env_configure_view_grouped(config, view.groups, view.gammas)
         except Exception:
             self._ctx.close()
             raise
@@ -1006,15 +1139,32 @@ class _DeviceVectorEnv(_VectorEnvBase):
             raise ValueError(f"{type(self).__name__} was built without learner_view=")
         return self._learner_view
 
-    def view_statistics(self):
+    def view_statistics(self, group=None):
         """{"mean", "var", "count"}: float64[W + 1] each, the returns last, from the device (what VecNormalize.save
-        keeps).  Synchronises."""
-        self._the_view()
-        return dict(zip(("mean", "var", "count"), self._ctx.env_view_statistics()))
+        keeps).  With a grouped view float64[G, W + 1] each, or with group=g that group's (W + 1,) rows.
+        Synchronises."""
+        groups = self._the_view().groups
+        if group is not None:
+            group = _checked_group(group, groups)
+        if groups is None:
+            return dict(zip(("mean", "var", "count"), self._ctx.env_view_statistics()))
+        arrays = self._ctx.env_view_statistics_grouped()
+        return dict(zip(("mean", "var", "count"), arrays if group is None else (a[group].copy() for a in arrays)))
 
-    def set_view_statistics(self, statistics):
-        self._the_view()
-        self._ctx.env_view_set_statistics(statistics["mean"], statistics["var"], statistics["count"])
+    def set_view_statistics(self, statistics, group=None):
+        groups = self._the_view().groups
+        arrays = [statistics[key] for key in ("mean", "var", "count")]
+        if group is not None:  # (one group's rows: the others keep theirs)
+            group = _checked_group(group, groups)
+            rows = [np.array(a, dtype=np.float64) for a in arrays]
+            arrays = self._ctx.env_view_statistics_grouped()
+            for a, row in zip(arrays, rows):
+                assert row.shape == a[group].shape, f"statistics of shape {row.shape}, not {a[group].shape}"
+                a[group] = row
+        if groups is None:
+            self._ctx.env_view_set_statistics(*arrays)
+        else:
+            self._ctx.env_view_set_statistics_grouped(*arrays)
 
     def set_view_training(self, training):
         """VecNormalize.training: False freezes the moments and the returns."""

@@ -15,9 +15,16 @@ e T + t, so the rows of consecutive environments are contiguous).
                              kind, so Rollout.collect / DeviceRollout.collect take it as they take a Policy / DevicePolicy
     DevicePopulationLearner  update / train: three launches per minibatch whatever G is (rf_ppo_update_grouped)
 
-The Categorical head (MlpPolicySpec) only.  Out of scope: per-group gamma / gae_lambda (the rollout's GAE keeps its
-scalars), per-group LearnerView statistics (with learner_view= the running moments are taken over all lanes: groups share
-one normaliser), the sde, lstm and lstm-sde heads, groups that differ in architecture, m, T or batch size.
+A normaliser and GAE discounts per group (include/reinfocus_hip.h, "population view"): an environment built with
+learner_view=harness.LearnerView(..., gamma=scalar | G values, groups=G) keeps running moments per group, taken over the
+group's own lanes, and rollout.Rollout / DeviceRollout(env, n_steps, gamma, gae_lambda, groups=G) take a gamma and a
+gae_lambda per group -- what a stand-alone trial over m environments normalises and discounts by.  VecNormalize's gamma
+(the view's) and the rollout's gamma are passed separately; rl_zoo3 sets both from the trial's gamma.
+
+The Categorical head (MlpPolicySpec) only.  Out of scope: the sde, lstm and lstm-sde heads; groups that differ in
+architecture, m, T or batch size; SB3Wrapper; and the environment's shared reset-state generator -- lanes that end are
+ranked across all groups, so which reset state a lane draws depends on other groups' episode ends: the independence
+covers what the learner is given the raw step, not the environment's draws.
 
 torch is imported lazily, by the device classes only (reinfocus_amd/torch_interop.py says why import order matters).
 """

@@ -64,6 +64,49 @@ def gae_numpy(rewards, values, truncated, final_values, last_values, gamma, gae_
     return advantages, returns
 
 
+def gae_numpy_grouped(rewards, values, truncated, final_values, last_values, gammas, gae_lambdas):
+    """gae_numpy with discounts per group (include/reinfocus_hip.h, "population view"): gammas and gae_lambdas hold G
+    values each, the n columns are G groups of m = n / G consecutive ones, and group g's columns are gae_numpy's of that
+    slice with gammas[g] and gae_lambdas[g] -- literally so."""
+    rewards = np.asarray(rewards, dtype=np.float64)
+    steps, num_envs = rewards.shape
+    gammas, gae_lambdas = _per_group(gammas, len(gammas), "gamma"), _per_group(gae_lambdas, len(gammas), "gae_lambda")
+    groups = len(gammas)
+    if num_envs % groups != 0:
+        raise ValueError(f"{groups} groups do not divide {num_envs} environments")
+    m = num_envs // groups
+    values = np.asarray(values, dtype=np.float32).reshape(steps, num_envs)
+    truncated = np.asarray(truncated, dtype=np.uint8).reshape(steps, num_envs)
+    last_values = np.asarray(last_values, dtype=np.float32).reshape(num_envs)
+    if final_values is not None:
+        final_values = np.asarray(final_values, dtype=np.float32).reshape(steps, num_envs)
+    advantages = np.empty((steps, num_envs), dtype=np.float32)
+    returns = np.empty((steps, num_envs), dtype=np.float32)
+    for g in range(groups):
+        lanes = slice(g * m, (g + 1) * m)
+        advantages[:, lanes], returns[:, lanes] = gae_numpy(
+            rewards[:, lanes], values[:, lanes], truncated[:, lanes],
+            None if final_values is None else final_values[:, lanes], last_values[lanes], gammas[g], gae_lambdas[g])
+    return advantages, returns
+
+
+def _per_group(value, groups, name):
+    """`value` as a tuple of `groups` Python floats: a scalar for all groups, or one value per group."""
+    values = np.asarray(value, dtype=np.float64)
+    if values.ndim == 0:
+        values = np.full(groups, float(values))
+    if values.shape != (groups,):
+        raise ValueError(f"{name} has shape {values.shape}: a scalar or {groups} values, one per group")
+    return tuple(float(x) for x in values)
+
+
+def discount_table(gammas, gae_lambdas):
+    """float32 [G, 2]: (g, gl) per group as rf_rollout_advantages_grouped reads them -- g = float32(gamma),
+    gl = float32(gamma * gae_lambda) with the product taken in float64."""
+    return np.array([(np.float32(gamma), np.float32(gamma * gae_lambda)) for gamma, gae_lambda in zip(gammas, gae_lambdas)],
+                    dtype=np.float32).reshape(len(gammas), 2)
+
+
 def _index_task(env):
     return isinstance(env.single_action_space, spaces.Discrete)
 
@@ -72,13 +115,30 @@ class _Bookkeeping:
     """What both forms count on the host (plain Python integers: nothing is asked of the device): the step within the
     rollout, how many of its steps were bootstrapped, and whether a rollout is open."""
 
-    def _configure(self, env, n_steps, gamma, gae_lambda, records):
+    def _configure(self, env, n_steps, gamma, gae_lambda, records, groups=None):
         self.env = env
         self.n_steps = int(n_steps)
-        self.gamma, self.gae_lambda = float(gamma), float(gae_lambda)
+        self.groups = None if groups is None else int(groups)
+        self.num_envs = int(env.num_envs)
+        if self.groups is None:
+            if np.ndim(gamma) != 0 or np.ndim(gae_lambda) != 0:
+                raise ValueError("gamma and gae_lambda are scalars without groups= (one value per group needs groups=G)")
+            self.gamma, self.gae_lambda = float(gamma), float(gae_lambda)
+        else:
+            # gamma and gae_lambda: scalars or G values; plain attributes, read again by every finish()
+            if self.groups != groups or self.groups < 1:
+                raise ValueError(f"groups {groups!r} is not a positive integer")
+            if self.num_envs % self.groups != 0:
+                raise ValueError(f"{self.groups} groups do not divide the environment's {self.num_envs} lanes")
+            view = getattr(env, "_learner_view", None) or getattr(getattr(env, "_view", None), "config", None)
+            view_groups = getattr(view, "groups", None)
+            if view_groups is not None and view_groups != self.groups:
+                raise ValueError(f"the rollout has groups={self.groups}, and the environment's learner view has "
+                                 f"groups={view_groups}: group g owns the same lanes in both")
+            self.gamma, self.gae_lambda = gamma, gae_lambda
+            self._discounts()
         if self.n_steps < 1:
             raise ValueError(f"n_steps {n_steps!r} is not at least 1")
-        self.num_envs = int(env.num_envs)
         self.obs_width = int(env.single_observation_space.shape[0])
         self._records = bool(records)
         self._t = None  # (None: no rollout is open)
@@ -90,6 +150,10 @@ class _Bookkeeping:
         # uint8 [T + 1, n] and lstm_states float32 [T + 1, 2, 2, n, H] -- what sb3-contrib's RecurrentRolloutBuffer hands
         # to the update.  A rollout that never sees such a policy allocates neither.
         self.episode_starts = self.lstm_states = None
+
+    def _discounts(self):
+        """(gammas, gae_lambdas) of a grouped rollout as tuples of G floats, from the attributes as they are now."""
+        return (_per_group(self.gamma, self.groups, "gamma"), _per_group(self.gae_lambda, self.groups, "gae_lambda"))
 
     def _begin(self, obs):
         if obs is None and not self._complete:
@@ -143,6 +207,10 @@ class _Bookkeeping:
         if not sde and not _index_task(self.env):
             raise ValueError("collect() takes a policy with a Categorical head, and the environment's action space is "
                              f"{self.env.single_action_space!r}: continuous action spaces are out of scope")
+        policy_groups = getattr(policy, "groups", None)
+        if self.groups is not None and policy_groups is not None and int(policy_groups) != self.groups:
+            raise ValueError(f"collect() of a rollout with groups={self.groups} was given a population policy of "
+                             f"{policy_groups} groups")
         if int(sde_sample_freq) != sde_sample_freq or (sde_sample_freq < 1 and sde_sample_freq != -1):
             raise ValueError(f"sde_sample_freq {sde_sample_freq!r} is not -1 or a positive integer")
         if not sde and sde_sample_freq != -1:
@@ -174,9 +242,11 @@ class Rollout(_Bookkeeping):
         rollout.start()                                                 # row T becomes row 0
     """
 
-    def __init__(self, env, n_steps, gamma=0.99, gae_lambda=0.95):
+    def __init__(self, env, n_steps, gamma=0.99, gae_lambda=0.95, groups=None):
+        """groups=G: gamma and gae_lambda are scalars or G values, group g's for lanes [g m, (g + 1) m) (plain
+        attributes: they may be reassigned between rollouts)."""
         self._configure(env, n_steps, gamma, gae_lambda, getattr(env, "_records", None) is not None
-                        or bool(getattr(env, "_episode_records", False)))
+                        or bool(getattr(env, "_episode_records", False)), groups)
         steps, n = self.n_steps, self.num_envs
         self.observations = np.zeros((steps + 1, n, self.obs_width), dtype=np.float32)
         self.actions = np.zeros((steps, n), dtype=np.int64 if _index_task(env) else np.float32)
@@ -206,8 +276,12 @@ class Rollout(_Bookkeeping):
 
     def finish(self, last_values):
         final_values = self.final_values if self._finishing() else None
-        self.advantages, self.returns = gae_numpy(self.rewards, self.values, self.truncated, final_values, last_values,
-                                                  self.gamma, self.gae_lambda)
+        if self.groups is None:
+            self.advantages, self.returns = gae_numpy(self.rewards, self.values, self.truncated, final_values, last_values,
+                                                      self.gamma, self.gae_lambda)
+        else:
+            self.advantages, self.returns = gae_numpy_grouped(self.rewards, self.values, self.truncated, final_values,
+                                                              last_values, *self._discounts())
         return self.advantages, self.returns
 
     def collect(self, policy, deterministic=False, sde_sample_freq=-1):
@@ -294,7 +368,11 @@ class DeviceRollout(_Bookkeeping):
     copy and no launch is added for the step's outputs.  finish() is one launch of rollout_gae_kernel
     (rf_rollout_advantages) on torch's current stream.  No method synchronises the host."""
 
-    def __init__(self, env, n_steps, gamma=0.99, gae_lambda=0.95):
+    def __init__(self, env, n_steps, gamma=0.99, gae_lambda=0.95, groups=None):
+        """groups=G: as Rollout's; finish() is then one launch of rollout_gae_kernel<true>
+        (rf_rollout_advantages_grouped), which reads (g, gl) per group from a device table the rollout owns.  The
+        table is repacked -- one small copy on the current stream -- when gamma or gae_lambda have changed since the
+        last finish(), as the population learner repacks its hyper-parameter records."""
         from reinfocus_amd.environments import harness
 
         if not isinstance(env, harness._DeviceVectorEnv):
@@ -303,7 +381,7 @@ class DeviceRollout(_Bookkeeping):
             raise TypeError(f"DeviceRollout needs a device-resident environment, not {type(env).__name__} (the numpy "
                             "twins have Rollout)")
         io = env._tensor_io()  # (ValueError, as step_tensors': a host initializer, a render_mode)
-        self._configure(env, n_steps, gamma, gae_lambda, env._episode_records)
+        self._configure(env, n_steps, gamma, gae_lambda, env._episode_records, groups)
         from reinfocus_amd import torch_interop
 
         torch = self._torch = torch_interop._torch()
@@ -323,6 +401,18 @@ class DeviceRollout(_Bookkeeping):
             slab(torch.float32) for _ in range(5))
         self._last_values = None  # (collect()'s V(observations[T]), made on first use)
         self._env_actions = None  # (collect()'s clamped actions of an sde policy, made on first use)
+        self._table = self._table_of = None  # (a grouped rollout's (g, gl) float32 [G, 2] and what it was packed from)
+
+    def _discount_table(self):
+        """The device table of a grouped rollout, repacked when gamma or gae_lambda have changed."""
+        discounts = self._discounts()
+        if self._table_of != discounts:
+            packed = self._torch.from_numpy(discount_table(*discounts))
+            if self._table is None:
+                self._table = self._torch.zeros((self.groups, 2), dtype=self._torch.float32, device=self.device)
+            self._table.copy_(packed, non_blocking=True)
+            self._table_of = discounts
+        return self._table
 
     def _row(self, tensor, what):
         """`tensor` as a float32-or-whatever [n] row on the buffer's GPU (a view, never a host copy)."""
@@ -370,11 +460,19 @@ class DeviceRollout(_Bookkeeping):
         last_values = self._row(last_values, "last_values")
         if last_values.dtype != self._torch.float32 or not last_values.is_contiguous():
             last_values = last_values.to(self._torch.float32).contiguous()
+        table = None if self.groups is None else self._discount_table()  # (a refused value: before anything changes)
         bootstrapped = self._finishing()
-        self._ctx.rollout_advantages(self.n_steps, self.num_envs, self.rewards.data_ptr(), self.values.data_ptr(),
-                                     self.truncated.data_ptr(), self.final_values.data_ptr() if bootstrapped else None,
-                                     last_values.data_ptr(), self.gamma, self.gae_lambda, self.advantages.data_ptr(),
-                                     self.returns.data_ptr(), self._io._stream())
+        final_ptr = self.final_values.data_ptr() if bootstrapped else None
+        if table is None:
+            self._ctx.rollout_advantages(self.n_steps, self.num_envs, self.rewards.data_ptr(), self.values.data_ptr(),
+                                         self.truncated.data_ptr(), final_ptr, last_values.data_ptr(), self.gamma,
+                                         self.gae_lambda, self.advantages.data_ptr(), self.returns.data_ptr(),
+                                         self._io._stream())
+        else:
+            self._ctx.rollout_advantages_grouped(self.n_steps, self.num_envs, self.groups, self.rewards.data_ptr(),
+                                                 self.values.data_ptr(), self.truncated.data_ptr(), final_ptr,
+                                                 last_values.data_ptr(), table.data_ptr(), self.advantages.data_ptr(),
+                                                 self.returns.data_ptr(), self._io._stream())
         return self.advantages, self.returns
 
     def collect(self, policy, deterministic=False, sde_sample_freq=-1):
