@@ -1346,8 +1346,8 @@ int rf_lstm_critic_sde_update(rf_ctx *ctx, const rf_lstm_critic_desc *desc, cons
  *  G7 Stats and skips.  d_stats is float32 [G][8].  A group whose minibatch is invalid or whose gradient norm is not finite
  *     is skipped and flagged in its own stats[7] exactly as step 8 says; the other groups are untouched by it.
  * Limits: G 1 .. RF_POPULATION_MAX_GROUPS (the grid's y / z limit), m >= 1, G m <= 2^30 (G N alike), B as in G4.
- * A normaliser and GAE discounts per group: "population view", above.  Out of scope: the sde and lstm heads, groups that
- * differ in architecture, m, T or B.
+ * A normaliser and GAE discounts per group: "population view", above.  The Gaussian head: "population sde", below.  Out of
+ * scope: the lstm heads, groups that differ in architecture, m, T or B.
  *
  *   rf_policy_forward_grouped      rf_policy_forward over (G, m) in place of n: one launch, grid (ceil(m / 8), nets, G);
  *                                  the same outputs over G m rows, the same refusals (with d_gens, a device array, in
@@ -1376,6 +1376,54 @@ int rf_ppo_update_grouped(rf_ctx *ctx, const rf_policy_desc *policy, int G, int 
                           float *d_params, void *d_state, void *d_workspace, const float *d_obs, const long long *d_actions,
                           const float *d_old_log_probs, const float *d_advantages, const float *d_returns, int B,
                           const long long *d_index, float *d_stats, void *caller_stream);
+
+/* ---- population sde: a population of gSDE learners, each group with its own log_std and noise schedule -------------------
+ * The reference's hyper-parameter search draws a sde_sample_freq and a log_std_init per trial for ContinuousJumps-v0
+ * (use_sde).  Written as deltas of "population" and "sde policy": the arithmetic of a group is exactly that of "sde policy"
+ * and its update (steps 1', 3', 5', 6', 7'); only addressing changes.  numpy twins environments/population.py (G of
+ * sde.SdePolicy / learner.Learner over slices), kernels sde_noise_kernel<true>, sde_forward_kernel<true> (csrc/rf_sde.h),
+ * ppo_backward_kernel<true, true>, ppo_gradient_kernel<true>, ppo_adam_kernel<true> (csrc/rf_ppo.h).
+ *
+ *  S1 G1, G4, G5, G6 and G7 of "population" hold unchanged, with P + L parameters (rf_sde_params_size) in place of P:
+ *     d_params is float32 [G][P + L], group g's log_std its last L floats; d_actions of an update are the raw actions,
+ *     float32 [G N].
+ *  S2 Noise.  d_theta is float32 [G m][L]; d_gens is uint64 [G][4] as in G3, d_consumed uint64 [G], the draws each
+ *     generator has given, read on the device and never written.  theta[(g m + e) L + k] = the theta of "sde policy" from
+ *     draw number consumed[g] + e L + k (64-bit) of generator g and log_std_k of group g: what a stand-alone
+ *     rf_sde_noise_reset over the group's m rows gives whose generator was advanced by consumed[g] before.  d_select is
+ *     uint8 [G] or NULL: a group whose byte is 0 writes nothing, its rows of theta keep their bytes; NULL selects every
+ *     group.  The caller adds m L to consumed[g] of every selected group after the call.
+ *  S3 Forward.  Group g's rows are computed from params[g] (its own log_std in sigma) and its own rows of theta.
+ * Limits: G 1 .. RF_POPULATION_MAX_GROUPS, m 1 .. 2^20 (an update: m >= 1), G m <= 2^30 (G m T alike),
+ * 1 <= B <= min(m T, RF_PPO_MAX_BATCH), n_actions 1.  Out of scope: more than one action dimension.
+ *
+ *   rf_sde_noise_reset_grouped     rf_sde_noise_reset over (G, m) in place of n: one launch, grid (ceil(m L / 256), G); the
+ *                                  same refusals (with d_gens, a device array, in place of gen), d_consumed or d_select no
+ *                                  device array of G elements, d_theta overlapping an input, and G or m outside the limits.
+ *   rf_sde_forward_grouped         rf_sde_forward over (G, m) in place of n: one launch, grid (ceil(m / 8), nets, G); the
+ *                                  same outputs over G m rows, the same refusals, and G or m outside the limits.
+ *   rf_sde_grouped_state_size      G (32 + 8 (P + L)) bytes; 0 where rf_ppo_grouped_state_size is, over the sde limits
+ *   rf_sde_grouped_workspace_size  G rf_sde_workspace_size(policy, B) bytes; 0 where rf_ppo_grouped_workspace_size is
+ *   rf_sde_update_grouped          rf_sde_update over (G, m, T) in place of N, N = m T rows per group: three launches
+ *                                  whatever G is, the refusals of rf_ppo_update_grouped (a capturing caller stream among
+ *                                  them) with the sde limits of the desc.
+ * A refused call enqueues nothing and dereferences no device pointer.
+ * (The tag between return type and name marks the section a declaration belongs to: tests/test_sde_logic.py takes a census
+ * of the six entry points of "sde policy" by their plain declarations, and these five are not among them.) */
+int /* population sde */ rf_sde_noise_reset_grouped(rf_ctx *ctx, const rf_policy_desc *desc, int G, int m,
+        const float *d_params, const unsigned long long *d_gens /* [G][4] */, const unsigned long long *d_consumed /* [G] */,
+        const unsigned char *d_select /* [G] or NULL */, float *d_theta /* [G m][L] */, void *caller_stream);
+int /* population sde */ rf_sde_forward_grouped(rf_ctx *ctx, const rf_policy_desc *desc, int G, int m, const float *d_params,
+        const float *d_obs, const float *d_final_obs, const float *d_theta, int flags, float *d_actions,
+        float *d_env_actions, float *d_log_probs, float *d_values, float *d_final_values, float *d_mean, float *d_sigma,
+        void *caller_stream);
+unsigned long long /* population sde */ rf_sde_grouped_state_size(rf_ctx *ctx, const rf_policy_desc *policy, int G, int m);
+unsigned long long /* population sde */ rf_sde_grouped_workspace_size(rf_ctx *ctx, const rf_policy_desc *policy, int G, int m,
+        int T, int B);
+int /* population sde */ rf_sde_update_grouped(rf_ctx *ctx, const rf_policy_desc *policy, int G, int m, int T,
+        const rf_ppo_hyper *d_hyper, float *d_params, void *d_state, void *d_workspace, const float *d_obs,
+        const float *d_actions, const float *d_old_log_probs, const float *d_advantages, const float *d_returns, int B,
+        const long long *d_index, float *d_stats, void *caller_stream);
 
 #ifdef __cplusplus
 }

@@ -115,6 +115,11 @@ SYMBOLS = (
     "rf_sde_state_size",
     "rf_sde_workspace_size",
     "rf_sde_update",
+    "rf_sde_noise_reset_grouped",
+    "rf_sde_forward_grouped",
+    "rf_sde_grouped_state_size",
+    "rf_sde_grouped_workspace_size",
+    "rf_sde_update_grouped",
     "rf_lstm_params_size",
     "rf_lstm_state_size",
     "rf_lstm_forward",
@@ -424,6 +429,13 @@ def load():
     lib.rf_sde_workspace_size.restype = ctypes.c_ulonglong
     lib.rf_sde_workspace_size.argtypes = [vp, vp, i32]
     lib.rf_sde_update.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp]
+    lib.rf_sde_noise_reset_grouped.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    lib.rf_sde_forward_grouped.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.rf_sde_grouped_state_size.restype = ctypes.c_ulonglong
+    lib.rf_sde_grouped_state_size.argtypes = [vp, vp, i32, i32]
+    lib.rf_sde_grouped_workspace_size.restype = ctypes.c_ulonglong
+    lib.rf_sde_grouped_workspace_size.argtypes = [vp, vp, i32, i32, i32, i32]
+    lib.rf_sde_update_grouped.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]
     lib.rf_lstm_params_size.restype = ctypes.c_ulonglong
     lib.rf_lstm_params_size.argtypes = [vp, vp]
     lib.rf_lstm_state_size.restype = ctypes.c_ulonglong
@@ -866,6 +878,46 @@ class Context:
         the groups' pieces back to back (per_group x steps rows each), hyper_ptr: the device array of rf_ppo_hyper,
         index_ptr: int64 [groups][batch] of rows local to each group.  Only enqueues."""
         rc = self._lib.rf_ppo_update_grouped(self._h, ctypes.byref(PolicyDesc(*desc)), groups, per_group, steps, hyper_ptr,
+                                             params_ptr, state_ptr, workspace_ptr, obs_ptr, actions_ptr, old_log_probs_ptr,
+                                             advantages_ptr, returns_ptr, batch, index_ptr, stats_ptr, stream)
+        if rc != 0:
+            _check(rc)
+
+    # --- population sde (rf_sde_*_grouped): the sde policy below over G groups of m environments, one launch per stage ---
+    def sde_noise_reset_grouped(self, desc, groups, per_group, params_ptr, gens_ptr, consumed_ptr, select_ptr, theta_ptr,
+                                stream):
+        """rf_sde_noise_reset_grouped: theta float32 [groups x per_group][L], group g's rows from generator g of the device
+        table gens_ptr (uint64 [groups][4]) advanced by consumed_ptr[g] (device uint64 [groups]) and from the log_std of
+        params[g]; select_ptr: device uint8 [groups] (0: the group keeps its rows) or None for every group.  Only
+        enqueues."""
+        rc = self._lib.rf_sde_noise_reset_grouped(self._h, ctypes.byref(PolicyDesc(*desc)), groups, per_group, params_ptr,
+                                                  gens_ptr, consumed_ptr, select_ptr, theta_ptr, stream)
+        if rc != 0:
+            _check(rc)
+
+    def sde_forward_grouped(self, desc, groups, per_group, params_ptr, obs_ptr, final_obs_ptr, theta_ptr, flags, actions_ptr,
+                            env_actions_ptr, log_probs_ptr, values_ptr, final_values_ptr, mean_ptr, sigma_ptr, stream):
+        """rf_sde_forward_grouped: sde_forward over groups x per_group rows, parameters [groups][P + L].  Only enqueues."""
+        rc = self._lib.rf_sde_forward_grouped(self._h, ctypes.byref(PolicyDesc(*desc)), groups, per_group, params_ptr, obs_ptr,
+                                              final_obs_ptr, theta_ptr, flags, actions_ptr, env_actions_ptr, log_probs_ptr,
+                                              values_ptr, final_values_ptr, mean_ptr, sigma_ptr, stream)
+        if rc != 0:
+            _check(rc)
+
+    def sde_grouped_state_size(self, desc, groups, per_group):
+        """rf_sde_grouped_state_size: bytes of the optimizer states of `groups` sde networks `desc`; 0 if refused."""
+        return int(self._lib.rf_sde_grouped_state_size(self._h, ctypes.byref(PolicyDesc(*desc)), groups, per_group))
+
+    def sde_grouped_workspace_size(self, desc, groups, per_group, steps, batch):
+        """rf_sde_grouped_workspace_size: as ppo_grouped_workspace_size, over the sde layout; 0 if refused."""
+        return int(self._lib.rf_sde_grouped_workspace_size(self._h, ctypes.byref(PolicyDesc(*desc)), groups, per_group,
+                                                           steps, batch))
+
+    def sde_update_grouped(self, desc, groups, per_group, steps, hyper_ptr, params_ptr, state_ptr, workspace_ptr, obs_ptr,
+                           actions_ptr, old_log_probs_ptr, advantages_ptr, returns_ptr, batch, index_ptr, stats_ptr, stream):
+        """rf_sde_update_grouped: ppo_update_grouped with the Gaussian head (actions float32, the raw ones).  Only
+        enqueues."""
+        rc = self._lib.rf_sde_update_grouped(self._h, ctypes.byref(PolicyDesc(*desc)), groups, per_group, steps, hyper_ptr,
                                              params_ptr, state_ptr, workspace_ptr, obs_ptr, actions_ptr, old_log_probs_ptr,
                                              advantages_ptr, returns_ptr, batch, index_ptr, stats_ptr, stream)
         if rc != 0:

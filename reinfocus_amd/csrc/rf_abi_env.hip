@@ -2377,19 +2377,23 @@ unsigned long long rf_ppo_grouped_workspace_size(rf_ctx *ctx, const rf_policy_de
     return rf::population_workspace_bytes(*policy, G, m, T, B);
 }
 
-int rf_ppo_update_grouped(rf_ctx *ctx, const rf_policy_desc *policy, int G, int m, int T, const rf_ppo_hyper *d_hyper,
-                          float *d_params, void *d_state, void *d_workspace, const float *d_obs, const long long *d_actions,
-                          const float *d_old_log_probs, const float *d_advantages, const float *d_returns, int B,
-                          const long long *d_index, float *d_stats, void *caller_stream)
+// What rf_ppo_update_grouped and rf_sde_update_grouped do once they have checked ctx and made its device current: one body,
+// the head chosen by `sde` as in ppo_update_any
+static int ppo_update_grouped_any(const char *fn, bool sde, rf_ctx *ctx, const rf_policy_desc *policy, int G, int m, int T,
+                                  const rf_ppo_hyper *d_hyper, float *d_params, void *d_state, void *d_workspace,
+                                  const float *d_obs, const void *d_actions, const float *d_old_log_probs,
+                                  const float *d_advantages, const float *d_returns, int B, const long long *d_index,
+                                  float *d_stats, void *caller_stream)
 {
-    const char *fn = "rf_ppo_update_grouped";
-    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", fn);
-    RF_HIP(hipSetDevice(ctx->device));
     RF_REQUIRE(policy && d_hyper && d_params && d_state && d_workspace && d_obs && d_actions && d_old_log_probs
                && d_advantages && d_returns && d_index && d_stats, "%s: NULL argument", fn);
     rf::PolicyLayout layout;
-    RF_REQUIRE(rf::policy_layout(*policy, layout), RF_POLICY_LIMITS, fn, RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_WIDTH,
-               RF_POLICY_MAX_ACTIONS);
+    if (sde) {
+        RF_REQUIRE(rf::sde_layout(*policy, layout), RF_SDE_LIMITS, fn, RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_WIDTH);
+    } else {
+        RF_REQUIRE(rf::policy_layout(*policy, layout), RF_POLICY_LIMITS, fn, RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_WIDTH,
+                   RF_POLICY_MAX_ACTIONS);
+    }
     RF_REQUIRE(m >= 1 && T >= 1 && rf::population_rows(G, (long long)m * (long long)T),
                "%s: G = %d must be in 1 .. %d, m = %d and T = %d at least 1 and G m T at most 2^30", fn, G,
                RF_POPULATION_MAX_GROUPS, m, T);
@@ -2406,7 +2410,7 @@ int rf_ppo_update_grouped(rf_ctx *ctx, const rf_policy_desc *policy, int G, int 
         const char *what;
     };
     const Array inputs[] = {{d_obs, rows * (size_t)layout.obs_width * 4, 4, "d_obs"},
-                            {d_actions, rows * 8, 8, "d_actions"},
+                            {d_actions, rows * (sde ? 4 : 8), sde ? (size_t)4 : (size_t)8, "d_actions"},
                             {d_old_log_probs, rows * 4, 4, "d_old_log_probs"},
                             {d_advantages, rows * 4, 4, "d_advantages"},
                             {d_returns, rows * 4, 4, "d_returns"},
@@ -2436,9 +2440,9 @@ int rf_ppo_update_grouped(rf_ctx *ctx, const rf_policy_desc *policy, int G, int 
     float *ws = (float *)d_workspace;
     const rf::PpoHyper *hypers = (const rf::PpoHyper *)d_hyper;
     const unsigned tiles = (unsigned)((B + rf::kPolicyTile - 1) / rf::kPolicyTile);
-    const auto backward = rf::ppo_backward_kernel<false, true>;
+    const auto backward = sde ? rf::ppo_backward_kernel<true, true> : rf::ppo_backward_kernel<false, true>;
     hipLaunchKernelGGL(backward, dim3(tiles, 2u, (unsigned)G), dim3(rf::kPpoThreads), 0, caller, layout, work, rf::PpoHyper{},
-                       (const float *)d_params, (const rf::PpoHeader *)d_state, ws, N, d_obs, (const void *)d_actions,
+                       (const float *)d_params, (const rf::PpoHeader *)d_state, ws, N, d_obs, d_actions,
                        d_old_log_probs, d_advantages, d_returns, B, (const int64_t *)d_index, hypers);
     RF_HIP(hipGetLastError());
     hipLaunchKernelGGL(rf::ppo_gradient_kernel<true>, dim3(work.partials, (unsigned)G), dim3(rf::kPpoThreads), 0, caller,
@@ -2449,6 +2453,18 @@ int rf_ppo_update_grouped(rf_ctx *ctx, const rf_policy_desc *policy, int G, int 
                        layout.total, work, rf::PpoHyper{}, d_params, (float *)d_state, (const float *)ws, B, d_stats, hypers);
     RF_HIP(hipGetLastError());
     return RF_OK;
+}
+
+int rf_ppo_update_grouped(rf_ctx *ctx, const rf_policy_desc *policy, int G, int m, int T, const rf_ppo_hyper *d_hyper,
+                          float *d_params, void *d_state, void *d_workspace, const float *d_obs, const long long *d_actions,
+                          const float *d_old_log_probs, const float *d_advantages, const float *d_returns, int B,
+                          const long long *d_index, float *d_stats, void *caller_stream)
+{
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", "rf_ppo_update_grouped");
+    RF_HIP(hipSetDevice(ctx->device));
+    return ppo_update_grouped_any("rf_ppo_update_grouped", false, ctx, policy, G, m, T, d_hyper, d_params, d_state, d_workspace,
+                                  d_obs, d_actions, d_old_log_probs, d_advantages, d_returns, B, d_index, d_stats,
+                                  caller_stream);
 }
 
 int rf_sde_update(rf_ctx *ctx, const rf_policy_desc *policy, const rf_ppo_desc *ppo, float *d_params, void *d_state,
@@ -2513,8 +2529,9 @@ int rf_sde_noise_reset(rf_ctx *ctx, const rf_policy_desc *desc, const float *d_p
     for (int i = 0; i < 4; ++i)
         words.word[i] = gen[i];
     const unsigned blocks = (unsigned)((cells + rf::kPolicyThreads - 1) / rf::kPolicyThreads);
-    hipLaunchKernelGGL(rf::sde_noise_kernel, dim3(blocks), dim3(rf::kPolicyThreads), 0, (hipStream_t)caller_stream, words,
-                       d_params + layout.log_std, n, (int)layout.sde, d_theta);
+    hipLaunchKernelGGL(rf::sde_noise_kernel<false>, dim3(blocks), dim3(rf::kPolicyThreads), 0, (hipStream_t)caller_stream,
+                       words, d_params + layout.log_std, n, (int)layout.sde, d_theta, (const rf::PolicyGen *)nullptr,
+                       (const uint64_t *)nullptr, (const uint8_t *)nullptr, 0u);
     RF_HIP(hipGetLastError());
     return RF_OK;
 }
@@ -2571,11 +2588,148 @@ int rf_sde_forward(rf_ctx *ctx, const rf_policy_desc *desc, const float *d_param
                        a.what, b.what);
     }
     const unsigned tiles = (unsigned)((rows + rf::kPolicyTile - 1) / rf::kPolicyTile);
-    hipLaunchKernelGGL(rf::sde_forward_kernel, dim3(tiles, pi && vf ? 2u : 1u), dim3(rf::kPolicyThreads), 0,
+    hipLaunchKernelGGL(rf::sde_forward_kernel<false>, dim3(tiles, pi && vf ? 2u : 1u), dim3(rf::kPolicyThreads), 0,
                        (hipStream_t)caller_stream, layout, d_params, n, d_obs, d_final_obs, sampled ? d_theta : nullptr,
                        pi ? 0 : 1, d_actions, d_env_actions, d_log_probs, d_values, d_final_values, d_mean, d_sigma);
     RF_HIP(hipGetLastError());
     return RF_OK;
+}
+
+// ---- population sde (include/reinfocus_hip.h): the sde entry points above over G groups, one launch per stage ---------------
+
+#define RF_POPULATION_LIMITS "%s: G = %d must be in 1 .. %d, m = %d in 1 .. 2^20 and G m at most 2^30"
+
+int rf_sde_noise_reset_grouped(rf_ctx *ctx, const rf_policy_desc *desc, int G, int m, const float *d_params,
+                               const unsigned long long *d_gens, const unsigned long long *d_consumed,
+                               const unsigned char *d_select, float *d_theta, void *caller_stream)
+{
+    const char *fn = "rf_sde_noise_reset_grouped";
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", fn);
+    RF_REQUIRE(desc != nullptr && d_params != nullptr && d_gens != nullptr && d_consumed != nullptr && d_theta != nullptr,
+               "%s: NULL argument", fn);
+    rf::PolicyLayout layout;
+    RF_REQUIRE(rf::sde_layout(*desc, layout), RF_SDE_LIMITS, fn, RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_WIDTH);
+    RF_REQUIRE(rf::population_rows(G, m) && m <= (1 << 20), RF_POPULATION_LIMITS, fn, G, RF_POPULATION_MAX_GROUPS, m);
+    RF_HIP(hipSetDevice(ctx->device));
+    const size_t groups = (size_t)G, cells = (size_t)m * (size_t)layout.sde;
+    struct Array {
+        const void *p;
+        size_t bytes, align;
+        const char *what;
+    };
+    const Array inputs[] = {{d_params, groups * (size_t)layout.total * 4, 4, "d_params"},
+                            {d_gens, groups * 32, 8, "d_gens"},
+                            {d_consumed, groups * 8, 8, "d_consumed"},
+                            {d_select, groups, 1, "d_select"}};
+    for (const Array &a : inputs) {
+        if (a.p == nullptr)
+            continue;
+        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
+            return rc;
+    }
+    if (int rc = check_device_array(ctx, d_theta, groups * cells * 4, 4, "d_theta", fn))
+        return rc;
+    for (const Array &b : inputs)
+        RF_REQUIRE(b.p == nullptr || !ranges_overlap(d_theta, groups * cells * 4, b.p, b.bytes), "%s: d_theta overlaps %s", fn,
+                   b.what);
+    // As rf_sde_noise_reset: one launch on the caller's stream, nothing allocated, nothing waited for; the generators'
+    // words, their draw counts and the selection are read on the device.
+    static_assert(sizeof(rf::PolicyGen) == 32, "d_gens is uint64 [G][4]");
+    const unsigned blocks = (unsigned)((cells + rf::kPolicyThreads - 1) / rf::kPolicyThreads);
+    hipLaunchKernelGGL(rf::sde_noise_kernel<true>, dim3(blocks, (unsigned)G), dim3(rf::kPolicyThreads), 0,
+                       (hipStream_t)caller_stream, rf::PolicyGen{}, d_params + layout.log_std, m, (int)layout.sde, d_theta,
+                       (const rf::PolicyGen *)d_gens, (const uint64_t *)d_consumed, (const uint8_t *)d_select, layout.total);
+    RF_HIP(hipGetLastError());
+    return RF_OK;
+}
+
+int rf_sde_forward_grouped(rf_ctx *ctx, const rf_policy_desc *desc, int G, int m, const float *d_params, const float *d_obs,
+                           const float *d_final_obs, const float *d_theta, int flags, float *d_actions, float *d_env_actions,
+                           float *d_log_probs, float *d_values, float *d_final_values, float *d_mean, float *d_sigma,
+                           void *caller_stream)
+{
+    const char *fn = "rf_sde_forward_grouped";
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", fn);
+    RF_REQUIRE(desc != nullptr && d_params != nullptr && d_obs != nullptr, "%s: NULL argument", fn);
+    rf::PolicyLayout layout;
+    RF_REQUIRE(rf::sde_layout(*desc, layout), RF_SDE_LIMITS, fn, RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_WIDTH);
+    RF_REQUIRE(rf::population_rows(G, m) && m <= (1 << 20), RF_POPULATION_LIMITS, fn, G, RF_POPULATION_MAX_GROUPS, m);
+    RF_REQUIRE((flags & ~RF_POLICY_DETERMINISTIC) == 0, "%s: unknown flags %d", fn, flags);
+    const bool pi = d_actions || d_env_actions || d_log_probs || d_mean || d_sigma;
+    const bool vf = d_values != nullptr || d_final_values != nullptr;
+    RF_REQUIRE(pi || vf, "%s: no output is asked for", fn);
+    RF_REQUIRE(d_final_values == nullptr || d_final_obs != nullptr, "%s: d_final_values needs d_final_obs", fn);
+    const bool sampled = pi && (flags & RF_POLICY_DETERMINISTIC) == 0;
+    RF_REQUIRE(!sampled || d_theta != nullptr, "%s: a sampled call needs d_theta (rf_sde_noise_reset_grouped)", fn);
+    RF_HIP(hipSetDevice(ctx->device));
+    const size_t rows = (size_t)G * (size_t)m;
+    struct Array {
+        const void *p;
+        size_t bytes, align;
+        const char *what;
+    };
+    const Array inputs[] = {{d_params, (size_t)G * (size_t)layout.total * 4, 4, "d_params"},
+                            {d_obs, rows * (size_t)layout.obs_width * 4, 4, "d_obs"},
+                            {d_final_obs, rows * (size_t)layout.obs_width * 4, 4, "d_final_obs"},
+                            {sampled ? d_theta : nullptr, rows * (size_t)layout.sde * 4, 4, "d_theta"}};
+    const Array outputs[] = {{d_actions, rows * 4, 4, "d_actions"},       {d_env_actions, rows * 4, 4, "d_env_actions"},
+                             {d_log_probs, rows * 4, 4, "d_log_probs"},   {d_values, rows * 4, 4, "d_values"},
+                             {d_final_values, rows * 4, 4, "d_final_values"}, {d_mean, rows * 4, 4, "d_mean"},
+                             {d_sigma, rows * 4, 4, "d_sigma"}};
+    for (const Array &a : inputs) {
+        if (a.p == nullptr)
+            continue;
+        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
+            return rc;
+    }
+    for (const Array &a : outputs) {
+        if (a.p == nullptr)
+            continue;
+        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
+            return rc;
+        for (const Array &b : inputs)
+            RF_REQUIRE(b.p == nullptr || !ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s (an output must "
+                       "not alias an input: other blocks still read it)", fn, a.what, b.what);
+        for (const Array &b : outputs)
+            RF_REQUIRE(&b >= &a || b.p == nullptr || !ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s", fn,
+                       a.what, b.what);
+    }
+    const unsigned tiles = (unsigned)(((size_t)m + rf::kPolicyTile - 1) / rf::kPolicyTile);
+    hipLaunchKernelGGL(rf::sde_forward_kernel<true>, dim3(tiles, pi && vf ? 2u : 1u, (unsigned)G), dim3(rf::kPolicyThreads), 0,
+                       (hipStream_t)caller_stream, layout, d_params, m, d_obs, d_final_obs, sampled ? d_theta : nullptr,
+                       pi ? 0 : 1, d_actions, d_env_actions, d_log_probs, d_values, d_final_values, d_mean, d_sigma);
+    RF_HIP(hipGetLastError());
+    return RF_OK;
+}
+
+unsigned long long rf_sde_grouped_state_size(rf_ctx *ctx, const rf_policy_desc *policy, int G, int m)
+{
+    if (ctx == nullptr || policy == nullptr)
+        return 0;
+    if (hipSetDevice(ctx->device) != hipSuccess) // (as every entry point; nothing of the device is needed)
+        (void)hipGetLastError();
+    return rf::population_state_bytes(*policy, G, m, true);
+}
+
+unsigned long long rf_sde_grouped_workspace_size(rf_ctx *ctx, const rf_policy_desc *policy, int G, int m, int T, int B)
+{
+    if (ctx == nullptr || policy == nullptr)
+        return 0;
+    if (hipSetDevice(ctx->device) != hipSuccess)
+        (void)hipGetLastError();
+    return rf::population_workspace_bytes(*policy, G, m, T, B, true);
+}
+
+int rf_sde_update_grouped(rf_ctx *ctx, const rf_policy_desc *policy, int G, int m, int T, const rf_ppo_hyper *d_hyper,
+                          float *d_params, void *d_state, void *d_workspace, const float *d_obs, const float *d_actions,
+                          const float *d_old_log_probs, const float *d_advantages, const float *d_returns, int B,
+                          const long long *d_index, float *d_stats, void *caller_stream)
+{
+    RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", "rf_sde_update_grouped");
+    RF_HIP(hipSetDevice(ctx->device));
+    return ppo_update_grouped_any("rf_sde_update_grouped", true, ctx, policy, G, m, T, d_hyper, d_params, d_state, d_workspace,
+                                  d_obs, d_actions, d_old_log_probs, d_advantages, d_returns, B, d_index, d_stats,
+                                  caller_stream);
 }
 
 // The recurrent entry points are written once, over (desc, sde, critic): the rf_lstm_ / rf_lstm_sde_ ones are these with
@@ -2758,8 +2912,9 @@ static int lstm_sde_noise_reset_any(const char *fn, int critic, rf_ctx *ctx, con
         words.word[i] = gen[i];
     // sde_noise_kernel as rf_sde_noise_reset launches it, with this layout's log_std
     const unsigned blocks = (unsigned)((cells + rf::kPolicyThreads - 1) / rf::kPolicyThreads);
-    hipLaunchKernelGGL(rf::sde_noise_kernel, dim3(blocks), dim3(rf::kPolicyThreads), 0, (hipStream_t)caller_stream, words,
-                       d_params + layout.mlp.log_std, n, (int)layout.mlp.sde, d_theta);
+    hipLaunchKernelGGL(rf::sde_noise_kernel<false>, dim3(blocks), dim3(rf::kPolicyThreads), 0, (hipStream_t)caller_stream,
+                       words, d_params + layout.mlp.log_std, n, (int)layout.mlp.sde, d_theta, (const rf::PolicyGen *)nullptr,
+                       (const uint64_t *)nullptr, (const uint8_t *)nullptr, 0u);
     RF_HIP(hipGetLastError());
     return RF_OK;
 }

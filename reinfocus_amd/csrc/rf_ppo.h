@@ -122,20 +122,21 @@ RF_HD bool population_rows(int G, long long rows)
 }
 
 // What rf_ppo_grouped_state_size and rf_ppo_grouped_workspace_size return for a ctx (0: refused): G times the ungrouped
-// sizes, for minibatches of B out of the m T rows of a group
-RF_HD unsigned long long population_state_bytes(const rf_policy_desc &d, int G, int m)
+// sizes, for minibatches of B out of the m T rows of a group.  sde ("population sde", rf_sde_grouped_*): over sde_layout's
+// P + L parameters.
+RF_HD unsigned long long population_state_bytes(const rf_policy_desc &d, int G, int m, bool sde = false)
 {
     PolicyLayout L;
-    if (!policy_layout(d, L) || !population_rows(G, m))
+    if (!(sde ? sde_layout(d, L) : policy_layout(d, L)) || !population_rows(G, m))
         return 0;
     return (unsigned long long)G * (4ull * kPpoStateHeader + 8ull * L.total);
 }
 
-RF_HD unsigned long long population_workspace_bytes(const rf_policy_desc &d, int G, int m, int T, int B)
+RF_HD unsigned long long population_workspace_bytes(const rf_policy_desc &d, int G, int m, int T, int B, bool sde = false)
 {
     PolicyLayout L;
     PpoWork W;
-    if (!policy_layout(d, L) || m < 1 || T < 1 || !population_rows(G, (long long)m * (long long)T)
+    if (!(sde ? sde_layout(d, L) : policy_layout(d, L)) || m < 1 || T < 1 || !population_rows(G, (long long)m * (long long)T)
         || (long long)B > (long long)m * (long long)T || !ppo_work(L, B, W))
         return 0;
     return (unsigned long long)G * 4ull * W.total;
@@ -448,7 +449,8 @@ __device__ __forceinline__ void ppo_store_tile(float *__restrict__ out, const fl
 // array), parameters params + g P, optimizer state + g (kPpoStateHeader + 2 P) floats (`header` is the first group's),
 // workspace ws + g W.total (W.total is even: float64 data stays aligned), hyper-parameters hypers[g], index + g B (rows
 // local to the group) and stats + 8 g.  No block reads what a block of another group writes.  Ungrouped, hypers is unused
-// and the code is what it was without it.
+// and the code is what it was without it.  With kSde as well ("population sde") the actions move as float rows and P is
+// sde_layout's P + L.
 template <bool kSde, bool kGrouped = false>
 __global__ __launch_bounds__(kPpoThreads) void ppo_backward_kernel(
     PolicyLayout L, PpoWork W, PpoHyper hy, const float *__restrict__ params, const PpoHeader *__restrict__ header,
@@ -456,7 +458,6 @@ __global__ __launch_bounds__(kPpoThreads) void ppo_backward_kernel(
     const float *__restrict__ old_log_probs, const float *__restrict__ advantages, const float *__restrict__ returns,
     int B, const int64_t *__restrict__ index, const PpoHyper *__restrict__ hypers /* [G] or null */)
 {
-    static_assert(!(kSde && kGrouped), "a population has the Categorical head");
     if (kGrouped) { // (block-uniform)
         const size_t g = blockIdx.z, row = g * (size_t)N;
         hy = hypers[g];
@@ -465,7 +466,10 @@ __global__ __launch_bounds__(kPpoThreads) void ppo_backward_kernel(
                                                      + g * ((size_t)kPpoStateHeader + 2 * (size_t)L.total));
         ws += g * (size_t)W.total;
         obs += row * (size_t)L.obs_width;
-        actions_any = static_cast<const int64_t *>(actions_any) + row;
+        if (kSde)
+            actions_any = static_cast<const float *>(actions_any) + row;
+        else
+            actions_any = static_cast<const int64_t *>(actions_any) + row;
         old_log_probs += row, advantages += row, returns += row;
         index += g * (size_t)B;
     }

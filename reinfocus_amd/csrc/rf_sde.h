@@ -10,6 +10,8 @@
 //                       activations of its tile in LDS, thread k squares exp(log_std_k) once, and one lane per
 //                       environment runs the three chains over k -- the mean, the theta dot product and the variance.
 // The update is rf_ppo.h's three kernels with the Gaussian head compiled in (ppo_backward_kernel<true>).
+// Both kernels are templates over kGrouped ("population sde": G groups of n environments each in one launch, every group
+// with its own parameters, generator and draw count); the ungrouped instantiations are the kernels they were.
 #pragma once
 
 #include "rf_ppo.h"
@@ -23,14 +25,41 @@ RF_HD float sde_theta(const uint64_t gen[4], uint64_t i, float log_std)
 }
 
 #if defined(__HIPCC__)
+// kGrouped ("population sde"): grid (ceil(n L / kPolicyThreads), G) with n the environments of ONE group.  Block (., g) is
+// a block of the ungrouped kernel over group g's rows of theta -- rows [g n, (g + 1) n) -- with the generator gens[g], whose
+// draw number consumed[g] + e L + k the cell takes (64-bit), and the log_std of the group's parameters, log_std + g stride.
+// A group whose select byte is 0 writes nothing (null selects every group).  Ungrouped, the four last arguments are unused
+// and the code is what it was without them.
+template <bool kGrouped>
 __global__ __launch_bounds__(kPolicyThreads) void sde_noise_kernel(PolicyGen gen, const float *__restrict__ log_std, int n,
-                                                                   int L, float *__restrict__ theta)
+                                                                   int L, float *__restrict__ theta,
+                                                                   const PolicyGen *__restrict__ gens /* [G] or null */,
+                                                                   const uint64_t *__restrict__ consumed /* [G] or null */,
+                                                                   const uint8_t *__restrict__ select /* [G] or null */,
+                                                                   unsigned stride)
 {
+    uint64_t first = 0;
+    if (kGrouped) { // (block-uniform; the test on select comes first)
+        const size_t g = blockIdx.y;
+        if (select != nullptr && select[g] == 0)
+            return;
+        gen = gens[g];
+        first = consumed[g];
+        log_std += g * (size_t)stride;
+        theta += g * (size_t)n * (size_t)L;
+    }
     const size_t i = (size_t)blockIdx.x * (size_t)kPolicyThreads + (size_t)threadIdx.x;
     if (i < (size_t)n * (size_t)L)
-        theta[i] = sde_theta(gen.word, (uint64_t)i, log_std[i % (size_t)L]);
+        theta[i] = sde_theta(gen.word, kGrouped ? first + (uint64_t)i : (uint64_t)i, log_std[i % (size_t)L]);
 }
 
+// kGrouped ("population sde"): grid (ceil(n / kPolicyTile), nets, G) as policy_forward_kernel<true>: block (., ., g) is a
+// block of the ungrouped kernel over group g's rows of every array, with the parameters params + g (P + L) -- so s_std2 is
+// the group's own log_std -- and the group's rows of theta.  Tiles are cut per group.  Only params moves to the group's
+// piece; the rows are reached as row0 + env through the kernel's own argument pointers: moving all eleven (nine nullable)
+// pointers at the top, as policy_forward_kernel<true> does, took this kernel from 39 to 92 VGPRs and from 8 to 5 waves per
+// SIMD (profiles/population_sde.md).  Ungrouped, row0 is the constant 0 and the code is what it was.
+template <bool kGrouped>
 __global__ __launch_bounds__(kPolicyThreads) void sde_forward_kernel(
     PolicyLayout L, const float *__restrict__ params, int n, const float *__restrict__ obs,
     const float *__restrict__ final_obs /* or null */, const float *__restrict__ theta /* null: deterministic */,
@@ -39,6 +68,9 @@ __global__ __launch_bounds__(kPolicyThreads) void sde_forward_kernel(
 {
     __shared__ __align__(16) float s_act[2][kPolicyMaxWidth][kPolicyTile]; // inputs / activations, [k][environment]
     __shared__ float s_std2[kPolicyMaxWidth];
+    if (kGrouped)
+        params += (size_t)blockIdx.z * (size_t)L.total;
+    const size_t row0 = kGrouped ? (size_t)blockIdx.z * (size_t)n : 0;
     const int tid = threadIdx.x;
     const int net = (int)blockIdx.y + first_net;
     const int e0 = (int)blockIdx.x * kPolicyTile;
@@ -51,7 +83,7 @@ __global__ __launch_bounds__(kPolicyThreads) void sde_forward_kernel(
             continue;
         for (int i = tid; i < D * kPolicyTile; i += kPolicyThreads) {
             const int e = i / D, k = i - e * D;
-            s_act[0][k][e] = e0 + e < n ? in[(size_t)e0 * (size_t)D + (size_t)i] : 0.0f;
+            s_act[0][k][e] = e0 + e < n ? in[(row0 + (size_t)e0) * (size_t)D + (size_t)i] : 0.0f;
         }
         __syncthreads();
         int cur = 0, K = D;
@@ -70,33 +102,35 @@ __global__ __launch_bounds__(kPolicyThreads) void sde_forward_kernel(
             __syncthreads();
             const int env = e0 + tid;
             if (tid < kPolicyTile && env < n) {
+                const size_t at = row0 + (size_t)env;
                 const float *h = &s_act[cur][0][tid];
                 const float mu = policy_dot(h, kPolicyTile, params + L.weight[0][head], 1, params[L.bias[0][head]], K);
                 const float s = sde_sigma(h, kPolicyTile, s_std2, K);
                 float a = mu;
                 if (theta != nullptr)
-                    a = mu + policy_dot(h, kPolicyTile, theta + (size_t)env * (size_t)K, 1, 0.0f, K);
+                    a = mu + policy_dot(h, kPolicyTile, theta + at * (size_t)K, 1, 0.0f, K);
                 if (actions != nullptr)
-                    actions[env] = policy_canonical(a);
+                    actions[at] = policy_canonical(a);
                 if (env_actions != nullptr)
-                    env_actions[env] = sde_env_action(a);
+                    env_actions[at] = sde_env_action(a);
                 if (log_probs != nullptr)
-                    log_probs[env] = sde_log_prob(a, mu, s);
+                    log_probs[at] = sde_log_prob(a, mu, s);
                 if (mean != nullptr)
-                    mean[env] = policy_canonical(mu);
+                    mean[at] = policy_canonical(mu);
                 if (sigma != nullptr)
-                    sigma[env] = policy_canonical(s);
+                    sigma[at] = policy_canonical(s);
             }
         } else {
             const int env = e0 + tid;
             if (tid < kPolicyTile && env < n) {
+                const size_t at = row0 + (size_t)env;
                 const float y = policy_dot(&s_act[cur][0][tid], kPolicyTile, params + L.weight[1][head], 1,
                                            params[L.bias[1][head]], K);
                 if (pass == 0)
-                    values[env] = policy_canonical(y);
+                    values[at] = policy_canonical(y);
                 else {
-                    const float lead = in[(size_t)env * (size_t)D];
-                    final_values[env] = lead != lead ? bits_f32(kPolicyNaN) : policy_canonical(y);
+                    const float lead = in[at * (size_t)D];
+                    final_values[at] = lead != lead ? bits_f32(kPolicyNaN) : policy_canonical(y);
                 }
             }
         }

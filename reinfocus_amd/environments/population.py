@@ -15,14 +15,24 @@ e T + t, so the rows of consecutive environments are contiguous).
                              kind, so Rollout.collect / DeviceRollout.collect take it as they take a Policy / DevicePolicy
     DevicePopulationLearner  update / train: three launches per minibatch whatever G is (rf_ppo_update_grouped)
 
+The Gaussian head (include/reinfocus_hip.h, "population sde"): G gSDE learners over a Box(-1, 1, (1,)) action space, each
+group with its own log_std (log_std_init per group) and its own noise schedule (collect(sde_sample_freq=G values)), as
+the reference's search draws both per trial for ContinuousJumps-v0.
+
+    SdePopulationPolicy        the numpy twin: literally G sde.SdePolicy over slices, and the oracle
+    DeviceSdePopulationPolicy  reset_noise(groups=mask) / act / values in ONE launch each (rf_sde_noise_reset_grouped,
+                               rf_sde_forward_grouped); spec.kind is the sde kind
+    PopulationLearner / DevicePopulationLearner take them as they take the Categorical ones and dispatch on the spec's
+    kind (G learner.Learner over SdePolicy members; rf_sde_update_grouped)
+
 A normaliser and GAE discounts per group (include/reinfocus_hip.h, "population view"): an environment built with
 learner_view=harness.LearnerView(..., gamma=scalar | G values, groups=G) keeps running moments per group, taken over the
 group's own lanes, and rollout.Rollout / DeviceRollout(env, n_steps, gamma, gae_lambda, groups=G) take a gamma and a
 gae_lambda per group -- what a stand-alone trial over m environments normalises and discounts by.  VecNormalize's gamma
 (the view's) and the rollout's gamma are passed separately; rl_zoo3 sets both from the trial's gamma.
 
-The Categorical head (MlpPolicySpec) only.  Out of scope: the sde, lstm and lstm-sde heads; groups that differ in
-architecture, m, T or batch size; SB3Wrapper; and the environment's shared reset-state generator -- lanes that end are
+Out of scope: the lstm and lstm-sde heads; groups that differ in architecture, m, T or batch size; more than one action
+dimension; SB3Wrapper; and the environment's shared reset-state generator -- lanes that end are
 ranked across all groups, so which reset state a lane draws depends on other groups' episode ends: the independence
 covers what the learner is given the raw step, not the environment's draws.
 
@@ -33,6 +43,7 @@ import numpy as np
 
 from reinfocus_amd.environments import learner as learner_module
 from reinfocus_amd.environments import policy as policy_module
+from reinfocus_amd.environments import sde as sde_module
 from reinfocus_amd.environments.learner import MAX_BATCH, STATE_HEADER, f64
 from reinfocus_amd.environments.policy import DETERMINISTIC, f32
 
@@ -47,6 +58,10 @@ def _checked_population(spec, groups, seeds):
     if getattr(spec, "kind", None) != policy_module.MlpPolicySpec.kind:
         raise ValueError(f"a population has the Categorical head of MlpPolicySpec, not a spec of kind "
                          f"{getattr(spec, 'kind', None)!r}: the sde and lstm heads are out of scope")
+    return _checked_groups(groups, seeds)
+
+
+def _checked_groups(groups, seeds):
     groups = int(groups)
     if not 1 <= groups <= MAX_GROUPS:
         raise ValueError(f"groups {groups} is not in 1 .. {MAX_GROUPS}")
@@ -55,6 +70,34 @@ def _checked_population(spec, groups, seeds):
         raise ValueError(f"seeds must be a sequence of one seed per group ({groups}), not "
                          f"{'a scalar' if seeds is None else len(seeds)}")
     return groups, seeds
+
+
+def _checked_sde_population(spec, groups, seeds, log_std_init):
+    """(G, seeds, log_std_init per group) of a population with the Gaussian head."""
+    if getattr(spec, "kind", None) != sde_module.SdePolicySpec.kind:
+        raise ValueError(f"a population of gSDE learners has the Gaussian head of SdePolicySpec, not a spec of kind "
+                         f"{getattr(spec, 'kind', None)!r}: MlpPolicySpec has PopulationPolicy / DevicePopulationPolicy, "
+                         "the lstm heads are out of scope")
+    groups, seeds = _checked_groups(groups, seeds)
+    inits = per_group(spec.log_std_init if log_std_init is None else log_std_init, groups, "log_std_init")
+    return groups, seeds, np.array([float(x) for x in inits], dtype=f32)
+
+
+def _initial_params(spec, inits):
+    """float32 [G][P + L]: spec.initial() per group, with the group's own log_std_init."""
+    params = np.tile(spec.initial(), (len(inits), 1))
+    params[:, spec.log_std_at:] = inits[:, None]
+    return params
+
+
+def group_mask(selected, groups):
+    """`selected` as a bool array [G]: None for every group, else a boolean sequence of length G."""
+    if selected is None:
+        return np.ones(groups, dtype=bool)
+    mask = np.asarray(selected)
+    if mask.shape != (groups,) or mask.dtype not in (np.dtype(bool), np.dtype(np.uint8)) or mask.max(initial=0) > 1:
+        raise ValueError(f"groups must be None or a boolean sequence of one entry per group ({groups}), not {selected!r}")
+    return mask.astype(bool)
 
 
 def _per_group(lanes, groups):
@@ -121,6 +164,14 @@ def hyper_records(hypers):
     return records
 
 
+def _refuse_rollout(spec, rollout):
+    """A Categorical population refuses a Box rollout, one with the Gaussian head a Discrete one."""
+    if spec.kind == sde_module.SdePolicySpec.kind:
+        sde_module._refuse_discrete(rollout.env.single_action_space)
+    else:
+        policy_module._refuse_box(rollout.env.single_action_space)
+
+
 class PopulationPolicy:
     """The numpy twin of DevicePopulationPolicy, and its oracle: G policy.Policy, group g seeded with seeds[g], over
     slices of the rows.  `params` is one array [G][P]; policies[g].params is its row g."""
@@ -183,13 +234,70 @@ class PopulationPolicy:
             member.set_rng_state(state)
 
 
+class SdePopulationPolicy:
+    """The numpy twin of DeviceSdePopulationPolicy, and its oracle: G sde.SdePolicy, group g seeded with seeds[g], over
+    slices of the rows.  `params` is one array [G][P + L]; policies[g].params is its row g.  log_std_init: a scalar or G
+    values, which override the spec's per group.  num_envs (n = G m; reset_noise(num_envs=) sets it) says how many rows
+    of noise a group draws: m L draws of its own generator per reset."""
+
+    def __init__(self, spec, groups, seeds, log_std_init=None):
+        self.groups, seeds, inits = _checked_sde_population(spec, groups, seeds, log_std_init)
+        self.spec = spec
+        self.params = _initial_params(spec, inits)
+        self.policies = [sde_module.SdePolicy(spec, seed) for seed in seeds]
+        for g, member in enumerate(self.policies):
+            member.params = self.params[g]
+        self.num_envs = self.groups
+
+    _groups_of = PopulationPolicy._groups_of
+    load_state_dict = PopulationPolicy.load_state_dict
+    state_dict = PopulationPolicy.state_dict
+    _split = PopulationPolicy._split
+    values = PopulationPolicy.values
+    rng_state = PopulationPolicy.rng_state
+    set_rng_state = PopulationPolicy.set_rng_state
+
+    def reset_noise(self, groups=None, num_envs=None):
+        """A new theta [m, L] for every selected group (None: every group; else a boolean sequence of length G) from the
+        group's current log_std: m L draws of each selected group's generator.  An unselected group keeps its theta and
+        its generator state."""
+        mask = group_mask(groups, self.groups)
+        m = _per_group(self.num_envs if num_envs is None else int(num_envs), self.groups)
+        self.num_envs = m * self.groups
+        for member, selected in zip(self.policies, mask):
+            if selected:
+                member.reset_noise(m)
+
+    def noise(self):
+        """theta float32 [n, L] (a copy), or None while a group has none."""
+        parts = [member.noise() for member in self.policies]
+        return None if any(part is None for part in parts) else np.concatenate(parts)
+
+    def set_noise(self, theta):
+        if theta is None:
+            for member in self.policies:
+                member.set_noise(None)
+            return
+        theta = np.asarray(theta, dtype=f32).reshape(-1, self.spec.latent)
+        m = _per_group(theta.shape[0], self.groups)
+        for g, member in enumerate(self.policies):
+            member.set_noise(theta[g * m:(g + 1) * m])
+
+    def act(self, obs, final_obs=None, deterministic=False):
+        """(actions float32 [n] (raw), values, log_probs, final_values or None, env_actions float32 [n] (clamped)) over all
+        n = G m rows: group g's rows by policies[g] and its theta.  No draw is consumed."""
+        parts = [member.act(rows, final_rows, deterministic)
+                 for member, (rows, final_rows) in zip(self.policies, self._split(obs, final_obs))]
+        return tuple(None if parts[0][i] is None else np.concatenate([part[i] for part in parts]) for i in range(5))
+
+
 class PopulationLearner(_GroupHyper):
     """The numpy twin of DevicePopulationLearner, and its oracle: G learner.Learner, learners[g] over policies[g] and the
     group's rows."""
 
     def __init__(self, policy, learning_rate=3e-4, clip_range=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5,
                  normalize_advantage=True, betas=(0.9, 0.999), adam_eps=1e-5):
-        if not isinstance(policy, PopulationPolicy):
+        if not isinstance(policy, (PopulationPolicy, SdePopulationPolicy)):
             raise TypeError(f"PopulationLearner needs a PopulationPolicy, not {type(policy).__name__} (a "
                             "DevicePopulationPolicy has DevicePopulationLearner)")
         self.policy, self.spec, self.groups = policy, policy.spec, policy.groups
@@ -224,7 +332,7 @@ class PopulationLearner(_GroupHyper):
         may be shorter): stats float32 [n_epochs * ceil(m T / batch_size)][G][8].  Per epoch and group one permutation of
         the group's m T local rows: permutations[epoch][g] (int64 [n_epochs][G][m T]) if given, else
         generator.permutation(m T), drawn epoch by epoch and in group order."""
-        policy_module._refuse_box(rollout.env.single_action_space)
+        _refuse_rollout(self.spec, rollout)
         flat = rollout.flat()
         rows = _per_group(np.asarray(flat["actions"]).shape[0], self.groups)
         n_epochs, batch_size, per_epoch = self._batches(rows, n_epochs, batch_size)
@@ -388,27 +496,168 @@ class DevicePopulationPolicy:
         return values if final_obs is None else (values, final_values)
 
 
+class DeviceSdePopulationPolicy:
+    """The sde policies of G groups of m environments each of one device-resident environment with the Box(-1, 1, (1,))
+    action space (n = G m), over torch tensors on its GPU; used as SdePopulationPolicy is and bit for bit equal to it,
+    group by group equal to a stand-alone DeviceSdePolicy(seed=seeds[g]) over the group's m environments.
+
+    reset_noise(groups=mask), act() and values() are ONE launch each (rf_sde_noise_reset_grouped, grid (ceil(m L / 256),
+    G); rf_sde_forward_grouped, grid (ceil(m / 8), nets, G)).  `params` is one float32 tensor [G][P + L], theta one
+    [G m][L].  The generators' words live in a device table written at seeding and at set_rng_state only.  The draws each
+    generator has given are counted on the host (uint64 [G]); a reset sends them and the selection to the device from
+    pinned memory, stream-ordered, so no call waits for the host.  rng_state() is computed on the host."""
+
+    _device_env = policy_module.DevicePolicy._device_env
+    _rows = policy_module.DevicePolicy._rows
+    _out = policy_module.DevicePolicy._out
+
+    def __init__(self, env, spec, groups, seeds, log_std_init=None):
+        self._device_env(env)
+        sde_module._refuse_discrete(env.single_action_space)
+        self.groups, seeds, inits = _checked_sde_population(spec, groups, seeds, log_std_init)
+        self.num_envs = int(env.num_envs)
+        self.per_group = _per_group(self.num_envs, self.groups)
+        self._io = env._tensor_io()  # (ValueError, as step_tensors': a host initializer, a render_mode)
+        from reinfocus_amd import torch_interop
+
+        self._interop = torch_interop
+        torch = self._torch = torch_interop._torch()
+        self.spec = spec
+        self._ctx = env._ctx
+        self.device = torch.device("cuda", self._ctx.device)
+        self.params = torch.zeros((self.groups, spec.size), dtype=torch.float32, device=self.device)
+        self.params.copy_(torch.from_numpy(_initial_params(spec, inits)))
+        self._owned = {}
+        self._table = torch.zeros((self.groups, 4), dtype=torch.int64, device=self.device)  # (the bits of uint64 words)
+        self._theta = torch.zeros((self.num_envs, spec.latent), dtype=torch.float32, device=self.device)
+        self._has_noise = np.zeros(self.groups, dtype=bool)
+        # what a reset reads on the device: uint64 [G] draws given, then uint8 [G] selected
+        self._schedule = torch.zeros(9 * self.groups, dtype=torch.uint8, device=self.device)
+        self._set_generators([np.random.PCG64DXSM(seed) for seed in seeds])
+
+    def _set_generators(self, generators):
+        self._generators, self._consumed = generators, np.zeros(self.groups, dtype=np.uint64)
+        words = np.array([policy_module.generator_words(generator) for generator in generators], dtype=np.uint64)
+        self._table.copy_(self._torch.from_numpy(words.view(np.int64)))
+
+    def rng_state(self):
+        """What G stand-alone policies would return, in group order: each seed's generator advanced by the draws taken."""
+        states = []
+        for generator, consumed in zip(self._generators, self._consumed):
+            now = np.random.PCG64DXSM()
+            now.state = generator.state
+            states.append(now.advance(int(consumed)).state)
+        return states
+
+    set_rng_state = DevicePopulationPolicy.set_rng_state
+    _groups_of = PopulationPolicy._groups_of
+    load_state_dict = DevicePopulationPolicy.load_state_dict
+    state_dict = DevicePopulationPolicy.state_dict
+    _all_rows = DevicePopulationPolicy._all_rows
+
+    def reset_noise(self, groups=None, num_envs=None):
+        """A new theta [m, L] for every selected group (None: every group; else a boolean sequence of length G) from the
+        group's current log_std: ONE launch, and m L draws of each selected group's generator.  An unselected group keeps
+        its rows of theta and its generator state."""
+        torch = self._torch
+        mask = group_mask(groups, self.groups)
+        if num_envs is not None and int(num_envs) != self.num_envs:
+            raise ValueError(f"num_envs {num_envs} is not the environment's {self.num_envs}")
+        self._interop.check_one_runtime()
+        G = self.groups
+        packed = np.empty(9 * G, dtype=np.uint8)
+        packed[:8 * G] = self._consumed.view(np.uint8)
+        packed[8 * G:] = mask
+        # (a pinned buffer of its own per call: the copy is stream-ordered, and resets enqueued before keep what they read)
+        self._schedule.copy_(torch.from_numpy(packed).pin_memory(), non_blocking=True)
+        at = self._schedule.data_ptr()
+        self._ctx.sde_noise_reset_grouped(self.spec.desc(), G, self.per_group, self.params.data_ptr(),
+                                          self._table.data_ptr(), at, None if groups is None else at + 8 * G,
+                                          self._theta.data_ptr(), self._io._stream())
+        self._consumed[mask] += np.uint64(self.per_group * self.spec.latent)  # (after the call was taken)
+        self._has_noise |= mask
+
+    def noise(self):
+        """theta float32 [n, L] (a clone), or None while a group has none."""
+        return self._theta.clone() if self._has_noise.all() else None
+
+    def set_noise(self, theta):
+        torch = self._torch
+        if theta is None:
+            self._has_noise[:] = False
+            return
+        if not isinstance(theta, torch.Tensor) or theta.dtype != torch.float32 \
+                or tuple(theta.shape) != (self.num_envs, self.spec.latent):
+            raise ValueError(f"theta must be a torch.float32 tensor ({self.num_envs}, {self.spec.latent}) on {self.device}")
+        self._io._on_device(theta, "theta")
+        self._theta.copy_(theta)
+        self._has_noise[:] = True
+
+    def _forward(self, obs, final_obs, theta, flags, actions, env_actions, log_probs, values, final_values):
+        self._interop.check_one_runtime()
+        pointer = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        self._ctx.sde_forward_grouped(self.spec.desc(), self.groups, self.per_group, self.params.data_ptr(), obs.data_ptr(),
+                                      pointer(final_obs), pointer(theta), flags, pointer(actions), pointer(env_actions),
+                                      pointer(log_probs), pointer(values), pointer(final_values), None, None,
+                                      self._io._stream())
+
+    def act(self, obs, final_obs=None, deterministic=False, out=None):
+        """DeviceSdePolicy.act over all n = G m rows, group g's rows with params[g] and its rows of theta.  One launch; no
+        draw is consumed."""
+        torch = self._torch
+        obs = self._all_rows(obs, final_obs)
+        n = self.num_envs
+        if not deterministic and not self._has_noise.all():
+            raise ValueError("a sampled act() needs reset_noise() of every group first")
+        given = (None,) * 5 if out is None else tuple(out)
+        if len(given) != 5:
+            raise TypeError("out must be (actions, values, log_probs, final_values or None, env_actions)")
+        actions = self._out("raw_actions", given[0], n, torch.float32)
+        values = self._out("values", given[1], n, torch.float32)
+        log_probs = self._out("log_probs", given[2], n, torch.float32)
+        final_values = None if final_obs is None else self._out("final_values", given[3], n, torch.float32)
+        env_actions = self._out("env_actions", given[4], n, torch.float32)
+        self._forward(obs, final_obs, None if deterministic else self._theta,
+                      DETERMINISTIC if deterministic else 0, actions, env_actions, log_probs, values, final_values)
+        return actions, values, log_probs, final_values, env_actions
+
+    def values(self, obs, final_obs=None, out=None):
+        """DeviceSdePolicy.values over all n rows.  One launch, no draw."""
+        torch = self._torch
+        obs = self._all_rows(obs, final_obs)
+        given = (None, None) if out is None else tuple(out)
+        if len(given) != 2:
+            raise TypeError("out must be (values, final_values or None)")
+        values = self._out("last_values", given[0], self.num_envs, torch.float32)
+        final_values = None if final_obs is None else self._out("final_values", given[1], self.num_envs, torch.float32)
+        self._forward(obs, final_obs, None, 0, None, None, None, values, final_values)
+        return values if final_obs is None else (values, final_values)
+
+
 class DevicePopulationLearner(_GroupHyper):
-    """The learners of a DevicePopulationPolicy, over torch tensors on its GPU; used as PopulationLearner is and bit for
-    bit equal to it.  update() is rf_ppo_update_grouped: three launches on torch's current stream whatever G is, which
+    """The learners of a DevicePopulationPolicy or a DeviceSdePopulationPolicy, over torch tensors on its GPU; used as
+    PopulationLearner is and bit for bit equal to it.  update() is rf_ppo_update_grouped (rf_sde_update_grouped with the
+    Gaussian head, over float32 raw actions): three launches on torch's current stream whatever G is, which
     change policy.params in place.  The hyper-parameters are packed into one device tensor (G rf_ppo_hyper) when an
     update is enqueued, from pinned memory and only when they changed.  train() enqueues every update of every epoch back
     to back.  No method synchronises the host (state_dict() reads the steps and does)."""
 
     def __init__(self, policy, learning_rate=3e-4, clip_range=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5,
                  normalize_advantage=True, betas=(0.9, 0.999), adam_eps=1e-5):
-        if not isinstance(policy, DevicePopulationPolicy):
+        if not isinstance(policy, (DevicePopulationPolicy, DeviceSdePopulationPolicy)):
             raise TypeError(f"DevicePopulationLearner needs a DevicePopulationPolicy, not {type(policy).__name__} (a "
                             "PopulationPolicy has PopulationLearner, a DevicePolicy DeviceLearner)")
         self.policy, self.spec, self.groups = policy, policy.spec, policy.groups
+        self._sde = self.spec.kind == sde_module.SdePolicySpec.kind
         self._configure(learning_rate, clip_range, ent_coef, vf_coef, max_grad_norm, normalize_advantage, betas, adam_eps)
         self._torch, self._interop, self._io, self._ctx = policy._torch, policy._interop, policy._io, policy._ctx
         self.device = policy.device
         torch = self._torch
         self._state_floats = STATE_HEADER + 2 * self.spec.size
-        if self._ctx.ppo_grouped_state_size(self.spec.desc(), self.groups, policy.per_group) \
-                != 4 * self.groups * self._state_floats:
-            raise RuntimeError("rf_ppo_grouped_state_size disagrees with the packed optimizer states")
+        state_size = self._ctx.sde_grouped_state_size if self._sde else self._ctx.ppo_grouped_state_size
+        if state_size(self.spec.desc(), self.groups, policy.per_group) != 4 * self.groups * self._state_floats:
+            raise RuntimeError("rf_ppo_grouped_state_size / rf_sde_grouped_state_size disagrees with the packed optimizer "
+                               "states")
         self.state = torch.zeros((self.groups, self._state_floats), dtype=torch.float32, device=self.device)
         self._workspace, self._workspace_key = None, None
         self._stats = None
@@ -430,8 +679,8 @@ class DevicePopulationLearner(_GroupHyper):
     def _checked(self, flat, index):
         """(steps T, batch B) of flat() tensors of G m T rows and an index [G][B]."""
         torch = self._torch
-        wanted = {"observations": torch.float32, "actions": torch.int64, "log_probs": torch.float32,
-                  "advantages": torch.float32, "returns": torch.float32}
+        wanted = {"observations": torch.float32, "actions": torch.float32 if self._sde else torch.int64,
+                  "log_probs": torch.float32, "advantages": torch.float32, "returns": torch.float32}
         total = None
         for key, dtype in wanted.items():
             tensor = flat[key]
@@ -461,21 +710,21 @@ class DevicePopulationLearner(_GroupHyper):
     def _room(self, steps, batch):
         key = (steps, batch)
         if key != self._workspace_key:
-            size = self._ctx.ppo_grouped_workspace_size(self.spec.desc(), self.groups, self.policy.per_group, steps, batch)
+            workspace_size = self._ctx.sde_grouped_workspace_size if self._sde else self._ctx.ppo_grouped_workspace_size
+            size = workspace_size(self.spec.desc(), self.groups, self.policy.per_group, steps, batch)
             if size == 0:
-                raise RuntimeError(f"rf_ppo_grouped_workspace_size refuses minibatches of {batch} out of "
-                                   f"{steps * self.policy.per_group} rows")
+                raise RuntimeError(f"rf_ppo_grouped_workspace_size / rf_sde_grouped_workspace_size refuses minibatches of "
+                                   f"{batch} out of {steps * self.policy.per_group} rows")
             if self._workspace is None or self._workspace.numel() < size // 4:
                 self._workspace = self._torch.zeros(size // 4, dtype=self._torch.float32, device=self.device)
             self._workspace_key = key
 
     def _enqueue(self, flat, steps, index, stats, hyper):
-        self._ctx.ppo_update_grouped(self.spec.desc(), self.groups, self.policy.per_group, steps, hyper.data_ptr(),
-                                     self.policy.params.data_ptr(), self.state.data_ptr(), self._workspace.data_ptr(),
-                                     flat["observations"].data_ptr(), flat["actions"].data_ptr(),
-                                     flat["log_probs"].data_ptr(), flat["advantages"].data_ptr(),
-                                     flat["returns"].data_ptr(), index.shape[1], index.data_ptr(), stats.data_ptr(),
-                                     self._io._stream())
+        update = self._ctx.sde_update_grouped if self._sde else self._ctx.ppo_update_grouped
+        update(self.spec.desc(), self.groups, self.policy.per_group, steps, hyper.data_ptr(), self.policy.params.data_ptr(),
+               self.state.data_ptr(), self._workspace.data_ptr(), flat["observations"].data_ptr(),
+               flat["actions"].data_ptr(), flat["log_probs"].data_ptr(), flat["advantages"].data_ptr(),
+               flat["returns"].data_ptr(), index.shape[1], index.data_ptr(), stats.data_ptr(), self._io._stream())
 
     def update(self, flat, index):
         """One minibatch update of every group from rows index[g] (int64 device tensor [G][B], local to the group) of its
@@ -494,7 +743,7 @@ class DevicePopulationLearner(_GroupHyper):
         uniform draw [G][m T]; generator: a torch.Generator of that device).  Returns the stats as one device tensor
         [n_epochs * ceil(m T / batch_size)][G][8].  Nothing waits for the host."""
         torch = self._torch
-        policy_module._refuse_box(rollout.env.single_action_space)
+        _refuse_rollout(self.spec, rollout)
         if getattr(rollout, "device", None) != self.device:
             raise ValueError(f"the rollout lives on {getattr(rollout, 'device', 'the host')}, the policy on {self.device}")
         flat = rollout.flat()

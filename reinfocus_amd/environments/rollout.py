@@ -146,6 +146,7 @@ class _Bookkeeping:
         self._last_bootstrap = -1
         self._complete = False  # (row T holds the observation the next rollout begins with)
         self._fresh = self._lstm = False
+        self._sde_freqs = None  # (collect() with a population of gSDE learners: sde_sample_freq per group)
         # what collect() keeps of a recurrent policy (environments/lstm.py), made on first use with one: episode_starts
         # uint8 [T + 1, n] and lstm_states float32 [T + 1, 2, 2, n, H] -- what sb3-contrib's RecurrentRolloutBuffer hands
         # to the update.  A rollout that never sees such a policy allocates neither.
@@ -211,11 +212,44 @@ class _Bookkeeping:
         if self.groups is not None and policy_groups is not None and int(policy_groups) != self.groups:
             raise ValueError(f"collect() of a rollout with groups={self.groups} was given a population policy of "
                              f"{policy_groups} groups")
+        # (a population of gSDE learners, environments/population.py: a noise schedule per group)
+        self._sde_freqs = None
+        if sde and policy_groups is not None:
+            self._sde_freqs = self._group_freqs(sde_sample_freq, int(policy_groups))
+            return sde
         if int(sde_sample_freq) != sde_sample_freq or (sde_sample_freq < 1 and sde_sample_freq != -1):
             raise ValueError(f"sde_sample_freq {sde_sample_freq!r} is not -1 or a positive integer")
         if not sde and sde_sample_freq != -1:
             raise ValueError("sde_sample_freq belongs to the policies of environments/sde.py and lstm_sde.py")
         return sde
+
+    @staticmethod
+    def _group_freqs(sde_sample_freq, groups):
+        """sde_sample_freq of a population as G integers: a scalar for all groups, or one value per group."""
+        if isinstance(sde_sample_freq, (list, tuple, np.ndarray)):
+            freqs = list(sde_sample_freq)
+            if len(freqs) != groups:
+                raise ValueError(f"sde_sample_freq has {len(freqs)} entries, the population {groups} groups")
+        else:
+            freqs = [sde_sample_freq] * groups
+        for freq in freqs:
+            if int(freq) != freq or (freq < 1 and freq != -1):
+                raise ValueError(f"sde_sample_freq {freq!r} is not -1 or a positive integer")
+        return [int(freq) for freq in freqs]
+
+    def _reset_noise(self, policy, t, sde_sample_freq):
+        """stable-baselines3's collect_rollouts: reset_noise before the loop (t None), and in it when _resample says so.
+        A population resets every group before the loop and at step t, in ONE call, the groups that are due by their own
+        sde_sample_freq -- none at all when no group is."""
+        if self._sde_freqs is None:
+            if t is None or self._resample(t, sde_sample_freq):
+                policy.reset_noise(self.num_envs)
+        elif t is None:
+            policy.reset_noise(num_envs=self.num_envs)
+        else:
+            mask = [self._resample(t, freq) for freq in self._sde_freqs]
+            if any(mask):
+                policy.reset_noise(groups=mask, num_envs=self.num_envs)
 
     @staticmethod
     def _resample(t, sde_sample_freq):
@@ -289,19 +323,22 @@ class Rollout(_Bookkeeping):
         records -- the bootstrap of every step, then finish(V(observations[T])).  V(final_observation) of step t - 1
         comes from the act of step t (the last one from the values-only call that gives last_values).  Equal to the
         explicit loop.  With an SdePolicy the noise is reset first and then whenever t % sde_sample_freq == 0 (never
-        again with -1), the slab keeps the raw action and the environment gets the clamped one.  With an LstmPolicy row 0
+        again with -1), the slab keeps the raw action and the environment gets the clamped one.  With a population of gSDE
+        learners (population.SdePopulationPolicy) sde_sample_freq is a scalar or G values: every group's noise is reset
+        first, and at step t one reset_noise(groups=mask) covers the groups with f_g > 0 and t % f_g == 0 (no call when
+        none is due).  With an LstmPolicy row 0
         of episode_starts is all ones after start(obs) and the row T of the rollout before after start(), row 0 of
         lstm_states is the policy's state, step t goes from lstm_states[t] to lstm_states[t + 1] with episode_starts[t],
         episode_starts[t + 1] = truncated[t], and afterwards the policy's state is row T."""
         sde = self._collecting(policy, sde_sample_freq)
         if sde:
-            policy.reset_noise(self.num_envs)
+            self._reset_noise(policy, None, sde_sample_freq)
         if self._lstm:
             self._recurrent_rows(policy)
         final_obs = None
         for t in range(self.n_steps):
-            if sde and self._resample(t, sde_sample_freq):
-                policy.reset_noise(self.num_envs)
+            if sde:
+                self._reset_noise(policy, t, sde_sample_freq)
             if self._lstm:
                 actions, values, log_probs, final_values, *clamped = policy.act(
                     self.observations[t], self.episode_starts[t], final_obs, deterministic,
@@ -478,7 +515,8 @@ class DeviceRollout(_Bookkeeping):
     def collect(self, policy, deterministic=False, sde_sample_freq=-1):
         """The whole rollout after start(), by a policy.DevicePolicy or an sde.DeviceSdePolicy (whose noise is reset as
         Rollout.collect says -- one launch each time --, whose raw action goes into actions[t] and whose clamped one,
-        a row the rollout owns, to the step): per step ONE policy launch, which writes
+        a row the rollout owns, to the step; with a population.DeviceSdePopulationPolicy and sde_sample_freq a scalar or
+        G values, one launch resets the groups that are due): per step ONE policy launch, which writes
         actions[t], values[t], log_probs[t] and -- with episode records, from the final_observation of the step before
         -- final_values[t - 1] straight into the slabs (no row copies), and the environment's step from actions[t];
         after step T a values-only launch gives last_values and final_values[T - 1]; then finish().  As bytes what the
@@ -488,7 +526,7 @@ class DeviceRollout(_Bookkeeping):
         the host."""
         sde = self._collecting(policy, sde_sample_freq)
         if sde:
-            policy.reset_noise(self.num_envs)
+            self._reset_noise(policy, None, sde_sample_freq)
             if self._env_actions is None:
                 self._env_actions = self._torch.zeros(self.num_envs, dtype=self._torch.float32, device=self.device)
         if self._lstm:
@@ -497,8 +535,8 @@ class DeviceRollout(_Bookkeeping):
         for _ in range(self.n_steps):
             t = self._next_step()
             final_out = None if final_obs is None else self.final_values[self._bootstrap_step()]
-            if sde and self._resample(t, sde_sample_freq):
-                policy.reset_noise(self.num_envs)
+            if sde:
+                self._reset_noise(policy, t, sde_sample_freq)
             out = (self.actions[t], self.values[t], self.log_probs[t], final_out)
             if sde:
                 out += (self._env_actions,)
