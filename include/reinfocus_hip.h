@@ -1347,7 +1347,8 @@ int rf_lstm_critic_sde_update(rf_ctx *ctx, const rf_lstm_critic_desc *desc, cons
  *     is skipped and flagged in its own stats[7] exactly as step 8 says; the other groups are untouched by it.
  * Limits: G 1 .. RF_POPULATION_MAX_GROUPS (the grid's y / z limit), m >= 1, G m <= 2^30 (G N alike), B as in G4.
  * A normaliser and GAE discounts per group: "population view", above.  The Gaussian head: "population sde", below.  Out of
- * scope: the lstm heads, groups that differ in architecture, m, T or B.
+ * scope: groups that differ in architecture, m, T or B.  The recurrent head: "population lstm", below (the lstm-sde head in
+ * a population is out of scope).
  *
  *   rf_policy_forward_grouped      rf_policy_forward over (G, m) in place of n: one launch, grid (ceil(m / 8), nets, G);
  *                                  the same outputs over G m rows, the same refusals (with d_gens, a device array, in
@@ -1424,6 +1425,65 @@ int /* population sde */ rf_sde_update_grouped(rf_ctx *ctx, const rf_policy_desc
         const rf_ppo_hyper *d_hyper, float *d_params, void *d_state, void *d_workspace, const float *d_obs,
         const float *d_actions, const float *d_old_log_probs, const float *d_advantages, const float *d_returns, int B,
         const long long *d_index, float *d_stats, void *caller_stream);
+
+/* ---- population lstm: a population of recurrent PPO learners (the Categorical head on the LSTM, either critic) -------------
+ * The reference's hyper-parameter search has a ppo_lstm sampler next to ppo, 20 trials side by side with n_envs 8, and two
+ * of its four training configurations are recurrent.  Written as deltas of "population", "lstm policy", "lstm update" and
+ * "lstm critic": the arithmetic of a group is exactly that of rf_lstm_forward / rf_lstm_ppo_update (rf_lstm_critic_forward /
+ * rf_lstm_critic_ppo_update with desc->critic == RF_LSTM_CRITIC_LINEAR); only addressing changes.  numpy twins
+ * environments/population.py (G of lstm.LstmPolicy / lstm_learner.LstmLearner over slices), kernels
+ * lstm_forward_kernel<false, kLinear, true> (csrc/rf_lstm.h), lstm_ppo_forward_kernel<kLinear, true>,
+ * lstm_ppo_mlp_kernel<false, true>, lstm_ppo_bptt_kernel<true>, lstm_ppo_gradient_kernel<false, kLinear, true>,
+ * lstm_ppo_norm_kernel<true> (csrc/rf_lstm_ppo.h) and ppo_adam_kernel<true> (csrc/rf_ppo.h).
+ *
+ *  L1 G1, G2, G3, G5, G6 and G7 of "population" hold unchanged, with the P of rf_lstm_params_size /
+ *     rf_lstm_critic_params_size and the workspace of rf_lstm_ppo_workspace_size / rf_lstm_critic_ppo_workspace_size;
+ *     d_episode_starts of a forward is uint8 [G m], group g's rows [g m, (g + 1) m).
+ *  L2 State.  The state keeps its single form float32 [2][2][n][H] with n = G m: group g owns rows [g m, (g + 1) m) of EACH
+ *     of the four [n][H] planes -- its rows are not one contiguous piece.  Element (net, which, e, unit) of group g is
+ *     ((net * 2 + which) * n + g m + e) * H + unit.  d_state_out is NULL, d_state_in itself (in place) or a range that
+ *     does not overlap it.  With the linear critic the pi block stores both halves, as "lstm critic" says.
+ *  L3 Update rows.  The five arrays of flat() have G N rows, N = m T, group g owning rows [g N, (g + 1) N) (G4).
+ *     d_episode_starts is uint8 [T + 1][n] and d_lstm_states float32 [T + 1][2][2][n][H] in their single form: environment e
+ *     of group g is column g m + e, the row stride of episode_starts is n and the plane stride of lstm_states n H.
+ *  L4 First rows.  d_firsts is int32 [G] on the device: group g's minibatch is rows (firsts[g] + b) mod N, b < B, LOCAL to
+ *     the group -- they wrap inside the group, and the sequence rule of "lstm update" runs over (T, m) with the group's
+ *     columns.  B is one value for all groups.  The host cannot check firsts[g]: the kernels clamp it into 0 .. N - 1, and a
+ *     value outside sets the group's validity flag, so the group is skipped with RF_PPO_INVALID in its stats[7] exactly as
+ *     an invalid index is in rf_ppo_update_grouped; the other groups are untouched by it.
+ * Limits: G 1 .. RF_POPULATION_MAX_GROUPS, m >= 1, T >= 1, G m <= 2^30 (G m T alike), 1 <= B <= min(m T,
+ * RF_PPO_MAX_BATCH); the desc as "lstm policy" / "lstm critic".  Out of scope: the lstm-sde head in a population; groups
+ * that differ in architecture, critic, m, T or B.
+ *
+ *   rf_lstm_forward_grouped             rf_lstm_forward / rf_lstm_critic_forward over (G, m) in place of n: one launch, grid
+ *                                       (ceil(m / 8), nets, G); the same outputs over G m rows, the same refusals (with
+ *                                       d_gens, a device array, in place of gen, needed when the call samples), G or m
+ *                                       outside the limits, and a capturing caller stream.
+ *   rf_lstm_ppo_grouped_state_size      G (32 + 8 P) bytes; 0 for a desc outside the limits, G outside its limits, m < 1 or
+ *                                       a NULL ctx
+ *   rf_lstm_ppo_grouped_workspace_size  G times the ungrouped workspace of B; 0 if that is, for G outside its limits, m < 1,
+ *                                       T < 1 or B > min(m T, RF_PPO_MAX_BATCH)
+ *   rf_lstm_ppo_update_grouped          rf_lstm_ppo_update / rf_lstm_critic_ppo_update over (G, m, T): six launches whatever
+ *                                       G is; the refusals of rf_lstm_ppo_update and rf_ppo_update_grouped over the G-fold
+ *                                       arrays (a capturing caller stream and overlapping outputs among them), a NULL
+ *                                       d_firsts.
+ * A refused call returns RF_ERR_INVALID, enqueues nothing and dereferences no device pointer.
+ * (The tag between return type and name: several tests take a census of the rf_lstm_ entry points by their plain
+ * declarations, and these four are not among them.) */
+int /* population lstm */ rf_lstm_forward_grouped(rf_ctx *ctx, const rf_lstm_critic_desc *desc, int G, int m,
+        const float *d_params, const float *d_obs, const uint8_t *d_episode_starts, const float *d_final_obs,
+        const float *d_state_in, float *d_state_out, const unsigned long long *d_gens /* [G][4] */,
+        unsigned long long consumed, int flags, long long *d_actions, float *d_log_probs, float *d_values,
+        float *d_final_values, float *d_logits, void *caller_stream);
+unsigned long long /* population lstm */ rf_lstm_ppo_grouped_state_size(rf_ctx *ctx, const rf_lstm_critic_desc *desc, int G,
+        int m);
+unsigned long long /* population lstm */ rf_lstm_ppo_grouped_workspace_size(rf_ctx *ctx, const rf_lstm_critic_desc *desc,
+        int G, int m, int T, int B);
+int /* population lstm */ rf_lstm_ppo_update_grouped(rf_ctx *ctx, const rf_lstm_critic_desc *desc, int G, int m, int T,
+        const rf_ppo_hyper *d_hyper, float *d_params, void *d_state, void *d_workspace, const float *d_observations,
+        const long long *d_actions, const float *d_log_probs, const float *d_advantages, const float *d_returns,
+        const uint8_t *d_episode_starts, const float *d_lstm_states, const int *d_firsts /* [G] */, int B,
+        float *d_stats, void *caller_stream);
 
 #ifdef __cplusplus
 }

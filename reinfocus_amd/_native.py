@@ -143,6 +143,10 @@ SYMBOLS = (
     "rf_lstm_critic_sde_state_size",
     "rf_lstm_critic_sde_workspace_size",
     "rf_lstm_critic_sde_update",
+    "rf_lstm_forward_grouped",
+    "rf_lstm_ppo_grouped_state_size",
+    "rf_lstm_ppo_grouped_workspace_size",
+    "rf_lstm_ppo_update_grouped",
     "rf_render_kernel_name",
     "rf_pixels_rendered",
     "rf_allocations_poisoned",
@@ -462,6 +466,14 @@ def load():
         for name in ("state_size", "workspace_size", "update"):
             ours, theirs = getattr(lib, f"rf_lstm_critic_{head or 'ppo_'}{name}"), getattr(lib, f"rf_lstm_{head or 'ppo_'}{name}")
             ours.restype, ours.argtypes = theirs.restype, theirs.argtypes
+    lib.rf_lstm_forward_grouped.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, ctypes.c_ulonglong, i32, vp, vp, vp,
+                                            vp, vp, vp]
+    lib.rf_lstm_ppo_grouped_state_size.restype = ctypes.c_ulonglong
+    lib.rf_lstm_ppo_grouped_state_size.argtypes = [vp, vp, i32, i32]
+    lib.rf_lstm_ppo_grouped_workspace_size.restype = ctypes.c_ulonglong
+    lib.rf_lstm_ppo_grouped_workspace_size.argtypes = [vp, vp, i32, i32, i32, i32]
+    lib.rf_lstm_ppo_update_grouped.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp,
+                                               vp]
     lib.rf_render_kernel_name.restype = ctypes.c_char_p
     lib.rf_render_kernel_name.argtypes = [vp]
     lib.rf_pixels_rendered.restype = ctypes.c_ulonglong
@@ -920,6 +932,44 @@ class Context:
         rc = self._lib.rf_sde_update_grouped(self._h, ctypes.byref(PolicyDesc(*desc)), groups, per_group, steps, hyper_ptr,
                                              params_ptr, state_ptr, workspace_ptr, obs_ptr, actions_ptr, old_log_probs_ptr,
                                              advantages_ptr, returns_ptr, batch, index_ptr, stats_ptr, stream)
+        if rc != 0:
+            _check(rc)
+
+    # --- population lstm (rf_lstm_*_grouped): the recurrent policy and update below over G groups of m environments; `desc`
+    # is the eleven integers of rf_lstm_critic_desc (either critic) ---------------------------------------------------------
+    def lstm_forward_grouped(self, desc, groups, per_group, params_ptr, obs_ptr, episode_starts_ptr, final_obs_ptr,
+                             state_in_ptr, state_out_ptr, gens_ptr, consumed, flags, actions_ptr, log_probs_ptr, values_ptr,
+                             final_values_ptr, logits_ptr, stream):
+        """rf_lstm_forward_grouped: lstm_forward over groups x per_group rows, parameters [groups][P], the state in its single
+        form [2][2][groups x per_group][H]; row e of group g takes draw consumed + e of generator g of the device table
+        gens_ptr (uint64 [groups][4]; None for a deterministic call).  Only enqueues."""
+        rc = self._lib.rf_lstm_forward_grouped(self._h, ctypes.byref(LstmCriticDesc(*desc)), groups, per_group, params_ptr,
+                                               obs_ptr, episode_starts_ptr, final_obs_ptr, state_in_ptr, state_out_ptr,
+                                               gens_ptr, consumed, flags, actions_ptr, log_probs_ptr, values_ptr,
+                                               final_values_ptr, logits_ptr, stream)
+        if rc != 0:
+            _check(rc)
+
+    def lstm_ppo_grouped_state_size(self, desc, groups, per_group):
+        """rf_lstm_ppo_grouped_state_size: bytes of the optimizer states of `groups` recurrent networks; 0 if refused."""
+        return int(self._lib.rf_lstm_ppo_grouped_state_size(self._h, ctypes.byref(LstmCriticDesc(*desc)), groups, per_group))
+
+    def lstm_ppo_grouped_workspace_size(self, desc, groups, per_group, steps, batch):
+        """rf_lstm_ppo_grouped_workspace_size: bytes of the workspaces of `groups` groups for minibatches of `batch` out of
+        per_group x steps rows each; 0 if refused."""
+        return int(self._lib.rf_lstm_ppo_grouped_workspace_size(self._h, ctypes.byref(LstmCriticDesc(*desc)), groups,
+                                                                per_group, steps, batch))
+
+    def lstm_ppo_update_grouped(self, desc, groups, per_group, steps, hyper_ptr, params_ptr, state_ptr, workspace_ptr,
+                                observations_ptr, actions_ptr, log_probs_ptr, advantages_ptr, returns_ptr,
+                                episode_starts_ptr, lstm_states_ptr, firsts_ptr, batch, stats_ptr, stream):
+        """rf_lstm_ppo_update_grouped: one recurrent minibatch update of every group, six launches on `stream`; group g's
+        rows are (firsts[g] + b) mod (per_group x steps), b < batch, of its piece of the flat arrays (firsts_ptr: device
+        int32 [groups]), hyper_ptr the device array of `groups` rf_ppo_hyper, stats_ptr float32 [groups][8].  Only enqueues."""
+        rc = self._lib.rf_lstm_ppo_update_grouped(self._h, ctypes.byref(LstmCriticDesc(*desc)), groups, per_group, steps,
+                                                  hyper_ptr, params_ptr, state_ptr, workspace_ptr, observations_ptr,
+                                                  actions_ptr, log_probs_ptr, advantages_ptr, returns_ptr, episode_starts_ptr,
+                                                  lstm_states_ptr, firsts_ptr, batch, stats_ptr, stream)
         if rc != 0:
             _check(rc)
 

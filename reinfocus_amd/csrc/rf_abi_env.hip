@@ -919,39 +919,6 @@ int env_step_plan(rf_ctx *ctx, const T *host_actions, int *host_n_reset, const c
 
 // ---- device steps: rf_env_step_device, rf_env_reset_device (kernels: rf_env_io.h) -----------------------------------
 
-// A caller's array of `bytes` bytes: device memory of the context's GPU, aligned for its elements, and inside one
-// allocation -- asked of the runtime, never dereferenced.
-int check_device_array(const rf_ctx *ctx, const void *p, size_t bytes, size_t align, const char *what, const char *fn)
-{
-    hipPointerAttribute_t attr{};
-    const hipError_t e = hipPointerGetAttributes(&attr, p);
-    if (e != hipSuccess)
-        (void)hipGetLastError(); // (what the runtime says of a pointer it does not know)
-    RF_REQUIRE(e == hipSuccess && attr.type == hipMemoryTypeDevice && attr.device == ctx->device,
-               "%s: %s is not device memory of the context's GPU %d", fn, what, ctx->device);
-    RF_REQUIRE((uintptr_t)p % align == 0, "%s: %s is not aligned to %zu bytes", fn, what, align);
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) == hipSuccess)
-        RF_REQUIRE((const char *)p + bytes <= (const char *)base + size, "%s: %s has fewer than %zu bytes", fn, what, bytes);
-    else
-        (void)hipGetLastError();
-    return RF_OK;
-}
-
-// Calling a device form while the caller's stream is being captured is out of scope: the events below would become
-// nodes of the caller's graph, and the host bookkeeping would run once for any number of replays.
-int refuse_capturing(hipStream_t caller, const char *fn)
-{
-    hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
-    const hipError_t e = hipStreamIsCapturing(caller, &status);
-    if (e != hipSuccess)
-        (void)hipGetLastError();
-    RF_REQUIRE(e == hipSuccess && status == hipStreamCaptureStatusNone,
-               "%s: the caller's stream is being captured (a device step cannot be part of the caller's graph)", fn);
-    return RF_OK;
-}
-
 // The ctx's stream waits for what the caller's stream holds now / the caller's stream waits for what the ctx's holds
 // now: ordering by events only, no host synchronisation.
 int wait_for_caller(rf_ctx *ctx, hipStream_t caller)
@@ -1142,13 +1109,6 @@ int env_reset_device(rf_ctx *ctx, float *d_obs, float *d_view_obs, void *caller_
     ctx->io_scene_pending = false;
     ctx->env_started = true;
     return RF_OK;
-}
-
-// [a, a + a_bytes) and [b, b + b_bytes) share a byte (addresses compared as integers, nothing dereferenced)
-bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + b_bytes && y < x + a_bytes;
 }
 
 } // namespace
@@ -2863,7 +2823,7 @@ static int lstm_forward_any(const char *fn, int critic, rf_ctx *ctx, const rf_ls
     hipLaunchKernelGGL(kernel, dim3(tiles, pi && vf ? 2u : 1u), dim3(rf::kPolicyThreads), 0,
                        (hipStream_t)caller_stream, layout, d_params, n, d_obs, d_episode_starts, d_final_obs, d_state_in,
                        d_state_out, words, sampled ? 1 : 0, pi ? 0 : 1, (int64_t *)d_actions, d_log_probs, d_values,
-                       d_final_values, d_logits, rf::LstmNoSde{});
+                       d_final_values, d_logits, rf::LstmNoSde{}, (const rf::PolicyGen *)nullptr, (uint64_t)0, 0);
     RF_HIP(hipGetLastError());
     return RF_OK;
 }
@@ -2998,7 +2958,8 @@ static int lstm_sde_forward_any(const char *fn, int critic, rf_ctx *ctx, const r
     hipLaunchKernelGGL(kernel, dim3(tiles, pi && vf ? 2u : 1u), dim3(rf::kPolicyThreads), 0,
                        (hipStream_t)caller_stream, layout, d_params, n, d_obs, d_episode_starts, d_final_obs, d_state_in,
                        d_state_out, rf::PolicyGen{}, 0, pi ? 0 : 1, d_actions, d_log_probs, d_values, d_final_values, d_mean,
-                       rf::LstmSde{sampled ? d_theta : nullptr, d_env_actions, d_sigma});
+                       rf::LstmSde{sampled ? d_theta : nullptr, d_env_actions, d_sigma}, (const rf::PolicyGen *)nullptr,
+                       (uint64_t)0, 0);
     RF_HIP(hipGetLastError());
     return RF_OK;
 }
@@ -3107,20 +3068,20 @@ static int lstm_update_any(const char *fn, bool sde, int critic, rf_ctx *ctx, co
     const auto forward = linear ? rf::lstm_ppo_forward_kernel<true> : rf::lstm_ppo_forward_kernel<false>;
     hipLaunchKernelGGL(forward, dim3((unsigned)B + (linear ? tiles : 0u), walks), threads, 0, caller, layout, work,
                        (const float *)d_params, ws, n_steps, num_envs, d_observations, d_episode_starts, d_lstm_states, first,
-                       B);
+                       B, (const int *)nullptr, 0);
     RF_HIP(hipGetLastError());
     hipLaunchKernelGGL(sde ? rf::lstm_ppo_mlp_kernel<true> : rf::lstm_ppo_mlp_kernel<false>, dim3(tiles, 2u), threads, 0,
                        caller, layout, work, hyper, (const float *)d_params, (const rf::PpoHeader *)d_state, ws, N, d_actions,
-                       d_log_probs, d_advantages, d_returns, first, B);
+                       d_log_probs, d_advantages, d_returns, first, B, (const rf::PpoHyper *)nullptr, (const int *)nullptr);
     RF_HIP(hipGetLastError());
-    hipLaunchKernelGGL(rf::lstm_ppo_bptt_kernel, dim3((unsigned)B, walks), threads, 0, caller, layout, work,
-                       (const float *)d_params, ws, n_steps, num_envs, d_episode_starts, first, B);
+    hipLaunchKernelGGL(rf::lstm_ppo_bptt_kernel<false>, dim3((unsigned)B, walks), threads, 0, caller, layout, work,
+                       (const float *)d_params, ws, n_steps, num_envs, d_episode_starts, first, B, (const int *)nullptr, 0);
     RF_HIP(hipGetLastError());
     const auto gradient = linear ? (sde ? rf::lstm_ppo_gradient_kernel<true, true> : rf::lstm_ppo_gradient_kernel<false, true>)
                                  : (sde ? rf::lstm_ppo_gradient_kernel<true> : rf::lstm_ppo_gradient_kernel<false>);
     hipLaunchKernelGGL(gradient, dim3(work.mlp.partials), threads, 0, caller, layout, work, ws, B, (const float *)d_params);
     RF_HIP(hipGetLastError());
-    hipLaunchKernelGGL(rf::lstm_ppo_norm_kernel, dim3(work.supers), dim3(rf::kLstmPpoGroup), 0, caller, work, ws);
+    hipLaunchKernelGGL(rf::lstm_ppo_norm_kernel<false>, dim3(work.supers), dim3(rf::kLstmPpoGroup), 0, caller, work, ws);
     RF_HIP(hipGetLastError());
     const unsigned slices = (layout.total + rf::kPpoAdamSlice - 1) / rf::kPpoAdamSlice;
     hipLaunchKernelGGL(rf::ppo_adam_kernel<false>, dim3(slices + 1u), threads, 0, caller, layout.total,

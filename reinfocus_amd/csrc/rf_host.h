@@ -13,8 +13,12 @@
 //                       and rf_lstm_forward (lstm_forward_kernel, rf_lstm.h)
 //                       and rf_lstm_ppo_update (the five kernels of rf_lstm_ppo.h, then rf_ppo.h's ppo_adam_kernel)
 //   rf_abi_snapshot.hip snapshots of a device-resident environment (rf_env_snapshot* / rf_env_restore*): copies only
+//   rf_abi_lstm_grouped.hip  "population lstm": rf_lstm_forward_grouped, rf_lstm_ppo_update_grouped and their size
+//                       functions -- the kGrouped instantiations of rf_lstm.h and rf_lstm_ppo.h, compiled apart from the
+//                       ungrouped ones of rf_abi_env.hip (profiles/population_lstm.md)
 //
-// Every kernel is defined in exactly one unit (the one that launches it); the units share only host functions.
+// Every kernel instantiation is defined in the unit that launches it (ppo_adam_kernel<true>, the last launch of both
+// grouped updates, in two: each has its own copy); the units share only host functions.
 #pragma once
 #include <cstring>
 
@@ -307,6 +311,47 @@ inline hipError_t host_malloc(void **p, size_t bytes)
     if (e == hipSuccess && bytes && poison_allocations())
         memset(*p, 0xA5, bytes);
     return e;
+}
+
+// ---- what the entry points over caller-owned device arrays share (rf_abi_env.hip, rf_abi_lstm_grouped.hip) ----------------
+// A caller's array of `bytes` bytes: device memory of the context's GPU, aligned for its elements, and inside one
+// allocation -- asked of the runtime, never dereferenced.
+inline int check_device_array(const rf_ctx *ctx, const void *p, size_t bytes, size_t align, const char *what, const char *fn)
+{
+    hipPointerAttribute_t attr{};
+    const hipError_t e = hipPointerGetAttributes(&attr, p);
+    if (e != hipSuccess)
+        (void)hipGetLastError(); // (what the runtime says of a pointer it does not know)
+    RF_REQUIRE(e == hipSuccess && attr.type == hipMemoryTypeDevice && attr.device == ctx->device,
+               "%s: %s is not device memory of the context's GPU %d", fn, what, ctx->device);
+    RF_REQUIRE((uintptr_t)p % align == 0, "%s: %s is not aligned to %zu bytes", fn, what, align);
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) == hipSuccess)
+        RF_REQUIRE((const char *)p + bytes <= (const char *)base + size, "%s: %s has fewer than %zu bytes", fn, what, bytes);
+    else
+        (void)hipGetLastError();
+    return RF_OK;
+}
+
+// Calling a device form while the caller's stream is being captured is out of scope: the events below would become
+// nodes of the caller's graph, and the host bookkeeping would run once for any number of replays.
+inline int refuse_capturing(hipStream_t caller, const char *fn)
+{
+    hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
+    const hipError_t e = hipStreamIsCapturing(caller, &status);
+    if (e != hipSuccess)
+        (void)hipGetLastError();
+    RF_REQUIRE(e == hipSuccess && status == hipStreamCaptureStatusNone,
+               "%s: the caller's stream is being captured (a device step cannot be part of the caller's graph)", fn);
+    return RF_OK;
+}
+
+// [a, a + a_bytes) and [b, b + b_bytes) share a byte (addresses compared as integers, nothing dereferenced)
+inline bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + b_bytes && y < x + a_bytes;
 }
 
 } // namespace rfh

@@ -211,17 +211,42 @@ __device__ __forceinline__ void lstm_linear_tile(const float *__restrict__ param
 // then float32 [n] (the raw actions) and `logits` receives the mean.
 // kLinear: "lstm critic" (L.critic == kLstmCriticLinear): the vf block is the linear layer, the pi block stores both halves
 // of the state; a launch asks for the vf block only where a value is wanted.
-template <bool kSde, bool kLinear = false>
+// kGrouped ("population lstm"): grid (ceil(n / kPolicyTile), nets, G) as policy_forward_kernel<true>, n the environments
+// of ONE group.  Block (., ., g) is a block of the ungrouped kernel over group g's rows -- rows [g n, (g + 1) n) of obs,
+// final_obs, starts and every output -- with the parameters params + g P and the generator gens[g], whose draw number
+// consumed + (row - g n) the row takes.  The state keeps its single form [2][2][lanes][H] with lanes = G n: a group's rows
+// are NOT one piece of it, each of the four planes contributes rows [g n, (g + 1) n), so the state is reached as
+// (plane stride `lanes`, environment lane0 + e) and its pointers do not move.  Ungrouped, lanes is n, lane0 the constant
+// 0, gens / consumed / lanes are unused and the code is what it was without them.
+template <bool kSde, bool kLinear = false, bool kGrouped = false>
 __global__ __launch_bounds__(kPolicyThreads) void lstm_forward_kernel(
     LstmLayout L, const float *__restrict__ params, int n, const float *__restrict__ obs,
     const uint8_t *__restrict__ starts, const float *__restrict__ final_obs /* or null */, const float *state_in,
     float *state_out /* null, state_in itself, or a range that does not overlap it */, PolicyGen gen, int sampled,
     int first_net, typename std::conditional<kSde, float, int64_t>::type *__restrict__ actions,
     float *__restrict__ log_probs, float *__restrict__ values, float *__restrict__ final_values,
-    float *__restrict__ logits, typename LstmSdeOf<kSde>::type sde)
+    float *__restrict__ logits, typename LstmSdeOf<kSde>::type sde, const PolicyGen *__restrict__ gens /* [G] or null */,
+    uint64_t consumed, int lanes_all)
 {
+    static_assert(!(kSde && kGrouped), "the lstm-sde head has no population yet");
     const float *__restrict__ theta = sde.theta;
     float *__restrict__ env_actions = sde.env_actions, *__restrict__ sigma = sde.sigma;
+    if (kGrouped) { // (block-uniform: every row pointer moves to the group's piece; null stays null; the state stays)
+        const size_t g = blockIdx.z, row = g * (size_t)n, cell = row * (size_t)L.obs_width;
+        params += g * (size_t)L.total;
+        obs += cell;
+        starts += row;
+        final_obs = final_obs != nullptr ? final_obs + cell : nullptr;
+        actions = actions != nullptr ? actions + row : nullptr;
+        log_probs = log_probs != nullptr ? log_probs + row : nullptr;
+        values = values != nullptr ? values + row : nullptr;
+        final_values = final_values != nullptr ? final_values + row : nullptr;
+        logits = logits != nullptr ? logits + row * (size_t)L.mlp.n_actions : nullptr;
+        if (sampled)
+            gen = gens[g];
+    }
+    const int lanes = kGrouped ? lanes_all : n;                    // the state's plane stride
+    const int lane0 = kGrouped ? (int)blockIdx.z * n : 0;          // the state's environment of the group's row 0
     __shared__ __align__(16) float s_x[kPolicyMaxWidth][kPolicyTile];      // the tile's observations, [k][environment]
     __shared__ __align__(16) float s_act[2][kPolicyMaxWidth][kPolicyTile]; // [1]: h; [0]: h', then the MLP's activations
     __shared__ float s_logit[kPolicyTile][kPolicyMaxActions];
@@ -250,7 +275,7 @@ __global__ __launch_bounds__(kPolicyThreads) void lstm_forward_kernel(
                 const int e = i / H, k = i - e * H, env = e0 + e;
                 // an episode start replaces the state by +0: a select, so no NaN or inf of a dead state survives it
                 const bool kept = env < n && (pass == 1 || starts[env] == 0);
-                s_act[1][k][e] = kept ? state_in[lstm_state_at(net, 0, n, H, env, k)] : 0.0f;
+                s_act[1][k][e] = kept ? state_in[lstm_state_at(net, 0, lanes, H, lane0 + env, k)] : 0.0f;
             }
         __syncthreads();
         if (kLinear && net == 1) {
@@ -271,16 +296,16 @@ __global__ __launch_bounds__(kPolicyThreads) void lstm_forward_kernel(
             for (int e = 0; e < kPolicyTile; ++e) {
                 const int env = e0 + e;
                 const bool kept = env < n && (pass == 1 || starts[env] == 0);
-                const float c = kept ? state_in[lstm_state_at(net, 1, n, H, env, tid)] : 0.0f;
+                const float c = kept ? state_in[lstm_state_at(net, 1, lanes, H, lane0 + env, tid)] : 0.0f;
                 float h1, c1;
                 lstm_cell(acc[0][e], acc[1][e], acc[2][e], acc[3][e], c, &h1, &c1);
                 s_act[0][tid][e] = h1;
                 if (pass == 0 && state_out != nullptr && env < n) {
-                    state_out[lstm_state_at(net, 0, n, H, env, tid)] = policy_canonical(h1);
-                    state_out[lstm_state_at(net, 1, n, H, env, tid)] = policy_canonical(c1);
+                    state_out[lstm_state_at(net, 0, lanes, H, lane0 + env, tid)] = policy_canonical(h1);
+                    state_out[lstm_state_at(net, 1, lanes, H, lane0 + env, tid)] = policy_canonical(c1);
                     if constexpr (kLinear) { // (net == 0: sb3-contrib's lstm_states_vf = lstm_states_pi; nothing reads it)
-                        state_out[lstm_state_at(1, 0, n, H, env, tid)] = policy_canonical(h1);
-                        state_out[lstm_state_at(1, 1, n, H, env, tid)] = policy_canonical(c1);
+                        state_out[lstm_state_at(1, 0, lanes, H, lane0 + env, tid)] = policy_canonical(h1);
+                        state_out[lstm_state_at(1, 1, lanes, H, lane0 + env, tid)] = policy_canonical(c1);
                     }
                 }
             }
@@ -343,7 +368,7 @@ __global__ __launch_bounds__(kPolicyThreads) void lstm_forward_kernel(
             __syncthreads();
             if (net == 0 && actions != nullptr && tid < kPolicyTile && e0 + tid < n) {
                 const int env = e0 + tid;
-                const double u = sampled ? policy_draw(gen.word, (uint64_t)env) : 0.0;
+                const double u = sampled ? policy_draw(gen.word, kGrouped ? consumed + (uint64_t)env : (uint64_t)env) : 0.0;
                 int64_t action;
                 float log_prob;
                 policy_head(&s_logit[tid][0], L.mlp.n_actions, !sampled, u, &s_sum[tid][0], &action, &log_prob);

@@ -134,29 +134,80 @@ RF_HD int lstm_ppo_row(int first, int b, int N)
     return r >= N ? r - N : r;
 }
 
-// Row b starts a sequence: b == 0, or t == 0 (the environment changes), or episode_starts[t][e] != 0
-RF_HD bool lstm_ppo_is_start(const uint8_t *starts, int T, int n, int first, int b)
+// "population lstm": where the n environments of ONE group lie among the `lanes` of the slabs the update reads --
+// episode_starts [T + 1][lanes] and lstm_states [T + 1][2][2][lanes][H] keep their single form, so environment e of the
+// group is lane lane0 + e and the row and plane stride is lanes, not n.  Ungrouped: {n, 0}.
+struct LstmLanes {
+    int lanes, lane0;
+};
+
+// group g of G groups of m environments each
+RF_HD LstmLanes lstm_group_lanes(int G, int m, int g)
+{
+    return LstmLanes{G * m, g * m};
+}
+
+// firsts[g] as the kernels take it: clamped into 0 .. N - 1 (a value outside sets the group's skip flag)
+RF_HD int lstm_ppo_first(int raw, int N)
+{
+    return raw < 0 ? 0 : (raw >= N ? N - 1 : raw);
+}
+
+// Row b starts a sequence: b == 0, or t == 0 (the environment changes), or episode_starts[t][e] != 0.  Rows are local to
+// the group: they wrap modulo T n, n the group's environments.
+RF_HD bool lstm_ppo_is_start(const uint8_t *starts, int T, int n, int first, int b, LstmLanes at)
 {
     if (b == 0)
         return true;
     const int r = lstm_ppo_row(first, b, T * n);
     const int e = r / T, t = r - e * T;
-    return t == 0 || starts[(size_t)t * (size_t)n + (size_t)e] != 0;
+    return t == 0 || starts[(size_t)t * (size_t)at.lanes + (size_t)(at.lane0 + e)] != 0;
+}
+
+RF_HD bool lstm_ppo_is_start(const uint8_t *starts, int T, int n, int first, int b)
+{
+    return lstm_ppo_is_start(starts, T, n, first, b, LstmLanes{n, 0});
 }
 
 // One past the last row of the sequence that starts at row b
-RF_HD int lstm_ppo_end(const uint8_t *starts, int T, int n, int first, int b, int B)
+RF_HD int lstm_ppo_end(const uint8_t *starts, int T, int n, int first, int b, int B, LstmLanes at)
 {
     int end = b + 1;
-    while (end < B && !lstm_ppo_is_start(starts, T, n, first, end))
+    while (end < B && !lstm_ppo_is_start(starts, T, n, first, end, at))
         ++end;
     return end;
+}
+
+RF_HD int lstm_ppo_end(const uint8_t *starts, int T, int n, int first, int b, int B)
+{
+    return lstm_ppo_end(starts, T, n, first, b, B, LstmLanes{n, 0});
 }
 
 // Element (t, net, which: 0 h / 1 c, env, unit) of the rollout's lstm_states [T + 1][2][2][n][H]
 RF_HD size_t lstm_ppo_state_at(int t, int net, int which, int n, int H, int env, int unit)
 {
     return (size_t)t * lstm_state_floats(n, H) + lstm_state_at(net, which, n, H, env, unit);
+}
+
+// "population lstm": what rf_lstm_ppo_grouped_state_size and rf_lstm_ppo_grouped_workspace_size return for a ctx (0:
+// refused): G times the ungrouped sizes, for minibatches of B out of the m T rows of a group
+RF_HD unsigned long long lstm_population_state_bytes(const rf_lstm_critic_desc &d, int G, int m)
+{
+    LstmLayout L;
+    if (!lstm_layout_nets(d.lstm, L, false, d.critic) || !population_rows(G, m))
+        return 0;
+    return (unsigned long long)G * (4ull * kPpoStateHeader + 8ull * L.total);
+}
+
+RF_HD unsigned long long lstm_population_workspace_bytes(const rf_lstm_critic_desc &d, int G, int m, int T, int B)
+{
+    LstmLayout L;
+    LstmPpoWork W;
+    if (!lstm_layout_nets(d.lstm, L, false, d.critic) || m < 1 || T < 1
+        || !population_rows(G, (long long)m * (long long)T) || (long long)B > (long long)m * (long long)T
+        || !lstm_ppo_work(L, B, W))
+        return 0;
+    return (unsigned long long)G * 4ull * W.total;
 }
 
 // lstm_cell with the gate values kept: gate[0 .. 3] = i, f, g, o; the same operations, so the same h' and c'
@@ -358,11 +409,30 @@ __device__ __forceinline__ void lstm_gates_row(const float *__restrict__ params,
 
 // kLinear: "lstm critic" -- the grid is B + ceil(B / kPolicyTile) blocks by 1: block b < B walks the pi sequence that
 // starts at row b, block B + i takes rows [8 i, 8 i + 8) of the vf net's linear layer
-template <bool kLinear = false>
+// kGrouped ("population lstm", all five kernels here and ppo_adam_kernel<true>): a group dimension on the grid (the last
+// one the kernel does not use yet).  A block of group g is a block of the ungrouped kernel over the group's own N = n T
+// rows (rows [g N, (g + 1) N) of flat()'s arrays; n the environments of ONE group), with the parameters params + g P, the
+// optimizer state + g (kPpoStateHeader + 2 P) floats, the workspace ws + g W.total (W.total is even: float64 data stays
+// aligned), hyper-parameters hypers[g], stats + 8 g and its own first row firsts[g], read from a device table and clamped
+// into 0 .. N - 1 (lstm_ppo_first; lstm_ppo_mlp_kernel flags a value outside).  Rows are local to the group and wrap inside
+// it; episode_starts and lstm_states keep their single form over all G n lanes and are reached through LstmLanes, their
+// pointers do not move.  No block reads what a block of another group writes.  Ungrouped, firsts / lanes_all (and hypers)
+// are unused and the code is what it was without them.
+template <bool kLinear = false, bool kGrouped = false>
 __global__ __launch_bounds__(kPpoThreads) void lstm_ppo_forward_kernel(
     LstmLayout L, LstmPpoWork W, const float *__restrict__ params, float *__restrict__ ws, int T, int n,
-    const float *__restrict__ obs, const uint8_t *__restrict__ starts, const float *__restrict__ states, int first, int B)
+    const float *__restrict__ obs, const uint8_t *__restrict__ starts, const float *__restrict__ states, int first, int B,
+    const int *__restrict__ firsts /* [G] or null */, int lanes_all)
 {
+    LstmLanes at{n, 0};
+    if (kGrouped) { // (block-uniform)
+        const size_t g = blockIdx.z;
+        params += g * (size_t)L.total;
+        ws += g * (size_t)W.total;
+        obs += g * (size_t)T * (size_t)n * (size_t)L.obs_width;
+        first = lstm_ppo_first(firsts[g], T * n);
+        at = LstmLanes{lanes_all, (int)blockIdx.z * n};
+    }
     if constexpr (kLinear) {
         if ((int)blockIdx.x >= B) { // (block-uniform)
             __shared__ __align__(16) float s_in[kPolicyMaxWidth][kPolicyTile];  // the tile's observations, [k][row]
@@ -383,19 +453,19 @@ __global__ __launch_bounds__(kPpoThreads) void lstm_ppo_forward_kernel(
     __shared__ float s_x[kPolicyMaxWidth];
     __shared__ float s_h[kPolicyMaxWidth];
     const int b0 = (int)blockIdx.x, net = (int)blockIdx.y, tid = threadIdx.x;
-    if (!lstm_ppo_is_start(starts, T, n, first, b0)) // (block-uniform)
+    if (!lstm_ppo_is_start(starts, T, n, first, b0, at)) // (block-uniform)
         return;
-    const int end = lstm_ppo_end(starts, T, n, first, b0, B);
+    const int end = lstm_ppo_end(starts, T, n, first, b0, B, at);
     const int D = L.obs_width, H = L.hidden, N = T * n;
     float c = 0.0f;
     {
         const int r = lstm_ppo_row(first, b0, N);
         const int e = r / T, t = r - e * T;
         // an episode start replaces the stored state by +0: a select, so no NaN or inf of a dead state enters
-        const bool kept = starts[(size_t)t * (size_t)n + (size_t)e] == 0;
+        const bool kept = starts[(size_t)t * (size_t)at.lanes + (size_t)(at.lane0 + e)] == 0;
         if (tid < H) {
-            s_h[tid] = kept ? states[lstm_ppo_state_at(t, net, 0, n, H, e, tid)] : 0.0f;
-            c = kept ? states[lstm_ppo_state_at(t, net, 1, n, H, e, tid)] : 0.0f;
+            s_h[tid] = kept ? states[lstm_ppo_state_at(t, net, 0, at.lanes, H, at.lane0 + e, tid)] : 0.0f;
+            c = kept ? states[lstm_ppo_state_at(t, net, 1, at.lanes, H, at.lane0 + e, tid)] : 0.0f;
         }
     }
     for (int b = b0; b < end; ++b) {
@@ -470,12 +540,29 @@ __device__ __forceinline__ void lstm_ppo_back_input_tile(const float *__restrict
 
 // kSde: the Gaussian head of "lstm sde update" (L from lstm_sde_layout; actions float32 [N], the raw ones) in place of the
 // Categorical one (actions int64 [N]), as ppo_backward_kernel<kSde>
-template <bool kSde>
+// kGrouped: grid (ceil(B / 8), 2, G); N is the rows of ONE group; `header` is the first group's
+template <bool kSde, bool kGrouped = false>
 __global__ __launch_bounds__(kPpoThreads) void lstm_ppo_mlp_kernel(
     LstmLayout L, LstmPpoWork W, PpoHyper hy, const float *__restrict__ params, const PpoHeader *__restrict__ header,
     float *__restrict__ ws, int N, const void *__restrict__ actions_any, const float *__restrict__ old_log_probs,
-    const float *__restrict__ advantages, const float *__restrict__ returns, int first, int B)
+    const float *__restrict__ advantages, const float *__restrict__ returns, int first, int B,
+    const PpoHyper *__restrict__ hypers /* [G] or null */, const int *__restrict__ firsts /* [G] or null */)
 {
+    static_assert(!(kSde && kGrouped), "the lstm-sde head has no population yet");
+    int outside = 0; // (kGrouped: firsts[g] was not a row of the group -- the update is skipped and flagged)
+    if (kGrouped) {  // (block-uniform)
+        const size_t g = blockIdx.z, row = g * (size_t)N;
+        hy = hypers[g];
+        params += g * (size_t)L.total;
+        header = reinterpret_cast<const PpoHeader *>(reinterpret_cast<const float *>(header)
+                                                     + g * ((size_t)kPpoStateHeader + 2 * (size_t)L.total));
+        ws += g * (size_t)W.total;
+        actions_any = static_cast<const int64_t *>(actions_any) + row;
+        old_log_probs += row, advantages += row, returns += row;
+        const int raw = firsts[g];
+        first = lstm_ppo_first(raw, N);
+        outside = raw != first;
+    }
     const int64_t *__restrict__ actions = static_cast<const int64_t *>(actions_any); // (!kSde)
     const float *__restrict__ raw_actions = static_cast<const float *>(actions_any); // (kSde)
     __shared__ __align__(16) float s_act[2][kPolicyMaxWidth][kPolicyTile];   // h' / activations, [k][sample]
@@ -493,7 +580,7 @@ __global__ __launch_bounds__(kPpoThreads) void lstm_ppo_mlp_kernel(
     const bool normalise = hy.normalize != 0 && B > 1;
     if (net == 0) { // (block-uniform)
         const int size = ppo_pow2(B);
-        int bad = 0;
+        int bad = kGrouped ? outside : 0;
         for (int b = tid; b < size; b += kPpoThreads) {
             double a = 0.0;
             if (b < B) {
@@ -608,17 +695,31 @@ __global__ __launch_bounds__(kPpoThreads) void lstm_ppo_mlp_kernel(
     ppo_store_tile(ws + W.dh[net], s_act[0], H, b0, B, tid);
 }
 
+// kGrouped: the forward kernel's grid rule, (B, walks, G)
+template <bool kGrouped = false>
 __global__ __launch_bounds__(kPpoThreads) void lstm_ppo_bptt_kernel(LstmLayout L, LstmPpoWork W,
                                                                     const float *__restrict__ params,
                                                                     float *__restrict__ ws, int T, int n,
-                                                                    const uint8_t *__restrict__ starts, int first, int B)
+                                                                    const uint8_t *__restrict__ starts, int first, int B,
+                                                                    const int *__restrict__ firsts /* [G] or null */,
+                                                                    int lanes_all)
 {
+    LstmLanes at{n, 0};
+    if (kGrouped) { // (block-uniform)
+        const size_t g = blockIdx.z;
+        ws += g * (size_t)W.total;
+        first = lstm_ppo_first(firsts[g], T * n);
+        at = LstmLanes{lanes_all, (int)blockIdx.z * n};
+    }
+    // (the group's parameters are reached as params + group_params below: moving `params` itself here took the grouped
+    // kernel from 71 to 90 VGPRs and from 7 to 5 waves per SIMD)
+    const size_t group_params = kGrouped ? (size_t)blockIdx.z * (size_t)L.total : (size_t)0;
     __shared__ float s_da[4 * kPolicyMaxWidth]; // the row's deltas, [q][j]
     __shared__ float s_dh[kPolicyMaxWidth];     // dh_rec of the row
     const int b0 = (int)blockIdx.x, net = (int)blockIdx.y, tid = threadIdx.x;
-    if (!lstm_ppo_is_start(starts, T, n, first, b0)) // (block-uniform)
+    if (!lstm_ppo_is_start(starts, T, n, first, b0, at)) // (block-uniform)
         return;
-    const int end = lstm_ppo_end(starts, T, n, first, b0, B);
+    const int end = lstm_ppo_end(starts, T, n, first, b0, B, at);
     const int H = L.hidden;
     float dc_next = 0.0f;
     if (tid < H)
@@ -641,18 +742,24 @@ __global__ __launch_bounds__(kPpoThreads) void lstm_ppo_bptt_kernel(LstmLayout L
             break;
         __syncthreads();
         if (tid < H)
-            s_dh[tid] = lstm_bptt_rec(params + L.w_hh[net] + (size_t)tid * (size_t)(4 * H), s_da, H);
+            s_dh[tid] = lstm_bptt_rec(params + group_params + L.w_hh[net] + (size_t)tid * (size_t)(4 * H), s_da, H);
         __syncthreads(); // (the row before overwrites s_da)
     }
 }
 
 // kSde: the threads past both nets sum the log_std gradients (sde_log_std_gradient, which needs params for std2_j)
 // kLinear: "lstm critic" -- the sources of lstm_ppo_source_critic
-template <bool kSde, bool kLinear = false>
+// kGrouped: grid (partials, G)
+template <bool kSde, bool kLinear = false, bool kGrouped = false>
 __global__ __launch_bounds__(kPpoThreads) void lstm_ppo_gradient_kernel(LstmLayout L, LstmPpoWork W, float *__restrict__ ws,
                                                                         int B, const float *__restrict__ params)
 {
+    static_assert(!(kSde && kGrouped), "the lstm-sde head has no population yet");
     __shared__ double s_red[kPpoLeaves];
+    if (kGrouped) {
+        ws += (size_t)blockIdx.y * (size_t)W.total;
+        params += (size_t)blockIdx.y * (size_t)L.total;
+    }
     const int tid = threadIdx.x;
     const unsigned p = blockIdx.x * (unsigned)kPpoLeaves + (unsigned)tid;
     double square = 0.0;
@@ -680,9 +787,13 @@ __global__ __launch_bounds__(kPpoThreads) void lstm_ppo_gradient_kernel(LstmLayo
 }
 
 // Eight more levels of the norm's tree: block g sums partials [256 g, 256 g + 256), those past the end as +0.0
+// kGrouped: grid (supers, G)
+template <bool kGrouped = false>
 __global__ __launch_bounds__(kLstmPpoGroup) void lstm_ppo_norm_kernel(LstmPpoWork W, float *__restrict__ ws)
 {
     __shared__ double s_red[kLstmPpoGroup];
+    if (kGrouped)
+        ws += (size_t)blockIdx.y * (size_t)W.total;
     const int tid = threadIdx.x;
     const unsigned i = blockIdx.x * (unsigned)kLstmPpoGroup + (unsigned)tid;
     s_red[tid] = i < W.mlp.partials ? reinterpret_cast<const double *>(ws + W.mlp.partial)[i] : 0.0;

@@ -31,7 +31,18 @@ group's own lanes, and rollout.Rollout / DeviceRollout(env, n_steps, gamma, gae_
 gae_lambda per group -- what a stand-alone trial over m environments normalises and discounts by.  VecNormalize's gamma
 (the view's) and the rollout's gamma are passed separately; rl_zoo3 sets both from the trial's gamma.
 
-Out of scope: the lstm and lstm-sde heads; groups that differ in architecture, m, T or batch size; more than one action
+The recurrent head (include/reinfocus_hip.h, "population lstm"): G recurrent PPO learners (the Categorical head on the
+LSTM, either critic kind), as the reference's search runs its ppo_lstm sampler.
+
+    LstmPopulationPolicy         the numpy twin: literally G lstm.LstmPolicy over lane slices, and the oracle
+    DevicePopulationLstmPolicy   act / values in ONE launch (rf_lstm_forward_grouped); the state keeps its single form
+                                 [2][2][n][H], so rollout slabs, lstm_state(), snapshots and collect() do not change shape;
+                                 spec.kind is the lstm kind, so collect() keeps episode_starts and lstm_states
+    PopulationLearner / DevicePopulationLearner become the recurrent learner with them: update(rollout_or_parts, firsts,
+    count) and train(rollout, n_epochs, batch_size, splits) as lstm_learner's, with one first row / split per group
+    (G lstm_learner.LstmLearner over slice-parts; rf_lstm_ppo_update_grouped, six launches whatever G is)
+
+Out of scope: the lstm-sde head (the next step); groups that differ in architecture, m, T or batch size; more than one action
 dimension; SB3Wrapper; and the environment's shared reset-state generator -- lanes that end are
 ranked across all groups, so which reset state a lane draws depends on other groups' episode ends: the independence
 covers what the learner is given the raw step, not the environment's draws.
@@ -42,6 +53,8 @@ torch is imported lazily, by the device classes only (reinfocus_amd/torch_intero
 import numpy as np
 
 from reinfocus_amd.environments import learner as learner_module
+from reinfocus_amd.environments import lstm as lstm_module
+from reinfocus_amd.environments import lstm_learner as lstm_learner_module
 from reinfocus_amd.environments import policy as policy_module
 from reinfocus_amd.environments import sde as sde_module
 from reinfocus_amd.environments.learner import MAX_BATCH, STATE_HEADER, f64
@@ -81,6 +94,59 @@ def _checked_sde_population(spec, groups, seeds, log_std_init):
     groups, seeds = _checked_groups(groups, seeds)
     inits = per_group(spec.log_std_init if log_std_init is None else log_std_init, groups, "log_std_init")
     return groups, seeds, np.array([float(x) for x in inits], dtype=f32)
+
+
+LSTM_KIND = "lstm"  # (LstmPolicySpec.kind)
+
+
+def _checked_lstm_population(spec, groups, seeds):
+    if getattr(spec, "kind", None) != LSTM_KIND:
+        raise ValueError(f"a population of recurrent learners has the Categorical head of LstmPolicySpec, not a spec of kind "
+                         f"{getattr(spec, 'kind', None)!r}: MlpPolicySpec has PopulationPolicy / DevicePopulationPolicy, "
+                         "SdePolicySpec SdePopulationPolicy / DeviceSdePopulationPolicy; the lstm-sde head (LstmSdePolicySpec) "
+                         "in a population is out of scope -- it is the next step")
+    return _checked_groups(groups, seeds)
+
+
+def group_parts(parts, groups, g):
+    """Group g's slice of parts_of(rollout) over n = G m lanes, as a stand-alone rollout of m lanes would hand it over:
+    rows [g m T, (g + 1) m T) of the flat arrays, columns [g m, (g + 1) m) of episode_starts and lstm_states (views)."""
+    steps, lanes = int(parts["n_steps"]), int(parts["num_envs"])
+    m = _per_group(lanes, groups)
+    rows = m * steps
+    out = {key: parts[key][g * rows:(g + 1) * rows] for key in learner_module.BATCH_KEYS}
+    out.update(episode_starts=parts["episode_starts"][:, g * m:(g + 1) * m],
+               lstm_states=parts["lstm_states"][:, :, :, g * m:(g + 1) * m, :], n_steps=steps, num_envs=m)
+    return out
+
+
+def _checked_firsts(firsts, groups, rows, what="firsts"):
+    """G integers in 0 .. rows - 1."""
+    values = np.asarray(firsts)
+    if values.shape != (groups,) or not np.issubdtype(values.dtype, np.integer) or values.min() < 0 or values.max() >= rows:
+        raise ValueError(f"{what} must be {groups} integers in 0 .. {rows - 1}, one per group, not {firsts!r}")
+    return [int(v) for v in values]
+
+
+def _group_splits(splits, n_epochs, groups, rows, generator):
+    """The split index of every epoch and group, int [n_epochs][G]: `splits` if given, else generator.integers(rows,
+    size=G) per epoch (a host draw)."""
+    if splits is not None:
+        values = np.asarray(splits)
+        if values.shape != (n_epochs, groups) or not np.issubdtype(values.dtype, np.integer) or values.min() < 0 \
+                or values.max() >= rows:
+            raise ValueError(f"splits must be integers in 0 .. {rows - 1} of shape ({n_epochs}, {groups}): one per epoch and "
+                             f"group, not shape {values.shape}")
+        return values.astype(np.int64)
+    if generator is None:
+        generator = np.random.default_rng()
+    return np.stack([generator.integers(rows, size=groups) for _ in range(n_epochs)]).astype(np.int64)
+
+
+def _refuse_other_groups(rollout, groups):
+    other = getattr(rollout, "groups", None)
+    if other is not None and int(other) != groups:
+        raise ValueError(f"the rollout was made with groups={other}, the population has {groups} groups")
 
 
 def _initial_params(spec, inits):
@@ -168,6 +234,8 @@ def _refuse_rollout(spec, rollout):
     """A Categorical population refuses a Box rollout, one with the Gaussian head a Discrete one."""
     if spec.kind == sde_module.SdePolicySpec.kind:
         sde_module._refuse_discrete(rollout.env.single_action_space)
+    elif spec.kind == LSTM_KIND:
+        lstm_module._refuse_box(rollout.env.single_action_space)
     else:
         policy_module._refuse_box(rollout.env.single_action_space)
 
@@ -291,18 +359,105 @@ class SdePopulationPolicy:
         return tuple(None if parts[0][i] is None else np.concatenate([part[i] for part in parts]) for i in range(5))
 
 
+class LstmPopulationPolicy:
+    """The numpy twin of DevicePopulationLstmPolicy, and its oracle: G lstm.LstmPolicy, group g seeded with seeds[g], over
+    slices of the lanes.  `params` is one array [G][P]; policies[g].params is its row g.  The state is ONE array
+    [2, 2, n, H] over all n = G m lanes (None before the first call of a population built without num_envs); group g's
+    member works on its columns [g m, (g + 1) m)."""
+
+    def __init__(self, spec, groups, seeds, num_envs=None):
+        self.groups, seeds = _checked_lstm_population(spec, groups, seeds)
+        self.spec = spec
+        self.params = np.zeros((self.groups, spec.size), dtype=f32)
+        self.policies = [lstm_module.LstmPolicy(spec, seed) for seed in seeds]
+        for g, member in enumerate(self.policies):
+            member.params = self.params[g]
+        self._state = None
+        if num_envs is not None:
+            _per_group(int(num_envs), self.groups)
+            self._state = np.zeros(spec.state_shape(num_envs), dtype=f32)
+
+    _groups_of = PopulationPolicy._groups_of
+    load_state_dict = PopulationPolicy.load_state_dict
+    state_dict = PopulationPolicy.state_dict
+    rng_state = PopulationPolicy.rng_state
+    set_rng_state = PopulationPolicy.set_rng_state
+
+    def _own_state(self, n):
+        if self._state is None or self._state.shape[2] != n:
+            self._state = np.zeros(self.spec.state_shape(n), dtype=f32)
+        return self._state
+
+    def lstm_state(self):
+        """A copy of the state float32 [2, 2, n, H] (None before the first call of a population built without num_envs)."""
+        return None if self._state is None else self._state.copy()
+
+    def set_lstm_state(self, state):
+        state = np.array(state, dtype=f32)
+        if state.ndim != 4 or state.shape[:2] != (2, 2) or state.shape[3] != self.spec.lstm_hidden:
+            raise ValueError(f"a state has shape (2, 2, n, {self.spec.lstm_hidden}), not {state.shape}")
+        _per_group(state.shape[2], self.groups)
+        self._state = state
+
+    def reset_state(self):
+        if self._state is not None:
+            self._state[...] = 0.0
+
+    def _split(self, obs, episode_starts, final_obs):
+        """Per group (rows of obs, of episode_starts, of final_obs or None, the lane slice)."""
+        obs = np.asarray(obs, dtype=f32).reshape(-1, self.spec.obs_width)
+        n = obs.shape[0]
+        m = _per_group(n, self.groups)
+        starts = np.asarray(episode_starts).reshape(n)
+        if final_obs is not None:
+            final_obs = np.asarray(final_obs, dtype=f32).reshape(obs.shape)
+        return n, [(obs[g * m:(g + 1) * m], starts[g * m:(g + 1) * m],
+                    None if final_obs is None else final_obs[g * m:(g + 1) * m], slice(g * m, (g + 1) * m))
+                   for g in range(self.groups)]
+
+    def act(self, obs, episode_starts, final_obs=None, deterministic=False, states=None):
+        """(actions int64 [n], values, log_probs, final_values or None) over all n = G m rows: group g's rows by
+        policies[g] from its columns of the state, which draws m of its own generator's numbers unless deterministic.  The
+        population's own state advances in place, or -- with states=(in, out), two float32 [2, 2, n, H] arrays -- `out` is
+        written from `in` and the own state stays."""
+        n, pieces = self._split(obs, episode_starts, final_obs)
+        source, target = (self._own_state(n),) * 2 if states is None else states
+        parts = []
+        for member, (rows, starts, final_rows, lanes) in zip(self.policies, pieces):
+            before = np.ascontiguousarray(source[:, :, lanes, :])
+            after = np.empty_like(before)
+            parts.append(member.act(rows, starts, final_rows, deterministic, states=(before, after)))
+            target[:, :, lanes, :] = after
+        return tuple(None if parts[0][i] is None else np.concatenate([part[i] for part in parts]) for i in range(4))
+
+    def values(self, obs, episode_starts, final_obs=None):
+        """V(obs) from the own state masked by episode_starts; with final_obs (V(obs), V(final_obs)).  The state stays."""
+        n, pieces = self._split(obs, episode_starts, final_obs)
+        state = self._own_state(n)
+        parts = []
+        for member, (rows, starts, final_rows, lanes) in zip(self.policies, pieces):
+            member.set_lstm_state(state[:, :, lanes, :])
+            parts.append(member.values(rows, starts, final_rows))
+        if final_obs is None:
+            return np.concatenate(parts)
+        return np.concatenate([part[0] for part in parts]), np.concatenate([part[1] for part in parts])
+
+
 class PopulationLearner(_GroupHyper):
     """The numpy twin of DevicePopulationLearner, and its oracle: G learner.Learner, learners[g] over policies[g] and the
-    group's rows."""
+    group's rows.  With an LstmPopulationPolicy it is the recurrent learner: G lstm_learner.LstmLearner over slice-parts
+    (group_parts), update(rollout_or_parts, firsts, count) and train(rollout, n_epochs, batch_size, splits, generator)."""
 
     def __init__(self, policy, learning_rate=3e-4, clip_range=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5,
                  normalize_advantage=True, betas=(0.9, 0.999), adam_eps=1e-5):
-        if not isinstance(policy, (PopulationPolicy, SdePopulationPolicy)):
+        if not isinstance(policy, (PopulationPolicy, SdePopulationPolicy, LstmPopulationPolicy)):
             raise TypeError(f"PopulationLearner needs a PopulationPolicy, not {type(policy).__name__} (a "
                             "DevicePopulationPolicy has DevicePopulationLearner)")
         self.policy, self.spec, self.groups = policy, policy.spec, policy.groups
+        self._lstm = self.spec.kind == LSTM_KIND
         self._configure(learning_rate, clip_range, ent_coef, vf_coef, max_grad_norm, normalize_advantage, betas, adam_eps)
-        self.learners = [learner_module.Learner(member) for member in policy.policies]
+        member_learner = lstm_learner_module.LstmLearner if self._lstm else learner_module.Learner
+        self.learners = [member_learner(member) for member in policy.policies]
 
     def _hand_down(self):
         for member, hyper in zip(self.learners, self.hypers()):
@@ -315,9 +470,40 @@ class PopulationLearner(_GroupHyper):
         return rows, [{key: np.asarray(flat[key])[g * rows:(g + 1) * rows] for key in learner_module.BATCH_KEYS}
                       for g in range(self.groups)]
 
-    def update(self, flat, index):
+    def _recurrent_update(self, rollout_or_parts, firsts, count):
+        parts = lstm_learner_module._parts(rollout_or_parts)
+        rows = _per_group(int(parts["num_envs"]), self.groups) * int(parts["n_steps"])
+        firsts = _checked_firsts(firsts, self.groups, rows)
+        if not 1 <= int(count) <= min(rows, MAX_BATCH):
+            raise ValueError(f"a minibatch of {count} rows is not in 1 .. {min(rows, MAX_BATCH)} (min(m T, {MAX_BATCH}))")
+        self._hand_down()
+        return np.stack([member.update(group_parts(parts, self.groups, g), firsts[g], int(count))
+                         for g, member in enumerate(self.learners)])
+
+    def _recurrent_train(self, rollout, n_epochs, batch_size, splits, generator):
+        _refuse_rollout(self.spec, rollout)
+        _refuse_other_groups(rollout, self.groups)
+        parts = lstm_learner_module.parts_of(rollout)
+        rows = _per_group(int(parts["num_envs"]), self.groups) * int(parts["n_steps"])
+        n_epochs, batch_size, per_epoch = self._batches(rows, n_epochs, batch_size)
+        splits = _group_splits(splits, n_epochs, self.groups, rows, generator)
+        stats = np.zeros((n_epochs * per_epoch, self.groups, 8), dtype=f32)
+        for epoch in range(n_epochs):
+            for i in range(per_epoch):
+                firsts = (splits[epoch] + i * batch_size) % rows
+                stats[epoch * per_epoch + i] = self._recurrent_update(parts, firsts, min(batch_size, rows - i * batch_size))
+        return stats
+
+    def update(self, flat, index, count=None):
         """One minibatch update of every group: index int64 [G][B] of rows local to each group's piece of flat().
-        Returns the stats float32 [G][8]."""
+        Returns the stats float32 [G][8].  The recurrent learner: update(rollout_or_parts, firsts, count) -- G first rows,
+        group g's minibatch is rows (firsts[g] + b) mod m T, b < count, of its own piece."""
+        if self._lstm:
+            if count is None:
+                raise TypeError("the recurrent learner's update takes (rollout_or_parts, firsts, count)")
+            return self._recurrent_update(flat, index, count)
+        if count is not None:
+            raise TypeError("count belongs to the recurrent learner's update(rollout_or_parts, firsts, count)")
         index = np.asarray(index, dtype=np.int64)
         if index.ndim != 2 or index.shape[0] != self.groups:
             raise ValueError(f"index has shape {index.shape}, not ({self.groups}, B)")
@@ -327,11 +513,20 @@ class PopulationLearner(_GroupHyper):
         self._hand_down()
         return np.stack([member.update(piece, index[g]) for g, (member, piece) in enumerate(zip(self.learners, pieces))])
 
-    def train(self, rollout, n_epochs, batch_size, permutations=None, generator=None):
+    def train(self, rollout, n_epochs, batch_size, permutations=None, generator=None, splits=None):
         """n_epochs passes of every group over its rows of a finished rollout, in minibatches of batch_size (the last one
         may be shorter): stats float32 [n_epochs * ceil(m T / batch_size)][G][8].  Per epoch and group one permutation of
         the group's m T local rows: permutations[epoch][g] (int64 [n_epochs][G][m T]) if given, else
-        generator.permutation(m T), drawn epoch by epoch and in group order."""
+        generator.permutation(m T), drawn epoch by epoch and in group order.
+        The recurrent learner: train(rollout, n_epochs, batch_size, splits=None, generator=None) -- the fourth argument is
+        its splits, integers [n_epochs][G] in 0 .. m T - 1 (else generator.integers(m T, size=G) per epoch); per epoch and
+        group the rows are rotated by the split and cut into consecutive minibatches, as lstm_learner.LstmLearner.train."""
+        if self._lstm:
+            if permutations is not None and splits is not None:
+                raise TypeError("the recurrent learner takes its splits once (the fourth argument, or splits=)")
+            return self._recurrent_train(rollout, n_epochs, batch_size, permutations if splits is None else splits, generator)
+        if splits is not None:
+            raise TypeError("splits belong to the recurrent learner; this one takes permutations")
         _refuse_rollout(self.spec, rollout)
         flat = rollout.flat()
         rows = _per_group(np.asarray(flat["actions"]).shape[0], self.groups)
@@ -634,30 +829,145 @@ class DeviceSdePopulationPolicy:
         return values if final_obs is None else (values, final_values)
 
 
+class DevicePopulationLstmPolicy:
+    """The recurrent policies of G groups of m environments each of one device-resident environment with a Discrete action
+    space (n = G m), over torch tensors on its GPU; used as LstmPopulationPolicy is and bit for bit equal to it, group by
+    group equal to a stand-alone lstm.DeviceLstmPolicy(seed=seeds[g]) over the group's m environments.  The spec is an
+    LstmPolicySpec with either enable_critic_lstm.
+
+    Every act() / values() is ONE launch (rf_lstm_forward_grouped), grid (ceil(m / 8), nets, G).  `params` is one float32
+    tensor [G][P]; the state is one float32 [2, 2, n, H] tensor in DeviceLstmPolicy's form, which act() updates in place
+    -- group g owns columns [g m, (g + 1) m) of each of its four planes.  The generators are DevicePopulationPolicy's: a
+    device table of words written at seeding and at set_rng_state only, the draws taken travel by value.  Nothing waits
+    for the host."""
+
+    _device_env = policy_module.DevicePolicy._device_env
+    _rows = policy_module.DevicePolicy._rows
+    _out = policy_module.DevicePolicy._out
+
+    def __init__(self, env, spec, groups, seeds):
+        self._device_env(env)
+        self.groups, seeds = _checked_lstm_population(spec, groups, seeds)
+        if not hasattr(env.single_action_space, "n"):
+            raise ValueError(f"a population of recurrent learners has a Categorical head over a Discrete action space, not "
+                             f"{env.single_action_space!r}: the lstm-sde head in a population is out of scope -- it is the "
+                             "next step")
+        if env.single_action_space.n != spec.n_actions:
+            raise ValueError(f"the spec has {spec.n_actions} actions, the environment {env.single_action_space.n}")
+        self.num_envs = int(env.num_envs)
+        self.per_group = _per_group(self.num_envs, self.groups)
+        self._io = env._tensor_io()  # (ValueError, as step_tensors': a host initializer, a render_mode)
+        from reinfocus_amd import torch_interop
+
+        self._interop = torch_interop
+        torch = self._torch = torch_interop._torch()
+        self.spec = spec
+        self._ctx = env._ctx
+        self.device = torch.device("cuda", self._ctx.device)
+        self.params = torch.zeros((self.groups, spec.size), dtype=torch.float32, device=self.device)
+        self._owned = {}
+        self._table = torch.zeros((self.groups, 4), dtype=torch.int64, device=self.device)  # (the bits of uint64 words)
+        self._state = torch.zeros(spec.state_shape(self.num_envs), dtype=torch.float32, device=self.device)
+        self._set_generators([np.random.PCG64DXSM(seed) for seed in seeds])
+
+    _set_generators = DevicePopulationPolicy._set_generators
+    rng_state = DevicePopulationPolicy.rng_state
+    set_rng_state = DevicePopulationPolicy.set_rng_state
+    _groups_of = PopulationPolicy._groups_of
+    load_state_dict = DevicePopulationPolicy.load_state_dict
+    state_dict = DevicePopulationPolicy.state_dict
+    _all_rows = DevicePopulationPolicy._all_rows
+    _checked_state = lstm_module.DeviceLstmPolicy._checked_state
+    lstm_state = lstm_module.DeviceLstmPolicy.lstm_state
+    set_lstm_state = lstm_module.DeviceLstmPolicy.set_lstm_state
+    reset_state = lstm_module.DeviceLstmPolicy.reset_state
+    _starts = lstm_module.DeviceLstmPolicy._starts
+
+    def _forward(self, obs, episode_starts, final_obs, state_in, state_out, sampled, flags, actions, log_probs, values,
+                 final_values):
+        self._interop.check_one_runtime()
+        pointer = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        self._ctx.lstm_forward_grouped(self.spec.critic_desc(), self.groups, self.per_group, self.params.data_ptr(),
+                                       obs.data_ptr(), episode_starts.data_ptr(), pointer(final_obs), state_in.data_ptr(),
+                                       pointer(state_out), self._table.data_ptr() if sampled else None, self._consumed,
+                                       flags, pointer(actions), pointer(log_probs), pointer(values), pointer(final_values),
+                                       None, self._io._stream())
+
+    def act(self, obs, episode_starts, final_obs=None, deterministic=False, out=None, states=None):
+        """DeviceLstmPolicy.act over all n = G m rows, group g's rows with params[g], its own generator and its columns of
+        the state.  The own state advances in place; with states=(in, out), two device tensors float32 [2, 2, n, H], the
+        call goes from `in` to `out` instead (the same tensor, or two that do not overlap) and the own state stays.  One
+        launch; a sampled call takes m draws of every generator."""
+        torch = self._torch
+        obs = self._all_rows(obs, final_obs)
+        n = self.num_envs
+        episode_starts = self._starts(episode_starts, n)
+        if states is None:
+            state_in = state_out = self._state
+        else:
+            state_in, state_out = states
+            state_in, state_out = self._checked_state(state_in, "states[0]"), self._checked_state(state_out, "states[1]")
+        given = (None,) * 4 if out is None else tuple(out)
+        if len(given) != 4:
+            raise TypeError("out must be (actions, values, log_probs, final_values or None)")
+        actions = self._out("actions", given[0], n, torch.int64)
+        values = self._out("values", given[1], n, torch.float32)
+        log_probs = self._out("log_probs", given[2], n, torch.float32)
+        final_values = None if final_obs is None else self._out("final_values", given[3], n, torch.float32)
+        self._forward(obs, episode_starts, final_obs, state_in, state_out, not deterministic,
+                      DETERMINISTIC if deterministic else 0, actions, log_probs, values, final_values)
+        if not deterministic:
+            self._consumed += self.per_group  # (after the call was taken: a refused call consumes nothing)
+        return actions, values, log_probs, final_values
+
+    def values(self, obs, episode_starts, final_obs=None, out=None):
+        """DeviceLstmPolicy.values over all n rows.  One launch, no draw; the state stays."""
+        torch = self._torch
+        obs = self._all_rows(obs, final_obs)
+        episode_starts = self._starts(episode_starts, self.num_envs)
+        given = (None, None) if out is None else tuple(out)
+        if len(given) != 2:
+            raise TypeError("out must be (values, final_values or None)")
+        values = self._out("last_values", given[0], self.num_envs, torch.float32)
+        final_values = None if final_obs is None else self._out("final_values", given[1], self.num_envs, torch.float32)
+        self._forward(obs, episode_starts, final_obs, self._state, None, False, 0, None, None, values, final_values)
+        return values if final_obs is None else (values, final_values)
+
+
 class DevicePopulationLearner(_GroupHyper):
     """The learners of a DevicePopulationPolicy or a DeviceSdePopulationPolicy, over torch tensors on its GPU; used as
     PopulationLearner is and bit for bit equal to it.  update() is rf_ppo_update_grouped (rf_sde_update_grouped with the
     Gaussian head, over float32 raw actions): three launches on torch's current stream whatever G is, which
     change policy.params in place.  The hyper-parameters are packed into one device tensor (G rf_ppo_hyper) when an
     update is enqueued, from pinned memory and only when they changed.  train() enqueues every update of every epoch back
-    to back.  No method synchronises the host (state_dict() reads the steps and does)."""
+    to back.  No method synchronises the host (state_dict() reads the steps and does).
+
+    With a DevicePopulationLstmPolicy it is the recurrent learner: update(rollout_or_parts, firsts, count) and
+    train(rollout, n_epochs, batch_size, splits, generator) as PopulationLearner's, rf_lstm_ppo_update_grouped -- six
+    launches whatever G is.  The G first rows of every update are computed on the host and uploaded as one int32 table
+    [updates][G] from pinned memory, stream-ordered."""
 
     def __init__(self, policy, learning_rate=3e-4, clip_range=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5,
                  normalize_advantage=True, betas=(0.9, 0.999), adam_eps=1e-5):
-        if not isinstance(policy, (DevicePopulationPolicy, DeviceSdePopulationPolicy)):
+        if not isinstance(policy, (DevicePopulationPolicy, DeviceSdePopulationPolicy, DevicePopulationLstmPolicy)):
             raise TypeError(f"DevicePopulationLearner needs a DevicePopulationPolicy, not {type(policy).__name__} (a "
                             "PopulationPolicy has PopulationLearner, a DevicePolicy DeviceLearner)")
         self.policy, self.spec, self.groups = policy, policy.spec, policy.groups
         self._sde = self.spec.kind == sde_module.SdePolicySpec.kind
+        self._lstm = self.spec.kind == LSTM_KIND
         self._configure(learning_rate, clip_range, ent_coef, vf_coef, max_grad_norm, normalize_advantage, betas, adam_eps)
         self._torch, self._interop, self._io, self._ctx = policy._torch, policy._interop, policy._io, policy._ctx
         self.device = policy.device
         torch = self._torch
         self._state_floats = STATE_HEADER + 2 * self.spec.size
-        state_size = self._ctx.sde_grouped_state_size if self._sde else self._ctx.ppo_grouped_state_size
-        if state_size(self.spec.desc(), self.groups, policy.per_group) != 4 * self.groups * self._state_floats:
-            raise RuntimeError("rf_ppo_grouped_state_size / rf_sde_grouped_state_size disagrees with the packed optimizer "
-                               "states")
+        if self._lstm:
+            state_bytes = self._ctx.lstm_ppo_grouped_state_size(self.spec.critic_desc(), self.groups, policy.per_group)
+        else:
+            state_size = self._ctx.sde_grouped_state_size if self._sde else self._ctx.ppo_grouped_state_size
+            state_bytes = state_size(self.spec.desc(), self.groups, policy.per_group)
+        if state_bytes != 4 * self.groups * self._state_floats:
+            raise RuntimeError("rf_ppo_grouped_state_size / rf_sde_grouped_state_size / rf_lstm_ppo_grouped_state_size "
+                               "disagrees with the packed optimizer states")
         self.state = torch.zeros((self.groups, self._state_floats), dtype=torch.float32, device=self.device)
         self._workspace, self._workspace_key = None, None
         self._stats = None
@@ -710,8 +1020,12 @@ class DevicePopulationLearner(_GroupHyper):
     def _room(self, steps, batch):
         key = (steps, batch)
         if key != self._workspace_key:
-            workspace_size = self._ctx.sde_grouped_workspace_size if self._sde else self._ctx.ppo_grouped_workspace_size
-            size = workspace_size(self.spec.desc(), self.groups, self.policy.per_group, steps, batch)
+            if self._lstm:
+                size = self._ctx.lstm_ppo_grouped_workspace_size(self.spec.critic_desc(), self.groups, self.policy.per_group,
+                                                                 steps, batch)
+            else:
+                workspace_size = self._ctx.sde_grouped_workspace_size if self._sde else self._ctx.ppo_grouped_workspace_size
+                size = workspace_size(self.spec.desc(), self.groups, self.policy.per_group, steps, batch)
             if size == 0:
                 raise RuntimeError(f"rf_ppo_grouped_workspace_size / rf_sde_grouped_workspace_size refuses minibatches of "
                                    f"{batch} out of {steps * self.policy.per_group} rows")
@@ -726,9 +1040,97 @@ class DevicePopulationLearner(_GroupHyper):
                flat["actions"].data_ptr(), flat["log_probs"].data_ptr(), flat["advantages"].data_ptr(),
                flat["returns"].data_ptr(), index.shape[1], index.data_ptr(), stats.data_ptr(), self._io._stream())
 
-    def update(self, flat, index):
+    # ---- the recurrent learner (a DevicePopulationLstmPolicy) ---------------------------------------------------------
+    def _own(self, rollout):
+        if getattr(rollout, "device", None) != self.device:
+            raise ValueError(f"the rollout lives on {getattr(rollout, 'device', 'the host')}, the policy on {self.device}")
+
+    def _checked_parts(self, parts):
+        """(steps T, rows m T of one group) of parts whose tensors are what rf_lstm_ppo_update_grouped reads."""
+        torch = self._torch
+        steps, lanes = int(parts["n_steps"]), int(parts["num_envs"])
+        if steps < 1 or lanes != self.policy.num_envs:
+            raise ValueError(f"the parts have n_steps {steps} and num_envs {lanes}; the population has "
+                             f"{self.policy.num_envs} environments")
+        total, hidden = steps * lanes, self.spec.lstm_hidden
+        wanted = {"observations": (torch.float32, (total, self.spec.obs_width)), "actions": (torch.int64, (total,)),
+                  "log_probs": (torch.float32, (total,)), "advantages": (torch.float32, (total,)),
+                  "returns": (torch.float32, (total,)), "episode_starts": (torch.uint8, (steps + 1, lanes)),
+                  "lstm_states": (torch.float32, (steps + 1, 2, 2, lanes, hidden))}
+        for key, (dtype, shape) in wanted.items():
+            tensor = parts[key]
+            if not isinstance(tensor, torch.Tensor):
+                raise TypeError(f"{key} must be a torch.Tensor on {self.device}, not {type(tensor).__name__}")
+            self._io._on_device(tensor, key)
+            if tensor.dtype != dtype or tuple(tensor.shape) != shape or not tensor.is_contiguous():
+                raise ValueError(f"{key} is {tensor.dtype} {tuple(tensor.shape)}, not contiguous {dtype} {shape}")
+        return steps, steps * self.policy.per_group
+
+    def _upload_firsts(self, table):
+        """int [updates][G] as a device tensor int32, from pinned memory and stream-ordered: updates enqueued before keep
+        what they read, and nothing waits for the host."""
+        torch = self._torch
+        host = torch.from_numpy(np.ascontiguousarray(table, dtype=np.int32)).pin_memory()
+        return torch.empty(host.shape, dtype=torch.int32, device=self.device).copy_(host, non_blocking=True)
+
+    def _enqueue_recurrent(self, parts, steps, firsts, count, stats, hyper):
+        self._ctx.lstm_ppo_update_grouped(
+            self.spec.critic_desc(), self.groups, self.policy.per_group, steps, hyper.data_ptr(),
+            self.policy.params.data_ptr(), self.state.data_ptr(), self._workspace.data_ptr(),
+            parts["observations"].data_ptr(), parts["actions"].data_ptr(), parts["log_probs"].data_ptr(),
+            parts["advantages"].data_ptr(), parts["returns"].data_ptr(), parts["episode_starts"].data_ptr(),
+            parts["lstm_states"].data_ptr(), firsts.data_ptr(), count, stats.data_ptr(), self._io._stream())
+
+    def _recurrent_update(self, rollout_or_parts, firsts, count):
+        if hasattr(rollout_or_parts, "flat"):
+            self._own(rollout_or_parts)
+            _refuse_other_groups(rollout_or_parts, self.groups)
+        parts = lstm_learner_module._parts(rollout_or_parts)
+        steps, rows = self._checked_parts(parts)
+        firsts = _checked_firsts(firsts, self.groups, rows)
+        count = int(count)
+        if not 1 <= count <= min(rows, MAX_BATCH):
+            raise ValueError(f"a minibatch of {count} rows is not in 1 .. {min(rows, MAX_BATCH)} (min(m T, {MAX_BATCH}))")
+        self._interop.check_one_runtime()
+        self._room(steps, count)
+        if self._stats is None:
+            self._stats = self._torch.zeros((self.groups, 8), dtype=self._torch.float32, device=self.device)
+        self._enqueue_recurrent(parts, steps, self._upload_firsts(firsts), count, self._stats, self._packed_hyper())
+        return self._stats
+
+    def _recurrent_train(self, rollout, n_epochs, batch_size, splits, generator):
+        torch = self._torch
+        _refuse_rollout(self.spec, rollout)
+        self._own(rollout)
+        _refuse_other_groups(rollout, self.groups)
+        parts = lstm_learner_module.parts_of(rollout)
+        steps, rows = self._checked_parts(parts)
+        n_epochs, batch_size, per_epoch = self._batches(rows, n_epochs, batch_size)
+        splits = _group_splits(splits, n_epochs, self.groups, rows, generator)
+        # every update's G first rows, on the host: (split + i * batch_size) mod m T
+        shifts = (np.arange(per_epoch, dtype=np.int64) * batch_size)[None, :, None]
+        table = ((splits[:, None, :] + shifts) % rows).reshape(n_epochs * per_epoch, self.groups)
+        self._interop.check_one_runtime()
+        firsts = self._upload_firsts(table)
+        hyper = self._packed_hyper()
+        stats = torch.zeros((n_epochs * per_epoch, self.groups, 8), dtype=torch.float32, device=self.device)
+        for update in range(n_epochs * per_epoch):
+            i = update % per_epoch
+            count = min(batch_size, rows - i * batch_size)
+            self._room(steps, count)
+            self._enqueue_recurrent(parts, steps, firsts[update], count, stats[update], hyper)
+        return stats
+
+    def update(self, flat, index, count=None):
         """One minibatch update of every group from rows index[g] (int64 device tensor [G][B], local to the group) of its
-        piece of flat(); returns the stats, a float32 [G][8] tensor the learner owns and the next update() overwrites."""
+        piece of flat(); returns the stats, a float32 [G][8] tensor the learner owns and the next update() overwrites.
+        The recurrent learner: update(rollout_or_parts, firsts, count) with G host integers as firsts."""
+        if self._lstm:
+            if count is None:
+                raise TypeError("the recurrent learner's update takes (rollout_or_parts, firsts, count)")
+            return self._recurrent_update(flat, index, count)
+        if count is not None:
+            raise TypeError("count belongs to the recurrent learner's update(rollout_or_parts, firsts, count)")
         steps, batch = self._checked(flat, index)
         self._interop.check_one_runtime()
         self._room(steps, batch)
@@ -737,11 +1139,20 @@ class DevicePopulationLearner(_GroupHyper):
         self._enqueue(flat, steps, index, self._stats, self._packed_hyper())
         return self._stats
 
-    def train(self, rollout, n_epochs, batch_size, permutations=None, generator=None):
+    def train(self, rollout, n_epochs, batch_size, permutations=None, generator=None, splits=None):
         """As PopulationLearner.train, over a finished DeviceRollout of the policy's GPU: permutations is an int64 device
         tensor [n_epochs][G][m T] of local rows, else per epoch one device permutation per group (the argsort of one
         uniform draw [G][m T]; generator: a torch.Generator of that device).  Returns the stats as one device tensor
-        [n_epochs * ceil(m T / batch_size)][G][8].  Nothing waits for the host."""
+        [n_epochs * ceil(m T / batch_size)][G][8].  Nothing waits for the host.
+        The recurrent learner: train(rollout, n_epochs, batch_size, splits=None, generator=None) -- the fourth argument is
+        its splits, host integers [n_epochs][G] in 0 .. m T - 1 (else generator.integers(m T, size=G) per epoch of a
+        numpy.random.Generator: a host draw costs no synchronisation)."""
+        if self._lstm:
+            if permutations is not None and splits is not None:
+                raise TypeError("the recurrent learner takes its splits once (the fourth argument, or splits=)")
+            return self._recurrent_train(rollout, n_epochs, batch_size, permutations if splits is None else splits, generator)
+        if splits is not None:
+            raise TypeError("splits belong to the recurrent learner; this one takes permutations")
         torch = self._torch
         _refuse_rollout(self.spec, rollout)
         if getattr(rollout, "device", None) != self.device:
