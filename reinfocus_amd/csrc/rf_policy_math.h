@@ -35,10 +35,12 @@ RF_HD float bits_f32(uint32_t u)
 constexpr uint32_t kPolicyNaN = 0x7fc00000u; // the one NaN the policy ever stores
 
 // What is stored: a NaN result is the same 32 bits everywhere (x86 and gfx950 differ in sign and payload of the NaNs
-// their operations make).
+// their operations make).  The test is on the bits, not `x != x`: to the compiler the payload of a NaN that an operation
+// makes is anyone's choice, so it may drop a floating-point select whose two sides are both a NaN -- the gfx950 build did
+// for policy_canonical(sqrtf(x)), which isnan(sqrt(x)) == !(x >= 0) turns into one (tests/mathcheck found 0x7fc00001).
 RF_HD float policy_canonical(float x)
 {
-    return x != x ? bits_f32(kPolicyNaN) : x;
+    return (f32_bits(x) & 0x7fffffffu) > 0x7f800000u ? bits_f32(kPolicyNaN) : x;
 }
 
 // ln 2 = kLn2Hi + kLn2Lo; kLn2Hi has 10 significant bits, so k * kLn2Hi is exact for |k| < 2^14
