@@ -74,13 +74,13 @@ def limit_layouts_of(index):
     return ["depth/0/17"] if index == LIMITS else []
 
 
-def starts_of(kind, n_steps, num_envs):
+def starts_of(kind, n_steps, num_envs, seed=DRAWN_SEED):
     """uint8 [T + 1, n].  mixed (T = 5, n = 3): environment 0 starts at t = 0 (byte 1) and t = 2 (byte 2), environment 1
     runs four rows from its stored, non-zero state and starts at t = 4 (byte 255), environment 2 starts at t = 0 and 3.
     depth (T = 17, n = 4): environment 0 starts at t = 0 (one sequence of 17 rows), environment 1 at t = 1 (1 and 16
     rows, the first from its stored state), environment 2 at t = 8 (8 and 9), environment 3 at t = 16 (16 and 1).
     drawn: every byte of rows 0 .. T - 1 is a start with probability DRAWN_SHARE, by turns 1, 2 and 255, from
-    DRAWN_SEED; environment 0's first row is none."""
+    `seed` (DRAWN_SEED); environment 0's first row is none."""
     starts = np.zeros((n_steps + 1, num_envs), dtype=np.uint8)
     if kind == "every":
         starts[...] = np.array([1, 2, 255], dtype=np.uint8)[np.arange(starts.size) % 3].reshape(starts.shape)
@@ -91,7 +91,7 @@ def starts_of(kind, n_steps, num_envs):
         for step, env, byte in DEPTH_STARTS:
             starts[step, env] = byte
     elif kind == "drawn":
-        drawn = np.random.default_rng(DRAWN_SEED).random((n_steps, num_envs)) < DRAWN_SHARE
+        drawn = np.random.default_rng(seed).random((n_steps, num_envs)) < DRAWN_SHARE
         drawn[0, 0] = False
         starts[:n_steps][drawn] = np.array([1, 2, 255], dtype=np.uint8)[np.arange(int(drawn.sum())) % 3]
     else:

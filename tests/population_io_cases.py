@@ -13,6 +13,7 @@ import sys
 
 import numpy as np
 
+from tests import learner_io_cases as learner_cases
 from tests import policy_io_cases as policy_cases
 from tests import rollout_io_cases as rollout_cases
 
@@ -36,6 +37,16 @@ WIDE_FORWARD = ((0, 64, 8), (1, 64, 8), (0, 65, 8), (1, 65, 8), (0, 512, 8), (0,
 # ppo_tuned.yml's first shape for 64 groups on NETWORKS[1]: m = 8, T = 32, B = 64, so 4 minibatches per epoch; one row of
 # group 31 holds a NaN observation
 WIDE_UPDATE = dict(index=1, groups=64, per_group=8, steps=32, batch=64, nan_group=31, nan_row=100)
+# large minibatches on ppo_tuned.yml's ContinuousJumps shape, m = 8, T = 128 (N = 1024 rows per group): the sizes the
+# ungrouped update is held to (learner_io_cases.LIMIT_BATCHES: the last single trip of the s_red reductions, the first
+# second trip with a ragged last tile, no multiple of the tile, RF_PPO_MAX_BATCH) at G = 3 on NETWORKS[1], and 513 at G = 2
+# on stable-baselines3's default network (LARGE_NETWORKS, index 2); two consecutive updates each.  LARGE_ALONE also runs as
+# G stand-alone rf_ppo_update launches
+LARGE = dict(per_group=8, steps=128, updates=2)
+LARGE_NETWORKS = (learner_cases.NETWORKS[2],)
+LARGE_CASES = tuple((1, 3, batch) for batch in learner_cases.LIMIT_BATCHES) + ((2, 2, 513),)  # (network, G, B)
+LARGE_ALONE = (1, 3, 513)
+ALONE_ENTRIES = ("ppo_update", "ppo_workspace_size")
 # the limit: RF_POPULATION_MAX_GROUPS groups of one row on the least network; group g has parameter set g % 7, observation
 # block g % 5 and hyper-parameter set g % 3, so neighbours differ in all three and g % 105 names the combination
 LIMIT_GROUPS, LIMIT_PERIODS = 65535, (7, 5, 3)
@@ -49,7 +60,7 @@ def seeds_of(groups):
 
 
 def spec_of(index):
-    return policy_cases.spec_of(NETWORKS[index])
+    return policy_cases.spec_of((NETWORKS + LARGE_NETWORKS)[index])
 
 
 def group_states(spec, groups, base):
@@ -212,6 +223,56 @@ def wide_update_promises(want, before):
             assert bits(states[w["nan_group"]]) == bits(want[update - 1][1][w["nan_group"]])
     params = want[-1][0]
     assert bits(params[1]) == bits(before[1]) and all(bits(params[g]) != bits(before[g]) for g in (0, 30, 31, 32, 63))
+
+
+# ---- large minibatches ---------------------------------------------------------------------------------------------------
+def chained_updates(twin, flat, hypers, order):
+    """Per update of `order` (params [G][P], states [G][S], stats [G][8]) of a PopulationLearner over `twin`."""
+    from reinfocus_amd.environments import harness
+
+    learner = harness.PopulationLearner(twin, **hypers)
+    seen = []
+    for rows in order:
+        stats = learner.update(flat, rows)
+        seen.append((twin.params.copy(), twin_states(learner), stats.copy()))
+    return seen
+
+
+def large_indices(groups, batch, seed):
+    """The index arrays [G][B] of LARGE's consecutive updates, every group's row its own: a permutation of the group's N
+    rows where B = N, else B rows drawn with repeats."""
+    rows = LARGE["per_group"] * LARGE["steps"]
+    rng = np.random.default_rng(seed)
+    order = []
+    for _ in range(LARGE["updates"]):
+        if batch == rows:
+            order.append(np.stack([rng.permutation(rows) for _ in range(groups)]).astype(np.int64))
+        else:
+            order.append(rng.integers(0, rows, (groups, batch)).astype(np.int64))
+    return order
+
+
+def large_inputs(index, groups, batch):
+    """(spec, twin, flat, hypers' keywords, the index arrays of the updates) of one of LARGE_CASES."""
+    spec, twin, flat = update_batch(index, groups, LARGE["per_group"], seed=3, steps=LARGE["steps"])
+    return spec, twin, flat, group_hypers(groups), large_indices(groups, batch, 500 + 7 * index + batch)
+
+
+@functools.lru_cache(maxsize=None)
+def large_twin_updates(index, groups, batch):
+    spec, twin, flat, hypers, order = large_inputs(index, groups, batch)
+    return chained_updates(twin, flat, hypers, order)
+
+
+def large_update_promises(want, before, hypers):
+    """No comparison of a large case is vacuous: every group is taken in every update (flags 0); every group whose
+    learning rate is not 0 ends with other parameters than it began with, the one whose is 0 with the same."""
+    assert len(want) == LARGE["updates"] and all((stats[:, 7] == 0).all() for _, _, stats in want)
+    rates = hypers["learning_rate"]
+    assert 0.0 in rates and any(rates)
+    for g, rate in enumerate(rates):
+        assert (bits(want[-1][0][g]) == bits(before[g])) == (rate == 0), f"group {g} with learning_rate {rate}"
+    assert bits(want[0][1]) != bits(want[1][1])  # (the optimizer header and moments the first wrote, the second read)
 
 
 # ---- the limit: 65535 groups of one row --------------------------------------------------------------------------------
@@ -535,6 +596,56 @@ def wide_update_case(torch, ctx):
             _same_update(tuple(x[g] for x in got), tuple(x[g] for x in want[update]), f"update {update}, group {g}")
         _same_update(got, want[update], f"update {update}")
     wide_update_promises(want, twin.params)
+
+
+def large_update_case(torch, ctx, index, groups, batch, cases=None):
+    """The grouped update on m = 8, T = 128 at B = `batch`, index [G][B] with rows of its own per group, against the twin
+    population over LARGE's consecutive updates: parameters, optimizer states and stats of every group as bytes, parameters
+    and states between guard rows, the workspace of exactly the grouped size function's bytes between guard floats.  For
+    LARGE_ALONE also G stand-alone ungrouped launches on contiguous copies of the groups' slices.  `cases`: this module, or
+    the gSDE population's with the same names."""
+    from reinfocus_amd.environments import learner
+
+    cases = cases or sys.modules[__name__]
+    spec, twin, flat, keywords, order = cases.large_inputs(index, groups, batch)
+    want = cases.large_twin_updates(index, groups, batch)
+    assert all(rows.shape == (groups, batch) for rows in order)
+    hypers = chained_hypers(twin, keywords)
+    per_group, steps = LARGE["per_group"], LARGE["steps"]
+    device = cases._Learner(torch, ctx, spec, twin, flat, per_group, hypers, batch, steps=steps, guarded=True)
+    for update, index_rows in enumerate(order):
+        got = device.update(index_rows)
+        for g in range(groups):
+            _same_update(tuple(x[g] for x in got), tuple(x[g] for x in want[update]), f"update {update}, group {g}")
+    large_update_promises(want, twin.params, keywords)
+    if (index, groups, batch) != cases.LARGE_ALONE:
+        return
+    update_alone, size_alone = (getattr(ctx, name) for name in cases.ALONE_ENTRIES)
+    rows = per_group * steps
+    stream = torch.cuda.current_stream().cuda_stream
+    for g in range(groups):
+        piece = {key: torch.from_numpy(np.ascontiguousarray(flat[key][g * rows:(g + 1) * rows])).cuda()
+                 for key in learner.BATCH_KEYS}
+        params = torch.from_numpy(twin.params[g].copy()).cuda()
+        state = torch.from_numpy(learner.fresh_state(spec)).cuda()
+        workspace = torch.zeros(size_alone(spec.desc(), batch) // 4, dtype=torch.float32, device="cuda")
+        stats = torch.zeros(8, dtype=torch.float32, device="cuda")
+        for update, index_rows in enumerate(order):
+            chosen = torch.from_numpy(np.ascontiguousarray(index_rows[g])).cuda()
+            update_alone(spec.desc(), tuple(hypers[g]), params.data_ptr(), state.data_ptr(), workspace.data_ptr(), rows,
+                         piece["observations"].data_ptr(), piece["actions"].data_ptr(), piece["log_probs"].data_ptr(),
+                         piece["advantages"].data_ptr(), piece["returns"].data_ptr(), batch, chosen.data_ptr(),
+                         stats.data_ptr(), stream)
+            torch.cuda.synchronize()
+            _same_update((params.cpu().numpy(), state.cpu().numpy(), stats.cpu().numpy()),
+                         tuple(x[g] for x in want[update]), f"stand-alone group {g}, update {update}")
+
+
+def chained_hypers(twin, keywords):
+    """learner.Hyper per group of the keywords, without touching the twin."""
+    from reinfocus_amd.environments import harness
+
+    return harness.PopulationLearner(twin, **keywords).hypers()
 
 
 def limit_case(torch, ctx):
@@ -865,6 +976,9 @@ def run_cases(path):
             forward_case(torch, ctx, index, groups, per_group)
     with record.case("update/wide"):
         wide_update_case(torch, ctx)
+    for index, groups, batch in LARGE_CASES:
+        with record.case(f"update/large/{index}/{groups}/{batch}"):
+            large_update_case(torch, ctx, index, groups, batch)
     with record.case("limit"):
         limit_case(torch, ctx)
     with record.case("isolation"):

@@ -41,6 +41,39 @@ UPDATE = dict(groups=3, steps=4, per_group=3, firsts=(0, 7, 11), batches=(5, 12)
 LIMIT = dict(index=lstm_cases.DEFAULT, groups=2, steps=3, per_group=2, batch=6, firsts=(0, 4))
 WIDE_UPDATE = dict(index=lstm_cases.TUNED, groups=64, steps=8, per_group=8, batch=8)
 E2E = dict(groups=3, per_group=3, steps=4, epochs=2, batch=5, iterations=2)
+# the grouped update on lstm_learner_io_cases.LIMIT_LAYOUTS, whose (T, m, starts kind, _, B) each entry takes; every group
+# has its own first row (update u starts at firsts + u) and, by group_starts' roll, its own sequence structure:
+#   depth/    T = 17, m = 4: sequences of 1, 8, 9, 16 and 17 rows.  G = 3 on the tuned network at B = 65 and at B = 68 = N,
+#             where two groups wrap at different rows (these two also as G stand-alone launches); G = 2 on sb3-contrib's
+#             default network (H = 256: every thread of a block owns a unit) at B = 65
+#   untuned/  ppo_lstm_untuned.yml's T = 128, m = 8, B = 128, drawn starts: group 1 crosses an environment boundary, group 2
+#             wraps; every group has a sequence of more than 64 rows and one of one row.  G = 3 on the tuned network, and
+#             G = 2 on the default network with the LSTM critic (the real shape)
+#   wave/     T = 16, m = 64, N = 1024, G = 2 on the tuned network: every row a start at B = 1024 (1024 one-row sequences
+#             per group, 128 MLP tiles, the second trip of the reductions), no flagged start at B = 513
+# updates: two consecutive ones (the second reads the optimizer header the first wrote) where the numpy twin is cheap, one
+# at the 1024-row layouts and at H = 256 over 128 steps, whose twins cost seconds each
+LAYOUT_CASES = {
+    "depth/65": dict(layout="depth/0/65", index=lstm_cases.TUNED, critics=CRITICS, firsts=(0, 5, 30), updates=2, alone=True),
+    "depth/68": dict(layout="depth/5/68", index=lstm_cases.TUNED, critics=CRITICS, firsts=(5, 0, 67), updates=2, alone=True),
+    "depth/65/default": dict(layout="depth/0/65", index=lstm_cases.DEFAULT, critics=CRITICS, firsts=(0, 5), updates=2,
+                             alone=False),
+    "untuned": dict(layout="untuned/0/128", index=lstm_cases.TUNED, critics=CRITICS, firsts=(0, 100, 1000), updates=2,
+                    alone=False),
+    "untuned/default": dict(layout="untuned/0/128", index=lstm_cases.DEFAULT, critics=(True,), firsts=(0, 100), updates=1,
+                            alone=False),
+    "wave/1024": dict(layout="wave/7/1024", index=lstm_cases.TUNED, critics=CRITICS, firsts=(7, 0), updates=1, alone=False),
+    "wave/513": dict(layout="wave/0/513", index=lstm_cases.TUNED, critics=CRITICS, firsts=(0, 9), updates=1, alone=False)}
+LAYOUT_KINDS = ("depth", "drawn")  # the kinds whose sequence lengths are the point: group_starts adds no start to them
+# the seed of the drawn starts: the first with which all three groups -- rolled by g, from rows 0, 100 and 1000 -- hold a
+# sequence of more than 64 rows and one of one row in both updates (lstm_learner_io_cases.DRAWN_SEED gives group 2 neither)
+DRAWN_SEED = 69
+# the group limit: RF_POPULATION_MAX_GROUPS groups of m = T = B = 1 on the least network, by population_io_cases' scheme:
+# group g has parameter set g % 7, input block g % 5 (its state on level g % 5) and hyper-parameter set g % 3; a sampled
+# forward draws from generator g % 11; firsts[g] = 1 = N (outside) where g % 11 = 5
+LIMIT_GROUPS, LIMIT_PERIODS, LIMIT_GENERATORS = 65535, (7, 5, 3), 11
+LIMIT_STARTS = (0, 0, 1, 0, 255)  # the start byte of block j: three of the five levels are read through the state
+LIMIT_OUTSIDE = (11, 5)  # g % 11 == 5
 INVALID, NONFINITE = 1, 2  # RF_PPO_INVALID, RF_PPO_NONFINITE
 
 
@@ -112,17 +145,17 @@ def regrouped_state(state, groups, per_group):
 
 # ---- update ----------------------------------------------------------------------------------------------------------------
 def group_starts(groups, steps, per_group, kind="mixed"):
-    """uint8 [T + 1][G m]: lstm_learner_io_cases.starts_of per group, group g's columns rolled by g and its bytes changed,
-    so the sequence structure differs per group."""
+    """uint8 [T + 1][G m]: lstm_learner_io_cases.starts_of per group (drawn: from DRAWN_SEED), group g's columns rolled by g
+    and -- but for LAYOUT_KINDS -- its bytes changed, so the sequence structure differs per group."""
     columns = []
     for g in range(groups):
         if kind == "some":  # (any shape: environment 0 starts at t = 0, environment 1 at the last step)
             piece = np.zeros((steps + 1, per_group), dtype=np.uint8)
             piece[0, 0], piece[steps - 1, per_group - 1] = 1, 255
         else:
-            piece = lstm_learner_cases.starts_of(kind, steps, per_group)
+            piece = lstm_learner_cases.starts_of(kind, steps, per_group, seed=DRAWN_SEED)
         piece = np.roll(piece, g, axis=1)
-        if g % 3 == 2 and steps > 1:
+        if g % 3 == 2 and steps > 1 and kind not in LAYOUT_KINDS:
             piece[1, 0] = 2  # (one more start, in the middle of environment 0's rows)
         columns.append(piece)
     return np.concatenate(columns, axis=1)
@@ -204,6 +237,133 @@ def firsts_of(firsts, update, rows):
 def wide_firsts():
     rows = WIDE_UPDATE["steps"] * WIDE_UPDATE["per_group"]
     return tuple((7 * g) % rows for g in range(WIDE_UPDATE["groups"]))
+
+
+def layout_shape(name, critic_lstm):
+    """(index, critic_lstm, G, T, m), kind, firsts, B of a case of LAYOUT_CASES."""
+    case = LAYOUT_CASES[name]
+    steps, per_group, kind, _, batch = lstm_learner_cases.LIMIT_LAYOUTS[case["layout"]]
+    return (case["index"], critic_lstm, len(case["firsts"]), steps, per_group), kind, case["firsts"], batch
+
+
+def layout_twin_updates(name, critic_lstm):
+    shape, kind, firsts, batch = layout_shape(name, critic_lstm)
+    return twin_updates(*shape, firsts, batch, LAYOUT_CASES[name]["updates"], kind)
+
+
+def layout_update_promises(name, critic_lstm):
+    """No comparison of a layout case is vacuous: every group is taken in every update (flags 0), every group whose
+    learning rate is not 0 ends with other parameters than it began with (the one whose is 0 with the same), parameters
+    differ per group and every hyper-parameter between neighbours."""
+    from reinfocus_amd.environments import harness
+
+    shape, kind, firsts, batch = layout_shape(name, critic_lstm)
+    spec, twin, _ = update_inputs(*shape, kind)
+    want = layout_twin_updates(name, critic_lstm)
+    assert len(want) == LAYOUT_CASES[name]["updates"] and all((stats[:, 7] == 0).all() for _, _, stats in want)
+    hypers = harness.PopulationLearner(fresh_twin(spec, twin), **hypers_of(shape[2])).hypers()
+    assert len({bits(row) for row in twin.params}) == shape[2]
+    for one, other in zip(hypers, hypers[1:]):
+        assert all(x != y for x, y in zip(one, other))
+    assert [h.learning_rate == 0 for h in hypers] == [g == 1 for g in range(shape[2])]
+    for g, h in enumerate(hypers):
+        assert (bits(want[-1][0][g]) == bits(twin.params[g])) == (h.learning_rate == 0), f"group {g}"
+    if len(want) > 1:  # (the optimizer header and moments the first wrote, the second read)
+        assert bits(want[0][1]) != bits(want[1][1])
+
+
+# ---- the limit: 65535 groups of one environment, one step ---------------------------------------------------------------
+def limit_spec(critic_lstm):
+    return spec_of(0, critic_lstm)
+
+
+@functools.lru_cache(maxsize=None)
+def limit_parts(critic_lstm):
+    """(7 packed parameter sets; 5 input blocks of one row -- obs, final_obs, start byte, state [2][2][1][1] around level
+    0.125 (1 + j) (every plane its own value), action, log_prob, advantage, return, the rollout's stored states
+    [2][2][2][1][1] --; 3 hyper-parameter sets; 11 generators).  adam_eps is large, so the first Adam step depends on the
+    gradient's size."""
+    from reinfocus_amd.environments import learner
+
+    spec = limit_spec(critic_lstm)
+    rng = np.random.default_rng(65535)
+    params = [np.abs(spec.pack(lstm_cases.state_dict(spec, 700 + k))) + F32(0.25 + 0.125 * k) for k in range(LIMIT_PERIODS[0])]
+    blocks = []
+    for j in range(LIMIT_PERIODS[1]):
+        level = F32(0.125 * (1 + j)) + F32(0.03125) * np.arange(4, dtype=F32).reshape(2, 2, 1, 1)
+        blocks.append(dict(observations=np.array([[0.5 + 0.75 * j]], dtype=F32), final=np.array([[3.0 - 0.5 * j]], dtype=F32),
+                           starts=np.array([LIMIT_STARTS[j]], dtype=np.uint8), state=level.astype(F32),
+                           actions=np.array([j % 2], dtype=np.int64), log_probs=np.array([-0.7 + 0.1 * j], dtype=F32),
+                           advantages=rng.standard_normal(1).astype(F32), returns=rng.standard_normal(1).astype(F32),
+                           episode_starts=np.array([[LIMIT_STARTS[j]], [1]], dtype=np.uint8),
+                           lstm_states=np.stack([level, level + F32(7.0)]).astype(F32)))
+    hypers = [learner.Hyper(learning_rate=1e-2 / (1 + h), clip_range=0.1 + 0.1 * h, ent_coef=0.01 * (1 + h),
+                            vf_coef=0.5 + 0.25 * h, max_grad_norm=(1e6, 0.5, 0.05)[h], beta1=0.9 - 0.1 * h,
+                            beta2=0.999 - 0.01 * h, adam_eps=(0.1, 0.3, 1.0)[h], normalize_advantage=h % 2)
+              for h in range(LIMIT_PERIODS[2])]
+    return params, blocks, hypers, [np.random.PCG64DXSM(900 + i) for i in range(LIMIT_GENERATORS)]
+
+
+@functools.lru_cache(maxsize=None)
+def limit_results(critic_lstm):
+    """By the existing twin functions.  forwards[deterministic][k][j][i]: (actions, values, log_probs, final_values, next
+    state [2][2][1][1]) of parameter set k on block j with the draw of generator i after CONSUMED[1] draws; updates[c]: the
+    first update's (params, state, stats) of combination c (k = c % 7, j = c % 5, h = c % 3) from a fresh optimizer."""
+    from reinfocus_amd.environments import learner, lstm, lstm_learner
+
+    spec = limit_spec(critic_lstm)
+    params, blocks, hypers, generators = limit_parts(critic_lstm)
+    draws = []
+    for generator in generators:
+        moved = np.random.PCG64DXSM()
+        moved.state = generator.state
+        draws.append(np.random.Generator(moved.advance(CONSUMED[1])).random(1)[0])
+    forwards = {}
+    for deterministic in (False, True):
+        forwards[deterministic] = [[[None] * LIMIT_GENERATORS for _ in blocks] for _ in params]
+        for k, packed in enumerate(params):
+            for j, block in enumerate(blocks):
+                for i, u in enumerate(draws):
+                    got = lstm.lstm_numpy(spec, packed, block["observations"], block["starts"], block["state"], block["final"],
+                                          None if deterministic else np.array([u]), deterministic)
+                    forwards[deterministic][k][j][i] = tuple(got[name] for name in ORDER) + (got["state"],)
+    updates = []
+    for c in range(105):
+        k, j, h = (c % period for period in LIMIT_PERIODS)
+        batch = {key: blocks[j][key] for key in learner.BATCH_KEYS}
+        updates.append(lstm_learner.lstm_update_numpy(spec, params[k], learner.fresh_state(spec), batch,
+                                                      blocks[j]["episode_starts"], blocks[j]["lstm_states"], 1, 1, 0, 1, hypers[h]))
+    return forwards, updates
+
+
+def limit_arrays(critic_lstm, groups=LIMIT_GROUPS):
+    """What group g gets and what it must give, for g = 0 .. groups - 1: (inputs dict -- the forward's arrays, the update's
+    parts, "firsts", "outside" (where firsts[g] = N), "hyper", "gens" --, {deterministic: wanted (actions, values,
+    log_probs, final_values, state [2][2][G][1])}, wanted (params [G][P], states [G][S], stats [G][8]) of the groups that
+    are inside)."""
+    from reinfocus_amd.environments import learner, policy, population
+
+    params, blocks, hypers, generators = limit_parts(critic_lstm)
+    forwards, updates = limit_results(critic_lstm)
+    g = np.arange(groups)
+    k, j, h, c, i = g % LIMIT_PERIODS[0], g % LIMIT_PERIODS[1], g % LIMIT_PERIODS[2], g % 105, g % LIMIT_GENERATORS
+    outside = g % LIMIT_OUTSIDE[0] == LIMIT_OUTSIDE[1]
+    inputs = {"params": np.stack(params)[k], "hyper": population.hyper_records(hypers)[h], "outside": outside,
+              "firsts": outside.astype(np.int32),
+              "gens": np.array([policy.generator_words(generator) for generator in generators], dtype=np.uint64)[i]}
+    for key in ("observations", "final", "starts") + tuple(key for key in learner.BATCH_KEYS if key != "observations"):
+        inputs[key] = np.concatenate([block[key] for block in blocks])[j]
+    inputs["state"] = np.ascontiguousarray(np.concatenate([block["state"] for block in blocks], axis=2)[:, :, j, :])
+    inputs["episode_starts"] = np.ascontiguousarray(np.concatenate([block["episode_starts"] for block in blocks], axis=1)[:, j])
+    inputs["lstm_states"] = np.ascontiguousarray(np.concatenate([block["lstm_states"] for block in blocks], axis=3)[:, :, :, j, :])
+    at = (k * len(blocks) + j) * LIMIT_GENERATORS + i  # (the place of (k, j, i) in a table's order)
+    wanted_forward = {}
+    for deterministic, table in forwards.items():
+        results = [result for per_set in table for per_block in per_set for result in per_block]
+        wanted_forward[deterministic] = tuple(np.concatenate([result[part] for result in results])[at] for part in range(4)) + (
+            np.ascontiguousarray(np.concatenate([result[4] for result in results], axis=2)[:, :, at, :]),)
+    wanted_update = tuple(np.stack([update[part] for update in updates])[c] for part in range(3))
+    return inputs, wanted_forward, wanted_update
 
 
 def hostcheck():
@@ -423,6 +583,7 @@ class _Learner:
     """The raw arrays of rf_lstm_ppo_update_grouped on the device, parameters, states and stats between guard floats."""
 
     def __init__(self, torch, ctx, spec, twin, parts, hypers, batch):
+        """hypers: learner.Hyper per group, or the packed records."""
         from reinfocus_amd.environments import learner, population
 
         self.torch, self.ctx, self.spec, self.groups = torch, ctx, spec, twin.groups
@@ -436,7 +597,8 @@ class _Learner:
         self.state.copy_(torch.from_numpy(fresh))
         self.whole_stats, self.stats = _guarded_floats(torch, np.zeros((self.groups, 8), dtype=F32))
         self.stats.view(torch.int32).fill_(SENTINEL)
-        self.hyper = torch.from_numpy(population.hyper_records(hypers).view(np.float64).copy()).cuda()
+        records = hypers if isinstance(hypers, np.ndarray) else population.hyper_records(hypers)
+        self.hyper = torch.from_numpy(records.view(np.float64).copy()).cuda()
         size = ctx.lstm_ppo_grouped_workspace_size(spec.critic_desc(), self.groups, self.per_group, self.steps, batch)
         assert size > 0 and size % 8 == 0
         self.whole_workspace = torch.full((size // 4 + 4,), SENTINEL, dtype=torch.int32, device="cuda").view(torch.float32)
@@ -444,7 +606,7 @@ class _Learner:
         self.batch = batch
 
     def update(self, firsts, changed=(), stream=None):
-        self.enqueue(self.torch.tensor(list(firsts), dtype=self.torch.int32, device="cuda"), changed, stream)
+        self.enqueue(self.torch.from_numpy(np.array(firsts, dtype=np.int32)).cuda(), changed, stream)
         self.torch.cuda.synchronize()
         return self.outputs()
 
@@ -488,8 +650,6 @@ def update_case(torch, ctx, index, critic_lstm, batch):
     """rf_lstm_ppo_update_grouped against the twin population over two consecutive updates: parameters, optimizer states
     and stats as bytes between guards; then G stand-alone rf_lstm_ppo_update / rf_lstm_critic_ppo_update launches on
     contiguous slice copies give the same bytes."""
-    from reinfocus_amd.environments import learner
-
     u = UPDATE
     rows = u["steps"] * u["per_group"]
     spec, twin, hypers, device = _learner_of(torch, ctx, index, critic_lstm, u["groups"], u["steps"], u["per_group"], batch)
@@ -499,29 +659,114 @@ def update_case(torch, ctx, index, critic_lstm, batch):
     assert device.guards_kept(), "a guard was written"
     assert all((stats[:, 7] == 0).all() for _, _, stats in want)
     assert bits(want[1][0][1]) == bits(twin.params[1]) and bits(want[1][0][0]) != bits(twin.params[0])  # (lr 0: group 1)
-    # the same device, G stand-alone learners over contiguous copies of the groups' slices
     _, _, parts = update_inputs(index, critic_lstm, u["groups"], u["steps"], u["per_group"])
+    _alone_updates(torch, ctx, spec, twin, hypers, parts, u["firsts"], batch, want)
+
+
+def _alone_updates(torch, ctx, spec, twin, hypers, parts, firsts, batch, want):
+    """The same device, G stand-alone learners over contiguous copies of the groups' slices: len(want) consecutive
+    rf_lstm_ppo_update (rf_lstm_critic_ppo_update) launches each give the bytes of want[update][.][g]."""
+    from reinfocus_amd.environments import learner
+
+    critic_lstm, groups = spec.enable_critic_lstm, twin.groups
+    steps, per_group = parts["n_steps"], parts["num_envs"] // groups
     update_alone = ctx.lstm_ppo_update if critic_lstm else ctx.lstm_critic_ppo_update
     size_alone = (ctx.lstm_ppo_workspace_size(spec.desc(), batch) if critic_lstm
                   else ctx.lstm_critic_workspace_size(spec.critic_desc(), batch))
     desc = spec.desc() if critic_lstm else spec.critic_desc()
     stream = torch.cuda.current_stream().cuda_stream
-    for g in range(u["groups"]):
-        piece = {key: torch.from_numpy(value).cuda() for key, value in group_slices(parts, u["groups"], g).items()
+    for g in range(groups):
+        piece = {key: torch.from_numpy(value).cuda() for key, value in group_slices(parts, groups, g).items()
                  if isinstance(value, np.ndarray)}
         params = torch.from_numpy(twin.params[g].copy()).cuda()
         state = torch.from_numpy(learner.fresh_state(spec)).cuda()
         workspace = torch.zeros(size_alone // 4, dtype=torch.float32, device="cuda")
         stats = torch.zeros(8, dtype=torch.float32, device="cuda")
-        for update in range(u["updates"]):
-            update_alone(desc, hypers[g], params.data_ptr(), state.data_ptr(), workspace.data_ptr(), u["steps"],
-                         u["per_group"], piece["observations"].data_ptr(), piece["actions"].data_ptr(),
-                         piece["log_probs"].data_ptr(), piece["advantages"].data_ptr(), piece["returns"].data_ptr(),
-                         piece["episode_starts"].data_ptr(), piece["lstm_states"].data_ptr(),
-                         firsts_of(u["firsts"], update, rows)[g], batch, stats.data_ptr(), stream)
+        for update in range(len(want)):
+            update_alone(desc, hypers[g], params.data_ptr(), state.data_ptr(), workspace.data_ptr(), steps, per_group,
+                         piece["observations"].data_ptr(), piece["actions"].data_ptr(), piece["log_probs"].data_ptr(),
+                         piece["advantages"].data_ptr(), piece["returns"].data_ptr(), piece["episode_starts"].data_ptr(),
+                         piece["lstm_states"].data_ptr(), firsts_of(firsts, update, steps * per_group)[g], batch,
+                         stats.data_ptr(), stream)
             torch.cuda.synchronize()
             _same_update((params.cpu().numpy(), state.cpu().numpy(), stats.cpu().numpy()),
                          tuple(x[g] for x in want[update]), f"stand-alone group {g}, update {update}")
+
+
+def layout_case(torch, ctx, name, critic_lstm):
+    """rf_lstm_ppo_update_grouped on a case of LAYOUT_CASES against the twin population over the case's consecutive
+    updates, group by group: parameters, optimizer states and stats as bytes between guard floats, the workspace of exactly
+    rf_lstm_ppo_grouped_workspace_size(B)'s bytes between guards; where the case says so, also G stand-alone launches on
+    contiguous slice copies."""
+    shape, kind, firsts, batch = layout_shape(name, critic_lstm)
+    groups, steps, per_group = shape[2:]
+    spec, twin, hypers, device = _learner_of(torch, ctx, *shape, batch, kind=kind)
+    want = layout_twin_updates(name, critic_lstm)
+    for update in range(len(want)):
+        got = device.update(firsts_of(firsts, update, steps * per_group))
+        for g in range(groups):
+            _same_update(tuple(x[g] for x in got), tuple(x[g] for x in want[update]), f"update {update}, group {g}")
+    assert device.guards_kept(), "a guard was written"
+    layout_update_promises(name, critic_lstm)
+    if LAYOUT_CASES[name]["alone"]:
+        _alone_updates(torch, ctx, spec, twin, hypers, update_inputs(*shape, kind)[2], firsts, batch, want)
+
+
+def _groups_that_differ(got, want, axis=0):
+    """Indices along `axis` (the groups') at which two equally shaped arrays differ in a byte."""
+    x = np.moveaxis(np.ascontiguousarray(got), axis, 0)
+    y = np.moveaxis(np.ascontiguousarray(want), axis, 0)
+    x, y = (np.ascontiguousarray(a).view(np.uint8).reshape(a.shape[0], -1) for a in (x, y))
+    return np.flatnonzero((x != y).any(axis=1))
+
+
+def group_limit_case(torch, ctx, critic_lstm):
+    """RF_POPULATION_MAX_GROUPS groups of one environment on the least network (limit_arrays): rf_lstm_forward_grouped
+    sampled (every generator CONSUMED[1] draws on) and deterministic with the state in place, then one
+    rf_lstm_ppo_update_grouped at m = T = B = 1 of fresh optimizers: every output byte of every group against its
+    combination's result.  The groups whose firsts[g] = 1 = N carry RF_PPO_INVALID and keep parameters and optimizer state;
+    all others, their neighbours included, equal the twin."""
+    from reinfocus_amd.environments import learner, policy
+
+    spec, groups = limit_spec(critic_lstm), LIMIT_GROUPS
+    inputs, wanted_forward, wanted_update = limit_arrays(critic_lstm)
+    params, obs, final_obs, starts = (torch.from_numpy(inputs[key]).cuda() for key in ("params", "observations", "final", "starts"))
+    table = torch.from_numpy(inputs["gens"].view(np.int64)).cuda()
+    for deterministic in (False, True):
+        whole, out = _guarded(torch, groups)
+        whole_state, state = _guarded_floats(torch, inputs["state"])
+        _forward(torch, ctx, spec, groups, 1, params, obs, starts, final_obs, state, state, table, CONSUMED[1],
+                 policy.DETERMINISTIC if deterministic else 0, out)
+        torch.cuda.synchronize()
+        for name, wanted in zip(ORDER, wanted_forward[deterministic]):
+            differ = _groups_that_differ(out[name].cpu().numpy(), wanted)
+            assert differ.size == 0, f"deterministic {deterministic}: {name} differ in {differ.size} groups, first {differ[:4]}"
+            assert _untouched(whole[name][0]) and _untouched(whole[name][groups + 1]), f"a guard row of {name} was written"
+        differ = _groups_that_differ(state.cpu().numpy(), wanted_forward[deterministic][4], axis=2)
+        assert differ.size == 0, f"deterministic {deterministic}: the state differs in {differ.size} groups, first {differ[:4]}"
+        assert _guards_kept(whole_state), "a guard float of the state was written"
+    parts = {key: inputs[key] for key in learner.BATCH_KEYS + ("episode_starts", "lstm_states")}
+    parts.update(n_steps=1, num_envs=groups)
+    device = _Learner(torch, ctx, spec, _Packed(inputs["params"]), parts, inputs["hyper"], 1)
+    before = device.outputs()
+    got = device.update(inputs["firsts"])
+    assert device.guards_kept(), "a guard was written"
+    inside, outside = ~inputs["outside"], inputs["outside"]
+    assert outside.sum() == 5958 and outside[5] and outside[16] and not outside[4] and not outside[6]
+    for name, x, y, kept in zip(("parameters", "optimizer states", "stats"), got, wanted_update, before):
+        differ = _groups_that_differ(x[inside], y[inside])
+        assert differ.size == 0, f"{name} differ in {differ.size} groups, first {np.flatnonzero(inside)[differ[:4]]}"
+        if name != "stats":
+            differ = _groups_that_differ(x[outside], kept[outside])
+            assert differ.size == 0, f"{name} of {differ.size} groups outside moved, first {np.flatnonzero(outside)[differ[:4]]}"
+    assert (got[2][outside, 7] == INVALID).all(), "a group whose first row lies outside does not carry RF_PPO_INVALID"
+
+
+class _Packed:
+    """What _Learner reads of a twin population, around packed parameters [G][P]."""
+
+    def __init__(self, params):
+        self.params, self.groups = params, params.shape[0]
 
 
 def limit_case(torch, ctx):
@@ -932,6 +1177,13 @@ def run_cases(path):
         wide_update_case(torch, ctx)
     with record.case("limit"):
         limit_case(torch, ctx)
+    for name, case in LAYOUT_CASES.items():
+        for critic_lstm in case["critics"]:
+            with record.case(f"layout/{name}/{critic_name(critic_lstm)}"):
+                layout_case(torch, ctx, name, critic_lstm)
+    for critic_lstm in CRITICS:
+        with record.case(f"group-limit/{critic_name(critic_lstm)}"):
+            group_limit_case(torch, ctx, critic_lstm)
     with record.case("kernel-refusals"):
         kernel_refusal_case(torch, ctx)
     ctx.close()

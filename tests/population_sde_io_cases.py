@@ -36,6 +36,13 @@ UPDATE_SHAPES = pop_cases.UPDATE_SHAPES  # (B, m): m T = 12 (B = 5, 8) and 44 (B
 EPOCHS = pop_cases.EPOCHS
 WIDE = ((0, 64, 8), (1, 64, 8), (0, 65, 8), (1, 65, 8))  # (network, G, m) of noise and forward
 WIDE_UPDATE = dict(index=1, groups=64, per_group=8, steps=32, batch=64)
+# large minibatches, as population_io_cases.LARGE_CASES (m = 8, T = 128, N = 1024 rows per group): 512, 513, 1000 and 1024
+# at G = 3 on NETWORKS[1], and 513 at G = 2 on the widest network of sde_io_cases (LARGE_NETWORKS, index 2; P + L = 138 k)
+LARGE = pop_cases.LARGE
+LARGE_NETWORKS = (sde_cases.NETWORKS[3],)
+LARGE_CASES = tuple((1, 3, batch) for batch in (512, 513, 1000, 1024)) + ((2, 2, 513),)  # (network, G, B)
+LARGE_ALONE = (1, 3, 1000)
+ALONE_ENTRIES = ("sde_update", "sde_workspace_size")
 LIMIT_GROUPS, LIMIT_PERIODS, LIMIT_GENERATORS = 65535, (7, 5, 3), 11
 LIMIT_NETWORK = (1, (1,), (1,), "relu")
 E2E = dict(envs=6, groups=3, steps=rollout_cases.T, epochs=2, batch=4, iterations=2, freqs=[-1, 1, 3],
@@ -50,7 +57,7 @@ minibatches, update_permutations, twin_states = pop_cases.minibatches, pop_cases
 
 
 def spec_of(index):
-    return sde_cases.spec_of(NETWORKS[index])
+    return sde_cases.spec_of((NETWORKS + LARGE_NETWORKS)[index])
 
 
 def twin_policy(index, groups, base=100, hot=None):
@@ -175,6 +182,21 @@ def wide_update_inputs():
 def wide_twin_updates():
     spec, twin, flat, hypers, order = wide_update_inputs()
     return _chained(twin, flat, hypers, order)
+
+
+def large_inputs(index, groups, batch):
+    """(spec, twin, flat, hypers' keywords, the index arrays of the updates) of one of LARGE_CASES."""
+    spec, twin, flat = update_batch(index, groups, LARGE["per_group"], seed=3, steps=LARGE["steps"])
+    return spec, twin, flat, group_hypers(groups), pop_cases.large_indices(groups, batch, 900 + 7 * index + batch)
+
+
+@functools.lru_cache(maxsize=None)
+def large_twin_updates(index, groups, batch):
+    spec, twin, flat, hypers, order = large_inputs(index, groups, batch)
+    return _chained(twin, flat, hypers, order)
+
+
+large_update_promises = pop_cases.large_update_promises
 
 
 def isolation_inputs():
@@ -912,6 +934,9 @@ def run_cases(path):
             forward_case(torch, ctx, index, groups, per_group)
     with record.case("update/wide"):
         wide_update_case(torch, ctx)
+    for index, groups, batch in LARGE_CASES:
+        with record.case(f"update/large/{index}/{groups}/{batch}"):
+            pop_cases.large_update_case(torch, ctx, index, groups, batch, sys.modules[__name__])
     with record.case("limit"):
         limit_case(torch, ctx)
     with record.case("isolation"):

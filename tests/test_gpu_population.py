@@ -7,8 +7,8 @@ As tests/test_gpu_policy.py: the cases need torch and the library in one process
 that imports torch first (tests/population_io_cases.py), started once per session; each test below looks its case up.
 tests/test_population_logic.py holds the twins to G independent existing twins on the CPU, on the same inputs.
 
-Development run on an MI355X: all 33 tests pass, the child process takes 4.4 s (2.5 s before the cases at 64, 65, 512 and
-65535 groups)."""
+Development run on an MI355X: all 38 tests pass, the child process takes 4.4 s (4.4 s on the same machine before the five
+cases at B = 512 .. 1024, whose twins take 0.1 to 0.2 s each; 2.5 s before the cases at 64, 65, 512 and 65535 groups)."""
 
 import json
 import os
@@ -86,6 +86,21 @@ def test_grouped_update_at_64_groups_on_the_tuned_shape(recorded):
     epoch that takes it the group carries RF_PPO_NONFINITE and keeps its bytes.  Parameters and states lie between guard
     rows, the workspace of exactly rf_ppo_grouped_workspace_size's bytes between guard floats."""
     _passed(recorded, "update/wide")
+
+
+@pytest.mark.parametrize("index,groups,batch", cases.LARGE_CASES)
+def test_grouped_update_at_large_minibatches(index, groups, batch, recorded):
+    """rf_ppo_update_grouped on ppo_tuned.yml's ContinuousJumps shape, m = 8, T = 128 (N = 1024 rows per group), at the
+    sizes the ungrouped update is held to: B = 512 (the last single trip of the s_red reductions), 513 (the second trip,
+    a ragged last tile), 1000 (no multiple of the tile) and 1024 (RF_PPO_MAX_BATCH) at G = 3 on the network whose widths
+    are no multiple of a wave (P = 1324), and B = 513 at G = 2 on stable-baselines3's default network (P = 11918).
+    index is [G][B], every group's row its own: a permutation at B = N, drawn with repeats below.  Two consecutive
+    updates against PopulationLearner, every group's parameters, optimizer state and stats as bytes; parameters and
+    states between guard rows, the workspace of exactly rf_ppo_grouped_workspace_size's bytes between guard floats.  No
+    group is skipped and the group with learning_rate 0 alone keeps its parameters (tests/test_population_logic.py shows
+    the same without a GPU).  At B = 513, G = 3 also three stand-alone rf_ppo_update launches on contiguous copies of the
+    groups' slices give the same bytes."""
+    _passed(recorded, f"update/large/{index}/{groups}/{batch}")
 
 
 def test_forward_and_update_at_the_group_limit(recorded):

@@ -9,7 +9,8 @@ process that imports torch first (tests/population_lstm_io_cases.py), started on
 test below looks its case up.  tests/test_population_lstm_logic.py holds the twins to G independent existing twins on the
 CPU, on the same inputs.
 
-Development run on an MI355X: all 67 tests pass, the child process takes 8.6 s."""
+Development run on an MI355X: all 82 tests pass, the child process takes 15.2 s (7.4 s on the same machine before the
+cases on the limit layouts and at 65535 groups; the difference is the numpy twins of the 13 layout cases)."""
 
 import json
 import os
@@ -90,6 +91,46 @@ def test_grouped_update_equals_the_twin_population(critic, index, batch, recorde
 def test_update_at_the_widest_cell(recorded):
     """H = 256 (sb3-contrib's default network), G = 2, m = 2, T = 3, B = 6 = m T, both critic kinds, against the twin."""
     _passed(recorded, "limit")
+
+
+_LAYOUTS = [(name, cases.critic_name(critic_lstm)) for name, case in cases.LAYOUT_CASES.items()
+            for critic_lstm in case["critics"]]
+
+
+@pytest.mark.parametrize("name,critic", _LAYOUTS)
+def test_grouped_update_on_the_limit_layouts(name, critic, recorded):
+    """rf_lstm_ppo_update_grouped on the layouts the ungrouped update is held to (tests/lstm_learner_io_cases.py's
+    LIMIT_LAYOUTS), every group with its own parameters, hyper-parameters, first row and -- its columns rolled -- sequence
+    structure, against PopulationLearner group by group: parameters, optimizer states and stats as bytes between guard
+    floats, the workspace of exactly rf_lstm_ppo_grouped_workspace_size(B)'s bytes between guards.
+    depth: T = 17, m = 4, sequences of 1, 8, 9, 16 and 17 rows (past the 8 rows whose weights both walks load before
+    the first is used: the steady state of that prefetch and its tails), through the group's lane window of stride G m.
+    G = 3 on ppo_lstm_tuned.yml's network at B = 65 with firsts (0, 5, 30) and at B = 68 = N with firsts (5, 0, 67), two
+    groups wrapping at different rows; both also as three stand-alone rf_lstm_ppo_update (rf_lstm_critic_ppo_update)
+    launches on contiguous slice copies.  G = 2 on sb3-contrib's default network (H = 256: every thread of a block owns a
+    unit, parameters at g P) at B = 65.  Two consecutive updates each.
+    untuned: ppo_lstm_untuned.yml's T = 128, m = 8, B = 128 with drawn starts, firsts (0, 100, 1000): group 1 crosses an
+    environment boundary, group 2 wraps, every group holds a sequence of more than 64 rows and one of one row; G = 3 on
+    the tuned network (two updates) and G = 2 on the default network with the LSTM critic, the real shape (one update).
+    wave: T = 16, m = 64, N = 1024, G = 2 on the tuned network, one update: every row a start at B = 1024 from rows
+    (7, 0) -- 1024 one-row sequences per group, 128 MLP tiles, the second trip of the reductions --, and no flagged start
+    at B = 513 from rows (0, 9).
+    tests/test_population_lstm_logic.py shows without a GPU that the layouts hold these sequences and that no update of the
+    twin is skipped or leaves a group with a learning rate where it was."""
+    _passed(recorded, f"layout/{name}/{critic}")
+
+
+@_critic
+def test_forward_and_update_at_the_group_limit(critic, recorded):
+    """G = RF_POPULATION_MAX_GROUPS = 65535 groups of one environment on the least network.  rf_lstm_forward_grouped at
+    m = 1, sampled (generator g % 11, 2^32 + 5 draws taken before) and deterministic, the state in place;
+    rf_lstm_ppo_update_grouped at m = T = B = 1 of fresh optimizers.  Group g has parameter set g % 7, input block g % 5
+    with its state on a level of its own and hyper-parameter set g % 3, so neighbours differ in all of them and a wrong
+    stride of parameters, states, workspace, stats, rows or state planes shows at every g; every output byte of every
+    group -- the next state included -- is compared with the twin functions' result for its combination.  Where
+    g % 11 = 5, firsts[g] = 1 = N: those 5958 groups carry RF_PPO_INVALID and keep parameters and optimizer state byte
+    for byte, their neighbours equal the twin.  (65536 groups are refused: test_refusals_come_before_anything_is_enqueued.)"""
+    _passed(recorded, f"group-limit/{critic}")
 
 
 @_critic

@@ -9,7 +9,8 @@ process that imports torch first (tests/population_sde_io_cases.py), started onc
 test below looks its case up.  tests/test_population_sde_logic.py holds the twins to G independent existing twins on the
 CPU, on the same inputs.
 
-Development run on an MI355X: all 54 tests pass, the child process takes 3.3 s."""
+Development run on an MI355X: all 59 tests pass, the child process takes 4.1 s (3.3 s on the same machine before the five
+cases at B = 512 .. 1024; the twin of the two 256-256 groups takes most of the difference)."""
 
 import json
 import os
@@ -98,6 +99,20 @@ def test_grouped_update_at_64_groups_on_the_tuned_shape(recorded):
     hyper-parameters that differ between neighbouring groups: all 64 groups as bytes; the workspace has exactly
     rf_sde_grouped_workspace_size's bytes between guard floats."""
     _passed(recorded, "update/wide")
+
+
+@pytest.mark.parametrize("index,groups,batch", cases.LARGE_CASES)
+def test_grouped_update_at_large_minibatches(index, groups, batch, recorded):
+    """rf_sde_update_grouped (ppo_backward_kernel<true, true>) on ppo_tuned.yml's ContinuousJumps shape, m = 8, T = 128
+    (N = 1024 rows per group): B = 512, 513 (the second trip of the s_red reductions, a ragged last tile), 1000 and 1024
+    (RF_PPO_MAX_BATCH) at G = 3 on the network whose vf widths are no multiple of a wave (L = 64), and B = 513 at G = 2 on
+    the widest network of tests/sde_io_cases.py (256-256 both nets).  index is [G][B], every group's row its own: a
+    permutation at B = N, drawn with repeats below.  Two consecutive updates against PopulationLearner, every group's
+    parameters (log_std included), optimizer state and stats as bytes, between guard rows; the workspace has exactly
+    rf_sde_grouped_workspace_size's bytes between guard floats.  No group is skipped, and the group with learning_rate 0
+    alone keeps its parameters.  At B = 1000, G = 3 also three stand-alone rf_sde_update launches on contiguous copies of
+    the groups' slices give the same bytes."""
+    _passed(recorded, f"update/large/{index}/{groups}/{batch}")
 
 
 def test_noise_forward_and_update_at_the_group_limit(recorded):

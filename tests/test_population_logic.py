@@ -3,7 +3,8 @@ PopulationPolicy / PopulationLearner against G independent existing twins (polic
 seeds, hyper-parameters and permutations, bit for bit; the size rules of the grouped entry points and the layout of the
 hyper-parameter record, through the host build of the kernels' own header (tests/popcheck); every refusal; the binding.
 At 64, 65 and 512 groups, too (the forward), at 64 groups on ppo_tuned.yml's first shape (the update), and the 105
-combinations that stand for the 65535 groups of the limit case are pairwise distinct."""
+combinations that stand for the 65535 groups of the limit case are pairwise distinct.  The large minibatches (B = 512,
+513, 1000, 1024 on m = 8, T = 128) hold what their docstrings promise, and no update in them is skipped."""
 
 import ctypes
 import os
@@ -170,6 +171,64 @@ def test_wide_population_learner_equals_independent_learners():
             assert bits(want[update][2][g]) == bits(stats), f"update {update}, group {g}: stats differ"
             assert bits(want[update][0][g]) == bits(member.policy.params), f"update {update}, group {g}: params differ"
             assert bits(want[update][1][g]) == bits(member.state), f"update {update}, group {g}: state differs"
+
+
+def _alone(member, h):
+    return harness.Learner(member, learning_rate=h.learning_rate, clip_range=h.clip_range, ent_coef=h.ent_coef,
+                           vf_coef=h.vf_coef, max_grad_norm=h.max_grad_norm, normalize_advantage=bool(h.normalize_advantage),
+                           betas=(h.beta1, h.beta2), adam_eps=h.adam_eps)
+
+
+def large_case_holds(module, members, index, groups, batch, sizes=None):
+    """What a case of LARGE_CASES (this population's or the gSDE one's) promises, and that its twin population is G
+    stand-alone learners over contiguous copies of the groups' slices.  sizes: the host build's (grouped state size,
+    grouped workspace size, ungrouped state size, ungrouped workspace size), where there is one."""
+    large = module.LARGE
+    rows = large["per_group"] * large["steps"]
+    assert (rows, large["updates"]) == (1024, 2) and batch <= rows
+    spec, twin, flat, keywords, order = module.large_inputs(index, groups, batch)
+    before = twin.params.copy()
+    want = module.large_twin_updates(index, groups, batch)
+    module.large_update_promises(want, before, keywords)
+    assert len({bits(row) for row in before}) == groups, "two groups share their parameters"
+    hypers = harness.PopulationLearner(twin, **keywords).hypers()
+    for g, (one, other) in enumerate(zip(hypers, hypers[1:])):
+        assert all(x != y for x, y in zip(one, other)), f"groups {g} and {g + 1} share a hyper-parameter"
+    assert len(order) == 2 and bits(order[0]) != bits(order[1])
+    for index_rows in order:
+        assert index_rows.shape == (groups, batch) and index_rows.dtype == np.int64
+        assert index_rows.min() >= 0 and index_rows.max() < rows
+        assert len({bits(row) for row in index_rows}) == groups, "two groups share their index row"
+        for row in index_rows:  # (a permutation of the group's rows at B = N, drawn with repeats below)
+            assert (len(np.unique(row)) == batch) == (batch == rows)
+    alone = [_alone(member, h) for member, h in zip(members, hypers)]
+    for update, index_rows in enumerate(order):
+        for g, member in enumerate(alone):
+            piece = {key: np.ascontiguousarray(flat[key][g * rows:(g + 1) * rows]) for key in learner.BATCH_KEYS}
+            stats = member.update(piece, index_rows[g].copy())
+            assert bits(want[update][2][g]) == bits(stats), f"update {update}, group {g}: stats differ"
+            assert bits(want[update][0][g]) == bits(member.policy.params), f"update {update}, group {g}: params differ"
+            assert bits(want[update][1][g]) == bits(member.state), f"update {update}, group {g}: state differs"
+    if sizes is None:
+        return
+    grouped_state, grouped_workspace, one_state, one_workspace = sizes
+    desc = ctypes.byref(_native.PolicyDesc(*spec.desc()))
+    assert grouped_state(desc, groups, large["per_group"]) == groups * one_state(desc) > 0
+    assert grouped_workspace(desc, groups, large["per_group"], large["steps"], batch) == groups * one_workspace(desc, batch) > 0
+
+
+@pytest.mark.parametrize("index,groups,batch", cases.LARGE_CASES)
+def test_large_minibatches_hold_what_they_promise(index, groups, batch, popcheck, ppocheck):
+    """cases.LARGE_CASES -- m = 8, T = 128, B = 512, 513, 1000 and 1024 at G = 3 on the network whose widths are no
+    multiple of a wave, 513 at G = 2 on stable-baselines3's default -- without a GPU: the index is [G][B] with a row of
+    its own per group (a permutation at B = N, repeats below), parameters differ per group and every hyper-parameter
+    between neighbours, the twin population equals G learner.Learner over contiguous slice copies byte for byte over
+    both updates, no group is skipped, every group with a learning rate ends with other parameters, and the header's
+    workspace size is G times the ungrouped one."""
+    assert cases.LARGE_ALONE in cases.LARGE_CASES
+    large_case_holds(cases, _members(index, groups, base=300), index, groups, batch,
+                     (popcheck.pop_state_size, popcheck.pop_workspace_size, ppocheck.ppc_state_size,
+                      ppocheck.ppc_workspace_size))
 
 
 def test_the_105_combinations_of_the_group_limit_are_distinct(popcheck, ppocheck):

@@ -4,8 +4,9 @@ lstm_learner.LstmLearner) over copied slices, the size rules and the grouped add
 (tests/lstmpopcheck, a host build) are G times the ungrouped sizes and the restated sequence rule per group, header,
 binding and library agree on the four entry points, and the surface refuses what it cannot express.  The arithmetic of one
 group is held to the host build of the kernels' functions by tests/test_lstm_logic.py and tests/test_lstm_learner_logic.py;
-nothing here needs a GPU.  tests/test_gpu_population_lstm.py holds the device classes and the grouped entry points to
-these twins as bytes."""
+nothing here needs a GPU.  The layout cases (sequences of 1 to 17 and of more than 64 rows, 1024 and 513 rows, H = 256) and
+the 65535 groups of the limit hold what their docstrings promise.  tests/test_gpu_population_lstm.py holds the device
+classes and the grouped entry points to these twins as bytes."""
 
 import ctypes
 import os
@@ -110,6 +111,160 @@ def test_population_learner_is_g_learners_over_slices(index, batch, critic_lstm)
     assert len(structures) == u["groups"], "the groups' sequence structures do not differ"
     assert bits(population.group_parts(parts, u["groups"], 1)["lstm_states"]) == \
         bits(cases.group_slices(parts, u["groups"], 1)["lstm_states"])
+
+
+def _alone(member, h):
+    return harness.LstmLearner(member, h.learning_rate, h.clip_range, h.ent_coef, h.vf_coef, h.max_grad_norm,
+                               bool(h.normalize_advantage), (h.beta1, h.beta2), h.adam_eps)
+
+
+def _sequences(lib, starts, groups, per_group, g, steps, first, batch):
+    """Group g's minibatch by the kernels' own helpers, held to the restated rule over the group's own columns: (the
+    lengths of its sequences in order, the lane read for every row)."""
+    own = np.ascontiguousarray(starts[:, g * per_group:(g + 1) * per_group])
+    want = lstm_learner_cases.restated_rows(own, steps, per_group, first, batch)
+    rows, start, end, lane = (np.zeros(batch, dtype=np.int32) for _ in range(4))
+    assert lib.lpop_sequences(starts.ctypes.data, groups, per_group, g, steps, first, batch, rows.ctypes.data,
+                              start.ctypes.data, end.ctypes.data, lane.ctypes.data) == groups * per_group
+    assert [int(r) for r in rows] == [row for row, _, _ in want]
+    assert [bool(f) for f in start] == [is_start for _, is_start, _ in want]
+    assert [int(x) for x in lane] == [g * per_group + row // steps for row, _, _ in want]  # (the lane read: g m + e)
+    begins = [b for b in range(batch) if want[b][1]]
+    lengths = [nxt - b for b, nxt in zip(begins, begins[1:] + [batch])]
+    assert [int(end[b]) - b for b in begins] == lengths
+    return lengths, rows
+
+
+@pytest.mark.parametrize("name", cases.LAYOUT_CASES)
+def test_layout_cases_hold_what_they_promise(name):
+    """cases.LAYOUT_CASES through the kernels' own addressing helpers (tests/lstmpopcheck) and the restated sequence rule,
+    per group and update: the depth cases hold sequences of exactly 1, 8, 9, 16 and 17 rows in every group's first
+    minibatch (at B = 68 = N group 0's first row 5 cuts its 17-row environment into 12 + 5, so it holds the other four;
+    groups 0 and 2 wrap, at different rows); every group of the untuned cases holds one sequence of more than 64 rows and
+    one of one row, group 1 crosses an environment boundary and group 2 wraps; the wave cases hold 1024 one-row
+    sequences, and 33 or 34 as the first row decides; the lane read for every row is g m + e; the groups' structures
+    differ; the workspace size is G times the ungrouped one."""
+    lib = cases.hostcheck()
+    case = cases.LAYOUT_CASES[name]
+    for critic_lstm in case["critics"]:
+        shape, kind, firsts, batch = cases.layout_shape(name, critic_lstm)
+        index, _, groups, steps, per_group = shape
+        spec, twin, parts = cases.update_inputs(*shape, kind)
+        starts = parts["episode_starts"]
+        total = steps * per_group
+        assert starts.shape == (steps + 1, groups * per_group) and len(firsts) == groups and batch <= min(total, 1024)
+        structures = {np.ascontiguousarray(starts[:, g * per_group:(g + 1) * per_group]).tobytes() for g in range(groups)}
+        assert len(structures) == (groups if kind != "none" else 1)
+        for update in range(case["updates"]):
+            for g, first in enumerate(cases.firsts_of(firsts, update, total)):
+                lengths, rows = _sequences(lib, starts, groups, per_group, g, steps, first, batch)
+                wraps = first + batch > total
+                if kind == "depth" and update == 0:
+                    assert {1, 8, 9, 16} <= set(lengths), (g, lengths)
+                    if batch == total and g == 0:
+                        assert first == 5 and 17 not in lengths and lengths[0] == 12 and lengths[-1] == 5
+                    else:
+                        assert 17 in lengths, (g, lengths)
+                    if batch == total:
+                        assert wraps == (g != 1) and firsts[0] != firsts[2]
+                elif kind == "drawn":
+                    assert max(lengths) > 64 and min(lengths) == 1, (update, g, lengths)
+                    assert wraps == (g == 2)
+                    if update == 0:  # (g = 1: across an environment boundary)
+                        assert len({int(r) // steps for r in rows}) == (1 if g == 0 else 2)
+                elif kind == "every":
+                    assert batch == total == 1024 and lengths == [1] * 1024
+                elif kind == "none":
+                    touched = (first + batch - 1) // steps - first // steps + 1
+                    assert batch == 513 and total == 1024 and len(lengths) == touched and touched in (33, 34)
+                    assert max(lengths) == steps
+        desc = cases.critic_desc(spec)
+        one = lib.lpop_workspace_size(ctypes.byref(desc), 1, per_group, steps, batch)
+        assert lib.lpop_workspace_size(ctypes.byref(desc), groups, per_group, steps, batch) == groups * one > 0
+        if critic_lstm:
+            plain = lstm_learner_cases._lstm_desc(spec)
+            assert lstm_learner_cases.hostcheck().lpc_workspace_size(ctypes.byref(plain), batch) == one
+    assert case["index"] == (lstm_cases.DEFAULT if name.endswith("default") else lstm_cases.TUNED)
+
+
+@pytest.mark.parametrize("name,critic_lstm", [(name, critic_lstm) for name, case in cases.LAYOUT_CASES.items()
+                                              for critic_lstm in case["critics"]])
+def test_layout_twin_population_is_g_learners_over_slices(name, critic_lstm):
+    """The twin results the GPU file compares rf_lstm_ppo_update_grouped with on cases.LAYOUT_CASES equal G LstmLearner over
+    contiguous copies of the groups' slice-parts, each with its own hyper-parameters and first row, byte for byte; and no
+    comparison is vacuous (cases.layout_update_promises): flags 0 in every group and update, every group with a learning
+    rate ends with other parameters, parameters differ per group and hyper-parameters between neighbours."""
+    cases.layout_update_promises(name, critic_lstm)
+    shape, kind, firsts, batch = cases.layout_shape(name, critic_lstm)
+    groups, steps, per_group = shape[2:]
+    spec, twin, parts = cases.update_inputs(*shape, kind)
+    want = cases.layout_twin_updates(name, critic_lstm)
+    hypers = harness.PopulationLearner(cases.fresh_twin(spec, twin), **cases.hypers_of(groups)).hypers()
+    for g, member in enumerate(_members(spec, twin)):
+        alone = _alone(member, hypers[g])
+        piece = cases.group_slices(parts, groups, g)
+        with np.errstate(all="ignore"):
+            for update in range(len(want)):
+                stats = alone.update(piece, cases.firsts_of(firsts, update, steps * per_group)[g], batch)
+                assert bits(stats) == bits(want[update][2][g]), (g, update)
+                assert bits(member.params) == bits(want[update][0][g]) and bits(alone.state) == bits(want[update][1][g])
+
+
+@pytest.mark.parametrize("critic_lstm", cases.CRITICS)
+def test_the_combinations_of_the_group_limit_are_distinct(critic_lstm):
+    """cases.limit_results / limit_arrays, what stands for the 65535 groups of m = T = B = 1: the 105 combinations give 105
+    different updated parameters, optimizer states and stats, all taken and all moved; the 35 (parameter set, block)
+    pairs give 35 different values, final values and next states; both actions are sampled; the three blocks that read
+    their state would give another result on another block's level (so a wrong state stride shows); neighbouring groups
+    differ in parameters, inputs, state, hyper-parameters and generator; the groups with g % 11 = 5 have firsts[g] = N,
+    which the kernels' lstm_ppo_first flags, and their neighbours have 0; the size functions take 65535 groups and
+    refuse 65536."""
+    from reinfocus_amd.environments import lstm
+
+    lib = cases.hostcheck()
+    spec = cases.limit_spec(critic_lstm)
+    params, blocks, hypers, generators = cases.limit_parts(critic_lstm)
+    forwards, updates = cases.limit_results(critic_lstm)
+    for part, name in enumerate(("params", "state", "stats")):
+        assert len({bits(update[part]) for update in updates}) == 105, name
+    assert all(update[2][7] == 0 for update in updates)
+    assert all(bits(update[0]) != bits(params[c % 7]) for c, update in enumerate(updates))
+    pairs = [forwards[True][k][j][0] for k in range(7) for j in range(5)]
+    for part in (1, 3, 4):
+        assert len({bits(pair[part]) for pair in pairs}) == 35, part
+    sampled = [forwards[False][k][j][i] for k in range(7) for j in range(5) for i in range(cases.LIMIT_GENERATORS)]
+    assert {int(one[0][0]) for one in sampled} == {0, 1}
+    assert np.isfinite(np.concatenate([np.concatenate([one[1], one[2], one[3]]) for one in sampled])).all()
+    for j, block in enumerate(blocks):  # (another block's level under the same inputs)
+        other = blocks[(j + 1) % 5]["state"]
+        got = lstm.lstm_numpy(spec, params[0], block["observations"], block["starts"], other, block["final"], None, True)
+        assert (bits(got["state"]) != bits(forwards[True][0][j][0][4])) == (cases.LIMIT_STARTS[j] == 0), j
+    assert sum(byte == 0 for byte in cases.LIMIT_STARTS) == 3
+    inputs, wanted_forward, wanted_update = cases.limit_arrays(critic_lstm)
+    assert inputs["params"].shape == (65535, spec.size) and inputs["state"].shape == (2, 2, 65535, 1)
+    assert inputs["lstm_states"].shape == (2, 2, 2, 65535, 1) and inputs["episode_starts"].shape == (2, 65535)
+    for key in ("params", "observations", "hyper", "gens"):
+        rows = inputs[key].reshape(65535, -1)
+        assert all(rows[g].tobytes() != rows[g + 1].tobytes() for g in range(0, 65534, 257)), key
+    state = inputs["state"]
+    assert all(bits(state[:, :, g]) != bits(state[:, :, g + 1]) for g in range(0, 65534, 257))
+    for g in (0, 5, 247, 65534):
+        k, j, i = g % 7, g % 5, g % cases.LIMIT_GENERATORS
+        for deterministic in (False, True):
+            for part in range(4):
+                assert bits(wanted_forward[deterministic][part][g:g + 1]) == bits(forwards[deterministic][k][j][i][part])
+            assert bits(wanted_forward[deterministic][4][:, :, g:g + 1]) == bits(forwards[deterministic][k][j][i][4])
+        assert all(bits(wanted_update[part][g]) == bits(updates[g % 105][part]) for part in range(3))
+        assert bits(state[:, :, g:g + 1]) == bits(blocks[j]["state"])
+    outside = inputs["outside"]
+    assert list(np.flatnonzero(outside)[:3]) == [5, 16, 27] and outside.sum() == 5958
+    flag = ctypes.c_int(0)
+    for g in (4, 5, 6, 16, 65533):
+        assert lib.lpop_first(int(inputs["firsts"][g]), 1, ctypes.byref(flag)) == 0 and flag.value == int(outside[g])
+    desc = cases.critic_desc(spec)
+    one = lib.lpop_workspace_size(ctypes.byref(desc), 1, 1, 1, 1)
+    assert lib.lpop_workspace_size(ctypes.byref(desc), 65535, 1, 1, 1) == 65535 * one > 0
+    assert lib.lpop_workspace_size(ctypes.byref(desc), 65536, 1, 1, 1) == 0 == lib.lpop_state_size(ctypes.byref(desc), 65536, 1)
 
 
 class _Finished:

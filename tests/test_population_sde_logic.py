@@ -16,6 +16,7 @@ from reinfocus_amd.environments import harness, learner, policy, sde
 from tests import population_sde_io_cases as cases
 from tests import rollout_io_cases as rollout_cases
 from tests import sde_io_cases as sde_cases
+from tests import test_population_logic as population_logic
 from tests.test_composed_env_logic import no_gpu  # noqa: F401 -- a fixture
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -149,6 +150,20 @@ def test_population_learner_equals_independent_learners(index, batch, per_group)
             assert bits(member.policy.params) == bits(want[update][0][g]), (update, g)
             assert bits(member.state) == bits(want[update][1][g]), (update, g)
     assert bits(want[-1][0][0, spec.log_std_at:]) != log_stds[0]  # (log_std is trained)
+
+
+@pytest.mark.parametrize("index,groups,batch", cases.LARGE_CASES)
+def test_large_minibatches_hold_what_they_promise(index, groups, batch):
+    """cases.LARGE_CASES -- m = 8, T = 128, B = 512, 513, 1000 and 1024 at G = 3 on NETWORKS[1], 513 at G = 2 on the widest
+    network of tests/sde_io_cases.py -- without a GPU, by tests/test_population_logic.py's checks: the index is [G][B] with
+    a row of its own per group (a permutation at B = N, repeats below), parameters (log_std included) differ per group
+    and every hyper-parameter between neighbours, the twin population equals G learner.Learner over SdePolicy members on
+    contiguous slice copies byte for byte over both updates, no group is skipped, and every group with a learning rate
+    ends with other parameters."""
+    assert cases.LARGE_ALONE in cases.LARGE_CASES
+    spec, members = _members(index, groups, base=300)
+    assert len({bits(member.params[spec.log_std_at:]) for member in members}) == groups
+    population_logic.large_case_holds(cases, members, index, groups, batch)
 
 
 def test_learner_state_dict_resumes_bit_for_bit():
