@@ -1973,6 +1973,17 @@ int rf_env_device_status(rf_ctx *ctx, int *fault_step, int *fault_env)
     return RF_OK;
 }
 
+// ---- the learner entry points: every array is the caller's, checked by check_device_arrays (rf_host.h) -------------------
+// What they say of a desc, or of a population's shape, that they refuse (RF_LSTM_LIMITS: rf_host.h)
+#define RF_POLICY_LIMITS "%s: the desc is outside the limits (obs_width 1 .. %d, 1 or 2 hidden layers of width 1 .. %d per " \
+                         "net, n_actions 2 .. %d, activation RF_POLICY_RELU or RF_POLICY_TANH)"
+#define RF_SDE_LIMITS "%s: the desc is outside the limits (obs_width 1 .. %d, 1 or 2 hidden layers of width 1 .. %d per net, " \
+                      "n_actions 1: the Gaussian head has one action, activation RF_POLICY_RELU or RF_POLICY_TANH)"
+#define RF_LSTM_SDE_LIMITS "%s: the desc is outside the limits (obs_width and lstm_hidden 1 .. %d, 1 or 2 hidden layers of " \
+                           "width 1 .. %d per net, n_actions 1: the Gaussian head has one action, activation RF_POLICY_RELU " \
+                           "or RF_POLICY_TANH, critic RF_LSTM_CRITIC_LSTM or RF_LSTM_CRITIC_LINEAR)"
+#define RF_POPULATION_LIMITS "%s: G = %d must be in 1 .. %d, m = %d in 1 .. 2^20 and G m at most 2^30"
+
 // rf_rollout_advantages (groups = 0: the scalars) and rf_rollout_advantages_grouped (groups >= 1: d_discounts)
 static int rollout_advantages(rf_ctx *ctx, int T, int n, int groups, const double *d_rewards, const float *d_values,
                               const uint8_t *d_truncated, const float *d_final_values, const float *d_last_values,
@@ -1991,32 +2002,17 @@ static int rollout_advantages(rf_ctx *ctx, int T, int n, int groups, const doubl
     }
     RF_HIP(hipSetDevice(ctx->device));
     const size_t cells = (size_t)T * (size_t)n;
-    struct Array {
-        const void *p;
-        size_t bytes, align;
-        const char *what;
-    };
-    const Array inputs[] = {{d_rewards, cells * 8, 8, "d_rewards"},
-                            {d_values, cells * 4, 4, "d_values"},
-                            {d_truncated, cells, 1, "d_truncated"},
-                            {d_final_values, cells * 4, 4, "d_final_values"},
-                            {d_last_values, (size_t)n * 4, 4, "d_last_values"},
-                            {groups ? d_discounts : nullptr, (size_t)groups * 8, 8, "d_discounts"}};
-    const Array outputs[] = {{d_advantages, cells * 4, 4, "d_advantages"}, {d_returns, cells * 4, 4, "d_returns"}};
-    for (const Array &a : inputs) {
-        if (a.p == nullptr) // (d_final_values: no bootstrap; d_discounts: the scalars)
-            continue;
-        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
-            return rc;
-    }
-    for (const Array &a : outputs) {
-        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
-            return rc;
-        for (const Array &b : inputs)
-            RF_REQUIRE(b.p == nullptr || !ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s (an output "
-                       "must not alias an input: the chain writes a step before the steps before it are read)", fn, a.what,
-                       b.what);
-    }
+    const DeviceArray inputs[] = {{d_rewards, cells * 8, 8, "d_rewards"},
+                                  {d_values, cells * 4, 4, "d_values"},
+                                  {d_truncated, cells, 1, "d_truncated"},
+                                  {d_final_values, cells * 4, 4, "d_final_values"},
+                                  {d_last_values, (size_t)n * 4, 4, "d_last_values"},
+                                  {groups ? d_discounts : nullptr, (size_t)groups * 8, 8, "d_discounts"}};
+    const DeviceArray outputs[] = {{d_advantages, cells * 4, 4, "d_advantages"}, {d_returns, cells * 4, 4, "d_returns"}};
+    // (null inputs: d_final_values without a bootstrap, d_discounts with the scalars)
+    if (int rc = check_device_arrays(ctx, inputs, outputs, fn, kNotAmongOutputs,
+                                     "the chain writes a step before the steps before it are read"))
+        return rc;
     RF_REQUIRE(!ranges_overlap(d_advantages, cells * 4, d_returns, cells * 4), "%s: d_advantages overlaps d_returns", fn);
     const hipStream_t caller = (hipStream_t)caller_stream;
     if (int rc = refuse_capturing(caller, fn))
@@ -2064,9 +2060,62 @@ unsigned long long rf_policy_params_size(rf_ctx *ctx, const rf_policy_desc *desc
     rf::PolicyLayout layout;
     if (ctx == nullptr || desc == nullptr || !rf::policy_layout(*desc, layout))
         return 0;
-    if (hipSetDevice(ctx->device) != hipSuccess) // (as every entry point; nothing of the device is needed)
-        (void)hipGetLastError();
+    ignore_error(hipSetDevice(ctx->device));
     return layout.total;
+}
+
+// rf_policy_forward (G = 0: n rows, gen the host's four words) and rf_policy_forward_grouped (G >= 1: m rows per group, gen
+// the groups' generators on the device) are one function in two parts, between which each makes the device current: what
+// a call may ask for (sampled: whether it draws) ...
+static int policy_forward_asks(const char *fn, int G, const float *d_final_obs, const unsigned long long *gen, int flags,
+                               const long long *d_actions, const float *d_log_probs, const float *d_values,
+                               const float *d_final_values, const float *d_logits, bool &sampled)
+{
+    RF_REQUIRE((flags & ~RF_POLICY_DETERMINISTIC) == 0, "%s: unknown flags %d", fn, flags);
+    RF_REQUIRE(d_actions || d_values || d_final_values || d_logits, "%s: no output is asked for", fn);
+    RF_REQUIRE(d_log_probs == nullptr || d_actions != nullptr, "%s: d_log_probs are those of d_actions, which is NULL", fn);
+    RF_REQUIRE(d_final_values == nullptr || d_final_obs != nullptr, "%s: d_final_values needs d_final_obs", fn);
+    sampled = d_actions != nullptr && (flags & RF_POLICY_DETERMINISTIC) == 0;
+    RF_REQUIRE(!sampled || gen != nullptr, "%s: a sampled call needs %s", fn, G ? "d_gens" : "gen");
+    return RF_OK;
+}
+
+// ... and its arrays, their check and the launch
+static int policy_forward_any(const char *fn, rf_ctx *ctx, const rf::PolicyLayout &layout, int G, int m, const float *d_params,
+                              const float *d_obs, const float *d_final_obs, const unsigned long long *gen,
+                              unsigned long long consumed, bool sampled, long long *d_actions, float *d_log_probs,
+                              float *d_values, float *d_final_values, float *d_logits, void *caller_stream)
+{
+    static_assert(sizeof(rf::PolicyGen) == 32, "d_gens is uint64 [G][4]");
+    const rf::PolicyGen *d_gens = (const rf::PolicyGen *)(G && sampled ? gen : nullptr);
+    const size_t groups = G ? (size_t)G : 1, rows = groups * (size_t)m;
+    const DeviceArray inputs[] = {{d_params, groups * (size_t)layout.total * 4, 4, "d_params"},
+                                  {d_obs, rows * (size_t)layout.obs_width * 4, 4, "d_obs"},
+                                  {d_final_obs, rows * (size_t)layout.obs_width * 4, 4, "d_final_obs"},
+                                  {d_gens, groups * 32, 8, "d_gens"}};
+    const DeviceArray outputs[] = {{d_actions, rows * 8, 8, "d_actions"},
+                                   {d_log_probs, rows * 4, 4, "d_log_probs"},
+                                   {d_values, rows * 4, 4, "d_values"},
+                                   {d_final_values, rows * 4, 4, "d_final_values"},
+                                   {d_logits, rows * (size_t)layout.n_actions * 4, 4, "d_logits"}};
+    if (int rc = check_device_arrays(ctx, inputs, outputs, fn))
+        return rc;
+    // Every array is the caller's; gen is read here, by value, or on the device with the draw count by value: one launch on
+    // the caller's stream, nothing allocated, nothing waited for (a caller may capture it; a replay then repeats the same
+    // draws).
+    rf::PolicyGen words{};
+    if (sampled && !G)
+        for (int i = 0; i < 4; ++i)
+            words.word[i] = gen[i];
+    const bool pi = d_actions != nullptr || d_logits != nullptr, vf = d_values != nullptr || d_final_values != nullptr;
+    const unsigned tiles = (unsigned)(((size_t)m + rf::kPolicyTile - 1) / rf::kPolicyTile);
+    hipLaunchKernelGGL(G ? rf::policy_forward_kernel<true> : rf::policy_forward_kernel<false>,
+                       dim3(tiles, pi && vf ? 2u : 1u, (unsigned)groups), dim3(rf::kPolicyThreads), 0,
+                       (hipStream_t)caller_stream, layout, d_params, m, d_obs, d_final_obs, words, sampled ? 1 : 0,
+                       pi ? 0 : 1, (int64_t *)d_actions, d_log_probs, d_values, d_final_values, d_logits, d_gens,
+                       (uint64_t)consumed);
+    RF_HIP(hipGetLastError());
+    return RF_OK;
 }
 
 int rf_policy_forward(rf_ctx *ctx, const rf_policy_desc *desc, const float *d_params, int n, const float *d_obs,
@@ -2077,64 +2126,16 @@ int rf_policy_forward(rf_ctx *ctx, const rf_policy_desc *desc, const float *d_pa
     RF_REQUIRE(ctx != nullptr, "%s: ctx is NULL", fn);
     RF_REQUIRE(desc != nullptr && d_params != nullptr && d_obs != nullptr, "%s: NULL argument", fn);
     rf::PolicyLayout layout;
-    RF_REQUIRE(rf::policy_layout(*desc, layout),
-               "%s: the desc is outside the limits (obs_width 1 .. %d, 1 or 2 hidden layers of width 1 .. %d per net, "
-               "n_actions 2 .. %d, activation RF_POLICY_RELU or RF_POLICY_TANH)", fn, RF_POLICY_MAX_WIDTH,
-               RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_ACTIONS);
+    RF_REQUIRE(rf::policy_layout(*desc, layout), RF_POLICY_LIMITS, fn, RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_WIDTH,
+               RF_POLICY_MAX_ACTIONS);
     RF_REQUIRE(n >= 1 && n <= (1 << 30), "%s: n = %d must be at least 1 (and at most 2^30)", fn, n);
-    RF_REQUIRE((flags & ~RF_POLICY_DETERMINISTIC) == 0, "%s: unknown flags %d", fn, flags);
-    RF_REQUIRE(d_actions || d_values || d_final_values || d_logits, "%s: no output is asked for", fn);
-    RF_REQUIRE(d_log_probs == nullptr || d_actions != nullptr, "%s: d_log_probs are those of d_actions, which is NULL", fn);
-    RF_REQUIRE(d_final_values == nullptr || d_final_obs != nullptr, "%s: d_final_values needs d_final_obs", fn);
-    const bool sampled = d_actions != nullptr && (flags & RF_POLICY_DETERMINISTIC) == 0;
-    RF_REQUIRE(!sampled || gen != nullptr, "%s: a sampled call needs gen", fn);
+    bool sampled;
+    if (int rc = policy_forward_asks(fn, 0, d_final_obs, gen, flags, d_actions, d_log_probs, d_values, d_final_values, d_logits,
+                                     sampled))
+        return rc;
     RF_HIP(hipSetDevice(ctx->device));
-    const size_t rows = (size_t)n;
-    struct Array {
-        const void *p;
-        size_t bytes, align;
-        const char *what;
-    };
-    const Array inputs[] = {{d_params, (size_t)layout.total * 4, 4, "d_params"},
-                            {d_obs, rows * (size_t)layout.obs_width * 4, 4, "d_obs"},
-                            {d_final_obs, rows * (size_t)layout.obs_width * 4, 4, "d_final_obs"}};
-    const Array outputs[] = {{d_actions, rows * 8, 8, "d_actions"},
-                             {d_log_probs, rows * 4, 4, "d_log_probs"},
-                             {d_values, rows * 4, 4, "d_values"},
-                             {d_final_values, rows * 4, 4, "d_final_values"},
-                             {d_logits, rows * (size_t)layout.n_actions * 4, 4, "d_logits"}};
-    for (const Array &a : inputs) {
-        if (a.p == nullptr)
-            continue;
-        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
-            return rc;
-    }
-    for (const Array &a : outputs) {
-        if (a.p == nullptr)
-            continue;
-        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
-            return rc;
-        for (const Array &b : inputs)
-            RF_REQUIRE(b.p == nullptr || !ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s (an output must "
-                       "not alias an input: other blocks still read it)", fn, a.what, b.what);
-        for (const Array &b : outputs)
-            RF_REQUIRE(&b >= &a || b.p == nullptr || !ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s", fn,
-                       a.what, b.what);
-    }
-    // Every array is the caller's and gen is read here, by value: one launch on the caller's stream, nothing allocated,
-    // nothing waited for (a caller may capture it; a replay then repeats the same draws).
-    rf::PolicyGen words{};
-    if (sampled)
-        for (int i = 0; i < 4; ++i)
-            words.word[i] = gen[i];
-    const bool pi = d_actions != nullptr || d_logits != nullptr, vf = d_values != nullptr || d_final_values != nullptr;
-    const unsigned tiles = (unsigned)((rows + rf::kPolicyTile - 1) / rf::kPolicyTile);
-    hipLaunchKernelGGL(rf::policy_forward_kernel<false>, dim3(tiles, pi && vf ? 2u : 1u), dim3(rf::kPolicyThreads), 0,
-                       (hipStream_t)caller_stream, layout, d_params, n, d_obs, d_final_obs, words, sampled ? 1 : 0,
-                       pi ? 0 : 1, (int64_t *)d_actions, d_log_probs, d_values, d_final_values, d_logits,
-                       (const rf::PolicyGen *)nullptr, (uint64_t)0);
-    RF_HIP(hipGetLastError());
-    return RF_OK;
+    return policy_forward_any(fn, ctx, layout, 0, n, d_params, d_obs, d_final_obs, gen, 0, sampled, d_actions, d_log_probs,
+                              d_values, d_final_values, d_logits, caller_stream);
 }
 
 unsigned long long rf_ppo_state_size(rf_ctx *ctx, const rf_policy_desc *policy)
@@ -2142,8 +2143,7 @@ unsigned long long rf_ppo_state_size(rf_ctx *ctx, const rf_policy_desc *policy)
     rf::PolicyLayout layout;
     if (ctx == nullptr || policy == nullptr || !rf::policy_layout(*policy, layout))
         return 0;
-    if (hipSetDevice(ctx->device) != hipSuccess) // (as every entry point; nothing of the device is needed)
-        (void)hipGetLastError();
+    ignore_error(hipSetDevice(ctx->device));
     return 4ull * rf::kPpoStateHeader + 8ull * layout.total;
 }
 
@@ -2153,13 +2153,9 @@ unsigned long long rf_ppo_workspace_size(rf_ctx *ctx, const rf_policy_desc *poli
     rf::PpoWork work;
     if (ctx == nullptr || policy == nullptr || !rf::policy_layout(*policy, layout) || !rf::ppo_work(layout, max_batch, work))
         return 0;
-    if (hipSetDevice(ctx->device) != hipSuccess)
-        (void)hipGetLastError();
+    ignore_error(hipSetDevice(ctx->device));
     return 4ull * work.total;
 }
-
-#define RF_SDE_LIMITS "%s: the desc is outside the limits (obs_width 1 .. %d, 1 or 2 hidden layers of width 1 .. %d per net, " \
-                      "n_actions 1: the Gaussian head has one action, activation RF_POLICY_RELU or RF_POLICY_TANH)"
 
 // What rf_ppo_update and rf_sde_update do once they have checked ctx and made its device current: one body, the head
 // chosen by `sde` (the layout, the dtype of the actions, the kernel)
@@ -2174,10 +2170,8 @@ static int ppo_update_any(const char *fn, bool sde, rf_ctx *ctx, const rf_policy
     if (sde) {
         RF_REQUIRE(rf::sde_layout(*policy, layout), RF_SDE_LIMITS, fn, RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_WIDTH);
     } else {
-        RF_REQUIRE(rf::policy_layout(*policy, layout),
-                   "%s: the desc is outside the limits (obs_width 1 .. %d, 1 or 2 hidden layers of width 1 .. %d per net, "
-                   "n_actions 2 .. %d, activation RF_POLICY_RELU or RF_POLICY_TANH)", fn, RF_POLICY_MAX_WIDTH,
-                   RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_ACTIONS);
+        RF_REQUIRE(rf::policy_layout(*policy, layout), RF_POLICY_LIMITS, fn, RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_WIDTH,
+                   RF_POLICY_MAX_ACTIONS);
     }
     RF_REQUIRE(N >= 1 && N <= (1 << 30), "%s: N = %d must be at least 1 (and at most 2^30)", fn, N);
     RF_REQUIRE(B >= 1 && B <= RF_PPO_MAX_BATCH, "%s: B = %d is not in 1 .. %d", fn, B, RF_PPO_MAX_BATCH);
@@ -2187,33 +2181,18 @@ static int ppo_update_any(const char *fn, bool sde, rf_ctx *ctx, const rf_policy
     rf::PpoWork work;
     RF_REQUIRE(rf::ppo_work(layout, B, work), "%s: no workspace layout for B = %d", fn, B);
     const size_t rows = (size_t)N;
-    struct Array {
-        const void *p;
-        size_t bytes, align;
-        const char *what;
-    };
-    const Array inputs[] = {{d_obs, rows * (size_t)layout.obs_width * 4, 4, "d_obs"},
-                            {d_actions, rows * (sde ? 4 : 8), sde ? (size_t)4 : (size_t)8, "d_actions"},
-                            {d_old_log_probs, rows * 4, 4, "d_old_log_probs"},
-                            {d_advantages, rows * 4, 4, "d_advantages"},
-                            {d_returns, rows * 4, 4, "d_returns"},
-                            {d_index, (size_t)B * 8, 8, "d_index"}};
-    const Array outputs[] = {{d_params, (size_t)layout.total * 4, 4, "d_params"},
-                             {d_state, 4 * (size_t)rf::kPpoStateHeader + 8 * (size_t)layout.total, 8, "d_state"},
-                             {d_workspace, (size_t)work.total * 4, 8, "d_workspace"},
-                             {d_stats, 32, 4, "d_stats"}};
-    for (const Array &a : inputs)
-        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
-            return rc;
-    for (const Array &a : outputs) {
-        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
-            return rc;
-        for (const Array &b : inputs)
-            RF_REQUIRE(!ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s (an output must not alias an "
-                       "input: other blocks still read it)", fn, a.what, b.what);
-        for (const Array &b : outputs)
-            RF_REQUIRE(&b >= &a || !ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s", fn, a.what, b.what);
-    }
+    const DeviceArray inputs[] = {{d_obs, rows * (size_t)layout.obs_width * 4, 4, "d_obs"},
+                                  {d_actions, rows * (sde ? 4 : 8), sde ? (size_t)4 : (size_t)8, "d_actions"},
+                                  {d_old_log_probs, rows * 4, 4, "d_old_log_probs"},
+                                  {d_advantages, rows * 4, 4, "d_advantages"},
+                                  {d_returns, rows * 4, 4, "d_returns"},
+                                  {d_index, (size_t)B * 8, 8, "d_index"}};
+    const DeviceArray outputs[] = {{d_params, (size_t)layout.total * 4, 4, "d_params"},
+                                   {d_state, 4 * (size_t)rf::kPpoStateHeader + 8 * (size_t)layout.total, 8, "d_state"},
+                                   {d_workspace, (size_t)work.total * 4, 8, "d_workspace"},
+                                   {d_stats, 32, 4, "d_stats"}};
+    if (int rc = check_device_arrays(ctx, inputs, outputs, fn))
+        return rc;
     const hipStream_t caller = (hipStream_t)caller_stream;
     if (int rc = refuse_capturing(caller, fn))
         return rc;
@@ -2250,9 +2229,6 @@ int rf_ppo_update(rf_ctx *ctx, const rf_policy_desc *policy, const rf_ppo_desc *
 
 // ---- population (include/reinfocus_hip.h): the two entry points above over G groups, one launch per stage ----------------
 
-#define RF_POLICY_LIMITS "%s: the desc is outside the limits (obs_width 1 .. %d, 1 or 2 hidden layers of width 1 .. %d per " \
-                         "net, n_actions 2 .. %d, activation RF_POLICY_RELU or RF_POLICY_TANH)"
-
 int rf_policy_forward_grouped(rf_ctx *ctx, const rf_policy_desc *desc, int G, int m, const float *d_params,
                               const float *d_obs, const float *d_final_obs, const unsigned long long *d_gens,
                               unsigned long long consumed, int flags, long long *d_actions, float *d_log_probs,
@@ -2266,65 +2242,20 @@ int rf_policy_forward_grouped(rf_ctx *ctx, const rf_policy_desc *desc, int G, in
                RF_POLICY_MAX_ACTIONS);
     RF_REQUIRE(rf::population_rows(G, m), "%s: G = %d must be in 1 .. %d, m = %d at least 1 and G m at most 2^30", fn, G,
                RF_POPULATION_MAX_GROUPS, m);
-    RF_REQUIRE((flags & ~RF_POLICY_DETERMINISTIC) == 0, "%s: unknown flags %d", fn, flags);
-    RF_REQUIRE(d_actions || d_values || d_final_values || d_logits, "%s: no output is asked for", fn);
-    RF_REQUIRE(d_log_probs == nullptr || d_actions != nullptr, "%s: d_log_probs are those of d_actions, which is NULL", fn);
-    RF_REQUIRE(d_final_values == nullptr || d_final_obs != nullptr, "%s: d_final_values needs d_final_obs", fn);
-    const bool sampled = d_actions != nullptr && (flags & RF_POLICY_DETERMINISTIC) == 0;
-    RF_REQUIRE(!sampled || d_gens != nullptr, "%s: a sampled call needs d_gens", fn);
+    bool sampled;
+    if (int rc = policy_forward_asks(fn, G, d_final_obs, d_gens, flags, d_actions, d_log_probs, d_values, d_final_values,
+                                     d_logits, sampled))
+        return rc;
     RF_HIP(hipSetDevice(ctx->device));
-    const size_t rows = (size_t)G * (size_t)m;
-    struct Array {
-        const void *p;
-        size_t bytes, align;
-        const char *what;
-    };
-    const Array inputs[] = {{d_params, (size_t)G * (size_t)layout.total * 4, 4, "d_params"},
-                            {d_obs, rows * (size_t)layout.obs_width * 4, 4, "d_obs"},
-                            {d_final_obs, rows * (size_t)layout.obs_width * 4, 4, "d_final_obs"},
-                            {sampled ? d_gens : nullptr, (size_t)G * 32, 8, "d_gens"}};
-    const Array outputs[] = {{d_actions, rows * 8, 8, "d_actions"},
-                             {d_log_probs, rows * 4, 4, "d_log_probs"},
-                             {d_values, rows * 4, 4, "d_values"},
-                             {d_final_values, rows * 4, 4, "d_final_values"},
-                             {d_logits, rows * (size_t)layout.n_actions * 4, 4, "d_logits"}};
-    for (const Array &a : inputs) {
-        if (a.p == nullptr)
-            continue;
-        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
-            return rc;
-    }
-    for (const Array &a : outputs) {
-        if (a.p == nullptr)
-            continue;
-        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
-            return rc;
-        for (const Array &b : inputs)
-            RF_REQUIRE(b.p == nullptr || !ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s (an output must "
-                       "not alias an input: other blocks still read it)", fn, a.what, b.what);
-        for (const Array &b : outputs)
-            RF_REQUIRE(&b >= &a || b.p == nullptr || !ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s", fn,
-                       a.what, b.what);
-    }
-    // As rf_policy_forward: one launch on the caller's stream, nothing allocated, nothing waited for; the generators'
-    // words are read on the device and the draw count travels by value.
-    static_assert(sizeof(rf::PolicyGen) == 32, "d_gens is uint64 [G][4]");
-    const bool pi = d_actions != nullptr || d_logits != nullptr, vf = d_values != nullptr || d_final_values != nullptr;
-    const unsigned tiles = (unsigned)(((size_t)m + rf::kPolicyTile - 1) / rf::kPolicyTile);
-    hipLaunchKernelGGL(rf::policy_forward_kernel<true>, dim3(tiles, pi && vf ? 2u : 1u, (unsigned)G),
-                       dim3(rf::kPolicyThreads), 0, (hipStream_t)caller_stream, layout, d_params, m, d_obs, d_final_obs,
-                       rf::PolicyGen{}, sampled ? 1 : 0, pi ? 0 : 1, (int64_t *)d_actions, d_log_probs, d_values,
-                       d_final_values, d_logits, (const rf::PolicyGen *)(sampled ? d_gens : nullptr), (uint64_t)consumed);
-    RF_HIP(hipGetLastError());
-    return RF_OK;
+    return policy_forward_any(fn, ctx, layout, G, m, d_params, d_obs, d_final_obs, d_gens, consumed, sampled, d_actions,
+                              d_log_probs, d_values, d_final_values, d_logits, caller_stream);
 }
 
 unsigned long long rf_ppo_grouped_state_size(rf_ctx *ctx, const rf_policy_desc *policy, int G, int m)
 {
     if (ctx == nullptr || policy == nullptr)
         return 0;
-    if (hipSetDevice(ctx->device) != hipSuccess) // (as every entry point; nothing of the device is needed)
-        (void)hipGetLastError();
+    ignore_error(hipSetDevice(ctx->device));
     return rf::population_state_bytes(*policy, G, m);
 }
 
@@ -2332,8 +2263,7 @@ unsigned long long rf_ppo_grouped_workspace_size(rf_ctx *ctx, const rf_policy_de
 {
     if (ctx == nullptr || policy == nullptr)
         return 0;
-    if (hipSetDevice(ctx->device) != hipSuccess)
-        (void)hipGetLastError();
+    ignore_error(hipSetDevice(ctx->device));
     return rf::population_workspace_bytes(*policy, G, m, T, B);
 }
 
@@ -2364,34 +2294,19 @@ static int ppo_update_grouped_any(const char *fn, bool sde, rf_ctx *ctx, const r
     RF_REQUIRE(rf::ppo_work(layout, B, work), "%s: no workspace layout for B = %d", fn, B);
     const size_t groups = (size_t)G, rows = groups * (size_t)N;
     const size_t state_floats = (size_t)rf::kPpoStateHeader + 2 * (size_t)layout.total;
-    struct Array {
-        const void *p;
-        size_t bytes, align;
-        const char *what;
-    };
-    const Array inputs[] = {{d_obs, rows * (size_t)layout.obs_width * 4, 4, "d_obs"},
-                            {d_actions, rows * (sde ? 4 : 8), sde ? (size_t)4 : (size_t)8, "d_actions"},
-                            {d_old_log_probs, rows * 4, 4, "d_old_log_probs"},
-                            {d_advantages, rows * 4, 4, "d_advantages"},
-                            {d_returns, rows * 4, 4, "d_returns"},
-                            {d_index, groups * (size_t)B * 8, 8, "d_index"},
-                            {d_hyper, groups * sizeof(rf_ppo_hyper), 8, "d_hyper"}};
-    const Array outputs[] = {{d_params, groups * (size_t)layout.total * 4, 4, "d_params"},
-                             {d_state, groups * state_floats * 4, 8, "d_state"},
-                             {d_workspace, groups * (size_t)work.total * 4, 8, "d_workspace"},
-                             {d_stats, groups * 32, 4, "d_stats"}};
-    for (const Array &a : inputs)
-        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
-            return rc;
-    for (const Array &a : outputs) {
-        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
-            return rc;
-        for (const Array &b : inputs)
-            RF_REQUIRE(!ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s (an output must not alias an "
-                       "input: other blocks still read it)", fn, a.what, b.what);
-        for (const Array &b : outputs)
-            RF_REQUIRE(&b >= &a || !ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s", fn, a.what, b.what);
-    }
+    const DeviceArray inputs[] = {{d_obs, rows * (size_t)layout.obs_width * 4, 4, "d_obs"},
+                                  {d_actions, rows * (sde ? 4 : 8), sde ? (size_t)4 : (size_t)8, "d_actions"},
+                                  {d_old_log_probs, rows * 4, 4, "d_old_log_probs"},
+                                  {d_advantages, rows * 4, 4, "d_advantages"},
+                                  {d_returns, rows * 4, 4, "d_returns"},
+                                  {d_index, groups * (size_t)B * 8, 8, "d_index"},
+                                  {d_hyper, groups * sizeof(rf_ppo_hyper), 8, "d_hyper"}};
+    const DeviceArray outputs[] = {{d_params, groups * (size_t)layout.total * 4, 4, "d_params"},
+                                   {d_state, groups * state_floats * 4, 8, "d_state"},
+                                   {d_workspace, groups * (size_t)work.total * 4, 8, "d_workspace"},
+                                   {d_stats, groups * 32, 4, "d_stats"}};
+    if (int rc = check_device_arrays(ctx, inputs, outputs, fn))
+        return rc;
     const hipStream_t caller = (hipStream_t)caller_stream;
     if (int rc = refuse_capturing(caller, fn))
         return rc;
@@ -2443,8 +2358,7 @@ unsigned long long rf_sde_params_size(rf_ctx *ctx, const rf_policy_desc *desc)
     rf::PolicyLayout layout;
     if (ctx == nullptr || desc == nullptr || !rf::sde_layout(*desc, layout))
         return 0;
-    if (hipSetDevice(ctx->device) != hipSuccess) // (as every entry point; nothing of the device is needed)
-        (void)hipGetLastError();
+    ignore_error(hipSetDevice(ctx->device));
     return layout.total;
 }
 
@@ -2453,8 +2367,7 @@ unsigned long long rf_sde_state_size(rf_ctx *ctx, const rf_policy_desc *policy)
     rf::PolicyLayout layout;
     if (ctx == nullptr || policy == nullptr || !rf::sde_layout(*policy, layout))
         return 0;
-    if (hipSetDevice(ctx->device) != hipSuccess)
-        (void)hipGetLastError();
+    ignore_error(hipSetDevice(ctx->device));
     return 4ull * rf::kPpoStateHeader + 8ull * layout.total;
 }
 
@@ -2464,8 +2377,7 @@ unsigned long long rf_sde_workspace_size(rf_ctx *ctx, const rf_policy_desc *poli
     rf::PpoWork work;
     if (ctx == nullptr || policy == nullptr || !rf::sde_layout(*policy, layout) || !rf::ppo_work(layout, max_batch, work))
         return 0;
-    if (hipSetDevice(ctx->device) != hipSuccess)
-        (void)hipGetLastError();
+    ignore_error(hipSetDevice(ctx->device));
     return 4ull * work.total;
 }
 
@@ -2480,11 +2392,10 @@ int rf_sde_noise_reset(rf_ctx *ctx, const rf_policy_desc *desc, const float *d_p
     RF_REQUIRE(n >= 1 && n <= (1 << 20), "%s: n = %d must be at least 1 (and at most 2^20)", fn, n);
     RF_HIP(hipSetDevice(ctx->device));
     const size_t cells = (size_t)n * (size_t)layout.sde;
-    if (int rc = check_device_array(ctx, d_params, (size_t)layout.total * 4, 4, "d_params", fn))
+    const DeviceArray inputs[] = {{d_params, (size_t)layout.total * 4, 4, "d_params"}};
+    const DeviceArray outputs[] = {{d_theta, cells * 4, 4, "d_theta"}};
+    if (int rc = check_device_arrays(ctx, inputs, outputs, fn, 0, nullptr))
         return rc;
-    if (int rc = check_device_array(ctx, d_theta, cells * 4, 4, "d_theta", fn))
-        return rc;
-    RF_REQUIRE(!ranges_overlap(d_theta, cells * 4, d_params, (size_t)layout.total * 4), "%s: d_theta overlaps d_params", fn);
     rf::PolicyGen words{};
     for (int i = 0; i < 4; ++i)
         words.word[i] = gen[i];
@@ -2492,6 +2403,49 @@ int rf_sde_noise_reset(rf_ctx *ctx, const rf_policy_desc *desc, const float *d_p
     hipLaunchKernelGGL(rf::sde_noise_kernel<false>, dim3(blocks), dim3(rf::kPolicyThreads), 0, (hipStream_t)caller_stream,
                        words, d_params + layout.log_std, n, (int)layout.sde, d_theta, (const rf::PolicyGen *)nullptr,
                        (const uint64_t *)nullptr, (const uint8_t *)nullptr, 0u);
+    RF_HIP(hipGetLastError());
+    return RF_OK;
+}
+
+// rf_sde_forward (G = 0: n rows) and rf_sde_forward_grouped (G >= 1: m rows per group), in two parts as the policy forwards
+// are: what a call may ask for (pi: something of the actor; sampled: with d_theta's noise) ...
+static int sde_forward_asks(const char *fn, int G, const float *d_final_obs, const float *d_theta, int flags, bool pi,
+                            const float *d_values, const float *d_final_values, bool &sampled)
+{
+    RF_REQUIRE((flags & ~RF_POLICY_DETERMINISTIC) == 0, "%s: unknown flags %d", fn, flags);
+    RF_REQUIRE(pi || d_values || d_final_values, "%s: no output is asked for", fn);
+    RF_REQUIRE(d_final_values == nullptr || d_final_obs != nullptr, "%s: d_final_values needs d_final_obs", fn);
+    sampled = pi && (flags & RF_POLICY_DETERMINISTIC) == 0;
+    RF_REQUIRE(!sampled || d_theta != nullptr, "%s: a sampled call needs d_theta (%s)", fn,
+               G ? "rf_sde_noise_reset_grouped" : "rf_sde_noise_reset");
+    return RF_OK;
+}
+
+// ... and its arrays, their check and the launch
+static int sde_forward_any(const char *fn, rf_ctx *ctx, const rf::PolicyLayout &layout, int G, int m, const float *d_params,
+                           const float *d_obs, const float *d_final_obs, const float *d_theta, bool sampled, float *d_actions,
+                           float *d_env_actions, float *d_log_probs, float *d_values, float *d_final_values, float *d_mean,
+                           float *d_sigma, void *caller_stream)
+{
+    const bool pi = d_actions || d_env_actions || d_log_probs || d_mean || d_sigma;
+    const bool vf = d_values != nullptr || d_final_values != nullptr;
+    const size_t groups = G ? (size_t)G : 1, rows = groups * (size_t)m;
+    const DeviceArray inputs[] = {{d_params, groups * (size_t)layout.total * 4, 4, "d_params"},
+                                  {d_obs, rows * (size_t)layout.obs_width * 4, 4, "d_obs"},
+                                  {d_final_obs, rows * (size_t)layout.obs_width * 4, 4, "d_final_obs"},
+                                  {sampled ? d_theta : nullptr, rows * (size_t)layout.sde * 4, 4, "d_theta"}};
+    const DeviceArray outputs[] = {{d_actions, rows * 4, 4, "d_actions"},       {d_env_actions, rows * 4, 4, "d_env_actions"},
+                                   {d_log_probs, rows * 4, 4, "d_log_probs"},   {d_values, rows * 4, 4, "d_values"},
+                                   {d_final_values, rows * 4, 4, "d_final_values"}, {d_mean, rows * 4, 4, "d_mean"},
+                                   {d_sigma, rows * 4, 4, "d_sigma"}};
+    if (int rc = check_device_arrays(ctx, inputs, outputs, fn))
+        return rc;
+    // one launch on the caller's stream, nothing allocated, nothing waited for (a caller may capture it)
+    const unsigned tiles = (unsigned)(((size_t)m + rf::kPolicyTile - 1) / rf::kPolicyTile);
+    hipLaunchKernelGGL(G ? rf::sde_forward_kernel<true> : rf::sde_forward_kernel<false>,
+                       dim3(tiles, pi && vf ? 2u : 1u, (unsigned)groups), dim3(rf::kPolicyThreads), 0,
+                       (hipStream_t)caller_stream, layout, d_params, m, d_obs, d_final_obs, sampled ? d_theta : nullptr,
+                       pi ? 0 : 1, d_actions, d_env_actions, d_log_probs, d_values, d_final_values, d_mean, d_sigma);
     RF_HIP(hipGetLastError());
     return RF_OK;
 }
@@ -2507,58 +2461,16 @@ int rf_sde_forward(rf_ctx *ctx, const rf_policy_desc *desc, const float *d_param
     rf::PolicyLayout layout;
     RF_REQUIRE(rf::sde_layout(*desc, layout), RF_SDE_LIMITS, fn, RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_WIDTH);
     RF_REQUIRE(n >= 1 && n <= (1 << 20), "%s: n = %d must be at least 1 (and at most 2^20)", fn, n);
-    RF_REQUIRE((flags & ~RF_POLICY_DETERMINISTIC) == 0, "%s: unknown flags %d", fn, flags);
     const bool pi = d_actions || d_env_actions || d_log_probs || d_mean || d_sigma;
-    const bool vf = d_values != nullptr || d_final_values != nullptr;
-    RF_REQUIRE(pi || vf, "%s: no output is asked for", fn);
-    RF_REQUIRE(d_final_values == nullptr || d_final_obs != nullptr, "%s: d_final_values needs d_final_obs", fn);
-    const bool sampled = pi && (flags & RF_POLICY_DETERMINISTIC) == 0;
-    RF_REQUIRE(!sampled || d_theta != nullptr, "%s: a sampled call needs d_theta (rf_sde_noise_reset)", fn);
+    bool sampled;
+    if (int rc = sde_forward_asks(fn, 0, d_final_obs, d_theta, flags, pi, d_values, d_final_values, sampled))
+        return rc;
     RF_HIP(hipSetDevice(ctx->device));
-    const size_t rows = (size_t)n;
-    struct Array {
-        const void *p;
-        size_t bytes, align;
-        const char *what;
-    };
-    const Array inputs[] = {{d_params, (size_t)layout.total * 4, 4, "d_params"},
-                            {d_obs, rows * (size_t)layout.obs_width * 4, 4, "d_obs"},
-                            {d_final_obs, rows * (size_t)layout.obs_width * 4, 4, "d_final_obs"},
-                            {sampled ? d_theta : nullptr, rows * (size_t)layout.sde * 4, 4, "d_theta"}};
-    const Array outputs[] = {{d_actions, rows * 4, 4, "d_actions"},       {d_env_actions, rows * 4, 4, "d_env_actions"},
-                             {d_log_probs, rows * 4, 4, "d_log_probs"},   {d_values, rows * 4, 4, "d_values"},
-                             {d_final_values, rows * 4, 4, "d_final_values"}, {d_mean, rows * 4, 4, "d_mean"},
-                             {d_sigma, rows * 4, 4, "d_sigma"}};
-    for (const Array &a : inputs) {
-        if (a.p == nullptr)
-            continue;
-        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
-            return rc;
-    }
-    for (const Array &a : outputs) {
-        if (a.p == nullptr)
-            continue;
-        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
-            return rc;
-        for (const Array &b : inputs)
-            RF_REQUIRE(b.p == nullptr || !ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s (an output must "
-                       "not alias an input: other blocks still read it)", fn, a.what, b.what);
-        for (const Array &b : outputs)
-            RF_REQUIRE(&b >= &a || b.p == nullptr || !ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s", fn,
-                       a.what, b.what);
-    }
-    const unsigned tiles = (unsigned)((rows + rf::kPolicyTile - 1) / rf::kPolicyTile);
-    hipLaunchKernelGGL(rf::sde_forward_kernel<false>, dim3(tiles, pi && vf ? 2u : 1u), dim3(rf::kPolicyThreads), 0,
-                       (hipStream_t)caller_stream, layout, d_params, n, d_obs, d_final_obs, sampled ? d_theta : nullptr,
-                       pi ? 0 : 1, d_actions, d_env_actions, d_log_probs, d_values, d_final_values, d_mean, d_sigma);
-    RF_HIP(hipGetLastError());
-    return RF_OK;
+    return sde_forward_any(fn, ctx, layout, 0, n, d_params, d_obs, d_final_obs, d_theta, sampled, d_actions, d_env_actions,
+                           d_log_probs, d_values, d_final_values, d_mean, d_sigma, caller_stream);
 }
 
 // ---- population sde (include/reinfocus_hip.h): the sde entry points above over G groups, one launch per stage ---------------
-
-#define RF_POPULATION_LIMITS "%s: G = %d must be in 1 .. %d, m = %d in 1 .. 2^20 and G m at most 2^30"
-
 int rf_sde_noise_reset_grouped(rf_ctx *ctx, const rf_policy_desc *desc, int G, int m, const float *d_params,
                                const unsigned long long *d_gens, const unsigned long long *d_consumed,
                                const unsigned char *d_select, float *d_theta, void *caller_stream)
@@ -2572,26 +2484,13 @@ int rf_sde_noise_reset_grouped(rf_ctx *ctx, const rf_policy_desc *desc, int G, i
     RF_REQUIRE(rf::population_rows(G, m) && m <= (1 << 20), RF_POPULATION_LIMITS, fn, G, RF_POPULATION_MAX_GROUPS, m);
     RF_HIP(hipSetDevice(ctx->device));
     const size_t groups = (size_t)G, cells = (size_t)m * (size_t)layout.sde;
-    struct Array {
-        const void *p;
-        size_t bytes, align;
-        const char *what;
-    };
-    const Array inputs[] = {{d_params, groups * (size_t)layout.total * 4, 4, "d_params"},
-                            {d_gens, groups * 32, 8, "d_gens"},
-                            {d_consumed, groups * 8, 8, "d_consumed"},
-                            {d_select, groups, 1, "d_select"}};
-    for (const Array &a : inputs) {
-        if (a.p == nullptr)
-            continue;
-        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
-            return rc;
-    }
-    if (int rc = check_device_array(ctx, d_theta, groups * cells * 4, 4, "d_theta", fn))
+    const DeviceArray inputs[] = {{d_params, groups * (size_t)layout.total * 4, 4, "d_params"},
+                                  {d_gens, groups * 32, 8, "d_gens"},
+                                  {d_consumed, groups * 8, 8, "d_consumed"},
+                                  {d_select, groups, 1, "d_select"}};
+    const DeviceArray outputs[] = {{d_theta, groups * cells * 4, 4, "d_theta"}};
+    if (int rc = check_device_arrays(ctx, inputs, outputs, fn, 0, nullptr))
         return rc;
-    for (const Array &b : inputs)
-        RF_REQUIRE(b.p == nullptr || !ranges_overlap(d_theta, groups * cells * 4, b.p, b.bytes), "%s: d_theta overlaps %s", fn,
-                   b.what);
     // As rf_sde_noise_reset: one launch on the caller's stream, nothing allocated, nothing waited for; the generators'
     // words, their draw counts and the selection are read on the device.
     static_assert(sizeof(rf::PolicyGen) == 32, "d_gens is uint64 [G][4]");
@@ -2614,60 +2513,20 @@ int rf_sde_forward_grouped(rf_ctx *ctx, const rf_policy_desc *desc, int G, int m
     rf::PolicyLayout layout;
     RF_REQUIRE(rf::sde_layout(*desc, layout), RF_SDE_LIMITS, fn, RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_WIDTH);
     RF_REQUIRE(rf::population_rows(G, m) && m <= (1 << 20), RF_POPULATION_LIMITS, fn, G, RF_POPULATION_MAX_GROUPS, m);
-    RF_REQUIRE((flags & ~RF_POLICY_DETERMINISTIC) == 0, "%s: unknown flags %d", fn, flags);
     const bool pi = d_actions || d_env_actions || d_log_probs || d_mean || d_sigma;
-    const bool vf = d_values != nullptr || d_final_values != nullptr;
-    RF_REQUIRE(pi || vf, "%s: no output is asked for", fn);
-    RF_REQUIRE(d_final_values == nullptr || d_final_obs != nullptr, "%s: d_final_values needs d_final_obs", fn);
-    const bool sampled = pi && (flags & RF_POLICY_DETERMINISTIC) == 0;
-    RF_REQUIRE(!sampled || d_theta != nullptr, "%s: a sampled call needs d_theta (rf_sde_noise_reset_grouped)", fn);
+    bool sampled;
+    if (int rc = sde_forward_asks(fn, G, d_final_obs, d_theta, flags, pi, d_values, d_final_values, sampled))
+        return rc;
     RF_HIP(hipSetDevice(ctx->device));
-    const size_t rows = (size_t)G * (size_t)m;
-    struct Array {
-        const void *p;
-        size_t bytes, align;
-        const char *what;
-    };
-    const Array inputs[] = {{d_params, (size_t)G * (size_t)layout.total * 4, 4, "d_params"},
-                            {d_obs, rows * (size_t)layout.obs_width * 4, 4, "d_obs"},
-                            {d_final_obs, rows * (size_t)layout.obs_width * 4, 4, "d_final_obs"},
-                            {sampled ? d_theta : nullptr, rows * (size_t)layout.sde * 4, 4, "d_theta"}};
-    const Array outputs[] = {{d_actions, rows * 4, 4, "d_actions"},       {d_env_actions, rows * 4, 4, "d_env_actions"},
-                             {d_log_probs, rows * 4, 4, "d_log_probs"},   {d_values, rows * 4, 4, "d_values"},
-                             {d_final_values, rows * 4, 4, "d_final_values"}, {d_mean, rows * 4, 4, "d_mean"},
-                             {d_sigma, rows * 4, 4, "d_sigma"}};
-    for (const Array &a : inputs) {
-        if (a.p == nullptr)
-            continue;
-        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
-            return rc;
-    }
-    for (const Array &a : outputs) {
-        if (a.p == nullptr)
-            continue;
-        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
-            return rc;
-        for (const Array &b : inputs)
-            RF_REQUIRE(b.p == nullptr || !ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s (an output must "
-                       "not alias an input: other blocks still read it)", fn, a.what, b.what);
-        for (const Array &b : outputs)
-            RF_REQUIRE(&b >= &a || b.p == nullptr || !ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s", fn,
-                       a.what, b.what);
-    }
-    const unsigned tiles = (unsigned)(((size_t)m + rf::kPolicyTile - 1) / rf::kPolicyTile);
-    hipLaunchKernelGGL(rf::sde_forward_kernel<true>, dim3(tiles, pi && vf ? 2u : 1u, (unsigned)G), dim3(rf::kPolicyThreads), 0,
-                       (hipStream_t)caller_stream, layout, d_params, m, d_obs, d_final_obs, sampled ? d_theta : nullptr,
-                       pi ? 0 : 1, d_actions, d_env_actions, d_log_probs, d_values, d_final_values, d_mean, d_sigma);
-    RF_HIP(hipGetLastError());
-    return RF_OK;
+    return sde_forward_any(fn, ctx, layout, G, m, d_params, d_obs, d_final_obs, d_theta, sampled, d_actions, d_env_actions,
+                           d_log_probs, d_values, d_final_values, d_mean, d_sigma, caller_stream);
 }
 
 unsigned long long rf_sde_grouped_state_size(rf_ctx *ctx, const rf_policy_desc *policy, int G, int m)
 {
     if (ctx == nullptr || policy == nullptr)
         return 0;
-    if (hipSetDevice(ctx->device) != hipSuccess) // (as every entry point; nothing of the device is needed)
-        (void)hipGetLastError();
+    ignore_error(hipSetDevice(ctx->device));
     return rf::population_state_bytes(*policy, G, m, true);
 }
 
@@ -2675,8 +2534,7 @@ unsigned long long rf_sde_grouped_workspace_size(rf_ctx *ctx, const rf_policy_de
 {
     if (ctx == nullptr || policy == nullptr)
         return 0;
-    if (hipSetDevice(ctx->device) != hipSuccess)
-        (void)hipGetLastError();
+    ignore_error(hipSetDevice(ctx->device));
     return rf::population_workspace_bytes(*policy, G, m, T, B, true);
 }
 
@@ -2727,8 +2585,8 @@ static unsigned long long lstm_workspace_size_any(rf_ctx *ctx, const rf_lstm_pol
 
 unsigned long long rf_lstm_params_size(rf_ctx *ctx, const rf_lstm_policy_desc *desc)
 {
-    if (ctx != nullptr && hipSetDevice(ctx->device) != hipSuccess) // (as every entry point; nothing of the device is needed)
-        (void)hipGetLastError();
+    if (ctx != nullptr)
+        ignore_error(hipSetDevice(ctx->device));
     return lstm_params_size_any(ctx, desc, false, RF_LSTM_CRITIC_LSTM);
 }
 
@@ -2737,8 +2595,7 @@ unsigned long long rf_lstm_state_size(rf_ctx *ctx, const rf_lstm_policy_desc *de
     rf::LstmLayout layout;
     if (ctx == nullptr || desc == nullptr || n < 1 || !rf::lstm_layout(*desc, layout))
         return 0;
-    if (hipSetDevice(ctx->device) != hipSuccess)
-        (void)hipGetLastError();
+    ignore_error(hipSetDevice(ctx->device));
     return rf::lstm_state_floats(n, layout.hidden);
 }
 
@@ -2752,10 +2609,8 @@ static int lstm_forward_any(const char *fn, int critic, rf_ctx *ctx, const rf_ls
     RF_REQUIRE(desc != nullptr && d_params != nullptr && d_obs != nullptr && d_episode_starts != nullptr &&
                d_state_in != nullptr, "%s: NULL argument", fn);
     rf::LstmLayout layout;
-    RF_REQUIRE(lstm_layout_any(desc, false, critic, layout),
-               "%s: the desc is outside the limits (obs_width and lstm_hidden 1 .. %d, 1 or 2 hidden layers of width 1 .. %d "
-               "per net, n_actions 2 .. %d, activation RF_POLICY_RELU or RF_POLICY_TANH, critic RF_LSTM_CRITIC_LSTM or "
-               "RF_LSTM_CRITIC_LINEAR)", fn, RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_ACTIONS);
+    RF_REQUIRE(lstm_layout_any(desc, false, critic, layout), RF_LSTM_LIMITS, fn, RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_WIDTH,
+               RF_POLICY_MAX_ACTIONS);
     RF_REQUIRE(n >= 1 && n <= (1 << 30), "%s: n = %d must be at least 1 (and at most 2^30)", fn, n);
     RF_REQUIRE((flags & ~RF_POLICY_DETERMINISTIC) == 0, "%s: unknown flags %d", fn, flags);
     RF_REQUIRE(d_actions || d_values || d_final_values || d_logits || d_state_out, "%s: no output is asked for", fn);
@@ -2766,48 +2621,19 @@ static int lstm_forward_any(const char *fn, int critic, rf_ctx *ctx, const rf_ls
     RF_HIP(hipSetDevice(ctx->device));
     const size_t rows = (size_t)n;
     const size_t state_bytes = rf::lstm_state_floats(n, layout.hidden) * 4;
-    struct Array {
-        const void *p;
-        size_t bytes, align;
-        const char *what;
-    };
-    const Array inputs[] = {{d_params, (size_t)layout.total * 4, 4, "d_params"},
-                            {d_obs, rows * (size_t)layout.obs_width * 4, 4, "d_obs"},
-                            {d_episode_starts, rows, 1, "d_episode_starts"},
-                            {d_final_obs, rows * (size_t)layout.obs_width * 4, 4, "d_final_obs"},
-                            {d_state_in, state_bytes, 4, "d_state_in"}};
-    const Array outputs[] = {{d_actions, rows * 8, 8, "d_actions"},
-                             {d_log_probs, rows * 4, 4, "d_log_probs"},
-                             {d_values, rows * 4, 4, "d_values"},
-                             {d_final_values, rows * 4, 4, "d_final_values"},
-                             {d_logits, rows * (size_t)layout.mlp.n_actions * 4, 4, "d_logits"},
-                             {d_state_out, state_bytes, 4, "d_state_out"}};
-    for (const Array &a : inputs) {
-        if (a.p == nullptr)
-            continue;
-        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
-            return rc;
-    }
-    for (const Array &a : outputs) {
-        if (a.p == nullptr)
-            continue;
-        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
-            return rc;
-        for (const Array &b : inputs) {
-            if (&a == &outputs[5] && &b == &inputs[4]) { // d_state_out against d_state_in
-                // in place (a block reads its own rows of the state before it writes them), or apart
-                RF_REQUIRE(a.p == b.p || !ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: d_state_out overlaps d_state_in "
-                           "without being it (the same pointer updates the state in place; any other overlap would have a "
-                           "block overwrite rows another still reads)", fn);
-                continue;
-            }
-            RF_REQUIRE(b.p == nullptr || !ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s (an output must "
-                       "not alias an input: other blocks still read it)", fn, a.what, b.what);
-        }
-        for (const Array &b : outputs)
-            RF_REQUIRE(&b >= &a || b.p == nullptr || !ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s", fn,
-                       a.what, b.what);
-    }
+    const DeviceArray inputs[] = {{d_params, (size_t)layout.total * 4, 4, "d_params"},
+                                  {d_obs, rows * (size_t)layout.obs_width * 4, 4, "d_obs"},
+                                  {d_episode_starts, rows, 1, "d_episode_starts"},
+                                  {d_final_obs, rows * (size_t)layout.obs_width * 4, 4, "d_final_obs"},
+                                  {d_state_in, state_bytes, 4, "d_state_in"}};
+    const DeviceArray outputs[] = {{d_actions, rows * 8, 8, "d_actions"},
+                                   {d_log_probs, rows * 4, 4, "d_log_probs"},
+                                   {d_values, rows * 4, 4, "d_values"},
+                                   {d_final_values, rows * 4, 4, "d_final_values"},
+                                   {d_logits, rows * (size_t)layout.mlp.n_actions * 4, 4, "d_logits"},
+                                   {d_state_out, state_bytes, 4, "d_state_out"}};
+    if (int rc = check_device_arrays(ctx, inputs, outputs, fn, kStateInPlace))
+        return rc;
     // As rf_policy_forward: every array is the caller's and gen is read here, by value: one launch on the caller's stream.
     rf::PolicyGen words{};
     if (sampled)
@@ -2840,14 +2666,10 @@ int rf_lstm_forward(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const float *d
                             d_final_values, d_logits, caller_stream);
 }
 
-#define RF_LSTM_SDE_LIMITS "%s: the desc is outside the limits (obs_width and lstm_hidden 1 .. %d, 1 or 2 hidden layers of " \
-                           "width 1 .. %d per net, n_actions 1: the Gaussian head has one action, activation RF_POLICY_RELU " \
-                           "or RF_POLICY_TANH, critic RF_LSTM_CRITIC_LSTM or RF_LSTM_CRITIC_LINEAR)"
-
 unsigned long long rf_lstm_sde_params_size(rf_ctx *ctx, const rf_lstm_policy_desc *desc)
 {
-    if (ctx != nullptr && hipSetDevice(ctx->device) != hipSuccess) // (as every entry point; nothing of the device is needed)
-        (void)hipGetLastError();
+    if (ctx != nullptr)
+        ignore_error(hipSetDevice(ctx->device));
     return lstm_params_size_any(ctx, desc, true, RF_LSTM_CRITIC_LSTM);
 }
 
@@ -2862,11 +2684,10 @@ static int lstm_sde_noise_reset_any(const char *fn, int critic, rf_ctx *ctx, con
     RF_REQUIRE(n >= 1 && n <= (1 << 20), "%s: n = %d must be at least 1 (and at most 2^20)", fn, n);
     RF_HIP(hipSetDevice(ctx->device));
     const size_t cells = (size_t)n * (size_t)layout.mlp.sde;
-    if (int rc = check_device_array(ctx, d_params, (size_t)layout.total * 4, 4, "d_params", fn))
+    const DeviceArray inputs[] = {{d_params, (size_t)layout.total * 4, 4, "d_params"}};
+    const DeviceArray outputs[] = {{d_theta, cells * 4, 4, "d_theta"}};
+    if (int rc = check_device_arrays(ctx, inputs, outputs, fn, 0, nullptr))
         return rc;
-    if (int rc = check_device_array(ctx, d_theta, cells * 4, 4, "d_theta", fn))
-        return rc;
-    RF_REQUIRE(!ranges_overlap(d_theta, cells * 4, d_params, (size_t)layout.total * 4), "%s: d_theta overlaps d_params", fn);
     rf::PolicyGen words{};
     for (int i = 0; i < 4; ++i)
         words.word[i] = gen[i];
@@ -2909,46 +2730,18 @@ static int lstm_sde_forward_any(const char *fn, int critic, rf_ctx *ctx, const r
     RF_HIP(hipSetDevice(ctx->device));
     const size_t rows = (size_t)n;
     const size_t state_bytes = rf::lstm_state_floats(n, layout.hidden) * 4;
-    struct Array {
-        const void *p;
-        size_t bytes, align;
-        const char *what;
-    };
-    const Array inputs[] = {{d_params, (size_t)layout.total * 4, 4, "d_params"},
-                            {d_obs, rows * (size_t)layout.obs_width * 4, 4, "d_obs"},
-                            {d_episode_starts, rows, 1, "d_episode_starts"},
-                            {d_final_obs, rows * (size_t)layout.obs_width * 4, 4, "d_final_obs"},
-                            {sampled ? d_theta : nullptr, rows * (size_t)layout.mlp.sde * 4, 4, "d_theta"},
-                            {d_state_in, state_bytes, 4, "d_state_in"}};
-    const Array outputs[] = {{d_actions, rows * 4, 4, "d_actions"},       {d_env_actions, rows * 4, 4, "d_env_actions"},
-                             {d_log_probs, rows * 4, 4, "d_log_probs"},   {d_values, rows * 4, 4, "d_values"},
-                             {d_final_values, rows * 4, 4, "d_final_values"}, {d_mean, rows * 4, 4, "d_mean"},
-                             {d_sigma, rows * 4, 4, "d_sigma"},           {d_state_out, state_bytes, 4, "d_state_out"}};
-    for (const Array &a : inputs) {
-        if (a.p == nullptr)
-            continue;
-        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
-            return rc;
-    }
-    for (const Array &a : outputs) {
-        if (a.p == nullptr)
-            continue;
-        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
-            return rc;
-        for (const Array &b : inputs) {
-            if (&a == &outputs[7] && &b == &inputs[5]) { // d_state_out against d_state_in: in place, or apart
-                RF_REQUIRE(a.p == b.p || !ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: d_state_out overlaps d_state_in "
-                           "without being it (the same pointer updates the state in place; any other overlap would have a "
-                           "block overwrite rows another still reads)", fn);
-                continue;
-            }
-            RF_REQUIRE(b.p == nullptr || !ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s (an output must "
-                       "not alias an input: other blocks still read it)", fn, a.what, b.what);
-        }
-        for (const Array &b : outputs)
-            RF_REQUIRE(&b >= &a || b.p == nullptr || !ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s", fn,
-                       a.what, b.what);
-    }
+    const DeviceArray inputs[] = {{d_params, (size_t)layout.total * 4, 4, "d_params"},
+                                  {d_obs, rows * (size_t)layout.obs_width * 4, 4, "d_obs"},
+                                  {d_episode_starts, rows, 1, "d_episode_starts"},
+                                  {d_final_obs, rows * (size_t)layout.obs_width * 4, 4, "d_final_obs"},
+                                  {sampled ? d_theta : nullptr, rows * (size_t)layout.mlp.sde * 4, 4, "d_theta"},
+                                  {d_state_in, state_bytes, 4, "d_state_in"}};
+    const DeviceArray outputs[] = {{d_actions, rows * 4, 4, "d_actions"},       {d_env_actions, rows * 4, 4, "d_env_actions"},
+                                   {d_log_probs, rows * 4, 4, "d_log_probs"},   {d_values, rows * 4, 4, "d_values"},
+                                   {d_final_values, rows * 4, 4, "d_final_values"}, {d_mean, rows * 4, 4, "d_mean"},
+                                   {d_sigma, rows * 4, 4, "d_sigma"},           {d_state_out, state_bytes, 4, "d_state_out"}};
+    if (int rc = check_device_arrays(ctx, inputs, outputs, fn, kStateInPlace))
+        return rc;
     // As rf_lstm_forward: one launch on the caller's stream; with d_state_out both cells run, whatever is asked of the heads
     const bool linear = critic == RF_LSTM_CRITIC_LINEAR;
     const bool pi = pi_out || d_state_out != nullptr;
@@ -2977,21 +2770,17 @@ int rf_lstm_sde_forward(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const floa
                                 d_values, d_final_values, d_mean, d_sigma, caller_stream);
 }
 
-#define RF_LSTM_LIMITS "%s: the desc is outside the limits (obs_width and lstm_hidden 1 .. %d, 1 or 2 hidden layers of width " \
-                       "1 .. %d per net, n_actions 2 .. %d, activation RF_POLICY_RELU or RF_POLICY_TANH, critic " \
-                       "RF_LSTM_CRITIC_LSTM or RF_LSTM_CRITIC_LINEAR)"
-
 unsigned long long rf_lstm_ppo_state_size(rf_ctx *ctx, const rf_lstm_policy_desc *desc)
 {
-    if (ctx != nullptr && hipSetDevice(ctx->device) != hipSuccess) // (as every entry point; nothing of the device is needed)
-        (void)hipGetLastError();
+    if (ctx != nullptr)
+        ignore_error(hipSetDevice(ctx->device));
     return lstm_state_size_any(ctx, desc, false, RF_LSTM_CRITIC_LSTM);
 }
 
 unsigned long long rf_lstm_ppo_workspace_size(rf_ctx *ctx, const rf_lstm_policy_desc *desc, int max_batch)
 {
-    if (ctx != nullptr && hipSetDevice(ctx->device) != hipSuccess)
-        (void)hipGetLastError();
+    if (ctx != nullptr)
+        ignore_error(hipSetDevice(ctx->device));
     return lstm_workspace_size_any(ctx, desc, false, RF_LSTM_CRITIC_LSTM, max_batch);
 }
 
@@ -3026,34 +2815,19 @@ static int lstm_update_any(const char *fn, bool sde, int critic, rf_ctx *ctx, co
     rf::LstmPpoWork work;
     RF_REQUIRE(rf::lstm_ppo_work(layout, B, work), "%s: no workspace layout for B = %d", fn, B);
     const size_t rows = (size_t)N, slab = (size_t)(n_steps + 1) * (size_t)num_envs;
-    struct Array {
-        const void *p;
-        size_t bytes, align;
-        const char *what;
-    };
-    const Array inputs[] = {{d_observations, rows * (size_t)layout.obs_width * 4, 4, "d_observations"},
-                            {d_actions, rows * (sde ? 4 : 8), sde ? (size_t)4 : (size_t)8, "d_actions"},
-                            {d_log_probs, rows * 4, 4, "d_log_probs"},
-                            {d_advantages, rows * 4, 4, "d_advantages"},
-                            {d_returns, rows * 4, 4, "d_returns"},
-                            {d_episode_starts, slab, 1, "d_episode_starts"},
-                            {d_lstm_states, slab * 4 * (size_t)layout.hidden * 4, 4, "d_lstm_states"}};
-    const Array outputs[] = {{d_params, (size_t)layout.total * 4, 4, "d_params"},
-                             {d_state, 4 * (size_t)rf::kPpoStateHeader + 8 * (size_t)layout.total, 8, "d_state"},
-                             {d_workspace, (size_t)work.total * 4, 8, "d_workspace"},
-                             {d_stats, 32, 4, "d_stats"}};
-    for (const Array &a : inputs)
-        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
-            return rc;
-    for (const Array &a : outputs) {
-        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
-            return rc;
-        for (const Array &b : inputs)
-            RF_REQUIRE(!ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s (an output must not alias an "
-                       "input: other blocks still read it)", fn, a.what, b.what);
-        for (const Array &b : outputs)
-            RF_REQUIRE(&b >= &a || !ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s", fn, a.what, b.what);
-    }
+    const DeviceArray inputs[] = {{d_observations, rows * (size_t)layout.obs_width * 4, 4, "d_observations"},
+                                  {d_actions, rows * (sde ? 4 : 8), sde ? (size_t)4 : (size_t)8, "d_actions"},
+                                  {d_log_probs, rows * 4, 4, "d_log_probs"},
+                                  {d_advantages, rows * 4, 4, "d_advantages"},
+                                  {d_returns, rows * 4, 4, "d_returns"},
+                                  {d_episode_starts, slab, 1, "d_episode_starts"},
+                                  {d_lstm_states, slab * 4 * (size_t)layout.hidden * 4, 4, "d_lstm_states"}};
+    const DeviceArray outputs[] = {{d_params, (size_t)layout.total * 4, 4, "d_params"},
+                                   {d_state, 4 * (size_t)rf::kPpoStateHeader + 8 * (size_t)layout.total, 8, "d_state"},
+                                   {d_workspace, (size_t)work.total * 4, 8, "d_workspace"},
+                                   {d_stats, 32, 4, "d_stats"}};
+    if (int rc = check_device_arrays(ctx, inputs, outputs, fn))
+        return rc;
     const hipStream_t caller = (hipStream_t)caller_stream;
     if (int rc = refuse_capturing(caller, fn))
         return rc;
@@ -3106,15 +2880,15 @@ int rf_lstm_ppo_update(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const rf_pp
 
 unsigned long long rf_lstm_sde_state_size(rf_ctx *ctx, const rf_lstm_policy_desc *desc)
 {
-    if (ctx != nullptr && hipSetDevice(ctx->device) != hipSuccess) // (as every entry point; nothing of the device is needed)
-        (void)hipGetLastError();
+    if (ctx != nullptr)
+        ignore_error(hipSetDevice(ctx->device));
     return lstm_state_size_any(ctx, desc, true, RF_LSTM_CRITIC_LSTM);
 }
 
 unsigned long long rf_lstm_sde_workspace_size(rf_ctx *ctx, const rf_lstm_policy_desc *desc, int max_batch)
 {
-    if (ctx != nullptr && hipSetDevice(ctx->device) != hipSuccess)
-        (void)hipGetLastError();
+    if (ctx != nullptr)
+        ignore_error(hipSetDevice(ctx->device));
     return lstm_workspace_size_any(ctx, desc, true, RF_LSTM_CRITIC_LSTM, max_batch);
 }
 
@@ -3134,8 +2908,8 @@ int rf_lstm_sde_update(rf_ctx *ctx, const rf_lstm_policy_desc *desc, const rf_pp
 // ---- "lstm critic": the siblings over rf_lstm_critic_desc -- thin wrappers around the bodies above --------------------------
 unsigned long long rf_lstm_critic_params_size(rf_ctx *ctx, const rf_lstm_critic_desc *desc)
 {
-    if (ctx != nullptr && hipSetDevice(ctx->device) != hipSuccess) // (as every entry point; nothing of the device is needed)
-        (void)hipGetLastError();
+    if (ctx != nullptr)
+        ignore_error(hipSetDevice(ctx->device));
     return desc == nullptr ? 0 : lstm_params_size_any(ctx, &desc->lstm, false, desc->critic);
 }
 
@@ -3154,15 +2928,15 @@ int rf_lstm_critic_forward(rf_ctx *ctx, const rf_lstm_critic_desc *desc, const f
 
 unsigned long long rf_lstm_critic_ppo_state_size(rf_ctx *ctx, const rf_lstm_critic_desc *desc)
 {
-    if (ctx != nullptr && hipSetDevice(ctx->device) != hipSuccess)
-        (void)hipGetLastError();
+    if (ctx != nullptr)
+        ignore_error(hipSetDevice(ctx->device));
     return desc == nullptr ? 0 : lstm_state_size_any(ctx, &desc->lstm, false, desc->critic);
 }
 
 unsigned long long rf_lstm_critic_ppo_workspace_size(rf_ctx *ctx, const rf_lstm_critic_desc *desc, int max_batch)
 {
-    if (ctx != nullptr && hipSetDevice(ctx->device) != hipSuccess)
-        (void)hipGetLastError();
+    if (ctx != nullptr)
+        ignore_error(hipSetDevice(ctx->device));
     return desc == nullptr ? 0 : lstm_workspace_size_any(ctx, &desc->lstm, false, desc->critic, max_batch);
 }
 
@@ -3182,8 +2956,8 @@ int rf_lstm_critic_ppo_update(rf_ctx *ctx, const rf_lstm_critic_desc *desc, cons
 
 unsigned long long rf_lstm_critic_sde_params_size(rf_ctx *ctx, const rf_lstm_critic_desc *desc)
 {
-    if (ctx != nullptr && hipSetDevice(ctx->device) != hipSuccess)
-        (void)hipGetLastError();
+    if (ctx != nullptr)
+        ignore_error(hipSetDevice(ctx->device));
     return desc == nullptr ? 0 : lstm_params_size_any(ctx, &desc->lstm, true, desc->critic);
 }
 
@@ -3213,15 +2987,15 @@ int rf_lstm_critic_sde_forward(rf_ctx *ctx, const rf_lstm_critic_desc *desc, con
 
 unsigned long long rf_lstm_critic_sde_state_size(rf_ctx *ctx, const rf_lstm_critic_desc *desc)
 {
-    if (ctx != nullptr && hipSetDevice(ctx->device) != hipSuccess)
-        (void)hipGetLastError();
+    if (ctx != nullptr)
+        ignore_error(hipSetDevice(ctx->device));
     return desc == nullptr ? 0 : lstm_state_size_any(ctx, &desc->lstm, true, desc->critic);
 }
 
 unsigned long long rf_lstm_critic_sde_workspace_size(rf_ctx *ctx, const rf_lstm_critic_desc *desc, int max_batch)
 {
-    if (ctx != nullptr && hipSetDevice(ctx->device) != hipSuccess)
-        (void)hipGetLastError();
+    if (ctx != nullptr)
+        ignore_error(hipSetDevice(ctx->device));
     return desc == nullptr ? 0 : lstm_workspace_size_any(ctx, &desc->lstm, true, desc->critic, max_batch);
 }
 

@@ -10,15 +10,6 @@
 
 using namespace rfh;
 
-#define RF_LSTM_LIMITS "%s: the desc is outside the limits (obs_width and lstm_hidden 1 .. %d, 1 or 2 hidden layers of width " \
-                       "1 .. %d per net, n_actions 2 .. %d, activation RF_POLICY_RELU or RF_POLICY_TANH, critic " \
-                       "RF_LSTM_CRITIC_LSTM or RF_LSTM_CRITIC_LINEAR)"
-
-static bool lstm_layout_any(const rf_lstm_policy_desc *desc, bool sde, int critic, rf::LstmLayout &layout)
-{
-    return desc != nullptr && rf::lstm_layout_nets(*desc, layout, sde, critic);
-}
-
 extern "C" {
 
 // One set for both critic kinds (rf_lstm_critic_desc.critic); the Categorical head only.
@@ -34,7 +25,7 @@ int rf_lstm_forward_grouped(rf_ctx *ctx, const rf_lstm_critic_desc *desc, int G,
     RF_REQUIRE(desc != nullptr && d_params != nullptr && d_obs != nullptr && d_episode_starts != nullptr &&
                d_state_in != nullptr, "%s: NULL argument", fn);
     rf::LstmLayout layout;
-    RF_REQUIRE(lstm_layout_any(&desc->lstm, false, desc->critic, layout), RF_LSTM_LIMITS, fn, RF_POLICY_MAX_WIDTH,
+    RF_REQUIRE(rf::lstm_layout_nets(desc->lstm, layout, false, desc->critic), RF_LSTM_LIMITS, fn, RF_POLICY_MAX_WIDTH,
                RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_ACTIONS);
     RF_REQUIRE(rf::population_rows(G, m), "%s: G = %d must be in 1 .. %d, m = %d at least 1 and G m at most 2^30", fn, G,
                RF_POPULATION_MAX_GROUPS, m);
@@ -48,49 +39,20 @@ int rf_lstm_forward_grouped(rf_ctx *ctx, const rf_lstm_critic_desc *desc, int G,
     const int lanes = G * m;
     const size_t rows = (size_t)lanes;
     const size_t state_bytes = rf::lstm_state_floats(lanes, layout.hidden) * 4;
-    struct Array {
-        const void *p;
-        size_t bytes, align;
-        const char *what;
-    };
-    const Array inputs[] = {{d_params, (size_t)G * (size_t)layout.total * 4, 4, "d_params"},
-                            {d_obs, rows * (size_t)layout.obs_width * 4, 4, "d_obs"},
-                            {d_episode_starts, rows, 1, "d_episode_starts"},
-                            {d_final_obs, rows * (size_t)layout.obs_width * 4, 4, "d_final_obs"},
-                            {d_state_in, state_bytes, 4, "d_state_in"},
-                            {sampled ? d_gens : nullptr, (size_t)G * 32, 8, "d_gens"}};
-    const Array outputs[] = {{d_actions, rows * 8, 8, "d_actions"},
-                             {d_log_probs, rows * 4, 4, "d_log_probs"},
-                             {d_values, rows * 4, 4, "d_values"},
-                             {d_final_values, rows * 4, 4, "d_final_values"},
-                             {d_logits, rows * (size_t)layout.mlp.n_actions * 4, 4, "d_logits"},
-                             {d_state_out, state_bytes, 4, "d_state_out"}};
-    for (const Array &a : inputs) {
-        if (a.p == nullptr)
-            continue;
-        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
-            return rc;
-    }
-    for (const Array &a : outputs) {
-        if (a.p == nullptr)
-            continue;
-        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
-            return rc;
-        for (const Array &b : inputs) {
-            if (&a == &outputs[5] && &b == &inputs[4]) { // d_state_out against d_state_in
-                // in place (a block reads its own rows of the state before it writes them), or apart
-                RF_REQUIRE(a.p == b.p || !ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: d_state_out overlaps d_state_in "
-                           "without being it (the same pointer updates the state in place; any other overlap would have a "
-                           "block overwrite rows another still reads)", fn);
-                continue;
-            }
-            RF_REQUIRE(b.p == nullptr || !ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s (an output must "
-                       "not alias an input: other blocks still read it)", fn, a.what, b.what);
-        }
-        for (const Array &b : outputs)
-            RF_REQUIRE(&b >= &a || b.p == nullptr || !ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s", fn,
-                       a.what, b.what);
-    }
+    const DeviceArray inputs[] = {{d_params, (size_t)G * (size_t)layout.total * 4, 4, "d_params"},
+                                  {d_obs, rows * (size_t)layout.obs_width * 4, 4, "d_obs"},
+                                  {d_episode_starts, rows, 1, "d_episode_starts"},
+                                  {d_final_obs, rows * (size_t)layout.obs_width * 4, 4, "d_final_obs"},
+                                  {d_state_in, state_bytes, 4, "d_state_in"},
+                                  {sampled ? d_gens : nullptr, (size_t)G * 32, 8, "d_gens"}};
+    const DeviceArray outputs[] = {{d_actions, rows * 8, 8, "d_actions"},
+                                   {d_log_probs, rows * 4, 4, "d_log_probs"},
+                                   {d_values, rows * 4, 4, "d_values"},
+                                   {d_final_values, rows * 4, 4, "d_final_values"},
+                                   {d_logits, rows * (size_t)layout.mlp.n_actions * 4, 4, "d_logits"},
+                                   {d_state_out, state_bytes, 4, "d_state_out"}};
+    if (int rc = check_device_arrays(ctx, inputs, outputs, fn, kStateInPlace))
+        return rc;
     const hipStream_t caller = (hipStream_t)caller_stream;
     if (int rc = refuse_capturing(caller, fn))
         return rc;
@@ -115,8 +77,7 @@ unsigned long long rf_lstm_ppo_grouped_state_size(rf_ctx *ctx, const rf_lstm_cri
 {
     if (ctx == nullptr || desc == nullptr)
         return 0;
-    if (hipSetDevice(ctx->device) != hipSuccess) // (as every entry point; nothing of the device is needed)
-        (void)hipGetLastError();
+    ignore_error(hipSetDevice(ctx->device));
     return rf::lstm_population_state_bytes(*desc, G, m);
 }
 
@@ -125,8 +86,7 @@ unsigned long long rf_lstm_ppo_grouped_workspace_size(rf_ctx *ctx, const rf_lstm
 {
     if (ctx == nullptr || desc == nullptr)
         return 0;
-    if (hipSetDevice(ctx->device) != hipSuccess)
-        (void)hipGetLastError();
+    ignore_error(hipSetDevice(ctx->device));
     return rf::lstm_population_workspace_bytes(*desc, G, m, T, B);
 }
 
@@ -143,7 +103,7 @@ int rf_lstm_ppo_update_grouped(rf_ctx *ctx, const rf_lstm_critic_desc *desc, int
                d_advantages && d_returns && d_episode_starts && d_lstm_states && d_firsts && d_stats, "%s: NULL argument",
                fn);
     rf::LstmLayout layout;
-    RF_REQUIRE(lstm_layout_any(&desc->lstm, false, desc->critic, layout), RF_LSTM_LIMITS, fn, RF_POLICY_MAX_WIDTH,
+    RF_REQUIRE(rf::lstm_layout_nets(desc->lstm, layout, false, desc->critic), RF_LSTM_LIMITS, fn, RF_POLICY_MAX_WIDTH,
                RF_POLICY_MAX_WIDTH, RF_POLICY_MAX_ACTIONS);
     RF_REQUIRE(m >= 1 && T >= 1 && rf::population_rows(G, (long long)m * (long long)T),
                "%s: G = %d must be in 1 .. %d, m = %d and T = %d at least 1 and G m T at most 2^30", fn, G,
@@ -155,36 +115,21 @@ int rf_lstm_ppo_update_grouped(rf_ctx *ctx, const rf_lstm_critic_desc *desc, int
     RF_REQUIRE(rf::lstm_ppo_work(layout, B, work), "%s: no workspace layout for B = %d", fn, B);
     const size_t groups = (size_t)G, rows = groups * (size_t)N, slab = (size_t)(T + 1) * (size_t)lanes;
     const size_t state_floats = (size_t)rf::kPpoStateHeader + 2 * (size_t)layout.total;
-    struct Array {
-        const void *p;
-        size_t bytes, align;
-        const char *what;
-    };
-    const Array inputs[] = {{d_observations, rows * (size_t)layout.obs_width * 4, 4, "d_observations"},
-                            {d_actions, rows * 8, 8, "d_actions"},
-                            {d_log_probs, rows * 4, 4, "d_log_probs"},
-                            {d_advantages, rows * 4, 4, "d_advantages"},
-                            {d_returns, rows * 4, 4, "d_returns"},
-                            {d_episode_starts, slab, 1, "d_episode_starts"},
-                            {d_lstm_states, slab * 4 * (size_t)layout.hidden * 4, 4, "d_lstm_states"},
-                            {d_firsts, groups * 4, 4, "d_firsts"},
-                            {d_hyper, groups * sizeof(rf_ppo_hyper), 8, "d_hyper"}};
-    const Array outputs[] = {{d_params, groups * (size_t)layout.total * 4, 4, "d_params"},
-                             {d_state, groups * state_floats * 4, 8, "d_state"},
-                             {d_workspace, groups * (size_t)work.total * 4, 8, "d_workspace"},
-                             {d_stats, groups * 32, 4, "d_stats"}};
-    for (const Array &a : inputs)
-        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
-            return rc;
-    for (const Array &a : outputs) {
-        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
-            return rc;
-        for (const Array &b : inputs)
-            RF_REQUIRE(!ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s (an output must not alias an "
-                       "input: other blocks still read it)", fn, a.what, b.what);
-        for (const Array &b : outputs)
-            RF_REQUIRE(&b >= &a || !ranges_overlap(a.p, a.bytes, b.p, b.bytes), "%s: %s overlaps %s", fn, a.what, b.what);
-    }
+    const DeviceArray inputs[] = {{d_observations, rows * (size_t)layout.obs_width * 4, 4, "d_observations"},
+                                  {d_actions, rows * 8, 8, "d_actions"},
+                                  {d_log_probs, rows * 4, 4, "d_log_probs"},
+                                  {d_advantages, rows * 4, 4, "d_advantages"},
+                                  {d_returns, rows * 4, 4, "d_returns"},
+                                  {d_episode_starts, slab, 1, "d_episode_starts"},
+                                  {d_lstm_states, slab * 4 * (size_t)layout.hidden * 4, 4, "d_lstm_states"},
+                                  {d_firsts, groups * 4, 4, "d_firsts"},
+                                  {d_hyper, groups * sizeof(rf_ppo_hyper), 8, "d_hyper"}};
+    const DeviceArray outputs[] = {{d_params, groups * (size_t)layout.total * 4, 4, "d_params"},
+                                   {d_state, groups * state_floats * 4, 8, "d_state"},
+                                   {d_workspace, groups * (size_t)work.total * 4, 8, "d_workspace"},
+                                   {d_stats, groups * 32, 4, "d_stats"}};
+    if (int rc = check_device_arrays(ctx, inputs, outputs, fn))
+        return rc;
     const hipStream_t caller = (hipStream_t)caller_stream;
     if (int rc = refuse_capturing(caller, fn))
         return rc;

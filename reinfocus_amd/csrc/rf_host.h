@@ -5,13 +5,15 @@
 //   rf_abi_render.hip   which render kernel a launch takes (render_form, pick_tile_layout, launch_render), rf_render,
 //                       the frame buffer, the focus measure (launch_focus, rf_focus, rf_step)
 //   rf_abi_general.hip  rf_render_general
-//   rf_abi_env.hip      the device-resident environment step and its schedules
-//                       and rf_rollout_advantages (rollout_gae_kernel, rf_rollout.h), which shares its pointer checks,
-//                       and rf_policy_forward (policy_forward_kernel, rf_policy.h), which shares them too
-//                       and rf_ppo_update (the three kernels of rf_ppo.h), which shares them as well
-//                       and rf_sde_noise_reset / rf_sde_forward (rf_sde.h) / rf_sde_update (rf_ppo.h's Gaussian head)
-//                       and rf_lstm_forward (lstm_forward_kernel, rf_lstm.h)
-//                       and rf_lstm_ppo_update (the five kernels of rf_lstm_ppo.h, then rf_ppo.h's ppo_adam_kernel)
+//   rf_abi_env.hip      the device-resident environment step and its schedules; then the learner
+//                       entry points over caller-owned device arrays, ungrouped and grouped ("population") alike but for
+//                       the grouped recurrent ones:
+//                         rf_rollout_advantages*                   rollout_gae_kernel (rf_rollout.h)
+//                         rf_policy_forward*                       policy_forward_kernel (rf_policy.h)
+//                         rf_ppo_update*, rf_sde_update*           the three kernels of rf_ppo.h (either head)
+//                         rf_sde_noise_reset*, rf_sde_forward*     rf_sde.h
+//                         rf_lstm_*, rf_lstm_critic_* forwards     lstm_forward_kernel (rf_lstm.h), rf_sde.h's noise kernel
+//                         ... and updates                          the five kernels of rf_lstm_ppo.h, then ppo_adam_kernel
 //   rf_abi_snapshot.hip snapshots of a device-resident environment (rf_env_snapshot* / rf_env_restore*): copies only
 //   rf_abi_lstm_grouped.hip  "population lstm": rf_lstm_forward_grouped, rf_lstm_ppo_update_grouped and their size
 //                       functions -- the kGrouped instantiations of rf_lstm.h and rf_lstm_ppo.h, compiled apart from the
@@ -314,6 +316,9 @@ inline hipError_t host_malloc(void **p, size_t bytes)
 }
 
 // ---- what the entry points over caller-owned device arrays share (rf_abi_env.hip, rf_abi_lstm_grouped.hip) ----------------
+// check_device_array asks the runtime about one array (rf_abi_snapshot.hip and the device steps use it alone),
+// refuse_capturing about the caller's stream, ranges_overlap compares two address ranges; check_device_arrays is the
+// learner entry points' whole rule -- which arrays may alias and what a refusal says -- over the tables each of them keeps.
 // A caller's array of `bytes` bytes: device memory of the context's GPU, aligned for its elements, and inside one
 // allocation -- asked of the runtime, never dereferenced.
 inline int check_device_array(const rf_ctx *ctx, const void *p, size_t bytes, size_t align, const char *what, const char *fn)
@@ -353,5 +358,70 @@ inline bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t 
     const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
     return x < y + b_bytes && y < x + a_bytes;
 }
+
+// One row of an entry point's table of arrays: what it reads (inputs) or writes (outputs).  p == null: not handed in.
+struct DeviceArray {
+    const void *p;
+    size_t bytes, align;
+    const char *what;
+};
+
+// What an entry point may ask of check_device_arrays beyond the common rule
+enum ArrayRule : unsigned {
+    kStateInPlace = 1u,    // the output "d_state_out" may be the input "d_state_in" itself (the recurrent forwards)
+    kNotAmongOutputs = 2u, // the outputs are not held against each other (the rollout does that itself, in its own words)
+};
+
+// The contract of every entry point over caller-owned arrays, in the order in which a call with several faults hears of
+// them: every input that is there passes check_device_array, in table order; then every output that is there, in table
+// order, passes it too, overlaps no input (table order) and no earlier output.  `why` is what the refusal of an aliased
+// input ends on (null: the bare "overlaps").
+template <size_t kIn, size_t kOut>
+inline int check_device_arrays(const rf_ctx *ctx, const DeviceArray (&inputs)[kIn], const DeviceArray (&outputs)[kOut],
+                               const char *fn, unsigned rules = 0, const char *why = "other blocks still read it")
+{
+    for (const DeviceArray &a : inputs)
+        if (a.p != nullptr)
+            if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
+                return rc;
+    for (const DeviceArray &a : outputs) {
+        if (a.p == nullptr)
+            continue;
+        if (int rc = check_device_array(ctx, a.p, a.bytes, a.align, a.what, fn))
+            return rc;
+        for (const DeviceArray &b : inputs) {
+            if (b.p == nullptr || !ranges_overlap(a.p, a.bytes, b.p, b.bytes))
+                continue;
+            if ((rules & kStateInPlace) && !strcmp(a.what, "d_state_out") && !strcmp(b.what, "d_state_in")) {
+                // in place (a block reads its own rows of the state before it writes them), or apart
+                RF_REQUIRE(a.p == b.p, "%s: d_state_out overlaps d_state_in without being it (the same pointer updates the "
+                           "state in place; any other overlap would have a block overwrite rows another still reads)", fn);
+                continue;
+            }
+            if (why != nullptr)
+                set_err("%s: %s overlaps %s (an output must not alias an input: %s)", fn, a.what, b.what, why);
+            else
+                set_err("%s: %s overlaps %s", fn, a.what, b.what);
+            return RF_ERR_INVALID;
+        }
+        for (const DeviceArray *b = outputs; b != &a && !(rules & kNotAmongOutputs); ++b)
+            RF_REQUIRE(b->p == nullptr || !ranges_overlap(a.p, a.bytes, b->p, b->bytes), "%s: %s overlaps %s", fn, a.what,
+                       b->what);
+    }
+    return RF_OK;
+}
+
+// ignore_error(hipSetDevice(ctx->device)): the size functions make the context's device current as every entry point does,
+// though they need nothing of it.  All they can return is a size, so what the runtime says to that is dropped.
+inline void ignore_error(hipError_t e)
+{
+    if (e != hipSuccess)
+        (void)hipGetLastError();
+}
+
+// what the recurrent entry points of both units say of a desc they refuse (the Categorical head)
+#define RF_LSTM_LIMITS "%s: the desc is outside the limits (obs_width and lstm_hidden 1 .. %d, 1 or 2 hidden layers of width " \
+                       "1 .. %d per net, n_actions 2 .. %d, activation RF_POLICY_RELU or RF_POLICY_TANH, critic " \
+                       "RF_LSTM_CRITIC_LSTM or RF_LSTM_CRITIC_LINEAR)"
 
 } // namespace rfh
