@@ -1347,8 +1347,8 @@ int rf_lstm_critic_sde_update(rf_ctx *ctx, const rf_lstm_critic_desc *desc, cons
  *     is skipped and flagged in its own stats[7] exactly as step 8 says; the other groups are untouched by it.
  * Limits: G 1 .. RF_POPULATION_MAX_GROUPS (the grid's y / z limit), m >= 1, G m <= 2^30 (G N alike), B as in G4.
  * A normaliser and GAE discounts per group: "population view", above.  The Gaussian head: "population sde", below.  Out of
- * scope: groups that differ in architecture, m, T or B.  The recurrent head: "population lstm", below (the lstm-sde head in
- * a population is out of scope).
+ * scope: groups that differ in architecture, m, T or B.  The recurrent head: "population lstm", below, and with the
+ * Gaussian head "population lstm sde", at the end.
  *
  *   rf_policy_forward_grouped      rf_policy_forward over (G, m) in place of n: one launch, grid (ceil(m / 8), nets, G);
  *                                  the same outputs over G m rows, the same refusals (with d_gens, a device array, in
@@ -1396,7 +1396,8 @@ int rf_ppo_update_grouped(rf_ctx *ctx, const rf_policy_desc *policy, int G, int 
  *     group.  The caller adds m L to consumed[g] of every selected group after the call.
  *  S3 Forward.  Group g's rows are computed from params[g] (its own log_std in sigma) and its own rows of theta.
  * Limits: G 1 .. RF_POPULATION_MAX_GROUPS, m 1 .. 2^20 (an update: m >= 1), G m <= 2^30 (G m T alike),
- * 1 <= B <= min(m T, RF_PPO_MAX_BATCH), n_actions 1.  Out of scope: more than one action dimension.
+ * 1 <= B <= min(m T, RF_PPO_MAX_BATCH), n_actions 1.  The Gaussian head on the LSTM: "population lstm sde", at the end.
+ * Out of scope: more than one action dimension.
  *
  *   rf_sde_noise_reset_grouped     rf_sde_noise_reset over (G, m) in place of n: one launch, grid (ceil(m L / 256), G); the
  *                                  same refusals (with d_gens, a device array, in place of gen), d_consumed or d_select no
@@ -1452,8 +1453,8 @@ int /* population sde */ rf_sde_update_grouped(rf_ctx *ctx, const rf_policy_desc
  *     value outside sets the group's validity flag, so the group is skipped with RF_PPO_INVALID in its stats[7] exactly as
  *     an invalid index is in rf_ppo_update_grouped; the other groups are untouched by it.
  * Limits: G 1 .. RF_POPULATION_MAX_GROUPS, m >= 1, T >= 1, G m <= 2^30 (G m T alike), 1 <= B <= min(m T,
- * RF_PPO_MAX_BATCH); the desc as "lstm policy" / "lstm critic".  Out of scope: the lstm-sde head in a population; groups
- * that differ in architecture, critic, m, T or B.
+ * RF_PPO_MAX_BATCH); the desc as "lstm policy" / "lstm critic".  The lstm-sde head in a population: "population lstm
+ * sde", below.  Out of scope: groups that differ in architecture, critic, m, T or B.
  *
  *   rf_lstm_forward_grouped             rf_lstm_forward / rf_lstm_critic_forward over (G, m) in place of n: one launch, grid
  *                                       (ceil(m / 8), nets, G); the same outputs over G m rows, the same refusals (with
@@ -1484,6 +1485,63 @@ int /* population lstm */ rf_lstm_ppo_update_grouped(rf_ctx *ctx, const rf_lstm_
         const long long *d_actions, const float *d_log_probs, const float *d_advantages, const float *d_returns,
         const uint8_t *d_episode_starts, const float *d_lstm_states, const int *d_firsts /* [G] */, int B,
         float *d_stats, void *caller_stream);
+
+/* ---- population lstm sde: a population of recurrent gSDE learners (the Gaussian head on the LSTM, either critic) -----------
+ * The reference trains ContinuousJumps-v0 with the recurrent policy and use_sde (examples/ppo_lstm_untuned.yml), and its
+ * ppo_lstm search draws a log_std_init and a sde_sample_freq per trial.  Written as deltas of "population sde" (S1 - S3) and
+ * "population lstm" (L1 - L4): the arithmetic of a group is exactly that of "lstm sde policy" / "lstm sde update" with
+ * either critic kind of "lstm critic"; only addressing changes.  numpy twins environments/population.py (G of
+ * lstm_sde.LstmSdePolicy / lstm_learner.LstmLearner over slices), kernels sde_noise_kernel<true> (csrc/rf_sde.h),
+ * lstm_forward_kernel<true, kLinear, true> (csrc/rf_lstm.h), lstm_ppo_forward_kernel<kLinear, true>,
+ * lstm_ppo_mlp_kernel<true, true>, lstm_ppo_bptt_kernel<true>, lstm_ppo_gradient_kernel<true, kLinear, true>,
+ * lstm_ppo_norm_kernel<true> (csrc/rf_lstm_ppo.h) and ppo_adam_kernel<true> (csrc/rf_ppo.h).
+ *
+ *  S1' S1 with the P + L of rf_lstm_critic_sde_params_size: d_params is float32 [G][P + L], group g's log_std the last L
+ *      floats of its own piece; d_actions of an update are the raw actions, float32 [G N].
+ *  S2' S2 unchanged: theta[(g m + e) L + k] is what a stand-alone rf_lstm_critic_sde_noise_reset over the group's m rows
+ *      gives whose generator was advanced by consumed[g] before; log_std_k is read at params + g (P + L) + P.
+ *  S3' S3 over the recurrent forward: group g's rows are computed from params[g] and its own rows of theta, d_env_actions
+ *      and d_sigma.  Nothing is drawn in a forward (the noise is theta): no generator travels, and a NULL d_theta or
+ *      RF_POLICY_DETERMINISTIC gives the mean.  Each pi output may be asked for by itself.
+ *  L1' - L4' L1 (without G3: no generators in a forward), L2, L3 and L4 hold unchanged, with the workspace of
+ *      rf_lstm_critic_sde_workspace_size.  The validity rule of a group's minibatch is the Gaussian head's (a NaN raw
+ *      action), OR-ed with L4's flag of a first row outside the group.
+ * Limits: G 1 .. RF_POPULATION_MAX_GROUPS, m 1 .. 2^20 (an update: m >= 1), T >= 1, G m <= 2^30 (G m T alike),
+ * 1 <= B <= min(m T, RF_PPO_MAX_BATCH); the desc as "lstm sde policy" / "lstm critic".  Out of scope: groups that differ in
+ * architecture, critic, m, T or B; more than one action dimension.
+ *
+ *   rf_lstm_sde_noise_reset_grouped     rf_lstm_critic_sde_noise_reset over (G, m) in place of n: one launch, grid
+ *                                       (ceil(m L / 256), G); the refusals of rf_sde_noise_reset_grouped with the lstm-sde
+ *                                       limits of the desc.
+ *   rf_lstm_sde_forward_grouped         rf_lstm_critic_sde_forward over (G, m) in place of n: one launch, grid (ceil(m / 8),
+ *                                       nets, G); the same outputs over G m rows, the same refusals, G or m outside the
+ *                                       limits, and a capturing caller stream.
+ *   rf_lstm_sde_grouped_state_size      G (32 + 8 (P + L)) bytes; 0 where rf_lstm_ppo_grouped_state_size is, over the
+ *                                       lstm-sde limits
+ *   rf_lstm_sde_grouped_workspace_size  G times the ungrouped lstm-sde workspace of B; 0 where
+ *                                       rf_lstm_ppo_grouped_workspace_size is
+ *   rf_lstm_sde_update_grouped          rf_lstm_critic_sde_update over (G, m, T): six launches whatever G is; the refusals of
+ *                                       rf_lstm_ppo_update_grouped with the lstm-sde limits of the desc.
+ * A refused call returns RF_ERR_INVALID, enqueues nothing and dereferences no device pointer.
+ * (The tag between return type and name: tests/test_lstm_sde_logic.py and tests/test_sde_logic.py take a census of the plain
+ * rf_lstm_sde_ / rf_sde_ declarations, and these five are not among them.) */
+int /* population lstm sde */ rf_lstm_sde_noise_reset_grouped(rf_ctx *ctx, const rf_lstm_critic_desc *desc, int G, int m,
+        const float *d_params, const unsigned long long *d_gens /* [G][4] */, const unsigned long long *d_consumed /* [G] */,
+        const unsigned char *d_select /* [G] or NULL */, float *d_theta /* [G m][L] */, void *caller_stream);
+int /* population lstm sde */ rf_lstm_sde_forward_grouped(rf_ctx *ctx, const rf_lstm_critic_desc *desc, int G, int m,
+        const float *d_params, const float *d_obs, const uint8_t *d_episode_starts, const float *d_final_obs,
+        const float *d_state_in, float *d_state_out, const float *d_theta, int flags, float *d_actions,
+        float *d_env_actions, float *d_log_probs, float *d_values, float *d_final_values, float *d_mean, float *d_sigma,
+        void *caller_stream);
+unsigned long long /* population lstm sde */ rf_lstm_sde_grouped_state_size(rf_ctx *ctx, const rf_lstm_critic_desc *desc,
+        int G, int m);
+unsigned long long /* population lstm sde */ rf_lstm_sde_grouped_workspace_size(rf_ctx *ctx, const rf_lstm_critic_desc *desc,
+        int G, int m, int T, int B);
+int /* population lstm sde */ rf_lstm_sde_update_grouped(rf_ctx *ctx, const rf_lstm_critic_desc *desc, int G, int m, int T,
+        const rf_ppo_hyper *d_hyper, float *d_params, void *d_state, void *d_workspace, const float *d_observations,
+        const float *d_actions /* float32 raw */, const float *d_log_probs, const float *d_advantages,
+        const float *d_returns, const uint8_t *d_episode_starts, const float *d_lstm_states,
+        const int *d_firsts /* [G] */, int B, float *d_stats, void *caller_stream);
 
 #ifdef __cplusplus
 }

@@ -147,6 +147,11 @@ SYMBOLS = (
     "rf_lstm_ppo_grouped_state_size",
     "rf_lstm_ppo_grouped_workspace_size",
     "rf_lstm_ppo_update_grouped",
+    "rf_lstm_sde_noise_reset_grouped",
+    "rf_lstm_sde_forward_grouped",
+    "rf_lstm_sde_grouped_state_size",
+    "rf_lstm_sde_grouped_workspace_size",
+    "rf_lstm_sde_update_grouped",
     "rf_render_kernel_name",
     "rf_pixels_rendered",
     "rf_allocations_poisoned",
@@ -473,6 +478,15 @@ def load():
     lib.rf_lstm_ppo_grouped_workspace_size.restype = ctypes.c_ulonglong
     lib.rf_lstm_ppo_grouped_workspace_size.argtypes = [vp, vp, i32, i32, i32, i32]
     lib.rf_lstm_ppo_update_grouped.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp,
+                                               vp]
+    lib.rf_lstm_sde_noise_reset_grouped.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    lib.rf_lstm_sde_forward_grouped.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp,
+                                                vp]
+    lib.rf_lstm_sde_grouped_state_size.restype = ctypes.c_ulonglong
+    lib.rf_lstm_sde_grouped_state_size.argtypes = [vp, vp, i32, i32]
+    lib.rf_lstm_sde_grouped_workspace_size.restype = ctypes.c_ulonglong
+    lib.rf_lstm_sde_grouped_workspace_size.argtypes = [vp, vp, i32, i32, i32, i32]
+    lib.rf_lstm_sde_update_grouped.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp,
                                                vp]
     lib.rf_render_kernel_name.restype = ctypes.c_char_p
     lib.rf_render_kernel_name.argtypes = [vp]
@@ -967,6 +981,50 @@ class Context:
         rows are (firsts[g] + b) mod (per_group x steps), b < batch, of its piece of the flat arrays (firsts_ptr: device
         int32 [groups]), hyper_ptr the device array of `groups` rf_ppo_hyper, stats_ptr float32 [groups][8].  Only enqueues."""
         rc = self._lib.rf_lstm_ppo_update_grouped(self._h, ctypes.byref(LstmCriticDesc(*desc)), groups, per_group, steps,
+                                                  hyper_ptr, params_ptr, state_ptr, workspace_ptr, observations_ptr,
+                                                  actions_ptr, log_probs_ptr, advantages_ptr, returns_ptr, episode_starts_ptr,
+                                                  lstm_states_ptr, firsts_ptr, batch, stats_ptr, stream)
+        if rc != 0:
+            _check(rc)
+
+    # --- population lstm sde (rf_lstm_sde_*_grouped): the two sections above together -- the recurrent policy with the
+    # Gaussian head over G groups; `desc` is the eleven integers of rf_lstm_critic_desc (either critic) ---------------------
+    def lstm_sde_noise_reset_grouped(self, desc, groups, per_group, params_ptr, gens_ptr, consumed_ptr, select_ptr, theta_ptr,
+                                     stream):
+        """rf_lstm_sde_noise_reset_grouped: sde_noise_reset_grouped over the lstm-sde layout's log_std.  Only enqueues."""
+        rc = self._lib.rf_lstm_sde_noise_reset_grouped(self._h, ctypes.byref(LstmCriticDesc(*desc)), groups, per_group,
+                                                       params_ptr, gens_ptr, consumed_ptr, select_ptr, theta_ptr, stream)
+        if rc != 0:
+            _check(rc)
+
+    def lstm_sde_forward_grouped(self, desc, groups, per_group, params_ptr, obs_ptr, episode_starts_ptr, final_obs_ptr,
+                                 state_in_ptr, state_out_ptr, theta_ptr, flags, actions_ptr, env_actions_ptr, log_probs_ptr,
+                                 values_ptr, final_values_ptr, mean_ptr, sigma_ptr, stream):
+        """rf_lstm_sde_forward_grouped: lstm_sde_forward over groups x per_group rows, parameters [groups][P + L], theta
+        [groups x per_group][L] (None: deterministic), the state in its single form [2][2][groups x per_group][H].  Only
+        enqueues."""
+        rc = self._lib.rf_lstm_sde_forward_grouped(self._h, ctypes.byref(LstmCriticDesc(*desc)), groups, per_group, params_ptr,
+                                                   obs_ptr, episode_starts_ptr, final_obs_ptr, state_in_ptr, state_out_ptr,
+                                                   theta_ptr, flags, actions_ptr, env_actions_ptr, log_probs_ptr, values_ptr,
+                                                   final_values_ptr, mean_ptr, sigma_ptr, stream)
+        if rc != 0:
+            _check(rc)
+
+    def lstm_sde_grouped_state_size(self, desc, groups, per_group):
+        """rf_lstm_sde_grouped_state_size: bytes of the optimizer states of `groups` lstm-sde networks; 0 if refused."""
+        return int(self._lib.rf_lstm_sde_grouped_state_size(self._h, ctypes.byref(LstmCriticDesc(*desc)), groups, per_group))
+
+    def lstm_sde_grouped_workspace_size(self, desc, groups, per_group, steps, batch):
+        """rf_lstm_sde_grouped_workspace_size: as lstm_ppo_grouped_workspace_size, over the lstm-sde layout; 0 if refused."""
+        return int(self._lib.rf_lstm_sde_grouped_workspace_size(self._h, ctypes.byref(LstmCriticDesc(*desc)), groups,
+                                                                per_group, steps, batch))
+
+    def lstm_sde_update_grouped(self, desc, groups, per_group, steps, hyper_ptr, params_ptr, state_ptr, workspace_ptr,
+                                observations_ptr, actions_ptr, log_probs_ptr, advantages_ptr, returns_ptr,
+                                episode_starts_ptr, lstm_states_ptr, firsts_ptr, batch, stats_ptr, stream):
+        """rf_lstm_sde_update_grouped: lstm_ppo_update_grouped with the Gaussian head (actions float32, the raw ones).  Only
+        enqueues."""
+        rc = self._lib.rf_lstm_sde_update_grouped(self._h, ctypes.byref(LstmCriticDesc(*desc)), groups, per_group, steps,
                                                   hyper_ptr, params_ptr, state_ptr, workspace_ptr, observations_ptr,
                                                   actions_ptr, log_probs_ptr, advantages_ptr, returns_ptr, episode_starts_ptr,
                                                   lstm_states_ptr, firsts_ptr, batch, stats_ptr, stream)

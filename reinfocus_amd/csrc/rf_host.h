@@ -18,9 +18,12 @@
 //   rf_abi_lstm_grouped.hip  "population lstm": rf_lstm_forward_grouped, rf_lstm_ppo_update_grouped and their size
 //                       functions -- the kGrouped instantiations of rf_lstm.h and rf_lstm_ppo.h, compiled apart from the
 //                       ungrouped ones of rf_abi_env.hip (profiles/population_lstm.md)
+//   rf_abi_lstm_sde_grouped.hip  "population lstm sde": rf_lstm_sde_noise_reset_grouped, rf_lstm_sde_forward_grouped,
+//                       rf_lstm_sde_update_grouped and their size functions -- the kSde && kGrouped instantiations, compiled
+//                       apart from both units above (profiles/population_lstm_sde.md)
 //
-// Every kernel instantiation is defined in the unit that launches it (ppo_adam_kernel<true>, the last launch of both
-// grouped updates, in two: each has its own copy); the units share only host functions.
+// Every kernel instantiation is defined in the unit that launches it (ppo_adam_kernel<true>, the last launch of the three
+// grouped updates, in three: each has its own copy; sde_noise_kernel<true> in two); the units share only host functions.
 #pragma once
 #include <cstring>
 
@@ -315,7 +318,7 @@ inline hipError_t host_malloc(void **p, size_t bytes)
     return e;
 }
 
-// ---- what the entry points over caller-owned device arrays share (rf_abi_env.hip, rf_abi_lstm_grouped.hip) ----------------
+// ---- what the entry points over caller-owned device arrays share (rf_abi_env.hip and the two grouped recurrent units) ------
 // check_device_array asks the runtime about one array (rf_abi_snapshot.hip and the device steps use it alone),
 // refuse_capturing about the caller's stream, ranges_overlap compares two address ranges; check_device_arrays is the
 // learner entry points' whole rule -- which arrays may alias and what a refusal says -- over the tables each of them keeps.

@@ -103,6 +103,18 @@ RF_HD bool lstm_sde_layout(const rf_lstm_policy_desc &d, LstmLayout &p)
     return lstm_layout_nets(d, p, true);
 }
 
+// "population lstm sde": where group g's pieces begin, in floats -- its rows of theta [G n][L] (n the environments of ONE
+// group), and its log_std inside the parameters [G][P + L]: the last L floats of its own piece
+RF_HD size_t lstm_sde_group_theta(const LstmLayout &L, int n, size_t g)
+{
+    return g * (size_t)n * (size_t)L.mlp.sde;
+}
+
+RF_HD size_t lstm_sde_group_log_std(const LstmLayout &L, size_t g)
+{
+    return g * (size_t)L.total + (size_t)L.mlp.log_std;
+}
+
 // floats of the state [2 nets][2: h, c][n][H]
 RF_HD size_t lstm_state_floats(int n, int H)
 {
@@ -218,6 +230,8 @@ __device__ __forceinline__ void lstm_linear_tile(const float *__restrict__ param
 // are NOT one piece of it, each of the four planes contributes rows [g n, (g + 1) n), so the state is reached as
 // (plane stride `lanes`, environment lane0 + e) and its pointers do not move.  Ungrouped, lanes is n, lane0 the constant
 // 0, gens / consumed / lanes are unused and the code is what it was without them.
+// kSde && kGrouped ("population lstm sde"): P is the lstm-sde layout's total, so group g's log_std is the last L floats of
+// its own piece; theta, env_actions and sigma move with the rows; gens / consumed stay unused (the noise is theta).
 template <bool kSde, bool kLinear = false, bool kGrouped = false>
 __global__ __launch_bounds__(kPolicyThreads) void lstm_forward_kernel(
     LstmLayout L, const float *__restrict__ params, int n, const float *__restrict__ obs,
@@ -228,7 +242,6 @@ __global__ __launch_bounds__(kPolicyThreads) void lstm_forward_kernel(
     float *__restrict__ logits, typename LstmSdeOf<kSde>::type sde, const PolicyGen *__restrict__ gens /* [G] or null */,
     uint64_t consumed, int lanes_all)
 {
-    static_assert(!(kSde && kGrouped), "the lstm-sde head has no population yet");
     const float *__restrict__ theta = sde.theta;
     float *__restrict__ env_actions = sde.env_actions, *__restrict__ sigma = sde.sigma;
     if (kGrouped) { // (block-uniform: every row pointer moves to the group's piece; null stays null; the state stays)
@@ -242,7 +255,11 @@ __global__ __launch_bounds__(kPolicyThreads) void lstm_forward_kernel(
         values = values != nullptr ? values + row : nullptr;
         final_values = final_values != nullptr ? final_values + row : nullptr;
         logits = logits != nullptr ? logits + row * (size_t)L.mlp.n_actions : nullptr;
-        if (sampled)
+        if constexpr (kSde) { // ("population lstm sde": theta [G n][L] and the head's two outputs; nothing is drawn)
+            theta = theta != nullptr ? theta + lstm_sde_group_theta(L, n, g) : nullptr;
+            env_actions = env_actions != nullptr ? env_actions + row : nullptr;
+            sigma = sigma != nullptr ? sigma + row : nullptr;
+        } else if (sampled)
             gen = gens[g];
     }
     const int lanes = kGrouped ? lanes_all : n;                    // the state's plane stride

@@ -147,6 +147,13 @@ RF_HD LstmLanes lstm_group_lanes(int G, int m, int g)
     return LstmLanes{G * m, g * m};
 }
 
+// "population lstm sde": where group g's raw actions begin in the float32 [G N] array of an update, in floats (N the rows
+// of ONE group) -- not the int64 elements of the Categorical head
+RF_HD size_t lstm_sde_group_actions(size_t g, int N)
+{
+    return g * (size_t)N;
+}
+
 // firsts[g] as the kernels take it: clamped into 0 .. N - 1 (a value outside sets the group's skip flag)
 RF_HD int lstm_ppo_first(int raw, int N)
 {
@@ -190,20 +197,22 @@ RF_HD size_t lstm_ppo_state_at(int t, int net, int which, int n, int H, int env,
 }
 
 // "population lstm": what rf_lstm_ppo_grouped_state_size and rf_lstm_ppo_grouped_workspace_size return for a ctx (0:
-// refused): G times the ungrouped sizes, for minibatches of B out of the m T rows of a group
-RF_HD unsigned long long lstm_population_state_bytes(const rf_lstm_critic_desc &d, int G, int m)
+// refused): G times the ungrouped sizes, for minibatches of B out of the m T rows of a group.  sde ("population lstm sde",
+// rf_lstm_sde_grouped_state_size / rf_lstm_sde_grouped_workspace_size): the same over lstm_sde_layout
+RF_HD unsigned long long lstm_population_state_bytes(const rf_lstm_critic_desc &d, int G, int m, bool sde = false)
 {
     LstmLayout L;
-    if (!lstm_layout_nets(d.lstm, L, false, d.critic) || !population_rows(G, m))
+    if (!lstm_layout_nets(d.lstm, L, sde, d.critic) || !population_rows(G, m))
         return 0;
     return (unsigned long long)G * (4ull * kPpoStateHeader + 8ull * L.total);
 }
 
-RF_HD unsigned long long lstm_population_workspace_bytes(const rf_lstm_critic_desc &d, int G, int m, int T, int B)
+RF_HD unsigned long long lstm_population_workspace_bytes(const rf_lstm_critic_desc &d, int G, int m, int T, int B,
+                                                         bool sde = false)
 {
     LstmLayout L;
     LstmPpoWork W;
-    if (!lstm_layout_nets(d.lstm, L, false, d.critic) || m < 1 || T < 1
+    if (!lstm_layout_nets(d.lstm, L, sde, d.critic) || m < 1 || T < 1
         || !population_rows(G, (long long)m * (long long)T) || (long long)B > (long long)m * (long long)T
         || !lstm_ppo_work(L, B, W))
         return 0;
@@ -548,7 +557,6 @@ __global__ __launch_bounds__(kPpoThreads) void lstm_ppo_mlp_kernel(
     const float *__restrict__ advantages, const float *__restrict__ returns, int first, int B,
     const PpoHyper *__restrict__ hypers /* [G] or null */, const int *__restrict__ firsts /* [G] or null */)
 {
-    static_assert(!(kSde && kGrouped), "the lstm-sde head has no population yet");
     int outside = 0; // (kGrouped: firsts[g] was not a row of the group -- the update is skipped and flagged)
     if (kGrouped) {  // (block-uniform)
         const size_t g = blockIdx.z, row = g * (size_t)N;
@@ -557,7 +565,10 @@ __global__ __launch_bounds__(kPpoThreads) void lstm_ppo_mlp_kernel(
         header = reinterpret_cast<const PpoHeader *>(reinterpret_cast<const float *>(header)
                                                      + g * ((size_t)kPpoStateHeader + 2 * (size_t)L.total));
         ws += g * (size_t)W.total;
-        actions_any = static_cast<const int64_t *>(actions_any) + row;
+        if constexpr (kSde) // ("population lstm sde": the raw actions are float32)
+            actions_any = static_cast<const float *>(actions_any) + lstm_sde_group_actions(g, N);
+        else
+            actions_any = static_cast<const int64_t *>(actions_any) + row;
         old_log_probs += row, advantages += row, returns += row;
         const int raw = firsts[g];
         first = lstm_ppo_first(raw, N);
@@ -749,12 +760,11 @@ __global__ __launch_bounds__(kPpoThreads) void lstm_ppo_bptt_kernel(LstmLayout L
 
 // kSde: the threads past both nets sum the log_std gradients (sde_log_std_gradient, which needs params for std2_j)
 // kLinear: "lstm critic" -- the sources of lstm_ppo_source_critic
-// kGrouped: grid (partials, G)
+// kGrouped: grid (partials, G); params moves with the group, so std2_j is read from the group's own log_std
 template <bool kSde, bool kLinear = false, bool kGrouped = false>
 __global__ __launch_bounds__(kPpoThreads) void lstm_ppo_gradient_kernel(LstmLayout L, LstmPpoWork W, float *__restrict__ ws,
                                                                         int B, const float *__restrict__ params)
 {
-    static_assert(!(kSde && kGrouped), "the lstm-sde head has no population yet");
     __shared__ double s_red[kPpoLeaves];
     if (kGrouped) {
         ws += (size_t)blockIdx.y * (size_t)W.total;

@@ -1994,6 +1994,7 @@ from reinfocus_amd.environments.learner import DeviceLearner, Learner, ppo_updat
 from reinfocus_amd.environments.population import DevicePopulationLearner, DevicePopulationPolicy, PopulationLearner, PopulationPolicy  # noqa: E402,F401 -- G learners in lock-step
 from reinfocus_amd.environments.population import DeviceSdePopulationPolicy, SdePopulationPolicy  # noqa: E402,F401 -- G gSDE learners in lock-step
 from reinfocus_amd.environments.population import DevicePopulationLstmPolicy, LstmPopulationPolicy  # noqa: E402,F401 -- G recurrent learners in lock-step
+from reinfocus_amd.environments.population import DevicePopulationLstmSdePolicy, LstmSdePopulationPolicy  # noqa: E402,F401 -- G recurrent gSDE learners in lock-step
 from reinfocus_amd.environments.sde import DeviceSdePolicy, SdePolicy, SdePolicySpec, sde_numpy  # noqa: E402,F401 -- the gSDE actor-critic
 from reinfocus_amd.environments.lstm import DeviceLstmPolicy, LstmPolicy, LstmPolicySpec, lstm_numpy  # noqa: E402,F401 -- the recurrent actor-critic
 from reinfocus_amd.environments.lstm_learner import DeviceLstmLearner, LstmLearner, lstm_gradient_numpy, lstm_update_numpy  # noqa: E402,F401 -- the recurrent PPO minibatch update

@@ -42,7 +42,19 @@ LSTM, either critic kind), as the reference's search runs its ppo_lstm sampler.
     count) and train(rollout, n_epochs, batch_size, splits) as lstm_learner's, with one first row / split per group
     (G lstm_learner.LstmLearner over slice-parts; rf_lstm_ppo_update_grouped, six launches whatever G is)
 
-Out of scope: the lstm-sde head (the next step); groups that differ in architecture, m, T or batch size; more than one action
+The recurrent Gaussian head (include/reinfocus_hip.h, "population lstm sde"): G recurrent gSDE learners over a
+Box(-1, 1, (1,)) action space -- both rules at once, as the reference's ppo_lstm search runs ContinuousJumps-v0: each group
+with its own log_std_init and sde_sample_freq, the state in its single form, float32 raw actions in the update.
+
+    LstmSdePopulationPolicy        the numpy twin: literally G lstm_sde.LstmSdePolicy over lane slices, and the oracle
+    DevicePopulationLstmSdePolicy  reset_noise(groups=mask) / act / values in ONE launch each
+                                   (rf_lstm_sde_noise_reset_grouped, rf_lstm_sde_forward_grouped); spec.kind is the
+                                   lstm_sde kind, so collect() keeps episode_starts and lstm_states and resets the noise
+                                   per group
+    PopulationLearner / DevicePopulationLearner become the recurrent learner over float32 raw actions with them
+    (G lstm_learner.LstmLearner over LstmSdePolicy members; rf_lstm_sde_update_grouped, six launches whatever G is)
+
+Out of scope: groups that differ in architecture, critic kind, m, T or batch size; more than one action
 dimension; SB3Wrapper; and the environment's shared reset-state generator -- lanes that end are
 ranked across all groups, so which reset state a lane draws depends on other groups' episode ends: the independence
 covers what the learner is given the raw step, not the environment's draws.
@@ -55,6 +67,7 @@ import numpy as np
 from reinfocus_amd.environments import learner as learner_module
 from reinfocus_amd.environments import lstm as lstm_module
 from reinfocus_amd.environments import lstm_learner as lstm_learner_module
+from reinfocus_amd.environments import lstm_sde as lstm_sde_module
 from reinfocus_amd.environments import policy as policy_module
 from reinfocus_amd.environments import sde as sde_module
 from reinfocus_amd.environments.learner import MAX_BATCH, STATE_HEADER, f64
@@ -104,8 +117,25 @@ def _checked_lstm_population(spec, groups, seeds):
         raise ValueError(f"a population of recurrent learners has the Categorical head of LstmPolicySpec, not a spec of kind "
                          f"{getattr(spec, 'kind', None)!r}: MlpPolicySpec has PopulationPolicy / DevicePopulationPolicy, "
                          "SdePolicySpec SdePopulationPolicy / DeviceSdePopulationPolicy; the lstm-sde head (LstmSdePolicySpec) "
-                         "in a population is out of scope -- it is the next step")
+                         "in a population is out of scope here -- it is the next step, LstmSdePopulationPolicy / "
+                         "DevicePopulationLstmSdePolicy")
     return _checked_groups(groups, seeds)
+
+
+LSTM_SDE_KIND = lstm_sde_module.LstmSdePolicySpec.kind
+RECURRENT_KINDS = (LSTM_KIND, LSTM_SDE_KIND)
+
+
+def _checked_lstm_sde_population(spec, groups, seeds, log_std_init):
+    """(G, seeds, log_std_init per group) of a population with the Gaussian head on the LSTM."""
+    if getattr(spec, "kind", None) != LSTM_SDE_KIND:
+        raise ValueError(f"a population of recurrent gSDE learners has the Gaussian head of LstmSdePolicySpec, not a spec of "
+                         f"kind {getattr(spec, 'kind', None)!r}: MlpPolicySpec has PopulationPolicy / DevicePopulationPolicy, "
+                         "SdePolicySpec SdePopulationPolicy / DeviceSdePopulationPolicy, LstmPolicySpec LstmPopulationPolicy / "
+                         "DevicePopulationLstmPolicy")
+    groups, seeds = _checked_groups(groups, seeds)
+    inits = per_group(spec.log_std_init if log_std_init is None else log_std_init, groups, "log_std_init")
+    return groups, seeds, np.array([float(x) for x in inits], dtype=f32)
 
 
 def group_parts(parts, groups, g):
@@ -234,6 +264,8 @@ def _refuse_rollout(spec, rollout):
     """A Categorical population refuses a Box rollout, one with the Gaussian head a Discrete one."""
     if spec.kind == sde_module.SdePolicySpec.kind:
         sde_module._refuse_discrete(rollout.env.single_action_space)
+    elif spec.kind == LSTM_SDE_KIND:
+        lstm_sde_module._refuse_discrete(rollout.env.single_action_space)
     elif spec.kind == LSTM_KIND:
         lstm_module._refuse_box(rollout.env.single_action_space)
     else:
@@ -443,18 +475,75 @@ class LstmPopulationPolicy:
         return np.concatenate([part[0] for part in parts]), np.concatenate([part[1] for part in parts])
 
 
+class LstmSdePopulationPolicy:
+    """The numpy twin of DevicePopulationLstmSdePolicy, and its oracle: G lstm_sde.LstmSdePolicy, group g seeded with
+    seeds[g], over slices of the lanes.  `params` is one array [G][P + L]; policies[g].params is its row g.  log_std_init: a
+    scalar or G values, which override the spec's per group.  The state is ONE array [2, 2, n, H] as LstmPopulationPolicy's;
+    num_envs (n = G m; reset_noise(num_envs=) sets it) says how many rows of noise a group draws: m L draws of its own
+    generator per reset."""
+
+    def __init__(self, spec, groups, seeds, log_std_init=None, num_envs=None):
+        self.groups, seeds, inits = _checked_lstm_sde_population(spec, groups, seeds, log_std_init)
+        self.spec = spec
+        self.params = _initial_params(spec, inits)
+        self._state = None
+        self.num_envs = self.groups
+        if num_envs is not None:
+            _per_group(int(num_envs), self.groups)
+            self.num_envs = int(num_envs)
+            self._state = np.zeros(spec.state_shape(num_envs), dtype=f32)
+        self.policies = [lstm_sde_module.LstmSdePolicy(spec, seed, self.num_envs // self.groups) for seed in seeds]
+        for g, member in enumerate(self.policies):
+            member.params = self.params[g]
+
+    _groups_of = PopulationPolicy._groups_of
+    load_state_dict = PopulationPolicy.load_state_dict
+    state_dict = PopulationPolicy.state_dict
+    rng_state = PopulationPolicy.rng_state
+    set_rng_state = PopulationPolicy.set_rng_state
+    _own_state = LstmPopulationPolicy._own_state
+    lstm_state = LstmPopulationPolicy.lstm_state
+    set_lstm_state = LstmPopulationPolicy.set_lstm_state
+    reset_state = LstmPopulationPolicy.reset_state
+    _split = LstmPopulationPolicy._split
+    values = LstmPopulationPolicy.values
+    reset_noise = SdePopulationPolicy.reset_noise
+    noise = SdePopulationPolicy.noise
+    set_noise = SdePopulationPolicy.set_noise
+
+    def act(self, obs, episode_starts, final_obs=None, deterministic=False, states=None):
+        """(actions float32 [n] (raw), values, log_probs, final_values or None, env_actions float32 [n] (clamped)) over all
+        n = G m rows: group g's rows by policies[g] from its columns of the state and its theta.  No draw is consumed.  The
+        state advances as LstmPopulationPolicy.act's does."""
+        n, pieces = self._split(obs, episode_starts, final_obs)
+        if not deterministic:
+            for member, (rows, _, _, _) in zip(self.policies, pieces):  # (before any group's state moves)
+                theta = member.noise()
+                if theta is None or theta.shape[0] != rows.shape[0]:
+                    raise ValueError("a sampled act() needs reset_noise() of every group first")
+        source, target = (self._own_state(n),) * 2 if states is None else states
+        parts = []
+        for member, (rows, starts, final_rows, lanes) in zip(self.policies, pieces):
+            before = np.ascontiguousarray(source[:, :, lanes, :])
+            after = np.empty_like(before)
+            parts.append(member.act(rows, starts, final_rows, deterministic, states=(before, after)))
+            target[:, :, lanes, :] = after
+        return tuple(None if parts[0][i] is None else np.concatenate([part[i] for part in parts]) for i in range(5))
+
+
 class PopulationLearner(_GroupHyper):
     """The numpy twin of DevicePopulationLearner, and its oracle: G learner.Learner, learners[g] over policies[g] and the
     group's rows.  With an LstmPopulationPolicy it is the recurrent learner: G lstm_learner.LstmLearner over slice-parts
-    (group_parts), update(rollout_or_parts, firsts, count) and train(rollout, n_epochs, batch_size, splits, generator)."""
+    (group_parts), update(rollout_or_parts, firsts, count) and train(rollout, n_epochs, batch_size, splits, generator);
+    with an LstmSdePopulationPolicy the same over float32 raw actions (the members' Gaussian head)."""
 
     def __init__(self, policy, learning_rate=3e-4, clip_range=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5,
                  normalize_advantage=True, betas=(0.9, 0.999), adam_eps=1e-5):
-        if not isinstance(policy, (PopulationPolicy, SdePopulationPolicy, LstmPopulationPolicy)):
+        if not isinstance(policy, (PopulationPolicy, SdePopulationPolicy, LstmPopulationPolicy, LstmSdePopulationPolicy)):
             raise TypeError(f"PopulationLearner needs a PopulationPolicy, not {type(policy).__name__} (a "
                             "DevicePopulationPolicy has DevicePopulationLearner)")
         self.policy, self.spec, self.groups = policy, policy.spec, policy.groups
-        self._lstm = self.spec.kind == LSTM_KIND
+        self._lstm = self.spec.kind in RECURRENT_KINDS
         self._configure(learning_rate, clip_range, ent_coef, vf_coef, max_grad_norm, normalize_advantage, betas, adam_eps)
         member_learner = lstm_learner_module.LstmLearner if self._lstm else learner_module.Learner
         self.learners = [member_learner(member) for member in policy.policies]
@@ -850,8 +939,8 @@ class DevicePopulationLstmPolicy:
         self.groups, seeds = _checked_lstm_population(spec, groups, seeds)
         if not hasattr(env.single_action_space, "n"):
             raise ValueError(f"a population of recurrent learners has a Categorical head over a Discrete action space, not "
-                             f"{env.single_action_space!r}: the lstm-sde head in a population is out of scope -- it is the "
-                             "next step")
+                             f"{env.single_action_space!r}: the lstm-sde head in a population is out of scope here -- it is "
+                             "the next step, DevicePopulationLstmSdePolicy")
         if env.single_action_space.n != spec.n_actions:
             raise ValueError(f"the spec has {spec.n_actions} actions, the environment {env.single_action_space.n}")
         self.num_envs = int(env.num_envs)
@@ -934,6 +1023,135 @@ class DevicePopulationLstmPolicy:
         return values if final_obs is None else (values, final_values)
 
 
+class DevicePopulationLstmSdePolicy:
+    """The recurrent sde policies of G groups of m environments each of one device-resident environment with the
+    Box(-1, 1, (1,)) action space (n = G m), over torch tensors on its GPU; used as LstmSdePopulationPolicy is and bit for
+    bit equal to it, group by group equal to a stand-alone lstm_sde.DeviceLstmSdePolicy(seed=seeds[g]) over the group's m
+    environments.  The spec is an LstmSdePolicySpec with either enable_critic_lstm.
+
+    reset_noise(groups=mask), act() and values() are ONE launch each (rf_lstm_sde_noise_reset_grouped, grid
+    (ceil(m L / 256), G); rf_lstm_sde_forward_grouped, grid (ceil(m / 8), nets, G)).  `params` is one float32 tensor
+    [G][P + L], theta one [G m][L], the state one [2, 2, n, H] in DeviceLstmPolicy's form, which act() updates in place.
+    The generators are DeviceSdePopulationPolicy's: a device table of words written at seeding and at set_rng_state only,
+    the draws each has given counted on the host and sent with the selection from pinned memory, stream-ordered.  Nothing
+    waits for the host."""
+
+    _device_env = policy_module.DevicePolicy._device_env
+    _rows = policy_module.DevicePolicy._rows
+    _out = policy_module.DevicePolicy._out
+
+    def __init__(self, env, spec, groups, seeds, log_std_init=None):
+        self._device_env(env)
+        lstm_sde_module._refuse_discrete(env.single_action_space)
+        self.groups, seeds, inits = _checked_lstm_sde_population(spec, groups, seeds, log_std_init)
+        self.num_envs = int(env.num_envs)
+        self.per_group = _per_group(self.num_envs, self.groups)
+        self._io = env._tensor_io()  # (ValueError, as step_tensors': a host initializer, a render_mode)
+        from reinfocus_amd import torch_interop
+
+        self._interop = torch_interop
+        torch = self._torch = torch_interop._torch()
+        self.spec = spec
+        self._ctx = env._ctx
+        self.device = torch.device("cuda", self._ctx.device)
+        self.params = torch.zeros((self.groups, spec.size), dtype=torch.float32, device=self.device)
+        self.params.copy_(torch.from_numpy(_initial_params(spec, inits)))
+        self._owned = {}
+        self._table = torch.zeros((self.groups, 4), dtype=torch.int64, device=self.device)  # (the bits of uint64 words)
+        self._theta = torch.zeros((self.num_envs, spec.latent), dtype=torch.float32, device=self.device)
+        self._state = torch.zeros(spec.state_shape(self.num_envs), dtype=torch.float32, device=self.device)
+        self._has_noise = np.zeros(self.groups, dtype=bool)
+        # what a reset reads on the device: uint64 [G] draws given, then uint8 [G] selected
+        self._schedule = torch.zeros(9 * self.groups, dtype=torch.uint8, device=self.device)
+        self._set_generators([np.random.PCG64DXSM(seed) for seed in seeds])
+
+    _set_generators = DeviceSdePopulationPolicy._set_generators
+    rng_state = DeviceSdePopulationPolicy.rng_state
+    set_rng_state = DevicePopulationPolicy.set_rng_state
+    _groups_of = PopulationPolicy._groups_of
+    load_state_dict = DevicePopulationPolicy.load_state_dict
+    state_dict = DevicePopulationPolicy.state_dict
+    _all_rows = DevicePopulationPolicy._all_rows
+    _checked_state = lstm_module.DeviceLstmPolicy._checked_state
+    lstm_state = lstm_module.DeviceLstmPolicy.lstm_state
+    set_lstm_state = lstm_module.DeviceLstmPolicy.set_lstm_state
+    reset_state = lstm_module.DeviceLstmPolicy.reset_state
+    _starts = lstm_module.DeviceLstmPolicy._starts
+    noise = DeviceSdePopulationPolicy.noise
+    set_noise = DeviceSdePopulationPolicy.set_noise
+
+    def reset_noise(self, groups=None, num_envs=None):
+        """DeviceSdePopulationPolicy.reset_noise over this layout's log_std: ONE launch, and m L draws of each selected
+        group's generator.  An unselected group keeps its rows of theta and its generator state."""
+        torch = self._torch
+        mask = group_mask(groups, self.groups)
+        if num_envs is not None and int(num_envs) != self.num_envs:
+            raise ValueError(f"num_envs {num_envs} is not the environment's {self.num_envs}")
+        self._interop.check_one_runtime()
+        G = self.groups
+        packed = np.empty(9 * G, dtype=np.uint8)
+        packed[:8 * G] = self._consumed.view(np.uint8)
+        packed[8 * G:] = mask
+        # (a pinned buffer of its own per call: the copy is stream-ordered, and resets enqueued before keep what they read)
+        self._schedule.copy_(torch.from_numpy(packed).pin_memory(), non_blocking=True)
+        at = self._schedule.data_ptr()
+        self._ctx.lstm_sde_noise_reset_grouped(self.spec.critic_desc(), G, self.per_group, self.params.data_ptr(),
+                                               self._table.data_ptr(), at, None if groups is None else at + 8 * G,
+                                               self._theta.data_ptr(), self._io._stream())
+        self._consumed[mask] += np.uint64(self.per_group * self.spec.latent)  # (after the call was taken)
+        self._has_noise |= mask
+
+    def _forward(self, obs, episode_starts, final_obs, state_in, state_out, theta, flags, actions, env_actions, log_probs,
+                 values, final_values):
+        self._interop.check_one_runtime()
+        pointer = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        self._ctx.lstm_sde_forward_grouped(self.spec.critic_desc(), self.groups, self.per_group, self.params.data_ptr(),
+                                           obs.data_ptr(), episode_starts.data_ptr(), pointer(final_obs), state_in.data_ptr(),
+                                           pointer(state_out), pointer(theta), flags, pointer(actions), pointer(env_actions),
+                                           pointer(log_probs), pointer(values), pointer(final_values), None, None,
+                                           self._io._stream())
+
+    def act(self, obs, episode_starts, final_obs=None, deterministic=False, out=None, states=None):
+        """DeviceLstmSdePolicy.act over all n = G m rows, group g's rows with params[g], its rows of theta and its columns
+        of the state.  The own state advances in place; with states=(in, out) the call goes from `in` to `out` instead and
+        the own state stays.  One launch; no draw is consumed."""
+        torch = self._torch
+        obs = self._all_rows(obs, final_obs)
+        n = self.num_envs
+        episode_starts = self._starts(episode_starts, n)
+        if not deterministic and not self._has_noise.all():
+            raise ValueError("a sampled act() needs reset_noise() of every group first")
+        if states is None:
+            state_in = state_out = self._state
+        else:
+            state_in, state_out = states
+            state_in, state_out = self._checked_state(state_in, "states[0]"), self._checked_state(state_out, "states[1]")
+        given = (None,) * 5 if out is None else tuple(out)
+        if len(given) != 5:
+            raise TypeError("out must be (actions, values, log_probs, final_values or None, env_actions)")
+        actions = self._out("raw_actions", given[0], n, torch.float32)
+        values = self._out("values", given[1], n, torch.float32)
+        log_probs = self._out("log_probs", given[2], n, torch.float32)
+        final_values = None if final_obs is None else self._out("final_values", given[3], n, torch.float32)
+        env_actions = self._out("env_actions", given[4], n, torch.float32)
+        self._forward(obs, episode_starts, final_obs, state_in, state_out, None if deterministic else self._theta,
+                      DETERMINISTIC if deterministic else 0, actions, env_actions, log_probs, values, final_values)
+        return actions, values, log_probs, final_values, env_actions
+
+    def values(self, obs, episode_starts, final_obs=None, out=None):
+        """DeviceLstmSdePolicy.values over all n rows.  One launch, no draw; the state stays."""
+        torch = self._torch
+        obs = self._all_rows(obs, final_obs)
+        episode_starts = self._starts(episode_starts, self.num_envs)
+        given = (None, None) if out is None else tuple(out)
+        if len(given) != 2:
+            raise TypeError("out must be (values, final_values or None)")
+        values = self._out("last_values", given[0], self.num_envs, torch.float32)
+        final_values = None if final_obs is None else self._out("final_values", given[1], self.num_envs, torch.float32)
+        self._forward(obs, episode_starts, final_obs, self._state, None, None, 0, None, None, None, values, final_values)
+        return values if final_obs is None else (values, final_values)
+
+
 class DevicePopulationLearner(_GroupHyper):
     """The learners of a DevicePopulationPolicy or a DeviceSdePopulationPolicy, over torch tensors on its GPU; used as
     PopulationLearner is and bit for bit equal to it.  update() is rf_ppo_update_grouped (rf_sde_update_grouped with the
@@ -944,30 +1162,34 @@ class DevicePopulationLearner(_GroupHyper):
 
     With a DevicePopulationLstmPolicy it is the recurrent learner: update(rollout_or_parts, firsts, count) and
     train(rollout, n_epochs, batch_size, splits, generator) as PopulationLearner's, rf_lstm_ppo_update_grouped -- six
-    launches whatever G is.  The G first rows of every update are computed on the host and uploaded as one int32 table
+    launches whatever G is; with a DevicePopulationLstmSdePolicy the same over float32 raw actions and P + L parameters
+    (rf_lstm_sde_update_grouped).  The G first rows of every update are computed on the host and uploaded as one int32 table
     [updates][G] from pinned memory, stream-ordered."""
 
     def __init__(self, policy, learning_rate=3e-4, clip_range=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5,
                  normalize_advantage=True, betas=(0.9, 0.999), adam_eps=1e-5):
-        if not isinstance(policy, (DevicePopulationPolicy, DeviceSdePopulationPolicy, DevicePopulationLstmPolicy)):
+        if not isinstance(policy, (DevicePopulationPolicy, DeviceSdePopulationPolicy, DevicePopulationLstmPolicy,
+                                   DevicePopulationLstmSdePolicy)):
             raise TypeError(f"DevicePopulationLearner needs a DevicePopulationPolicy, not {type(policy).__name__} (a "
                             "PopulationPolicy has PopulationLearner, a DevicePolicy DeviceLearner)")
         self.policy, self.spec, self.groups = policy, policy.spec, policy.groups
         self._sde = self.spec.kind == sde_module.SdePolicySpec.kind
-        self._lstm = self.spec.kind == LSTM_KIND
+        self._lstm = self.spec.kind in RECURRENT_KINDS
+        self._gaussian = self.spec.kind == LSTM_SDE_KIND  # (the recurrent learner over float32 raw actions)
         self._configure(learning_rate, clip_range, ent_coef, vf_coef, max_grad_norm, normalize_advantage, betas, adam_eps)
         self._torch, self._interop, self._io, self._ctx = policy._torch, policy._interop, policy._io, policy._ctx
         self.device = policy.device
         torch = self._torch
         self._state_floats = STATE_HEADER + 2 * self.spec.size
         if self._lstm:
-            state_bytes = self._ctx.lstm_ppo_grouped_state_size(self.spec.critic_desc(), self.groups, policy.per_group)
+            state_size = self._ctx.lstm_sde_grouped_state_size if self._gaussian else self._ctx.lstm_ppo_grouped_state_size
+            state_bytes = state_size(self.spec.critic_desc(), self.groups, policy.per_group)
         else:
             state_size = self._ctx.sde_grouped_state_size if self._sde else self._ctx.ppo_grouped_state_size
             state_bytes = state_size(self.spec.desc(), self.groups, policy.per_group)
         if state_bytes != 4 * self.groups * self._state_floats:
-            raise RuntimeError("rf_ppo_grouped_state_size / rf_sde_grouped_state_size / rf_lstm_ppo_grouped_state_size "
-                               "disagrees with the packed optimizer states")
+            raise RuntimeError("rf_ppo_grouped_state_size / rf_sde_grouped_state_size / rf_lstm_ppo_grouped_state_size / "
+                               "rf_lstm_sde_grouped_state_size disagrees with the packed optimizer states")
         self.state = torch.zeros((self.groups, self._state_floats), dtype=torch.float32, device=self.device)
         self._workspace, self._workspace_key = None, None
         self._stats = None
@@ -1021,8 +1243,9 @@ class DevicePopulationLearner(_GroupHyper):
         key = (steps, batch)
         if key != self._workspace_key:
             if self._lstm:
-                size = self._ctx.lstm_ppo_grouped_workspace_size(self.spec.critic_desc(), self.groups, self.policy.per_group,
-                                                                 steps, batch)
+                workspace_size = self._ctx.lstm_sde_grouped_workspace_size if self._gaussian \
+                    else self._ctx.lstm_ppo_grouped_workspace_size
+                size = workspace_size(self.spec.critic_desc(), self.groups, self.policy.per_group, steps, batch)
             else:
                 workspace_size = self._ctx.sde_grouped_workspace_size if self._sde else self._ctx.ppo_grouped_workspace_size
                 size = workspace_size(self.spec.desc(), self.groups, self.policy.per_group, steps, batch)
@@ -1053,7 +1276,8 @@ class DevicePopulationLearner(_GroupHyper):
             raise ValueError(f"the parts have n_steps {steps} and num_envs {lanes}; the population has "
                              f"{self.policy.num_envs} environments")
         total, hidden = steps * lanes, self.spec.lstm_hidden
-        wanted = {"observations": (torch.float32, (total, self.spec.obs_width)), "actions": (torch.int64, (total,)),
+        wanted = {"observations": (torch.float32, (total, self.spec.obs_width)),
+                  "actions": (torch.float32 if self._gaussian else torch.int64, (total,)),
                   "log_probs": (torch.float32, (total,)), "advantages": (torch.float32, (total,)),
                   "returns": (torch.float32, (total,)), "episode_starts": (torch.uint8, (steps + 1, lanes)),
                   "lstm_states": (torch.float32, (steps + 1, 2, 2, lanes, hidden))}
@@ -1074,7 +1298,8 @@ class DevicePopulationLearner(_GroupHyper):
         return torch.empty(host.shape, dtype=torch.int32, device=self.device).copy_(host, non_blocking=True)
 
     def _enqueue_recurrent(self, parts, steps, firsts, count, stats, hyper):
-        self._ctx.lstm_ppo_update_grouped(
+        update = self._ctx.lstm_sde_update_grouped if self._gaussian else self._ctx.lstm_ppo_update_grouped
+        update(
             self.spec.critic_desc(), self.groups, self.policy.per_group, steps, hyper.data_ptr(),
             self.policy.params.data_ptr(), self.state.data_ptr(), self._workspace.data_ptr(),
             parts["observations"].data_ptr(), parts["actions"].data_ptr(), parts["log_probs"].data_ptr(),

@@ -22,7 +22,10 @@ device a step is then one policy launch, which writes rows of the slabs, and the
 With a recurrent policy of environments/lstm.py (LstmPolicy, DeviceLstmPolicy) or, over the Box space, of
 environments/lstm_sde.py (LstmSdePolicy, DeviceLstmSdePolicy: both rules at once) collect() also keeps what sb3-contrib's
 RecurrentRolloutBuffer hands to the update -- episode_starts uint8 [T + 1, n] and lstm_states float32
-[T + 1, 2, 2, n, H], made on first use with such a policy --; flat() and minibatches() are unchanged.
+[T + 1, 2, 2, n, H], made on first use with such a policy --; flat() and minibatches() are unchanged.  The populations of
+environments/population.py are taken the same way, by their spec's kind and their `groups`: one with a Gaussian head
+(SdePopulationPolicy, LstmSdePopulationPolicy and their device classes) has sde_sample_freq as a scalar or G values and
+one masked reset per step, a recurrent one (LstmPopulationPolicy, LstmSdePopulationPolicy) keeps the two slabs.
 
 torch is imported lazily, by DeviceRollout only (reinfocus_amd/torch_interop.py says why import order matters).
 """
