@@ -1543,6 +1543,86 @@ int /* population lstm sde */ rf_lstm_sde_update_grouped(rf_ctx *ctx, const rf_l
         const float *d_returns, const uint8_t *d_episode_starts, const float *d_lstm_states,
         const int *d_firsts /* [G] */, int B, float *d_stats, void *caller_stream);
 
+/* ---- parameter init: the packed parameters of G learners initialised on the device, as SB3 does ------------------------------
+ * Every policy class starts with its parameters at zero, from which no net learns anything but its head biases: hidden
+ * activations are 0, so every head weight's gradient is 0, so every delta handed back is 0.  The reference's tuned
+ * configurations and every trial of its search use ortho_init=False (PyTorch's default initialisation); its untuned ones
+ * leave SB3's ortho_init=True (orthogonal MLPs and heads with gains sqrt 2 / 0.01 / 1 and zero biases; the LSTMs and the
+ * linear critic keep PyTorch's default).  Head-agnostic: the caller describes ONE group's packed array of `stride` floats
+ * as at most RF_PARAM_MAX_SEGMENTS segments; what a segment means to a network is the caller's business
+ * (environments/param_init.py builds the tables of the five specs).  numpy twin environments/param_init.py init_numpy,
+ * kernels param_fill_kernel and param_orthogonal_kernel (csrc/rf_param_init.h), host build tests/paraminitcheck.
+ *
+ *  I1 Segments.  rf_param_segment {at, out, in, scheme, scale}: `at` the offset in floats, 1 <= out, in <=
+ *     RF_POLICY_MAX_WIDTH; the segment covers the out * in floats from `at`.  Segments must not overlap and must lie inside
+ *     the stride; they need not cover it, and a position outside every segment is not written.  A weight is packed as
+ *     everywhere here, transposed: W^T[k][j] at at + k out + j, k < in, j < out.  A vector (a bias, log_std) has in = 1.
+ *     Only RF_INIT_ORTHOGONAL reads out and in as a shape: the other schemes depend on the position alone, so for them a
+ *     segment is a run of out * in floats however it is cut.  That is how the length of an LSTM's arrays is carried, whose
+ *     4 H rows do not fit the width limit: W_ih^T [D][4H], W_hh^T [H][4H], b_ih and b_hh are packed one after the other
+ *     and share one scale, so they are one run of 4 (D + H + 2) rows of H floats, passed as segments of out = H and
+ *     in <= RF_POLICY_MAX_WIDTH rows each.  One draw per packed position either way (I2).
+ *  I2 Draws.  Group g draws from numpy's Generator(PCG64DXSM(seed_g)), whose four words the caller passes (d_gens[g]: state
+ *     low, state high, inc low, inc high).  Packed position i uses draw number i, u_i = the i-th random() after that state
+ *     (the jump-ahead of "policy"), so no result depends on the launch shape; a position whose scheme needs no draw leaves
+ *     its draw unused.
+ *  I3 RF_INIT_ZERO: 0.0f.  RF_INIT_CONSTANT: d_constants[g], one float per group and call (log_std takes each group's
+ *     log_std_init this way).
+ *  I4 RF_INIT_UNIFORM: float32((2.0 * u_i - 1.0) * scale) in float64 -- one multiply, one subtract, one multiply, one
+ *     rounding.  scale is computed once on the host as 1.0 / sqrt(float64(fan)), with PyTorch's fans: an nn.Linear(in, out)
+ *     weight AND bias fan = in; every array of an nn.LSTM(D, H) fan = H; the linear critic nn.Linear(D, H) fan = D.
+ *  I5 RF_INIT_ORTHOGONAL (scale = the gain): torch.nn.init.orthogonal_'s result -- the Q of the sign-fixed QR (positive
+ *     diagonal of R, hence the same Haar distribution) -- by Gram-Schmidt in a fixed float64 order, rounded once.  t = max(out, in),
+ *     s = min(out, in), A[a][b] = normal32(u_(at + a s + b)) for a < t, b < s (normal32 of "sde policy").  For b = 0 .. s - 1
+ *     start from v[a] = float64(A[a][b]) and do the projection step TWICE (CGS2), every operation a float64 one: for every p < b, c_p = the sum over a ascending,
+ *     from +0, of q_p[a] * v[a] (multiply, then add; every c_p from the same v); then for p ascending v[a] = v[a] -
+ *     c_p * q_p[a].  After both passes n2 = the same chain over v[a] * v[a], and q_b[a] = v[a] / sqrt(n2), kept as float64; the column is
+ *     all zeros where !(n2 > 0).  Packed result, with g = float32(scale) and q rounded to float32 (one float32 multiply):
+ *        out >= in (t = out, orthonormal columns of W):  W^T[k][j] = g * q_k[j]   (vector k < in, component j < out)
+ *        out <  in (t = in, orthonormal rows of W):      W^T[k][j] = g * q_j[k]   (vector j < out, component k < in)
+ *     -- torch draws [out][in], transposes it where out < in, takes Q [t][s] and transposes back.  No FMA contraction; the
+ *     float64 divide and sqrt are correctly rounded.
+ *  I6 Groups.  d_params is float32 [G][stride]; the same table serves every group; d_select (uint8 [G] or NULL: every
+ *     group) says which groups are written -- a group whose byte is 0 keeps every byte.  G = 1 is the ungrouped case.
+ *     (Float32 chains, which an earlier draft of this definition had, are as good as LAPACK's float32 QR but miss the
+ *     orthogonality of a float64 QR rounded once by a factor of 40 to 90 from 64 x 64 on: profiles/param_init.md.)
+ *  I7 Workspace.  The orthogonal kernel keeps each finished vector as float64, twice, by vector and by component, so that
+ *     both of its passes read consecutive doubles across threads; the destination is written once, at the end.
+ *     rf_params_init_workspace_size: 16 G (the sum of out * in over the orthogonal segments) bytes; d_workspace is
+ *     aligned to 8 bytes.
+ * Deliberate differences from SB3: the project's generator and normal32 in place of torch's global RNG, CGS2 in
+ * a fixed order in place of LAPACK's QR, one seed per group, draws indexed by position.
+ * Limits: count 0 .. RF_PARAM_MAX_SEGMENTS, G 1 .. RF_POPULATION_MAX_GROUPS, stride 1 .. 2^30 and G stride <= 2^31.
+ *
+ *   rf_params_init_workspace_size  bytes of the workspace of rf_params_init (0 without orthogonal segments); 0 as well for a
+ *                                  table rf_params_init refuses, G outside its limits or a NULL ctx
+ *   rf_params_init                 two launches on caller_stream (one without orthogonal segments): param_fill_kernel, grid
+ *                                  (ceil(stride / 256), G), then param_orthogonal_kernel, grid (orthogonal segments, G).
+ *                                  Nothing is allocated, nothing waited for.  Refused with a message: more than
+ *                                  RF_PARAM_MAX_SEGMENTS segments; out or in outside the limits; a segment out of range or
+ *                                  overlapping another; an unknown scheme; a scale of a UNIFORM / ORTHOGONAL segment that is
+ *                                  not finite and positive; a CONSTANT segment without d_constants; orthogonal segments
+ *                                  without d_workspace; G or stride outside the limits; an array that is not device memory
+ *                                  of the context's GPU, too small, misaligned or overlapping d_params; a capturing stream.
+ * A refused call returns RF_ERR_INVALID, enqueues nothing and dereferences no device pointer. */
+#define RF_PARAM_MAX_SEGMENTS 32
+#define RF_INIT_ZERO 0
+#define RF_INIT_CONSTANT 1
+#define RF_INIT_UNIFORM 2
+#define RF_INIT_ORTHOGONAL 3
+
+typedef struct rf_param_segment {
+    unsigned at;  /* offset in floats inside a group's piece */
+    int out, in;  /* 1 .. RF_POLICY_MAX_WIDTH each; the segment covers out * in floats */
+    int scheme;   /* RF_INIT_* */
+    double scale; /* UNIFORM: 1 / sqrt(fan); ORTHOGONAL: the gain; unused otherwise */
+} rf_param_segment;
+
+unsigned long long rf_params_init_workspace_size(rf_ctx *ctx, const rf_param_segment *segments, int count, int groups);
+int rf_params_init(rf_ctx *ctx, const rf_param_segment *segments, int count, int groups, unsigned stride, float *d_params,
+        const unsigned long long *d_gens /* [G][4] */, const unsigned char *d_select /* [G] or NULL */,
+        const float *d_constants /* [G] or NULL */, void *d_workspace, void *caller_stream);
+
 #ifdef __cplusplus
 }
 #endif

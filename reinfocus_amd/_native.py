@@ -152,6 +152,8 @@ SYMBOLS = (
     "rf_lstm_sde_grouped_state_size",
     "rf_lstm_sde_grouped_workspace_size",
     "rf_lstm_sde_update_grouped",
+    "rf_params_init_workspace_size",
+    "rf_params_init",
     "rf_render_kernel_name",
     "rf_pixels_rendered",
     "rf_allocations_poisoned",
@@ -488,6 +490,9 @@ def load():
     lib.rf_lstm_sde_grouped_workspace_size.argtypes = [vp, vp, i32, i32, i32, i32]
     lib.rf_lstm_sde_update_grouped.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp,
                                                vp]
+    lib.rf_params_init_workspace_size.restype = ctypes.c_ulonglong
+    lib.rf_params_init_workspace_size.argtypes = [vp, vp, i32, i32]
+    lib.rf_params_init.argtypes = [vp, vp, i32, i32, ctypes.c_uint, vp, vp, vp, vp, vp, vp]
     lib.rf_render_kernel_name.restype = ctypes.c_char_p
     lib.rf_render_kernel_name.argtypes = [vp]
     lib.rf_pixels_rendered.restype = ctypes.c_ulonglong
@@ -1028,6 +1033,21 @@ class Context:
                                                   hyper_ptr, params_ptr, state_ptr, workspace_ptr, observations_ptr,
                                                   actions_ptr, log_probs_ptr, advantages_ptr, returns_ptr, episode_starts_ptr,
                                                   lstm_states_ptr, firsts_ptr, batch, stats_ptr, stream)
+        if rc != 0:
+            _check(rc)
+
+    # --- parameter init (rf_params_init*): `segments` is a ctypes array of rf_param_segment (environments/param_init.py) --
+    def params_init_workspace_size(self, segments, count, groups):
+        """rf_params_init_workspace_size: bytes of the workspace of params_init (0 without orthogonal segments or if refused)."""
+        return int(self._lib.rf_params_init_workspace_size(self._h, segments, count, groups))
+
+    def params_init(self, segments, count, groups, stride, params_ptr, gens_ptr, select_ptr, constants_ptr, workspace_ptr,
+                    stream):
+        """rf_params_init: the packed parameters float32 [groups][stride] initialised from the table, two launches on
+        `stream`; gens_ptr device uint64 [groups][4], select_ptr uint8 [groups] or None, constants_ptr float32 [groups] or
+        None.  Only enqueues."""
+        rc = self._lib.rf_params_init(self._h, segments, count, groups, stride, params_ptr, gens_ptr, select_ptr,
+                                      constants_ptr, workspace_ptr, stream)
         if rc != 0:
             _check(rc)
 

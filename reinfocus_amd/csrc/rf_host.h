@@ -21,6 +21,9 @@
 //   rf_abi_lstm_sde_grouped.hip  "population lstm sde": rf_lstm_sde_noise_reset_grouped, rf_lstm_sde_forward_grouped,
 //                       rf_lstm_sde_update_grouped and their size functions -- the kSde && kGrouped instantiations, compiled
 //                       apart from both units above (profiles/population_lstm_sde.md)
+//   rf_abi_param_init.hip  "parameter init": rf_params_init and rf_params_init_workspace_size -- param_fill_kernel and
+//                       param_orthogonal_kernel (rf_param_init.h), compiled apart from every unit above
+//                       (profiles/param_init.md)
 //
 // Every kernel instantiation is defined in the unit that launches it (ppo_adam_kernel<true>, the last launch of the three
 // grouped updates, in three: each has its own copy; sde_noise_kernel<true> in two); the units share only host functions.
@@ -318,7 +321,7 @@ inline hipError_t host_malloc(void **p, size_t bytes)
     return e;
 }
 
-// ---- what the entry points over caller-owned device arrays share (rf_abi_env.hip and the two grouped recurrent units) ------
+// ---- what the entry points over caller-owned device arrays share (rf_abi_env.hip, the two grouped recurrent units and rf_abi_param_init.hip) ------
 // check_device_array asks the runtime about one array (rf_abi_snapshot.hip and the device steps use it alone),
 // refuse_capturing about the caller's stream, ranges_overlap compares two address ranges; check_device_arrays is the
 // learner entry points' whole rule -- which arrays may alias and what a refusal says -- over the tables each of them keeps.

@@ -224,6 +224,8 @@ class LstmPolicy(policy_module._Draws):
         self._state = None if num_envs is None else np.zeros(spec.state_shape(num_envs), dtype=f32)
         self._seed(seed)
 
+    init_parameters = policy_module.Policy.init_parameters
+
     def load_state_dict(self, state_dict):
         self.params = self.spec.pack(state_dict)
 

@@ -312,6 +312,14 @@ class Policy(_Draws):
     def state_dict(self):
         return self.spec.unpack(self.params)
 
+    def init_parameters(self, seed, ortho_init=True):
+        """The parameters as stable-baselines3 initialises them (environments/param_init.py): ortho_init=True is SB3's
+        default, False PyTorch's default initialisation, which the reference's tuned configurations use.  The generator
+        is the initialiser's own, made from `seed` for this call: the action generator and rng_state() are untouched."""
+        from reinfocus_amd.environments import param_init
+
+        param_init.init_twin(self.params.reshape(1, -1), self.spec, [seed], ortho_init)
+
     def act(self, obs, final_obs=None, deterministic=False):
         """(actions int64 [n], values, log_probs, final_values or None)."""
         obs = np.asarray(obs, dtype=f32).reshape(-1, self.spec.obs_width)
@@ -376,6 +384,13 @@ class DevicePolicy(_Draws):
                 tensor = state_dict[name].detach()
                 cells = tensor.numel()
                 self.params[at:at + cells].view(shape).copy_(tensor.t() if is_weight else tensor)
+
+    def init_parameters(self, seed, ortho_init=True):
+        """Policy.init_parameters on the device and bit for bit equal to it: rf_params_init, two launches on torch's
+        current stream into `params` in place (one where nothing is orthogonal); nothing waits for the host."""
+        from reinfocus_amd.environments import param_init
+
+        param_init.init_device(self, self.params, [seed], ortho_init)
 
     def state_dict(self):
         """Device tensors in SB3's names and shapes (copies)."""

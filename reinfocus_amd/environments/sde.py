@@ -222,6 +222,8 @@ class SdePolicy(policy_module._Draws):
         self._theta = None
         self._seed(seed)
 
+    init_parameters = policy_module.Policy.init_parameters
+
     def load_state_dict(self, state_dict):
         self.params = self.spec.pack(state_dict)
 
