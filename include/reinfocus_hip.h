@@ -1623,6 +1623,70 @@ int rf_params_init(rf_ctx *ctx, const rf_param_segment *segments, int count, int
         const unsigned long long *d_gens /* [G][4] */, const unsigned char *d_select /* [G] or NULL */,
         const float *d_constants /* [G] or NULL */, void *d_workspace, void *caller_stream);
 
+/* ---- evaluation: per-group scores of a population on the device, the best parameters kept -----------------------------------
+ * What the reference's hyper-parameter search optimises is each trial's evaluation score: stable-baselines3's
+ * evaluate_policy on a separate evaluation environment -- deterministic actions, a frozen VecNormalize synced from the
+ * training environment, raw rewards, a fixed number of episodes --, and the best model so far is kept.  This section is that
+ * measurement for G groups of m lanes (n = G m; G = 1 is the ungrouped case) from the episode records a step writes
+ * ("episode records": final_return float64 [n], final_length int32 [n], NaN / 0 where no episode ended).  numpy twin
+ * environments/evaluation.py, kernels csrc/rf_eval.h, host build tests/evalcheck.
+ *
+ *  E1 Targets.  Group g owns lanes [g m, (g + 1) m).  The lane with local index i keeps its first target(i) = (E + i) / m
+ *     episodes (integer division; SB3's episode_count_targets): the targets of a group sum to E.  K = ceil(E / m) is the slot
+ *     count per lane.  Tables: counts int32 [n], returns float64 [n][K], lengths int32 [n][K]; the caller zeroes counts
+ *     before a run, slots at or above a lane's count hold nothing.
+ *  E2 Accumulation, per step and lane: if final_length > 0 and count < target then returns[lane][count] = final_return,
+ *     lengths[lane][count] = final_length, count += 1.  A NaN return is a value and is kept with its bits; a lane at its
+ *     target is ignored.
+ *  E3 Positions.  The kept values of a group have fixed positions, lane-major and slot-minor: position(i, k) = the sum of
+ *     target(j) over j < i, plus k.  Deliberately not SB3's order in time: the same set, summed in another order.
+ *  E4 Sums.  treesum of "learner view" over the E positions: float64, padded with +0.0 to a power of two, adjacent pairs
+ *     added until one value is left, that value + (+0.0).  No FMA contraction.
+ *  E5 Result, float64 [G][8] per group: 0 mean return = treesum(x) / E; 1 population standard deviation =
+ *     sqrt(treesum((x - mean)^2) / E), two passes as numpy.std; 2 minimum and 3 maximum return, NaN if any kept return is
+ *     NaN, otherwise by the total order in which -0.0 is below +0.0; 4 mean length = treesum(lengths) / E; 5 episodes kept;
+ *     6 flags; 7 the serial of this evaluation (the caller's number).  A NaN in columns 0 .. 4 is the quiet NaN
+ *     0x7ff8000000000000 whatever sign the arithmetic gave it.  A group that has not reached all its targets gets
+ *     RF_EVAL_INCOMPLETE in column 6, NaN in columns 0 .. 4 and its true count in column 5.
+ *  E6 Best rule.  best_mean float64 [G] starts at -inf (the caller fills it), best_serial int64 [G].  A group improves iff it
+ *     is complete and mean > best_mean[g] -- strict, so a tie and a NaN never improve --; then improved[g] = 1 and
+ *     best_mean[g], best_serial[g] take the mean (as computed, before E5's canonical NaN, which it cannot be) and the serial;
+ *     otherwise improved[g] = 0 and both stay.
+ * Deliberate differences from SB3: E3 / E4 in place of numpy.mean over the time-ordered list; a fixed number of
+ * steps in place of looping until every lane is done (the caller's bound; a group that is not done is flagged).
+ * Limits: E 1 .. RF_EVAL_MAX_EPISODES, G 1 .. RF_POPULATION_MAX_GROUPS, m >= 1, n = G m, n K <= 2^31.
+ *
+ *   rf_eval_accumulate   E2: eval_accumulate_kernel, one thread per lane, no atomics.
+ *   rf_eval_finish       E3 .. E6: eval_finish_kernel, one block of 256 threads per group; one thread writes the row.
+ *   rf_eval_keep_rows    d_dst row g := d_src row g for the groups with d_select[g] != 0; rows of `words` 4-byte words,
+ *                        `stride` words apart (1 <= words <= stride, G stride <= 2^31).  eval_keep_rows_kernel, grid
+ *                        (ceil(words / 1024), G): 16-byte vectors with dword head and tail where d_src and d_dst are
+ *                        congruent mod 16 bytes, dwords otherwise.  With `improved` as the selection it keeps the best
+ *                        parameters and normaliser statistics; with a mask and the arrays exchanged it restores them.
+ *   rf_env_view_get_statistics_device / rf_env_view_set_statistics_device
+ *                        the running moments of the context's learner view to / from caller-owned device memory: float64
+ *                        [G][3][W + 1] (mean, var, count; the returns last) of a grouped view, [3][W + 1] of an ungrouped
+ *                        one.  One launch on the context's stream, ordered after what caller_stream holds, and caller_stream
+ *                        waits for it: what sync_envs_normalization needs without crossing to the host.  The context must
+ *                        be able to take device steps (rf_env_configure_initializer).
+ * All five only enqueue on (or order against) caller_stream, allocate nothing and wait for nothing.  Every device array is
+ * checked as the learner entry points' are (device memory of the context's GPU, aligned, large enough, outputs apart from
+ * inputs and from each other); a capturing stream is refused.  A refused call returns RF_ERR_INVALID with a message,
+ * enqueues nothing and dereferences no device pointer. */
+#define RF_EVAL_MAX_EPISODES 65536
+#define RF_EVAL_INCOMPLETE 1
+
+int rf_eval_accumulate(rf_ctx *ctx, int n, int groups, int m, int episodes, const double *d_final_return,
+        const int *d_final_length, int *d_counts, double *d_returns /* [n][K] */, int *d_lengths /* [n][K] */,
+        void *caller_stream);
+int rf_eval_finish(rf_ctx *ctx, int n, int groups, int m, int episodes, unsigned long long serial, const int *d_counts,
+        const double *d_returns, const int *d_lengths, double *d_results /* [G][8] */, double *d_best_mean /* [G] */,
+        long long *d_best_serial /* [G] */, unsigned char *d_improved /* [G] */, void *caller_stream);
+int rf_eval_keep_rows(rf_ctx *ctx, int groups, unsigned words, unsigned stride, const unsigned char *d_select /* [G] */,
+        const void *d_src, void *d_dst, void *caller_stream);
+int rf_env_view_get_statistics_device(rf_ctx *ctx, double *d_out, void *caller_stream);
+int rf_env_view_set_statistics_device(rf_ctx *ctx, const double *d_in, void *caller_stream);
+
 #ifdef __cplusplus
 }
 #endif

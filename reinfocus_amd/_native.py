@@ -154,6 +154,11 @@ SYMBOLS = (
     "rf_lstm_sde_update_grouped",
     "rf_params_init_workspace_size",
     "rf_params_init",
+    "rf_eval_accumulate",
+    "rf_eval_finish",
+    "rf_eval_keep_rows",
+    "rf_env_view_get_statistics_device",
+    "rf_env_view_set_statistics_device",
     "rf_render_kernel_name",
     "rf_pixels_rendered",
     "rf_allocations_poisoned",
@@ -493,6 +498,11 @@ def load():
     lib.rf_params_init_workspace_size.restype = ctypes.c_ulonglong
     lib.rf_params_init_workspace_size.argtypes = [vp, vp, i32, i32]
     lib.rf_params_init.argtypes = [vp, vp, i32, i32, ctypes.c_uint, vp, vp, vp, vp, vp, vp]
+    lib.rf_eval_accumulate.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+    lib.rf_eval_finish.argtypes = [vp, i32, i32, i32, i32, ctypes.c_ulonglong, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.rf_eval_keep_rows.argtypes = [vp, i32, ctypes.c_uint, ctypes.c_uint, vp, vp, vp, vp]
+    lib.rf_env_view_get_statistics_device.argtypes = [vp, vp, vp]
+    lib.rf_env_view_set_statistics_device.argtypes = [vp, vp, vp]
     lib.rf_render_kernel_name.restype = ctypes.c_char_p
     lib.rf_render_kernel_name.argtypes = [vp]
     lib.rf_pixels_rendered.restype = ctypes.c_ulonglong
@@ -1048,6 +1058,41 @@ class Context:
         None.  Only enqueues."""
         rc = self._lib.rf_params_init(self._h, segments, count, groups, stride, params_ptr, gens_ptr, select_ptr,
                                       constants_ptr, workspace_ptr, stream)
+        if rc != 0:
+            _check(rc)
+
+    # --- evaluation (rf_eval_*; environments/evaluation.py): device pointers in, launches on `stream`, nothing waited for ----
+    def eval_accumulate(self, n, groups, m, episodes, final_return_ptr, final_length_ptr, counts_ptr, returns_ptr,
+                        lengths_ptr, stream):
+        """rf_eval_accumulate: the step's episode records into the tables int32 [n], float64 [n][K], int32 [n][K]."""
+        rc = self._lib.rf_eval_accumulate(self._h, n, groups, m, episodes, final_return_ptr, final_length_ptr, counts_ptr,
+                                          returns_ptr, lengths_ptr, stream)
+        if rc != 0:
+            _check(rc)
+
+    def eval_finish(self, n, groups, m, episodes, serial, counts_ptr, returns_ptr, lengths_ptr, results_ptr, best_mean_ptr,
+                    best_serial_ptr, improved_ptr, stream):
+        """rf_eval_finish: the rows float64 [groups][8] and the best rule (float64 [G], int64 [G], uint8 [G])."""
+        rc = self._lib.rf_eval_finish(self._h, n, groups, m, episodes, serial, counts_ptr, returns_ptr, lengths_ptr,
+                                      results_ptr, best_mean_ptr, best_serial_ptr, improved_ptr, stream)
+        if rc != 0:
+            _check(rc)
+
+    def eval_keep_rows(self, groups, words, stride, select_ptr, src_ptr, dst_ptr, stream):
+        """rf_eval_keep_rows: dst row g := src row g where select[g] != 0; rows of `words` 4-byte words, `stride` apart."""
+        rc = self._lib.rf_eval_keep_rows(self._h, groups, words, stride, select_ptr, src_ptr, dst_ptr, stream)
+        if rc != 0:
+            _check(rc)
+
+    def env_view_statistics_device(self, out_ptr, stream):
+        """rf_env_view_get_statistics_device: the view's moments into device float64 [G][3][W + 1] ([3][W + 1] ungrouped)."""
+        rc = self._lib.rf_env_view_get_statistics_device(self._h, out_ptr, stream)
+        if rc != 0:
+            _check(rc)
+
+    def env_view_set_statistics_device(self, in_ptr, stream):
+        """rf_env_view_set_statistics_device: the view's moments from device float64 [G][3][W + 1] ([3][W + 1] ungrouped)."""
+        rc = self._lib.rf_env_view_set_statistics_device(self._h, in_ptr, stream)
         if rc != 0:
             _check(rc)
 

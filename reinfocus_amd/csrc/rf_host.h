@@ -24,6 +24,9 @@
 //   rf_abi_param_init.hip  "parameter init": rf_params_init and rf_params_init_workspace_size -- param_fill_kernel and
 //                       param_orthogonal_kernel (rf_param_init.h), compiled apart from every unit above
 //                       (profiles/param_init.md)
+//   rf_abi_eval.hip     "evaluation": rf_eval_accumulate, rf_eval_finish, rf_eval_keep_rows -- the three kernels of
+//                       rf_eval.h -- and rf_env_view_get / set_statistics_device (eval_statistics_kernel), compiled apart
+//                       from every unit above (profiles/evaluation.md)
 //
 // Every kernel instantiation is defined in the unit that launches it (ppo_adam_kernel<true>, the last launch of the three
 // grouped updates, in three: each has its own copy; sde_noise_kernel<true> in two); the units share only host functions.
@@ -321,7 +324,7 @@ inline hipError_t host_malloc(void **p, size_t bytes)
     return e;
 }
 
-// ---- what the entry points over caller-owned device arrays share (rf_abi_env.hip, the two grouped recurrent units and rf_abi_param_init.hip) ------
+// ---- what the entry points over caller-owned device arrays share (rf_abi_env.hip, the two grouped recurrent units, rf_abi_param_init.hip and rf_abi_eval.hip) ------
 // check_device_array asks the runtime about one array (rf_abi_snapshot.hip and the device steps use it alone),
 // refuse_capturing about the caller's stream, ranges_overlap compares two address ranges; check_device_arrays is the
 // learner entry points' whole rule -- which arrays may alias and what a refusal says -- over the tables each of them keeps.

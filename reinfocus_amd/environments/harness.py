@@ -187,6 +187,14 @@ class LearnerView:
 MAX_VIEW_GROUPS = 65535  # RF_POPULATION_MAX_GROUPS
 
 
+def io_torch():
+    """torch, imported where a *_tensors method needs it (reinfocus_amd/torch_interop.py)."""
+    from reinfocus_amd import torch_interop
+
+    torch_interop.check_one_runtime()
+    return torch_interop._torch()
+
+
 def _checked_view(learner_view):
     if learner_view is not None and not isinstance(learner_view, LearnerView):
         raise TypeError(f"learner_view must be a harness.LearnerView or None, not {type(learner_view).__name__}")
@@ -419,6 +427,21 @@ class _ViewedTwin:
             return
         _checked_group(group, view.config.groups)
         view.set_statistics(statistics["mean"], statistics["var"], statistics["count"], group)
+
+    def view_statistics_tensor(self, out=None):
+        """The statistics as one float64 array [G, 3, W + 1] (mean, var, count; [3, W + 1] of an ungrouped view): what
+        the device classes keep as a tensor (rf_env_view_get_statistics_device).  out=: written in place."""
+        statistics = self.view_statistics()
+        stacked = np.stack([statistics[key] for key in ("mean", "var", "count")], axis=-2)
+        if out is None:
+            return stacked
+        out[...] = stacked
+        return out
+
+    def set_view_statistics_tensor(self, statistics):
+        statistics = np.asarray(statistics, dtype=np.float64)
+        mean, var, count = (statistics[..., row, :] for row in range(3))
+        self.set_view_statistics({"mean": mean, "var": var, "count": count})
 
     def set_view_training(self, training):
         """VecNormalize.training: False freezes the moments and the returns."""
@@ -1165,6 +1188,42 @@ class _DeviceVectorEnv(_VectorEnvBase):
             self._ctx.env_view_set_statistics(*arrays)
         else:
             self._ctx.env_view_set_statistics_grouped(*arrays)
+
+    def _statistics_shape(self):
+        groups, columns = self._the_view().groups, self._ctx._env_obs_width + 1
+        return (3, columns) if groups is None else (groups, 3, columns)
+
+    def _checked_statistics_tensor(self, tensor, what):
+        io = self._tensor_io()
+        torch = io_torch()
+        shape = self._statistics_shape()
+        if not isinstance(tensor, torch.Tensor):
+            raise TypeError(f"{what} must be a torch.Tensor on the environment's GPU, not {type(tensor).__name__}")
+        if tensor.dtype != torch.float64 or tuple(tensor.shape) != shape or not tensor.is_contiguous():
+            raise ValueError(f"{what} is {tensor.dtype} {tuple(tensor.shape)}, not contiguous torch.float64 {shape}")
+        io._on_device(tensor, what)
+        return io
+
+    def view_statistics_tensor(self, out=None):
+        """view_statistics() without the host: one torch.float64 tensor [G, 3, W + 1] (mean, var, count; [3, W + 1] of an
+        ungrouped view) on the environment's GPU (rf_env_view_get_statistics_device).  Stream-ordered after the steps
+        before it, never waits.  out=: written in place; otherwise a fresh tensor."""
+        self._the_view()
+        if out is None:
+            self._tensor_io()
+            torch = io_torch()
+            out = torch.empty(self._statistics_shape(), dtype=torch.float64,
+                              device=torch.device("cuda", self._ctx.device))
+        io = self._checked_statistics_tensor(out, "out")
+        self._ctx.env_view_statistics_device(out.data_ptr(), io._stream())
+        return out
+
+    def set_view_statistics_tensor(self, statistics):
+        """set_view_statistics() from such a tensor (rf_env_view_set_statistics_device): what sync_envs_normalization
+        does, training environment -> tensor -> evaluation environment, without crossing to the host."""
+        self._the_view()
+        io = self._checked_statistics_tensor(statistics, "statistics")
+        self._ctx.env_view_set_statistics_device(statistics.data_ptr(), io._stream())
 
     def set_view_training(self, training):
         """VecNormalize.training: False freezes the moments and the returns."""
@@ -2000,3 +2059,4 @@ from reinfocus_amd.environments.lstm import DeviceLstmPolicy, LstmPolicy, LstmPo
 from reinfocus_amd.environments.lstm_learner import DeviceLstmLearner, LstmLearner, lstm_gradient_numpy, lstm_update_numpy  # noqa: E402,F401 -- the recurrent PPO minibatch update
 from reinfocus_amd.environments.lstm_sde import DeviceLstmSdePolicy, LstmSdePolicy, LstmSdePolicySpec, lstm_sde_numpy  # noqa: E402,F401 -- its Gaussian (gSDE) head
 from reinfocus_amd.environments.param_init import init_numpy, segments  # noqa: E402,F401 -- the parameter initialisation (init_parameters of the policy classes)
+from reinfocus_amd.environments.evaluation import DeviceEvaluation, Evaluation  # noqa: E402,F401 -- per-group evaluation scores, the best parameters kept
